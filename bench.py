@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- Mpts/s of Pipeline.ingest -> finalize on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the roofline of
+the timed steps).  Everything else listed below -- per_glyph, e2e_host, cpu_baseline and the measured copy bandwidth on
+one GPU; selfcheck, unrouted, one_gpu_same_problem and native_exchange on several -- runs only with --full.
+--dump-outputs DIR writes the finalized bands of the last timed step as DIR/*.npy (see dump_outputs).
 
 N > 1 runs either way: under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (WORLD_SIZE set:
 this process is a rank), or as plain `python bench.py --gpus N ...` -- then this process only starts that launcher as a
@@ -13,7 +18,7 @@ scripts/benchmarks/benchmark_glyph_full.py:80-97).  Finalized bands stay in HBM
 (PipelineConfig.result_location = Device).  Rank 0 prints ONE JSON line.
 
 N = 1 (default): BASELINE.json configs[1] ("C2"): 50 M uniform points, 4096 x 4096 grid, Point glyph,
-Sum + Count + Average on one channel -- the headline `value`.  The same run also reports
+Sum + Count + Average on one channel -- the headline `value`.  With --full the same run also reports
   per_glyph     Point / Average alone (and with TWO ingests into one pipeline per step: the second ingest read-modify-writes
                 the state planes, the first stores into fresh ones), clustered = configs[3] (10 000 hotspots, Max + Min),
                 Line hl=16 / Gaussian sigma = 1, 4, 16 on the same 50 M points and grid (configs[2] settings;
@@ -305,13 +310,22 @@ def cpu_baseline(workload, G, sample_pts, seed, budget_s=14.0):
     return res
 
 
-def time_steps(pipes, cloud, warmup, world, backend, ingests=1):
-    """W untimed + K timed steps of ingest+finalize.  Returns (elapsed seconds MAX over ranks, per-kernel ms of the
-    dominant kernel over the TIMED steps, per-kernel ms of every kernel over the WARM-UP steps).
+TIMED_CHUNK = 128                 # at most this many pre-created pipelines in device memory at once
+
+
+def time_steps(make_pipe, cloud, steps, warmup, world, backend, ingests=1):
+    """W untimed + K timed steps of ingest+finalize, each on a fresh pipeline from make_pipe().  Returns (elapsed seconds
+    MAX over ranks, per-kernel ms of the dominant kernel over the TIMED steps, per-kernel ms of every kernel over the
+    WARM-UP steps, the pipeline of the last timed step).
 
     HIP events serialise the stream (~4 us per bracketed launch: 52 us on a 0.69 ms step with every kernel bracketed),
     so the timed steps bracket ONE kernel -- the dominant one, known from the fully bracketed warm-up steps -- and
-    otherwise run as they do in production."""
+    otherwise run as they do in production.
+
+    Every pipeline holds its state planes and bands from create on, so K pipelines do not fit in device memory for a
+    large K: the timed steps run in chunks of pipelines created before the chunk's clock starts and released after it
+    stops (as many per chunk as half the free memory holds, at most TIMED_CHUNK; the same count on every rank).  Only
+    the steps themselves are inside the clock."""
     def step(sp):
         for _ in range(ingests):
             sp.ingest(cloud)
@@ -326,8 +340,29 @@ def time_steps(pipes, cloud, warmup, world, backend, ingests=1):
                 k[1] += ms
         return kernels
 
+    cap = None
+
+    def new_chunk(count):
+        nonlocal cap
+        free0 = torch.cuda.mem_get_info()[0]
+        pipes = [make_pipe()]
+        if cap is None:
+            free1 = torch.cuda.mem_get_info()[0]
+            cap = max(1, min(TIMED_CHUNK, int(free1 * 0.5 // max(free0 - free1, 1)) + 1))
+            if world > 1:
+                t = torch.tensor([cap], dtype=torch.int64, device="cuda" if backend == "nccl" else "cpu")
+                dist.all_reduce(t, op=dist.ReduceOp.MIN)
+                cap = int(t.item())
+        return pipes + [make_pipe() for _ in range(min(count, cap) - 1)]
+
+    # The warm-up pipelines and the first chunk (with W + K <= its size: every pipeline) are created before the warm-up,
+    # so that the warm-up steps run back to back and the clock starts right after the last of them, with nothing
+    # allocated or released in between; the warm-up pipelines live until the first chunk is timed.
+    first = new_chunk(warmup + steps)
+    held, pipes = first[:warmup], first[warmup:] or new_chunk(steps)
+    del first
     tables = []
-    for sp in pipes[:warmup]:
+    for sp in held:
         sp.pipe.profile_enable(True)
         step(sp)
         tables.append(drain([sp]))
@@ -342,23 +377,70 @@ def time_steps(pipes, cloud, warmup, world, backend, ingests=1):
             k[1] += ms / len(use)
     dom = max(warm, key=lambda k: warm[k][1]) if warm else ""
     on = os.environ.get("PCR_BENCH_NO_PROFILE") != "1"
-    for sp in pipes[warmup:]:
-        sp.pipe.profile_enable(on, dom)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for sp in pipes[warmup:]:
-        step(sp)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed, kernels, done = 0.0, {}, 0
+    while True:
+        for sp in pipes:
+            sp.pipe.profile_enable(on, dom)
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for sp in pipes:
+            step(sp)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        elapsed += time.perf_counter() - t0
+        for name, (launches, ms) in drain(pipes).items():
+            k = kernels.setdefault(name, [0, 0.0])
+            k[0] += launches
+            k[1] += ms
+        done += len(pipes)
+        if done >= steps:
+            break
+        pipes = held = None                          # the previous chunk's memory goes before this chunk's is taken
+        pipes = new_chunk(steps - done)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    return elapsed, drain(pipes[warmup:]), warm
+    return elapsed, kernels, warm, pipes[-1]
+
+
+DUMP_BYTES = 48 << 20             # --dump-outputs: all files together stay below this (plus their .npy headers)
+DUMP_SEED = 20240601              # the sampled cells depend only on this seed and the band's shape
+
+
+def dump_outputs(sp, directory, rank, world):
+    """--dump-outputs: the finalized bands of the last timed step -- what the caller of ingest -> finalize receives -- as
+    float32 .npy files (rank<r>_ in front of every name for each rank's strip when N > 1):
+      band<b>_<name>.npy        the band's values, 0 in the cells that hold none
+      band<b>_<name>_valid.npy  1 where the band holds a value, 0 where it holds no data (NaN: an empty cell of every
+                                reduction but Sum) -- so that every file is finite and a change in the empty cells shows
+    A band larger than its share of DUMP_BYTES is written as a fixed, seeded sample of its cells (sorted flat indices
+    into the row-major strip, the same cells for every band), so two builds run with the same arguments dump the same
+    cells."""
+    res = sp.pipe.result()
+    nb, W = res.num_bands(), sp.width
+    rows = sp.own[1] - sp.own[0]
+    cells = rows * W
+    k = min(cells, DUMP_BYTES // (2 * 4 * nb * world))       # two float32 files per band
+    idx = None if k == cells else np.sort(np.random.default_rng(DUMP_SEED).choice(cells, k, replace=False))
+    on_device = res.location() == pcr.MemoryLocation.Device
+    os.makedirs(directory, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for b in range(nb):
+        if on_device:
+            view = pcr.DeviceArrayView(sp.pipe.result_band_device_ptr(b), (rows, W), "<f4", owner=sp.pipe)
+            band = torch.as_tensor(view, device="cuda").cpu().numpy()
+        else:
+            band = np.array(res.band_array(b))
+        band = np.ascontiguousarray(band, dtype=np.float32)
+        out = band if idx is None else band.reshape(-1)[idx]
+        name = "".join(c if c.isalnum() or c in "-_" else "_" for c in res.band_desc(b).name)
+        valid = np.isfinite(out)
+        np.save(os.path.join(directory, f"{prefix}band{b}_{name}.npy"), np.where(valid, out, np.float32(0)))
+        np.save(os.path.join(directory, f"{prefix}band{b}_{name}_valid.npy"), valid.astype(np.float32))
 
 
 def measured_copy_gbs():
@@ -466,7 +548,15 @@ def main():
                          "untimed, and compared bit for bit (native_exchange in the line)")
     ap.add_argument("--native-check-limit", type=float, default=120.0,
                     help="seconds the untimed native-vs-torch exchange check may take before the line is printed without it")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline: measured copy bandwidth, per_glyph / e2e_host legs, CPU "
+                         "baseline; N > 1: selfcheck, unrouted, one_gpu_same_problem, native_exchange")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the finalized bands of the last timed step to DIR/*.npy (float32, finite: values with 0 "
+                         "for no data plus a _valid mask per band; a fixed, seeded sample of the cells beyond 48 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the driver's form: plain `python bench.py --gpus N`.  Decided before torch / pcr are imported.
@@ -530,22 +620,25 @@ def main():
                                      y_hi - (2.0 if rank == 0 else 0.0), seed=42 + rank)
     else:
         x, y, v, ch = make_points(workload, n, G, y_lo, y_hi, seed=42 + rank)
-        if WORKLOADS[workload][1] != "line" and not args.no_extras and world == 1:
+        if WORKLOADS[workload][1] != "line" and args.full and not args.no_extras and world == 1:
             ch = dict(ch, direction=np.random.default_rng(4242).uniform(0, np.pi, n).astype(np.float32))   # per_glyph line16
         host_cloud = make_cloud(x, y, v, ch)
         cloud = host_cloud if args.host_cloud else host_cloud.to_device()
         del x, y, v, ch
 
-    def run(wl, steps, warmup, the_cloud=None, cfg_edit=None, ingests=1):
+    def run(wl, steps, warmup, the_cloud=None, cfg_edit=None, ingests=1, dump_dir=None):
         cfg = make_cfg(wl)
         if cfg_edit:
             cfg_edit(cfg)
-        pipes = [ShardedPipeline(cfg, rank, world, device_id=local_rank, comm=args.comm if world > 1 else "torch")
-                 for _ in range(warmup + steps)]
-        elapsed, kernels, warm = time_steps(pipes, the_cloud if the_cloud is not None else cloud, warmup, world, args.backend,
-                                            ingests)
-        info = pipes[-1].pipe.last_scatter()
-        sp = pipes[-1]
+
+        def make_pipe():
+            return ShardedPipeline(cfg, rank, world, device_id=local_rank, comm=args.comm if world > 1 else "torch")
+
+        elapsed, kernels, warm, sp = time_steps(make_pipe, the_cloud if the_cloud is not None else cloud, steps, warmup,
+                                                world, args.backend, ingests)
+        info = sp.pipe.last_scatter()
+        if dump_dir:
+            dump_outputs(sp, dump_dir, rank, world)
         extra = {"halo_rows": sp.halo, "tiles_local": sp.tiles_local, "comm": sp.comm_kind if world > 1 else None,
                  "collectives_per_step": dict(zip(("p2p_messages", "all_reduces"), sp.collectives_per_step())),
                  "halo_bytes_sent_per_step": sp.halo_bytes_per_step()}
@@ -569,7 +662,7 @@ def main():
                 extra["lds_plane_updates_per_s"] = visits * nplanes / (ms_line * 1e-3)
             except Exception as exc:
                 extra["lds_atomic_lane_ops_per_s"] = repr(exc)
-        del pipes
+        del sp
         return elapsed, kernels, info, cfg, extra
 
     def selfcheck():
@@ -788,10 +881,10 @@ def main():
     except (OSError, ValueError):
         pass
 
-    elapsed, kernels, info, cfg, extra = run(workload, args.steps, args.warmup)
+    elapsed, kernels, info, cfg, extra = run(workload, args.steps, args.warmup, dump_dir=args.dump_outputs)
     warm_table = extra.pop("_warm")
     check = None
-    if strong and not args.no_selfcheck:
+    if strong and args.full and not args.no_selfcheck:
         try:
             check = selfcheck()
         except Exception as exc:                                      # a broken check must be visible, not fatal to the line
@@ -836,7 +929,7 @@ def main():
             out["step_roofline"] = {"algorithmic_bytes": step_bytes,
                                     "achieved": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 2), "unit": "GB/s",
                                     "frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}
-            if world == 1 and not args.same_device:
+            if args.full and world == 1 and not args.same_device:
                 try:
                     rates = measured_copy_gbs()
                     copy = max(rates["float4_kernel"], rates["float4_kernel_nt"])
@@ -849,7 +942,7 @@ def main():
                     roof["measured_copy_GBps"] = repr(exc)
 
     # ---- the rest of the metric, same run ---------------------------------------------------------
-    if not args.no_extras and args.workload is None and not args.host_cloud and not args.host_result:
+    if args.full and not args.no_extras and args.workload is None and not args.host_cloud and not args.host_result:
         k_extra, w_extra = max(3, min(args.steps, 5)), 2
         per_glyph = {}
         legs = [(wl, 1) for wl in (PER_GLYPH if world == 1 else (("C5_gauss1",) if strong else ()))]
@@ -939,7 +1032,7 @@ def main():
                 if rank == 0:
                     out["unrouted"] = {"error": repr(exc)}
 
-    if strong and not args.no_extras and args.workload is None:
+    if strong and args.full and not args.no_extras and args.workload is None:
         # the SAME problem on ONE GPU (rank 0 alone, the other ranks wait): the denominator of "x-fold at N GPUs on the
         # 16384^2 grid".  The driver's own N = 1 run measures C2 (4096^2), which is a different problem.
         one = None
@@ -975,7 +1068,7 @@ def main():
 
     # ---- N > 1 over RCCL: the transport that was NOT timed runs the same Gaussian round once and must agree bit for bit
     hard_exit = False
-    if strong and world > 1 and not args.no_selfcheck and (args.backend == "nccl" or args.comm == "native"):
+    if strong and world > 1 and args.full and not args.no_selfcheck and (args.backend == "nccl" or args.comm == "native"):
         import threading
         lock = threading.Lock()
         state = {"printed": False}
@@ -1021,7 +1114,7 @@ def main():
             if glyph == "gauss":
                 sigma = WORKLOADS[workload][2]
                 sample = max(200_000, int(1e9 / (2 * min(3 * sigma, 64) + 1) ** 2 / 4))
-        if world == 1 and sample > 0:
+        if args.full and world == 1 and sample > 0:
             out["cpu_baseline"] = cpu_baseline(workload, G, min(sample, n), seed=42)
         print(json.dumps(out), flush=True)
 

@@ -5,6 +5,8 @@ accumulate_glyph() (src/engine/glyph_kernels.cu:571-604) or Accumulator::accumul
 (src/engine/accumulator.cpp:33-59) on a batch whose points all have their centre cell in
 the tile [col0, col0+tw) x [row0, row0+th) of the grid.
 """
+import hashlib
+
 import numpy as np
 
 SUM, MAX, MIN, AVERAGE, WEIGHTED_AVERAGE, COUNT = 0, 1, 2, 3, 4, 5
@@ -91,3 +93,45 @@ def point_inputs(case):
     ci[ci % 13 == 0] = 1
     v = rng.normal(0.0, 100.0, n).astype(np.float32)
     return ci, v
+
+
+def random_glyph_case(seed):
+    """A random accumulate_glyph() call: grid origin / cell sizes / tile rectangle, glyph type and parameters, per-point channels
+    (with the values the reference special-cases: sigma <= 0, directions on the axes), every reduction a glyph takes."""
+    rng = np.random.default_rng(90000 + seed)
+    W, H = int(rng.integers(24, 120)), int(rng.integers(24, 120))
+    csx = float(rng.choice([0.25, 0.5, 1.0, 2.0, 3.0]))
+    csy = -float(rng.choice([0.25, 0.5, 1.0, 2.0, 3.0]))
+    x0, y1 = float(rng.choice([0.0, 100.0, -512.5, 1e5])), float(rng.choice([0.0, -50.0, 777.25, 1e5]))
+    grid = dict(bounds=(x0, y1 + H * csy, x0 + W * csx, y1), cell=(csx, csy), dims=(W, H))
+    if rng.uniform() < 0.5:
+        tile = dict(col0=0, row0=0, tw=W, th=H)
+    else:                                                     # an interior tile: footprints are clipped to it (Q4)
+        tw, th = int(rng.integers(8, W)), int(rng.integers(8, H))
+        tile = dict(col0=int(rng.integers(0, W - tw + 1)), row0=int(rng.integers(0, H - th + 1)), tw=tw, th=th)
+    case = dict(name=f"random_{seed}", grid=grid, tile=tile, n=int(rng.integers(50, 1500)), seed=int(rng.integers(1, 1 << 30)),
+                max_radius=float(rng.choice([2.0, 4.0, 7.5, 12.0, 32.0])))
+    if rng.uniform() < 0.5:
+        case["glyph"] = GAUSSIAN
+        case["rtype"] = int(rng.choice([SUM, AVERAGE, WEIGHTED_AVERAGE, COUNT, MAX, MIN]))
+        case["sigma"] = (float(rng.uniform(0.3, 4.0)) * csx, float(rng.uniform(0.3, 4.0)) * abs(csy))
+        case["rotation"] = float(rng.choice([0.0, 0.0, rng.uniform(-3.2, 3.2)]))
+        names = [c for c in ("sigma_x", "sigma_y", "rotation") if rng.uniform() < 0.3]
+    else:
+        case["glyph"] = LINE
+        case["rtype"] = int(rng.choice([SUM, WEIGHTED_AVERAGE, COUNT, AVERAGE, MAX, MIN]))
+        case["half_length"] = float(rng.uniform(0.3, 14.0)) * csx * float(rng.choice([1.0, 1.0, -1.0]))
+        case["direction"] = float(rng.uniform(-7.0, 7.0))
+        names = [c for c in ("direction", "half_length") if rng.uniform() < 0.5]
+        case["axis_dirs"] = bool(rng.uniform() < 0.2)
+    if names:
+        case["channels"] = tuple(names)
+    return case
+
+
+def digest(a):
+    """sha256 of an array's float32 bits with every NaN made the same NaN: equal digests <=> same NaN mask and the same
+    bits everywhere else (the comparison of tests/test_oracle_vs_ref.py::_same, for outputs recorded as digests)."""
+    a = np.array(a, dtype=np.float32).reshape(-1)
+    a[np.isnan(a)] = np.float32("nan")
+    return hashlib.sha256(a.view(np.uint32).tobytes()).hexdigest()

@@ -35,7 +35,7 @@ def _run(extra, launcher=True, ranks=2, extra_env=None):
 
 
 def test_default_multi_gpu_bench_is_c5_strong_scaling_with_live_exchange():
-    r = _run(["--grid", "6144", "--points", "3000000", "--unrouted"])      # 2 x 3072 rows: cuts the 4096-row tiles
+    r = _run(["--grid", "6144", "--points", "3000000", "--unrouted", "--full"])      # 2 x 3072 rows: cuts the 4096-row tiles
     assert r["n_gpus"] == 2 and r["scaling"] == "strong"
     c = r["config"]
     assert c["workload"].startswith("C5_point") and c["grid"] == "6144x6144" and c["rows_per_gpu"] == 3072
@@ -66,7 +66,7 @@ def _check_selfcheck(r, ranks=2):
 
 def test_plain_python_bench_gpus_2_launches_its_own_ranks_and_checks_the_exchange():
     """`python bench.py --gpus 2 ...` with no launcher around it (the driver's form)."""
-    r = _run(["--grid", "6144", "--points", "3000000"], launcher=False)
+    r = _run(["--grid", "6144", "--points", "3000000", "--full"], launcher=False)
     assert r["n_gpus"] == 2 and r["scaling"] == "strong" and r["value"] > 0
     _check_selfcheck(r)
 
@@ -83,7 +83,7 @@ def test_the_eight_rank_geometry_with_the_four_ranks_a_one_gpu_box_admits():
     is still going away counts too, so the same blocks are instantiated as FOUR ranks on a 16384 x 8192 grid (blocks 0|1 and
     2|3 share a tile row and exchange; 1|2 meet on a tile boundary -- exactly the alternation the 8-rank run has; ranks 1 and
     2 have two neighbours), through the driver's launcher path: the run must validate itself."""
-    r = _run(["--grid", "16384", "--height", "8192", "--points", "1500000"], launcher=False, ranks=4)
+    r = _run(["--grid", "16384", "--height", "8192", "--points", "1500000", "--full"], launcher=False, ranks=4)
     assert r["n_gpus"] == 4 and r["scaling"] == "strong"
     c = r["config"]
     assert c["grid"] == "16384x8192" and c["rows_per_gpu"] == 2048 and c["tiles_local"] is False
@@ -107,7 +107,7 @@ def test_bench_times_the_native_exchange_and_compares_the_two_transports_on_the_
     fake = str(tmp_path / "libfake_rccl.so")
     subprocess.run([gxx, "-std=c++17", "-O1", "-shared", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
                     os.path.join(ROOT, "tests", "native", "fake_rccl.cpp"), "-o", fake, "-L/opt/rocm/lib", "-lamdhip64"], check=True)
-    r = _run(["--grid", "6144", "--points", "2000000", "--comm", "native"], ranks=3,
+    r = _run(["--grid", "6144", "--points", "2000000", "--comm", "native", "--full"], ranks=3,
              extra_env=dict(PCR_HIP_RCCL=fake, PCR_FAKE_RCCL_DIR=str(tmp_path)))
     assert r["n_gpus"] == 3 and r["config"]["rows_per_gpu"] == 2048 and r["config"]["tiles_local"] is False
     sc = r["selfcheck"]

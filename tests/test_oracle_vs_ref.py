@@ -2,12 +2,12 @@
 
  * test_*_fixture: against tests/golden/ref_vectors.npz (outputs of oracle/_ref, committed);
    runs everywhere, including the GPU box where /root/reference does not exist.
- * test_*_live: against oracle/_ref/libpcr_ref.so when it was built (development container).
+ * test_*_live: against oracle/_ref/libpcr_ref.so when it was built (development container), and against
+   its outputs recorded in tests/golden/ref_live.npz (make_ref_live.py) everywhere else.
 
 Both sides fold points sequentially in input order with the same fp32 operations, so the
 comparison is BIT-EXACT on the raw tile state and on the finalized tile.
 """
-import ctypes as C
 import os
 import sys
 
@@ -19,6 +19,7 @@ import pcr_oracle_py as O
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 import cases                      # noqa: E402
 import make_ref_vectors as MRV    # noqa: E402
+import make_ref_live as MRL       # noqa: E402
 
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_vectors.npz")
 
@@ -37,6 +38,11 @@ def _same(a, b, what):
 @pytest.fixture(scope="module")
 def fixture_vectors():
     return np.load(FIX)
+
+
+@pytest.fixture(scope="module")
+def live_vectors():
+    return np.load(MRL.PATH)
 
 
 @pytest.mark.parametrize("case", cases.GLYPH_CASES, ids=lambda c: c["name"])
@@ -60,116 +66,84 @@ def test_point_fixture(case, fixture_vectors):
         assert np.isnan(fin).any(), "case should contain empty cells"
 
 
-@pytest.mark.skipif(O.ref_lib() is None, reason="oracle/_ref not built (reference tree absent)")
 def test_live_ref_matches_fixture_and_oracle():
     R, L = O.ref_lib(), O.lib()
     fx = np.load(FIX)
     for case in cases.GLYPH_CASES:
-        st_r, fin_r = MRV.run_glyph(R.pcr_ref_accumulate_glyph, R.pcr_ref_init_state,
-                                    R.pcr_ref_finalize_state, case)
         st_o, fin_o = MRV.run_glyph(L.pcro_accumulate_glyph, L.pcro_init_state,
                                     L.pcro_finalize_state, case)
+        if R is None:
+            st_r, fin_r = fx[case["name"] + "/state"], fx[case["name"] + "/final"]
+        else:
+            st_r, fin_r = MRV.run_glyph(R.pcr_ref_accumulate_glyph, R.pcr_ref_init_state,
+                                        R.pcr_ref_finalize_state, case)
         _same(st_o, st_r, case["name"])
         _same(fin_o, fin_r, case["name"])
         _same(st_r, fx[case["name"] + "/state"], case["name"] + " (fixture stale?)")
     for case in cases.POINT_CASES:
-        st_r, fin_r = MRV.run_point(R.pcr_ref_accumulate, R.pcr_ref_init_state, R.pcr_ref_finalize_state, case)
         st_o, fin_o = MRV.run_point(L.pcro_accumulate, L.pcro_init_state, L.pcro_finalize_state, case)
+        if R is None:
+            st_r, fin_r = fx[case["name"] + "/state"], fx[case["name"] + "/final"]
+        else:
+            st_r, fin_r = MRV.run_point(R.pcr_ref_accumulate, R.pcr_ref_init_state, R.pcr_ref_finalize_state, case)
         _same(st_o, st_r, case["name"])
         _same(fin_o, fin_r, case["name"])
 
 
-@pytest.mark.skipif(O.ref_lib() is None, reason="oracle/_ref not built (reference tree absent)")
-def test_live_ref_merge_state():
+def test_live_ref_merge_state(live_vectors):
     R, L = O.ref_lib(), O.lib()
-    rng = np.random.default_rng(3)
-    for rt in range(6):
-        k = L.pcro_state_floats(rt)
-        a = rng.normal(size=k * 64).astype(np.float32)
-        b = rng.normal(size=k * 64).astype(np.float32)
+    for rt, a, b in MRL.merge_inputs(L):
         a2 = a.copy()
-        assert R.pcr_ref_merge_state(rt, a.ctypes.data, b.ctypes.data, 64) == 0
+        if R is None:
+            a = live_vectors[f"merge/{rt}"]
+        else:
+            assert R.pcr_ref_merge_state(rt, a.ctypes.data, b.ctypes.data, 64) == 0
+            _same(a, live_vectors[f"merge/{rt}"], f"merge {rt} (fixture stale?)")
         assert L.pcro_merge_state(rt, a2.ctypes.data, b.ctypes.data, 64) == 0
         _same(a, a2, f"merge {rt}")
 
 
-@pytest.mark.skipif(O.ref_lib() is None, reason="oracle/_ref not built (reference tree absent)")
-def test_live_ref_glyph_quirk_probes(known_answers):
-    """The survey-verified glyph probes, re-checked against the reference code itself."""
-    R = O.ref_lib()
-    for c in known_answers["glyph"]:
-        gj, s = c["grid"], c["spec"]
-        if gj["tile"][0] < gj["dims"][0]:
-            continue   # tile clipping needs the router; covered at state level by *_clip cases
-        grid = O.make_grid(tuple(gj["bounds"]), cell=tuple(gj["cell"]), dims=tuple(gj["dims"]))
-        rt = {"Sum": O.SUM, "Count": O.COUNT, "WeightedAverage": O.WEIGHTED_AVERAGE}[s["type"]]
-        if s["glyph"] == "Gaussian":
-            gl = O.make_glyph(O.GLYPH_GAUSSIAN, sigma_x=s["sigma"], sigma_y=s["sigma"], max_radius=s["max_radius"])
+def test_live_ref_glyph_quirk_probes(known_answers, live_vectors):
+    """The survey-verified glyph probes, re-checked against the reference code itself (without oracle/_ref: against what it
+    returned, recorded, which the oracle must reproduce bit for bit)."""
+    R, L = O.ref_lib(), O.lib()
+    for i, c in enumerate(known_answers["glyph"]):
+        if R is None:
+            band = MRL.probe_band(L.pcro_accumulate_glyph, c)
+            if band is None:
+                continue   # tile clipping needs the router; covered at state level by *_clip cases
+            _same(band, live_vectors[f"probe/{i}"], f"probe case {i}: oracle vs recorded reference")
         else:
-            gl = O.make_glyph(O.GLYPH_LINE, direction=s["direction"], half_length=s["half_length"],
-                              max_radius=s["max_radius"])
-        pts, keep = O.make_points(c["x"], c["y"], c["value"])
-        cells = grid.width * grid.height
-        st = np.zeros(cells, dtype=np.float32)
-        assert R.pcr_ref_accumulate_glyph(C.byref(gl), rt, C.byref(pts), st.ctypes.data, cells,
-                                          C.byref(grid), 0, 0, grid.width, grid.height) == 0
-        band = st.reshape(grid.height, grid.width)
+            band = MRL.probe_band(R.pcr_ref_accumulate_glyph, c)
+            if band is None:
+                continue
+            _same(band, live_vectors[f"probe/{i}"], f"probe case {i} (fixture stale?)")
         for row, col, val in c.get("probes", []):
             assert band[row, col] == pytest.approx(val, rel=c["rtol"])
         if "cells_set" in c:
             assert sorted([int(r), int(cc)] for r, cc in np.argwhere(band != 0)) == sorted(c["cells_set"])
 
 
-def _random_glyph_case(seed):
-    """A random accumulate_glyph() call: grid origin / cell sizes / tile rectangle, glyph type and parameters, per-point channels
-    (with the values the reference special-cases: sigma <= 0, directions on the axes), every reduction a glyph takes."""
-    rng = np.random.default_rng(90000 + seed)
-    W, H = int(rng.integers(24, 120)), int(rng.integers(24, 120))
-    csx = float(rng.choice([0.25, 0.5, 1.0, 2.0, 3.0]))
-    csy = -float(rng.choice([0.25, 0.5, 1.0, 2.0, 3.0]))
-    x0, y1 = float(rng.choice([0.0, 100.0, -512.5, 1e5])), float(rng.choice([0.0, -50.0, 777.25, 1e5]))
-    grid = dict(bounds=(x0, y1 + H * csy, x0 + W * csx, y1), cell=(csx, csy), dims=(W, H))
-    if rng.uniform() < 0.5:
-        tile = dict(col0=0, row0=0, tw=W, th=H)
-    else:                                                     # an interior tile: footprints are clipped to it (Q4)
-        tw, th = int(rng.integers(8, W)), int(rng.integers(8, H))
-        tile = dict(col0=int(rng.integers(0, W - tw + 1)), row0=int(rng.integers(0, H - th + 1)), tw=tw, th=th)
-    case = dict(name=f"random_{seed}", grid=grid, tile=tile, n=int(rng.integers(50, 1500)), seed=int(rng.integers(1, 1 << 30)),
-                max_radius=float(rng.choice([2.0, 4.0, 7.5, 12.0, 32.0])))
-    if rng.uniform() < 0.5:
-        case["glyph"] = cases.GAUSSIAN
-        case["rtype"] = int(rng.choice([cases.SUM, cases.AVERAGE, cases.WEIGHTED_AVERAGE, cases.COUNT, cases.MAX, cases.MIN]))
-        case["sigma"] = (float(rng.uniform(0.3, 4.0)) * csx, float(rng.uniform(0.3, 4.0)) * abs(csy))
-        case["rotation"] = float(rng.choice([0.0, 0.0, rng.uniform(-3.2, 3.2)]))
-        names = [c for c in ("sigma_x", "sigma_y", "rotation") if rng.uniform() < 0.3]
-    else:
-        case["glyph"] = cases.LINE
-        case["rtype"] = int(rng.choice([cases.SUM, cases.WEIGHTED_AVERAGE, cases.COUNT, cases.AVERAGE, cases.MAX, cases.MIN]))
-        case["half_length"] = float(rng.uniform(0.3, 14.0)) * csx * float(rng.choice([1.0, 1.0, -1.0]))
-        case["direction"] = float(rng.uniform(-7.0, 7.0))
-        names = [c for c in ("direction", "half_length") if rng.uniform() < 0.5]
-        case["axis_dirs"] = bool(rng.uniform() < 0.2)
-    if names:
-        case["channels"] = tuple(names)
-    return case
-
-
-@pytest.mark.skipif(O.ref_lib() is None, reason="oracle/_ref not built (reference tree absent)")
 @pytest.mark.parametrize("block", range(8))
-def test_live_ref_matches_oracle_on_random_glyph_cases(block):
-    """320 random accumulate_glyph() calls, the C restatement against the reference's own code: raw tile state and finalized
-    tile bit for bit (both fold the points in input order with the same fp32 operations) for the 206 the reference accepts;
-    the 114 it refuses (Max / Min through a glyph) the restatement refuses too."""
+def test_live_ref_matches_oracle_on_random_glyph_cases(block, live_vectors):
+    """320 random accumulate_glyph() calls, the C restatement against the reference's own code (without oracle/_ref: against
+    the digests of what it returned, tests/golden/ref_live.npz): raw tile state and finalized tile bit for bit (both fold the
+    points in input order with the same fp32 operations) for the 206 the reference accepts; the 114 it refuses (Max / Min
+    through a glyph) the restatement refuses too."""
     R, L = O.ref_lib(), O.lib()
     for seed in range(block * 40, block * 40 + 40):
-        case = _random_glyph_case(seed)
-        try:
-            st_r, fin_r = MRV.run_glyph(R.pcr_ref_accumulate_glyph, R.pcr_ref_init_state, R.pcr_ref_finalize_state, case)
-        except AssertionError:
+        case = cases.random_glyph_case(seed)
+        recorded = tuple(str(s) for s in live_vectors[f"random/{seed}"])
+        if R is not None:
+            assert MRL.random_case_record(R, case) == recorded, f"{case['name']} (fixture stale?)"
+        if recorded == ("refused",):
             # the reference refuses the combination (e.g. a reduction its glyph path does not take): the oracle must too
             with pytest.raises(AssertionError):
                 MRV.run_glyph(L.pcro_accumulate_glyph, L.pcro_init_state, L.pcro_finalize_state, case)
             continue
         st_o, fin_o = MRV.run_glyph(L.pcro_accumulate_glyph, L.pcro_init_state, L.pcro_finalize_state, case)
-        _same(st_o, st_r, f"{case['name']} state ({case})")
-        _same(fin_o, fin_r, f"{case['name']} final ({case})")
+        if R is not None:
+            st_r, fin_r = MRV.run_glyph(R.pcr_ref_accumulate_glyph, R.pcr_ref_init_state, R.pcr_ref_finalize_state, case)
+            _same(st_o, st_r, f"{case['name']} state ({case})")
+            _same(fin_o, fin_r, f"{case['name']} final ({case})")
+        assert (cases.digest(st_o), cases.digest(fin_o)) == recorded, f"{case['name']} vs recorded reference ({case})"

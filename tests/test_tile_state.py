@@ -14,6 +14,7 @@ from conftest import GOLDEN, assert_band_close
 
 sys.path.insert(0, GOLDEN)
 from make_ref_tile_state import fixture_state   # noqa: E402
+import make_ref_live as MRL                     # noqa: E402
 
 FIXTURE = os.path.join(GOLDEN, "ref_tile_0001_0002.pcrt")     # written by the reference's own writer
 
@@ -55,25 +56,29 @@ def test_filename_and_errors(tmp_path):
         pcr.read_tile_state(str(tmp_path / "v2.pcrt"))
 
 
-@pytest.mark.skipif(O.ref_lib() is None, reason="oracle/_ref not built (reference tree absent)")
 def test_live_reference_round_trips(tmp_path):
+    """Our file is the reference's, byte for byte, and the reference reads it back; the same file name.  Against the
+    reference's own code when oracle/_ref was built, else against what it returned, recorded (tests/golden/ref_live.npz)."""
     R = O.ref_lib()
-    R.pcr_ref_write_tile_state.argtypes = [C.c_char_p] + [C.c_int] * 6 + [C.c_void_p]
-    R.pcr_ref_read_tile_state.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 6 + [C.c_void_p]
-    rng = np.random.default_rng(2)
-    st = rng.normal(size=(1, 7, 9)).astype(np.float32)
+    fx = np.load(MRL.PATH)
+    st = MRL.tile_state_inputs()
     mine = str(tmp_path / "mine.pcrt")
     pcr.write_tile_state(mine, 4, 5, st, pcr.ReductionType.Max)
-    v = [C.c_int(0) for _ in range(6)]
-    out = np.zeros_like(st)
-    assert R.pcr_ref_read_tile_state(mine.encode(), *[C.byref(a) for a in v], out.ctypes.data) == 0
-    assert [a.value for a in v] == [4, 5, 9, 7, 1, 1] and np.array_equal(out, st)      # the reference reads ours
-    theirs = str(tmp_path / "theirs.pcrt")
-    assert R.pcr_ref_write_tile_state(theirs.encode(), 4, 5, 9, 7, 1, 1, st.ctypes.data) == 0
-    assert open(theirs, "rb").read() == open(mine, "rb").read()                       # and writes the same bytes
-    buf = C.create_string_buffer(256)
-    R.pcr_ref_tile_state_filename(b"/a/b", 12, 345, buf, 256)
-    assert buf.value.decode() == pcr.tile_state_filename("/a/b", 12, 345)
+    if R is None:
+        theirs, header, out, name = (fx["tile_state/bytes"].tobytes(), fx["tile_state/read_header"].tolist(),
+                                     fx["tile_state/read_data"], str(fx["tile_state/filename"]))
+    else:
+        R.pcr_ref_read_tile_state.argtypes = [C.c_char_p] + [C.POINTER(C.c_int)] * 6 + [C.c_void_p]
+        v = [C.c_int(0) for _ in range(6)]
+        out = np.zeros_like(st)
+        assert R.pcr_ref_read_tile_state(mine.encode(), *[C.byref(a) for a in v], out.ctypes.data) == 0
+        header = [a.value for a in v]
+        theirs = MRL.ref_tile_state(R, str(tmp_path))[0]
+        name = MRL.ref_tile_name(R)
+        assert theirs == fx["tile_state/bytes"].tobytes() and name == str(fx["tile_state/filename"]), "fixture stale?"
+    assert header == [4, 5, 9, 7, 1, 1] and np.array_equal(out, st)                   # the reference reads ours
+    assert theirs == open(mine, "rb").read()                                          # and writes the same bytes
+    assert name == pcr.tile_state_filename(*MRL.TILE_NAME_ARGS)
 
 
 def _cfg(reductions, state_dir="", resume=False, tile=5, G=10):
