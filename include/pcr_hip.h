@@ -32,7 +32,8 @@ extern "C" {
 
 #define PCR_HIP_ABI_VERSION 5   /* 3 (round 4): + comm_halo_plan / comm_agree_max_i32 / signed_max_f32_masked / copy_kernel; planes_fresh takes 0, 1, 2;
                                  * 4: + engine_finalize_with_scatter / engine_finalize_taken / finalize_group_unless / touched_union;
-                                 * 5 (round 5): + comm_alltoall_counts / comm_alltoallv / comm_gatherv / comm_xfer_plan / touched_union_owned; halo_reduce resets the sent apron rows */
+                                 * 5 (round 5): + comm_alltoall_counts / comm_alltoallv / comm_gatherv / comm_xfer_plan / touched_union_owned; halo_reduce resets the sent apron rows;
+                                 *   later, additive (same version): + crs_from_epsg / transform_xy / transform_xy_host */
 
 typedef enum pcr_hip_status {
     PCR_HIP_OK = 0,
@@ -402,6 +403,38 @@ int pcr_hip_scatter_point(pcr_hip_engine* e, uint32_t plane_mask, const pcr_hip_
 int pcr_hip_scatter_glyph(pcr_hip_engine* e, const pcr_hip_glyph* glyph, uint32_t plane_mask,
                           const pcr_hip_planes* planes,
                           const double* d_x, const double* d_y, const float* d_value, uint64_t n);
+
+/* ---- coordinate reprojection.  No reference counterpart: PipelineConfig::target_crs / auto_reproject are declared there
+ *      (include/pcr/engine/pipeline.h:55-56) and src/engine/reprojection.cpp is a TODO.  No PROJ: a fixed set of EPSG codes
+ *      resolves to a descriptor, and every transform goes source -> geographic -> destination.
+ *        geographic   4326 (WGS 84), 4269 (NAD83), 4258 (ETRS89): x = longitude, y = latitude, degrees
+ *        web mercator 3857 (spherical formulas on a = 6378137)
+ *        UTM          32601-32660 / 32701-32760 (WGS 84, north / south), 26901-26923 (NAD83), 25828-25838 (ETRS89):
+ *                     Krueger's series to n^6 (Karney 2011), k0 0.9996, FE 500 000, FN 0 / 10 000 000
+ *      WGS 84, NAD83 and ETRS89 are one datum here (no datum shift: PROJ's "ballpark" transformation without grids).
+ *      A point outside the domain becomes NaN on both axes: |latitude| > 90, |lon - lon0| >= 90 degrees for UTM, the poles
+ *      for 3857.  Two descriptors of the same code copy the coordinates bit for bit; two geographic ones copy them too
+ *      (NaN where |latitude| > 90).  out_x / out_y are either x / y themselves (in place) or do not overlap them. */
+enum { PCR_HIP_CRS_GEOGRAPHIC = 1, PCR_HIP_CRS_WEB_MERCATOR = 2, PCR_HIP_CRS_TRANSVERSE_MERCATOR = 3 };
+typedef struct pcr_hip_crs_desc {
+    int32_t epsg;
+    int32_t kind;                    /* PCR_HIP_CRS_* */
+    double a, f;                     /* ellipsoid (web mercator: the sphere's radius a, f = 0) */
+    double lon0;                     /* central meridian, degrees */
+    double k0, fe, fn;               /* scale on the central meridian, false easting / northing (metres) */
+    double e;                        /* first eccentricity */
+    double ka;                       /* k0 * rectifying radius */
+    double alpha[6], beta[6];        /* Krueger series: forward, inverse */
+    double delta[6];                 /* conformal -> geodetic latitude series */
+} pcr_hip_crs_desc;
+/* PCR_HIP_NOT_IMPLEMENTED (with the code in pcr_hip_last_error) for a code outside the list above. */
+int pcr_hip_crs_from_epsg(int epsg, pcr_hip_crs_desc* out);
+/* n points on the device, enqueued on s. */
+int pcr_hip_transform_xy(const pcr_hip_crs_desc* src, const pcr_hip_crs_desc* dst, const double* d_x, const double* d_y,
+                         double* d_out_x, double* d_out_y, uint64_t n, pcr_hip_stream s);
+/* The same on host arrays, in the calling thread (pure, thread-safe: the host engine calls it from its OpenMP loop). */
+int pcr_hip_transform_xy_host(const pcr_hip_crs_desc* src, const pcr_hip_crs_desc* dst, const double* h_x, const double* h_y,
+                              double* h_out_x, double* h_out_y, uint64_t n);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,8 @@ public:
     /// (pcr_hip_comm_alltoallv: counts agreed first, one grouped ncclSend / ncclRecv round for x, y and every channel), and
     /// each rank ingests what it receives.  Collective: every rank calls it once per round, with an empty cloud (count() == 0)
     /// if it has nothing to contribute.  Channels must be 4 or 8 bytes wide; at most six of them.  `ingested` = points received.
+    /// A cloud in another CRS than the grid's is reprojected before it is routed (PipelineConfig::auto_reproject); when any
+    /// rank's cloud cannot be, every rank returns CrsError and nothing is accumulated.
     Status ingest_unrouted(const PointCloud& cloud, size_t* ingested = nullptr);
     /// The exchange alone (finalize() calls it): apron rows to their owners, touched-tile union.
     Status exchange();
@@ -81,6 +83,8 @@ private:
     std::string output_path_;         // taken from the configuration: rank 0 writes ONE GeoTIFF at finalize()
     std::string state_dir_;
     std::vector<ReductionSpec> reductions_;
+    CRS target_crs_;                  // with auto_reproject_: ingest_unrouted reprojects before it routes
+    bool auto_reproject_ = true;
     bool tiles_local_ = false;
     bool line_hl_groups_ = false;     // a Line group with a per-point half_length channel: ingest agrees on its reach first
 };

@@ -64,6 +64,23 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         Status ok = detail::validate_cloud(cfg, *cloud, 0, 0);
         if (!ok.ok()) return ok;
     }
+    // a cloud in another CRS than the grid's: its coordinates transformed into host vectors (the cloud stays as it is)
+    detail::Reprojection rp;
+    {
+        Status ok = detail::plan_reprojection(cfg, *cloud, &rp);
+        if (!ok.ok()) return ok;
+    }
+    std::vector<double> rx, ry;
+    const double* px = cloud->x();
+    const double* py = cloud->y();
+    if (rp.needed) {
+        rx.resize(n);
+        ry.resize(n);
+        Status ok = detail::transform_host(rp.src, rp.dst, px, py, rx.data(), ry.data(), n, engine->threads());
+        if (!ok.ok()) return ok;
+        px = rx.data();
+        py = ry.data();
+    }
     auto f32 = [&](const std::string& name) -> const float* {
         if (name.empty()) return nullptr;
         const ChannelDesc* d = cloud->channel(name);
@@ -112,7 +129,7 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     size_t valid = 0;
     for (size_t i0 = 0; i0 < n; i0 += slice) {
         const size_t m = std::min(slice, n - i0);
-        valid += engine->route(cloud->x() + i0, cloud->y() + i0, keep.empty() ? nullptr : keep.data() + i0, m);
+        valid += engine->route(px + i0, py + i0, keep.empty() ? nullptr : keep.data() + i0, m);
         for (auto& gr : groups) {
             const float* v = f32(gr.value_channel);
             if (gr.glyph.type == GlyphType::Point) {

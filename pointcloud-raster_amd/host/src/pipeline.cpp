@@ -423,6 +423,11 @@ struct Pipeline::Impl {
             Status ok = detail::validate_cloud(cfg, cloud, PCR_HIP_MAX_FILTER_SET, PCR_HIP_MAX_FILTER_PREDICATES);
             if (!ok.ok()) return ok;
         }
+        detail::Reprojection rp;
+        {
+            Status ok = detail::plan_reprojection(cfg, cloud, &rp);
+            if (!ok.ok()) return ok;
+        }
 
         const MemoryLocation loc = cloud.location();
         const void *dx = nullptr, *dy = nullptr;
@@ -430,6 +435,24 @@ struct Pipeline::Impl {
         if (!s.ok()) return s;
         s = device_array(cloud.y(), loc, n * sizeof(double), "y", &dy);
         if (!s.ok()) return s;
+        // A cloud in another CRS than the grid's: x, y transformed into a staging buffer of their own (the caller's device
+        // arrays are only read), which every kernel below reads instead
+        if (rp.needed) {
+            detail::Buffer& rb = staging["reproject:xy"];
+            if (rb.bytes() < 2 * n * sizeof(double)) {
+                // earlier kernels (chunks of ingest_async / ingest_file still in flight) may still read the old block
+                if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
+                if (!(s = rb.allocate(2 * (n + n / 8) * sizeof(double), MemoryLocation::Device)).ok()) return s;
+            }
+            const size_t cap = rb.bytes() / (2 * sizeof(double));
+            double* rx = static_cast<double*>(rb.data());
+            double* ry = rx + cap;
+            s = detail::hip_status(pcr_hip_transform_xy(&rp.src, &rp.dst, static_cast<const double*>(dx),
+                                                        static_cast<const double*>(dy), rx, ry, n, stream));
+            if (!s.ok()) return s;
+            dx = rx;
+            dy = ry;
+        }
 
         std::map<std::string, const void*> staged;      // a channel is staged once per ingest, whoever asks first
         auto f32_channel = [&](const std::string& name, const void** out) -> Status {
@@ -989,12 +1012,24 @@ struct Pipeline::Banded {
         // the checks every band's ingest would make, made once and whether or not the cloud reaches a band
         Status ok = detail::validate_cloud(cfg, cloud, PCR_HIP_MAX_FILTER_SET, PCR_HIP_MAX_FILTER_PREDICATES);
         if (!ok.ok()) return ok;
+        detail::Reprojection rp;
+        if (!(ok = detail::plan_reprojection(cfg, cloud, &rp)).ok()) return ok;
         // one device copy of a host cloud for all bands (each band's kernels read every point and keep its own)
         std::unique_ptr<PointCloud> staged;
         const PointCloud* src = &cloud;
-        if (cloud.location() != MemoryLocation::Device) {
+        if (cloud.location() != MemoryLocation::Device || rp.needed) {
             staged = cloud.to(MemoryLocation::Device);
             if (staged) src = staged.get();
+            else if (rp.needed) return Status::error(StatusCode::OutOfMemory, "pipeline: cannot copy the cloud to the device for its reprojection");
+        }
+        // A cloud in another CRS than the grid's is transformed once, on that copy (the caller's cloud is only read); the
+        // bands' sub-pipelines see it tagged with the grid's CRS and do not transform it again
+        if (rp.needed) {
+            Impl::DeviceScope dev(cfg.cuda_device_id);
+            if (!(ok = detail::hip_status(pcr_hip_transform_xy(&rp.src, &rp.dst, staged->x(), staged->y(), staged->x(), staged->y(),
+                                                               staged->count(), nullptr))).ok()) return ok;
+            if (!(ok = detail::hip_status(pcr_hip_stream_synchronize(nullptr))).ok()) return ok;
+            staged->set_crs(rp.dst_crs);
         }
         // points_processed counts the filter's survivors (round 5's fuzz: it counted the cloud); none: nothing to do, and the
         // ingest is not a collection either (src/engine/pipeline.cpp:349-353)
@@ -1288,6 +1323,7 @@ Status Pipeline::ingest_file(const std::string& path, size_t chunk_points, size_
     const MemoryLocation where = host_ ? MemoryLocation::Host : MemoryLocation::HostPinned;    // (no device: no page-locking either)
     std::unique_ptr<PointCloud> buf[2] = {PointCloud::create(chunk_points, where), PointCloud::create(chunk_points, where)};
     if (!buf[0] || !buf[1]) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate page-locked chunk buffers");
+    for (auto& b : buf) b->set_crs(reader->info().crs);      // the file's CRS: ingest reprojects the chunks when it differs from the grid's
     size_t total = 0;
     int cur = 0;
     size_t got = reader->read_chunk(*buf[cur], chunk_points);

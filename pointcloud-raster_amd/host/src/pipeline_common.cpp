@@ -2,6 +2,7 @@
 #include "pipeline_common.h"
 
 #include "pcr/core/point_cloud.h"
+#include "pcr/core/reproject.h"
 #include "pcr/io/tile_state_io.h"
 
 #include <algorithm>
@@ -33,6 +34,20 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
             return Status::error(StatusCode::NotImplemented,
                 "pipeline: glyph splatting only supports WeightedAverage, Average, Sum, or Count reduction types");
     }
+    return Status::success();
+}
+
+Status plan_reprojection(const PipelineConfig& cfg, const PointCloud& cloud, Reprojection* out) {
+    *out = Reprojection{};
+    if (!cfg.auto_reproject) return Status::success();
+    const CRS& dst = cfg.grid.crs.is_valid() ? cfg.grid.crs : cfg.target_crs;
+    const int from = crs_epsg(cloud.crs()), to = crs_epsg(dst);
+    if (from == 0 || to == 0 || from == to) return Status::success();
+    if (pcr_hip_crs_from_epsg(from, &out->src) != PCR_HIP_OK || pcr_hip_crs_from_epsg(to, &out->dst) != PCR_HIP_OK)
+        return Status::error(StatusCode::CrsError, "pipeline: cannot reproject the cloud from EPSG:" + std::to_string(from) +
+                             " to EPSG:" + std::to_string(to) + " (" + pcr_hip_last_error() + "); nothing was accumulated");
+    out->needed = true;
+    out->dst_crs = dst;
     return Status::success();
 }
 

@@ -4,6 +4,7 @@
 
 #include "pcr/core/grid_config.h"
 #include "pcr/engine/pipeline.h"
+#include "pcr_hip.h"
 
 #include <cstdint>
 #include <functional>
@@ -103,6 +104,24 @@ struct StateWindow {
     int own_row0 = -1, own_row1 = -1;      // >= 0: only tiles whose rows lie inside [own_row0, own_row1) (a shard with apron rows)
     std::function<float*(int group, int p)> plane;
 };
+
+// ---- reprojection on ingest (PipelineConfig::target_crs / auto_reproject; pcr/core/reproject.h) ---------------------------
+/// CRS -> the C-ABI's descriptor; CrsError when it is unidentified or not supported.  role: "source" / "destination".
+Status crs_desc(const CRS& crs, const char* role, pcr_hip_crs_desc* out);
+/// pcr_hip_transform_xy_host over `threads` OpenMP threads, in chunks.
+Status transform_host(const pcr_hip_crs_desc& src, const pcr_hip_crs_desc& dst, const double* x, const double* y, double* ox,
+                      double* oy, size_t n, int threads);
+/// What an ingest does about the cloud's CRS, decided before any state changes.  The destination is the grid's CRS when it
+/// is valid, else target_crs.  The cloud is reprojected only when auto_reproject is set, both CRSs are identified
+/// (crs_epsg) and their codes differ; anything else -- unidentified, untagged, equal -- ingests the coordinates as they are.
+struct Reprojection {
+    bool needed = false;
+    pcr_hip_crs_desc src{}, dst{};
+    CRS dst_crs;                         // what the reprojected points are tagged with
+};
+/// CrsError (naming both codes; nothing may be accumulated then) when both are identified and differ but either is not
+/// supported.
+Status plan_reprojection(const PipelineConfig& cfg, const PointCloud& cloud, Reprojection* out);
 
 /// "<dir>" for a single reduction (the reference's layout), "<dir>/reduction_<r>" otherwise.
 std::string reduction_state_dir(const std::string& dir, size_t r, size_t n_outputs);

@@ -9,6 +9,7 @@
 #include "buffer.h"
 #include "pcr/core/grid.h"
 #include "pcr/core/point_cloud.h"
+#include "pcr/core/reproject.h"
 #include "pcr/io/grid_io.h"
 #include "pcr_hip.h"
 #include "pipeline_common.h"
@@ -56,6 +57,8 @@ std::unique_ptr<ShardedPipeline> ShardedPipeline::create(PipelineConfig cfg, con
     cfg.output_path.clear();
     sp->state_dir_ = cfg.state_dir;
     sp->reductions_ = cfg.reductions;
+    sp->target_crs_ = cfg.target_crs;
+    sp->auto_reproject_ = cfg.auto_reproject;
     sp->pipe_ = Pipeline::create(cfg);
     if (!sp->pipe_) {
         g_create_error = "ShardedPipeline: " + pipeline_create_error();
@@ -266,12 +269,37 @@ Status ShardedPipeline::ingest_unrouted(const PointCloud& cloud_in, size_t* inge
     // A rank whose own part fails still takes part in every collective of the round (with nothing to send), so that the
     // others are not left waiting; its error is returned at the end.
     Status local = Status::success();
+    // Points are routed by their x, y in the GRID's CRS: a cloud in another one is reprojected first.  Whether a rank can is
+    // agreed over the ranks before the first collective of the round -- every rank passes the same verdict (the destination
+    // is the same on every rank: when it is unidentified no rank can refuse, and the round costs no agreement).
+    PipelineConfig rcfg;
+    rcfg.grid.crs = grid_.crs;
+    rcfg.target_crs = target_crs_;
+    rcfg.auto_reproject = auto_reproject_;
+    detail::Reprojection rp;
+    const Status crs = cloud_in.count() > 0 ? detail::plan_reprojection(rcfg, cloud_in, &rp) : Status::success();
+    if (world_ > 1 && comm_ && auto_reproject_ && crs_epsg(grid_.crs.is_valid() ? grid_.crs : target_crs_) != 0) {
+        int32_t refused = crs.ok() ? 0 : 1;
+        Status a = detail::hip_status(pcr_hip_comm_agree_max_i32(comm_, &refused, stream));
+        if (!a.ok()) return a;
+        if (!crs.ok()) return crs;
+        if (refused)
+            return Status::error(StatusCode::CrsError, "pipeline: another rank's cloud cannot be reprojected into the grid's CRS "
+                                                       "(refused on every rank, nothing was accumulated)");
+    } else if (!crs.ok()) {
+        return crs;
+    }
     std::unique_ptr<PointCloud> staged;
     const PointCloud* cloud = &cloud_in;
-    if (cloud->count() > 0 && cloud->location() != MemoryLocation::Device) {
+    if (cloud->count() > 0 && (cloud->location() != MemoryLocation::Device || rp.needed)) {
         staged = cloud->to(MemoryLocation::Device);
         if (!staged) local = Status::error(StatusCode::OutOfMemory, "ShardedPipeline::ingest_unrouted: cannot copy the cloud to the device");
         else cloud = staged.get();
+    }
+    if (rp.needed && local.ok()) {
+        local = detail::hip_status(pcr_hip_transform_xy(&rp.src, &rp.dst, staged->x(), staged->y(), staged->x(), staged->y(),
+                                                        staged->count(), stream));
+        staged->set_crs(rp.dst_crs);
     }
     const std::vector<std::string> names = cloud->channel_names();
     const int narrays = 2 + (int)names.size();
@@ -339,6 +367,7 @@ Status ShardedPipeline::ingest_unrouted(const PointCloud& cloud_in, size_t* inge
     void* dst[PCR_HIP_MAX_ROUTE_ARRAYS] = {};
     bool have = mine != nullptr;
     if (have) {
+        if (rp.needed) mine->set_crs(rp.dst_crs);           // (already in the grid's CRS: ingest() leaves it as it is)
         for (size_t c = 0; c < names.size() && have; ++c) have = mine->add_channel(names[c], cloud->channel(names[c])->dtype).ok();
         if (have) have = mine->resize((size_t)total_recv).ok();
     }

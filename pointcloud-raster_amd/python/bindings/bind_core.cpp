@@ -4,6 +4,10 @@
 #include "pcr/core/grid.h"
 #include "pcr/core/grid_config.h"
 #include "pcr/core/point_cloud.h"
+#include "pcr/core/reproject.h"
+#include "pcr/engine/pipeline.h"
+#include "pcr_hip.h"
+#include "../../host/src/pipeline_common.h"
 
 #include <cstring>
 
@@ -289,4 +293,54 @@ void bind_core(py::module_& m) {
             return "PointCloud(count=" + std::to_string(pc.count()) + ", capacity=" + std::to_string(pc.capacity()) +
                    ", channels=" + std::to_string(pc.channel_names().size()) + ")";
         });
+
+    // ---- reprojection (pcr/core/reproject.h); pcr.transform_xy in pcr/__init__.py picks the host or the device form
+    m.def("crs_epsg", &crs_epsg, py::arg("crs"),
+          "EPSG code of a CRS: CRS.epsg, else the top-level EPSG authority of its WKT; 0 when unidentified");
+    m.def("_transform_xy_host", [](const CRS& src, const CRS& dst,
+                                   py::array_t<double, py::array::c_style | py::array::forcecast> x,
+                                   py::array_t<double, py::array::c_style | py::array::forcecast> y) {
+        auto bx = x.request(), by = y.request();
+        if (bx.ndim != 1 || by.ndim != 1 || bx.shape[0] != by.shape[0])
+            throw std::runtime_error("transform_xy: x and y must be 1-D arrays of the same length");
+        const size_t n = static_cast<size_t>(bx.shape[0]);
+        py::array_t<double> ox(static_cast<py::ssize_t>(n)), oy(static_cast<py::ssize_t>(n));
+        Status s;
+        {
+            py::gil_scoped_release nogil;
+            s = transform_xy(src, dst, static_cast<const double*>(bx.ptr), static_cast<const double*>(by.ptr),
+                             ox.mutable_data(), oy.mutable_data(), n, MemoryLocation::Host);
+        }
+        raise_if_error(s);
+        return py::make_tuple(ox, oy);
+    });
+    // device arrays given by address, enqueued on `stream` (0: the null stream)
+    m.def("_transform_xy_device", [](const CRS& src, const CRS& dst, uintptr_t x, uintptr_t y, uintptr_t ox, uintptr_t oy,
+                                     size_t n, uintptr_t stream) {
+        pcr_hip_crs_desc s, d;
+        raise_if_error(detail::crs_desc(src, "source", &s));
+        raise_if_error(detail::crs_desc(dst, "destination", &d));
+        const int rc = pcr_hip_transform_xy(&s, &d, reinterpret_cast<const double*>(x), reinterpret_cast<const double*>(y),
+                                            reinterpret_cast<double*>(ox), reinterpret_cast<double*>(oy), n,
+                                            reinterpret_cast<void*>(stream));
+        if (rc != PCR_HIP_OK) throw std::runtime_error(pcr_hip_last_error());
+    });
+    m.def("reproject", [](PointCloud& cloud, const CRS& dst) {
+        Status s;
+        {
+            py::gil_scoped_release nogil;
+            s = reproject(cloud, dst);
+        }
+        raise_if_error(s);
+    }, py::arg("cloud"), py::arg("dst_crs"), "Reprojects the cloud's x, y in place (Host, HostPinned or Device) and sets its CRS");
+    // what Pipeline.ingest would do about this cloud's CRS: None (ingest it as it is) or the CRS it is reprojected into;
+    // RuntimeError when it would refuse (pcr/distributed.py routes by x, y and decides first)
+    m.def("_plan_reprojection", [](const PipelineConfig& cfg, const CRS& cloud_crs) -> py::object {
+        std::unique_ptr<PointCloud> probe = PointCloud::create(1);
+        probe->set_crs(cloud_crs);
+        detail::Reprojection rp;
+        raise_if_error(detail::plan_reprojection(cfg, *probe, &rp));
+        if (!rp.needed) return py::none();
+        return py::cast(rp.dst_crs);
+    });
 }

@@ -71,7 +71,34 @@ from ._pcr import (  # noqa: E402,F401
     read_geotiff_info, read_point_cloud, read_point_cloud_info, write_geotiff, write_point_cloud,
     read_tile_state, tile_state_filename, write_tile_state,
     read_geotiff_band, read_geotiff_band_names, TiledGeoTiffWriter,
+    crs_epsg, reproject,
 )
+from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
+
+
+def _as_crs(c):
+    return CRS.from_epsg(int(c)) if isinstance(c, int) else c
+
+
+def transform_xy(src_crs, dst_crs, x, y):
+    """(x2, y2): the points (x, y) transformed from `src_crs` into `dst_crs` (pcr.CRS or EPSG codes).  numpy arrays are
+    transformed on the host and give numpy arrays; device tensors (torch, on the GPU) on the device, on torch's current
+    stream, and give new tensors.  Points outside the domain become NaN; RuntimeError for an unidentified or unsupported CRS."""
+    src_crs, dst_crs = _as_crs(src_crs), _as_crs(dst_crs)
+    if hasattr(x, "__cuda_array_interface__") or hasattr(y, "__cuda_array_interface__"):
+        import torch
+        if not (torch.is_tensor(x) and torch.is_tensor(y) and x.is_cuda and y.is_cuda):
+            raise TypeError("transform_xy: device arrays must be torch tensors on the GPU")
+        if x.dtype != torch.float64 or y.dtype != torch.float64 or x.dim() != 1 or x.shape != y.shape:
+            raise ValueError("transform_xy: x and y must be 1-D float64 tensors of the same length")
+        x, y = x.contiguous(), y.contiguous()
+        ox, oy = torch.empty_like(x), torch.empty_like(y)
+        with torch.cuda.device(x.device):
+            _transform_xy_device(src_crs, dst_crs, x.data_ptr(), y.data_ptr(), ox.data_ptr(), oy.data_ptr(), x.numel(),
+                                 torch.cuda.current_stream().cuda_stream)
+        return ox, oy
+    return _transform_xy_host(src_crs, dst_crs, x, y)
+
 
 
 def _splat_spec(value_channel, glyph_type, max_radius_cells, output_band_name):
@@ -141,4 +168,5 @@ __all__ = [
     "DeviceArrayView", "hip_runtime_paths", "device_count", "device_name", "pipeline_create_error",
     "read_tile_state", "write_tile_state", "tile_state_filename",
     "read_geotiff_band", "read_geotiff_band_names", "TiledGeoTiffWriter",
+    "crs_epsg", "transform_xy", "reproject",
 ]

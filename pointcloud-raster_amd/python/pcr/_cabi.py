@@ -55,6 +55,12 @@ class ScatterStats(C.Structure):
                 ("num_bins", C.c_int32), ("scatter_chunk", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class CrsDesc(C.Structure):
+    _fields_ = [("epsg", C.c_int32), ("kind", C.c_int32), ("a", C.c_double), ("f", C.c_double), ("lon0", C.c_double),
+                ("k0", C.c_double), ("fe", C.c_double), ("fn", C.c_double), ("e", C.c_double), ("ka", C.c_double),
+                ("alpha", C.c_double * 6), ("beta", C.c_double * 6), ("delta", C.c_double * 6)]
+
+
 # every symbol include/pcr_hip.h declares: name -> argtypes (restype is int unless noted)
 _VP, _SZ, _I64, _U64, _U32 = C.c_void_p, C.c_size_t, C.c_int64, C.c_uint64, C.c_uint32
 class HaloPlane(C.Structure):
@@ -149,6 +155,9 @@ SYMBOLS = {
     "pcr_hip_engine_profile_read": [_VP, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int), C.c_int],
     "pcr_hip_scatter_point": [_VP, _U32, C.POINTER(Planes), _VP, _VP, _VP, _U64],
     "pcr_hip_scatter_glyph": [_VP, C.POINTER(Glyph), _U32, C.POINTER(Planes), _VP, _VP, _VP, _U64],
+    "pcr_hip_crs_from_epsg": [C.c_int, C.POINTER(CrsDesc)],
+    "pcr_hip_transform_xy": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64, _VP],
+    "pcr_hip_transform_xy_host": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64],
 }
 
 _lib = None

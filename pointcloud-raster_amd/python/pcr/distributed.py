@@ -312,6 +312,10 @@ class ShardedPipeline:
         self.comm_kind = comm
         self._comm = None
         self.grid = cfg.grid
+        # what ingest_unrouted needs to reproject a cloud before it routes it (Pipeline.ingest decides the same way)
+        self._crs_cfg = pcr.PipelineConfig()
+        self._crs_cfg.grid.crs, self._crs_cfg.target_crs = cfg.grid.crs, cfg.target_crs
+        self._crs_cfg.auto_reproject = cfg.auto_reproject
         self.exchange_ms = None              # set by exchange(timed=True)
         self.blocks = [row_block(r, world, cfg.grid.height, align) for r in range(world)]
         self.own = self.blocks[rank]
@@ -415,6 +419,39 @@ class ShardedPipeline:
                 f"the row-block shards keep a halo of {self.halo} rows; set PipelineConfig.shard_halo_rows >= {need} "
                 "on every rank, or use tile-aligned row blocks (refused on every rank, nothing was accumulated)")
 
+    def _agree_reprojection(self, cloud):
+        """The CRS this rank's cloud is reprojected into before routing (None: routed as it is).  Every rank passes the
+        same verdict: a cloud that cannot be reprojected is refused on every rank, before the first collective."""
+        import pcr
+        cfg = self._crs_cfg
+        dst = cfg.grid.crs if cfg.grid.crs.is_valid() else cfg.target_crs
+        if not cfg.auto_reproject or pcr.crs_epsg(dst) == 0:
+            return None                          # no rank can refuse: no agreement either
+        err, out = None, None
+        if cloud.count() > 0:
+            try:
+                out = pcr._pcr._plan_reprojection(cfg, cloud.crs())
+            except RuntimeError as e:
+                err = e
+        refused = 1 if err is not None else 0
+        if self._comm is not None:
+            import ctypes as C
+            from . import _cabi as A
+            word = C.c_int32(refused)
+            A.check(A.lib().pcr_hip_comm_agree_max_i32(self._comm, C.byref(word), self.pipe.stream_ptr()))
+            refused = int(word.value)
+        else:
+            cpu = dist.get_backend(self.group) == "gloo"
+            t = torch.tensor([refused], dtype=torch.int32, device="cpu" if cpu else "cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+            refused = int(t.item())
+        if err is not None:
+            raise err
+        if refused:
+            raise RuntimeError("pipeline: another rank's cloud cannot be reprojected into the grid's CRS "
+                               "(refused on every rank, nothing was accumulated)")
+        return out
+
     def _engine_stream(self):
         ptr = self.pipe.stream_ptr()
         if ptr:
@@ -429,13 +466,18 @@ class ShardedPipeline:
         if self.world == 1:
             return self.pipe.ingest(cloud)
         import pcr
-        if cloud.location() != pcr.MemoryLocation.Device:
-            cloud = cloud.to_device()
+        dst = self._agree_reprojection(cloud)
+        if cloud.location() != pcr.MemoryLocation.Device or dst is not None:
+            cloud = cloud.to_device()                # (a copy: the caller's cloud is never modified)
+        if dst is not None:
+            pcr.reproject(cloud, dst)                # points are routed by their x, y in the grid's CRS
         ptr, ctx = self._engine_stream()
         with ctx:
             mine = route_cloud(cloud, self.grid, self.blocks, self.rank, self.world, self.group, ptr, comm=self._comm)
             if not ptr:
                 torch.cuda.current_stream().synchronize()
+        if dst is not None:
+            mine.set_crs(dst)                    # (already in the grid's CRS: ingest leaves it as it is)
         self._agree_line_reach(mine)         # after routing: every rank asks about the points it will really ingest
         self.pipe.ingest(mine)
         self.pipe.synchronize()              # `mine` is freed on return
