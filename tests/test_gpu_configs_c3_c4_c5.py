@@ -13,6 +13,7 @@ import pytest
 
 import pcr
 import pcr_oracle_py as O
+import window_oracle as WO
 from conftest import assert_band_close
 from test_gpu_pipeline_api import cloud_from, config_for, spec
 
@@ -82,10 +83,12 @@ def test_c3_full_size_line_binned_vs_direct():
     cloud = cloud_from(x, y, {"value": v, "direction": d}, "device")
     ls = pcr.line_splat_spec("value", direction_channel="direction", default_half_length=16.0, max_radius_cells=18.0)
     lc = pcr.line_splat_spec("value", direction_channel="direction", default_half_length=16.0, max_radius_cells=18.0)
+    lw = pcr.line_splat_spec("value", direction_channel="direction", default_half_length=16.0, max_radius_cells=18.0)
     ls.type, lc.type = pcr.ReductionType.Sum, pcr.ReductionType.Count
+    assert lw.type == pcr.ReductionType.WeightedAverage                # the bench's line16 band
     out = {}
     for path in (2, 1):
-        p = pcr.Pipeline.create(config_for(og, [ls, lc], scatter_path=path))
+        p = pcr.Pipeline.create(config_for(og, [ls, lc, lw], scatter_path=path))
         p.ingest(cloud)
         p.finalize()
         out[path] = bands(p)
@@ -103,6 +106,20 @@ def test_c3_full_size_line_binned_vs_direct():
                  direction=d[sel])
     w, g = np.nan_to_num(want[lo:hi, lo:hi]), np.nan_to_num(out[2][1][lo:hi, lo:hi])
     assert np.array_equal(w, g), "Line count differs from the oracle on the [1000, 1200)^2 window"
+    # Sum and WeightedAverage of both paths against the double-accumulated oracle on the same window (NaN masks against the
+    # single-accumulated one), 1e-4 with the floor of the Gaussian window tests
+    ogl = O.make_glyph(O.GLYPH_LINE, half_length=16.0, max_radius=18.0)
+    for b, rt in ((0, O.SUM), (2, O.WEIGHTED_AVERAGE)):
+        exact, single = WO.window(og, rt, x, y, v, (lo, hi, lo, hi), glyph=ogl, direction=d)
+        for path in (2, 1):
+            g = out[path][b][lo:hi, lo:hi]
+            what = f"Line {O.RTYPE_NAMES[rt]}, path {path}, vs the oracle on the [1000, 1200)^2 window"
+            assert np.array_equal(np.isnan(g), np.isnan(single)), what + ": NaN mask"
+            ok = ~np.isnan(single)
+            assert ok.all()                                                # ~33 cell visits per cell: every cell is reached
+            e = exact[ok].astype(np.float64)
+            err = np.abs(g[ok].astype(np.float64) - e)
+            assert (err <= 1e-4 * np.maximum(1e-3, np.abs(e))).all(), f"{what}: max rel err {np.max(err / np.abs(e)):.3g}"
 
 
 def test_c3_full_size_gaussian_sigma4_three_paths():
@@ -211,10 +228,12 @@ def test_c2_full_size_sum_count_average_vs_oracle_window():
     assert (gs[~occ] == 0.0).all()                                  # Q2: Sum of an empty cell inside a touched tile
 
 
-@pytest.mark.parametrize("sigma,max_r,win", [(1.0, 4.0, 128), (16.0, 64.0, 48)], ids=["sigma1_cell_tiles", "sigma16_moments"])
+@pytest.mark.parametrize("sigma,max_r,win", [(1.0, 4.0, 128), (4.0, 12.0, 96), (16.0, 64.0, 48)],
+                         ids=["sigma1_cell_tiles", "sigma4_moments_k5", "sigma16_moments"])
 def test_bench_gaussian_clouds_full_size_vs_oracle_window(sigma, max_r, win):
-    """The two Gaussian clouds of bench.py's per_glyph legs exactly as the driver times them (50 M uniform points, 4096^2,
-    seed 42; sigma = 1 through the register-accumulating cell tiles, sigma = 16 through moments + the matrix-core column pass):
+    """The three Gaussian clouds of bench.py's per_glyph legs exactly as the driver times them (50 M uniform points, 4096^2,
+    seed 42; sigma = 1 through the register-accumulating cell tiles, sigma = 4 r <= 12 (C3) and sigma = 16 through moments +
+    the matrix-core column pass):
     every cell of a window against the oracle run on the points whose footprint can reach it."""
     G, n = 4096, 50_000_000
     rng = np.random.default_rng(42)                                 # bench.py make_points(...)
