@@ -33,7 +33,9 @@ extern "C" {
 #define PCR_HIP_ABI_VERSION 5   /* 3 (round 4): + comm_halo_plan / comm_agree_max_i32 / signed_max_f32_masked / copy_kernel; planes_fresh takes 0, 1, 2;
                                  * 4: + engine_finalize_with_scatter / engine_finalize_taken / finalize_group_unless / touched_union;
                                  * 5 (round 5): + comm_alltoall_counts / comm_alltoallv / comm_gatherv / comm_xfer_plan / touched_union_owned; halo_reduce resets the sent apron rows;
-                                 *   later, additive (same version): + crs_from_epsg / transform_xy / transform_xy_host */
+                                 *   later, additive (same version): + crs_from_epsg / transform_xy / transform_xy_host;
+                                 *   + PCR_HIP_MOST_RECENT: select_pack / select_unpack / select_merge / scatter_select / finalize_select,
+                                 *     state_floats / state_init / state_merge accept type 8 */
 
 typedef enum pcr_hip_status {
     PCR_HIP_OK = 0,
@@ -45,11 +47,13 @@ typedef enum pcr_hip_status {
     PCR_HIP_NOT_IMPLEMENTED = 6
 } pcr_hip_status;
 
-/* pcr::ReductionType numbering (types.h:33-45); only these six are registered
- * (src/ops/reduction_registry.cpp:173-184). */
+/* pcr::ReductionType numbering (types.h:33-45).  The reference registers the first six
+ * (src/ops/reduction_registry.cpp:173-184); MostRecent it only declares (builtin_ops.h:106-124): this build implements it
+ * for the Point glyph through the pcr_hip_*select* entry points below.  The functions that take pcr_hip_planes refuse it. */
 enum {
     PCR_HIP_SUM = 0, PCR_HIP_MAX = 1, PCR_HIP_MIN = 2,
-    PCR_HIP_AVERAGE = 3, PCR_HIP_WEIGHTED_AVERAGE = 4, PCR_HIP_COUNT = 5
+    PCR_HIP_AVERAGE = 3, PCR_HIP_WEIGHTED_AVERAGE = 4, PCR_HIP_COUNT = 5,
+    PCR_HIP_MOST_RECENT = 8
 };
 
 /* pcr::GlyphType numbering (include/pcr/engine/glyph.h:11-15). */
@@ -403,6 +407,36 @@ int pcr_hip_scatter_point(pcr_hip_engine* e, uint32_t plane_mask, const pcr_hip_
 int pcr_hip_scatter_glyph(pcr_hip_engine* e, const pcr_hip_glyph* glyph, uint32_t plane_mask,
                           const pcr_hip_planes* planes,
                           const double* d_x, const double* d_y, const float* d_value, uint64_t n);
+
+/* ---- MostRecent: per cell, the value of the point with the greatest key (timestamp).  Point glyph only.
+ *      replaces: MostRecentOp / combine_timestamped (include/pcr/ops/builtin_ops.h:106-124), which the reference declares but
+ *      never registers, and its racy kernel_accumulate_most_recent (src/engine/accumulator_kernels.cu:136-167).
+ *   On the device a group's state is ONE plane of packed 64-bit words in grid layout (8 bytes per cell):
+ *      ord(f)     = bits(f) ^ (sign(f) ? 0xFFFFFFFF : 0x80000000)        (monotone float -> unsigned)
+ *      word(t, v) = (uint64(ord(t + 0.0f)) << 32) | ord(v)
+ *   A point is ACCEPTED when it is inside the bounds and the owned rows, the mask keeps it, and its key t satisfies t == t and
+ *   t > -FLT_MAX.  A cell holds the MAXIMUM word of its accepted points, 0 when it has none (every accepted word is
+ *   > 0x0080000000000000: a memset defines the plane).  Among equal keys the greater value by ord() wins; a NaN value is
+ *   copied like any other.  The fold is associative, commutative and idempotent: every path, split and order gives the same
+ *   bits.  At the boundary (checkpoints, `.pcrt` files, host copies) the state is the reference's layout, two float planes:
+ *   plane 0 the value, plane 1 the key, an empty cell {NaN 0x7FC00000, -FLT_MAX} (pack_state<MostRecentOp>,
+ *   builtin_ops.h:178-183); pcr_hip_state_init / _merge of type 8 work on that layout (d_state = 2 planes, stride = cells).
+ *      select_pack      float planes -> words (a NaN or <= -FLT_MAX key means empty)
+ *      select_unpack    words -> float planes
+ *      select_merge     d_dst[i] = max(d_dst[i], d_src[i]), 64-bit unsigned
+ *      scatter_select   the scatter; honours pcr_hip_engine_set_path (1 direct: one 64-bit global atomic max per accepted
+ *                       point; 2 binned: 8-byte index records, one 64-bit LDS atomic max per record, tile merge; 0 / 3 auto),
+ *                       pcr_hip_engine_planes_fresh (0 / 1 / 2, with "identity" = 0), the point mask, the owned rows, the
+ *                       touched flags, pcr_hip_engine_stats and the profile timers, like pcr_hip_scatter_point
+ *      finalize_select  out = value where the word is non-zero and the cell's reference tile is touched, NaN elsewhere;
+ *                       rows [own_row0, own_row1) as pcr_hip_finalize */
+int pcr_hip_select_pack(const float* d_value, const float* d_key, uint64_t* d_packed, int64_t cells, pcr_hip_stream s);
+int pcr_hip_select_unpack(const uint64_t* d_packed, float* d_value, float* d_key, int64_t cells, pcr_hip_stream s);
+int pcr_hip_select_merge(uint64_t* d_dst, const uint64_t* d_src, int64_t cells, pcr_hip_stream s);
+int pcr_hip_scatter_select(pcr_hip_engine* e, uint64_t* d_packed, const double* d_x, const double* d_y,
+                           const float* d_value, const float* d_key, uint64_t n);
+int pcr_hip_finalize_select(const pcr_hip_grid* g, const uint64_t* d_packed, const uint32_t* d_tile_touched, float* d_out,
+                            pcr_hip_stream s);
 
 /* ---- coordinate reprojection.  No reference counterpart: PipelineConfig::target_crs / auto_reproject are declared there
  *      (include/pcr/engine/pipeline.h:55-56) and src/engine/reprojection.cpp is a TODO.  No PROJ: a fixed set of EPSG codes

@@ -234,6 +234,24 @@ __device__ __forceinline__ void atomic_min_f32(float* p, float v) {
     else atomicMax(reinterpret_cast<unsigned*>(p), b);
 }
 
+// ---- MostRecent (pcr_hip.h: "MostRecent") ------------------------------------------------------
+// word(t, v) = ord(t + 0.0f) << 32 | ord(v), ord = the monotone map of float bits onto unsigned integers; the maximum word of a
+// cell's accepted points IS its state, so the whole fold is one 64-bit integer max per point: ds_max_u64 in an LDS tile,
+// global_atomic_umax_x2 on the plane (plain atomicMax on unsigned long long compiles to both).  "+ 0.0f" (a -0.0 key counts as
+// +0.0) is done on the bits, so that it does not depend on the denormal mode.
+__device__ __forceinline__ unsigned select_ord(unsigned b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+__device__ __forceinline__ unsigned select_unord(unsigned u) { return (u >> 31) ? (u ^ 0x80000000u) : ~u; }
+// combine_timestamped's `ts > acc.timestamp` against the identity's -FLT_MAX (builtin_ops.h:114-116); false for NaN
+__device__ __forceinline__ bool select_accepts(float t) { return t > -FLT_MAX; }
+__device__ __forceinline__ unsigned long long select_word(float t, float v) {
+    unsigned tb = __float_as_uint(t);
+    if (tb == 0x80000000u) tb = 0u;
+    return ((unsigned long long)select_ord(tb) << 32) | select_ord(__float_as_uint(v));
+}
+__device__ __forceinline__ float select_value(unsigned long long w) { return __uint_as_float(select_unord((unsigned)w)); }
+__device__ __forceinline__ float select_key(unsigned long long w) { return __uint_as_float(select_unord((unsigned)(w >> 32))); }
+constexpr unsigned kSelectEmptyValueBits = 0x7FC00000u;        // the identity's NaN (MostRecentOp::identity)
+
 // Mark the reference tile of (row, col) as having state (pipeline.cpp:688-691, 1220).
 __device__ __forceinline__ void touch_tile(const GridDev& g, uint32_t* touched, int row, int col) {
     int t = fast_div(row, g.th) * g.tiles_x + fast_div(col, g.tw);

@@ -386,6 +386,39 @@ int pcr_hip_scatter_point(pcr_hip_engine* e, uint32_t plane_mask, const pcr_hip_
     return rc;
 }
 
+int pcr_hip_scatter_select(pcr_hip_engine* e, uint64_t* d_packed, const double* d_x, const double* d_y,
+                           const float* d_value, const float* d_key, uint64_t n) {
+    PCR_REQUIRE(e, "scatter_select: null engine");
+    e->fused_outs.n = 0;                                  // (a pending finalize-with-scatter hint does not apply here)
+    e->fused_done = nullptr;
+    e->fused_taken = false;
+    PCR_REQUIRE(d_packed, "scatter_select: null packed plane");
+    PCR_REQUIRE((reinterpret_cast<uintptr_t>(d_packed) & 7) == 0, "scatter_select: the packed plane must be 8-byte aligned");
+    if (n == 0) return PCR_HIP_OK;                       // empty cloud is a no-op, as for pcr_hip_scatter_point
+    PCR_REQUIRE(n < ((uint64_t)1 << 40), "scatter_select: too many points in one call");
+    PCR_REQUIRE(d_x && d_y, "scatter_select: null coordinate array");
+    PCR_REQUIRE(d_value && d_key, "scatter_select: null value or key array");
+    auto* packed = reinterpret_cast<unsigned long long*>(d_packed);
+    DeviceGuard dev(e->device);
+    int rc = begin_scatter(e, n);
+    if (rc) return rc;
+    const bool can_bin = binned_select_supported(e);
+    if (e->forced_path == 2 && !can_bin)
+        return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_select: binned path forced but not applicable to this grid");
+    if (e->forced_path == 1 || !can_bin) {
+        if (e->planes_fresh == 2) {                       // an undefined plane: every word 0 (the identity) first
+            ScopedKernelTimer t(e, "k_state_init");
+            PCR_HIP_TRY(hipMemsetAsync(packed, 0, (size_t)e->gd.st_rows * e->gd.W * sizeof(unsigned long long), e->stream));
+        }
+        e->planes_fresh = 0;
+        return direct_select(e, packed, d_x, d_y, d_value, d_key, n);
+    }
+    rc = binned_select(e, packed, d_x, d_y, d_value, d_key, n);
+    e->planes_fresh = 0;                                  // the hint covers one scatter
+    release_scratch(e);
+    return rc;
+}
+
 int pcr_hip_scatter_glyph(pcr_hip_engine* e, const pcr_hip_glyph* glyph, uint32_t plane_mask,
                           const pcr_hip_planes* planes,
                           const double* d_x, const double* d_y, const float* d_value, uint64_t n) {

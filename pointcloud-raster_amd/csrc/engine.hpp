@@ -89,6 +89,7 @@ struct BinBuffers {                     // device pointers into the engine's scr
     const BinItem* items;
     const unsigned* n_items;            // [0] = items, [1] = 1 when some bin was split into several items
     int max_items;
+    void* extra;                        // extra_bytes of the same scratch allocation, 256-B aligned, for the caller's own pass
 };
 constexpr int kMaxBins = 12160;        // scatter pass LDS: the 8192-record staging window (64 KB) + 8 B per bin = 159 KB of the CU's 160.
                                         // Round 5 (8064 until then, "beyond this a block's runs are single records anyway"): measured on
@@ -117,7 +118,8 @@ inline int band_rows_for(const GridDev& g, int tile_w, int tile_h, int max_bins)
 enum class RecordKind { Value, Index };
 // every_bin: an item (possibly of zero records) for EVERY bin, so that the tile pass visits every cell of the band.
 int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const double* x, const double* y, const float* v,
-               uint64_t n, RecordKind kind, const GlyphDev* gl, unsigned item_records, BinBuffers* out, bool every_bin = false);
+               uint64_t n, RecordKind kind, const GlyphDev* gl, unsigned item_records, BinBuffers* out, bool every_bin = false,
+               size_t extra_bytes = 0);
 // Identity values (0, 0, -FLT_MAX, +FLT_MAX) into the planes of `mask` over the engine's state window (engine.hip).
 int fill_identity(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl);
 
@@ -125,7 +127,8 @@ int fill_identity(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl);
 // 8-byte Value or Index records.  two_level_shift: 0 when not applicable (disabled, or more than kMaxTiles tiles).
 int two_level_shift(const pcr_hip_engine* e, int tiles);
 int bin_points_two_level(pcr_hip_engine* e, const BinGeom& tiles, const double* x, const double* y, const float* v,
-                         uint64_t n, bool index_records, unsigned item_records, BinBuffers* out, bool every_bin = false);
+                         uint64_t n, bool index_records, unsigned item_records, BinBuffers* out, bool every_bin = false,
+                         size_t extra_bytes = 0);
 
 // direct path (global atomics), scatter_direct.hip
 int direct_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
@@ -140,6 +143,14 @@ int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
 bool binned_glyph_supported(const pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask);
 int binned_glyph(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const PlanesDev& pl,
                  const double* x, const double* y, const float* v, uint64_t n);
+
+// MostRecent (pcr_hip_scatter_select): one plane of packed 64-bit words, common.hpp select_word.  direct: scatter_direct.hip;
+// binned: Index records through the Point front end (bin_points / bin_points_two_level), tile pass in scatter_binned.hip.
+int direct_select(pcr_hip_engine* e, unsigned long long* packed, const double* x, const double* y, const float* v,
+                  const float* key, uint64_t n);
+bool binned_select_supported(const pcr_hip_engine* e);
+int binned_select(pcr_hip_engine* e, unsigned long long* packed, const double* x, const double* y, const float* v,
+                  const float* key, uint64_t n);
 
 // Gaussian cell tiles on 16-byte value records (default-sigma, unrotated, r <= 3), scatter_cells.hip
 bool cells_gauss_supported(const pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask);

@@ -797,6 +797,134 @@ void launch_accum(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const 
     else go(&k_tile_accum<MASK, false>, FinalizeOuts{}, nullptr);
 }
 
+// ---- pass C (MostRecent, pcr_hip_scatter_select): fold a work item's records into an LDS tile of packed words ------------
+// One unsigned long long per cell (common.hpp: select_word), 128 x 128 cells = 128 KB: the fold is ONE ds_max_u64 per record
+// (~12 cycles per wave-instruction, like ds_add_u64 above), whatever the order.  The records are the Point front end's INDEX
+// records {local cell, point index}; what is gathered by index is the point's ready-made word (k_select_words: one streaming
+// pass packs key and value, 0 for a refused key) -- ONE 8-byte load per record where gathering key and value apart fetched two
+// cache lines (measured: profiles/most_recent.md; DESIGN.md "MostRecent" says why not wider records).  A batch's gathers are
+// issued together ahead of its LDS atomics.
+// Merge: an exclusively owned bin max-merges into the plane with plain 16-byte read-modify-writes (fresh: stores; full: every
+// cell stored, empty ones as 0); a bin the scan split merges with the global 64-bit atomic max, on a plane k_zero_if defined.
+constexpr uint32_t kSelectGeomMask = PCR_HIP_PLANE_SUM;       // point_bin_geom / point_bands: 8 B per cell, like the Sum plane's doubles
+
+__global__ void __launch_bounds__(kThreads)
+k_tile_select(GridDev g, BinGeom b, unsigned long long* __restrict__ packed, const uint2* __restrict__ records,
+              const BinItem* __restrict__ items, const unsigned* __restrict__ n_items, int fresh,
+              const unsigned long long* __restrict__ words) {
+    extern __shared__ unsigned long long lds_words[];
+    if (blockIdx.x >= *n_items) return;
+    const bool full = fresh == 2 && n_items[1] == 0u;          // as in k_tile_accum
+    const BinItem it = items[blockIdx.x];
+    const int cells = b.tile_w * b.tile_h;                     // multiple of 1024
+
+    constexpr int kUnroll = 4;
+    const uint2* rec = records + it.first;
+    uint2 cur[kUnroll], nxt[kUnroll];
+    auto fetch = [&](uint2 (&r)[kUnroll], unsigned j0) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const unsigned j = j0 + u * kThreads;
+            r[u] = j < it.count ? stream_load(rec + j) : make_uint2(0xFFFFFFFFu, 0u);
+        }
+    };
+    fetch(cur, threadIdx.x);
+    for (int i = threadIdx.x; i < cells; i += kThreads) lds_words[i] = 0ull;
+    __syncthreads();
+
+    for (unsigned j0 = threadIdx.x; j0 < it.count; j0 += kUnroll * kThreads) {
+        fetch(nxt, j0 + kUnroll * kThreads);                    // past the end: sentinels, no loads issued
+        unsigned long long w[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) w[u] = cur[u].x != 0xFFFFFFFFu ? words[cur[u].y] : 0ull;
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u)
+            if (w[u]) atomicMax(&lds_words[cur[u].x], w[u]);
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) cur[u] = nxt[u];
+    }
+    __syncthreads();
+
+    const int bx = it.bin % b.bins_x, by = it.bin / b.bins_x;
+    const int c0 = bx * b.tile_w, r0 = b.row0 + by * b.tile_h;        // r0 relative to the state window
+    const int w = min(b.tile_w, g.W - c0), h = min(b.tile_h, b.row0 + b.rows - r0);
+    const bool vec = !it.shared && (g.W % 2 == 0) && (w % 2 == 0) && (reinterpret_cast<uintptr_t>(packed) & 15) == 0;
+    if (vec) {
+        // one lane = 2 consecutive cells of a row = 16 bytes
+        const int hrow = b.tile_w >> 1;
+        for (int i = threadIdx.x; i < hrow * h; i += kThreads) {
+            const int ly = i / hrow, lx = (i - ly * hrow) << 1;
+            if (lx >= w) continue;
+            ulonglong2* dst = reinterpret_cast<ulonglong2*>(packed + (int64_t)(r0 + ly) * g.W + (c0 + lx));
+            ulonglong2 a = *reinterpret_cast<const ulonglong2*>(lds_words + ly * b.tile_w + lx);
+            if (!full && !(a.x | a.y)) continue;
+            if (!fresh) {
+                const ulonglong2 cur2 = *dst;
+                a.x = a.x > cur2.x ? a.x : cur2.x;
+                a.y = a.y > cur2.y ? a.y : cur2.y;
+            }
+            *dst = a;
+        }
+        return;
+    }
+    for (int i = threadIdx.x; i < b.tile_w * h; i += kThreads) {
+        const int ly = i / b.tile_w, lx = i - ly * b.tile_w;
+        if (lx >= w) continue;
+        unsigned long long* dst = packed + (int64_t)(r0 + ly) * g.W + (c0 + lx);
+        const unsigned long long a = lds_words[ly * b.tile_w + lx];
+        if (full) *dst = a;                                           // (an item per bin, none of them shared)
+        else if (!a) continue;
+        else if (it.shared) atomicMax(dst, a);
+        else if (fresh) *dst = a;
+        else if (a > *dst) *dst = a;
+    }
+}
+
+// words[i] = word(key[i], v[i]), 0 where the key is refused: 8 B read and 8 B written per point, streaming.  VEC: four
+// points per lane (16-byte loads, two 16-byte stores) when v and key are 16-byte aligned; the ragged end goes one by one.
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+k_select_words(const float* __restrict__ v, const float* __restrict__ key, unsigned long long* __restrict__ words, uint64_t n) {
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    const uint64_t first = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    auto one = [](float t, float val) { return select_accepts(t) ? select_word(t, val) : 0ull; };
+    const uint64_t n4 = VEC ? n >> 2 : 0;
+    for (uint64_t q = first; q < n4; q += stride) {
+        const float4 t = stream_load(reinterpret_cast<const float4*>(key) + q);
+        const float4 a = stream_load(reinterpret_cast<const float4*>(v) + q);
+        ulonglong2* dst = reinterpret_cast<ulonglong2*>(words + 4 * q);
+        dst[0] = make_ulonglong2(one(t.x, a.x), one(t.y, a.y));
+        dst[1] = make_ulonglong2(one(t.z, a.z), one(t.w, a.w));
+    }
+    for (uint64_t i = (n4 << 2) + first; i < n; i += stride) words[i] = one(key[i], v[i]);
+}
+
+// Undefined plane, and the scan found a bin it had to split (k_fill_if's role for the packed plane): zero it after all.
+__global__ void __launch_bounds__(256) k_zero_if(const unsigned* __restrict__ n_items, unsigned long long* __restrict__ packed, int64_t cells2) {
+    if (n_items[1] == 0u) return;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cells2; i += stride)
+        reinterpret_cast<ulonglong2*>(packed)[i] = make_ulonglong2(0ull, 0ull);
+}
+
+void launch_select(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, unsigned long long* packed, const BinBuffers& bb,
+                   const float* v, const float* key, uint64_t n) {
+    auto* words = static_cast<unsigned long long*>(bb.extra);
+    {
+        ScopedKernelTimer t(e, "k_select_words");
+        const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)8 * e->num_cus));
+        if (((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(key)) & 15) == 0)
+            hipLaunchKernelGGL(k_select_words<true>, dim3(blocks), dim3(256), 0, e->stream, v, key, words, n);
+        else
+            hipLaunchKernelGGL(k_select_words<false>, dim3(blocks), dim3(256), 0, e->stream, v, key, words, n);
+    }
+    ScopedKernelTimer t(e, "k_tile_select");
+    const size_t lds = (size_t)b.tile_w * b.tile_h * sizeof(unsigned long long);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_tile_select, dim3(bb.max_items), dim3(kThreads), lds, e->stream, gd, b, packed, bb.records, bb.items,
+                       bb.n_items, e->planes_fresh, (const unsigned long long*)words);
+}
+
 inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
 }  // namespace
@@ -804,7 +932,8 @@ inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 namespace pcrhip {
 
 int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const double* x, const double* y, const float* v,
-               uint64_t n, RecordKind kind, const GlyphDev* gl, unsigned item_records, BinBuffers* out, bool every_bin) {
+               uint64_t n, RecordKind kind, const GlyphDev* gl, unsigned item_records, BinBuffers* out, bool every_bin,
+               size_t extra_bytes) {
     const int max_items = b.nbins + (int)(n / item_records) + 1;
     const size_t rec_bytes = sizeof(uint2);
 
@@ -820,6 +949,7 @@ int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const dou
     const size_t o_items = off;  off += align256((size_t)max_items * sizeof(BinItem));
     const size_t o_rec = off;    off += align256((size_t)n * rec_bytes);
     const size_t o_keys = off;   off += align256((size_t)n * sizeof(unsigned));
+    const size_t o_extra = off;  off += align256(extra_bytes);
     int rc = ensure_scratch(e, off);
     if (rc) return rc;
     char* s = e->d_scratch;
@@ -866,6 +996,7 @@ int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const dou
     out->items = d_items;
     out->n_items = d_nitems;
     out->max_items = max_items;
+    out->extra = extra_bytes ? s + o_extra : nullptr;
     return PCR_HIP_OK;
 }
 
@@ -882,7 +1013,8 @@ int two_level_shift(const pcr_hip_engine* e, int tiles) {
 }
 
 int bin_points_two_level(pcr_hip_engine* e, const BinGeom& tiles, const double* x, const double* y, const float* v,
-                         uint64_t n, bool index_records, unsigned item_records, BinBuffers* out, bool every_bin) {
+                         uint64_t n, bool index_records, unsigned item_records, BinBuffers* out, bool every_bin,
+                         size_t extra_bytes) {
     BinGeom l1 = tiles;                                                   // first level: groups of tiles
     l1.nbins = (tiles.nbins + (1 << tiles.sup_shift) - 1) >> tiles.sup_shift;
     const ScatterShape sh1 = scatter_shape(l1.nbins);
@@ -901,6 +1033,7 @@ int bin_points_two_level(pcr_hip_engine* e, const BinGeom& tiles, const double* 
     const size_t o_count2 = carve((size_t)tiles.nbins * 4), o_cursor2 = carve((size_t)tiles.nbins * 4), o_nitems2 = carve(8);
     const size_t o_items2 = carve((size_t)max_items2 * sizeof(BinItem));
     const size_t o_keys = carve((size_t)n * 4), o_rec1 = carve((size_t)n * 8), o_rec2 = carve((size_t)n * 8);
+    const size_t o_extra = carve(extra_bytes);
     int rc = ensure_scratch(e, off);
     if (rc) return rc;
     char* s = e->d_scratch;
@@ -957,6 +1090,7 @@ int bin_points_two_level(pcr_hip_engine* e, const BinGeom& tiles, const double* 
     out->items = d_items2;
     out->n_items = U(o_nitems2);
     out->max_items = max_items2;
+    out->extra = extra_bytes ? s + o_extra : nullptr;
     return PCR_HIP_OK;
 }
 
@@ -1051,6 +1185,61 @@ int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
 #undef PCR_ACC
             default: return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_point: empty plane mask");
         }
+    }
+    PCR_HIP_TRY(hipGetLastError());
+    e->stats.path = 1;
+    e->stats.lds_tile_w = b.tile_w;
+    e->stats.lds_tile_h = b.tile_h;
+    e->stats.lds_apron = 0;
+    e->stats.num_bins = total_bins;
+    return PCR_HIP_OK;
+}
+
+bool binned_select_supported(const pcr_hip_engine* e) { return binned_point_supported(e, kSelectGeomMask); }
+
+// pcr_hip_scatter_select on the binned path: binned_point's structure (one level / two sort levels / row bands, the same
+// limits) on Index records, with k_tile_select as the tile pass.
+int binned_select(pcr_hip_engine* e, unsigned long long* packed, const double* x, const double* y, const float* v,
+                  const float* key, uint64_t n) {
+    int band_rows = 0;
+    int nbands = point_bands(e, kSelectGeomMask, &band_rows);
+    int total_bins = 0;
+    BinGeom b = point_bin_geom(e->gd, kSelectGeomMask, 0, e->gd.st_rows);
+    const int shift = nbands != 1 ? two_level_shift(e, b.nbins) : 0;
+    const int64_t cells = (int64_t)e->gd.st_rows * e->gd.W;
+    // undefined plane: one band of bins over the whole window lets the tile pass store every word itself (16-byte groups)
+    const bool define_all = e->planes_fresh == 2 && (nbands == 1 || shift > 0) && cells % 2 == 0 && e->gd.W % 2 == 0 &&
+                            (reinterpret_cast<uintptr_t>(packed) & 15) == 0;
+    if (e->planes_fresh == 2 && !define_all) {
+        ScopedKernelTimer t(e, "k_state_init");
+        PCR_HIP_TRY(hipMemsetAsync(packed, 0, (size_t)cells * sizeof(unsigned long long), e->stream));
+        e->planes_fresh = 1;
+    }
+    if (shift > 0) {                                            // one sweep, two sort levels
+        b.sup_shift = shift;
+        BinBuffers bb{};
+        int rc = bin_points_two_level(e, b, x, y, nullptr, n, true, kPointItemRecords, &bb, define_all, (size_t)n * 8);
+        if (rc) return rc;
+        if (define_all) hipLaunchKernelGGL(k_zero_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, packed, cells / 2);
+        launch_select(e, e->gd, b, packed, bb, v, key, n);
+        total_bins = b.nbins;
+        nbands = 0;
+    } else if (nbands < 1) {
+        return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_select: grid cannot be binned");
+    }
+    for (int band = 0; band < nbands; ++band) {
+        const int row0 = band * band_rows, rows = std::min(band_rows, e->gd.st_rows - row0);
+        GridDev gd = e->gd;                                     // this band's points only
+        gd.own_r0 = std::max(e->gd.own_r0, e->gd.st_r0 + row0);
+        gd.own_r1 = std::min(e->gd.own_r1, e->gd.st_r0 + row0 + rows);
+        if (gd.own_r0 >= gd.own_r1) continue;
+        b = point_bin_geom(e->gd, kSelectGeomMask, row0, rows);
+        total_bins += b.nbins;
+        BinBuffers bb{};
+        int rc = bin_points(e, gd, b, x, y, nullptr, n, RecordKind::Index, nullptr, kPointItemRecords, &bb, define_all, (size_t)n * 8);
+        if (rc) return rc;
+        if (define_all) hipLaunchKernelGGL(k_zero_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, packed, cells / 2);
+        launch_select(e, gd, b, packed, bb, v, key, n);
     }
     PCR_HIP_TRY(hipGetLastError());
     e->stats.path = 1;

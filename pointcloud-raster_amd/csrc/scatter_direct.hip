@@ -53,6 +53,32 @@ k_point_direct(GridDev g, PlanesDev pl, const double* __restrict__ x, const doub
     }
 }
 
+// ---- MostRecent (Point glyph): one 64-bit atomic max per accepted point (common.hpp: select_word) ----
+// x / y / value / key are read once, coalesced (24 B/point); the cell's word only ever grows, so the order of the atomics
+// does not matter and a cell's final word is the maximum of its points' words (global_atomic_umax_x2, no return value).
+__global__ void __launch_bounds__(kBlock)
+k_select_direct(GridDev g, unsigned long long* __restrict__ packed, const double* __restrict__ x, const double* __restrict__ y,
+                const float* __restrict__ v, const float* __restrict__ key, uint64_t n, uint32_t* __restrict__ touched,
+                unsigned long long* __restrict__ counters) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint64_t n_round = ((n + 63) / 64) * 64;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n_round; i += stride) {
+        bool valid = false;
+        int col = 0, row = 0;
+        if (i < n) {
+            valid = point_kept(g, i) && world_to_cell(g, x[i], y[i], col, row);
+            valid = valid && row >= g.own_r0 && row < g.own_r1;
+        }
+        if (valid) {
+            // a point whose key is refused still lies in its tile: the tile has state (touched), the cell stays empty
+            const float t = key[i];
+            if (select_accepts(t)) atomicMax(packed + ((int64_t)(row - g.st_r0) * g.W + col), select_word(t, v[i]));
+            touch_tile(g, touched, row, col);
+        }
+        count_valid(counters, valid);
+    }
+}
+
 // ---- Glyph sinks -------------------------------------------------------------------
 template <unsigned MASK>
 struct GlobalSink {
@@ -160,6 +186,17 @@ int direct_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
         PCR_DISPATCH_POINT_MASK(13) PCR_DISPATCH_POINT_MASK(14) PCR_DISPATCH_POINT_MASK(15)
         default: return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_point: empty plane mask");
     }
+    PCR_HIP_TRY(hipGetLastError());
+    e->stats.path = 0;
+    return PCR_HIP_OK;
+}
+
+int direct_select(pcr_hip_engine* e, unsigned long long* packed, const double* x, const double* y, const float* v,
+                  const float* key, uint64_t n) {
+    const int blocks = blocks_for(n, 8, e->num_cus);
+    ScopedKernelTimer t(e, "k_select_direct");
+    hipLaunchKernelGGL(k_select_direct, dim3(blocks), dim3(kBlock), 0, e->stream, e->gd, packed, x, y, v, key, n, e->d_touched,
+                       e->d_counters);
     PCR_HIP_TRY(hipGetLastError());
     e->stats.path = 0;
     return PCR_HIP_OK;

@@ -171,6 +171,101 @@ k_finalize_group(GridDev g, PlanesDev pl, unsigned need, const uint32_t* __restr
     }
 }
 
+// ---- MostRecent: packed words <-> the reference's {value, timestamp} float planes (common.hpp: select_word) ------------
+__global__ void __launch_bounds__(kBlock)
+k_select_pack(const float* __restrict__ value, const float* __restrict__ key, unsigned long long* __restrict__ packed, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const float t = key[i];
+        packed[i] = select_accepts(t) ? select_word(t, value[i]) : 0ull;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_select_unpack(const unsigned long long* __restrict__ packed, float* __restrict__ value, float* __restrict__ key, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const unsigned long long w = packed[i];
+        value[i] = w ? select_value(w) : __uint_as_float(kSelectEmptyValueBits);
+        key[i] = w ? select_key(w) : -FLT_MAX;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_select_init(float* __restrict__ value, float* __restrict__ key, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        value[i] = __uint_as_float(kSelectEmptyValueBits);
+        key[i] = -FLT_MAX;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_select_merge(unsigned long long* __restrict__ d, const unsigned long long* __restrict__ s, int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int64_t n2 = n >> 1;
+    ulonglong2* d2 = reinterpret_cast<ulonglong2*>(d);
+    const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(s);
+    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n2; j += stride) {
+        ulonglong2 a = d2[j];
+        const ulonglong2 b = s2[j];
+        a.x = a.x > b.x ? a.x : b.x;
+        a.y = a.y > b.y ? a.y : b.y;
+        d2[j] = a;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) d[n - 1] = d[n - 1] > s[n - 1] ? d[n - 1] : s[n - 1];
+}
+
+// merge_tile_state of MostRecent on the float-plane layout (MostRecentOp::merge with this build's total order on ties)
+__global__ void __launch_bounds__(kBlock)
+k_select_merge_planes(float* __restrict__ dv, float* __restrict__ dk, const float* __restrict__ sv, const float* __restrict__ sk,
+                      int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const float ta = dk[i], tb = sk[i];
+        const unsigned long long a = select_accepts(ta) ? select_word(ta, dv[i]) : 0ull;
+        const unsigned long long b = select_accepts(tb) ? select_word(tb, sv[i]) : 0ull;
+        const unsigned long long w = a > b ? a : b;
+        dv[i] = w ? select_value(w) : __uint_as_float(kSelectEmptyValueBits);
+        dk[i] = w ? select_key(w) : -FLT_MAX;
+    }
+}
+
+// One thread = VEC consecutive cells of one row (VEC = 2: 16-byte loads of the words).
+template <int VEC>
+__global__ void __launch_bounds__(kBlock)
+k_finalize_select(GridDev g, const unsigned long long* __restrict__ packed, const uint32_t* __restrict__ touched,
+                  float* __restrict__ out) {
+    const int rows = g.own_r1 - g.own_r0;
+    const int per_row = g.W / VEC;
+    const int64_t items = (int64_t)rows * per_row;
+    const bool one_tile = (g.tiles_x * g.tiles_y == 1);
+    const bool all_touched = (touched == nullptr) || (one_tile && touched[0] != 0u);
+    const bool none_touched = (touched != nullptr) && one_tile && touched[0] == 0u;
+    for (int64_t it = (int64_t)blockIdx.x * kBlock + threadIdx.x; it < items; it += (int64_t)gridDim.x * kBlock) {
+        const int r = (int)(it / per_row);
+        const int c = (int)(it - (int64_t)r * per_row) * VEC;
+        const int row = g.own_r0 + r;
+        const int64_t si = (int64_t)(row - g.st_r0) * g.W + c;
+        const int64_t oi = (int64_t)r * g.W + c;
+        unsigned long long w[VEC];
+        if (VEC == 2) {
+            const ulonglong2 t = *reinterpret_cast<const ulonglong2*>(packed + si);
+            w[0] = t.x;
+            w[VEC - 1] = t.y;
+        } else {
+            w[0] = packed[si];
+        }
+        float v[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const bool live = all_touched || (!none_touched && touched[(row / g.th) * g.tiles_x + (c + k) / g.tw] != 0u);
+            v[k] = live && w[k] ? select_value(w[k]) : NAN;
+        }
+        if (VEC == 2) *reinterpret_cast<float2*>(out + oi) = make_float2(v[0], v[VEC - 1]);
+        else out[oi] = v[0];
+    }
+}
+
 // FilterSpec evaluation: AND of predicates (evaluate_predicate, src/engine/filter.cpp:34-56).
 struct PredSet {
     int n;
@@ -254,6 +349,7 @@ int pcr_hip_state_floats(int rtype, int* k) {
     switch (rtype) {
         case PCR_HIP_SUM: case PCR_HIP_MAX: case PCR_HIP_MIN: case PCR_HIP_COUNT: *k = 1; return PCR_HIP_OK;
         case PCR_HIP_AVERAGE: case PCR_HIP_WEIGHTED_AVERAGE: *k = 2; return PCR_HIP_OK;
+        case PCR_HIP_MOST_RECENT: *k = 2; return PCR_HIP_OK;                   // {value, timestamp}, builtin_ops.h:178-183
         default: *k = 0; return fail(PCR_HIP_INVALID_ARGUMENT, "pipeline: unknown reduction type");
     }
 }
@@ -277,6 +373,14 @@ int pcr_hip_state_init(int rtype, float* d_state, int64_t cells, pcr_hip_stream 
     int k = 0;
     int rc = pcr_hip_state_floats(rtype, &k);
     if (rc) return rc;
+    if (rtype == PCR_HIP_MOST_RECENT) {                                        // MostRecentOp::identity: {NaN, -FLT_MAX}
+        if (cells <= 0) return PCR_HIP_OK;
+        PCR_REQUIRE(d_state, "state_init: null state");
+        hipLaunchKernelGGL(k_select_init, dim3(grid_for(cells)), dim3(kBlock), 0, static_cast<hipStream_t>(s), d_state,
+                           d_state + cells, cells);
+        PCR_HIP_TRY(hipGetLastError());
+        return PCR_HIP_OK;
+    }
     float id = rtype == PCR_HIP_MAX ? -FLT_MAX : rtype == PCR_HIP_MIN ? FLT_MAX : 0.0f;
     return pcr_hip_plane_fill(d_state, id, (int64_t)k * cells, s);
 }
@@ -285,8 +389,66 @@ int pcr_hip_state_merge(int rtype, float* d_dst, const float* d_src, int64_t cel
     int k = 0;
     int rc = pcr_hip_state_floats(rtype, &k);
     if (rc) return rc;
+    if (rtype == PCR_HIP_MOST_RECENT) {
+        if (cells <= 0) return PCR_HIP_OK;
+        PCR_REQUIRE(d_dst && d_src, "merge: null plane");
+        hipLaunchKernelGGL(k_select_merge_planes, dim3(grid_for(cells)), dim3(kBlock), 0, static_cast<hipStream_t>(s), d_dst,
+                           d_dst + cells, d_src, d_src + cells, cells);
+        PCR_HIP_TRY(hipGetLastError());
+        return PCR_HIP_OK;
+    }
     int kind = rtype == PCR_HIP_MAX ? 1 : rtype == PCR_HIP_MIN ? 2 : 0;
     return merge_kind(kind, d_dst, d_src, (int64_t)k * cells, static_cast<hipStream_t>(s));
+}
+
+int pcr_hip_select_pack(const float* d_value, const float* d_key, uint64_t* d_packed, int64_t cells, pcr_hip_stream s) {
+    if (cells <= 0) return PCR_HIP_OK;
+    PCR_REQUIRE(d_value && d_key && d_packed, "select_pack: null plane");
+    PCR_REQUIRE((reinterpret_cast<uintptr_t>(d_packed) & 7) == 0, "select_pack: the packed plane must be 8-byte aligned");
+    hipLaunchKernelGGL(k_select_pack, dim3(grid_for(cells)), dim3(kBlock), 0, static_cast<hipStream_t>(s), d_value, d_key,
+                       reinterpret_cast<unsigned long long*>(d_packed), cells);
+    PCR_HIP_TRY(hipGetLastError());
+    return PCR_HIP_OK;
+}
+
+int pcr_hip_select_unpack(const uint64_t* d_packed, float* d_value, float* d_key, int64_t cells, pcr_hip_stream s) {
+    if (cells <= 0) return PCR_HIP_OK;
+    PCR_REQUIRE(d_value && d_key && d_packed, "select_unpack: null plane");
+    PCR_REQUIRE((reinterpret_cast<uintptr_t>(d_packed) & 7) == 0, "select_unpack: the packed plane must be 8-byte aligned");
+    hipLaunchKernelGGL(k_select_unpack, dim3(grid_for(cells)), dim3(kBlock), 0, static_cast<hipStream_t>(s),
+                       reinterpret_cast<const unsigned long long*>(d_packed), d_value, d_key, cells);
+    PCR_HIP_TRY(hipGetLastError());
+    return PCR_HIP_OK;
+}
+
+int pcr_hip_select_merge(uint64_t* d_dst, const uint64_t* d_src, int64_t cells, pcr_hip_stream s) {
+    if (cells <= 0) return PCR_HIP_OK;
+    PCR_REQUIRE(d_dst && d_src, "select_merge: null plane");
+    PCR_REQUIRE(((reinterpret_cast<uintptr_t>(d_dst) | reinterpret_cast<uintptr_t>(d_src)) & 15) == 0,
+                "select_merge: planes must be 16-byte aligned");
+    hipLaunchKernelGGL(k_select_merge, dim3(grid_for((cells + 1) / 2)), dim3(kBlock), 0, static_cast<hipStream_t>(s),
+                       reinterpret_cast<unsigned long long*>(d_dst), reinterpret_cast<const unsigned long long*>(d_src), cells);
+    PCR_HIP_TRY(hipGetLastError());
+    return PCR_HIP_OK;
+}
+
+int pcr_hip_finalize_select(const pcr_hip_grid* g, const uint64_t* d_packed, const uint32_t* d_tile_touched, float* d_out,
+                            pcr_hip_stream s) {
+    int rc = validate_grid(g);
+    if (rc) return rc;
+    PCR_REQUIRE(d_packed && d_out, "finalize_select: null argument");
+    PCR_REQUIRE((reinterpret_cast<uintptr_t>(d_packed) & 7) == 0, "finalize_select: the packed plane must be 8-byte aligned");
+    const GridDev gd = make_grid_dev(*g);
+    const int rows = gd.own_r1 - gd.own_r0;
+    if (rows <= 0) return PCR_HIP_OK;
+    const auto* pk = reinterpret_cast<const unsigned long long*>(d_packed);
+    const bool vec = gd.W % 2 == 0 && (reinterpret_cast<uintptr_t>(d_packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 7) == 0;
+    if (vec) hipLaunchKernelGGL(k_finalize_select<2>, dim3(grid_for((int64_t)rows * (gd.W / 2))), dim3(kBlock), 0,
+                                static_cast<hipStream_t>(s), gd, pk, d_tile_touched, d_out);
+    else hipLaunchKernelGGL(k_finalize_select<1>, dim3(grid_for((int64_t)rows * gd.W)), dim3(kBlock), 0,
+                            static_cast<hipStream_t>(s), gd, pk, d_tile_touched, d_out);
+    PCR_HIP_TRY(hipGetLastError());
+    return PCR_HIP_OK;
 }
 
 int pcr_hip_plane_merge(uint32_t plane_kind, float* d_dst, const float* d_src, int64_t cells, pcr_hip_stream s) {

@@ -27,6 +27,9 @@ struct ReductionSpec {
     std::string value_channel;
     ReductionType type = ReductionType::Sum;
     std::string weight_channel;        // declared; WeightedAverage uses weight 1 with the Point glyph (reference behaviour)
+    // MostRecent (Point glyph only): the Float32 channel whose greatest value picks the cell's point -- "newest survey wins".
+    // Points with a NaN or <= -FLT_MAX timestamp are ignored; among equal timestamps the greater value wins, so the result
+    // does not depend on the order, the engine or the split of the points.  Required for MostRecent, unused otherwise.
     std::string timestamp_channel;
     float percentile = 0.5f;
     std::string output_band_name;      // default "{value_channel}_{int(type)}"
@@ -137,7 +140,8 @@ public:
     //      e.g. torch.distributed over RCCL: see pcr/distributed.py) -------------------------
     struct PlaneView {
         void* device_ptr;      // first float of the plane (row state_row_begin)
-        int plane_kind;        // PCR_HIP_PLANE_* of include/pcr_hip.h
+        int plane_kind;        // PCR_HIP_PLANE_* of include/pcr_hip.h (a MostRecent group: a read-only snapshot of its value /
+                               // timestamp planes in the SUM / WGT slots, refreshed by every state_planes() call)
         int group;             // accumulation group index
         int reach_rows;        // rows the group's glyph can reach beyond a point's centre row (0: Point glyph -- its halo
                                // rows never receive anything and need no exchange)

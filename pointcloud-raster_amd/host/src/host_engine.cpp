@@ -1,6 +1,8 @@
 // host_engine.cpp -- see host_engine.h.  Arithmetic after the reference's CPU path, cited at each step; structure ours.
 #include "host_engine.h"
 
+#include "pipeline_common.h"
+
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -137,10 +139,12 @@ HostEngine::HostEngine(const GridConfig& grid, int threads) : g_(grid) {
     touched_.assign((size_t)tiles_x_ * tiles_y_, 0u);
 }
 
-void HostEngine::init_planes(HostPlanes& p, uint32_t mask) const {
+void HostEngine::init_planes(HostPlanes& p, uint32_t mask, bool select) const {
     p.mask = mask;
+    p.select = select;
     const size_t cells = (size_t)W_ * H_;
-    const float ident[4] = {0.0f, 0.0f, -FLT_MAX, FLT_MAX};            // builtin_ops.h: identity() of Sum / Count / Max / Min
+    // builtin_ops.h: identity() of Sum / Count / Max / Min; MostRecent {NaN, -FLT_MAX}
+    const float ident[4] = {plane_identity(select, 0), plane_identity(select, 1), plane_identity(select, 2), plane_identity(select, 3)};
     for (int k = 0; k < 4; ++k) {
         if (!(mask & (1u << k))) { std::vector<float>().swap(p.plane[k]); continue; }
         p.plane[k].resize(cells);
@@ -253,6 +257,37 @@ void HostEngine::scatter_point(HostPlanes& p, const float* v) {
     }
 }
 
+void HostEngine::scatter_select(HostPlanes& p, const float* v, const float* key) {
+    if (n_ == 0 || !v || !key) return;
+    std::vector<uint32_t> list;
+    std::vector<size_t> first;
+    build_lists(list, first, [&](size_t i, Span& sp) {
+        if (row_[i] < 0 || !select_accepts(key[i])) return false;
+        sp.lo = sp.hi = row_[i];
+        return true;
+    });
+    float* val = p.plane[0].data();
+    float* ts = p.plane[1].data();
+#pragma omp parallel for num_threads(threads_) schedule(dynamic, 1)
+    for (int s = 0; s < nstripes_; ++s) {
+        for (size_t k = first[(size_t)s]; k < first[(size_t)s + 1]; ++k) {
+            const uint32_t i = list[k];
+            const size_t cell = (size_t)row_[i] * W_ + (size_t)col_[i];
+            const uint64_t w = select_word(key[i], v[i]);
+            if (w > select_word_of_state(val[cell], ts[cell])) select_state_of_word(w, &val[cell], &ts[cell]);
+        }
+    }
+}
+
+void HostEngine::normalize_select(HostPlanes& p) const {
+    if (!p.select || p.plane[0].empty() || p.plane[1].empty()) return;
+    float* val = p.plane[0].data();
+    float* ts = p.plane[1].data();
+    const int64_t cells = (int64_t)W_ * H_;
+#pragma omp parallel for num_threads(threads_) schedule(static)
+    for (int64_t i = 0; i < cells; ++i) select_state_of_word(select_word_of_state(val[i], ts[i]), &val[i], &ts[i]);
+}
+
 void HostEngine::scatter_glyph(HostPlanes& p, const GlyphSpec& glyph, const HostGlyphArrays& arr, const float* v) {
     if (n_ == 0) return;
     float* sum = (p.mask & 1u) ? p.plane[0].data() : nullptr;
@@ -359,6 +394,9 @@ void HostEngine::finalize(const HostPlanes& p, ReductionType type, float* band) 
                     case ReductionType::Average:
                     case ReductionType::WeightedAverage:
                         out = sum && wgt && wgt[cell] > 0.0f ? sum[cell] / wgt[cell] : nan;
+                        break;
+                    case ReductionType::MostRecent:                  // plane 0 = value, plane 1 = timestamp
+                        out = p.select && sum && wgt && select_accepts(wgt[cell]) ? sum[cell] : nan;
                         break;
                     default: break;
                 }

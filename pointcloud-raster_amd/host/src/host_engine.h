@@ -27,8 +27,11 @@ namespace pcr {
 namespace detail {
 
 // plane order as on the device: 0 = sum (of v * w), 1 = weight (of w), 2 = max, 3 = min; bit p of `mask` = plane p exists
+// select: a MostRecent group -- plane 0 = value, plane 1 = timestamp (the reference's state layout, builtin_ops.h:178-183),
+// an empty cell {NaN, -FLT_MAX}
 struct HostPlanes {
     uint32_t mask = 0;
+    bool select = false;
     std::vector<float> plane[4];
 };
 
@@ -45,13 +48,19 @@ public:
     HostEngine(const GridConfig& grid, int threads);
 
     int threads() const { return threads_; }
-    /// Identity into the planes `mask` names (0 / 0 / -FLT_MAX / FLT_MAX), whole grid.
-    void init_planes(HostPlanes& p, uint32_t mask) const;
+    /// Identity into the planes `mask` names (0 / 0 / -FLT_MAX / FLT_MAX; select: NaN / -FLT_MAX), whole grid.
+    void init_planes(HostPlanes& p, uint32_t mask, bool select = false) const;
 
     /// Routes one cloud (at most 2^31 points): cell of every point, touched tiles.  keep[i] == 0: point i does not exist
     /// (the filter stage); keep may be null.  Returns the points inside the grid.  The scatter calls below fold THIS cloud.
     size_t route(const double* x, const double* y, const uint8_t* keep, size_t n);
     void scatter_point(HostPlanes& p, const float* v);
+    /// MostRecent: per stripe, the maximum word(key, v) of the accepted points of every cell (include/pcr_hip.h); the same
+    /// bits as the HIP engine whatever the thread count -- the fold is commutative and idempotent.
+    void scatter_select(HostPlanes& p, const float* v, const float* key);
+    /// A select group's planes as a checkpoint left them -> the canonical form a fold leaves (a NaN or <= -FLT_MAX timestamp
+    /// means empty: {NaN, -FLT_MAX}; a -0.0 timestamp is +0.0).
+    void normalize_select(HostPlanes& p) const;
     /// Planes 0 / 1 only (glyph reductions are Sum, Count, Average, WeightedAverage).
     void scatter_glyph(HostPlanes& p, const GlyphSpec& glyph, const HostGlyphArrays& arr, const float* v);
 

@@ -20,8 +20,10 @@ Status Pipeline::Host::init() {
         return Status::error(StatusCode::InvalidArgument, "pipeline: grid dimensions must be positive");
     if (g.tile_width <= 0 || g.tile_height <= 0)
         return Status::error(StatusCode::InvalidArgument, "pipeline: tile dimensions must be positive");
-    for (const auto& r : cfg.reductions)
-        if (!registered(r.type)) return Status::error(StatusCode::InvalidArgument, "pipeline: unknown reduction type");
+    {
+        Status ok = detail::check_reduction_specs(cfg.reductions);
+        if (!ok.ok()) return ok;
+    }
     if (cfg.shard_row_begin >= 0 || cfg.shard_row_end >= 0)
         return Status::error(StatusCode::InvalidArgument, "pipeline: row-block shards run on the GPU engine only (one process per GPU)");
     if (cfg.result_location == MemoryLocation::Device)
@@ -30,12 +32,16 @@ Status Pipeline::Host::init() {
     for (const auto& r : cfg.reductions) {
         int gi = -1;
         for (size_t k = 0; k < groups.size(); ++k)
-            if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph)) gi = (int)k;
+            if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph) &&
+                groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel))
+                gi = (int)k;                                         // (detail::same_group)
         if (gi < 0) {
             groups.emplace_back();
             gi = (int)groups.size() - 1;
             groups[(size_t)gi].value_channel = r.value_channel;
             groups[(size_t)gi].glyph = r.glyph;
+            groups[(size_t)gi].select = detail::is_select(r.type);
+            if (groups[(size_t)gi].select) groups[(size_t)gi].key_channel = r.timestamp_channel;
         }
         groups[(size_t)gi].mask |= planes_for(r.type);
         Output o;
@@ -45,7 +51,7 @@ Status Pipeline::Host::init() {
         outputs.push_back(o);
     }
     // Tile state is identity-initialised (src/engine/tile_manager.cpp:183-260); here for the whole grid at once.
-    for (auto& gr : groups) engine->init_planes(gr.planes, gr.mask);
+    for (auto& gr : groups) engine->init_planes(gr.planes, gr.mask, gr.select);
     return Status::success();
 }
 
@@ -132,7 +138,9 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         valid += engine->route(px + i0, py + i0, keep.empty() ? nullptr : keep.data() + i0, m);
         for (auto& gr : groups) {
             const float* v = f32(gr.value_channel);
-            if (gr.glyph.type == GlyphType::Point) {
+            if (gr.select) {                                         // (Point glyph: validate_cloud refused anything else)
+                engine->scatter_select(gr.planes, v + i0, f32(gr.key_channel) + i0);
+            } else if (gr.glyph.type == GlyphType::Point) {
                 engine->scatter_point(gr.planes, v + i0);
             } else {
                 detail::HostGlyphArrays arr;
@@ -208,7 +216,9 @@ Status Pipeline::Host::load_state(const std::string& dir_in) {
     w.row0 = 0;
     w.rows = cfg.grid.height;
     w.plane = [&](int g, int p) -> float* { auto& v = groups[(size_t)g].planes.plane[p]; return v.empty() ? nullptr : v.data(); };
-    return detail::read_state_tiles(cfg.grid, state_outputs(), w, engine->touched(), dir, nullptr);
+    Status s = detail::read_state_tiles(cfg.grid, state_outputs(), w, engine->touched(), dir, nullptr);
+    for (auto& gr : groups) engine->normalize_select(gr.planes);     // a state read from a file is judged by the acceptance rule again
+    return s;
 }
 
 ProgressInfo Pipeline::Host::stats() const {

@@ -18,6 +18,8 @@ namespace pcr {
 struct Pipeline::Host {
     struct Group {                       // one pass over the points: same grouping as the HIP pipeline
         std::string value_channel;
+        std::string key_channel;         // a MostRecent group: its timestamp channel
+        bool select = false;
         GlyphSpec glyph;
         detail::HostPlanes planes;
         uint32_t mask = 0;

@@ -57,6 +57,13 @@ struct Pipeline::Impl {
         uint32_t mask = 0;
         detail::Buffer planes[4];
         pcr_hip_planes view{};
+        // A MostRecent group (detail::is_select): its state on the device is ONE plane of packed 64-bit words (`packed`, 8 B per
+        // cell, include/pcr_hip.h "MostRecent").  mask names slots 0 / 1, the two float planes (value, timestamp) the state is
+        // at the host-visible boundary: planes[0] / planes[1] only exist while a checkpoint, a parked band or a shard's
+        // state_planes() needs that view (select_unpack / select_pack).
+        bool select = false;
+        std::string key_channel;
+        detail::Buffer packed;
         bool fresh = true;               // nothing has been accumulated yet: the first Point merge may store
         bool defined = false;            // the planes hold values (identity or accumulated).  They are NOT filled at create:
                                          // the first scatter defines them inside ingest, as the reference initialises its tile
@@ -113,6 +120,7 @@ struct Pipeline::Impl {
     // tile's state, src/engine/pipeline.cpp:1154-1286).
     bool offer_bands(size_t gi) {
         const Group& gr = groups[gi];
+        if (gr.select) return false;                   // (its tile pass stores no bands: finalize_select always runs)
         if (!cfg.finalize_with_first_ingest || gr.defined || gr.glyph.type != GlyphType::Point || state_shared || !result ||
             !d_bands_done.data()) return false;
         if (hg.own_row0 != hg.state_row0 || own_rows() != hg.state_rows || own_rows() <= 0) return false;
@@ -135,9 +143,10 @@ struct Pipeline::Impl {
             return Status::error(StatusCode::InvalidArgument, "pipeline: grid dimensions must be positive");
         if (g.tile_width <= 0 || g.tile_height <= 0)
             return Status::error(StatusCode::InvalidArgument, "pipeline: tile dimensions must be positive");
-        for (const auto& r : cfg.reductions)
-            if (!registered(r.type))
-                return Status::error(StatusCode::InvalidArgument, "pipeline: unknown reduction type");
+        {
+            Status ok = detail::check_reduction_specs(cfg.reductions);
+            if (!ok.ok()) return ok;
+        }
 
         // The reference's GPU-initialisation matrix (src/engine/pipeline.cpp:108-162), with its exact messages and status
         // codes.  Where the reference goes on in CPU mode it prints a Warning / Info line on stderr first; so does this build,
@@ -207,12 +216,16 @@ struct Pipeline::Impl {
         for (const auto& r : cfg.reductions) {
             int gi = -1;
             for (size_t k = 0; k < groups.size(); ++k)
-                if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph)) gi = (int)k;
+                if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph) &&
+                    groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel))
+                    gi = (int)k;                                 // (detail::same_group)
             if (gi < 0) {
                 groups.emplace_back();
                 gi = (int)groups.size() - 1;
                 groups[gi].value_channel = r.value_channel;
                 groups[gi].glyph = r.glyph;
+                groups[gi].select = detail::is_select(r.type);
+                if (groups[gi].select) groups[gi].key_channel = r.timestamp_channel;
             }
             // a glyph reduction of an unsupported type is rejected at ingest (as in the reference);
             // it still gets planes so that finalize has something to read.
@@ -265,6 +278,11 @@ struct Pipeline::Impl {
 
         const int64_t cells = (int64_t)hg.state_rows * hg.width;
         for (auto& gr : groups) {
+            if (gr.select) {
+                s = gr.packed.allocate((size_t)std::max<int64_t>(cells, 1) * sizeof(uint64_t), MemoryLocation::Device);
+                if (!s.ok()) return s;
+                continue;
+            }
             for (int p = 0; p < 4; ++p) {
                 if (!(gr.mask & kPlaneBits[p])) continue;
                 s = gr.planes[p].allocate((size_t)std::max<int64_t>(cells, 1) * sizeof(float), MemoryLocation::Device);
@@ -285,6 +303,12 @@ struct Pipeline::Impl {
     Status define_planes(Group& gr) {
         if (gr.defined) return Status::success();
         const int64_t cells = (int64_t)hg.state_rows * hg.width;
+        if (gr.select) {                                 // the identity of the packed words is 0
+            Status s = detail::hip_status(pcr_hip_memset(gr.packed.data(), 0, (size_t)cells * sizeof(uint64_t), stream));
+            if (!s.ok()) return s;
+            gr.defined = true;
+            return Status::success();
+        }
         for (int p = 0; p < 4; ++p) {
             if (!(gr.mask & kPlaneBits[p])) continue;
             const float ident = p == 2 ? -3.402823466e+38f : p == 3 ? 3.402823466e+38f : 0.0f;
@@ -294,6 +318,38 @@ struct Pipeline::Impl {
         gr.defined = true;
         return Status::success();
     }
+    // A MostRecent group's float-plane view (slot 0 value, slot 1 timestamp), filled from the packed words: what leaves the
+    // pipeline (checkpoints, parked bands, state_planes()).  pack_select is the way back.  drop_select_views frees the view
+    // once the stream is done with it: between two such calls the group costs its 8 bytes per cell only.
+    Status unpack_select(Group& gr) {
+        if (!gr.select) return Status::success();
+        const int64_t cells = (int64_t)hg.state_rows * hg.width;
+        Status s = define_planes(gr);
+        if (!s.ok()) return s;
+        if (!(s = alloc_select_views(gr)).ok()) return s;
+        return detail::hip_status(pcr_hip_select_unpack(static_cast<const uint64_t*>(gr.packed.data()), static_cast<float*>(gr.planes[0].data()),
+                                                        static_cast<float*>(gr.planes[1].data()), cells, stream));
+    }
+    Status alloc_select_views(Group& gr) {
+        const int64_t cells = (int64_t)hg.state_rows * hg.width;
+        for (int p = 0; p < 2; ++p) {
+            if (gr.planes[p].data()) continue;
+            Status s = gr.planes[p].allocate((size_t)std::max<int64_t>(cells, 1) * sizeof(float), MemoryLocation::Device);
+            if (!s.ok()) return s;
+        }
+        return Status::success();
+    }
+    Status pack_select(Group& gr) {
+        if (!gr.select) return Status::success();
+        const int64_t cells = (int64_t)hg.state_rows * hg.width;
+        return detail::hip_status(pcr_hip_select_pack(static_cast<const float*>(gr.planes[0].data()), static_cast<const float*>(gr.planes[1].data()),
+                                                      static_cast<uint64_t*>(gr.packed.data()), cells, stream));
+    }
+    void drop_select_views() {                           // (call with the stream synchronized)
+        for (auto& gr : groups)
+            if (gr.select) { gr.planes[0].release(); gr.planes[1].release(); }
+    }
+
     Status define_all_planes() {
         for (auto& gr : groups) {
             Status s = define_planes(gr);
@@ -531,7 +587,13 @@ struct Pipeline::Impl {
             // 2: the planes are still undefined -- the scatter defines every cell of the state window itself (the binned
             // Point path at no extra pass, every other path by filling first); 1: identity-filled, nothing accumulated yet
             pcr_hip_engine_planes_fresh(engine, !gr.defined ? 2 : (gr.fresh && gr.glyph.type == GlyphType::Point ? 1 : 0));
-            if (gr.glyph.type == GlyphType::Point) {
+            if (gr.select) {                             // (Point glyph: validate_cloud refused anything else)
+                const void* dk = nullptr;
+                if (!(s = f32_channel(gr.key_channel, &dk)).ok()) return s;
+                s = detail::hip_status(pcr_hip_scatter_select(
+                    engine, static_cast<uint64_t*>(gr.packed.data()), static_cast<const double*>(dx), static_cast<const double*>(dy),
+                    static_cast<const float*>(dv), static_cast<const float*>(dk), n));
+            } else if (gr.glyph.type == GlyphType::Point) {
                 gr.fresh = false;
                 const bool offered = offer_bands(gi);
                 s = detail::hip_status(pcr_hip_scatter_point(
@@ -648,6 +710,13 @@ struct Pipeline::Impl {
             };
             for (size_t r = 0; r < outputs.size(); ++r) {
                 if (outputs[r].group != (int)gi) continue;
+                if (groups[gi].select) {
+                    s = detail::hip_status(pcr_hip_finalize_select(&hg, static_cast<const uint64_t*>(groups[gi].packed.data()), d_touched,
+                                                                   band_device(r), stream));
+                    if (!s.ok()) return s;
+                    bands_of.push_back(r);
+                    continue;
+                }
                 types.push_back(static_cast<int>(outputs[r].type));
                 dsts.push_back(band_device(r));
                 bands_of.push_back(r);
@@ -724,6 +793,8 @@ struct Pipeline::Impl {
         if (!s.ok()) return s;
         const size_t cells = (size_t)hg.state_rows * hg.width;
         planes.assign(groups.size() * 4, {});
+        for (auto& gr : groups)
+            if (!(s = unpack_select(gr)).ok()) return s;
         for (size_t gi = 0; gi < groups.size(); ++gi)
             for (int p = 0; p < 4; ++p) {
                 if (!(groups[gi].mask & kPlaneBits[p])) continue;
@@ -736,7 +807,9 @@ struct Pipeline::Impl {
         if (!(s = detail::hip_status(pcr_hip_engine_tile_touched(engine, &d_touched, &tx, &ty))).ok()) return s;
         touched.resize((size_t)tx * ty);
         if (!(s = detail::hip_status(pcr_hip_memcpy_d2h(touched.data(), d_touched, touched.size() * 4, stream))).ok()) return s;
-        return detail::hip_status(pcr_hip_stream_synchronize(stream));
+        s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+        if (!state_shared) drop_select_views();
+        return s;
     }
     Status import_window(const std::vector<std::vector<float>>& planes, const std::vector<uint32_t>& touched) {
         bands_stale();
@@ -746,6 +819,7 @@ struct Pipeline::Impl {
             return Status::error(StatusCode::InvalidArgument, "pipeline: parked state does not match the pipeline's groups");
         Status s = Status::success();
         for (size_t gi = 0; gi < groups.size(); ++gi) {
+            if (groups[gi].select && !(s = alloc_select_views(groups[gi])).ok()) return s;
             for (int p = 0; p < 4; ++p) {
                 if (!(groups[gi].mask & kPlaneBits[p])) continue;
                 if (planes[gi * 4 + p].size() != cells)
@@ -753,6 +827,8 @@ struct Pipeline::Impl {
                 s = detail::hip_status(pcr_hip_memcpy_h2d(groups[gi].planes[p].data(), planes[gi * 4 + p].data(), cells * sizeof(float), stream));
                 if (!s.ok()) return s;
             }
+            // (a state that comes from outside is judged by the acceptance rule again: a NaN or <= -FLT_MAX timestamp = empty)
+            if (groups[gi].select && !(s = pack_select(groups[gi])).ok()) return s;
             groups[gi].defined = true;
             groups[gi].fresh = false;
         }
@@ -762,7 +838,9 @@ struct Pipeline::Impl {
         if (touched.size() != (size_t)tx * ty)
             return Status::error(StatusCode::InvalidArgument, "pipeline: parked touched flags do not match the tile grid");
         if (!(s = detail::hip_status(pcr_hip_memcpy_h2d(d_touched, touched.data(), touched.size() * 4, stream))).ok()) return s;
-        return detail::hip_status(pcr_hip_stream_synchronize(stream));
+        s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+        if (!state_shared) drop_select_views();
+        return s;
     }
 
     std::vector<detail::StateOutput> state_outputs() const {
@@ -861,7 +939,8 @@ struct Pipeline::Banded {
         }
     }
 
-    // bytes of device memory one grid row costs: 4 B per cell and plane, + the finalized bands a sub-pipeline keeps
+    // bytes of device memory one grid row costs: 4 B per cell and plane (a MostRecent group's packed words: 8 B per cell,
+    // its two slots), + the finalized bands a sub-pipeline keeps
     static size_t bytes_per_row(const PipelineConfig& c) {
         const detail::Grouping g = detail::group_reductions(c.reductions);
         size_t planes = 0;
@@ -888,7 +967,7 @@ struct Pipeline::Banded {
         for (size_t g = 0; g < grouping.masks.size(); ++g)
             for (int p = 0; p < 4; ++p)
                 if (grouping.masks[g] & kPlaneBits[p])
-                    k.planes[g * 4 + (size_t)p].assign(cells, p == 2 ? -3.402823466e+38f : p == 3 ? 3.402823466e+38f : 0.0f);
+                    k.planes[g * 4 + (size_t)p].assign(cells, detail::plane_identity(grouping.select[g] != 0, p));
         const GridConfig& g = cfg.grid;
         k.touched.assign((size_t)((g.width + g.tile_width - 1) / g.tile_width) * (size_t)((g.height + g.tile_height - 1) / g.tile_height), 0u);
     }
@@ -1217,8 +1296,10 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         }
         const size_t per_row = Banded::bytes_per_row(config);
         if (budget > 0 && per_row * (size_t)g.height > budget) {
-            for (const auto& r : config.reductions)
-                if (!registered(r.type)) return fail_with(Status::error(StatusCode::InvalidArgument, "pipeline: unknown reduction type"));
+            {
+                Status ok = detail::check_reduction_specs(config.reductions);
+                if (!ok.ok()) return fail_with(ok);
+            }
             const int th = g.tile_height;
             const size_t fit = budget / std::max<size_t>(per_row * (size_t)th, 1);          // whole tile rows that fit
             const int band_rows = (int)std::min<size_t>(std::max<size_t>(fit, 1) * (size_t)th, (size_t)g.height + th);
@@ -1303,10 +1384,8 @@ Status Pipeline::validate() const {
     for (const auto& r : c.reductions) {
         if (r.value_channel.empty())
             return Status::error(StatusCode::InvalidArgument, "pipeline: value_channel must be specified");
-        if (!registered(r.type))
-            return Status::error(StatusCode::InvalidArgument, "pipeline: unknown reduction type");
     }
-    return Status::success();
+    return detail::check_reduction_specs(c.reductions);
 }
 
 Status Pipeline::ingest(const PointCloud& cloud) { return host_ ? host_->ingest(cloud) : banded_ ? banded_->ingest(cloud) : impl_->ingest(cloud); }
@@ -1381,6 +1460,11 @@ std::vector<Pipeline::PlaneView> Pipeline::state_planes() const {
         (void)impl_->define_all_planes();               // the caller reads (and may write) them: identity where nothing was ingested
         // The fills run on the pipeline's stream and the caller may read on any other (torch's current stream, a host copy):
         // they are complete when the pointers leave.  Planes that were already defined cost no synchronisation.
+        // A MostRecent group leaves as a SNAPSHOT of its two float planes (value in the SUM slot, timestamp in the WGT slot --
+        // the layout of its `.pcrt` files, so a sharded save_state gathers it like an Average group), unpacked from the packed
+        // words at every call: read-only (the words stay the state), reach 0 (a Point glyph: no part in the halo exchange).
+        for (auto& g : impl_->groups)
+            if (g.select) { (void)impl_->unpack_select(g); filled = true; }
         if (filled) (void)pcr_hip_stream_synchronize(impl_->stream);
     }
     for (auto& g : impl_->groups) g.fresh = false;      // mutable pointers leave the pipeline: assume the planes get written

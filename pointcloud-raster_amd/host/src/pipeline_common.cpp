@@ -33,6 +33,13 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
         if (r.glyph.type != GlyphType::Point && !glyph_reduction_ok(r.type))
             return Status::error(StatusCode::NotImplemented,
                 "pipeline: glyph splatting only supports WeightedAverage, Average, Sum, or Count reduction types");
+        if (is_select(r.type)) {
+            if (!cloud.channel_data(r.timestamp_channel))
+                return Status::error(StatusCode::InvalidArgument, "pipeline: timestamp channel not found: " + r.timestamp_channel);
+            const ChannelDesc* t = cloud.channel(r.timestamp_channel);
+            if (!t || t->dtype != DataType::Float32)
+                return Status::error(StatusCode::InvalidArgument, "pipeline: timestamp channel must be Float32");
+        }
     }
     return Status::success();
 }

@@ -7,6 +7,7 @@
 #include "pcr_hip.h"
 
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
@@ -17,16 +18,32 @@ namespace detail {
 // plane bits = PCR_HIP_PLANE_* of include/pcr_hip.h (sum, weight, max, min)
 constexpr uint32_t kPlaneBits[4] = {1u, 2u, 4u, 8u};
 
-// Only these six have an implementation in the reference (src/ops/reduction_registry.cpp:173-184); Pipeline::create
-// refuses the others (src/engine/pipeline.cpp:229-233).
+// The first six have an implementation in the reference (src/ops/reduction_registry.cpp:173-184), and Pipeline::create
+// refuses the others (src/engine/pipeline.cpp:229-233).  MostRecent the reference only declares (builtin_ops.h:106-124);
+// this build implements it for the Point glyph (include/pcr_hip.h "MostRecent").  Median, Percentile, PriorityMerge and
+// Custom stay refused.
 inline bool registered(ReductionType t) {
     switch (t) {
         case ReductionType::Sum: case ReductionType::Max: case ReductionType::Min:
         case ReductionType::Average: case ReductionType::WeightedAverage: case ReductionType::Count:
+        case ReductionType::MostRecent:
             return true;
         default:
             return false;
     }
+}
+
+// A selection ("keep the entry with the greatest key"), not an accumulation: a group of its own, keyed by its key channel too.
+inline bool is_select(ReductionType t) { return t == ReductionType::MostRecent; }
+
+// What Pipeline::create checks of every ReductionSpec, on every engine.
+inline Status check_reduction_specs(const std::vector<ReductionSpec>& reductions) {
+    for (const auto& r : reductions) {
+        if (!registered(r.type)) return Status::error(StatusCode::InvalidArgument, "pipeline: unknown reduction type");
+        if (is_select(r.type) && r.timestamp_channel.empty())
+            return Status::error(StatusCode::InvalidArgument, "pipeline: MostRecent requires a timestamp_channel");
+    }
+    return Status::success();
 }
 
 // src/engine/pipeline.cpp:500-508
@@ -41,7 +58,9 @@ inline uint32_t planes_for(ReductionType t) {
         case ReductionType::Count: return kPlaneBits[1];
         case ReductionType::Max: return kPlaneBits[2];
         case ReductionType::Min: return kPlaneBits[3];
-        default: return kPlaneBits[0] | kPlaneBits[1];      // Average, WeightedAverage
+        // MostRecent: at the host-visible boundary its state is the reference's two float planes, value in slot 0 and
+        // timestamp in slot 1 (pack_state<MostRecentOp>, builtin_ops.h:178-183), in a group no accumulation shares
+        default: return kPlaneBits[0] | kPlaneBits[1];      // Average, WeightedAverage, MostRecent
     }
 }
 
@@ -64,8 +83,41 @@ inline int state_planes_of(ReductionType t, int out[2]) {
         case ReductionType::Count: out[0] = 1; return 1;
         case ReductionType::Max: out[0] = 2; return 1;
         case ReductionType::Min: out[0] = 3; return 1;
-        default: out[0] = 0; out[1] = 1; return 2;
+        default: out[0] = 0; out[1] = 1; return 2;           // Average, WeightedAverage {sum, weight}; MostRecent {value, timestamp}
     }
+}
+
+// Identity of plane slot p of a group as the checkpoints see it (builtin_ops.h: identity()).  select: a MostRecent group,
+// {NaN 0x7FC00000, -FLT_MAX}.
+inline float plane_identity(bool select, int p) {
+    if (select) {
+        if (p == 1) return -3.402823466e+38f;
+        const uint32_t bits = 0x7FC00000u;
+        float f;
+        std::memcpy(&f, &bits, sizeof f);
+        return f;
+    }
+    return p == 2 ? -3.402823466e+38f : p == 3 ? 3.402823466e+38f : 0.0f;
+}
+
+// The MostRecent fold on the host (include/pcr_hip.h): ord() maps float bits monotonically onto unsigned integers,
+// word(t, v) = ord(t + 0.0f) << 32 | ord(v); a cell's state is the maximum word of its accepted points, 0 when it has none.
+inline uint32_t select_ord(uint32_t b) { return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+inline uint32_t select_unord(uint32_t u) { return (u >> 31) ? (u ^ 0x80000000u) : ~u; }
+inline bool select_accepts(float t) { return t > -3.402823466e+38f; }      // false for NaN (combine_timestamped vs the identity)
+inline uint64_t select_word(float t, float v) {
+    uint32_t tb, vb;
+    std::memcpy(&tb, &t, 4);
+    std::memcpy(&vb, &v, 4);
+    if (tb == 0x80000000u) tb = 0u;                                          // t + 0.0f
+    return ((uint64_t)select_ord(tb) << 32) | select_ord(vb);
+}
+inline uint64_t select_word_of_state(float v, float t) { return select_accepts(t) ? select_word(t, v) : 0u; }
+inline void select_state_of_word(uint64_t w, float* v, float* t) {
+    if (!w) { *v = plane_identity(true, 0); *t = plane_identity(true, 1); return; }
+    const uint32_t vb = select_unord((uint32_t)w), tb = select_unord((uint32_t)(w >> 32));
+    std::memcpy(v, &vb, 4);
+    std::memcpy(t, &tb, 4);
 }
 
 inline std::string default_band_name(const ReductionSpec& r) {
@@ -81,16 +133,23 @@ struct StateOutput {
 // ReductionSpecs -> accumulation groups (same value channel through the same glyph = one pass, one set of planes).
 struct Grouping {
     std::vector<uint32_t> masks;             // per group: planes it keeps
+    std::vector<uint8_t> select;             // per group: a MostRecent group (planes 0 / 1 = value / timestamp)
     std::vector<StateOutput> outputs;        // per ReductionSpec
 };
+// A MostRecent spec is keyed by (value channel, timestamp channel) and never shares a group with the accumulations.
+inline bool same_group(const ReductionSpec& a, const ReductionSpec& b) {
+    if (is_select(a.type) != is_select(b.type)) return false;
+    if (is_select(a.type) && a.timestamp_channel != b.timestamp_channel) return false;
+    return a.value_channel == b.value_channel && same_glyph(a.glyph, b.glyph);
+}
 inline Grouping group_reductions(const std::vector<ReductionSpec>& reductions) {
     Grouping out;
     std::vector<const ReductionSpec*> first;
     for (const auto& r : reductions) {
         int gi = -1;
         for (size_t k = 0; k < first.size(); ++k)
-            if (first[k]->value_channel == r.value_channel && same_glyph(first[k]->glyph, r.glyph)) gi = (int)k;
-        if (gi < 0) { first.push_back(&r); out.masks.push_back(0u); gi = (int)first.size() - 1; }
+            if (same_group(*first[k], r)) gi = (int)k;
+        if (gi < 0) { first.push_back(&r); out.masks.push_back(0u); out.select.push_back(is_select(r.type) ? 1 : 0); gi = (int)first.size() - 1; }
         out.masks[(size_t)gi] |= planes_for(r.type);
         out.outputs.push_back({gi, r.type});
     }

@@ -66,7 +66,10 @@ void bind_engine(py::module_& m) {
         .def_readwrite("value_channel", &ReductionSpec::value_channel)
         .def_readwrite("type", &ReductionSpec::type)
         .def_readwrite("weight_channel", &ReductionSpec::weight_channel)
-        .def_readwrite("timestamp_channel", &ReductionSpec::timestamp_channel)
+        .def_readwrite("timestamp_channel", &ReductionSpec::timestamp_channel,
+                       "ReductionType.MostRecent (Point glyph only): the Float32 channel whose greatest value picks the cell's point "
+                       "(\"newest survey wins\"). Points with a NaN or <= -FLT_MAX timestamp are ignored; among equal timestamps the "
+                       "greater value wins, so the result does not depend on order, engine or chunking. Required for MostRecent.")
         .def_readwrite("percentile", &ReductionSpec::percentile)
         .def_readwrite("output_band_name", &ReductionSpec::output_band_name)
         .def_readwrite("glyph", &ReductionSpec::glyph);

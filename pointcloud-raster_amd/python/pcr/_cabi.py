@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "lib", "libpcr_hip.so"))
 
 SUM, MAX, MIN, AVERAGE, WEIGHTED_AVERAGE, COUNT = 0, 1, 2, 3, 4, 5
+MOST_RECENT = 8
 GLYPH_POINT, GLYPH_LINE, GLYPH_GAUSSIAN = 0, 1, 2
 PLANE_SUM, PLANE_WGT, PLANE_MAX, PLANE_MIN = 1, 2, 4, 8
 PATH_AUTO, PATH_DIRECT, PATH_BINNED = 0, 1, 2
@@ -155,6 +156,11 @@ SYMBOLS = {
     "pcr_hip_engine_profile_read": [_VP, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int), C.c_int],
     "pcr_hip_scatter_point": [_VP, _U32, C.POINTER(Planes), _VP, _VP, _VP, _U64],
     "pcr_hip_scatter_glyph": [_VP, C.POINTER(Glyph), _U32, C.POINTER(Planes), _VP, _VP, _VP, _U64],
+    "pcr_hip_select_pack": [_VP, _VP, _VP, _I64, _VP],
+    "pcr_hip_select_unpack": [_VP, _VP, _VP, _I64, _VP],
+    "pcr_hip_select_merge": [_VP, _VP, _I64, _VP],
+    "pcr_hip_scatter_select": [_VP, _VP, _VP, _VP, _VP, _VP, _U64],
+    "pcr_hip_finalize_select": [C.POINTER(Grid), _VP, _VP, _VP, _VP],
     "pcr_hip_crs_from_epsg": [C.c_int, C.POINTER(CrsDesc)],
     "pcr_hip_transform_xy": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64, _VP],
     "pcr_hip_transform_xy_host": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64],
