@@ -3,6 +3,7 @@
 
 #include "common.hpp"
 
+#include <functional>
 #include <map>
 #include <vector>
 
@@ -76,7 +77,8 @@ struct ScopedKernelTimer {
 struct BinGeom {
     int tile_w, tile_h;                 // interior of an LDS tile, cells (a bin owns these cells)
     int bins_x, bins_y, nbins;
-    int chunk;                          // points per workgroup in the count / scatter passes
+    int chunk;                          // points per workgroup in the count / scatter passes: set by the front end that
+                                        // picks the scatter shape (bin_points; the callers of b16::bin, bin16.hpp)
     int row0, rows;                     // the band of state rows [row0, row0 + rows) the bins cover (window-relative)
     int sup_shift;                      // two-level sort: the first level groups 2^sup_shift consecutive tiles (0: one level)
 };
@@ -110,25 +112,46 @@ inline int band_rows_for(const GridDev& g, int tile_w, int tile_h, int max_bins)
     return (int)(rows < g.st_rows ? rows : g.st_rows);
 }
 
+// The engine's grid with the owned rows narrowed to the band [row0, row0 + rows) of state rows (empty: own_r0 >= own_r1).
+inline GridDev band_grid(const GridDev& g, int row0, int rows) {
+    GridDev gd = g;
+    gd.own_r0 = std::max(g.own_r0, g.st_r0 + row0);
+    gd.own_r1 = std::min(g.own_r1, g.st_r0 + row0 + rows);
+    return gd;
+}
+// What a binned scatter reports (pcr_hip_scatter_stats): path 1 LDS tiles, 2 moments.
+inline void set_binned_stats(pcr_hip_engine* e, int path, int tile_w, int tile_h, int apron, int bins) {
+    e->stats.path = path;
+    e->stats.lds_tile_w = tile_w;
+    e->stats.lds_tile_h = tile_h;
+    e->stats.lds_apron = apron;
+    e->stats.num_bins = bins;
+}
+
 // Passes A (histogram + routing keys), scan, B (LDS-staged scatter) over the points that gd owns (for a band:
-// the engine's grid with the owned rows narrowed to the band).  Record kinds:
+// the engine's grid with the owned rows narrowed to the band).  b.sup_shift > 0: the two-level counting sort for windows with
+// more tiles than one pass counts -- A, scan, B on groups of 2^sup_shift tiles, then every group by tile (k_sub_count, scan,
+// k_sub_scatter); item_records and every_bin apply to the last level.  Record kinds:
 //   Value  8 B {local cell, value}         Point glyph
-//   Index  8 B {local cell, point index}   Gaussian tiles with per-point sigma / rotation channels or r > 3 (the others, and
-//                                          Lines, bin 16-byte value records: bin16.hpp)
+//   Index  8 B {local cell, point index}   MostRecent; Gaussian tiles with per-point sigma / rotation channels or r > 3 (the
+//                                          others, and Lines, bin 16-byte value records: bin16.hpp)
 enum class RecordKind { Value, Index };
 // every_bin: an item (possibly of zero records) for EVERY bin, so that the tile pass visits every cell of the band.
 int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const double* x, const double* y, const float* v,
-               uint64_t n, RecordKind kind, const GlyphDev* gl, unsigned item_records, BinBuffers* out, bool every_bin = false,
+               uint64_t n, RecordKind kind, unsigned item_records, BinBuffers* out, bool every_bin = false,
                size_t extra_bytes = 0);
 // Identity values (0, 0, -FLT_MAX, +FLT_MAX) into the planes of `mask` over the engine's state window (engine.hip).
 int fill_identity(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl);
 
-// Two-level counting sort (groups of 2^shift tiles, then tiles) for windows with more tiles than one pass counts;
-// 8-byte Value or Index records.  two_level_shift: 0 when not applicable (disabled, or more than kMaxTiles tiles).
-int two_level_shift(const pcr_hip_engine* e, int tiles);
-int bin_points_two_level(pcr_hip_engine* e, const BinGeom& tiles, const double* x, const double* y, const float* v,
-                         uint64_t n, bool index_records, unsigned item_records, BinBuffers* out, bool every_bin = false,
-                         size_t extra_bytes = 0);
+// One sweep over the tiles of the state window, `whole` being its bins (row0 = 0, rows = st_rows, sup_shift = 0): in one pass
+// when bin_points can count them (one sort level, or two), else in up to kMaxBands row bands.  Every pass bins the points of
+// its rows (8-byte records, bin_points' arguments) and calls tile_pass with the pass's grid, bins and buffers; a non-zero
+// status from it ends the sweep.  Returns the bins visited, or minus the error code.
+// sweep_passes: the passes the sweep would take; 1 = the whole window at once, 0 = it cannot be binned.
+using TilePass = std::function<int(const GridDev& gd, const BinGeom& b, const BinBuffers& bb)>;
+int sweep_passes(const pcr_hip_engine* e, const BinGeom& whole);
+int sweep_tiles(pcr_hip_engine* e, const BinGeom& whole, const double* x, const double* y, const float* v, uint64_t n,
+                RecordKind kind, unsigned item_records, bool every_bin, size_t extra_bytes, const TilePass& tile_pass);
 
 // direct path (global atomics), scatter_direct.hip
 int direct_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
@@ -145,7 +168,7 @@ int binned_glyph(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const Pla
                  const double* x, const double* y, const float* v, uint64_t n);
 
 // MostRecent (pcr_hip_scatter_select): one plane of packed 64-bit words, common.hpp select_word.  direct: scatter_direct.hip;
-// binned: Index records through the Point front end (bin_points / bin_points_two_level), tile pass in scatter_binned.hip.
+// binned: Index records through the Point front end (sweep_tiles), tile pass in scatter_binned.hip.
 int direct_select(pcr_hip_engine* e, unsigned long long* packed, const double* x, const double* y, const float* v,
                   const float* key, uint64_t n);
 bool binned_select_supported(const pcr_hip_engine* e);

@@ -166,13 +166,10 @@ void launch_bin_count(bool one_tile, dim3 grid, size_t lds, hipStream_t stream, 
 }
 
 // Points per workgroup of the count pass.  Every block flushes its LDS histogram with up to nbins global atomics, so many
-// bins want long chunks -- but long chunks mean few blocks in flight.  Measured in round 2, k_bin_count ms:
-//   chunk          8192    16384   32768   65536   131072
-//   1376 bins (C2, 50 M points)        0.228           0.267
-//   2816 bins (16384 x 2048, 125 M)  0.672   0.648   0.630   0.647   0.697
-//   5504 bins (16384 x 4096, 250 M)  1.260   1.193   1.154   1.178   1.231
-// The single-level path now counts in the scatter pass's own blocks (scatter_shape: 12 288 or 16 384 points), because
-// the counts are kept per virtual XCD and both passes must see a point in the same block (bin_points).
+// bins want long chunks -- but long chunks mean few blocks in flight.  The pass has no chunk of its own to choose: it walks
+// the cloud in the scatter pass's blocks (BinGeom::chunk = scatter_shape(nbins).chunk(), set in bin_points), because the
+// counts are kept per virtual XCD and both passes must see a point in the same block.  What is chosen per launch is how those
+// blocks are dealt to workgroups: count_split workgroups per block, or count_blocks blocks per workgroup.
 
 // Workgroups of the count pass per scatter block.  The scatter pass wants long chunks (its (block, bin) runs), the count pass
 // short ones: with round 2's 28 672-point chunks its 1 744 workgroups of 512 threads were 2.3 rounds of the 768 a launch keeps
@@ -592,17 +589,15 @@ inline int tile_cell_bytes(unsigned mask) {
 
 // LDS tile shape: 128 columns x as many rows (multiple of 8, <= 128) as fit ~150 KB of the CU's
 // 160 KB LDS at the per-cell footprint of the requested planes.
-inline BinGeom point_bin_geom(const GridDev& g, uint32_t mask, int row0, int rows) {
-    BinGeom b;
+// The bins of the whole state window (sweep_tiles cuts it into bands where it must; bin_points sets the chunk).
+inline BinGeom point_bin_geom(const GridDev& g, uint32_t mask) {
+    BinGeom b{};
     b.tile_w = 128;
     b.tile_h = std::min(128, (150 * 1024 / (std::max(tile_cell_bytes(mask), 4) * 128)) & ~7);
     b.bins_x = (g.W + b.tile_w - 1) / b.tile_w;
-    b.bins_y = (rows + b.tile_h - 1) / b.tile_h;
+    b.bins_y = (g.st_rows + b.tile_h - 1) / b.tile_h;
     b.nbins = b.bins_x * b.bins_y;
-    b.chunk = b.nbins <= 2048 ? 16384 : 8192;
-    b.row0 = row0;
-    b.rows = rows;
-    b.sup_shift = 0;
+    b.rows = g.st_rows;
     return b;
 }
 
@@ -927,82 +922,28 @@ void launch_select(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, unsig
 
 inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
-}  // namespace
-
-namespace pcrhip {
-
-int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const double* x, const double* y, const float* v,
-               uint64_t n, RecordKind kind, const GlyphDev* gl, unsigned item_records, BinBuffers* out, bool every_bin,
-               size_t extra_bytes) {
-    const int max_items = b.nbins + (int)(n / item_records) + 1;
-    const size_t rec_bytes = sizeof(uint2);
-
-    // Counts and cursors per VIRTUAL XCD (blockIdx % 8; workgroups are dealt to the XCDs round-robin): a bin's record range is
-    // split into eight sub-ranges and a (workgroup, bin) run of ~21 records only ever shares its first and last 128-byte line
-    // with runs written through the same L2, where they merge -- shared between XCDs they left as partial lines (504 MB
-    // written for 400 MB of records, profiles/r02_C2_rocprof.md).  Both passes use the same block -> points mapping.
+// The count pass over the points gd owns, for either level-one geometry (tiles, or groups of tiles): it walks the cloud in the
+// scatter pass's blocks -- full_blocks chunks of b.chunk points, then 4096-point blocks for the ragged end.
+void launch_count(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, int full_blocks, const double* x, const double* y,
+                  uint64_t n, unsigned* d_keys, unsigned* d_count) {
     constexpr int nvx = kVirtualXcds;
-    size_t off = 0;                                             // scratch carve-up
-    const size_t o_count = off;  off += align256((size_t)nvx * b.nbins * 4);
-    const size_t o_cursor = off; off += align256((size_t)nvx * b.nbins * 4);
-    const size_t o_nitems = off; off += 256;
-    const size_t o_items = off;  off += align256((size_t)max_items * sizeof(BinItem));
-    const size_t o_rec = off;    off += align256((size_t)n * rec_bytes);
-    const size_t o_keys = off;   off += align256((size_t)n * sizeof(unsigned));
-    const size_t o_extra = off;  off += align256(extra_bytes);
-    int rc = ensure_scratch(e, off);
-    if (rc) return rc;
-    char* s = e->d_scratch;
-    unsigned* d_count = reinterpret_cast<unsigned*>(s + o_count);
-    unsigned* d_cursor = reinterpret_cast<unsigned*>(s + o_cursor);
-    unsigned* d_nitems = reinterpret_cast<unsigned*>(s + o_nitems);
-    BinItem* d_items = reinterpret_cast<BinItem*>(s + o_items);
-    unsigned* d_keys = reinterpret_cast<unsigned*>(s + o_keys);
-
-    PCR_HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)nvx * b.nbins * 4, e->stream));
-    {
-        ScopedKernelTimer t(e, "k_bin_count");
-        // the count pass walks the cloud in the scatter pass's blocks (its chunks, then 4096-point blocks for the ragged end)
-        BinGeom bc = b;
-        const ScatterShape sh = scatter_shape(b.nbins);
-        bc.chunk = sh.chunk();
-        const int full_blocks = scatter_full_blocks(sh, v, n, kind == RecordKind::Index);
-        const uint64_t done = (uint64_t)full_blocks * sh.chunk();
-        const int cb = count_blocks(b.nbins, full_blocks, e->num_cus);
-        const unsigned tail_blocks = (unsigned)((n - done + 4095) / 4096);
-        if (cb > 1) {
-            const unsigned cblocks = (unsigned)nvx * (((unsigned)(full_blocks + nvx - 1) / nvx + cb - 1) / cb) + tail_blocks;
-            launch_bin_count<true>(gd.tiles_x * gd.tiles_y == 1, dim3(cblocks), (size_t)b.nbins * 4, e->stream,
-                                   gd, bc, (unsigned)full_blocks, cb, nvx, x, y, n, d_keys, d_count, e->d_touched, e->d_counters);
-        } else {
-            const int split = count_split(bc.chunk, b.nbins);
-            launch_bin_count<false>(gd.tiles_x * gd.tiles_y == 1, dim3((unsigned)full_blocks * (unsigned)split + tail_blocks),
-                                    (size_t)b.nbins * 4, e->stream,
-                                    gd, bc, (unsigned)full_blocks, split, nvx, x, y, n, d_keys, d_count, e->d_touched, e->d_counters);
-        }
-    }
-    {
-        ScopedKernelTimer t(e, "k_bin_scan");
-        hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(kThreads), 0, e->stream, b.nbins, nvx, item_records, d_count,
-                           d_cursor, d_items, d_nitems, every_bin ? 1 : 0);
-    }
-    {
-        uint2* d_rec = reinterpret_cast<uint2*>(s + o_rec);
-        if (kind == RecordKind::Index) launch_bin_scatter<true>(e, b, nvx, d_keys, v, n, d_cursor, d_rec);
-        else launch_bin_scatter<false>(e, b, nvx, d_keys, v, n, d_cursor, d_rec);
-        out->records = d_rec;
-    }
-    PCR_HIP_TRY(hipGetLastError());
-    out->items = d_items;
-    out->n_items = d_nitems;
-    out->max_items = max_items;
-    out->extra = extra_bytes ? s + o_extra : nullptr;
-    return PCR_HIP_OK;
+    const unsigned tail_blocks = (unsigned)((n - (uint64_t)full_blocks * b.chunk + 4095) / 4096);
+    const int cb = count_blocks(b.nbins, full_blocks, e->num_cus);
+    const int split = cb > 1 ? cb : count_split(b.chunk, b.nbins);      // k_bin_count<true> takes cb in `split`
+    const unsigned blocks = cb > 1 ? (unsigned)nvx * (((unsigned)(full_blocks + nvx - 1) / nvx + cb - 1) / cb)
+                                   : (unsigned)full_blocks * (unsigned)split;
+    ScopedKernelTimer t(e, "k_bin_count");
+    auto go = [&](auto multi) {
+        launch_bin_count<decltype(multi)::value>(gd.tiles_x * gd.tiles_y == 1, dim3(blocks + tail_blocks), (size_t)b.nbins * 4, e->stream,
+                                                 gd, b, (unsigned)full_blocks, split, nvx, x, y, n, d_keys, d_count, e->d_touched, e->d_counters);
+    };
+    if (cb > 1) go(std::true_type{});
+    else go(std::false_type{});
 }
 
-// Two-level counting sort for the Point glyph on grids with more LDS tiles than one pass can count
-// (16384^2 = 21 888 tiles): level 1 groups the points by runs of 2^s consecutive tiles (about sqrt(tiles)
-// groups), level 2 sorts every group by tile.  Both levels stream; see k_sub_count / k_sub_scatter.
+// Two-level counting sort for grids with more LDS tiles than one pass can count (16384^2 = 21 888 tiles): level 1 groups the
+// points by runs of 2^s consecutive tiles (about sqrt(tiles) groups), level 2 sorts every group by tile.  Both levels stream;
+// see k_sub_count / k_sub_scatter.  0 when not applicable (disabled, or more than kMaxTiles tiles).
 int two_level_shift(const pcr_hip_engine* e, int tiles) {
     // tile kMaxTiles-1 with local cell 2^15-1 would encode to the dropped-point sentinel 0xFFFFFFFF
     if (!e->two_level || tiles >= kMaxTiles) return 0;
@@ -1012,104 +953,124 @@ int two_level_shift(const pcr_hip_engine* e, int tiles) {
     return (1 << s) <= kMaxSubBins ? s : 0;
 }
 
-int bin_points_two_level(pcr_hip_engine* e, const BinGeom& tiles, const double* x, const double* y, const float* v,
-                         uint64_t n, bool index_records, unsigned item_records, BinBuffers* out, bool every_bin,
-                         size_t extra_bytes) {
-    BinGeom l1 = tiles;                                                   // first level: groups of tiles
-    l1.nbins = (tiles.nbins + (1 << tiles.sup_shift) - 1) >> tiles.sup_shift;
-    const ScatterShape sh1 = scatter_shape(l1.nbins);
-    l1.chunk = sh1.chunk();                                               // the count pass walks the scatter pass's blocks (bin_points)
-    constexpr int nvx = kVirtualXcds;                                     // (measured neutral here: the first level's runs are ~170 records long)
-    const unsigned sub_records = kSubPer * kThreads;
-    const int full_blocks = scatter_full_blocks(sh1, v, n, index_records);
-    const unsigned blocks = (unsigned)full_blocks + (unsigned)((n - (uint64_t)full_blocks * sh1.chunk() + 4095) / 4096);
-    const int max_items1 = l1.nbins + (int)(n / sub_records) + 1;
-    const int max_items2 = tiles.nbins + (int)(n / item_records) + 1;
+// How a window's tiles are reached: in one pass (one sort level, or two when shift > 0), or in `passes` bands of band_rows
+// state rows, each with at most max_bins LDS tiles; every band is a full pass over the points (routing keys are cheap: 5 ps per
+// point and band) that only keeps the points of its rows.  passes = 0: the window cannot be binned.
+struct SweepPlan {
+    int passes, band_rows, shift;
+};
+SweepPlan plan_sweep(const pcr_hip_engine* e, const BinGeom& whole) {
+    const int band_rows = band_rows_for(e->gd, whole.tile_w, whole.tile_h, e->max_bins);
+    const int nbands = band_rows > 0 ? (e->gd.st_rows + band_rows - 1) / band_rows : 0;
+    if (nbands == 1) return {1, band_rows, 0};
+    const int shift = two_level_shift(e, whole.nbins);
+    if (shift > 0) return {1, e->gd.st_rows, shift};
+    return {nbands <= kMaxBands ? nbands : 0, band_rows, 0};
+}
 
-    size_t off = 0;
+}  // namespace
+
+namespace pcrhip {
+
+int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const double* x, const double* y, const float* v,
+               uint64_t n, RecordKind kind, unsigned item_records, BinBuffers* out, bool every_bin, size_t extra_bytes) {
+    // Counts and cursors per VIRTUAL XCD (blockIdx % 8; workgroups are dealt to the XCDs round-robin): a bin's record range is
+    // split into eight sub-ranges and a (workgroup, bin) run of ~21 records only ever shares its first and last 128-byte line
+    // with runs written through the same L2, where they merge -- shared between XCDs they left as partial lines (504 MB
+    // written for 400 MB of records, profiles/r02_C2_rocprof.md).  Both passes use the same block -> points mapping.
+    // (Measured neutral for the first of two levels, whose runs are ~170 records long.)
+    constexpr int nvx = kVirtualXcds;
+    const bool index = kind == RecordKind::Index;
+    const int shift = b.sup_shift;
+    BinGeom l1 = b;                                             // the first level's bins: the tiles, or groups of 2^shift tiles
+    if (shift) l1.nbins = (b.nbins + (1 << shift) - 1) >> shift;
+    const ScatterShape sh = scatter_shape(l1.nbins);
+    l1.chunk = sh.chunk();
+    const int full_blocks = scatter_full_blocks(sh, v, n, index);
+    const unsigned sub_records = kSubPer * kThreads;            // a first-level item is what one k_sub_scatter workgroup sorts
+    const unsigned item_records1 = shift ? sub_records : item_records;
+    const int max_items1 = l1.nbins + (int)(n / item_records1) + 1;
+    const int max_items = b.nbins + (int)(n / item_records) + 1;
+
+    size_t off = 0;                                             // scratch carve-up; the second level's arrays are empty without one
     auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    const size_t two = shift ? 1 : 0;
     const size_t o_count1 = carve((size_t)nvx * l1.nbins * 4), o_cursor1 = carve((size_t)nvx * l1.nbins * 4), o_nitems1 = carve(8);
     const size_t o_items1 = carve((size_t)max_items1 * sizeof(BinItem));
-    const size_t o_count2 = carve((size_t)tiles.nbins * 4), o_cursor2 = carve((size_t)tiles.nbins * 4), o_nitems2 = carve(8);
-    const size_t o_items2 = carve((size_t)max_items2 * sizeof(BinItem));
-    const size_t o_keys = carve((size_t)n * 4), o_rec1 = carve((size_t)n * 8), o_rec2 = carve((size_t)n * 8);
+    const size_t o_rec1 = carve((size_t)n * sizeof(uint2)), o_keys = carve((size_t)n * sizeof(unsigned));
+    const size_t o_count2 = carve(two * b.nbins * 4), o_cursor2 = carve(two * b.nbins * 4), o_nitems2 = carve(two * 8);
+    const size_t o_items2 = carve(two * max_items * sizeof(BinItem)), o_rec2 = carve(two * n * sizeof(uint2));
     const size_t o_extra = carve(extra_bytes);
     int rc = ensure_scratch(e, off);
     if (rc) return rc;
     char* s = e->d_scratch;
     auto U = [&](size_t o) { return reinterpret_cast<unsigned*>(s + o); };
     BinItem* d_items1 = reinterpret_cast<BinItem*>(s + o_items1);
-    BinItem* d_items2 = reinterpret_cast<BinItem*>(s + o_items2);
     uint2* d_rec1 = reinterpret_cast<uint2*>(s + o_rec1);
-    uint2* d_rec2 = reinterpret_cast<uint2*>(s + o_rec2);
+    auto scan = [&](int nbins, int vx, unsigned records, size_t o_count, size_t o_cursor, size_t o_items, size_t o_nitems, bool every) {
+        ScopedKernelTimer t(e, "k_bin_scan");
+        hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(kThreads), 0, e->stream, nbins, vx, records, U(o_count), U(o_cursor),
+                           reinterpret_cast<BinItem*>(s + o_items), U(o_nitems), every ? 1 : 0);
+    };
 
     PCR_HIP_TRY(hipMemsetAsync(U(o_count1), 0, (size_t)nvx * l1.nbins * 4, e->stream));
-    PCR_HIP_TRY(hipMemsetAsync(U(o_count2), 0, (size_t)tiles.nbins * 4, e->stream));
-    {
-        ScopedKernelTimer t(e, "k_bin_count");
-        const int cb = count_blocks(l1.nbins, full_blocks, e->num_cus);
-        const unsigned tail_blocks = blocks - (unsigned)full_blocks;
-        if (cb > 1) {
-            const unsigned cblocks = (unsigned)nvx * (((unsigned)(full_blocks + nvx - 1) / nvx + cb - 1) / cb) + tail_blocks;
-            launch_bin_count<true>(e->gd.tiles_x * e->gd.tiles_y == 1, dim3(cblocks), (size_t)l1.nbins * 4, e->stream,
-                                   e->gd, l1, (unsigned)full_blocks, cb, nvx, x, y, n, U(o_keys), U(o_count1), e->d_touched, e->d_counters);
-        } else {
-            const int split = count_split(l1.chunk, l1.nbins);
-            launch_bin_count<false>(e->gd.tiles_x * e->gd.tiles_y == 1, dim3((unsigned)full_blocks * (unsigned)split + tail_blocks),
-                                    (size_t)l1.nbins * 4, e->stream,
-                                    e->gd, l1, (unsigned)full_blocks, split, nvx, x, y, n, U(o_keys), U(o_count1), e->d_touched, e->d_counters);
-        }
-    }
-    {
-        ScopedKernelTimer t(e, "k_bin_scan");
-        hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(kThreads), 0, e->stream, l1.nbins, nvx, sub_records, U(o_count1),
-                           U(o_cursor1), d_items1, U(o_nitems1), 0);
-    }
-    if (index_records) launch_bin_scatter<true>(e, l1, nvx, U(o_keys), v, n, U(o_cursor1), d_rec1);
+    if (shift) PCR_HIP_TRY(hipMemsetAsync(U(o_count2), 0, (size_t)b.nbins * 4, e->stream));
+    launch_count(e, gd, l1, full_blocks, x, y, n, U(o_keys), U(o_count1));
+    scan(l1.nbins, nvx, item_records1, o_count1, o_cursor1, o_items1, o_nitems1, every_bin && !shift);
+    if (index) launch_bin_scatter<true>(e, l1, nvx, U(o_keys), v, n, U(o_cursor1), d_rec1);
     else launch_bin_scatter<false>(e, l1, nvx, U(o_keys), v, n, U(o_cursor1), d_rec1);
-    const int tps = 1 << tiles.sup_shift;
-    {
-        ScopedKernelTimer t(e, "k_sub_count");
-        hipLaunchKernelGGL(k_sub_count, dim3(max_items1), dim3(kThreads), (size_t)tps * 4, e->stream, tiles.sup_shift,
-                           d_rec1, d_items1, U(o_nitems1), U(o_count2));
-    }
-    {
-        ScopedKernelTimer t(e, "k_bin_scan");
-        hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(kThreads), 0, e->stream, tiles.nbins, 1, item_records, U(o_count2),
-                           U(o_cursor2), d_items2, U(o_nitems2), every_bin ? 1 : 0);
-    }
-    {
+    if (shift) {                                                // second level: every first-level item by tile
+        const int tps = 1 << shift;
+        {
+            ScopedKernelTimer t(e, "k_sub_count");
+            hipLaunchKernelGGL(k_sub_count, dim3(max_items1), dim3(kThreads), (size_t)tps * 4, e->stream, shift,
+                               d_rec1, d_items1, U(o_nitems1), U(o_count2));
+        }
+        scan(b.nbins, 1, item_records, o_count2, o_cursor2, o_items2, o_nitems2, every_bin);
         ScopedKernelTimer t(e, "k_sub_scatter");
         const size_t lds = (size_t)sub_records * sizeof(uint2) + (size_t)tps * 4 * 3;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sub_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_sub_scatter, dim3(max_items1), dim3(kThreads), lds, e->stream, tiles.sup_shift, d_rec1, d_items1,
-                           U(o_nitems1), U(o_cursor2), d_rec2);
+        hipLaunchKernelGGL(k_sub_scatter, dim3(max_items1), dim3(kThreads), lds, e->stream, shift, d_rec1, d_items1,
+                           U(o_nitems1), U(o_cursor2), reinterpret_cast<uint2*>(s + o_rec2));
     }
     PCR_HIP_TRY(hipGetLastError());
-    out->records = d_rec2;
-    out->items = d_items2;
-    out->n_items = U(o_nitems2);
-    out->max_items = max_items2;
+    out->records = reinterpret_cast<uint2*>(s + (shift ? o_rec2 : o_rec1));
+    out->items = reinterpret_cast<BinItem*>(s + (shift ? o_items2 : o_items1));
+    out->n_items = U(shift ? o_nitems2 : o_nitems1);
+    out->max_items = max_items;
     out->extra = extra_bytes ? s + o_extra : nullptr;
     return PCR_HIP_OK;
 }
 
-// Bands of state rows, each with at most kMaxBins LDS tiles; every band is a full pass over the points
-// (routing keys are cheap: 5 ps per point and band) that only keeps the points of its rows.
-static int point_bands(const pcr_hip_engine* e, uint32_t mask, int* band_rows) {
-    const GridDev& g = e->gd;
-    const BinGeom b = point_bin_geom(g, mask, 0, g.st_rows);
-    *band_rows = band_rows_for(g, b.tile_w, b.tile_h, e->max_bins);
-    if (*band_rows <= 0) return 0;
-    return (g.st_rows + *band_rows - 1) / *band_rows;
+int sweep_passes(const pcr_hip_engine* e, const BinGeom& whole) { return plan_sweep(e, whole).passes; }
+
+int sweep_tiles(pcr_hip_engine* e, const BinGeom& whole, const double* x, const double* y, const float* v, uint64_t n,
+                RecordKind kind, unsigned item_records, bool every_bin, size_t extra_bytes, const TilePass& tile_pass) {
+    const SweepPlan plan = plan_sweep(e, whole);
+    if (plan.passes < 1) return -fail(PCR_HIP_INVALID_ARGUMENT, "binned scatter: grid cannot be binned");
+    int total_bins = 0;
+    for (int pass = 0; pass < plan.passes; ++pass) {
+        const int row0 = pass * plan.band_rows, rows = std::min(plan.band_rows, e->gd.st_rows - row0);
+        const GridDev gd = band_grid(e->gd, row0, rows);          // this band's points only
+        if (gd.own_r0 >= gd.own_r1 && !plan.shift) continue;      // (the two-level pass runs whatever the engine owns)
+        BinGeom b = whole;
+        b.row0 = row0;
+        b.rows = rows;
+        b.bins_y = (rows + b.tile_h - 1) / b.tile_h;
+        b.nbins = b.bins_x * b.bins_y;
+        b.sup_shift = plan.shift;
+        total_bins += b.nbins;
+        BinBuffers bb{};
+        int rc = bin_points(e, gd, b, x, y, v, n, kind, item_records, &bb, every_bin, extra_bytes);
+        if (rc == PCR_HIP_OK) rc = tile_pass(gd, b, bb);
+        if (rc) return -rc;
+    }
+    return total_bins;
 }
 
 bool binned_point_supported(const pcr_hip_engine* e, uint32_t mask) {
     if (mask == 0 || (mask & ~15u)) return false;
-    int band_rows = 0;
-    const int nbands = point_bands(e, mask, &band_rows);
-    const bool two_level = nbands != 1 && two_level_shift(e, point_bin_geom(e->gd, mask, 0, e->gd.st_rows).nbins) > 0;
-    if (!two_level && (nbands < 1 || nbands > kMaxBands)) return false;
+    if (sweep_passes(e, point_bin_geom(e->gd, mask)) < 1) return false;
     // not worth the fixed cost of sweeping every tile for a handful of points
     uint64_t cells = (uint64_t)e->gd.W * e->gd.st_rows;
     if (e->forced_path != 2 && e->stats.points_in * 16 < cells) return false;
@@ -1118,17 +1079,13 @@ bool binned_point_supported(const pcr_hip_engine* e, uint32_t mask) {
 
 int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
                  const double* x, const double* y, const float* v, uint64_t n) {
-    int band_rows = 0;
-    int nbands = point_bands(e, mask, &band_rows);
-    int total_bins = 0;
-    BinGeom b = point_bin_geom(e->gd, mask, 0, e->gd.st_rows);
-    const int shift = nbands != 1 ? two_level_shift(e, b.nbins) : 0;
-    // Undefined planes (pcr_hip_engine_planes_fresh(e, 2)): one band of bins covers the whole state window, so the tile
+    const BinGeom whole = point_bin_geom(e->gd, mask);
+    // Undefined planes (pcr_hip_engine_planes_fresh(e, 2)): one pass of bins covers the whole state window, so the tile
     // pass can define every cell itself -- an item for every bin, every cell stored -- and the state initialisation costs
     // no pass of its own.  Needs whole float4 groups per plane row (the merge's vector form is per row, the scalar form
-    // covers the rest); anything else (two sort levels, several bands) fills the planes first.
+    // covers the rest); anything else (several bands) fills the planes first.
     const int64_t cells = (int64_t)e->gd.st_rows * e->gd.W;
-    const bool define_all = e->planes_fresh == 2 && (nbands == 1 || shift > 0) && cells % 4 == 0 &&
+    const bool define_all = e->planes_fresh == 2 && sweep_passes(e, whole) == 1 && cells % 4 == 0 &&
                             ((reinterpret_cast<uintptr_t>(pl.sum) | reinterpret_cast<uintptr_t>(pl.wgt) |
                               reinterpret_cast<uintptr_t>(pl.mx) | reinterpret_cast<uintptr_t>(pl.mn)) & 15) == 0;
     if (e->planes_fresh == 2 && !define_all) {
@@ -1136,46 +1093,14 @@ int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
         if (rc) return rc;
         e->planes_fresh = 1;
     }
-    if (shift > 0) {                                            // one sweep, two sort levels
-        b.sup_shift = shift;
-        BinBuffers bb{};
-        int rc = bin_points_two_level(e, b, x, y, v, n, false, kPointItemRecords, &bb, define_all);
-        if (rc) return rc;
+    // the bands too, when the caller asked (pcr_hip_engine_finalize_with_scatter): the launch stores every cell of the
+    // window from float4 groups (define_all), and a band cell has the plane cell's index when the owned rows are the window
+    const bool fused = define_all && e->fused_outs.n > 0 && e->fused_done && e->gd.W % 4 == 0 &&
+                       e->gd.own_r0 == e->gd.st_r0 && e->gd.own_r1 - e->gd.own_r0 == e->gd.st_rows;
+    const int bins = sweep_tiles(e, whole, x, y, v, n, RecordKind::Value, kPointItemRecords, define_all, 0,
+                                 [&](const GridDev& gd, const BinGeom& b, const BinBuffers& bb) {
         if (define_all)
             hipLaunchKernelGGL(k_fill_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, pl, mask, cells / 4);
-        const bool fused = define_all && e->fused_outs.n > 0 && e->fused_done && e->gd.W % 4 == 0 &&
-                           e->gd.own_r0 == e->gd.st_r0 && e->gd.own_r1 - e->gd.own_r0 == e->gd.st_rows;
-        e->fused_taken = fused;
-        ScopedKernelTimer t(e, "k_tile_accum");
-        switch (mask) {
-#define PCR_ACC(M) case M: launch_accum<M>(e, e->gd, b, pl, bb, fused); break;
-            PCR_ACC(1) PCR_ACC(2) PCR_ACC(3) PCR_ACC(4) PCR_ACC(5) PCR_ACC(6) PCR_ACC(7) PCR_ACC(8)
-            PCR_ACC(9) PCR_ACC(10) PCR_ACC(11) PCR_ACC(12) PCR_ACC(13) PCR_ACC(14) PCR_ACC(15)
-#undef PCR_ACC
-            default: return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_point: empty plane mask");
-        }
-        total_bins = b.nbins;
-        nbands = 0;
-    } else if (nbands < 1) {
-        return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_point: grid cannot be binned");
-    }
-    for (int band = 0; band < nbands; ++band) {
-        const int row0 = band * band_rows, rows = std::min(band_rows, e->gd.st_rows - row0);
-        GridDev gd = e->gd;                                     // this band's points only
-        gd.own_r0 = std::max(e->gd.own_r0, e->gd.st_r0 + row0);
-        gd.own_r1 = std::min(e->gd.own_r1, e->gd.st_r0 + row0 + rows);
-        if (gd.own_r0 >= gd.own_r1) continue;
-        b = point_bin_geom(e->gd, mask, row0, rows);
-        total_bins += b.nbins;
-        BinBuffers bb{};
-        int rc = bin_points(e, gd, b, x, y, v, n, RecordKind::Value, nullptr, kPointItemRecords, &bb, define_all);
-        if (rc) return rc;
-        if (define_all)
-            hipLaunchKernelGGL(k_fill_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, pl, mask, cells / 4);
-        // the bands too, when the caller asked (pcr_hip_engine_finalize_with_scatter): this launch stores every cell of the
-        // window from float4 groups (define_all), and a band cell has the plane cell's index when the owned rows are the window
-        const bool fused = define_all && e->fused_outs.n > 0 && e->fused_done && e->gd.W % 4 == 0 &&
-                           e->gd.own_r0 == e->gd.st_r0 && e->gd.own_r1 - e->gd.own_r0 == e->gd.st_rows;
         e->fused_taken = fused;
         ScopedKernelTimer t(e, "k_tile_accum");
         switch (mask) {
@@ -1185,68 +1110,39 @@ int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
 #undef PCR_ACC
             default: return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_point: empty plane mask");
         }
-    }
+        return (int)PCR_HIP_OK;
+    });
+    if (bins < 0) return -bins;
     PCR_HIP_TRY(hipGetLastError());
-    e->stats.path = 1;
-    e->stats.lds_tile_w = b.tile_w;
-    e->stats.lds_tile_h = b.tile_h;
-    e->stats.lds_apron = 0;
-    e->stats.num_bins = total_bins;
+    set_binned_stats(e, 1, whole.tile_w, whole.tile_h, 0, bins);
     return PCR_HIP_OK;
 }
 
 bool binned_select_supported(const pcr_hip_engine* e) { return binned_point_supported(e, kSelectGeomMask); }
 
-// pcr_hip_scatter_select on the binned path: binned_point's structure (one level / two sort levels / row bands, the same
-// limits) on Index records, with k_tile_select as the tile pass.
+// pcr_hip_scatter_select on the binned path: binned_point's sweep (the same limits) on Index records, with k_tile_select as
+// the tile pass.
 int binned_select(pcr_hip_engine* e, unsigned long long* packed, const double* x, const double* y, const float* v,
                   const float* key, uint64_t n) {
-    int band_rows = 0;
-    int nbands = point_bands(e, kSelectGeomMask, &band_rows);
-    int total_bins = 0;
-    BinGeom b = point_bin_geom(e->gd, kSelectGeomMask, 0, e->gd.st_rows);
-    const int shift = nbands != 1 ? two_level_shift(e, b.nbins) : 0;
+    const BinGeom whole = point_bin_geom(e->gd, kSelectGeomMask);
     const int64_t cells = (int64_t)e->gd.st_rows * e->gd.W;
-    // undefined plane: one band of bins over the whole window lets the tile pass store every word itself (16-byte groups)
-    const bool define_all = e->planes_fresh == 2 && (nbands == 1 || shift > 0) && cells % 2 == 0 && e->gd.W % 2 == 0 &&
+    // undefined plane: one pass of bins over the whole window lets the tile pass store every word itself (16-byte groups)
+    const bool define_all = e->planes_fresh == 2 && sweep_passes(e, whole) == 1 && cells % 2 == 0 && e->gd.W % 2 == 0 &&
                             (reinterpret_cast<uintptr_t>(packed) & 15) == 0;
     if (e->planes_fresh == 2 && !define_all) {
         ScopedKernelTimer t(e, "k_state_init");
         PCR_HIP_TRY(hipMemsetAsync(packed, 0, (size_t)cells * sizeof(unsigned long long), e->stream));
         e->planes_fresh = 1;
     }
-    if (shift > 0) {                                            // one sweep, two sort levels
-        b.sup_shift = shift;
-        BinBuffers bb{};
-        int rc = bin_points_two_level(e, b, x, y, nullptr, n, true, kPointItemRecords, &bb, define_all, (size_t)n * 8);
-        if (rc) return rc;
-        if (define_all) hipLaunchKernelGGL(k_zero_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, packed, cells / 2);
-        launch_select(e, e->gd, b, packed, bb, v, key, n);
-        total_bins = b.nbins;
-        nbands = 0;
-    } else if (nbands < 1) {
-        return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_select: grid cannot be binned");
-    }
-    for (int band = 0; band < nbands; ++band) {
-        const int row0 = band * band_rows, rows = std::min(band_rows, e->gd.st_rows - row0);
-        GridDev gd = e->gd;                                     // this band's points only
-        gd.own_r0 = std::max(e->gd.own_r0, e->gd.st_r0 + row0);
-        gd.own_r1 = std::min(e->gd.own_r1, e->gd.st_r0 + row0 + rows);
-        if (gd.own_r0 >= gd.own_r1) continue;
-        b = point_bin_geom(e->gd, kSelectGeomMask, row0, rows);
-        total_bins += b.nbins;
-        BinBuffers bb{};
-        int rc = bin_points(e, gd, b, x, y, nullptr, n, RecordKind::Index, nullptr, kPointItemRecords, &bb, define_all, (size_t)n * 8);
-        if (rc) return rc;
+    const int bins = sweep_tiles(e, whole, x, y, nullptr, n, RecordKind::Index, kPointItemRecords, define_all, (size_t)n * 8,
+                                 [&](const GridDev& gd, const BinGeom& b, const BinBuffers& bb) {
         if (define_all) hipLaunchKernelGGL(k_zero_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, packed, cells / 2);
         launch_select(e, gd, b, packed, bb, v, key, n);
-    }
+        return (int)PCR_HIP_OK;
+    });
+    if (bins < 0) return -bins;
     PCR_HIP_TRY(hipGetLastError());
-    e->stats.path = 1;
-    e->stats.lds_tile_w = b.tile_w;
-    e->stats.lds_tile_h = b.tile_h;
-    e->stats.lds_apron = 0;
-    e->stats.num_bins = total_bins;
+    set_binned_stats(e, 1, whole.tile_w, whole.tile_h, 0, bins);
     return PCR_HIP_OK;
 }
 

@@ -645,7 +645,7 @@ int cell_bytes(int glyph_type, unsigned mask) {
 // Tile shape from the glyph's reach: the interior S x S is what the LDS leaves after an apron of `need`
 // cells on every side.  A grid with more such tiles than the binning passes take is swept in row bands
 // (band_rows rows each); only when even kMaxBands bands are not enough is S grown at the apron's expense.
-bool glyph_tile(const pcr_hip_engine* e, const GlyphDev& gl, unsigned mask, GlyphTile* out, int* band_rows) {
+bool glyph_tile(const pcr_hip_engine* e, const GlyphDev& gl, unsigned mask, GlyphTile* out) {
     const GridDev& g = e->gd;
     const int limit = 150 * 1024 / std::max(cell_bytes(gl.type, mask), 4);    // LDS cells per workgroup
     const int side = ((int)std::floor(std::sqrt((double)limit))) & ~1;
@@ -664,9 +664,8 @@ bool glyph_tile(const pcr_hip_engine* e, const GlyphDev& gl, unsigned mask, Glyp
     };
     while (bands_for(S) > kMaxBands && S < side - 8) S += 8;
     if (bands_for(S) > kMaxBands) return false;
-    GlyphTile t;
+    GlyphTile t{};
     t.need = need;
-    t.fixed_r = 0;
     if (gl.type == PCR_HIP_GLYPH_GAUSSIAN && !gl.sigma_x && !gl.sigma_y && !gl.rotation && gl.def_rotation == 0.0f) {
         // the r of gauss_params (glyph_device.hpp) for the default sigmas
         const float sx = gl.def_sigma_x * (float)g.inv_csx, sy = gl.def_sigma_y * (float)g.inv_csy;
@@ -680,13 +679,9 @@ bool glyph_tile(const pcr_hip_engine* e, const GlyphDev& gl, unsigned mask, Glyp
     t.bins.tile_w = S;
     t.bins.tile_h = S;
     t.bins.bins_x = (g.W + S - 1) / S;
-    *band_rows = band_rows_for(g, S, S, e->max_bins);
-    t.bins.row0 = 0;
-    t.bins.rows = g.st_rows;
-    t.bins.sup_shift = 0;
+    t.bins.rows = g.st_rows;                                // the whole state window (the front ends set the chunk)
     t.bins.bins_y = (g.st_rows + S - 1) / S;
     t.bins.nbins = t.bins.bins_x * t.bins.bins_y;
-    t.bins.chunk = t.bins.nbins <= 2048 ? 16384 : 8192;
     *out = t;
     return true;
 }
@@ -707,8 +702,7 @@ bool binned_glyph_supported(const pcr_hip_engine* e, const GlyphDev& gl, uint32_
     if (mask == 0 || (mask & ~3u)) return false;
     if (gl.type != PCR_HIP_GLYPH_GAUSSIAN && gl.type != PCR_HIP_GLYPH_LINE) return false;
     GlyphTile t;
-    int band_rows = 0;
-    if (!glyph_tile(e, gl, mask, &t, &band_rows)) return false;
+    if (!glyph_tile(e, gl, mask, &t)) return false;
     // every bin's window is swept once per scatter: not worth it for a handful of points
     uint64_t cells = (uint64_t)e->gd.W * e->gd.st_rows;
     if (e->forced_path != 2 && e->stats.points_in * 64 < cells) return false;
@@ -718,8 +712,7 @@ bool binned_glyph_supported(const pcr_hip_engine* e, const GlyphDev& gl, uint32_
 int binned_glyph(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const PlanesDev& pl,
                  const double* x, const double* y, const float* v, uint64_t n) {
     GlyphTile t;
-    int band_rows = 0;
-    if (!glyph_tile(e, gl, mask, &t, &band_rows)) return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_glyph: grid cannot be binned");
+    if (!glyph_tile(e, gl, mask, &t)) return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_glyph: grid cannot be binned");
     // work item size: ~4 M cell updates per workgroup for the Gaussian, 64 K segments for the Line
     unsigned item_points = 65535;                             // (k_tile_line_rec counts a cell's visits in 16 bits)
     if (gl.type == PCR_HIP_GLYPH_GAUSSIAN) {
@@ -729,44 +722,8 @@ int binned_glyph(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const Pla
     const size_t lds = (size_t)t.lw * t.lh * cell_bytes(gl.type, mask);
     const int S = t.bins.tile_h;
     int total_bins = 0;
-    // Gaussian on a window with more tiles than one pass counts: the 8-byte index records go through the same
-    // two-level sort as the Point glyph (one sweep instead of one per row band)
-    if (gl.type == PCR_HIP_GLYPH_GAUSSIAN && band_rows < e->gd.st_rows) {
-        const int shift = two_level_shift(e, t.bins.nbins);
-        if (shift > 0) {
-            t.bins.sup_shift = shift;
-            BinBuffers bb{};
-            int rc = bin_points_two_level(e, t.bins, x, y, nullptr, n, true, item_points, &bb);
-            if (rc) return rc;
-            {
-                ScopedKernelTimer tm(e, "k_tile_gauss");
-#define PCR_GAUSS(M, FR) launch_gauss(&k_tile_gauss<M, FR>, e, e->gd, gl, t, pl, bb, lds, x, y, v)
-#define PCR_GAUSS_R(M)                                                                          \
-                switch (t.fixed_r) {                                                            \
-                    case 1: PCR_GAUSS(M, 1); break;                                             \
-                    case 2: PCR_GAUSS(M, 2); break;                                             \
-                    case 3: PCR_GAUSS(M, 3); break;                                             \
-                    case 4: PCR_GAUSS(M, 4); break;                                             \
-                    case 5: PCR_GAUSS(M, 5); break;                                             \
-                    case 6: PCR_GAUSS(M, 6); break;                                             \
-                    case 7: PCR_GAUSS(M, 7); break;                                             \
-                    default: PCR_GAUSS(M, 0); break;                                            \
-                }
-                if (mask == 1) { PCR_GAUSS_R(1) } else if (mask == 2) { PCR_GAUSS_R(2) } else { PCR_GAUSS_R(3) }
-#undef PCR_GAUSS_R
-#undef PCR_GAUSS
-            }
-            PCR_HIP_TRY(hipGetLastError());
-            e->stats.path = 1;
-            e->stats.lds_tile_w = t.bins.tile_w;
-            e->stats.lds_tile_h = t.bins.tile_h;
-            e->stats.lds_apron = t.apron;
-            e->stats.num_bins = t.bins.nbins;
-            return PCR_HIP_OK;
-        }
-    }
     if (gl.type == PCR_HIP_GLYPH_LINE) {
-        // 16-byte end-point records through the shared front-end (bin16.hpp); bands as below
+        // 16-byte end-point records through the shared front-end (bin16.hpp), in row bands of their own bin limit
         const int band16 = band_rows_for(e->gd, S, S, b16::max_bins(e));
         if (band16 <= 0) return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_glyph: grid cannot be binned");
         const int max_bins = t.bins.bins_x * ((std::min(band16, e->gd.st_rows) + S - 1) / S);
@@ -779,9 +736,7 @@ int binned_glyph(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const Pla
         const bool state_records = covered && t.lw <= 127 && t.lw * t.lh <= kLineMaxCells;
         for (int row0 = 0; row0 < e->gd.st_rows; row0 += band16) {
             const int rows = std::min(band16, e->gd.st_rows - row0);
-            GridDev gd = e->gd;
-            gd.own_r0 = std::max(e->gd.own_r0, e->gd.st_r0 + row0);
-            gd.own_r1 = std::min(e->gd.own_r1, e->gd.st_r0 + row0 + rows);
+            const GridDev gd = band_grid(e->gd, row0, rows);
             if (gd.own_r0 >= gd.own_r1) continue;
             t.bins.row0 = row0;
             t.bins.rows = rows;
@@ -816,33 +771,19 @@ int binned_glyph(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const Pla
             else hipLaunchKernelGGL(k_line_list<3>, dim3(64), dim3(256), 0, e->stream, e->gd, gl, pl, d_fbl, d_fbc, x, y, v);
         }
         PCR_HIP_TRY(hipGetLastError());
-        e->stats.path = 1;
-        e->stats.lds_tile_w = t.bins.tile_w;
-        e->stats.lds_tile_h = t.bins.tile_h;
-        e->stats.lds_apron = t.apron;
-        e->stats.num_bins = total_bins;
+        set_binned_stats(e, 1, S, S, t.apron, total_bins);
         return PCR_HIP_OK;
     }
-    // row bands: a band bins the points whose CENTRE row it holds; footprints reach into neighbouring
-    // bands through the apron / global-atomic spill exactly as they reach into neighbouring tiles
-    for (int row0 = 0; row0 < e->gd.st_rows; row0 += band_rows) {
-        const int rows = std::min(band_rows, e->gd.st_rows - row0);
-        GridDev gd = e->gd;
-        gd.own_r0 = std::max(e->gd.own_r0, e->gd.st_r0 + row0);
-        gd.own_r1 = std::min(e->gd.own_r1, e->gd.st_r0 + row0 + rows);
-        if (gd.own_r0 >= gd.own_r1) continue;
-        t.bins.row0 = row0;
-        t.bins.rows = rows;
-        t.bins.bins_y = (rows + S - 1) / S;
-        t.bins.nbins = t.bins.bins_x * t.bins.bins_y;
-        t.bins.chunk = t.bins.nbins <= 2048 ? 16384 : 8192;
-        total_bins += t.bins.nbins;
-        BinBuffers bb{};
-        int rc = bin_points(e, gd, t.bins, x, y, v, n, RecordKind::Index, &gl, item_points, &bb);
-        if (rc) return rc;
+    // Gaussian: 8-byte index records through the Point glyph's sweep (one pass, two sort levels or row bands).  A band bins
+    // the points whose CENTRE row it holds; footprints reach into neighbouring bands through the apron / global-atomic
+    // spill exactly as they reach into neighbouring tiles.
+    total_bins = sweep_tiles(e, t.bins, x, y, nullptr, n, RecordKind::Index, item_points, false, 0,
+                             [&](const GridDev&, const BinGeom& b, const BinBuffers& bb) {
         // the tile kernel re-derives every point's geometry from the engine's grid: the band only selected them
+        GlyphTile tb = t;
+        tb.bins = b;
         ScopedKernelTimer tm(e, "k_tile_gauss");
-#define PCR_GAUSS(M, FR) launch_gauss(&k_tile_gauss<M, FR>, e, e->gd, gl, t, pl, bb, lds, x, y, v)
+#define PCR_GAUSS(M, FR) launch_gauss(&k_tile_gauss<M, FR>, e, e->gd, gl, tb, pl, bb, lds, x, y, v)
 #define PCR_GAUSS_R(M)                                                                          \
         switch (t.fixed_r) {                                                                    \
             case 1: PCR_GAUSS(M, 1); break;                                                     \
@@ -857,13 +798,11 @@ int binned_glyph(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const Pla
         if (mask == 1) { PCR_GAUSS_R(1) } else if (mask == 2) { PCR_GAUSS_R(2) } else { PCR_GAUSS_R(3) }
 #undef PCR_GAUSS_R
 #undef PCR_GAUSS
-    }
+        return (int)PCR_HIP_OK;
+    });
+    if (total_bins < 0) return -total_bins;
     PCR_HIP_TRY(hipGetLastError());
-    e->stats.path = 1;
-    e->stats.lds_tile_w = t.bins.tile_w;
-    e->stats.lds_tile_h = t.bins.tile_h;
-    e->stats.lds_apron = t.apron;
-    e->stats.num_bins = total_bins;
+    set_binned_stats(e, 1, S, S, t.apron, total_bins);
     return PCR_HIP_OK;
 }
 

@@ -491,9 +491,7 @@ int cells_gauss(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const Plan
     int total_bins = 0;
     for (int row0 = 0; row0 < ge.st_rows; row0 += band_rows) {
         const int rows = std::min(band_rows, ge.st_rows - row0);
-        GridDev gd = ge;                                          // this band's points only
-        gd.own_r0 = std::max(ge.own_r0, ge.st_r0 + row0);
-        gd.own_r1 = std::min(ge.own_r1, ge.st_r0 + row0 + rows);
+        const GridDev gd = band_grid(ge, row0, rows);            // this band's points only
         if (gd.own_r0 >= gd.own_r1) continue;
         BinGeom b = cell_bins(ge, p, row0, rows);
         b.chunk = chunk_of<GaussCellMaker>();
@@ -518,11 +516,7 @@ int cells_gauss(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const Plan
         else hipLaunchKernelGGL(k_cell_gauss_list<3>, dim3(64), dim3(256), 0, e->stream, ge, gl, pl, d_fbl, d_fbc, x, y, v);
     }
     PCR_HIP_TRY(hipGetLastError());
-    e->stats.path = 1;
-    e->stats.lds_tile_w = p.tile_w;
-    e->stats.lds_tile_h = p.tile_h;
-    e->stats.lds_apron = p.R;
-    e->stats.num_bins = total_bins;
+    set_binned_stats(e, 1, p.tile_w, p.tile_h, p.R, total_bins);
     return PCR_HIP_OK;
 }
 

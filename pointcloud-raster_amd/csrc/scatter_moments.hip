@@ -1042,11 +1042,7 @@ int moments_gauss(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const Pl
         }
     }
     PCR_HIP_TRY(hipGetLastError());
-    e->stats.path = 2;
-    e->stats.lds_tile_w = kTileW;
-    e->stats.lds_tile_h = kTileH;
-    e->stats.lds_apron = p.K;           // reported: expansion order
-    e->stats.num_bins = total_bins;
+    set_binned_stats(e, 2, kTileW, kTileH, p.K, total_bins);           // (apron: the expansion order is reported)
     return PCR_HIP_OK;
 }
 

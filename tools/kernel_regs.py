@@ -8,8 +8,15 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-ffp-contract=off",
-         "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "pointcloud-raster_amd", "csrc"), "--cuda-device-only", "-S"]
+
+
+def flags(root):
+    """build.py's code-generation flags for the tree at `root`, device assembly only"""
+    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-ffp-contract=off",
+            "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "pointcloud-raster_amd", "csrc"), "--cuda-device-only", "-S"]
+
+
+FLAGS = flags(ROOT)
 
 
 def kernels(src):
