@@ -181,8 +181,10 @@ int pcr_hip_finalize(int rtype, const pcr_hip_grid* g, const pcr_hip_planes* pla
 #define PCR_HIP_MAX_FINALIZE_OUTPUTS 8
 int pcr_hip_finalize_group(const pcr_hip_grid* g, const pcr_hip_planes* planes, const uint32_t* d_tile_touched,
                            int n_out, const int* rtypes, float* const* d_outs, pcr_hip_stream s);
-/* Same, but a no-op when the device word *d_bands_done is non-zero at the time the kernel runs (NULL: always runs):
- * the bands were already written by the scatter that defined the planes (pcr_hip_engine_finalize_with_scatter). */
+/* Same, but a no-op when the word *d_bands_done is non-zero at the time the kernel runs (NULL: always runs): the bands
+ * were already written by the scatter that defined the planes (pcr_hip_engine_finalize_with_scatter).  The launch itself is
+ * still made; a caller that waits for the stream anyway and keeps the word in page-locked host memory (below) can read it
+ * after the wait and not call at all, which is what the blocking Pipeline::finalize does. */
 int pcr_hip_finalize_group_unless(const pcr_hip_grid* g, const pcr_hip_planes* planes, const uint32_t* d_tile_touched,
                                   int n_out, const int* rtypes, float* const* d_outs, const uint32_t* d_bands_done,
                                   pcr_hip_stream s);
@@ -238,8 +240,10 @@ int pcr_hip_engine_planes_fresh(pcr_hip_engine* e, int fresh);
  * touched BY THIS SCATTER'S points, NaN elsewhere) from the LDS tile it has in hand: the planes are not read again
  * (Pipeline::finalize after a pipeline's only ingest: src/engine/pipeline.cpp:1154-1286 reads every tile's state back).
  * d_outs[i] holds own_rows * width floats, 16-byte aligned; the engine's owned rows must be its whole state window.
- * *d_bands_done (device word) is written by the scatter: 1 when every band cell was stored, 0 when the pass could not
- * (a bin the scan had to split).  pcr_hip_engine_finalize_taken: 1 when the last pcr_hip_scatter_point launched the
+ * *d_bands_done is written by the scatter, with one 4-byte store from the device: 1 when every band cell was stored, 0
+ * when the pass could not (a bin the scan had to split).  The word lives in any memory the device can address: device
+ * memory, or page-locked host memory from pcr_hip_host_alloc (mapped into the device's address space under the same
+ * pointer), which the host may read once the stream has been synchronised.  pcr_hip_engine_finalize_taken: 1 when the last pcr_hip_scatter_point launched the
  * fused form at all (else *d_bands_done was not written and the bands are untouched).  The bands stay valid only while
  * nothing else changes the planes or the touched flags: the caller decides (pcr_hip_finalize_group_unless). */
 int pcr_hip_engine_finalize_with_scatter(pcr_hip_engine* e, int n_out, const int* rtypes, float* const* d_outs,

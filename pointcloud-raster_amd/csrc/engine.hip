@@ -4,6 +4,7 @@
 #include "engine.hpp"
 
 #include <cstdlib>
+#include <map>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -113,6 +114,22 @@ int shared_taps(pcr_hip_engine* e, int K, int r, float sx, float sy,
     return PCR_HIP_OK;
 }
 
+void allow_dynamic_lds(const pcr_hip_engine* e, const void* kernel, size_t bytes) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, size_t> allowed;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = allowed[{e->device, kernel}];
+    if (bytes <= have) return;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) have = bytes;
+}
+
+int zero_counters(pcr_hip_engine* e) {
+    e->counters_clean = false;                            // (whoever asks counts into them and leaves them as they end up)
+    e->counters_published = false;
+    PCR_HIP_TRY(hipMemsetAsync(e->d_counters, 0, 8 * sizeof(unsigned long long), e->stream));
+    return PCR_HIP_OK;
+}
+
 // Called after a scatter has enqueued its last kernel.
 void release_scratch(pcr_hip_engine* e) {
     if (!e->scratch_borrowed) return;
@@ -159,7 +176,18 @@ int begin_scatter(pcr_hip_engine* e, uint64_t n) {
     e->stats.points_valid = 0;
     e->stats.lds_tile_w = e->stats.lds_tile_h = e->stats.lds_apron = e->stats.num_bins = 0;
     e->stats_scatter_chunk = 0;
-    PCR_HIP_TRY(hipMemsetAsync(e->d_counters, 0, 8 * sizeof(unsigned long long), e->stream));
+    e->counters_published = false;
+    return PCR_HIP_OK;
+}
+
+// The binned Point / MostRecent paths: nothing is enqueued for the counters -- they are zero already, their scans publish them
+// and leave them zero (engine.hpp) -- unless an earlier scatter left them otherwise.
+int begin_published(pcr_hip_engine* e) {
+    if (!e->counters_clean) {
+        PCR_HIP_TRY(hipMemsetAsync(e->d_counters, 0, 8 * sizeof(unsigned long long), e->stream));
+        e->counters_clean = true;
+    }
+    e->publish_counters = true;
     return PCR_HIP_OK;
 }
 
@@ -208,9 +236,13 @@ int pcr_hip_engine_create(pcr_hip_engine** out, const pcr_hip_grid* g, size_t sc
         e->ntiles = e->gd.tiles_x * e->gd.tiles_y;
         err = hipMalloc(reinterpret_cast<void**>(&e->d_touched), (size_t)e->ntiles * sizeof(uint32_t));
     }
-    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&e->d_counters), 8 * sizeof(unsigned long long));
+    const size_t count_bytes = ((size_t)kVirtualXcds * kMaxBins + kMaxTiles) * sizeof(unsigned);
+    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&e->d_counters), 16 * sizeof(unsigned long long));
+    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&e->d_bin_counts), count_bytes);
     if (err == hipSuccess) err = hipMemsetAsync(e->d_touched, 0, (size_t)e->ntiles * sizeof(uint32_t), e->stream);
-    if (err == hipSuccess) err = hipMemsetAsync(e->d_counters, 0, 8 * sizeof(unsigned long long), e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(e->d_counters, 0, 16 * sizeof(unsigned long long), e->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(e->d_bin_counts, 0, count_bytes, e->stream);
+    e->counts_clean = e->counters_clean = err == hipSuccess;
     if (err == hipSuccess && scratch_bytes) {
         // pre-size the device-wide arena at create time (outside any ingest)
         if (ensure_scratch(e, scratch_bytes) != PCR_HIP_OK) err = hipErrorOutOfMemory;
@@ -232,6 +264,7 @@ int pcr_hip_engine_destroy(pcr_hip_engine* e) {
     for (auto& p : e->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     if (e->d_touched) (void)hipFree(e->d_touched);
     if (e->d_counters) (void)hipFree(e->d_counters);
+    if (e->d_bin_counts) (void)hipFree(e->d_bin_counts);
     delete e;              // the scratch arena is device-wide and outlives engines
     return PCR_HIP_OK;
 }
@@ -290,7 +323,7 @@ int pcr_hip_engine_stats(const pcr_hip_engine* e, pcr_hip_scatter_stats* out) {
     PCR_REQUIRE(e && out, "engine_stats: null argument");
     unsigned long long c[8] = {0};
     DeviceGuard dev(e->device);
-    PCR_HIP_TRY(hipMemcpyAsync(c, e->d_counters, sizeof c, hipMemcpyDeviceToHost, e->stream));
+    PCR_HIP_TRY(hipMemcpyAsync(c, e->d_counters + (e->counters_published ? 8 : 0), sizeof c, hipMemcpyDeviceToHost, e->stream));
     PCR_HIP_TRY(hipStreamSynchronize(e->stream));
     *out = e->stats;
     out->points_valid = c[0];
@@ -376,11 +409,14 @@ int pcr_hip_scatter_point(pcr_hip_engine* e, uint32_t plane_mask, const pcr_hip_
     if (e->forced_path == 2 && !can_bin)
         return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_point: binned path forced but not applicable to this grid");
     if (e->forced_path == 1 || !can_bin) {
+        if ((rc = zero_counters(e)) != PCR_HIP_OK) return rc;
         if (e->planes_fresh == 2 && (rc = fill_identity(e, plane_mask, pl)) != PCR_HIP_OK) return rc;
         e->planes_fresh = 0;
         return direct_point(e, plane_mask, pl, d_x, d_y, d_value, n);
     }
+    if ((rc = begin_published(e)) != PCR_HIP_OK) return rc;
     rc = binned_point(e, plane_mask, pl, d_x, d_y, d_value, n);
+    e->publish_counters = false;
     e->planes_fresh = 0;                                  // the hint covers one scatter
     release_scratch(e);
     return rc;
@@ -406,6 +442,7 @@ int pcr_hip_scatter_select(pcr_hip_engine* e, uint64_t* d_packed, const double* 
     if (e->forced_path == 2 && !can_bin)
         return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_select: binned path forced but not applicable to this grid");
     if (e->forced_path == 1 || !can_bin) {
+        if ((rc = zero_counters(e)) != PCR_HIP_OK) return rc;
         if (e->planes_fresh == 2) {                       // an undefined plane: every word 0 (the identity) first
             ScopedKernelTimer t(e, "k_state_init");
             PCR_HIP_TRY(hipMemsetAsync(packed, 0, (size_t)e->gd.st_rows * e->gd.W * sizeof(unsigned long long), e->stream));
@@ -413,7 +450,9 @@ int pcr_hip_scatter_select(pcr_hip_engine* e, uint64_t* d_packed, const double* 
         e->planes_fresh = 0;
         return direct_select(e, packed, d_x, d_y, d_value, d_key, n);
     }
+    if ((rc = begin_published(e)) != PCR_HIP_OK) return rc;
     rc = binned_select(e, packed, d_x, d_y, d_value, d_key, n);
+    e->publish_counters = false;
     e->planes_fresh = 0;                                  // the hint covers one scatter
     release_scratch(e);
     return rc;
@@ -453,6 +492,7 @@ int pcr_hip_scatter_glyph(pcr_hip_engine* e, const pcr_hip_glyph* glyph, uint32_
     const bool undefined = e->planes_fresh == 2;
     e->planes_fresh = 0;                                  // the hint covers one scatter
     rc = begin_scatter(e, n);
+    if (rc == PCR_HIP_OK) rc = zero_counters(e);          // (every glyph path counts into the live words and leaves them)
     if (rc) return rc;
     if (e->forced_path == 3 || e->forced_path == 0) {
         bool can_mom = moments_supported(e, gl, plane_mask);

@@ -16,7 +16,24 @@ struct pcr_hip_engine {
 
     uint32_t* d_touched = nullptr;             // tiles_x * tiles_y words
     int ntiles = 0;
-    unsigned long long* d_counters = nullptr;  // [0] = valid points of the last scatter
+    unsigned long long* d_counters = nullptr;  // [0] = valid points of the scatter in flight; [8..16): what the last binned
+                                               // Point / MostRecent scatter published (see counters_published)
+
+    // Bin counts of the binning passes (bin_points): [kVirtualXcds][kMaxBins] for the first level, then [kMaxTiles] for the
+    // second.  Owned by the engine (not carved from the shared scratch) because of their invariant: ALL ZERO whenever no
+    // scatter of this engine is in flight -- zeroed once at create, and k_bin_scan, their last reader, writes the zeros back
+    // as it goes.  So no launch has to run ahead of the count pass.  (913 KB whatever the grid: the tile shape, and with it
+    // the number of bins, depends on the glyph and the planes of each scatter.)
+    unsigned* d_bin_counts = nullptr;
+    bool counts_clean = false;                 // cleared before a count pass is enqueued, set once the last scan of that
+                                               // bin_points is: a scatter that finds it cleared (an earlier one failed half
+                                               // way) zeroes the arrays itself
+    // The same for d_counters[0..8) on the binned Point / MostRecent paths (publish_counters set by their entry points): the
+    // first k_bin_scan of a scatter moves the eight words to [8..16) (further scans -- row bands -- add to them) and zeroes
+    // the live ones.  Every other path zeroes them at its start and leaves them as they end up (engine.hip: zero_counters).
+    bool counters_clean = false;               // [0..8) are zero once the stream reaches the next scatter
+    bool publish_counters = false;             // the scatter being enqueued publishes through its scans
+    bool counters_published = false;           // pcr_hip_engine_stats reads [8..16) (else [0..8))
 
     int forced_path = 0;                       // 0 auto, 1 direct, 2 binned, 3 moments (Gaussian only)
     int max_bins = 0;                          // LDS tiles per binning pass (kMaxBins; PCR_HIP_DEBUG_MAX_BINS lowers it
@@ -49,6 +66,11 @@ struct pcr_hip_engine {
 namespace pcrhip {
 
 int ensure_scratch(pcr_hip_engine* e, size_t bytes);
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the (device, kernel) pair and only ever has to grow: asked of the
+// runtime when a launch needs more than any launch before it did, not on every launch (engine.hip).
+void allow_dynamic_lds(const pcr_hip_engine* e, const void* kernel, size_t bytes);
+// d_counters[0..8) = 0 on the engine's stream, for a path whose kernels count into them and leave them so (engine.hip).
+int zero_counters(pcr_hip_engine* e);
 void release_scratch(pcr_hip_engine* e);
 // Device-resident tap tables of the moment path, shared by the engines of a device (engine.hip); call with the scratch
 // borrowed.  fill(tables, K, r, sx, sy) builds the host copy when the glyph spec changed.
@@ -86,13 +108,26 @@ constexpr int kMaxBands = 32;           // a grid with more LDS tiles than kMaxB
 struct BinItem {                        // one workgroup's share of a bin's records
     unsigned bin, first, count, shared; // shared != 0: the bin was split, merge with atomics
 };
+// Undefined planes whose tile pass merges a split bin with atomics need their identity values after all (n_items[1], known
+// once the scan has run).  The scatter pass takes the fill along: every k_bin_scatter workgroup, its records out, reads
+// n_items[1] and, only if it is set, stores its grid-stride share -- the usual case costs one scalar load per workgroup
+// where a launch of 2 048 no-op workgroups (k_fill_if) stood on the stream.
+struct TailFill {
+    const unsigned* n_items;            // set by bin_points; null: nothing to fill
+    void* plane[4];                     // 16-byte aligned, n16 groups of 16 bytes each; null: skipped
+    unsigned bits[4];                   // the 32-bit pattern of plane p
+    long long n16;
+};
 struct BinBuffers {                     // device pointers into the engine's scratch arena
     const uint2* records;               // Value / Index records, grouped by bin; .x = local cell
     const BinItem* items;
     const unsigned* n_items;            // [0] = items, [1] = 1 when some bin was split into several items
     int max_items;
     void* extra;                        // extra_bytes of the same scratch allocation, 256-B aligned, for the caller's own pass
+    bool fill_folded;                   // the TailFill given to bin_points went with the scatter pass (one sort level); else
+                                        // the tile pass fills behind the last scan itself
 };
+constexpr int kVirtualXcds = 8;         // record sub-ranges per bin (bin_points)
 constexpr int kMaxBins = 12160;        // scatter pass LDS: the 8192-record staging window (64 KB) + 8 B per bin = 159 KB of the CU's 160.
                                         // Round 5 (8064 until then, "beyond this a block's runs are single records anyway"): measured on
                                         // the window of a C5 shard at N = 2 (16384 x 8192, 11 008 tiles, 500 M points) one level with
@@ -139,7 +174,7 @@ enum class RecordKind { Value, Index };
 // every_bin: an item (possibly of zero records) for EVERY bin, so that the tile pass visits every cell of the band.
 int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const double* x, const double* y, const float* v,
                uint64_t n, RecordKind kind, unsigned item_records, BinBuffers* out, bool every_bin = false,
-               size_t extra_bytes = 0);
+               size_t extra_bytes = 0, const TailFill* fill = nullptr);
 // Identity values (0, 0, -FLT_MAX, +FLT_MAX) into the planes of `mask` over the engine's state window (engine.hip).
 int fill_identity(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl);
 
@@ -151,7 +186,8 @@ int fill_identity(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl);
 using TilePass = std::function<int(const GridDev& gd, const BinGeom& b, const BinBuffers& bb)>;
 int sweep_passes(const pcr_hip_engine* e, const BinGeom& whole);
 int sweep_tiles(pcr_hip_engine* e, const BinGeom& whole, const double* x, const double* y, const float* v, uint64_t n,
-                RecordKind kind, unsigned item_records, bool every_bin, size_t extra_bytes, const TilePass& tile_pass);
+                RecordKind kind, unsigned item_records, bool every_bin, size_t extra_bytes, const TilePass& tile_pass,
+                const TailFill* fill = nullptr);
 
 // direct path (global atomics), scatter_direct.hip
 int direct_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,

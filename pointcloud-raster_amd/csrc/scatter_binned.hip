@@ -200,46 +200,82 @@ inline int count_split(int chunk, int nbins) {
 // nvx > 1: counts and cursors are laid out [virtual XCD][bin]; a bin's records are [vx 0 | vx 1 | ...], contiguous.
 // every_bin: a bin without records still gets one (empty) item, so that the tile pass visits every cell (state
 // initialisation inside the scatter).  n_items[1] = 1 when some bin was split into several items.
+// The scan is the last reader of the counts and writes zeros behind itself: the engine's count arrays are all zero again when
+// the scatter is through (engine.hpp, d_bin_counts), and no fill kernel has to run ahead of the next count pass.  publish (the
+// binned Point / MostRecent paths): 1 the scatter's counters move to counters[8..16), 2 they are added there (a later row
+// band); the live words are zeroed.  0: they are left alone.
+// One workgroup, between the count and the scatter pass with nothing to overlap it: the prefix sums over the 1 024 threads'
+// spans are wave-shuffle scans joined over the 16 waves' totals (ONE barrier; the Hillis-Steele scan in LDS took 20), and the
+// eight per-XCD counts of a bin are loaded together.  No other workgroup is waited for, nothing is fenced.
 __global__ void __launch_bounds__(kThreads)
-k_bin_scan(int nbins, int nvx, unsigned item_records, const unsigned* __restrict__ bin_count,
-           unsigned* __restrict__ cursor, BinItem* __restrict__ items, unsigned* __restrict__ n_items, int every_bin) {
-    __shared__ unsigned part[kThreads];
-    __shared__ unsigned ipart[kThreads];
+k_bin_scan(int nbins, int nvx, unsigned item_records, unsigned* __restrict__ bin_count,
+           unsigned* __restrict__ cursor, BinItem* __restrict__ items, unsigned* __restrict__ n_items, int every_bin,
+           unsigned long long* __restrict__ counters, int publish) {
+    constexpr int kWaves = kThreads / 64;
+    __shared__ unsigned wave_s[kWaves], wave_it[kWaves], wave_split[kWaves];
+    if (publish && threadIdx.x < 8) {
+        const unsigned long long c = counters[threadIdx.x];
+        counters[8 + threadIdx.x] = publish == 2 ? counters[8 + threadIdx.x] + c : c;
+        counters[threadIdx.x] = 0ull;
+    }
     const int per = (nbins + kThreads - 1) / kThreads;
     const int lo = threadIdx.x * per, hi = min(lo + per, nbins);
-    auto total = [&](int i) {
-        unsigned c = 0;
-        for (int v = 0; v < nvx; ++v) c += bin_count[(size_t)v * nbins + i];
-        return c;
+    auto load = [&](int i, unsigned (&c)[kVirtualXcds]) {
+        if (nvx == kVirtualXcds) {
+#pragma unroll
+            for (int v = 0; v < kVirtualXcds; ++v) c[v] = bin_count[(size_t)v * nbins + i];
+        } else {
+            c[0] = bin_count[i];
+#pragma unroll
+            for (int v = 1; v < kVirtualXcds; ++v) c[v] = 0u;
+        }
     };
     unsigned s = 0, it = 0;
     int split = 0;
     for (int i = lo; i < hi; ++i) {
-        unsigned c = total(i);
+        unsigned cv[kVirtualXcds];
+        load(i, cv);
+        unsigned c = 0;
+#pragma unroll
+        for (int v = 0; v < kVirtualXcds; ++v) c += cv[v];
         s += c;
         const unsigned pieces = (c + item_records - 1) / item_records;
         it += (every_bin && pieces == 0) ? 1u : pieces;
         split |= pieces > 1;
     }
-    split = __syncthreads_or(split);
-    part[threadIdx.x] = s;
-    ipart[threadIdx.x] = it;
-    __syncthreads();
-    for (int off = 1; off < kThreads; off <<= 1) {             // Hillis-Steele inclusive scan
-        unsigned a = 0, c2 = 0;
-        if ((int)threadIdx.x >= off) { a = part[threadIdx.x - off]; c2 = ipart[threadIdx.x - off]; }
-        __syncthreads();
-        part[threadIdx.x] += a;
-        ipart[threadIdx.x] += c2;
-        __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned incl = s, iincl = it;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned a = __shfl_up(incl, off, 64), c2 = __shfl_up(iincl, off, 64);
+        if (lane >= off) { incl += a; iincl += c2; }
     }
-    unsigned run = part[threadIdx.x] - s;                       // exclusive prefixes of this thread's span
-    unsigned irun = ipart[threadIdx.x] - it;
+    const int wsplit = __any(split);
+    if (lane == 63) { wave_s[wave] = incl; wave_it[wave] = iincl; wave_split[wave] = wsplit ? 1u : 0u; }
+    __syncthreads();
+    unsigned run = incl - s, irun = iincl - it;                 // exclusive prefixes of this thread's span
+    unsigned total_items = 0, any_split = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        if (w < wave) { run += wave_s[w]; irun += wave_it[w]; }
+        total_items += wave_it[w];
+        any_split |= wave_split[w];
+    }
     for (int i = lo; i < hi; ++i) {
+        unsigned cv[kVirtualXcds];
+        load(i, cv);
         unsigned c = 0;
-        for (int v = 0; v < nvx; ++v) {
-            cursor[(size_t)v * nbins + i] = run + c;
-            c += bin_count[(size_t)v * nbins + i];
+        if (nvx == kVirtualXcds) {
+#pragma unroll
+            for (int v = 0; v < kVirtualXcds; ++v) {
+                cursor[(size_t)v * nbins + i] = run + c;
+                c += cv[v];
+                bin_count[(size_t)v * nbins + i] = 0u;
+            }
+        } else {
+            cursor[i] = run;
+            c = cv[0];
+            bin_count[i] = 0u;
         }
         unsigned pieces = (c + item_records - 1) / item_records;
         for (unsigned p = 0; p < pieces; ++p) {
@@ -251,7 +287,7 @@ k_bin_scan(int nbins, int nvx, unsigned item_records, const unsigned* __restrict
         run += c;
         irun += pieces;
     }
-    if (threadIdx.x == kThreads - 1) { n_items[0] = ipart[threadIdx.x]; n_items[1] = split ? 1u : 0u; }
+    if (threadIdx.x == kThreads - 1) { n_items[0] = total_items; n_items[1] = any_split ? 1u : 0u; }
 }
 
 // ---- pass B: scatter records, staged through LDS so that every bin's run is written contiguously
@@ -420,7 +456,7 @@ bin_scatter_chunk(unsigned char* lds_raw, const BinGeom& b, uint64_t base, const
 template <int THREADS, int PER_THREAD, int WINDOW, bool INDEX>
 __global__ void __launch_bounds__(THREADS, 4)          // <= 128 VGPRs
 k_bin_scatter(BinGeom b, unsigned full_blocks, int nvx, const unsigned* __restrict__ keys, const float* __restrict__ v,
-              uint64_t n, unsigned* __restrict__ cursor, uint2* __restrict__ records) {
+              uint64_t n, unsigned* __restrict__ cursor, uint2* __restrict__ records, TailFill fill) {
     extern __shared__ unsigned char lds_dyn[];
     cursor += (size_t)(blockIdx.x & (unsigned)(nvx - 1)) * b.nbins;      // this workgroup's virtual XCD (bin_points)
     if (blockIdx.x < full_blocks) {
@@ -429,6 +465,15 @@ k_bin_scatter(BinGeom b, unsigned full_blocks, int nvx, const unsigned* __restri
     } else {
         const uint64_t base = (uint64_t)full_blocks * (THREADS * PER_THREAD) + (uint64_t)(blockIdx.x - full_blocks) * 4096;
         bin_scatter_chunk<THREADS, 4096 / THREADS, WINDOW, false, INDEX>(lds_dyn, b, base, keys, v, n, cursor, records);
+    }
+    // (engine.hpp, TailFill: the scan split a bin and the tile pass merges into undefined planes -- the kernel boundary orders
+    // these stores before it)
+    if (fill.n_items && fill.n_items[1] != 0u) {
+        const long long stride = (long long)gridDim.x * THREADS;
+        for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < fill.n16; i += stride)
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if (fill.plane[p]) static_cast<uint4*>(fill.plane[p])[i] = make_uint4(fill.bits[p], fill.bits[p], fill.bits[p], fill.bits[p]);
     }
 }
 
@@ -452,7 +497,6 @@ inline ScatterShape scatter_shape(int nbins) {
     if (nbins <= 4032) return {1024, 16, 16384};            // 128 KB + 8 B per bin (+ the static words) = the whole LDS
     return {1024, 24, 8192};                                // (a quarter of C5, 5 504 bins: step 2.80 -> 2.72-2.76 ms against 1024 x 16; x 28: 2.86-2.95)
 }
-constexpr int kVirtualXcds = 8;                    // record sub-ranges per bin (bin_points)
 // full chunks of the scatter pass (the rest of the cloud goes in 4096-point blocks)
 inline int scatter_full_blocks(const ScatterShape& sh, const float* v, uint64_t n, bool index) {
     const bool aligned = index || (reinterpret_cast<uintptr_t>(v) & 15) == 0;     // the keys are 256-B aligned
@@ -461,7 +505,7 @@ inline int scatter_full_blocks(const ScatterShape& sh, const float* v, uint64_t 
 
 template <bool INDEX>
 void launch_bin_scatter(pcr_hip_engine* e, const BinGeom& b, int nvx, const unsigned* d_keys, const float* v, uint64_t n,
-                        unsigned* d_cursor, uint2* d_rec) {
+                        unsigned* d_cursor, uint2* d_rec, const TailFill& fill) {
     const ScatterShape sh = scatter_shape(b.nbins);
     const uint64_t chunk = (uint64_t)sh.chunk();
     const int full_blocks = scatter_full_blocks(sh, v, n, INDEX);
@@ -470,9 +514,9 @@ void launch_bin_scatter(pcr_hip_engine* e, const BinGeom& b, int nvx, const unsi
     const unsigned tail_blocks = (unsigned)((n - done + 4095) / 4096);            // the chunk is a multiple of 4096
     ScopedKernelTimer t(e, "k_bin_scatter");
     auto go = [&](auto kernel, int threads) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        allow_dynamic_lds(e, reinterpret_cast<const void*>(kernel), lds);
         hipLaunchKernelGGL(kernel, dim3((unsigned)full_blocks + tail_blocks), dim3(threads), lds, e->stream, b, (unsigned)full_blocks, nvx,
-                           d_keys, v, n, d_cursor, d_rec);
+                           d_keys, v, n, d_cursor, d_rec, fill);
     };
     if (sh.threads == 512) go(&k_bin_scatter<512, 24, 8192, INDEX>, 512);
     else if (sh.window == 16384) go(&k_bin_scatter<1024, 16, 16384, INDEX>, 1024);
@@ -763,7 +807,9 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
 }
 
 // Undefined planes, and the scan found a bin it had to split (n_items[1]): such a bin's items merge with atomics, which need
-// defined cells -- the planes get their identity values after all.  A no-op launch otherwise (the usual case).
+// defined cells -- the planes get their identity values after all.  With one sort level the scatter pass does it (TailFill,
+// engine.hpp) and this kernel is not launched; with two, the last scan runs behind the scatter pass, and this launch -- a no-op
+// in the usual case -- follows it.
 __global__ void __launch_bounds__(256)
 k_fill_if(const unsigned* __restrict__ n_items, PlanesDev pl, unsigned mask, int64_t cells4) {
     if (n_items[1] == 0u) return;
@@ -784,7 +830,7 @@ void launch_accum(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const 
     size_t lds = (size_t)b.tile_w * b.tile_h * tile_cell_bytes(MASK);
     // fresh: only when every bin is owned by one workgroup of this launch can a store replace the read-modify-write
     auto go = [&](auto kernel, const FinalizeOuts& fo, uint32_t* done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        allow_dynamic_lds(e, reinterpret_cast<const void*>(kernel), lds);
         hipLaunchKernelGGL(kernel, dim3(bb.max_items), dim3(kThreads), lds, e->stream, gd, b, pl,
                            bb.records, bb.items, bb.n_items, e->planes_fresh, fo, (const uint32_t*)e->d_touched, done);
     };
@@ -915,7 +961,7 @@ void launch_select(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, unsig
     }
     ScopedKernelTimer t(e, "k_tile_select");
     const size_t lds = (size_t)b.tile_w * b.tile_h * sizeof(unsigned long long);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tile_select), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    allow_dynamic_lds(e, reinterpret_cast<const void*>(&k_tile_select), lds);
     hipLaunchKernelGGL(k_tile_select, dim3(bb.max_items), dim3(kThreads), lds, e->stream, gd, b, packed, bb.records, bb.items,
                        bb.n_items, e->planes_fresh, (const unsigned long long*)words);
 }
@@ -973,7 +1019,8 @@ SweepPlan plan_sweep(const pcr_hip_engine* e, const BinGeom& whole) {
 namespace pcrhip {
 
 int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const double* x, const double* y, const float* v,
-               uint64_t n, RecordKind kind, unsigned item_records, BinBuffers* out, bool every_bin, size_t extra_bytes) {
+               uint64_t n, RecordKind kind, unsigned item_records, BinBuffers* out, bool every_bin, size_t extra_bytes,
+               const TailFill* fill) {
     // Counts and cursors per VIRTUAL XCD (blockIdx % 8; workgroups are dealt to the XCDs round-robin): a bin's record range is
     // split into eight sub-ranges and a (workgroup, bin) run of ~21 records only ever shares its first and last 128-byte line
     // with runs written through the same L2, where they merge -- shared between XCDs they left as partial lines (504 MB
@@ -995,10 +1042,10 @@ int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const dou
     size_t off = 0;                                             // scratch carve-up; the second level's arrays are empty without one
     auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
     const size_t two = shift ? 1 : 0;
-    const size_t o_count1 = carve((size_t)nvx * l1.nbins * 4), o_cursor1 = carve((size_t)nvx * l1.nbins * 4), o_nitems1 = carve(8);
+    const size_t o_cursor1 = carve((size_t)nvx * l1.nbins * 4), o_nitems1 = carve(8);
     const size_t o_items1 = carve((size_t)max_items1 * sizeof(BinItem));
     const size_t o_rec1 = carve((size_t)n * sizeof(uint2)), o_keys = carve((size_t)n * sizeof(unsigned));
-    const size_t o_count2 = carve(two * b.nbins * 4), o_cursor2 = carve(two * b.nbins * 4), o_nitems2 = carve(two * 8);
+    const size_t o_cursor2 = carve(two * b.nbins * 4), o_nitems2 = carve(two * 8);
     const size_t o_items2 = carve(two * max_items * sizeof(BinItem)), o_rec2 = carve(two * n * sizeof(uint2));
     const size_t o_extra = carve(extra_bytes);
     int rc = ensure_scratch(e, off);
@@ -1007,33 +1054,48 @@ int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const dou
     auto U = [&](size_t o) { return reinterpret_cast<unsigned*>(s + o); };
     BinItem* d_items1 = reinterpret_cast<BinItem*>(s + o_items1);
     uint2* d_rec1 = reinterpret_cast<uint2*>(s + o_rec1);
-    auto scan = [&](int nbins, int vx, unsigned records, size_t o_count, size_t o_cursor, size_t o_items, size_t o_nitems, bool every) {
+    // the engine's own count arrays (engine.hpp): zero now, zero again behind the scans
+    PCR_REQUIRE(l1.nbins <= kMaxBins && (!shift || b.nbins <= kMaxTiles), "bin_points: more bins than the count arrays hold");
+    unsigned* const d_count1 = e->d_bin_counts;
+    unsigned* const d_count2 = e->d_bin_counts + (size_t)nvx * kMaxBins;
+    auto scan = [&](int nbins, int vx, unsigned records, unsigned* d_count, size_t o_cursor, size_t o_items, size_t o_nitems, bool every,
+                    int publish) {
         ScopedKernelTimer t(e, "k_bin_scan");
-        hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(kThreads), 0, e->stream, nbins, vx, records, U(o_count), U(o_cursor),
-                           reinterpret_cast<BinItem*>(s + o_items), U(o_nitems), every ? 1 : 0);
+        hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(kThreads), 0, e->stream, nbins, vx, records, d_count, U(o_cursor),
+                           reinterpret_cast<BinItem*>(s + o_items), U(o_nitems), every ? 1 : 0, e->d_counters, publish);
     };
-
-    PCR_HIP_TRY(hipMemsetAsync(U(o_count1), 0, (size_t)nvx * l1.nbins * 4, e->stream));
-    if (shift) PCR_HIP_TRY(hipMemsetAsync(U(o_count2), 0, (size_t)b.nbins * 4, e->stream));
-    launch_count(e, gd, l1, full_blocks, x, y, n, U(o_keys), U(o_count1));
-    scan(l1.nbins, nvx, item_records1, o_count1, o_cursor1, o_items1, o_nitems1, every_bin && !shift);
-    if (index) launch_bin_scatter<true>(e, l1, nvx, U(o_keys), v, n, U(o_cursor1), d_rec1);
-    else launch_bin_scatter<false>(e, l1, nvx, U(o_keys), v, n, U(o_cursor1), d_rec1);
+    if (!e->counts_clean)                                       // (an earlier scatter failed between its count pass and its scan)
+        PCR_HIP_TRY(hipMemsetAsync(e->d_bin_counts, 0, ((size_t)nvx * kMaxBins + kMaxTiles) * sizeof(unsigned), e->stream));
+    e->counts_clean = false;
+    const int publish = !e->publish_counters ? 0 : e->counters_published ? 2 : 1;
+    if (publish) e->counters_clean = false;
+    TailFill tf{};
+    if (fill && !shift) {                                       // (two levels: the last scan runs after this scatter pass)
+        tf = *fill;
+        tf.n_items = U(o_nitems1);
+    }
+    launch_count(e, gd, l1, full_blocks, x, y, n, U(o_keys), d_count1);
+    scan(l1.nbins, nvx, item_records1, d_count1, o_cursor1, o_items1, o_nitems1, every_bin && !shift, publish);
+    if (index) launch_bin_scatter<true>(e, l1, nvx, U(o_keys), v, n, U(o_cursor1), d_rec1, tf);
+    else launch_bin_scatter<false>(e, l1, nvx, U(o_keys), v, n, U(o_cursor1), d_rec1, tf);
     if (shift) {                                                // second level: every first-level item by tile
         const int tps = 1 << shift;
         {
             ScopedKernelTimer t(e, "k_sub_count");
             hipLaunchKernelGGL(k_sub_count, dim3(max_items1), dim3(kThreads), (size_t)tps * 4, e->stream, shift,
-                               d_rec1, d_items1, U(o_nitems1), U(o_count2));
+                               d_rec1, d_items1, U(o_nitems1), d_count2);
         }
-        scan(b.nbins, 1, item_records, o_count2, o_cursor2, o_items2, o_nitems2, every_bin);
+        scan(b.nbins, 1, item_records, d_count2, o_cursor2, o_items2, o_nitems2, every_bin, 0);
         ScopedKernelTimer t(e, "k_sub_scatter");
         const size_t lds = (size_t)sub_records * sizeof(uint2) + (size_t)tps * 4 * 3;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sub_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        allow_dynamic_lds(e, reinterpret_cast<const void*>(&k_sub_scatter), lds);
         hipLaunchKernelGGL(k_sub_scatter, dim3(max_items1), dim3(kThreads), lds, e->stream, shift, d_rec1, d_items1,
                            U(o_nitems1), U(o_cursor2), reinterpret_cast<uint2*>(s + o_rec2));
     }
     PCR_HIP_TRY(hipGetLastError());
+    e->counts_clean = true;                                     // every launch was accepted: the scans leave zeros behind
+    if (publish) e->counters_clean = e->counters_published = true;
+    out->fill_folded = tf.n_items != nullptr;
     out->records = reinterpret_cast<uint2*>(s + (shift ? o_rec2 : o_rec1));
     out->items = reinterpret_cast<BinItem*>(s + (shift ? o_items2 : o_items1));
     out->n_items = U(shift ? o_nitems2 : o_nitems1);
@@ -1045,7 +1107,8 @@ int bin_points(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const dou
 int sweep_passes(const pcr_hip_engine* e, const BinGeom& whole) { return plan_sweep(e, whole).passes; }
 
 int sweep_tiles(pcr_hip_engine* e, const BinGeom& whole, const double* x, const double* y, const float* v, uint64_t n,
-                RecordKind kind, unsigned item_records, bool every_bin, size_t extra_bytes, const TilePass& tile_pass) {
+                RecordKind kind, unsigned item_records, bool every_bin, size_t extra_bytes, const TilePass& tile_pass,
+                const TailFill* fill) {
     const SweepPlan plan = plan_sweep(e, whole);
     if (plan.passes < 1) return -fail(PCR_HIP_INVALID_ARGUMENT, "binned scatter: grid cannot be binned");
     int total_bins = 0;
@@ -1061,7 +1124,7 @@ int sweep_tiles(pcr_hip_engine* e, const BinGeom& whole, const double* x, const 
         b.sup_shift = plan.shift;
         total_bins += b.nbins;
         BinBuffers bb{};
-        int rc = bin_points(e, gd, b, x, y, v, n, kind, item_records, &bb, every_bin, extra_bytes);
+        int rc = bin_points(e, gd, b, x, y, v, n, kind, item_records, &bb, every_bin, extra_bytes, fill);
         if (rc == PCR_HIP_OK) rc = tile_pass(gd, b, bb);
         if (rc) return -rc;
     }
@@ -1097,9 +1160,17 @@ int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
     // window from float4 groups (define_all), and a band cell has the plane cell's index when the owned rows are the window
     const bool fused = define_all && e->fused_outs.n > 0 && e->fused_done && e->gd.W % 4 == 0 &&
                        e->gd.own_r0 == e->gd.st_r0 && e->gd.own_r1 - e->gd.own_r0 == e->gd.st_rows;
+    // (define_all and the scan splits a bin: the planes get their identity values after all -- with the scatter pass, or, when
+    // the sort has two levels, by k_fill_if behind the last scan)
+    TailFill fill{};
+    fill.plane[0] = (mask & 1) ? pl.sum : nullptr; fill.bits[0] = 0u;
+    fill.plane[1] = (mask & 2) ? pl.wgt : nullptr; fill.bits[1] = 0u;
+    fill.plane[2] = (mask & 4) ? pl.mx : nullptr;  fill.bits[2] = 0xFF7FFFFFu;       // -FLT_MAX
+    fill.plane[3] = (mask & 8) ? pl.mn : nullptr;  fill.bits[3] = 0x7F7FFFFFu;       // +FLT_MAX
+    fill.n16 = cells / 4;
     const int bins = sweep_tiles(e, whole, x, y, v, n, RecordKind::Value, kPointItemRecords, define_all, 0,
                                  [&](const GridDev& gd, const BinGeom& b, const BinBuffers& bb) {
-        if (define_all)
+        if (define_all && !bb.fill_folded)
             hipLaunchKernelGGL(k_fill_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, pl, mask, cells / 4);
         e->fused_taken = fused;
         ScopedKernelTimer t(e, "k_tile_accum");
@@ -1111,7 +1182,7 @@ int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
             default: return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_point: empty plane mask");
         }
         return (int)PCR_HIP_OK;
-    });
+    }, define_all ? &fill : nullptr);
     if (bins < 0) return -bins;
     PCR_HIP_TRY(hipGetLastError());
     set_binned_stats(e, 1, whole.tile_w, whole.tile_h, 0, bins);
@@ -1134,12 +1205,16 @@ int binned_select(pcr_hip_engine* e, unsigned long long* packed, const double* x
         PCR_HIP_TRY(hipMemsetAsync(packed, 0, (size_t)cells * sizeof(unsigned long long), e->stream));
         e->planes_fresh = 1;
     }
+    TailFill fill{};                                              // (as in binned_point: one plane of 8-byte words, identity 0)
+    fill.plane[0] = packed;
+    fill.n16 = cells / 2;
     const int bins = sweep_tiles(e, whole, x, y, nullptr, n, RecordKind::Index, kPointItemRecords, define_all, (size_t)n * 8,
                                  [&](const GridDev& gd, const BinGeom& b, const BinBuffers& bb) {
-        if (define_all) hipLaunchKernelGGL(k_zero_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, packed, cells / 2);
+        if (define_all && !bb.fill_folded)
+            hipLaunchKernelGGL(k_zero_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, packed, cells / 2);
         launch_select(e, gd, b, packed, bb, v, key, n);
         return (int)PCR_HIP_OK;
-    });
+    }, define_all ? &fill : nullptr);
     if (bins < 0) return -bins;
     PCR_HIP_TRY(hipGetLastError());
     set_binned_stats(e, 1, whole.tile_w, whole.tile_h, 0, bins);

@@ -87,7 +87,10 @@ struct Pipeline::Impl {
     std::vector<Group> groups;
     std::vector<Output> outputs;
     std::vector<detail::Buffer> d_bands;     // finalized bands on the device (result_location == Host)
-    detail::Buffer d_bands_done;             // one device word per group: set by a scatter that stored the group's bands
+    detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
+                                             // host memory the device writes through its mapping (the pointer is the same on
+                                             // both sides): the blocking finalize reads it after its synchronise and launches
+                                             // nothing for a group whose bands are there
     bool state_shared = false;               // plane / touched-flag pointers have left the pipeline: never finalize with a scatter
     std::unique_ptr<Grid> result;
     bool finalized = false;                  // result() is null until the first finalize, as in the reference
@@ -294,7 +297,8 @@ struct Pipeline::Impl {
             gr.view.d_min = static_cast<float*>(gr.planes[3].data());
         }
         if (!outputs.empty() && !(s = allocate_result()).ok()) return s;
-        if (!(s = d_bands_done.allocate(std::max<size_t>(groups.size(), 1) * sizeof(uint32_t), MemoryLocation::Device)).ok()) return s;
+        if (!(s = d_bands_done.allocate(std::max<size_t>(groups.size(), 1) * sizeof(uint32_t), MemoryLocation::HostPinned)).ok()) return s;
+        std::memset(d_bands_done.data(), 0, d_bands_done.bytes());
         return detail::hip_status(pcr_hip_stream_synchronize(stream));
     }
 
@@ -693,6 +697,19 @@ struct Pipeline::Impl {
         uint32_t* d_touched = nullptr;
         Status s = detail::hip_status(pcr_hip_engine_tile_touched(engine, &d_touched, nullptr, nullptr));
         if (!s.ok()) return s;
+        // Bands the defining scatter may have stored: whether it did is a word the device wrote (not when the scan split a
+        // bin; cleared again by a touched-flag union that changed a flag).  The blocking call is going to wait for the stream
+        // anyway: it waits FIRST, reads the word, and enqueues the group's kernel only when the word says the bands are not
+        // there -- after a pipeline's only ingest nothing runs behind the tile pass.  finalize_async leaves the decision to
+        // the kernel (pcr_hip_finalize_group_unless), which reads the word when it runs.
+        bool host_decides = false;
+        if (wait)
+            for (const auto& gr : groups) host_decides = host_decides || gr.bands_with_scatter;
+        if (host_decides) {
+            s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+            if (!s.ok()) return s;
+        }
+        bool enqueued = !host_decides;           // anything on the stream since that synchronise
         // one sweep per accumulation group: its planes are read once for all of its bands
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             std::vector<int> types;
@@ -702,6 +719,11 @@ struct Pipeline::Impl {
                 if (types.empty()) return Status::success();
                 // (a group whose bands the defining scatter stored: the kernel returns at once when the device word says so)
                 const uint32_t* done = groups[gi].bands_with_scatter ? static_cast<const uint32_t*>(d_bands_done.data()) + gi : nullptr;
+                if (done && host_decides) {
+                    if (*static_cast<const volatile uint32_t*>(done) != 0u) { types.clear(); dsts.clear(); return Status::success(); }
+                    done = nullptr;              // (known to be 0: the kernel need not read it across the bus)
+                }
+                enqueued = true;
                 Status fs = detail::hip_status(pcr_hip_finalize_group_unless(&hg, &groups[gi].view, d_touched, (int)types.size(),
                                                                              types.data(), dsts.data(), done, stream));
                 types.clear();
@@ -714,6 +736,7 @@ struct Pipeline::Impl {
                     s = detail::hip_status(pcr_hip_finalize_select(&hg, static_cast<const uint64_t*>(groups[gi].packed.data()), d_touched,
                                                                    band_device(r), stream));
                     if (!s.ok()) return s;
+                    enqueued = true;
                     bands_of.push_back(r);
                     continue;
                 }
@@ -725,6 +748,7 @@ struct Pipeline::Impl {
             if (!(s = flush()).ok()) return s;
             if (!on_device) {
                 for (size_t r : bands_of) {
+                    enqueued = true;
                     s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)r), d_bands[r].data(),
                                                               (size_t)rows * W * sizeof(float), stream));
                     if (!s.ok()) return s;
@@ -732,7 +756,7 @@ struct Pipeline::Impl {
             }
         }
         // finalize_async: a device-resident result is stream-ordered like everything else on the device
-        if (wait || !on_device || !cfg.output_path.empty()) {
+        if ((wait || !on_device || !cfg.output_path.empty()) && enqueued) {
             s = detail::hip_status(pcr_hip_stream_synchronize(stream));
             if (!s.ok()) return s;
         }
