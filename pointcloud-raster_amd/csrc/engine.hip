@@ -3,6 +3,7 @@
 // scatter_direct.hip / scatter_binned.hip.
 #include "engine.hpp"
 
+#include <algorithm>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -233,6 +234,7 @@ int pcr_hip_engine_create(pcr_hip_engine** out, const pcr_hip_grid* g, size_t sc
     if (err == hipSuccess) err = hipGetDeviceProperties(&prop, e->device);
     if (err == hipSuccess) {
         e->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        e->lds_limit = std::max(prop.sharedMemPerBlock, prop.sharedMemPerBlockOptin);
         e->ntiles = e->gd.tiles_x * e->gd.tiles_y;
         err = hipMalloc(reinterpret_cast<void**>(&e->d_touched), (size_t)e->ntiles * sizeof(uint32_t));
     }

@@ -13,6 +13,7 @@ struct pcr_hip_engine {
     hipStream_t stream = nullptr;
     int device = 0;
     int num_cus = 256;
+    size_t lds_limit = 64 * 1024;              // LDS one workgroup may have on this device (queried at create)
 
     uint32_t* d_touched = nullptr;             // tiles_x * tiles_y words
     int ntiles = 0;

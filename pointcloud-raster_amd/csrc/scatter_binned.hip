@@ -631,14 +631,38 @@ inline int tile_cell_bytes(unsigned mask) {
     return ((mask & 1) ? 8 : 0) + ((mask & 2) ? 4 : 0) + ((mask & 4) ? 4 : 0) + ((mask & 8) ? 4 : 0);
 }
 
+constexpr int kPointTileW = 128;                  // every Point / MostRecent LDS tile is this wide (k_tile_accum's merge relies on it)
+// what a tile of h rows asks of a workgroup's LDS: the cells, plus one bit per cell for the fused merge's live map
+inline size_t point_tile_lds(int bytes_per_cell, int h) { return (size_t)kPointTileW * h * bytes_per_cell + (size_t)kPointTileW * h / 8; }
+
 // LDS tile shape: 128 columns x as many rows (multiple of 8, <= 128) as fit ~150 KB of the CU's
-// 160 KB LDS at the per-cell footprint of the requested planes.
+// 160 KB LDS at the per-cell footprint of the requested planes -- or more rows than that, as follows (up to 152 at 8 B per
+// cell, 248 at 4 B: at 256 rows the rounds x rows of 128 rows are never beaten).
+// A launch of few rounds (a workgroup holds a CU on its own, so nbins / CUs of them run one after another) pays for a last
+// round that is mostly empty: C2's 32 x 43 tiles of 128 x 96 are 5.375 rounds of 256 CUs.  Up to 16 rounds the height
+// becomes the one with the least rounds x rows among today's and the taller ones (steps of 8) that the device's
+// per-workgroup LDS and the 15-bit local cell hold -- C2: 128 x 104, 32 x 40 tiles, five whole rounds.  A tie keeps the
+// shorter tile; a shorter one than today's is never chosen.  The fit counts the fused merge's bit map (point_tile_lds) for
+// every launch, fused or not, MostRecent included: one rule for one grid and plane set, at the price of 1/96 to 1/32 of the
+// LDS that a launch without the map could have had.
 // The bins of the whole state window (sweep_tiles cuts it into bands where it must; bin_points sets the chunk).
-inline BinGeom point_bin_geom(const GridDev& g, uint32_t mask) {
+inline BinGeom point_bin_geom(const pcr_hip_engine* e, uint32_t mask) {
+    const GridDev& g = e->gd;
+    const int bytes = std::max(tile_cell_bytes(mask), 4);
     BinGeom b{};
-    b.tile_w = 128;
-    b.tile_h = std::min(128, (150 * 1024 / (std::max(tile_cell_bytes(mask), 4) * 128)) & ~7);
+    b.tile_w = kPointTileW;
     b.bins_x = (g.W + b.tile_w - 1) / b.tile_w;
+    auto bins_of = [&](int h) { return (int64_t)b.bins_x * ((g.st_rows + h - 1) / h); };
+    auto rounds_of = [&](int h) { return (bins_of(h) + e->num_cus - 1) / e->num_cus; };
+    b.tile_h = std::min(128, (150 * 1024 / (bytes * kPointTileW)) & ~7);
+    if (rounds_of(b.tile_h) <= 16) {
+        int64_t best = rounds_of(b.tile_h) * b.tile_h;
+        for (int h = b.tile_h + 8; kPointTileW * h <= (1 << kLcellBits) && point_tile_lds(bytes, h) <= e->lds_limit; h += 8)
+            if (rounds_of(h) * h < best) {
+                best = rounds_of(h) * h;
+                b.tile_h = h;
+            }
+    }
     b.bins_y = (g.st_rows + b.tile_h - 1) / b.tile_h;
     b.nbins = b.bins_x * b.bins_y;
     b.rows = g.st_rows;
@@ -663,11 +687,15 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
     // just before this launch and the merge proceeds as for 1 (a split bin's items merge with atomics).
     const bool full = fresh == 2 && n_items[1] == 0u;
     const BinItem it = items[blockIdx.x];
-    const int cells = b.tile_w * b.tile_h;                     // multiple of 1024
+    const int cells = kPointTileW * b.tile_h;                  // multiple of 1024
     double* t_sum = lds_tile;
     unsigned* t_wgt = reinterpret_cast<unsigned*>(t_sum + ((MASK & 1) ? cells : 0));
     float* t_max = reinterpret_cast<float*>(t_wgt + ((MASK & 2) ? cells : 0));
     float* t_min = t_max + ((MASK & 4) ? cells : 0);
+    unsigned* t_live = reinterpret_cast<unsigned*>(t_min + ((MASK & 8) ? cells : 0));   // FUSED: one bit per cell (below)
+    const int bx = it.bin % b.bins_x, by = it.bin / b.bins_x;
+    const int c0 = bx * kPointTileW, r0 = b.row0 + by * b.tile_h;     // r0 relative to the state window
+    const int w = min(kPointTileW, g.W - c0), h = min(b.tile_h, b.row0 + b.rows - r0);
 
     // records: kUnroll independent 8-byte loads per lane, double-buffered -- the next batch is in flight
     // (32 KB per CU) while the current one goes through the dependent LDS atomics, and the first batch is
@@ -686,11 +714,57 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
     };
     fetch(cur, threadIdx.x);
 
+    // FUSED: which cells lie in a touched reference tile is settled in this prologue, ahead of the first barrier, so that the
+    // merge neither divides nor loads.  The flags of the reference tiles under this LDS tile (one, at a grid of one reference
+    // tile; up to 64 are looked at) are loaded HERE, one per lane, behind the first record loads -- and looked at only behind
+    // the identity fill: vmcnt retires in order, so a use of the flag ahead of the fill would hold the fill back until the
+    // records have arrived too, where it is meant to run under them.
+    unsigned live_all = 0xFu, flag = 0u;
+    bool live_mixed = false;
+    int nt = 0;
+    if (FUSED && full) {
+        const int tr0 = (g.st_r0 + r0) / g.th, tc0 = c0 / g.tw;
+        const int nc = (c0 + w - 1) / g.tw - tc0 + 1, lane = threadIdx.x & 63;
+        nt = ((g.st_r0 + r0 + h - 1) / g.th - tr0 + 1) * nc;
+        if (nt <= 64 && lane < nt) flag = touched[(tr0 + lane / nc) * g.tiles_x + tc0 + lane % nc];
+    }
+
     for (int i = threadIdx.x; i < cells; i += kThreads) {      // identity fill
         if (MASK & 1) t_sum[i] = 0.0;
         if (MASK & 2) t_wgt[i] = 0u;
         if (MASK & 4) t_max[i] = -FLT_MAX;
         if (MASK & 8) t_min[i] = FLT_MAX;
+    }
+
+    // Every wave ballots the flags for itself: all set or none set makes live_all a wave-uniform answer for every cell.
+    // Mixed (or more than 64): t_live gets one bit per cell, a word per lane, walking its 32 columns from one reference tile
+    // to the next.
+    if (FUSED && full) {
+        // (the word as it was loaded, in its vector register up to here: left to itself the compiler compares it against 0
+        // right behind the load, to carry one bit across the fill, and waits for it there)
+        asm volatile("" : "+v"(flag));
+        live_mixed = nt > 64;
+        if (!live_mixed) {
+            const int set = __popcll(__ballot(flag != 0u));
+            live_all = set == nt ? 0xFu : 0u;
+            live_mixed = set != 0 && set != nt;
+        }
+        if (live_mixed)
+            for (int t = threadIdx.x; t < cells / 32; t += kThreads) {
+                const int ly = t >> 2, cb = c0 + ((t & 3) << 5);
+                unsigned bits = 0u;
+                if (ly < h && cb < g.W) {
+                    const uint32_t* trow = touched + ((g.st_r0 + r0 + ly) / g.th) * g.tiles_x;
+                    int tc = cb / g.tw, next = (tc + 1) * g.tw;
+                    unsigned on = trow[tc] != 0u;
+                    const int n = min(32, g.W - cb);
+                    for (int k = 0; k < n; ++k) {
+                        if (cb + k >= next) { ++tc; next += g.tw; on = trow[tc] != 0u; }
+                        bits |= on << k;
+                    }
+                }
+                t_live[t] = bits;
+            }
     }
     __syncthreads();
 
@@ -711,21 +785,116 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
     __syncthreads();
 
     // merge pass: tile -> HBM planes.  Exclusive owner => plain RMW; a split bin => atomics.
-    const int bx = it.bin % b.bins_x, by = it.bin / b.bins_x;
-    const int c0 = bx * b.tile_w, r0 = b.row0 + by * b.tile_h;        // r0 relative to the state window
-    const int w = min(b.tile_w, g.W - c0), h = min(b.tile_h, b.row0 + b.rows - r0);
     const bool vec = !it.shared && (g.W % 4 == 0) && (w % 4 == 0) &&
                      ((((MASK & 1) ? reinterpret_cast<uintptr_t>(pl.sum) : 0) | ((MASK & 2) ? reinterpret_cast<uintptr_t>(pl.wgt) : 0) |
                        ((MASK & 4) ? reinterpret_cast<uintptr_t>(pl.mx) : 0) | ((MASK & 8) ? reinterpret_cast<uintptr_t>(pl.mn) : 0)) & 15) == 0;
+    // one lane = 4 consecutive cells of a row (wide LDS reads, float4 global accesses).  A tile row is 32 such quads, so a
+    // lane keeps its columns and moves down 32 rows per iteration: no division anywhere.
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const int lx = (threadIdx.x & 31) << 2, ly0 = threadIdx.x >> 5;
+    if (vec && full) {
+        // Every cell is stored (the planes are undefined: nothing is read), and FUSED the bands with them.  What a band
+        // takes is settled ahead of the loop -- the output kinds and pointers in scalar registers, whether any of them
+        // divides, the live flags (above) -- and the loop is ds_read -> convert -> stores, a quad's stores back to back,
+        // with the next quad's LDS reads issued ahead of them.
+        if (lx >= w || ly0 >= h) return;
+        const int n_out = FUSED ? fo.n : 0;
+        float* band[PCR_HIP_MAX_FINALIZE_OUTPUTS];
+        bool divides = false;
+        unsigned kinds = 0u;                                           // three bits per output
+#pragma unroll
+        for (int o = 0; o < PCR_HIP_MAX_FINALIZE_OUTPUTS; ++o) {
+            band[o] = fo.out[o];
+            kinds |= ((unsigned)fo.rtype[o] & 7u) << (3 * o);
+            divides |= o < n_out && (fo.rtype[o] == PCR_HIP_AVERAGE || fo.rtype[o] == PCR_HIP_WEIGHTED_AVERAGE);
+        }
+        // in a vector register: a kind the compiler knows to be wave-uniform becomes a ladder of scalar branches around
+        // every cell; like this it is four compares and selects per output
+        const unsigned vkinds = (unsigned)vector_resident((int)kinds);
+        struct Quad {
+            double2 slo, shi;
+            uint4 cnt;
+            float4 mx, mn;
+            unsigned live;
+        };
+        auto read = [&](int ly) {
+            Quad q{};
+            const int li = ly * kPointTileW + lx;
+            if (MASK & 1) { q.slo = *reinterpret_cast<const double2*>(t_sum + li); q.shi = *reinterpret_cast<const double2*>(t_sum + li + 2); }
+            if (MASK & 2) q.cnt = *reinterpret_cast<const uint4*>(t_wgt + li);
+            if (MASK & 4) q.mx = *reinterpret_cast<const float4*>(t_max + li);
+            if (MASK & 8) q.mn = *reinterpret_cast<const float4*>(t_min + li);
+            q.live = live_all;
+            if (FUSED && live_mixed) q.live = t_live[li >> 5];              // (this quad's bits: live_shift up)
+            return q;
+        };
+        const int live_shift = (FUSED && live_mixed) ? (lx & 31) : 0;
+        // Registers: the read-ahead quad is up to 20 VGPRs; with it every instantiation stays within 64 except the four-plane
+        // k_tile_accum<15, *> (68 fused, 66 not).  That costs no occupancy -- 1 024 threads are 4 waves per SIMD, which may
+        // have 128 VGPRs each, and the LDS tile allows one workgroup per CU anyway -- and taking the read-ahead away from
+        // that instantiation did not bring it under 64 either (the four planes' values and identities are what it holds).
+        Quad nq = read(ly0);
+        int64_t cell = (int64_t)(r0 + ly0) * g.W + (c0 + lx);
+        for (int ly = ly0; ly < h; ly += 32, cell += (int64_t)32 * g.W) {
+            const Quad q = nq;
+            if (ly + 32 < h) nq = read(ly + 32);
+            // identity + tile, as the read-modify-write of identity planes would give it
+            float s4[4] = {0.f, 0.f, 0.f, 0.f}, w4[4] = {0.f, 0.f, 0.f, 0.f};
+            float x4[4] = {-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX}, m4[4] = {FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX};
+            if (MASK & 1) { s4[0] += (float)q.slo.x; s4[1] += (float)q.slo.y; s4[2] += (float)q.shi.x; s4[3] += (float)q.shi.y; }
+            if (MASK & 2) { w4[0] += (float)q.cnt.x; w4[1] += (float)q.cnt.y; w4[2] += (float)q.cnt.z; w4[3] += (float)q.cnt.w; }
+            if (MASK & 4) { x4[0] = fmaxf(x4[0], q.mx.x); x4[1] = fmaxf(x4[1], q.mx.y); x4[2] = fmaxf(x4[2], q.mx.z); x4[3] = fmaxf(x4[3], q.mx.w); }
+            if (MASK & 8) { m4[0] = fminf(m4[0], q.mn.x); m4[1] = fminf(m4[1], q.mn.y); m4[2] = fminf(m4[2], q.mn.z); m4[3] = fminf(m4[3], q.mn.w); }
+            float cnt4[4], avg4[4], max4[4], min4[4];
+            if (FUSED) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {                          // finalize_rt's cases, each once per cell
+                    cnt4[k] = w4[k] > 0.0f ? w4[k] : NAN;
+                    avg4[k] = NAN;
+                    max4[k] = x4[k] == -FLT_MAX ? NAN : x4[k];
+                    min4[k] = m4[k] == FLT_MAX ? NAN : m4[k];
+                }
+                if (divides) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) avg4[k] = w4[k] > 0.0f ? s4[k] / w4[k] : NAN;
+                }
+            }
+            // the Sum / Count planes leave with non-temporal stores: nothing reads them before the finalize pass, and
+            // streaming 134 MB through the L2 only evicts the records still to be folded (C2 step -1.2 %)
+            if (MASK & 1) __builtin_nontemporal_store(f4v{s4[0], s4[1], s4[2], s4[3]}, reinterpret_cast<f4v*>(pl.sum + cell));
+            if (MASK & 2) __builtin_nontemporal_store(f4v{w4[0], w4[1], w4[2], w4[3]}, reinterpret_cast<f4v*>(pl.wgt + cell));
+            if (MASK & 4) *reinterpret_cast<float4*>(pl.mx + cell) = make_float4(x4[0], x4[1], x4[2], x4[3]);
+            if (MASK & 8) *reinterpret_cast<float4*>(pl.mn + cell) = make_float4(m4[0], m4[1], m4[2], m4[3]);
+            if (FUSED) {
+                // (the owned rows are the state window: a band cell has the plane cell's index)
+#pragma unroll
+                for (int o = 0; o < PCR_HIP_MAX_FINALIZE_OUTPUTS; ++o) {
+                    if (o >= n_out) break;
+                    const unsigned kind = (vkinds >> (3 * o)) & 7u;
+                    const bool is_sum = kind == PCR_HIP_SUM, is_cnt = kind == PCR_HIP_COUNT, is_max = kind == PCR_HIP_MAX, is_min = kind == PCR_HIP_MIN;
+                    float v[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float f = avg4[k];
+                        f = is_min ? min4[k] : f;
+                        f = is_max ? max4[k] : f;
+                        f = is_cnt ? cnt4[k] : f;
+                        f = is_sum ? s4[k] : f;
+                        v[k] = ((q.live >> (live_shift + k)) & 1u) ? f : NAN;
+                    }
+                    __builtin_nontemporal_store(f4v{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4v*>(band[o] + cell));
+                }
+            }
+        }
+        return;
+    }
     if (vec) {
-        // one lane = 4 consecutive cells of a row: wide LDS reads, float4 global RMW; the planes'
-        // loads of an iteration are independent and issued together
-        const int qrow = b.tile_w >> 2;
-        for (int i = threadIdx.x; i < qrow * h; i += kThreads) {
-            int ly = i / qrow, lx = (i - ly * qrow) << 2;
-            if (lx >= w) continue;
+        // the planes hold identity values (fresh) or earlier contributions: stored / read-modify-written where the tile has
+        // something; the planes' loads of an iteration are independent and issued together
+        if (lx >= w) return;
+        for (int ly = ly0; ly < h; ly += 32) {
             int64_t cell = (int64_t)(r0 + ly) * g.W + (c0 + lx);
-            int li = ly * b.tile_w + lx;
+            int li = ly * kPointTileW + lx;
             float4 a1, a2, a4, a8, g1, g2, g4, g8;
             bool n1 = false, n2 = false, n4 = false, n8 = false;
             if (MASK & 1) {
@@ -752,33 +921,13 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
                 if ((MASK & 4) && n4) g4 = *reinterpret_cast<const float4*>(pl.mx + cell);
                 if ((MASK & 8) && n8) g8 = *reinterpret_cast<const float4*>(pl.mn + cell);
             }
-            // the Sum / Count planes leave with non-temporal stores: nothing reads them before the finalize pass, and
-            // streaming 134 MB through the L2 only evicts the records still to be folded (C2 step -1.2 %)
-            typedef float f4v __attribute__((ext_vector_type(4)));
-            if (full) n1 = n2 = n4 = n8 = true;
+            // (non-temporal, as above)
             if ((MASK & 1) && n1) { g1.x += a1.x; g1.y += a1.y; g1.z += a1.z; g1.w += a1.w;
                 __builtin_nontemporal_store(f4v{g1.x, g1.y, g1.z, g1.w}, reinterpret_cast<f4v*>(pl.sum + cell)); }
             if ((MASK & 2) && n2) { g2.x += a2.x; g2.y += a2.y; g2.z += a2.z; g2.w += a2.w;
                 __builtin_nontemporal_store(f4v{g2.x, g2.y, g2.z, g2.w}, reinterpret_cast<f4v*>(pl.wgt + cell)); }
             if ((MASK & 4) && n4) { g4.x = fmaxf(g4.x, a4.x); g4.y = fmaxf(g4.y, a4.y); g4.z = fmaxf(g4.z, a4.z); g4.w = fmaxf(g4.w, a4.w); *reinterpret_cast<float4*>(pl.mx + cell) = g4; }
             if ((MASK & 8) && n8) { g8.x = fminf(g8.x, a8.x); g8.y = fminf(g8.y, a8.y); g8.z = fminf(g8.z, a8.z); g8.w = fminf(g8.w, a8.w); *reinterpret_cast<float4*>(pl.mn + cell) = g8; }
-            if (FUSED && full) {
-                // (the owned rows are the state window: a band cell has the plane cell's index)
-                const float s4[4] = {g1.x, g1.y, g1.z, g1.w}, w4[4] = {g2.x, g2.y, g2.z, g2.w};
-                const float x4[4] = {g4.x, g4.y, g4.z, g4.w}, m4[4] = {g8.x, g8.y, g8.z, g8.w};
-                const int trow = ((g.st_r0 + r0 + ly) / g.th) * g.tiles_x;
-                bool live[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) live[k] = touched[trow + (c0 + lx + k) / g.tw] != 0u;
-                for (int o = 0; o < fo.n; ++o) {
-                    float v[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        v[k] = live[k] ? finalize_rt(fo.rtype[o], (MASK & 1) ? s4[k] : 0.f, (MASK & 2) ? w4[k] : 0.f,
-                                                     (MASK & 4) ? x4[k] : -FLT_MAX, (MASK & 8) ? m4[k] : FLT_MAX) : NAN;
-                    __builtin_nontemporal_store(f4v{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4v*>(fo.out[o] + cell));
-                }
-            }
         }
         return;
     }
@@ -827,7 +976,8 @@ k_fill_if(const unsigned* __restrict__ n_items, PlanesDev pl, unsigned mask, int
 template <unsigned MASK>
 void launch_accum(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const PlanesDev& pl, const BinBuffers& bb,
                   bool fused = false) {
-    size_t lds = (size_t)b.tile_w * b.tile_h * tile_cell_bytes(MASK);
+    // (the fused merge's live map comes with point_tile_lds; the other launches leave it out)
+    const size_t lds = fused ? point_tile_lds(tile_cell_bytes(MASK), b.tile_h) : (size_t)b.tile_w * b.tile_h * tile_cell_bytes(MASK);
     // fresh: only when every bin is owned by one workgroup of this launch can a store replace the read-modify-write
     auto go = [&](auto kernel, const FinalizeOuts& fo, uint32_t* done) {
         allow_dynamic_lds(e, reinterpret_cast<const void*>(kernel), lds);
@@ -1133,7 +1283,7 @@ int sweep_tiles(pcr_hip_engine* e, const BinGeom& whole, const double* x, const 
 
 bool binned_point_supported(const pcr_hip_engine* e, uint32_t mask) {
     if (mask == 0 || (mask & ~15u)) return false;
-    if (sweep_passes(e, point_bin_geom(e->gd, mask)) < 1) return false;
+    if (sweep_passes(e, point_bin_geom(e, mask)) < 1) return false;
     // not worth the fixed cost of sweeping every tile for a handful of points
     uint64_t cells = (uint64_t)e->gd.W * e->gd.st_rows;
     if (e->forced_path != 2 && e->stats.points_in * 16 < cells) return false;
@@ -1142,7 +1292,7 @@ bool binned_point_supported(const pcr_hip_engine* e, uint32_t mask) {
 
 int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
                  const double* x, const double* y, const float* v, uint64_t n) {
-    const BinGeom whole = point_bin_geom(e->gd, mask);
+    const BinGeom whole = point_bin_geom(e, mask);
     // Undefined planes (pcr_hip_engine_planes_fresh(e, 2)): one pass of bins covers the whole state window, so the tile
     // pass can define every cell itself -- an item for every bin, every cell stored -- and the state initialisation costs
     // no pass of its own.  Needs whole float4 groups per plane row (the merge's vector form is per row, the scalar form
@@ -1195,7 +1345,7 @@ bool binned_select_supported(const pcr_hip_engine* e) { return binned_point_supp
 // the tile pass.
 int binned_select(pcr_hip_engine* e, unsigned long long* packed, const double* x, const double* y, const float* v,
                   const float* key, uint64_t n) {
-    const BinGeom whole = point_bin_geom(e->gd, kSelectGeomMask);
+    const BinGeom whole = point_bin_geom(e, kSelectGeomMask);
     const int64_t cells = (int64_t)e->gd.st_rows * e->gd.W;
     // undefined plane: one pass of bins over the whole window lets the tile pass store every word itself (16-byte groups)
     const bool define_all = e->planes_fresh == 2 && sweep_passes(e, whole) == 1 && cells % 2 == 0 && e->gd.W % 2 == 0 &&
