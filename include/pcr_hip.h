@@ -474,6 +474,17 @@ int pcr_hip_transform_xy(const pcr_hip_crs_desc* src, const pcr_hip_crs_desc* ds
 int pcr_hip_transform_xy_host(const pcr_hip_crs_desc* src, const pcr_hip_crs_desc* dst, const double* h_x, const double* h_y,
                               double* h_out_x, double* h_out_y, uint64_t n);
 
+/* ---- overview pyramid of one band (GeoTIFF overviews; pcr/io/grid_io.h: build_overviews).  Level k (k >= 1) is made from
+ *      level k-1 (level 0 = src) and is ceil(w/2) x ceil(h/2) cells; cell (r, c) looks at (2r, 2c), (2r, 2c+1), (2r+1, 2c),
+ *      (2r+1, 2c+1); a cell outside the source or a NaN cell is invalid.  mode 0 "average": the invalid cells contribute
+ *      +0.0f, s = ((a + b) + c) + d in binary32, result s / n over the n valid cells (a true division), NaN when n == 0;
+ *      every NaN made here (Inf + -Inf included) is 0x7FC00000.  mode 1 "nearest": cell (2r, 2c), copied bit for bit.
+ *      src: `height` rows of `width` floats, `src_stride` floats apart (any 4-byte alignment; rows that start on 16 bytes
+ *      take the 16-byte loads).  dst: a HOST array of `levels` device pointers, dense planes of the levels' sizes.  The
+ *      source is read once per six levels; everything is enqueued on s, nothing is allocated or synchronised. */
+int pcr_hip_downsample2(const float* src, int width, int height, int64_t src_stride, float* const* dst, int levels, int mode,
+                        pcr_hip_stream s);
+
 #ifdef __cplusplus
 }
 #endif

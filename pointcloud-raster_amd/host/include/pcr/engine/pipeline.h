@@ -69,8 +69,9 @@ struct PipelineConfig {
     std::string state_dir;
     bool resume = false;
 
-    std::string output_path;                         // GeoTIFF writing is not part of this build
-    bool write_cog = false;
+    std::string output_path;                         // finalize() writes the result there as GeoTIFF (pcr/io/grid_io.h)
+    bool write_cog = false;                          // with overview levels (GeoTiffOptions::overviews = -1); the HIP engine
+                                                     // builds them in HBM and copies only the levels out
 
     // ---- extensions (not in the reference; defaults keep reference behaviour) ----------
     MemoryLocation result_location = MemoryLocation::Host;   // Device: finalize() leaves bands in HBM

@@ -81,6 +81,7 @@ private:
     int rank_ = 0, world_ = 1, r0_ = 0, r1_ = 0, halo_ = 0, width_ = 0, height_ = 0, align_ = 1;
     GridConfig grid_;                 // the WHOLE grid
     std::string output_path_;         // taken from the configuration: rank 0 writes ONE GeoTIFF at finalize()
+    bool write_cog_ = false;          // ... with overview levels
     std::string state_dir_;
     std::vector<ReductionSpec> reductions_;
     CRS target_crs_;                  // with auto_reproject_: ingest_unrouted reprojects before it routes

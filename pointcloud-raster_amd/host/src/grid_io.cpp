@@ -5,6 +5,7 @@
 // GeoTIFF 1.0 section 2.6-2.7 (tags 33550, 33922, 34264, 34735, 34737); GDAL's private tags 42112 / 42113.
 #include "pcr/io/grid_io.h"
 
+#include "overviews.h"
 #include "pcr/core/grid.h"
 
 #include <zlib.h>
@@ -202,7 +203,25 @@ public:
         if (spec.big) { hdr[2] = 43; hdr[4] = 8; }
         else hdr[2] = 42;
         pos_ = spec.big ? 16 : 8;
+        link_pos_ = spec.big ? 8 : 4;
+        overview_ = false;
+        dir_written_ = false;
         if (std::fwrite(hdr, 1, pos_, f_) != pos_) return io_error();
+        return Status::success();
+    }
+
+    // The image so far gets its directory; what follows is a reduced-resolution image of it (an overview level), whose
+    // directory is chained behind the last one.
+    Status next_image(const TiffSpec& spec) {
+        if (!f_) return Status::error(StatusCode::InvalidArgument, "writer not open");
+        if (!dir_written_) { Status s = finish_image(); if (!s.ok()) return s; }
+        spec_ = spec;
+        bxn_ = (spec.W + spec.bw - 1) / spec.bw;
+        byn_ = (spec.H + spec.bh - 1) / spec.bh;
+        offsets_.assign((size_t)bxn_ * byn_ * spec.nb, 0);
+        counts_.assign(offsets_.size(), 0);
+        overview_ = true;
+        dir_written_ = false;
         return Status::success();
     }
 
@@ -255,6 +274,15 @@ public:
 
     Status close() {
         if (!f_) return Status::error(StatusCode::InvalidArgument, "writer not open");
+        Status s = dir_written_ ? Status::success() : finish_image();
+        const bool bad = std::fclose(f_) != 0;
+        f_ = nullptr;
+        if (!s.ok()) return s;
+        return bad ? Status::error(StatusCode::IoError, "failed to write GeoTIFF") : Status::success();
+    }
+
+private:
+    Status finish_image() {
         // blocks nobody wrote share one all-nodata block
         uint64_t fill_off[2] = {0, 0}, fill_cnt[2] = {0, 0};       // [0] full block, [1] short last strip
         for (size_t i = 0; i < offsets_.size(); ++i) {
@@ -274,19 +302,18 @@ public:
                 counts_[i] = fill_cnt[kind];
             }
         }
-        Status s = write_directory();
-        const bool bad = std::fclose(f_) != 0;
-        f_ = nullptr;
-        if (!s.ok()) return s;
-        return bad ? Status::error(StatusCode::IoError, "failed to write GeoTIFF") : Status::success();
+        dir_written_ = true;
+        return write_directory();
     }
 
-private:
     TiffSpec spec_;
     GridConfig cfg_;
     std::vector<std::string> names_;
     FILE* f_ = nullptr;
     uint64_t pos_ = 0;
+    uint64_t link_pos_ = 0;           // where the offset of the next directory goes: the header, then each directory's last field
+    bool overview_ = false;           // the current image is an overview level: NewSubfileType, no georeferencing or metadata
+    bool dir_written_ = false;
     int bxn_ = 0, byn_ = 0;
     std::vector<uint64_t> offsets_, counts_;
     std::vector<float> raw_;
@@ -367,6 +394,7 @@ private:
     Status write_directory() {
         std::vector<TagOut> tags;
         const int nb = spec_.nb;
+        if (overview_) add_long(tags, 254, 1);                         // NewSubfileType: reduced-resolution image
         add_long(tags, 256, (uint32_t)spec_.W);
         add_long(tags, 257, (uint32_t)spec_.H);
         add_shorts(tags, 258, std::vector<uint16_t>(nb, 32));
@@ -387,6 +415,13 @@ private:
         if (nb > 1) add_shorts(tags, 338, std::vector<uint16_t>(nb - 1, 0));   // extra samples: unspecified
         add_shorts(tags, 339, std::vector<uint16_t>(nb, 3));           // IEEE floating point
 
+        if (!overview_) add_georeferencing(tags);
+        add_ascii(tags, 42113, "nan");
+        return put_directory(tags);
+    }
+
+    void add_georeferencing(std::vector<TagOut>& tags) {
+        const int nb = spec_.nb;
         // georeferencing: cell (col, row) corner -> world (gdal_geotransform of the reference)
         const double csx = cfg_.cell_size_x, csy = cfg_.cell_size_y;
         if (csy < 0.0 && csx > 0.0) {
@@ -421,8 +456,9 @@ private:
                 md << "  <Item name=\"DESCRIPTION\" sample=\"" << b << "\" role=\"description\">" << xml_escape(names_[b]) << "</Item>\n";
         md << "</GDALMetadata>\n";
         add_ascii(tags, 42112, md.str());
-        add_ascii(tags, 42113, "nan");
+    }
 
+    Status put_directory(std::vector<TagOut>& tags) {
         std::sort(tags.begin(), tags.end(), [](const TagOut& a, const TagOut& b) { return a.tag < b.tag; });
         // out-of-line values first, then the directory
         const size_t inline_cap = spec_.big ? 8 : 4;
@@ -454,16 +490,20 @@ private:
             return Status::error(StatusCode::IoError, "GeoTIFF larger than 4 GB needs options.bigtiff");
         Status s = put_bytes(dir.data(), dir.size());
         if (!s.ok()) return s;
-        if (std::fseek(f_, spec_.big ? 8 : 4, SEEK_SET) != 0) return io_error();
+        if (std::fseek(f_, (long)link_pos_, SEEK_SET) != 0) return io_error();
         if (spec_.big) { if (std::fwrite(&ifd, 8, 1, f_) != 1) return io_error(); }
         else { const uint32_t w = (uint32_t)ifd; if (std::fwrite(&w, 4, 1, f_) != 1) return io_error(); }
+        link_pos_ = ifd + dir.size() - (spec_.big ? 8 : 4);
+        if (std::fseek(f_, (long)pos_, SEEK_SET) != 0) return io_error();
         return Status::success();
     }
 };
 
 Status make_spec(const GridConfig& cfg, int nb, const GeoTiffOptions& opt, TiffSpec* out) {
     if (opt.cloud_optimized)
-        return Status::error(StatusCode::NotImplemented, "cloud-optimized GeoTIFF (overviews) is not implemented in this build");
+        return Status::error(StatusCode::NotImplemented,
+                             "the cloud-optimized GeoTIFF layout is not implemented in this build: set options.overviews for a "
+                             "file with overview levels in the ordinary layout");
     TiffSpec s;
     s.W = cfg.width;
     s.H = cfg.height;
@@ -492,6 +532,31 @@ Status make_spec(const GridConfig& cfg, int nb, const GeoTiffOptions& opt, TiffS
     return Status::success();
 }
 
+// Level 0's layout at an overview level's size: the same tiles, or strips by the strip rule on its own width.
+TiffSpec level_spec(const TiffSpec& base, int w, int h) {
+    TiffSpec s = base;
+    s.W = w;
+    s.H = h;
+    if (!s.tiled) {
+        s.bw = w;
+        s.bh = std::max(1, std::min(h, 65536 / std::max(1, w)));
+    }
+    return s;
+}
+
+std::vector<TiffOut::Job> block_jobs(const Grid& grid, const TiffSpec& spec, Status* st) {
+    const int bxn = (spec.W + spec.bw - 1) / spec.bw, byn = (spec.H + spec.bh - 1) / spec.bh;
+    std::vector<TiffOut::Job> jobs;
+    for (int b = 0; b < grid.num_bands(); ++b) {
+        const float* band = grid.band_f32(b);
+        if (!band) { *st = Status::error(StatusCode::IoError, "failed to get band " + std::to_string(b)); return {}; }
+        for (int by = 0; by < byn; ++by)
+            for (int bx = 0; bx < bxn; ++bx)
+                jobs.push_back({b, bx, by, band + (int64_t)by * spec.bh * spec.W + (int64_t)bx * spec.bw, spec.W});
+    }
+    return jobs;
+}
+
 // ---- TIFF input --------------------------------------------------------------------------------------
 struct TagIn {
     uint16_t type = 0;
@@ -514,9 +579,11 @@ struct TiffIn {
     bool big = false;
     uint64_t file_size = 0;
     std::map<uint16_t, TagIn> tags;
+    uint64_t next_ifd = 0;                 // of the directory in `tags`; 0 = the last one
     ~TiffIn() { if (f) std::fclose(f); }
 
-    Status open(const std::string& path) {
+    // `level`: which image of the file (0 = the first directory, k = k directories down the chain)
+    Status open(const std::string& path, int level = 0) {
         f = std::fopen(path.c_str(), "rb");
         if (!f) return Status::error(StatusCode::IoError, "failed to open file: " + path);
         uint8_t h[16];
@@ -531,6 +598,17 @@ struct TiffIn {
         } else return Status::error(StatusCode::IoError, "not a TIFF file: " + path);
         std::fseek(f, 0, SEEK_END);
         file_size = (uint64_t)std::ftell(f);
+        Status s = read_directory(ifd);
+        for (int k = 0; k < level && s.ok(); ++k) {
+            if (!next_ifd) return Status::error(StatusCode::InvalidArgument, "overview level out of range");
+            s = read_directory(next_ifd);
+        }
+        return s;
+    }
+
+    Status read_directory(uint64_t ifd) {
+        tags.clear();
+        next_ifd = 0;
         if (ifd >= file_size || std::fseek(f, (long)ifd, SEEK_SET) != 0)
             return Status::error(StatusCode::IoError, "bad TIFF directory offset");
         uint64_t n = 0;
@@ -540,6 +618,8 @@ struct TiffIn {
         const size_t esz = big ? 20 : 12, cap = big ? 8 : 4;
         std::vector<uint8_t> dir(n * esz);
         if (n && std::fread(dir.data(), 1, dir.size(), f) != dir.size()) return bad();
+        if (big) { if (std::fread(&next_ifd, 8, 1, f) != 1) next_ifd = 0; }
+        else { uint32_t o = 0; if (std::fread(&o, 4, 1, f) != 1) o = 0; next_ifd = o; }
         for (uint64_t i = 0; i < n; ++i) {
             const uint8_t* e = &dir[i * esz];
             uint16_t tag, type;
@@ -621,8 +701,8 @@ Status read_geom(const TiffIn& t, TiffGeom* g) {
     if (g->tiled) { g->bw = (int)t.uint_at(322, 0); g->bh = (int)t.uint_at(323, 0); }
     else { g->bw = g->W; g->bh = (int)std::min<uint64_t>(t.uint_at(278, 0, (uint64_t)g->H), (uint64_t)g->H); }
     if (g->bw <= 0 || g->bh <= 0) return Status::error(StatusCode::IoError, "TIFF with empty blocks");
-    g->bxn = (g->W + g->bw - 1) / g->bw;
-    g->byn = (g->H + g->bh - 1) / g->bh;
+    g->bxn = (int)(((int64_t)g->W + g->bw - 1) / g->bw);             // (a corrupt size may be near INT_MAX)
+    g->byn = (int)(((int64_t)g->H + g->bh - 1) / g->bh);
     return Status::success();
 }
 
@@ -630,6 +710,11 @@ Status read_geom(const TiffIn& t, TiffGeom* g) {
 
 // ---- writer API ----------------------------------------------------------------------------------------
 Status write_geotiff(const std::string& path, const Grid& grid, const GridConfig& config, const GeoTiffOptions& options) {
+    return write_geotiff(path, grid, config, options, std::vector<const Grid*>());
+}
+
+Status write_geotiff(const std::string& path, const Grid& grid, const GridConfig& config, const GeoTiffOptions& options,
+                     const std::vector<const Grid*>& overviews) {
     if (grid.location() != MemoryLocation::Host && grid.location() != MemoryLocation::HostPinned)
         return Status::error(StatusCode::InvalidArgument, "grid must be on host");
     if (grid.cols() != config.width || grid.rows() != config.height)
@@ -637,20 +722,43 @@ Status write_geotiff(const std::string& path, const Grid& grid, const GridConfig
     TiffSpec spec;
     Status s = make_spec(config, grid.num_bands(), options, &spec);
     if (!s.ok()) return s;
+    if (options.overviews != 0 && detail::overview_mode(options.overview_resampling) < 0)
+        return Status::error(StatusCode::InvalidArgument, "unknown overview_resampling: " + options.overview_resampling);
+    // the overview levels: the caller's, or (options.overviews != 0 and none supplied) built here
+    std::vector<std::unique_ptr<Grid>> built;
+    std::vector<const Grid*> levels = overviews;
+    if (levels.empty() && options.overviews != 0) {
+        const int n = detail::overview_levels(options.overviews, grid.cols(), grid.rows());
+        if (n < 0) return Status::error(StatusCode::InvalidArgument, "more overview levels than the grid has down to 1x1");
+        if (n > 0 && !(s = detail::build_overviews_host(grid, n, detail::overview_mode(options.overview_resampling), built)).ok())
+            return s;
+        for (const auto& g : built) levels.push_back(g.get());
+    } else if (!levels.empty()) {
+        int w = grid.cols(), h = grid.rows();
+        for (const Grid* g : levels) {
+            if (w == 1 && h == 1) return Status::error(StatusCode::InvalidArgument, "more overview levels than the grid has");
+            w = (w + 1) / 2;
+            h = (h + 1) / 2;
+            if (!g || (g->location() != MemoryLocation::Host && g->location() != MemoryLocation::HostPinned))
+                return Status::error(StatusCode::InvalidArgument, "overview levels must be on host");
+            if (g->cols() != w || g->rows() != h || g->num_bands() != grid.num_bands())
+                return Status::error(StatusCode::InvalidArgument, "overview level does not have the cascade's size and band count");
+        }
+    }
     std::vector<std::string> names;
     for (int b = 0; b < grid.num_bands(); ++b) names.push_back(grid.band_desc(b).name);
     TiffOut out;
     if (!(s = out.open(path, spec, config, names)).ok()) return s;
-    const int bxn = (spec.W + spec.bw - 1) / spec.bw, byn = (spec.H + spec.bh - 1) / spec.bh;
-    std::vector<TiffOut::Job> jobs;
-    for (int b = 0; b < grid.num_bands(); ++b) {
-        const float* band = grid.band_f32(b);
-        if (!band) return Status::error(StatusCode::IoError, "failed to get band " + std::to_string(b));
-        for (int by = 0; by < byn; ++by)
-            for (int bx = 0; bx < bxn; ++bx)
-                jobs.push_back({b, bx, by, band + (int64_t)by * spec.bh * spec.W + (int64_t)bx * spec.bw, spec.W});
-    }
+    std::vector<TiffOut::Job> jobs = block_jobs(grid, spec, &s);
+    if (!s.ok()) return s;
     if (!(s = out.write_blocks(jobs)).ok()) return s;
+    for (const Grid* g : levels) {
+        const TiffSpec ls = level_spec(spec, g->cols(), g->rows());
+        if (!(s = out.next_image(ls)).ok()) return s;
+        jobs = block_jobs(*g, ls, &s);
+        if (!s.ok()) return s;
+        if (!(s = out.write_blocks(jobs)).ok()) return s;
+    }
     return out.close();
 }
 
@@ -676,6 +784,7 @@ std::unique_ptr<TiledGeoTiffWriter> TiledGeoTiffWriter::open(const std::string& 
     Impl& s = *w->impl_;
     s.config = config;
     s.num_bands = (int)band_names.size();
+    if (options.overviews != 0) return nullptr;           // overviews need the whole image, which this writer never sees
     if (!make_spec(config, s.num_bands, options, &s.spec).ok()) return nullptr;
     const int tiles_x = (config.width + config.tile_width - 1) / config.tile_width;
     const int tiles_y = (config.height + config.tile_height - 1) / config.tile_height;
@@ -780,11 +889,29 @@ Status read_geotiff_info(const std::string& path, int& width, int& height, int& 
     return Status::success();
 }
 
-Status read_geotiff_band(const std::string& path, int band_index, float* data, int width, int height) {
-    if (!data) return Status::error(StatusCode::InvalidArgument, "null data pointer");
-    if (band_index < 0) return Status::error(StatusCode::InvalidArgument, "invalid band index");
+Status read_geotiff_overviews(const std::string& path, std::vector<std::pair<int, int>>& sizes) {
+    sizes.clear();
     TiffIn t;
     Status s = t.open(path);
+    if (!s.ok()) return s;
+    for (int k = 0; k < 64 && t.next_ifd; ++k) {                        // (a bound, against a chain that loops)
+        if (!(s = t.read_directory(t.next_ifd)).ok()) return s;
+        if (!(t.uint_at(254, 0) & 1)) continue;                         // a further page, not a reduced-resolution image
+        sizes.emplace_back((int)t.uint_at(256, 0), (int)t.uint_at(257, 0));
+    }
+    return Status::success();
+}
+
+Status read_geotiff_band(const std::string& path, int band_index, float* data, int width, int height) {
+    return read_geotiff_band_level(path, 0, band_index, data, width, height);
+}
+
+Status read_geotiff_band_level(const std::string& path, int level, int band_index, float* data, int width, int height) {
+    if (!data) return Status::error(StatusCode::InvalidArgument, "null data pointer");
+    if (band_index < 0) return Status::error(StatusCode::InvalidArgument, "invalid band index");
+    if (level < 0) return Status::error(StatusCode::InvalidArgument, "invalid overview level");
+    TiffIn t;
+    Status s = t.open(path, level);
     if (!s.ok()) return s;
     TiffGeom g;
     if (!(s = read_geom(t, &g)).ok()) return s;

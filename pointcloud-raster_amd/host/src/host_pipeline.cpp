@@ -189,7 +189,7 @@ Status Pipeline::Host::finalize() {
     for (size_t r = 0; r < outputs.size(); ++r)
         engine->finalize(groups[(size_t)outputs[r].group].planes, outputs[r].type, result->band_f32((int)r));
     finalized = true;
-    if (!cfg.output_path.empty()) return write_geotiff(cfg.output_path, *result, g, GeoTiffOptions());    // pipeline.cpp:1351-1361
+    if (!cfg.output_path.empty()) return write_geotiff(cfg.output_path, *result, g, pipeline_output_options(cfg.write_cog));    // pipeline.cpp:1351-1361
     return Status::success();
 }
 

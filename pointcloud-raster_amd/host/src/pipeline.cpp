@@ -13,6 +13,7 @@
 
 #include "buffer.h"
 #include "host_pipeline.h"
+#include "overviews.h"
 #include "pipeline_common.h"
 #include "pcr/core/grid.h"
 #include "pcr/core/point_cloud.h"
@@ -755,6 +756,37 @@ struct Pipeline::Impl {
                 }
             }
         }
+        // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
+        // kernels on the same stream; only the levels (a third of the data) cross the bus, the host never halves the grid.
+        std::vector<std::unique_ptr<Grid>> levels;
+        const GeoTiffOptions out_opt = pipeline_output_options(cfg.write_cog);
+        if (!cfg.output_path.empty() && out_opt.overviews != 0) {
+            const int n = detail::overview_levels(out_opt.overviews, W, rows);
+            if (n > 0) {
+                std::vector<const float*> dev_bands;
+                std::vector<BandDesc> descs;
+                for (size_t r = 0; r < outputs.size(); ++r) {
+                    dev_bands.push_back(band_device(r));
+                    descs.push_back(result->band_desc((int)r));
+                }
+                std::vector<std::unique_ptr<Grid>> d_levels;
+                s = detail::build_overviews_device(dev_bands, W, rows, descs, n, detail::overview_mode(out_opt.overview_resampling),
+                                                   stream, d_levels);
+                if (!s.ok()) return s;
+                enqueued = true;
+                for (const auto& d : d_levels) {
+                    auto h = Grid::create_host_page_locked(d->cols(), d->rows(), descs);
+                    if (!h) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate the overview levels");
+                    if (!(s = h->copy_from(*d, stream)).ok()) return s;
+                    levels.push_back(std::move(h));
+                }
+                s = detail::hip_status(pcr_hip_stream_synchronize(stream));      // d_levels is released at the end of this block
+                if (!s.ok()) return s;
+                enqueued = false;
+            }
+        }
+        std::vector<const Grid*> level_ptrs;
+        for (const auto& l : levels) level_ptrs.push_back(l.get());
         // finalize_async: a device-resident result is stream-ordered like everything else on the device
         if ((wait || !on_device || !cfg.output_path.empty()) && enqueued) {
             s = detail::hip_status(pcr_hip_stream_synchronize(stream));
@@ -774,9 +806,9 @@ struct Pipeline::Impl {
             if (on_device) {
                 std::unique_ptr<Grid> host = result->to(MemoryLocation::Host);
                 if (!host) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to copy the result grid to the host");
-                return write_geotiff(cfg.output_path, *host, out_cfg, GeoTiffOptions());
+                return write_geotiff(cfg.output_path, *host, out_cfg, out_opt, level_ptrs);
             }
-            return write_geotiff(cfg.output_path, *result, out_cfg, GeoTiffOptions());
+            return write_geotiff(cfg.output_path, *result, out_cfg, out_opt, level_ptrs);
         }
         return Status::success();
     }
@@ -1240,7 +1272,7 @@ struct Pipeline::Banded {
             else if (!(s = evict()).ok()) return s;
         }
         finalized = true;
-        if (!cfg.output_path.empty()) return write_geotiff(cfg.output_path, *result, cfg.grid, GeoTiffOptions());
+        if (!cfg.output_path.empty()) return write_geotiff(cfg.output_path, *result, cfg.grid, pipeline_output_options(cfg.write_cog));
         return Status::success();
     }
 

@@ -54,6 +54,7 @@ std::unique_ptr<ShardedPipeline> ShardedPipeline::create(PipelineConfig cfg, con
     // ONE file for the whole grid, written by rank 0 from the gathered strips (the reference writes one file,
     // src/engine/pipeline.cpp:1351-1361) -- not a strip per rank under the same name
     sp->output_path_ = cfg.output_path;
+    sp->write_cog_ = cfg.write_cog;
     cfg.output_path.clear();
     sp->state_dir_ = cfg.state_dir;
     sp->reductions_ = cfg.reductions;
@@ -153,7 +154,7 @@ Status ShardedPipeline::finalize() {
     std::unique_ptr<Grid> whole;
     if (!(s = gather(0, &whole)).ok()) return s;
     if (rank_ != 0) return s;
-    return write_geotiff(output_path_, *whole, grid_, GeoTiffOptions());
+    return write_geotiff(output_path_, *whole, grid_, pipeline_output_options(write_cog_));
 }
 
 Status ShardedPipeline::save_state(const std::string& dir_in) {

@@ -205,6 +205,11 @@ void bind_core(py::module_& m) {
             if (!h) throw std::runtime_error("Failed to copy grid to Host memory");
             return h;
         })
+        .def("to", [](const Grid& g, MemoryLocation loc) {
+            auto d = g.to(loc);
+            if (!d) throw std::runtime_error("Failed to copy the grid (HIP out of memory or no usable GPU)");
+            return d;
+        }, py::arg("location"), "A copy of the grid in `location` (MemoryLocation.Device: in GPU memory)")
         .def("__repr__", [](const Grid& g) {
             return "Grid(cols=" + std::to_string(g.cols()) + ", rows=" + std::to_string(g.rows()) +
                    ", bands=" + std::to_string(g.num_bands()) + ")";

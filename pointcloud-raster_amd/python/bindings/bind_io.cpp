@@ -56,7 +56,8 @@ void bind_io(py::module_& m) {
         .def_readwrite("tile_width", &GeoTiffOptions::tile_width)
         .def_readwrite("tile_height", &GeoTiffOptions::tile_height)
         .def_readwrite("bigtiff", &GeoTiffOptions::bigtiff)
-        .def_readwrite("overview_resampling", &GeoTiffOptions::overview_resampling);
+        .def_readwrite("overview_resampling", &GeoTiffOptions::overview_resampling)
+        .def_readwrite("overviews", &GeoTiffOptions::overviews);
 
     py::class_<PointCloudInfo>(m, "PointCloudInfo")
         .def(py::init<>())
@@ -95,9 +96,25 @@ void bind_io(py::module_& m) {
         }, py::arg("tile_row"), py::arg("tile_col"), py::arg("data"))
         .def("close", [](TiledGeoTiffWriter& w) { raise_if_error(w.close()); });
 
-    m.def("write_geotiff", [](const std::string& path, const Grid& grid, const GridConfig& config, const GeoTiffOptions& options) {
-        raise_if_error(write_geotiff(path, grid, config, options));
-    }, py::arg("path"), py::arg("grid"), py::arg("config"), py::arg("options") = GeoTiffOptions());
+    m.def("write_geotiff", [](const std::string& path, const Grid& grid, const GridConfig& config, const GeoTiffOptions& options,
+                              py::object overviews) {
+        std::vector<const Grid*> levels;                    // None: built by the writer when options.overviews != 0
+        if (!overviews.is_none()) levels = overviews.cast<std::vector<const Grid*>>();
+        raise_if_error(write_geotiff(path, grid, config, options, levels));
+    }, py::arg("path"), py::arg("grid"), py::arg("config"), py::arg("options") = GeoTiffOptions(),
+       py::arg("overviews") = py::none());
+    // extension: the overview levels of a grid, made where it lives (a Device grid: in HBM)
+    m.def("build_overviews", [](const Grid& grid, int levels, const std::string& resampling) {
+        Status s;
+        auto out = build_overviews(grid, levels, resampling, &s, nullptr);
+        raise_if_error(s);
+        return out;
+    }, py::arg("grid"), py::arg("levels") = -1, py::arg("resampling") = "average");
+    m.def("read_geotiff_overviews", [](const std::string& path) {
+        std::vector<std::pair<int, int>> sizes;
+        raise_if_error(read_geotiff_overviews(path, sizes));
+        return sizes;
+    }, py::arg("path"));
     m.def("read_geotiff_info", [](const std::string& path) {
         int w = 0, h = 0, nb = 0;
         CRS crs;
@@ -105,15 +122,22 @@ void bind_io(py::module_& m) {
         raise_if_error(read_geotiff_info(path, w, h, nb, crs, bounds));
         return py::make_tuple(w, h, nb, crs, bounds);
     }, py::arg("path"));
-    m.def("read_geotiff_band", [](const std::string& path, int band_index) {
+    m.def("read_geotiff_band", [](const std::string& path, int band_index, int level) {
         int w = 0, h = 0, nb = 0;
         CRS crs;
         BBox bounds;
         raise_if_error(read_geotiff_info(path, w, h, nb, crs, bounds));
+        if (level != 0) {
+            std::vector<std::pair<int, int>> sizes;
+            raise_if_error(read_geotiff_overviews(path, sizes));
+            if (level < 0 || level > (int)sizes.size()) throw std::runtime_error("read_geotiff_band: overview level out of range");
+            w = sizes[(size_t)level - 1].first;
+            h = sizes[(size_t)level - 1].second;
+        }
         py::array_t<float> out({h, w});
-        raise_if_error(read_geotiff_band(path, band_index, out.mutable_data(), w, h));
+        raise_if_error(read_geotiff_band_level(path, level, band_index, out.mutable_data(), w, h));
         return out;
-    }, py::arg("path"), py::arg("band_index") = 0);
+    }, py::arg("path"), py::arg("band_index") = 0, py::arg("level") = 0);
     m.def("read_geotiff_band_names", [](const std::string& path) {
         std::vector<std::string> names;
         raise_if_error(read_geotiff_band_names(path, names));

@@ -164,6 +164,7 @@ SYMBOLS = {
     "pcr_hip_crs_from_epsg": [C.c_int, C.POINTER(CrsDesc)],
     "pcr_hip_transform_xy": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64, _VP],
     "pcr_hip_transform_xy_host": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64],
+    "pcr_hip_downsample2": [_VP, C.c_int, C.c_int, _I64, C.POINTER(_VP), C.c_int, C.c_int, _VP],
 }
 
 _lib = None

@@ -323,6 +323,7 @@ class ShardedPipeline:
         # ONE file for the whole grid, written by rank 0 from the gathered strips (the reference writes one file,
         # src/engine/pipeline.cpp:1351-1361) -- not a strip per rank under the same name
         self.output_path, cfg.output_path = cfg.output_path, ""
+        self.write_cog = cfg.write_cog
         self._state_dir = cfg.state_dir
         self._rtypes = [r.type for r in cfg.reductions]
         if device_id is not None:
@@ -603,7 +604,10 @@ class ShardedPipeline:
             import pcr
             whole = self.gather(0)
             if self.rank == 0:
-                pcr.write_geotiff(self.output_path, whole, self.grid)
+                opts = pcr.GeoTiffOptions()
+                if self.write_cog:
+                    opts.overviews = -1
+                pcr.write_geotiff(self.output_path, whole, self.grid, opts)
 
     def save_state(self, directory=""):
         """`.pcrt` checkpoint of the sharded pipeline (collective): the exchange first (what a rank's apron rows hold belongs
