@@ -35,7 +35,9 @@ extern "C" {
                                  * 5 (round 5): + comm_alltoall_counts / comm_alltoallv / comm_gatherv / comm_xfer_plan / touched_union_owned; halo_reduce resets the sent apron rows;
                                  *   later, additive (same version): + crs_from_epsg / transform_xy / transform_xy_host;
                                  *   + PCR_HIP_MOST_RECENT: select_pack / select_unpack / select_merge / scatter_select / finalize_select,
-                                 *     state_floats / state_init / state_merge accept type 8 */
+                                 *     state_floats / state_init / state_merge accept type 8;
+                                 *   + engine_defer_planes / engine_planes_deferred / planes_from_bands_if; scatter_stats.reserved_ is now
+                                 *     deferred_planes (same place, 0 unless the hint was sent) */
 
 typedef enum pcr_hip_status {
     PCR_HIP_OK = 0,
@@ -108,7 +110,8 @@ typedef struct pcr_hip_scatter_stats {
     int32_t path;              /* 0 = direct global atomics, 1 = binned LDS tiles, 2 = moments + convolution */
     int32_t lds_tile_w, lds_tile_h, lds_apron, num_bins;
     int32_t scatter_chunk;     /* binned path: points per workgroup of the record-scatter pass (0 otherwise) */
-    int32_t reserved_;
+    int32_t deferred_planes;   /* PCR_HIP_PLANE_* bits the scatter left in the bands it stored (pcr_hip_engine_defer_planes;
+                                * the field was reserved_ and read 0) */
 } pcr_hip_scatter_stats;
 
 const char* pcr_hip_last_error(void);
@@ -188,6 +191,17 @@ int pcr_hip_finalize_group(const pcr_hip_grid* g, const pcr_hip_planes* planes, 
 int pcr_hip_finalize_group_unless(const pcr_hip_grid* g, const pcr_hip_planes* planes, const uint32_t* d_tile_touched,
                                   int n_out, const int* rtypes, float* const* d_outs, const uint32_t* d_bands_done,
                                   pcr_hip_stream s);
+/* The way back for planes a fused scatter left in its bands (pcr_hip_engine_defer_planes).  For every bit of plane_mask the
+ * plane is stored over the whole state window from d_bands[slot] (slot 0 the Sum band, 1 Count, 2 Max, 3 Min; other slots are
+ * not read) and the touched flags as they were when the scatter ran:
+ *   Sum   = touched tile ? band : 0          Count = isnan(band) ? 0 : band
+ *   Max   = isnan(band) ? -FLT_MAX : band    Min   = isnan(band) ? +FLT_MAX : band
+ * A no-op when *d_bands_done reads 0 at the time the kernel runs (the scatter stored the planes itself), so it can be enqueued
+ * without a host round trip.  The grid's owned rows must be its state window, width % 4 == 0, planes and bands 16-byte
+ * aligned -- what the fused scatter required. */
+int pcr_hip_planes_from_bands_if(const pcr_hip_grid* g, const pcr_hip_planes* planes, uint32_t plane_mask,
+                                 const float* const* d_bands, const uint32_t* d_tile_touched, const uint32_t* d_bands_done,
+                                 pcr_hip_stream s);
 
 /* Union of another rank's touched-tile flags into this device's (row-block shards: a reference tile is touched if ANY rank saw
  * a point in it).  d_local[i] |= d_union[i] != 0, i < n; when that changed a flag, the n_words device words at d_bands_done
@@ -249,6 +263,17 @@ int pcr_hip_engine_planes_fresh(pcr_hip_engine* e, int fresh);
 int pcr_hip_engine_finalize_with_scatter(pcr_hip_engine* e, int n_out, const int* rtypes, float* const* d_outs,
                                          uint32_t* d_bands_done);
 int pcr_hip_engine_finalize_taken(const pcr_hip_engine* e);
+/* Planes the NEXT pcr_hip_scatter_point may leave UNSTORED (PCR_HIP_PLANE_* bits; cleared by that scatter; send it after
+ * pcr_hip_engine_finalize_with_scatter, which resets it).  For the Point glyph a plane whose own reduction (Sum, Count, Max,
+ * Min) is one of the bands the fused tile pass stores is a bit-exact function of that band and the touched flags, so the pass
+ * can skip the plane's store and a caller that only finalizes never pays for it.  The engine takes a bit only when the
+ * launch is the fused one and the plane's own reduction is among the bands given; every other bit is dropped and the plane
+ * stored as always.  pcr_hip_engine_planes_deferred: the bits the last pcr_hip_scatter_point took.  They hold only where
+ * *d_bands_done reads 1 once the scatter has run -- where it reads 0 every plane was stored.  While a plane is deferred its
+ * memory is UNDEFINED and its band must not be written: pcr_hip_planes_from_bands_if puts it back.  A caller that never sends
+ * the hint gets every store. */
+int pcr_hip_engine_defer_planes(pcr_hip_engine* e, uint32_t plane_mask);
+int pcr_hip_engine_planes_deferred(const pcr_hip_engine* e);
 int pcr_hip_engine_stats(const pcr_hip_engine* e, pcr_hip_scatter_stats* out);
 /* device array of tiles_x*tiles_y words, non-zero where a valid point's centre cell fell */
 int pcr_hip_engine_tile_touched(pcr_hip_engine* e, uint32_t** d_tile_touched, int32_t* tiles_x, int32_t* tiles_y);

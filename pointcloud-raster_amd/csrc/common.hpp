@@ -54,6 +54,8 @@ struct PlanesDev {
 struct FinalizeOuts {
     int n;
     int rtype[PCR_HIP_MAX_FINALIZE_OUTPUTS];
+    unsigned defer;                   // PCR_HIP_PLANE_* bits: planes the fused tile pass leaves unstored, their values being in
+                                      // the bands it stores (pcr_hip_engine_defer_planes); sits in what was padding
     float* out[PCR_HIP_MAX_FINALIZE_OUTPUTS];
 };
 

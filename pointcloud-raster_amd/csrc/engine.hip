@@ -178,6 +178,7 @@ int begin_scatter(pcr_hip_engine* e, uint64_t n) {
     e->stats.lds_tile_w = e->stats.lds_tile_h = e->stats.lds_apron = e->stats.num_bins = 0;
     e->stats_scatter_chunk = 0;
     e->counters_published = false;
+    e->deferred_taken = 0;
     return PCR_HIP_OK;
 }
 
@@ -304,6 +305,7 @@ int pcr_hip_engine_finalize_with_scatter(pcr_hip_engine* e, int n_out, const int
     PCR_REQUIRE(e, "engine_finalize_with_scatter: null engine");
     e->fused_outs.n = 0;
     e->fused_done = nullptr;
+    e->defer_planes = 0;                                  // (belongs to the bands of one call: given after it)
     if (n_out == 0) return PCR_HIP_OK;                    // withdraws the hint
     PCR_REQUIRE(rtypes && d_outs && d_bands_done, "engine_finalize_with_scatter: null argument");
     PCR_REQUIRE(n_out >= 1 && n_out <= PCR_HIP_MAX_FINALIZE_OUTPUTS, "engine_finalize_with_scatter: 1..8 outputs");
@@ -321,6 +323,15 @@ int pcr_hip_engine_finalize_with_scatter(pcr_hip_engine* e, int n_out, const int
 
 int pcr_hip_engine_finalize_taken(const pcr_hip_engine* e) { return e && e->fused_taken ? 1 : 0; }
 
+int pcr_hip_engine_defer_planes(pcr_hip_engine* e, uint32_t plane_mask) {
+    PCR_REQUIRE(e, "engine_defer_planes: null engine");
+    PCR_REQUIRE((plane_mask & ~15u) == 0, "engine_defer_planes: unknown plane bit");
+    e->defer_planes = plane_mask;
+    return PCR_HIP_OK;
+}
+
+int pcr_hip_engine_planes_deferred(const pcr_hip_engine* e) { return e ? (int)e->deferred_taken : 0; }
+
 int pcr_hip_engine_stats(const pcr_hip_engine* e, pcr_hip_scatter_stats* out) {
     PCR_REQUIRE(e && out, "engine_stats: null argument");
     unsigned long long c[8] = {0};
@@ -330,6 +341,7 @@ int pcr_hip_engine_stats(const pcr_hip_engine* e, pcr_hip_scatter_stats* out) {
     *out = e->stats;
     out->points_valid = c[0];
     out->scatter_chunk = e->stats.path == 1 ? e->stats_scatter_chunk : 0;
+    out->deferred_planes = (int32_t)e->deferred_taken;
     return PCR_HIP_OK;
 }
 
@@ -394,9 +406,10 @@ int pcr_hip_scatter_point(pcr_hip_engine* e, uint32_t plane_mask, const pcr_hip_
     PCR_REQUIRE(e, "scatter_point: null engine");
     struct HintGuard {                                    // the fused-finalize hint covers this call, however it ends
         pcr_hip_engine* e;
-        ~HintGuard() { e->fused_outs.n = 0; e->fused_done = nullptr; }
+        ~HintGuard() { e->fused_outs.n = 0; e->fused_done = nullptr; e->defer_planes = 0; }
     } hint_guard{e};
     e->fused_taken = false;
+    e->deferred_taken = 0;
     PlanesDev pl;
     int rc = check_planes(plane_mask, planes, 15u, pl);
     if (rc) return rc;
@@ -430,6 +443,7 @@ int pcr_hip_scatter_select(pcr_hip_engine* e, uint64_t* d_packed, const double* 
     e->fused_outs.n = 0;                                  // (a pending finalize-with-scatter hint does not apply here)
     e->fused_done = nullptr;
     e->fused_taken = false;
+    e->defer_planes = e->deferred_taken = 0;
     PCR_REQUIRE(d_packed, "scatter_select: null packed plane");
     PCR_REQUIRE((reinterpret_cast<uintptr_t>(d_packed) & 7) == 0, "scatter_select: the packed plane must be 8-byte aligned");
     if (n == 0) return PCR_HIP_OK;                       // empty cloud is a no-op, as for pcr_hip_scatter_point

@@ -50,6 +50,9 @@ struct pcr_hip_engine {
     pcrhip::FinalizeOuts fused_outs{};
     uint32_t* fused_done = nullptr;
     bool fused_taken = false;
+    // pcr_hip_engine_defer_planes, for the same scatter: planes it may leave in those bands, and the ones it did
+    uint32_t defer_planes = 0;
+    uint32_t deferred_taken = 0;
 
     // optional per-kernel event timing
     bool profiling = false;

@@ -673,6 +673,8 @@ inline BinGeom point_bin_geom(const pcr_hip_engine* e, uint32_t mask) {
 // bands -- finalize(rtype) of the cell where its reference tile is touched, NaN elsewhere -- from the tile it has in hand, so
 // that the finalize pass does not read the planes back (C2: 134 MB).  The touched flags are complete: the counting pass of
 // this scatter set them.  *done tells the finalize call whether the bands were stored (not when the scan split a bin).
+// fo.defer names planes that launch does not store then: *done == 1 says two things at once, the bands are stored and the
+// deferred planes live in them.  A launch that is not `full` stores and merges every plane as if nothing had been deferred.
 template <unsigned MASK, bool FUSED>
 __global__ void __launch_bounds__(kThreads)
 k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ records,
@@ -799,6 +801,18 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
         // with the next quad's LDS reads issued ahead of them.
         if (lx >= w || ly0 >= h) return;
         const int n_out = FUSED ? fo.n : 0;
+        // A deferred plane (fo.defer) is not stored at all: its reduction is one of the bands, which holds the plane's value
+        // in every cell where the two can differ (pcr_hip_planes_from_bands_if).  The bit becomes a zero address in the scalar
+        // registers that hold the plane's address anyway, and the loop tests that pair (wave-uniform: a scalar compare and
+        // branch around the store).
+        const unsigned defer = FUSED ? fo.defer : 0u;
+        // (as integers, and stored through global-address-space pointers made from them: a pointer that has been through the
+        // pin below is a generic one to the compiler, and its stores came out as flat_store)
+        typedef __attribute__((address_space(1))) f4v* gf4p;
+        uintptr_t p_sum = (defer & 1u) ? 0 : reinterpret_cast<uintptr_t>(pl.sum);
+        uintptr_t p_wgt = (defer & 2u) ? 0 : reinterpret_cast<uintptr_t>(pl.wgt);
+        uintptr_t p_max = (defer & 4u) ? 0 : reinterpret_cast<uintptr_t>(pl.mx);
+        uintptr_t p_min = (defer & 8u) ? 0 : reinterpret_cast<uintptr_t>(pl.mn);
         float* band[PCR_HIP_MAX_FINALIZE_OUTPUTS];
         bool divides = false;
         unsigned kinds = 0u;                                           // three bits per output
@@ -861,10 +875,26 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
             }
             // the Sum / Count planes leave with non-temporal stores: nothing reads them before the finalize pass, and
             // streaming 134 MB through the L2 only evicts the records still to be folded (C2 step -1.2 %)
-            if (MASK & 1) __builtin_nontemporal_store(f4v{s4[0], s4[1], s4[2], s4[3]}, reinterpret_cast<f4v*>(pl.sum + cell));
-            if (MASK & 2) __builtin_nontemporal_store(f4v{w4[0], w4[1], w4[2], w4[3]}, reinterpret_cast<f4v*>(pl.wgt + cell));
-            if (MASK & 4) *reinterpret_cast<float4*>(pl.mx + cell) = make_float4(x4[0], x4[1], x4[2], x4[3]);
-            if (MASK & 8) *reinterpret_cast<float4*>(pl.mn + cell) = make_float4(m4[0], m4[1], m4[2], m4[3]);
+            // (the deferred bits stay ONE scalar register, tested here: left to itself the compiler turns every bit into a
+            // 64-bit lane mask ahead of the loop, and the fused instantiations have no scalar registers to spare)
+            // (the addresses as they are, in their scalar registers at this point: left to itself the compiler turns each test
+            // into a 64-bit lane mask ahead of the loop, and the fused instantiations have no scalar register to spare -- they
+            // spilled more and mask 9 took one more vector register)
+            if (FUSED && (MASK & 1)) asm volatile("" : "+s"(p_sum));
+            if (FUSED && (MASK & 2)) asm volatile("" : "+s"(p_wgt));
+            if (FUSED && (MASK & 4)) asm volatile("" : "+s"(p_max));
+            if (FUSED && (MASK & 8)) asm volatile("" : "+s"(p_min));
+            if (FUSED) {
+                if ((MASK & 1) && p_sum) __builtin_nontemporal_store(f4v{s4[0], s4[1], s4[2], s4[3]}, (gf4p)(p_sum + 4 * (uintptr_t)cell));
+                if ((MASK & 2) && p_wgt) __builtin_nontemporal_store(f4v{w4[0], w4[1], w4[2], w4[3]}, (gf4p)(p_wgt + 4 * (uintptr_t)cell));
+                if ((MASK & 4) && p_max) *(gf4p)(p_max + 4 * (uintptr_t)cell) = f4v{x4[0], x4[1], x4[2], x4[3]};
+                if ((MASK & 8) && p_min) *(gf4p)(p_min + 4 * (uintptr_t)cell) = f4v{m4[0], m4[1], m4[2], m4[3]};
+            } else {
+                if (MASK & 1) __builtin_nontemporal_store(f4v{s4[0], s4[1], s4[2], s4[3]}, reinterpret_cast<f4v*>(pl.sum + cell));
+                if (MASK & 2) __builtin_nontemporal_store(f4v{w4[0], w4[1], w4[2], w4[3]}, reinterpret_cast<f4v*>(pl.wgt + cell));
+                if (MASK & 4) *reinterpret_cast<float4*>(pl.mx + cell) = make_float4(x4[0], x4[1], x4[2], x4[3]);
+                if (MASK & 8) *reinterpret_cast<float4*>(pl.mn + cell) = make_float4(m4[0], m4[1], m4[2], m4[3]);
+            }
             if (FUSED) {
                 // (the owned rows are the state window: a band cell has the plane cell's index)
 #pragma unroll
@@ -975,7 +1005,7 @@ k_fill_if(const unsigned* __restrict__ n_items, PlanesDev pl, unsigned mask, int
 
 template <unsigned MASK>
 void launch_accum(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const PlanesDev& pl, const BinBuffers& bb,
-                  bool fused = false) {
+                  bool fused = false, unsigned defer = 0u) {
     // (the fused merge's live map comes with point_tile_lds; the other launches leave it out)
     const size_t lds = fused ? point_tile_lds(tile_cell_bytes(MASK), b.tile_h) : (size_t)b.tile_w * b.tile_h * tile_cell_bytes(MASK);
     // fresh: only when every bin is owned by one workgroup of this launch can a store replace the read-modify-write
@@ -984,7 +1014,9 @@ void launch_accum(pcr_hip_engine* e, const GridDev& gd, const BinGeom& b, const 
         hipLaunchKernelGGL(kernel, dim3(bb.max_items), dim3(kThreads), lds, e->stream, gd, b, pl,
                            bb.records, bb.items, bb.n_items, e->planes_fresh, fo, (const uint32_t*)e->d_touched, done);
     };
-    if (fused) go(&k_tile_accum<MASK, true>, e->fused_outs, e->fused_done);
+    FinalizeOuts fo = e->fused_outs;
+    fo.defer = defer;
+    if (fused) go(&k_tile_accum<MASK, true>, fo, e->fused_done);
     else go(&k_tile_accum<MASK, false>, FinalizeOuts{}, nullptr);
 }
 
@@ -1310,6 +1342,16 @@ int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
     // window from float4 groups (define_all), and a band cell has the plane cell's index when the owned rows are the window
     const bool fused = define_all && e->fused_outs.n > 0 && e->fused_done && e->gd.W % 4 == 0 &&
                        e->gd.own_r0 == e->gd.st_r0 && e->gd.own_r1 - e->gd.own_r0 == e->gd.st_rows;
+    // Planes the caller lets this scatter leave unstored (pcr_hip_engine_defer_planes): only the fused launch can, and only a
+    // plane whose own reduction is among the bands it stores -- any other bit is dropped here.
+    uint32_t defer = 0;
+    if (fused) {
+        uint32_t offered = 0;
+        for (int o = 0; o < e->fused_outs.n; ++o)
+            offered |= e->fused_outs.rtype[o] == PCR_HIP_SUM ? PCR_HIP_PLANE_SUM : e->fused_outs.rtype[o] == PCR_HIP_COUNT ? PCR_HIP_PLANE_WGT :
+                       e->fused_outs.rtype[o] == PCR_HIP_MAX ? PCR_HIP_PLANE_MAX : e->fused_outs.rtype[o] == PCR_HIP_MIN ? PCR_HIP_PLANE_MIN : 0u;
+        defer = e->defer_planes & mask & offered;
+    }
     // (define_all and the scan splits a bin: the planes get their identity values after all -- with the scatter pass, or, when
     // the sort has two levels, by k_fill_if behind the last scan)
     TailFill fill{};
@@ -1323,9 +1365,10 @@ int binned_point(pcr_hip_engine* e, uint32_t mask, const PlanesDev& pl,
         if (define_all && !bb.fill_folded)
             hipLaunchKernelGGL(k_fill_if, dim3(2048), dim3(256), 0, e->stream, bb.n_items, pl, mask, cells / 4);
         e->fused_taken = fused;
+        e->deferred_taken = defer;
         ScopedKernelTimer t(e, "k_tile_accum");
         switch (mask) {
-#define PCR_ACC(M) case M: launch_accum<M>(e, gd, b, pl, bb, fused); break;
+#define PCR_ACC(M) case M: launch_accum<M>(e, gd, b, pl, bb, fused, defer); break;
             PCR_ACC(1) PCR_ACC(2) PCR_ACC(3) PCR_ACC(4) PCR_ACC(5) PCR_ACC(6) PCR_ACC(7) PCR_ACC(8)
             PCR_ACC(9) PCR_ACC(10) PCR_ACC(11) PCR_ACC(12) PCR_ACC(13) PCR_ACC(14) PCR_ACC(15)
 #undef PCR_ACC

@@ -171,6 +171,52 @@ k_finalize_group(GridDev g, PlanesDev pl, unsigned need, const uint32_t* __restr
     }
 }
 
+// The way back for planes the fused Point tile pass left in its bands (pcr_hip_planes_from_bands_if).  As the merge computes
+// them a Sum plane is 0.f + the tile's sum and its band that value where the reference tile is touched (an untouched tile holds
+// no point: the plane is 0 there); a Count / Max / Min band is the plane with NaN where the plane holds its identity or the
+// tile is untouched (identity again), and such a plane never holds a NaN itself (a count; atomic_max_f32 / atomic_min_f32 skip
+// NaN values).  One lane = four cells of a row, the tile-to-flag mapping of k_finalize_group (the owned rows are the window).
+__global__ void __launch_bounds__(kBlock)
+k_planes_from_bands(GridDev g, PlanesDev pl, unsigned mask, const float* __restrict__ b_sum, const float* __restrict__ b_cnt,
+                    const float* __restrict__ b_max, const float* __restrict__ b_min, const uint32_t* __restrict__ touched,
+                    const uint32_t* __restrict__ bands_done) {
+    if (*bands_done == 0u) return;                            // the scatter stored the planes itself
+    const int per_row = g.W / 4;
+    const int64_t items = (int64_t)g.st_rows * per_row;
+    const bool one_tile = (g.tiles_x * g.tiles_y == 1);
+    const bool all_touched = one_tile && touched[0] != 0u;
+    const bool none_touched = one_tile && touched[0] == 0u;
+    for (int64_t it = (int64_t)blockIdx.x * kBlock + threadIdx.x; it < items; it += (int64_t)gridDim.x * kBlock) {
+        const int r = (int)(it / per_row);
+        const int c = (int)(it - (int64_t)r * per_row) * 4;
+        const int64_t si = (int64_t)r * g.W + c;
+        if (mask & 1) {
+            const float4 b = stream_load(reinterpret_cast<const float4*>(b_sum + si));
+            const uint32_t* trow = touched + ((g.st_r0 + r) / g.th) * g.tiles_x;
+            float v[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (!(all_touched || (!none_touched && trow[(c + k) / g.tw] != 0u))) v[k] = 0.0f;
+            *reinterpret_cast<float4*>(pl.sum + si) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+        if (mask & 2) {
+            const float4 b = stream_load(reinterpret_cast<const float4*>(b_cnt + si));
+            *reinterpret_cast<float4*>(pl.wgt + si) = make_float4(isnan(b.x) ? 0.0f : b.x, isnan(b.y) ? 0.0f : b.y,
+                                                                  isnan(b.z) ? 0.0f : b.z, isnan(b.w) ? 0.0f : b.w);
+        }
+        if (mask & 4) {
+            const float4 b = stream_load(reinterpret_cast<const float4*>(b_max + si));
+            *reinterpret_cast<float4*>(pl.mx + si) = make_float4(isnan(b.x) ? -FLT_MAX : b.x, isnan(b.y) ? -FLT_MAX : b.y,
+                                                                 isnan(b.z) ? -FLT_MAX : b.z, isnan(b.w) ? -FLT_MAX : b.w);
+        }
+        if (mask & 8) {
+            const float4 b = stream_load(reinterpret_cast<const float4*>(b_min + si));
+            *reinterpret_cast<float4*>(pl.mn + si) = make_float4(isnan(b.x) ? FLT_MAX : b.x, isnan(b.y) ? FLT_MAX : b.y,
+                                                                 isnan(b.z) ? FLT_MAX : b.z, isnan(b.w) ? FLT_MAX : b.w);
+        }
+    }
+}
+
 // ---- MostRecent: packed words <-> the reference's {value, timestamp} float planes (common.hpp: select_word) ------------
 __global__ void __launch_bounds__(kBlock)
 k_select_pack(const float* __restrict__ value, const float* __restrict__ key, unsigned long long* __restrict__ packed, int64_t n) {
@@ -545,6 +591,7 @@ int pcr_hip_finalize_group_unless(const pcr_hip_grid* g, const pcr_hip_planes* p
     if (rows <= 0) return PCR_HIP_OK;
     FinalizeOuts fo;
     fo.n = n_out;
+    fo.defer = 0u;
     unsigned need = 0;
     bool aligned = gd.W % 4 == 0;
     for (int i = 0; i < n_out; ++i) {
@@ -575,6 +622,33 @@ int pcr_hip_finalize_group_unless(const pcr_hip_grid* g, const pcr_hip_planes* p
         hipLaunchKernelGGL(k_finalize_group<1>, dim3(grid_for((int64_t)rows * gd.W)), dim3(kBlock), 0, st,
                            gd, pl, need, d_tile_touched, fo, d_bands_done);
     }
+    PCR_HIP_TRY(hipGetLastError());
+    return PCR_HIP_OK;
+}
+
+int pcr_hip_planes_from_bands_if(const pcr_hip_grid* g, const pcr_hip_planes* planes, uint32_t plane_mask,
+                                 const float* const* d_bands, const uint32_t* d_tile_touched, const uint32_t* d_bands_done,
+                                 pcr_hip_stream s) {
+    int rc = validate_grid(g);
+    if (rc) return rc;
+    PCR_REQUIRE(planes && d_bands && d_tile_touched && d_bands_done, "planes_from_bands: null argument");
+    PCR_REQUIRE((plane_mask & ~15u) == 0, "planes_from_bands: unknown plane bit");
+    if (plane_mask == 0) return PCR_HIP_OK;
+    const GridDev gd = make_grid_dev(*g);
+    PCR_REQUIRE(gd.own_r0 == gd.st_r0 && gd.own_r1 - gd.own_r0 == gd.st_rows && gd.st_rows > 0 && gd.W % 4 == 0,
+                "planes_from_bands: the owned rows must be the state window, the width a multiple of 4");
+    float* const plane[4] = {planes->d_sum, planes->d_wgt, planes->d_max, planes->d_min};
+    for (int p = 0; p < 4; ++p) {
+        if (!(plane_mask & (1u << p))) continue;
+        PCR_REQUIRE(plane[p] && d_bands[p], "planes_from_bands: a named plane or its band is null");
+        PCR_REQUIRE(((reinterpret_cast<uintptr_t>(plane[p]) | reinterpret_cast<uintptr_t>(d_bands[p])) & 15) == 0,
+                    "planes_from_bands: planes and bands must be 16-byte aligned");
+    }
+    auto band = [&](int p) { return (plane_mask & (1u << p)) ? d_bands[p] : nullptr; };
+    const PlanesDev pl{planes->d_sum, planes->d_wgt, planes->d_max, planes->d_min};
+    hipLaunchKernelGGL(k_planes_from_bands, dim3(grid_for((int64_t)gd.st_rows * (gd.W / 4))), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(s), gd, pl, plane_mask, band(0), band(1), band(2), band(3), d_tile_touched,
+                       d_bands_done);
     PCR_HIP_TRY(hipGetLastError());
     return PCR_HIP_OK;
 }

@@ -175,7 +175,9 @@ public:
     // path and LDS tiling the last scatter used (0 direct, 1 binned), exact valid-point count
     // bands_with_scatter: accumulation groups whose finished bands the scatter that defined their planes was asked to store
     // too and that nothing has invalidated since (finalize skips their kernel when the device confirms)
-    struct ScatterInfo { int path; int lds_tile_w, lds_tile_h, lds_apron, num_bins; size_t points_in, points_valid; int scatter_chunk; int bands_with_scatter; };
+    // deferred_planes: plane bits (1 Sum, 2 Count, 4 Max, 8 Min) that scatter was let off storing, their values being in the
+    // band of their own reduction; they are put back, once, in front of whatever next reads or changes the state
+    struct ScatterInfo { int path; int lds_tile_w, lds_tile_h, lds_apron, num_bins; size_t points_in, points_valid; int scatter_chunk; int bands_with_scatter; int deferred_planes; };
     ScatterInfo last_scatter() const;
 
     /// True when the grid's state did not fit the device budget and the pipeline sweeps it in row bands (out of core).

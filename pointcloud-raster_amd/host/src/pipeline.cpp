@@ -72,6 +72,13 @@ struct Pipeline::Impl {
         bool bands_with_scatter = false; // the scatter that defined the planes was asked to store this group's finished bands
                                          // too (pcr_hip_engine_finalize_with_scatter) and nothing has touched the planes or the
                                          // touched flags since: finalize() skips the group's kernel when the device agrees
+        uint32_t planes_in_bands = 0;    // PCR_HIP_PLANE_* bits of planes that scatter did NOT store (pcr_hip_engine_defer_planes):
+                                         // where the group's done word reads 1 their memory is undefined and their values are
+                                         // in the band of their own reduction -- restore_planes() puts them back in front of
+                                         // everything that reads or writes the planes or the touched flags, finalize apart.
+                                         // Non-zero only while bands_with_scatter is true.  Relies on the bands being the
+                                         // pipeline's alone to write: result() hands out a const Grid*, result_band_device() a
+                                         // const float*.
     };
     struct Output {                      // one ReductionSpec -> one band
         int group = 0;
@@ -114,7 +121,42 @@ struct Pipeline::Impl {
     int own_rows() const { return hg.own_row1 - hg.own_row0; }
 
     // Bands a scatter may have stored are stale as soon as anything else writes the planes or the touched flags.
-    void bands_stale() { for (auto& gr : groups) gr.bands_with_scatter = false; }
+    // Planes those bands still hold are put back FIRST, while the flags and the bands are what the scatter left.
+    Status bands_stale() {
+        Status s = restore_all_planes();
+        for (auto& gr : groups) gr.bands_with_scatter = false;
+        return s;
+    }
+    // The slot (0 Sum, 1 Count, 2 Max, 3 Min) of the plane a reduction finalizes unchanged; -1: none.
+    static int own_plane(ReductionType t) {
+        return t == ReductionType::Sum ? 0 : t == ReductionType::Count ? 1 : t == ReductionType::Max ? 2 : t == ReductionType::Min ? 3 : -1;
+    }
+    // Enqueues the rebuild of the planes a group's defining scatter left in its bands and clears the mask.  The kernel is
+    // conditional on the group's done word (0: the scatter stored the planes after all), so no host wait is needed.
+    Status restore_planes(size_t gi, bool* enqueued = nullptr) {
+        Group& gr = groups[gi];
+        const uint32_t m = gr.planes_in_bands;
+        if (!m) return Status::success();
+        gr.planes_in_bands = 0;
+        const float* src[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (size_t r = 0; r < outputs.size(); ++r) {
+            const int p = outputs[r].group == (int)gi ? own_plane(outputs[r].type) : -1;
+            if (p >= 0 && (m & kPlaneBits[p])) src[p] = band_device(r);
+        }
+        uint32_t* d_touched = nullptr;
+        Status s = detail::hip_status(pcr_hip_engine_tile_touched(engine, &d_touched, nullptr, nullptr));
+        if (!s.ok()) return s;
+        if (enqueued) *enqueued = true;
+        return detail::hip_status(pcr_hip_planes_from_bands_if(&hg, &gr.view, m, src, d_touched,
+                                                               static_cast<const uint32_t*>(d_bands_done.data()) + gi, stream));
+    }
+    Status restore_all_planes(bool* enqueued = nullptr) {
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            Status s = restore_planes(gi, enqueued);
+            if (!s.ok()) return s;
+        }
+        return Status::success();
+    }
     float* band_device(size_t r) {
         return cfg.result_location == MemoryLocation::Device ? result->band_f32((int)r) : static_cast<float*>(d_bands[r].data());
     }
@@ -131,14 +173,18 @@ struct Pipeline::Impl {
         int types[PCR_HIP_MAX_FINALIZE_OUTPUTS];
         float* dsts[PCR_HIP_MAX_FINALIZE_OUTPUTS];
         int n = 0;
+        uint32_t own = 0;                              // planes whose own reduction is an output: they can stay in its band
         for (size_t r = 0; r < outputs.size(); ++r) {
             if (outputs[r].group != (int)gi) continue;
             if (n == PCR_HIP_MAX_FINALIZE_OUTPUTS) return false;
             types[n] = static_cast<int>(outputs[r].type);
             dsts[n++] = band_device(r);
+            if (own_plane(outputs[r].type) >= 0) own |= kPlaneBits[own_plane(outputs[r].type)];
         }
         if (n == 0) return false;
-        return pcr_hip_engine_finalize_with_scatter(engine, n, types, dsts, static_cast<uint32_t*>(d_bands_done.data()) + gi) == PCR_HIP_OK;
+        if (pcr_hip_engine_finalize_with_scatter(engine, n, types, dsts, static_cast<uint32_t*>(d_bands_done.data()) + gi) != PCR_HIP_OK)
+            return false;
+        return pcr_hip_engine_defer_planes(engine, own & gr.mask) == PCR_HIP_OK;
     }
 
     Status init() {
@@ -305,7 +351,13 @@ struct Pipeline::Impl {
 
     // Identity values into a group's planes, for every reader that may come before the group's first scatter (finalize
     // of an empty pipeline, checkpoints, the halo exchange of a rank without points, state_planes()).
+    // Planes the defining scatter left in its bands are put back as well (restore_planes): what this returns from can be read.
     Status define_planes(Group& gr) {
+        Status s = define_identity(gr);
+        return s.ok() ? restore_planes((size_t)(&gr - groups.data())) : s;
+    }
+    // (finalize's form: it reads the planes of a group only where the done word says they were stored)
+    Status define_identity(Group& gr) {
         if (gr.defined) return Status::success();
         const int64_t cells = (int64_t)hg.state_rows * hg.width;
         if (gr.select) {                                 // the identity of the packed words is 0
@@ -583,7 +635,8 @@ struct Pipeline::Impl {
         }
         if (reach_needed > halo) return reach_error(reach_needed);
 
-        bands_stale();                                   // (this cloud's points change the planes and the touched flags)
+        // (this cloud's points change the planes and the touched flags)
+        if (!(s = bands_stale()).ok()) return s;
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             Group& gr = groups[gi];
             const void* dv = nullptr;
@@ -605,6 +658,7 @@ struct Pipeline::Impl {
                     engine, gr.mask, &gr.view, static_cast<const double*>(dx), static_cast<const double*>(dy),
                     static_cast<const float*>(dv), n));
                 gr.bands_with_scatter = offered && s.ok() && pcr_hip_engine_finalize_taken(engine) == 1;
+                gr.planes_in_bands = gr.bands_with_scatter ? (uint32_t)pcr_hip_engine_planes_deferred(engine) : 0u;
             } else {
                 pcr_hip_glyph hgph{};
                 hgph.type = static_cast<int32_t>(gr.glyph.type);
@@ -691,8 +745,8 @@ struct Pipeline::Impl {
             Status as = allocate_result();
             if (!as.ok()) return as;
         }
-        {
-            Status ds = define_all_planes();          // a group no cloud ever reached
+        for (auto& gr : groups) {                     // a group no cloud ever reached
+            Status ds = define_identity(gr);
             if (!ds.ok()) return ds;
         }
         uint32_t* d_touched = nullptr;
@@ -723,6 +777,7 @@ struct Pipeline::Impl {
                 if (done && host_decides) {
                     if (*static_cast<const volatile uint32_t*>(done) != 0u) { types.clear(); dsts.clear(); return Status::success(); }
                     done = nullptr;              // (known to be 0: the kernel need not read it across the bus)
+                    groups[gi].planes_in_bands = 0;  // (and the scatter stored every plane)
                 }
                 enqueued = true;
                 Status fs = detail::hip_status(pcr_hip_finalize_group_unless(&hg, &groups[gi].view, d_touched, (int)types.size(),
@@ -868,12 +923,12 @@ struct Pipeline::Impl {
         return s;
     }
     Status import_window(const std::vector<std::vector<float>>& planes, const std::vector<uint32_t>& touched) {
-        bands_stale();
         DeviceScope dev(cfg.cuda_device_id);
+        Status s = bands_stale();
+        if (!s.ok()) return s;
         const size_t cells = (size_t)hg.state_rows * hg.width;
         if (planes.size() != groups.size() * 4)
             return Status::error(StatusCode::InvalidArgument, "pipeline: parked state does not match the pipeline's groups");
-        Status s = Status::success();
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             if (groups[gi].select && !(s = alloc_select_views(groups[gi])).ok()) return s;
             for (int p = 0; p < 4; ++p) {
@@ -1512,7 +1567,7 @@ std::vector<Pipeline::PlaneView> Pipeline::state_planes() const {
     {
         Impl::DeviceScope dev(impl_->cfg.cuda_device_id);
         bool filled = false;
-        for (const auto& g : impl_->groups) filled = filled || !g.defined;
+        for (const auto& g : impl_->groups) filled = filled || !g.defined || g.planes_in_bands != 0;
         (void)impl_->define_all_planes();               // the caller reads (and may write) them: identity where nothing was ingested
         // The fills run on the pipeline's stream and the caller may read on any other (torch's current stream, a host copy):
         // they are complete when the pointers leave.  Planes that were already defined cost no synchronisation.
@@ -1525,7 +1580,7 @@ std::vector<Pipeline::PlaneView> Pipeline::state_planes() const {
     }
     for (auto& g : impl_->groups) g.fresh = false;      // mutable pointers leave the pipeline: assume the planes get written
     impl_->state_shared = true;
-    impl_->bands_stale();
+    (void)impl_->bands_stale();                         // (no plane is left in a band: define_all_planes above)
     for (size_t g = 0; g < impl_->groups.size(); ++g)
         for (int p = 0; p < 4; ++p)
             if (impl_->groups[g].mask & kPlaneBits[p])
@@ -1547,7 +1602,15 @@ void* Pipeline::tile_touched_device(int* tiles_x, int* tiles_y) const {
     int32_t tx = 0, ty = 0;
     if (pcr_hip_engine_tile_touched(impl_->engine, &d, &tx, &ty) != PCR_HIP_OK) return nullptr;
     impl_->state_shared = true;                         // (the flags may be written from outside: the shard exchange does)
-    impl_->bands_stale();
+    {
+        // planes a scatter left in its bands are rebuilt from the flags as they are now, and on this pipeline's stream: done
+        // before the pointer leaves
+        Impl::DeviceScope dev(impl_->cfg.cuda_device_id);
+        bool enqueued = false;
+        (void)impl_->restore_all_planes(&enqueued);
+        if (enqueued) (void)pcr_hip_stream_synchronize(impl_->stream);
+        (void)impl_->bands_stale();
+    }
     if (tiles_x) *tiles_x = tx;
     if (tiles_y) *tiles_y = ty;
     return d;
@@ -1571,6 +1634,8 @@ Status Pipeline::merge_touched(const void* d_union) {
     int32_t tx = 0, ty = 0;
     Status s = detail::hip_status(pcr_hip_engine_tile_touched(impl_->engine, &d, &tx, &ty));
     if (!s.ok()) return s;
+    // planes still in the bands go back first: a flag that changes clears the done words, and with them what says where they are
+    if (!(s = impl_->restore_all_planes()).ok()) return s;
     // (the stored bands' device words decide: the host keeps offering them to finalize, whose kernel runs when they are 0)
     // only a flag of a tile this device owns rows of can change its bands (the union used to drop the stored
     // bands whenever ANY tile of the grid changed, i.e. always, on shards that do not share every tile)
@@ -1621,10 +1686,13 @@ Pipeline::ScatterInfo Pipeline::last_scatter() const {
     if (banded_) return banded_->last;
     pcr_hip_scatter_stats st{};
     pcr_hip_engine_stats(impl_->engine, &st);
-    int fused = 0;
-    for (const auto& g : impl_->groups) fused += g.bands_with_scatter ? 1 : 0;
+    int fused = 0, deferred = 0;
+    for (const auto& g : impl_->groups) {
+        fused += g.bands_with_scatter ? 1 : 0;
+        deferred |= (int)g.planes_in_bands;
+    }
     return {st.path, st.lds_tile_w, st.lds_tile_h, st.lds_apron, st.num_bins,
-            (size_t)st.points_in, (size_t)st.points_valid, st.scatter_chunk, fused};
+            (size_t)st.points_in, (size_t)st.points_valid, st.scatter_chunk, fused, deferred};
 }
 
 }  // namespace pcr

@@ -196,6 +196,7 @@ void bind_engine(py::module_& m) {
             d["points_valid"] = s.points_valid;
             d["scatter_chunk"] = s.scatter_chunk;
             d["bands_with_scatter"] = s.bands_with_scatter;
+            d["deferred_planes"] = s.deferred_planes;
             return d;
         })
         .def("engine", [](const Pipeline& p) { return std::string(p.engine()); },

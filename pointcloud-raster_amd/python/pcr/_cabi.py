@@ -53,7 +53,7 @@ class KernelTime(C.Structure):
 class ScatterStats(C.Structure):
     _fields_ = [("points_in", C.c_uint64), ("points_valid", C.c_uint64), ("path", C.c_int32),
                 ("lds_tile_w", C.c_int32), ("lds_tile_h", C.c_int32), ("lds_apron", C.c_int32),
-                ("num_bins", C.c_int32), ("scatter_chunk", C.c_int32), ("reserved_", C.c_int32)]
+                ("num_bins", C.c_int32), ("scatter_chunk", C.c_int32), ("deferred_planes", C.c_int32)]
 
 
 class CrsDesc(C.Structure):
@@ -147,6 +147,9 @@ SYMBOLS = {
     "pcr_hip_engine_planes_fresh": [_VP, C.c_int],
     "pcr_hip_engine_finalize_with_scatter": [_VP, C.c_int, C.POINTER(C.c_int), C.POINTER(_VP), _VP],
     "pcr_hip_engine_finalize_taken": [_VP],
+    "pcr_hip_engine_defer_planes": [_VP, _U32],
+    "pcr_hip_engine_planes_deferred": [_VP],
+    "pcr_hip_planes_from_bands_if": [C.POINTER(Grid), C.POINTER(Planes), _U32, C.POINTER(_VP), _VP, _VP, _VP],
     "pcr_hip_engine_stats": [_VP, C.POINTER(ScatterStats)],
     "pcr_hip_engine_tile_touched": [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "pcr_hip_filter_mask": [C.POINTER(Predicate), C.c_int, _U64, _VP, _VP, _VP],
