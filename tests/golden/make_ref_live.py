@@ -8,6 +8,9 @@ is still what the reference returns.
   probe/<i>              pcr_ref_accumulate_glyph on known-answer glyph case i (the raw state band)
   random/<seed>          "refused", or the digests (cases.digest) of the raw state and the finalized tile of
                          cases.random_glyph_case(seed), seeds 0..319
+  lattice/<glyph>/<rt>   the digest of the raw state of pcr_ref_accumulate_glyph over the one tile of a 64 x 48 grid of
+                         0.1-unit cells, on the cloud that sits on its cell edges (tests/routing_lattice.py "ref_tile"):
+                         where the reference places a footprint whose centre is within an ulp of an edge
   tile_state/*           the .pcrt bytes the reference writes for tile_state_inputs(), what its reader returns for them,
                          and its file name for TILE_NAME_ARGS
 
@@ -25,15 +28,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
 
 import pcr_oracle_py as O   # noqa: E402
 import cases                 # noqa: E402
 import make_ref_vectors as MRV   # noqa: E402
+import routing_lattice as RL     # noqa: E402
 
 PATH = os.path.join(HERE, "ref_live.npz")
 RANDOM_SEEDS = range(320)
 TILE_NAME_ARGS = ("/a/b", 12, 345)
 TILE_HEADER = (4, 5, 9, 7, 1, 1)          # row, col, width, height, floats per cell, reduction type (Max)
+LATTICE_GLYPHS = {"gauss_r3": dict(type=cases.GAUSSIAN, sigma_x=0.1, sigma_y=0.1, max_radius=3.0),
+                  "line": dict(type=cases.LINE, direction=0.6, half_length=0.35, max_radius=32.0)}
+LATTICE_RTYPES = {"Sum": cases.SUM, "Count": cases.COUNT}
 
 
 def merge_inputs(L):
@@ -75,6 +83,21 @@ def random_case_record(R, case):
     return (cases.digest(st), cases.digest(fin))
 
 
+def lattice_state(acc_fn, glyph, rt):
+    """LATTICE_GLYPHS[glyph] accumulated by acc_fn over the whole "ref_tile" grid on its lattice cloud (the points inside the
+    bounds, as a TileBatch would hold them): the raw state [rows, cols]."""
+    grid = RL.grid("ref_tile")
+    x, y, v = RL.cloud("ref_tile")
+    ok = RL.in_bounds(grid, x, y)
+    gl = O.make_glyph(**LATTICE_GLYPHS[glyph])
+    pts, keep = O.make_points(x[ok], y[ok], v[ok])
+    cells = grid.width * grid.height
+    st = np.zeros(cells, dtype=np.float32)
+    assert acc_fn(C.byref(gl), rt, C.byref(pts), st.ctypes.data, cells, C.byref(grid), 0, 0, grid.width, grid.height) == 0
+    del keep
+    return st.reshape(grid.height, grid.width)
+
+
 def tile_state_inputs():
     return np.random.default_rng(2).normal(size=(1, 7, 9)).astype(np.float32)
 
@@ -114,6 +137,9 @@ def main():
             out[f"probe/{i}"] = band
     for seed in RANDOM_SEEDS:
         out[f"random/{seed}"] = np.array(random_case_record(R, cases.random_glyph_case(seed)))
+    for glyph in LATTICE_GLYPHS:
+        for name, rt in LATTICE_RTYPES.items():
+            out[f"lattice/{glyph}/{name}"] = np.array(cases.digest(lattice_state(R.pcr_ref_accumulate_glyph, glyph, rt)))
     with tempfile.TemporaryDirectory() as d:
         data, header, back = ref_tile_state(R, d)
     out["tile_state/bytes"] = np.frombuffer(data, dtype=np.uint8)

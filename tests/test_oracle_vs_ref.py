@@ -124,6 +124,28 @@ def test_live_ref_glyph_quirk_probes(known_answers, live_vectors):
             assert sorted([int(r), int(cc)] for r, cc in np.argwhere(band != 0)) == sorted(c["cells_set"])
 
 
+@pytest.mark.parametrize("rname", MRL.LATTICE_RTYPES)
+@pytest.mark.parametrize("glyph", MRL.LATTICE_GLYPHS)
+def test_live_ref_glyphs_on_cell_edges(glyph, rname, live_vectors):
+    """Footprints whose centre is on a cell edge or an ulp off it (tests/routing_lattice.py): the reference places them by
+    floor((wx - min_x) * (1 / cell_size)), a product, which on such points is not always the cell a division gives.  The
+    restatement against the reference's own code, bit for bit on the raw state (without oracle/_ref: against the digest of what
+    it returned)."""
+    R, L = O.ref_lib(), O.lib()
+    grid = MRL.RL.grid("ref_tile")
+    dx, dy = MRL.RL.disagreements(grid, *MRL.RL.cloud("ref_tile")[:2])
+    assert dx.sum() >= 50 and dy.sum() >= 50, "the cloud no longer holds points the two formulas place differently"
+    rt = MRL.LATTICE_RTYPES[rname]
+    recorded = str(live_vectors[f"lattice/{glyph}/{rname}"])
+    st_o = MRL.lattice_state(L.pcro_accumulate_glyph, glyph, rt)
+    if R is not None:
+        st_r = MRL.lattice_state(R.pcr_ref_accumulate_glyph, glyph, rt)
+        assert cases.digest(st_r) == recorded, f"{glyph}/{rname} (fixture stale?)"
+        _same(st_o, st_r, f"{glyph}/{rname} state")
+    assert cases.digest(st_o) == recorded, f"{glyph}/{rname} vs recorded reference"
+    assert np.isfinite(st_o).all() and (st_o != 0).any()
+
+
 @pytest.mark.parametrize("block", range(8))
 def test_live_ref_matches_oracle_on_random_glyph_cases(block, live_vectors):
     """320 random accumulate_glyph() calls, the C restatement against the reference's own code (without oracle/_ref: against
