@@ -1,0 +1,1021 @@
+// device_pipeline.cpp -- Pipeline::Impl (device_pipeline.h): the in-core pipeline on the HIP engine.
+//   * no router / sort / per-tile batches / tile manager: reductions that read the same value channel through the same glyph
+//     share ONE pass over the points and ONE set of device planes (sum, weight, max, min);
+//   * finalize runs on the device; only finalized bands cross PCIe (or stay in HBM).
+#include "device_pipeline.h"
+
+#include "overviews.h"
+#include "pcr/core/point_cloud.h"
+#include "pcr/io/grid_io.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <mutex>
+#include <set>
+
+namespace pcr {
+
+using detail::kPlaneBits;
+using detail::planes_for;
+using detail::same_glyph;
+
+Pipeline::Impl::~Impl() {
+    if (engine) pcr_hip_engine_destroy(engine);
+    groups.clear();
+    d_bands.clear();
+    staging.clear();
+    result.reset();
+    if (own_stream && stream) pcr_hip_stream_destroy(stream);
+}
+
+Status Pipeline::Impl::init() {
+    const GridConfig& g = cfg.grid;
+    if (g.width <= 0 || g.height <= 0)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: grid dimensions must be positive");
+    if (g.tile_width <= 0 || g.tile_height <= 0)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: tile dimensions must be positive");
+    {
+        Status ok = detail::check_reduction_specs(cfg.reductions);
+        if (!ok.ok()) return ok;
+    }
+
+    // The reference's GPU-initialisation matrix (src/engine/pipeline.cpp:108-162), with its exact messages and status
+    // codes.  Where the reference goes on in CPU mode it prints a Warning / Info line on stderr first; so does this build,
+    // and then Pipeline::create continues on the host engine (host_pipeline.h) -- never silently: the line is printed, and
+    // Pipeline::engine() says which engine a pipeline runs on.  PCR_REQUIRE_GPU_ENGINE=1 in the environment turns every
+    // such fallback into an error (GPU test suites and benchmarks set it: a CPU result must not pass for a GPU one).
+    auto no_cpu_engine = [this](const char* how) {
+        continue_on_host = true;
+        return Status::error(StatusCode::NotImplemented,
+            std::string("pipeline: ") + how + ", and PCR_REQUIRE_GPU_ENGINE forbids it");
+    };
+    int ndev = 0;
+    pcr_hip_device_count(&ndev);
+    if (ndev <= 0) {
+        const std::string msg = "No CUDA-capable GPU detected";
+        if (cfg.exec_mode != ExecutionMode::GPU) {                                                  // Auto, Hybrid
+            std::fprintf(stderr, "Info: %s - using CPU mode\n", msg.c_str());                       // pipeline.cpp:130
+            return no_cpu_engine("no GPU was found and the reference would use its CPU mode");
+        }
+        if (cfg.gpu_require_strict)
+            return Status::error(StatusCode::CudaError, msg + " - GPU mode requested but no GPU available");   // :118-119
+        if (cfg.gpu_fallback_to_cpu) {
+            std::fprintf(stderr, "Warning: %s - falling back to CPU mode\n", msg.c_str());          // :122
+            return no_cpu_engine("the reference would fall back to its CPU mode here");
+        }
+        return Status::error(StatusCode::CudaError, msg + " - GPU required but not available");         // :125-126
+    }
+    Status s = Status::success();
+    if (cfg.cuda_device_id >= 0) {
+        const int rc = cfg.cuda_device_id < ndev ? pcr_hip_set_device(cfg.cuda_device_id) : PCR_HIP_INVALID_ARGUMENT;
+        if (rc != PCR_HIP_OK) {
+            const std::string err_msg = "Failed to set CUDA device " + std::to_string(cfg.cuda_device_id) + ": " +
+                                        (cfg.cuda_device_id < ndev ? std::string(pcr_hip_last_error()) : std::string("invalid device ordinal"));   // :136-137
+            if (cfg.gpu_require_strict) return Status::error(StatusCode::CudaError, err_msg);          // :141
+            if (cfg.gpu_fallback_to_cpu) {
+                std::fprintf(stderr, "Warning: %s - falling back to CPU mode\n", err_msg.c_str());   // :143
+                return no_cpu_engine("the reference would fall back to its CPU mode here");
+            }
+            return Status::error(StatusCode::CudaError, err_msg);                                      // :146
+        }
+    } else {
+        return Status::error(StatusCode::InvalidArgument, "pipeline: invalid device id");
+    }
+    {
+        // pipeline.cpp:149-160, once per device and process (the reference prints it at every create; a bench that
+        // creates a pipeline per step would bury its own output)
+        static std::mutex mu;
+        static std::set<int> announced;
+        std::lock_guard<std::mutex> lock(mu);
+        if (announced.insert(cfg.cuda_device_id).second) {
+            const std::string name = cuda_device_name(cfg.cuda_device_id);
+            size_t free_mem = 0, total_mem = 0;
+            if (cuda_get_memory_info(&free_mem, &total_mem, cfg.cuda_device_id))
+                std::fprintf(stderr, "Info: Using GPU %d: %s (%.1f GB free / %.1f GB total)\n", cfg.cuda_device_id, name.c_str(),
+                             free_mem / (1024.0 * 1024.0 * 1024.0), total_mem / (1024.0 * 1024.0 * 1024.0));
+            else
+                std::fprintf(stderr, "Info: Using GPU %d: %s\n", cfg.cuda_device_id, name.c_str());
+        }
+    }
+    if (cfg.use_cuda_streams) {
+        s = detail::hip_status(pcr_hip_stream_create(&stream));
+        if (!s.ok()) return s;
+        own_stream = true;
+    }
+
+    // accumulation groups + outputs
+    for (const auto& r : cfg.reductions) {
+        int gi = -1;
+        for (size_t k = 0; k < groups.size(); ++k)
+            if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph) &&
+                groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel))
+                gi = (int)k;                                 // (detail::same_group)
+        if (gi < 0) {
+            groups.emplace_back();
+            gi = (int)groups.size() - 1;
+            groups[gi].value_channel = r.value_channel;
+            groups[gi].glyph = r.glyph;
+            groups[gi].select = detail::is_select(r.type);
+            if (groups[gi].select) groups[gi].key_channel = r.timestamp_channel;
+        }
+        // a glyph reduction of an unsupported type is rejected at ingest (as in the reference);
+        // it still gets planes so that finalize has something to read.
+        groups[gi].mask |= planes_for(r.type);
+        Output o;
+        o.group = gi;
+        o.type = r.type;
+        o.band_name = r.output_band_name.empty()
+            ? r.value_channel + "_" + std::to_string(static_cast<int>(r.type)) : r.output_band_name;
+        outputs.push_back(o);
+    }
+
+    // row window of this device
+    int r0 = 0, r1 = g.height;
+    if (cfg.shard_row_begin >= 0 || cfg.shard_row_end >= 0) {
+        r0 = cfg.shard_row_begin < 0 ? 0 : cfg.shard_row_begin;
+        r1 = cfg.shard_row_end < 0 ? g.height : cfg.shard_row_end;
+        if (r0 > r1 || r1 > g.height)
+            return Status::error(StatusCode::InvalidArgument, "pipeline: shard row range outside the grid");
+        for (const auto& gr : groups) halo = std::max(halo, reach_rows(gr.glyph));
+        halo = std::max(halo, cfg.shard_halo_rows);
+        halo = std::min(halo, g.height);
+        // -2 (the out-of-core bands): the block is made of whole reference-tile rows, footprints are clipped to the tile
+        // of their centre cell (Q4), nothing can land outside the block -- no apron rows at all
+        if (cfg.shard_halo_rows == -2 && r0 % g.tile_height == 0 && (r1 % g.tile_height == 0 || r1 == g.height)) halo = 0;
+    }
+    hg = detail::to_hip_grid(g);
+    hg.own_row0 = r0; hg.own_row1 = r1;
+    hg.state_row0 = std::max(0, r0 - halo);
+    hg.state_rows = std::min(g.height, r1 + halo) - hg.state_row0;
+
+    {
+        // arena pre-sized at create, like the reference's MemoryPool; a pool that cannot be created follows the
+        // reference's matrix too (src/engine/pipeline.cpp:181-192)
+        const int rc = pcr_hip_engine_create(&engine, &hg, cfg.gpu_pool_size_bytes, stream);
+        if (rc == PCR_HIP_OUT_OF_MEMORY) {
+            const std::string err_msg = "Failed to create GPU memory pool";
+            if (cfg.gpu_require_strict || !cfg.gpu_fallback_to_cpu) return Status::error(StatusCode::OutOfMemory, err_msg);
+            std::fprintf(stderr, "Warning: %s - falling back to CPU mode\n", err_msg.c_str());
+            return no_cpu_engine("the reference would fall back to its CPU mode here");
+        }
+        s = detail::hip_status(rc);
+        if (!s.ok()) return s;
+    }
+    s = detail::hip_status(pcr_hip_engine_set_path(engine, cfg.scatter_path));
+    if (!s.ok()) return s;
+
+    const int64_t cells = (int64_t)hg.state_rows * hg.width;
+    for (auto& gr : groups) {
+        if (gr.select) {
+            s = gr.packed.allocate((size_t)std::max<int64_t>(cells, 1) * sizeof(uint64_t), MemoryLocation::Device);
+            if (!s.ok()) return s;
+            continue;
+        }
+        for (int p = 0; p < 4; ++p) {
+            if (!(gr.mask & kPlaneBits[p])) continue;
+            s = gr.planes[p].allocate((size_t)std::max<int64_t>(cells, 1) * sizeof(float), MemoryLocation::Device);
+            if (!s.ok()) return s;
+        }
+        gr.view.d_sum = static_cast<float*>(gr.planes[0].data());
+        gr.view.d_wgt = static_cast<float*>(gr.planes[1].data());
+        gr.view.d_max = static_cast<float*>(gr.planes[2].data());
+        gr.view.d_min = static_cast<float*>(gr.planes[3].data());
+    }
+    if (!outputs.empty() && !(s = allocate_result()).ok()) return s;
+    if (!(s = d_bands_done.allocate(std::max<size_t>(groups.size(), 1) * sizeof(uint32_t), MemoryLocation::HostPinned)).ok()) return s;
+    std::memset(d_bands_done.data(), 0, d_bands_done.bytes());
+    return detail::hip_status(pcr_hip_stream_synchronize(stream));
+}
+
+// The slot (0 Sum, 1 Count, 2 Max, 3 Min) of the plane a reduction finalizes unchanged; -1: none.
+int Pipeline::Impl::own_plane(ReductionType t) {
+    return t == ReductionType::Sum ? 0 : t == ReductionType::Count ? 1 : t == ReductionType::Max ? 2 : t == ReductionType::Min ? 3 : -1;
+}
+float* Pipeline::Impl::band_device(size_t r) {
+    return cfg.result_location == MemoryLocation::Device ? result->band_f32((int)r) : static_cast<float*>(d_bands[r].data());
+}
+Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
+    return detail::hip_status(pcr_hip_engine_tile_touched(engine, d, tx, ty));
+}
+// The first Point scatter of a group defines its planes; when this device owns the whole state window (no halo) and
+// nobody outside holds pointers into the state, that scatter's tile pass is asked to store the group's finished bands too
+// -- finalize after a pipeline's only ingest then has nothing to read back (reference: finalize_result re-reads every
+// tile's state, src/engine/pipeline.cpp:1154-1286).
+bool Pipeline::Impl::offer_bands(size_t gi) {
+    const Group& gr = groups[gi];
+    if (gr.select) return false;                   // (its tile pass stores no bands: finalize_select always runs)
+    if (!cfg.finalize_with_first_ingest || gr.defined || gr.glyph.type != GlyphType::Point || state_shared || !result ||
+        !d_bands_done.data()) return false;
+    if (hg.own_row0 != hg.state_row0 || own_rows() != hg.state_rows || own_rows() <= 0) return false;
+    int types[PCR_HIP_MAX_FINALIZE_OUTPUTS];
+    float* dsts[PCR_HIP_MAX_FINALIZE_OUTPUTS];
+    int n = 0;
+    uint32_t own = 0;                              // planes whose own reduction is an output: they can stay in its band
+    for (size_t r = 0; r < outputs.size(); ++r) {
+        if (outputs[r].group != (int)gi) continue;
+        if (n == PCR_HIP_MAX_FINALIZE_OUTPUTS) return false;
+        types[n] = static_cast<int>(outputs[r].type);
+        dsts[n++] = band_device(r);
+        if (own_plane(outputs[r].type) >= 0) own |= kPlaneBits[own_plane(outputs[r].type)];
+    }
+    if (n == 0) return false;
+    if (pcr_hip_engine_finalize_with_scatter(engine, n, types, dsts, static_cast<uint32_t*>(d_bands_done.data()) + gi) != PCR_HIP_OK)
+        return false;
+    return pcr_hip_engine_defer_planes(engine, own & gr.mask) == PCR_HIP_OK;
+}
+
+// ---- plane state ---------------------------------------------------------------------------------------------------------
+// Six pieces of state say who may trust a group's planes, the touched flags and the bands a scatter stored: Group::fresh,
+// defined, bands_with_scatter, planes_in_bands, Impl::state_shared and the device's done words (d_bands_done).  The rule:
+//   * a group's planes hold values only once `defined`; until then a scatter defines them itself and every other reader
+//     fills the identity first (define_identity);
+//   * bands stored by the defining scatter (bands_with_scatter, confirmed by the group's done word) stay good only while
+//     nothing else writes the planes or the touched flags: every such writer calls bands_stale() first;
+//   * planes left in those bands (planes_in_bands) go back (restore_planes) in front of everything that reads or writes the
+//     planes or the flags, finalize apart;
+//   * once a plane or flag pointer has left the pipeline (state_shared) no scatter is offered bands again.
+// Every assignment to that state is in this block: two primitives (restore_planes, bands_stale), the identity fill, and one
+// method per event -- a scatter about to write the planes (bands_stale + scatter_mode), a scatter finished (scatter_done),
+// state imported from outside (bands_stale + state_imported), plane pointers leaving (planes_leave), the writable flag
+// pointer leaving (flags_leave), the host learning a done word is 0 (done_word_is_zero).
+
+// Enqueues the rebuild of the planes a group's defining scatter left in its bands and clears the mask.  The kernel is
+// conditional on the group's done word (0: the scatter stored the planes after all), so no host wait is needed.
+Status Pipeline::Impl::restore_planes(size_t gi, bool* enqueued) {
+    Group& gr = groups[gi];
+    const uint32_t m = gr.planes_in_bands;
+    if (!m) return Status::success();
+    gr.planes_in_bands = 0;
+    const float* src[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t r = 0; r < outputs.size(); ++r) {
+        const int p = outputs[r].group == (int)gi ? own_plane(outputs[r].type) : -1;
+        if (p >= 0 && (m & kPlaneBits[p])) src[p] = band_device(r);
+    }
+    uint32_t* d_touched = nullptr;
+    Status s = touched_flags(&d_touched);
+    if (!s.ok()) return s;
+    if (enqueued) *enqueued = true;
+    return detail::hip_status(pcr_hip_planes_from_bands_if(&hg, &gr.view, m, src, d_touched,
+                                                           static_cast<const uint32_t*>(d_bands_done.data()) + gi, stream));
+}
+Status Pipeline::Impl::restore_all_planes(bool* enqueued) {
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        Status s = restore_planes(gi, enqueued);
+        if (!s.ok()) return s;
+    }
+    return Status::success();
+}
+// Bands a scatter may have stored are stale as soon as anything else writes the planes or the touched flags.
+// Planes those bands still hold are put back FIRST, while the flags and the bands are what the scatter left.
+Status Pipeline::Impl::bands_stale() {
+    Status s = restore_all_planes();
+    for (auto& gr : groups) gr.bands_with_scatter = false;
+    return s;
+}
+// Identity values into a group's planes where nothing has defined them yet.  (finalize's form: it reads the planes of a
+// group only where the done word says they were stored)
+Status Pipeline::Impl::define_identity(Group& gr) {
+    if (gr.defined) return Status::success();
+    const int64_t cells = (int64_t)hg.state_rows * hg.width;
+    if (gr.select) {                                 // the identity of the packed words is 0
+        Status s = detail::hip_status(pcr_hip_memset(gr.packed.data(), 0, (size_t)cells * sizeof(uint64_t), stream));
+        if (!s.ok()) return s;
+        gr.defined = true;
+        return Status::success();
+    }
+    for (int p = 0; p < 4; ++p) {
+        if (!(gr.mask & kPlaneBits[p])) continue;
+        Status s = detail::hip_status(pcr_hip_plane_fill(static_cast<float*>(gr.planes[p].data()), detail::plane_identity(false, p), cells, stream));
+        if (!s.ok()) return s;
+    }
+    gr.defined = true;
+    return Status::success();
+}
+// The same for every reader that may come before the group's first scatter (finalize of an empty pipeline, checkpoints,
+// the halo exchange of a rank without points, state_planes()).
+// Planes the defining scatter left in its bands are put back as well (restore_planes): what this returns from can be read.
+Status Pipeline::Impl::define_planes(Group& gr) {
+    Status s = define_identity(gr);
+    return s.ok() ? restore_planes((size_t)(&gr - groups.data())) : s;
+}
+Status Pipeline::Impl::define_all_planes() {
+    for (auto& gr : groups) {
+        Status s = define_planes(gr);
+        if (!s.ok()) return s;
+    }
+    return Status::success();
+}
+// Event: a scatter is about to write a group's planes (after bands_stale()).  What it is told about them -- 2: the planes
+// are still undefined -- the scatter defines every cell of the state window itself (the binned Point path at no extra pass,
+// every other path by filling first); 1: identity-filled, nothing accumulated yet
+int Pipeline::Impl::scatter_mode(const Group& gr) const {
+    return !gr.defined ? 2 : (gr.fresh && gr.glyph.type == GlyphType::Point ? 1 : 0);
+}
+// Event: that scatter finished.  offered: it was a Point scatter asked to store the group's bands too (offer_bands).
+void Pipeline::Impl::scatter_done(Group& gr, bool offered, bool ok) {
+    gr.fresh = false;
+    gr.bands_with_scatter = offered && ok && pcr_hip_engine_finalize_taken(engine) == 1;
+    gr.planes_in_bands = gr.bands_with_scatter ? (uint32_t)pcr_hip_engine_planes_deferred(engine) : 0u;
+    if (ok) gr.defined = true;           // (n > 0 here: the scatter ran)
+}
+// Event: a group's state was copied in from outside (import_window, after bands_stale()).
+void Pipeline::Impl::state_imported(Group& gr) {
+    gr.defined = true;
+    gr.fresh = false;
+}
+// Event: mutable plane pointers leave the pipeline (state_planes()).
+void Pipeline::Impl::planes_leave() {
+    {
+        DeviceScope dev(cfg.cuda_device_id);
+        bool filled = false;
+        for (const auto& g : groups) filled = filled || !g.defined || g.planes_in_bands != 0;
+        (void)define_all_planes();                      // the caller reads (and may write) them: identity where nothing was ingested
+        // The fills run on the pipeline's stream and the caller may read on any other (torch's current stream, a host copy):
+        // they are complete when the pointers leave.  Planes that were already defined cost no synchronisation.
+        // A MostRecent group leaves as a SNAPSHOT of its two float planes (value in the SUM slot, timestamp in the WGT slot --
+        // the layout of its `.pcrt` files, so a sharded save_state gathers it like an Average group), unpacked from the packed
+        // words at every call: read-only (the words stay the state), reach 0 (a Point glyph: no part in the halo exchange).
+        for (auto& g : groups)
+            if (g.select) { (void)unpack_select(g); filled = true; }
+        if (filled) (void)pcr_hip_stream_synchronize(stream);
+    }
+    for (auto& g : groups) g.fresh = false;             // mutable pointers leave the pipeline: assume the planes get written
+    state_shared = true;
+    (void)bands_stale();                                // (no plane is left in a band: define_all_planes above)
+}
+// Event: the writable touched-flag pointer leaves the pipeline (the flags may be written from outside: the shard exchange does).
+void Pipeline::Impl::flags_leave() {
+    state_shared = true;
+    // planes a scatter left in its bands are rebuilt from the flags as they are now, and on this pipeline's stream: done
+    // before the pointer leaves
+    DeviceScope dev(cfg.cuda_device_id);
+    bool enqueued = false;
+    (void)restore_all_planes(&enqueued);
+    if (enqueued) (void)pcr_hip_stream_synchronize(stream);
+    (void)bands_stale();
+}
+// Event: the blocking finalize read a group's done word after its synchronise and found 0 (the scatter stored every plane).
+void Pipeline::Impl::done_word_is_zero(Group& gr) { gr.planes_in_bands = 0; }
+
+// ---- the shard accessors: where the events above happen --------------------------------------------------------------------
+std::vector<Pipeline::PlaneView> Pipeline::Impl::state_planes() {
+    planes_leave();
+    std::vector<PlaneView> out;
+    for (size_t g = 0; g < groups.size(); ++g)
+        for (int p = 0; p < 4; ++p)
+            if (groups[g].mask & kPlaneBits[p])
+                out.push_back({groups[g].planes[p].data(), (int)kPlaneBits[p], (int)g, groups[g].glyph.type == GlyphType::Point ? 0 : halo});
+    return out;
+}
+
+std::vector<int> Pipeline::Impl::reduction_groups() const {
+    std::vector<int> out;
+    for (const auto& o : outputs) out.push_back(o.group);
+    return out;
+}
+
+void* Pipeline::Impl::tile_touched_device(int* tiles_x, int* tiles_y) {
+    uint32_t* d = nullptr;
+    int32_t tx = 0, ty = 0;
+    if (!touched_flags(&d, &tx, &ty).ok()) return nullptr;
+    flags_leave();
+    if (tiles_x) *tiles_x = tx;
+    if (tiles_y) *tiles_y = ty;
+    return d;
+}
+
+const void* Pipeline::Impl::tile_touched_device_readonly(int* tiles_x, int* tiles_y) const {
+    uint32_t* d = nullptr;
+    int32_t tx = 0, ty = 0;
+    if (!touched_flags(&d, &tx, &ty).ok()) return nullptr;
+    if (tiles_x) *tiles_x = tx;
+    if (tiles_y) *tiles_y = ty;
+    return d;
+}
+
+Status Pipeline::Impl::merge_touched(const void* d_union) {
+    if (!d_union) return Status::error(StatusCode::InvalidArgument, "pipeline: merge_touched: null flags");
+    DeviceScope dev(cfg.cuda_device_id);
+    uint32_t* d = nullptr;
+    int32_t tx = 0, ty = 0;
+    Status s = touched_flags(&d, &tx, &ty);
+    if (!s.ok()) return s;
+    // planes still in the bands go back first: a flag that changes clears the done words, and with them what says where they are
+    if (!(s = restore_all_planes()).ok()) return s;
+    // (the stored bands' device words decide: the host keeps offering them to finalize, whose kernel runs when they are 0)
+    // only a flag of a tile this device owns rows of can change its bands (the union used to drop the stored
+    // bands whenever ANY tile of the grid changed, i.e. always, on shards that do not share every tile)
+    const int th = cfg.grid.tile_height;
+    const int t0 = hg.own_row0 / th, t1 = std::min(ty, (hg.own_row1 + th - 1) / th);
+    return detail::hip_status(pcr_hip_touched_union_owned(d, static_cast<const uint32_t*>(d_union), tx, ty, std::min(t0, t1), t1,
+                                                          static_cast<uint32_t*>(d_bands_done.data()), (int32_t)groups.size(), stream));
+}
+
+const float* Pipeline::Impl::result_band_device(int band) {
+    if (!finalized || !result || band < 0 || band >= (int)outputs.size()) return nullptr;
+    return band_device((size_t)band);
+}
+
+Status Pipeline::Impl::synchronize() { return detail::hip_status(pcr_hip_stream_synchronize(stream)); }
+
+void Pipeline::Impl::profile_enable(bool on, const std::string& only_kernel) {
+    pcr_hip_engine_profile_only(engine, only_kernel.c_str());
+    pcr_hip_engine_profile_enable(engine, on ? 1 : 0);
+}
+
+std::vector<Pipeline::KernelTime> Pipeline::Impl::profile_read(bool reset) {
+    std::vector<KernelTime> out;
+    pcr_hip_kernel_time buf[32];
+    int n = 0;
+    if (pcr_hip_engine_profile_read(engine, buf, 32, &n, reset ? 1 : 0) != PCR_HIP_OK) return out;
+    for (int i = 0; i < std::min(n, 32); ++i) out.push_back({buf[i].name, buf[i].launches, buf[i].total_ms});
+    return out;
+}
+
+Pipeline::ScatterInfo Pipeline::Impl::last_scatter() const {
+    pcr_hip_scatter_stats st{};
+    pcr_hip_engine_stats(engine, &st);
+    int fused = 0, deferred = 0;
+    for (const auto& g : groups) {
+        fused += g.bands_with_scatter ? 1 : 0;
+        deferred |= (int)g.planes_in_bands;
+    }
+    return {st.path, st.lds_tile_w, st.lds_tile_h, st.lds_apron, st.num_bins,
+            (size_t)st.points_in, (size_t)st.points_valid, st.scatter_chunk, fused, deferred};
+}
+
+// A MostRecent group's float-plane view (slot 0 value, slot 1 timestamp), filled from the packed words: what leaves the
+// pipeline (checkpoints, parked bands, state_planes()).  pack_select is the way back.  drop_select_views frees the view
+// once the stream is done with it: between two such calls the group costs its 8 bytes per cell only.
+Status Pipeline::Impl::unpack_select(Group& gr) {
+    if (!gr.select) return Status::success();
+    const int64_t cells = (int64_t)hg.state_rows * hg.width;
+    Status s = define_planes(gr);
+    if (!s.ok()) return s;
+    if (!(s = alloc_select_views(gr)).ok()) return s;
+    return detail::hip_status(pcr_hip_select_unpack(static_cast<const uint64_t*>(gr.packed.data()), static_cast<float*>(gr.planes[0].data()),
+                                                    static_cast<float*>(gr.planes[1].data()), cells, stream));
+}
+Status Pipeline::Impl::alloc_select_views(Group& gr) {
+    const int64_t cells = (int64_t)hg.state_rows * hg.width;
+    for (int p = 0; p < 2; ++p) {
+        if (gr.planes[p].data()) continue;
+        Status s = gr.planes[p].allocate((size_t)std::max<int64_t>(cells, 1) * sizeof(float), MemoryLocation::Device);
+        if (!s.ok()) return s;
+    }
+    return Status::success();
+}
+Status Pipeline::Impl::pack_select(Group& gr) {
+    if (!gr.select) return Status::success();
+    const int64_t cells = (int64_t)hg.state_rows * hg.width;
+    return detail::hip_status(pcr_hip_select_pack(static_cast<const float*>(gr.planes[0].data()), static_cast<const float*>(gr.planes[1].data()),
+                                                  static_cast<uint64_t*>(gr.packed.data()), cells, stream));
+}
+void Pipeline::Impl::drop_select_views() {                           // (call with the stream synchronized)
+    for (auto& gr : groups)
+        if (gr.select) { gr.planes[0].release(); gr.planes[1].release(); }
+}
+
+// rows a glyph can reach above/below its centre row (sizes the halo of a row-block shard)
+int Pipeline::Impl::reach_rows(const GlyphSpec& gl) const {
+    double cap = std::min<double>(std::max(0.0f, gl.max_radius_cells), 1 << 20);
+    if (gl.type == GlyphType::Gaussian) return (int)std::ceil(cap);
+    if (gl.type == GlyphType::Line) {
+        double hy = std::fabs((double)gl.default_half_length / cfg.grid.cell_size_y);
+        return (int)std::ceil(std::max(hy, cap)) + 1;
+    }
+    return 0;
+}
+
+// A footprint is clipped to the reference tile of its centre cell (Q4): when the owned block is made of whole
+// tile rows nothing can land outside it, whatever the glyph.
+bool Pipeline::Impl::block_is_whole_tiles() const {
+    const int th = cfg.grid.tile_height;
+    return hg.own_row0 % th == 0 && (hg.own_row1 % th == 0 || hg.own_row1 == hg.height);
+}
+
+// Row-block shards: a Line glyph with a per-point half_length channel reaches |hl_i / cell_size_y| rows (+1 for
+// the rounding of the end points), and on north-up grids max_radius_cells does not cap that (hy < 0 passes
+// std::min(h, cap) untouched, glyph_kernels.cu:228-234).  Cells beyond the halo would be clipped by the state
+// window and never reach their owner: refuse instead of returning a grid that differs from the unsharded one.
+// rows_needed: the reach of the longest segment among the points the filter keeps (0: the check does not apply).
+Status Pipeline::Impl::line_reach_rows(const GlyphSpec& gl, const void* d_half_length, const uint8_t* d_mask, size_t n, int* rows_needed) {
+    *rows_needed = 0;
+    if (gl.type != GlyphType::Line || !d_half_length) return Status::success();
+    if (own_rows() == hg.height || block_is_whole_tiles()) return Status::success();
+    detail::Buffer& word = staging["line_reach:word"];           // the reduction's device word, kept for the pipeline's life
+    if (word.bytes() < 4) {
+        Status a = word.allocate(256, MemoryLocation::Device);
+        if (!a.ok()) return a;
+    }
+    // hy = half_length / cell_size_y goes through std::min(hy, cap) (glyph_kernels.cu:228-234): the sign of half_length
+    // that makes hy positive is capped by max_radius_cells, the other one reaches |half_length / cell_size_y| rows
+    float max_pos = 0.f, max_neg = 0.f;
+    Status s = detail::hip_status(pcr_hip_signed_max_f32_masked(static_cast<const float*>(d_half_length), d_mask, n,
+                                                                static_cast<uint32_t*>(word.data()), &max_pos, &max_neg, stream));
+    if (!s.ok()) return s;
+    const double acsy = std::fabs(cfg.grid.cell_size_y);
+    const float capped_side = cfg.grid.cell_size_y > 0 ? max_pos : max_neg;
+    const float free_side = cfg.grid.cell_size_y > 0 ? max_neg : max_pos;
+    double rows = std::max(std::ceil((double)free_side / acsy),
+                           std::min(std::ceil((double)capped_side / acsy), std::ceil((double)std::max(gl.max_radius_cells, 0.0f))));
+    rows += 1.0;                                                 // rounding of the end points
+    rows = std::min<double>(rows, cfg.grid.tile_height - 1);
+    *rows_needed = (int)rows;
+    return Status::success();
+}
+
+Status Pipeline::Impl::reach_error(int rows) const {
+    return Status::error(StatusCode::InvalidArgument,
+        "pipeline: a Line segment of this cloud reaches " + std::to_string((long long)rows) +
+        " rows beyond its centre row, but this row-block shard keeps a halo of " + std::to_string(halo) +
+        " rows (sized from default_half_length / max_radius_cells); set PipelineConfig.shard_halo_rows >= " +
+        std::to_string((long long)rows) + " on every rank, or use tile-aligned row blocks");
+}
+
+// Device pointer of a named array of the cloud; host-resident arrays are staged to HBM.
+Status Pipeline::Impl::device_array(const void* src, MemoryLocation loc, size_t bytes, const std::string& key, const void** out) {
+    if (loc == MemoryLocation::Device) { *out = src; return Status::success(); }
+    detail::Buffer& b = staging[key];
+    if (b.bytes() < bytes) {
+        // earlier kernels may still read the old block
+        Status s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+        if (!s.ok()) return s;
+        s = b.allocate(bytes + bytes / 8, MemoryLocation::Device);
+        if (!s.ok()) return s;
+    }
+    Status s = detail::hip_status(pcr_hip_memcpy_h2d(b.data(), src, bytes, stream));
+    if (!s.ok()) return s;
+    *out = b.data();
+    return Status::success();
+}
+
+// Rows the Line groups of this pipeline need beyond a centre row for THIS cloud (0 when no check applies): what
+// ingest() would refuse above the shard's halo.  A sharded caller reduces it over the ranks (MAX) first, so that
+// every rank refuses together instead of one rank raising while the others wait in a collective.  The filter is
+// not applied here (an upper bound: ingest() itself checks the kept points only).
+Status Pipeline::Impl::query_line_reach(const PointCloud& cloud, int* rows_out) {
+    *rows_out = 0;
+    const size_t n = cloud.count();
+    if (n == 0) return Status::success();
+    DeviceScope dev(cfg.cuda_device_id);
+    for (const auto& gr : groups) {
+        if (gr.glyph.type != GlyphType::Line || gr.glyph.half_length_channel.empty()) continue;
+        const ChannelDesc* d = cloud.channel(gr.glyph.half_length_channel);
+        if (!d || d->dtype != DataType::Float32) continue;
+        const void* hl = nullptr;
+        Status s = device_array(cloud.channel_data(gr.glyph.half_length_channel), cloud.location(), n * sizeof(float),
+                                "ch:" + gr.glyph.half_length_channel, &hl);
+        if (!s.ok()) return s;
+        int rows = 0;
+        if (!(s = line_reach_rows(gr.glyph, hl, nullptr, n, &rows)).ok()) return s;
+        *rows_out = std::max(*rows_out, rows);
+    }
+    return Status::success();
+}
+
+// A Line / Gaussian GlyphSpec as the C-ABI takes it: the defaults, and the per-point channels the cloud has (null: the default).
+Status Pipeline::Impl::marshal_glyph(const GlyphSpec& gl, const detail::ChannelLookup& channel, pcr_hip_glyph* out) const {
+    *out = pcr_hip_glyph{};
+    out->type = static_cast<int32_t>(gl.type);
+    out->default_direction = gl.default_direction;
+    out->default_half_length = gl.default_half_length;
+    out->default_sigma_x = gl.default_sigma_x;
+    out->default_sigma_y = gl.default_sigma_y;
+    out->default_rotation = gl.default_rotation;
+    out->max_radius_cells = gl.max_radius_cells;
+    Status s = channel(gl.direction_channel, &out->d_direction);
+    if (s.ok()) s = channel(gl.half_length_channel, &out->d_half_length);
+    if (s.ok()) s = channel(gl.sigma_x_channel, &out->d_sigma_x);
+    if (s.ok()) s = channel(gl.sigma_y_channel, &out->d_sigma_y);
+    if (s.ok()) s = channel(gl.rotation_channel, &out->d_rotation);
+    return s;
+}
+
+Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
+    const size_t n = cloud.count();
+    if (n == 0) return Status::success();
+    DeviceScope dev(cfg.cuda_device_id);
+    // validate every predicate and reduction before touching state (pipeline_common.cpp: the reference's checks and messages)
+    {
+        Status ok = detail::validate_cloud(cfg, cloud, PCR_HIP_MAX_FILTER_SET, PCR_HIP_MAX_FILTER_PREDICATES);
+        if (!ok.ok()) return ok;
+    }
+    detail::Reprojection rp;
+    {
+        Status ok = detail::plan_reprojection(cfg, cloud, &rp);
+        if (!ok.ok()) return ok;
+    }
+
+    const MemoryLocation loc = cloud.location();
+    const void *dx = nullptr, *dy = nullptr;
+    Status s = device_array(cloud.x(), loc, n * sizeof(double), "x", &dx);
+    if (!s.ok()) return s;
+    s = device_array(cloud.y(), loc, n * sizeof(double), "y", &dy);
+    if (!s.ok()) return s;
+    // A cloud in another CRS than the grid's: x, y transformed into a staging buffer of their own (the caller's device
+    // arrays are only read), which every kernel below reads instead
+    if (rp.needed) {
+        detail::Buffer& rb = staging["reproject:xy"];
+        if (rb.bytes() < 2 * n * sizeof(double)) {
+            // earlier kernels (chunks of ingest_async / ingest_file still in flight) may still read the old block
+            if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
+            if (!(s = rb.allocate(2 * (n + n / 8) * sizeof(double), MemoryLocation::Device)).ok()) return s;
+        }
+        const size_t cap = rb.bytes() / (2 * sizeof(double));
+        double* rx = static_cast<double*>(rb.data());
+        double* ry = rx + cap;
+        s = detail::hip_status(pcr_hip_transform_xy(&rp.src, &rp.dst, static_cast<const double*>(dx),
+                                                    static_cast<const double*>(dy), rx, ry, n, stream));
+        if (!s.ok()) return s;
+        dx = rx;
+        dy = ry;
+    }
+
+    std::map<std::string, const float*> staged;      // a channel is staged once per ingest, whoever asks first
+    const detail::ChannelLookup f32_channel = [&](const std::string& name, const float** out) -> Status {
+        *out = nullptr;
+        if (name.empty()) return Status::success();
+        const ChannelDesc* d = cloud.channel(name);
+        if (!d || d->dtype != DataType::Float32) return Status::success();   // -> GlyphSpec default
+        auto hit = staged.find(name);
+        if (hit != staged.end()) { *out = hit->second; return Status::success(); }
+        const void* p = nullptr;
+        Status st = device_array(cloud.channel_data(name), loc, n * sizeof(float), "ch:" + name, &p);
+        if (st.ok()) staged[name] = *out = static_cast<const float*>(p);
+        return st;
+    };
+
+    // Filter stage, on the device: a byte mask evaluated once per ingest and honoured by every
+    // routing kernel.  (The reference gathers values by filter index but routes the UNFILTERED
+    // cloud, pipeline.cpp:436-438 vs :662, which is why its own WithFilter test is disabled;
+    // here a filtered-out point simply does not exist for any reduction.)
+    size_t kept = n;
+    const uint8_t* active_mask = nullptr;
+    if (!cfg.filter.empty()) {
+        std::vector<pcr_hip_predicate> preds;
+        if (!(s = detail::marshal_predicates(cfg.filter, f32_channel, &preds)).ok()) return s;
+        detail::Buffer& mb = staging["filter:mask"];
+        if (mb.bytes() < n + 8) {
+            if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
+            if (!(s = mb.allocate(n + n / 8 + 16, MemoryLocation::Device)).ok()) return s;
+        }
+        if (!(s = detail::count_survivors(preds, n, mb.data(), stream, &kept)).ok()) return s;
+        if (kept == 0) return Status::success();             // pipeline.cpp:349-353
+        active_mask = detail::filter_mask_of(mb.data());
+        pcr_hip_engine_set_point_mask(engine, active_mask);
+    }
+    struct MaskGuard {
+        pcr_hip_engine* e;
+        ~MaskGuard() { pcr_hip_engine_set_point_mask(e, nullptr); }
+    } mask_guard{engine};
+
+    // Row-block shards: every Line group's reach is checked BEFORE the first scatter of this ingest, so a refused
+    // cloud leaves no group half-accumulated (and, sharded, every rank can agree on the verdict first:
+    // Pipeline::line_reach_rows + pcr.distributed.ShardedPipeline.ingest).
+    int reach_needed = 0;
+    for (const auto& gr : groups) {
+        if (gr.glyph.type != GlyphType::Line) continue;
+        const float* hl = nullptr;
+        if (!(s = f32_channel(gr.glyph.half_length_channel, &hl)).ok()) return s;
+        int rows = 0;
+        if (!(s = line_reach_rows(gr.glyph, hl, active_mask, n, &rows)).ok()) return s;
+        reach_needed = std::max(reach_needed, rows);
+    }
+    if (reach_needed > halo) return reach_error(reach_needed);
+
+    // (this cloud's points change the planes and the touched flags)
+    if (!(s = bands_stale()).ok()) return s;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        Group& gr = groups[gi];
+        const float* dv = nullptr;
+        s = f32_channel(gr.value_channel, &dv);
+        if (!s.ok()) return s;
+        pcr_hip_engine_planes_fresh(engine, scatter_mode(gr));
+        bool offered = false;
+        if (gr.select) {                             // (Point glyph: validate_cloud refused anything else)
+            const float* dk = nullptr;
+            if (!(s = f32_channel(gr.key_channel, &dk)).ok()) return s;
+            s = detail::hip_status(pcr_hip_scatter_select(
+                engine, static_cast<uint64_t*>(gr.packed.data()), static_cast<const double*>(dx), static_cast<const double*>(dy), dv, dk, n));
+        } else if (gr.glyph.type == GlyphType::Point) {
+            offered = offer_bands(gi);
+            s = detail::hip_status(pcr_hip_scatter_point(
+                engine, gr.mask, &gr.view, static_cast<const double*>(dx), static_cast<const double*>(dy), dv, n));
+        } else {
+            pcr_hip_glyph hgph{};
+            if (!(s = marshal_glyph(gr.glyph, f32_channel, &hgph)).ok()) return s;
+            s = detail::hip_status(pcr_hip_scatter_glyph(
+                engine, &hgph, gr.mask & (PCR_HIP_PLANE_SUM | PCR_HIP_PLANE_WGT), &gr.view,
+                static_cast<const double*>(dx), static_cast<const double*>(dy), dv, n));
+        }
+        scatter_done(gr, offered, s.ok());
+        if (!s.ok()) return s;
+    }
+    // host arrays may be reused by the caller as soon as we return (ingest_async: page-locked arrays are
+    // read by the DMA engine later, the caller keeps them alive until synchronize())
+    if (loc != MemoryLocation::Device && (wait || loc != MemoryLocation::HostPinned)) {
+        s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+        if (!s.ok()) return s;
+    }
+
+    points += kept;                 // points_processed += filtered_count (pipeline.cpp:749)
+    collections++;
+    if (callback) {
+        ProgressInfo info = stats();
+        if (!callback(info))
+            return Status::error(StatusCode::InvalidArgument, "pipeline: cancelled by user");
+    }
+    return Status::success();
+}
+
+// The result grid (and, for a host-resident result, its device-side band buffers) is allocated
+// once, at create: finalize only launches kernels.
+Status Pipeline::Impl::allocate_result() {
+    const int rows = own_rows();
+    const int W = hg.width;
+    std::vector<BandDesc> bands;
+    for (const auto& o : outputs) {
+        BandDesc b;
+        b.name = o.band_name;
+        b.dtype = DataType::Float32;
+        b.is_state = false;
+        bands.push_back(b);
+    }
+    if (bands.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+    if (rows <= 0) { result.reset(); return Status::success(); }
+    const bool on_device = cfg.result_location == MemoryLocation::Device;
+    result = on_device ? Grid::create(W, rows, bands, MemoryLocation::Device)
+                       : Grid::create_host_page_locked(W, rows, bands);
+    if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+    if (!on_device) {
+        d_bands.resize(outputs.size());
+        for (auto& b : d_bands) {
+            Status s = b.allocate((size_t)rows * W * sizeof(float), MemoryLocation::Device);
+            if (!s.ok()) return s;
+        }
+    }
+    return Status::success();
+}
+
+Status Pipeline::Impl::finalize(bool wait) {
+    const int rows = own_rows();
+    const int W = hg.width;
+    if (outputs.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+    if (rows <= 0) return Status::success();
+    DeviceScope dev(cfg.cuda_device_id);
+    const bool on_device = cfg.result_location == MemoryLocation::Device;
+    if (!result) {
+        Status as = allocate_result();
+        if (!as.ok()) return as;
+    }
+    for (auto& gr : groups) {                     // a group no cloud ever reached
+        Status ds = define_identity(gr);
+        if (!ds.ok()) return ds;
+    }
+    uint32_t* d_touched = nullptr;
+    Status s = touched_flags(&d_touched);
+    if (!s.ok()) return s;
+    // Bands the defining scatter may have stored: whether it did is a word the device wrote (not when the scan split a
+    // bin; cleared again by a touched-flag union that changed a flag).  The blocking call is going to wait for the stream
+    // anyway: it waits FIRST, reads the word, and enqueues the group's kernel only when the word says the bands are not
+    // there -- after a pipeline's only ingest nothing runs behind the tile pass.  finalize_async leaves the decision to
+    // the kernel (pcr_hip_finalize_group_unless), which reads the word when it runs.
+    bool host_decides = false;
+    if (wait)
+        for (const auto& gr : groups) host_decides = host_decides || gr.bands_with_scatter;
+    if (host_decides) {
+        s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+        if (!s.ok()) return s;
+    }
+    bool enqueued = !host_decides;           // anything on the stream since that synchronise
+    // one sweep per accumulation group: its planes are read once for all of its bands
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        std::vector<int> types;
+        std::vector<float*> dsts;
+        std::vector<size_t> bands_of;
+        auto flush = [&]() -> Status {
+            if (types.empty()) return Status::success();
+            // (a group whose bands the defining scatter stored: the kernel returns at once when the device word says so)
+            const uint32_t* done = groups[gi].bands_with_scatter ? static_cast<const uint32_t*>(d_bands_done.data()) + gi : nullptr;
+            if (done && host_decides) {
+                if (*static_cast<const volatile uint32_t*>(done) != 0u) { types.clear(); dsts.clear(); return Status::success(); }
+                done = nullptr;              // (known to be 0: the kernel need not read it across the bus)
+                done_word_is_zero(groups[gi]);
+            }
+            enqueued = true;
+            Status fs = detail::hip_status(pcr_hip_finalize_group_unless(&hg, &groups[gi].view, d_touched, (int)types.size(),
+                                                                         types.data(), dsts.data(), done, stream));
+            types.clear();
+            dsts.clear();
+            return fs;
+        };
+        for (size_t r = 0; r < outputs.size(); ++r) {
+            if (outputs[r].group != (int)gi) continue;
+            if (groups[gi].select) {
+                s = detail::hip_status(pcr_hip_finalize_select(&hg, static_cast<const uint64_t*>(groups[gi].packed.data()), d_touched,
+                                                               band_device(r), stream));
+                if (!s.ok()) return s;
+                enqueued = true;
+                bands_of.push_back(r);
+                continue;
+            }
+            types.push_back(static_cast<int>(outputs[r].type));
+            dsts.push_back(band_device(r));
+            bands_of.push_back(r);
+            if (types.size() == PCR_HIP_MAX_FINALIZE_OUTPUTS && !(s = flush()).ok()) return s;
+        }
+        if (!(s = flush()).ok()) return s;
+        if (!on_device) {
+            for (size_t r : bands_of) {
+                enqueued = true;
+                s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)r), d_bands[r].data(),
+                                                          (size_t)rows * W * sizeof(float), stream));
+                if (!s.ok()) return s;
+            }
+        }
+    }
+    // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
+    // kernels on the same stream; only the levels (a third of the data) cross the bus, the host never halves the grid.
+    std::vector<std::unique_ptr<Grid>> levels;
+    const GeoTiffOptions out_opt = pipeline_output_options(cfg.write_cog);
+    if (!cfg.output_path.empty() && out_opt.overviews != 0) {
+        const int n = detail::overview_levels(out_opt.overviews, W, rows);
+        if (n > 0) {
+            std::vector<const float*> dev_bands;
+            std::vector<BandDesc> descs;
+            for (size_t r = 0; r < outputs.size(); ++r) {
+                dev_bands.push_back(band_device(r));
+                descs.push_back(result->band_desc((int)r));
+            }
+            std::vector<std::unique_ptr<Grid>> d_levels;
+            s = detail::build_overviews_device(dev_bands, W, rows, descs, n, detail::overview_mode(out_opt.overview_resampling),
+                                               stream, d_levels);
+            if (!s.ok()) return s;
+            enqueued = true;
+            for (const auto& d : d_levels) {
+                auto h = Grid::create_host_page_locked(d->cols(), d->rows(), descs);
+                if (!h) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate the overview levels");
+                if (!(s = h->copy_from(*d, stream)).ok()) return s;
+                levels.push_back(std::move(h));
+            }
+            s = detail::hip_status(pcr_hip_stream_synchronize(stream));      // d_levels is released at the end of this block
+            if (!s.ok()) return s;
+            enqueued = false;
+        }
+    }
+    std::vector<const Grid*> level_ptrs;
+    for (const auto& l : levels) level_ptrs.push_back(l.get());
+    // finalize_async: a device-resident result is stream-ordered like everything else on the device
+    if ((wait || !on_device || !cfg.output_path.empty()) && enqueued) {
+        s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+        if (!s.ok()) return s;
+    }
+    finalized = true;
+    if (!cfg.output_path.empty()) {
+        // pipeline.cpp:1351-1361 of the reference: the finalized grid goes to output_path as GeoTIFF.
+        // A shard writes its own row block (georeferenced as such); a device-resident result is copied out first.
+        GridConfig out_cfg = cfg.grid;
+        if (rows != cfg.grid.height) {
+            out_cfg.height = rows;
+            out_cfg.bounds.max_y = cfg.grid.bounds.max_y + hg.own_row0 * cfg.grid.cell_size_y;
+            out_cfg.bounds.min_y = out_cfg.bounds.max_y + rows * cfg.grid.cell_size_y;
+            if (out_cfg.bounds.min_y > out_cfg.bounds.max_y) std::swap(out_cfg.bounds.min_y, out_cfg.bounds.max_y);
+        }
+        if (on_device) {
+            std::unique_ptr<Grid> host = result->to(MemoryLocation::Host);
+            if (!host) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to copy the result grid to the host");
+            return write_geotiff(cfg.output_path, *host, out_cfg, out_opt, level_ptrs);
+        }
+        return write_geotiff(cfg.output_path, *result, out_cfg, out_opt, level_ptrs);
+    }
+    return Status::success();
+}
+
+// ---- `.pcrt` checkpoints ---------------------------------------------------------------
+// A whole-grid pipeline checkpoints every touched tile.  A row-block shard WRITES the tiles it owns whole -- which is all
+// of them when its block is made of whole reference-tile rows (ShardedPipeline(align = tile_height); the N = 2 and 4 blocks
+// of C5): every rank writes its own files into the same directory and their union is the pipeline's checkpoint, readable
+// by an unsharded pipeline too.  A block that cuts tiles shares them with its neighbours: ShardedPipeline::save_state
+// gathers the state to one rank for those.  Any shard LOADS: it takes its own rows out of every tile file they meet.
+Status Pipeline::Impl::checkpoint_dir(const std::string& dir_in, std::string* dir, bool writing) const {
+    *dir = dir_in.empty() ? cfg.state_dir : dir_in;
+    if (dir->empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
+    if (writing && own_rows() != hg.height && !block_is_whole_tiles())
+        return Status::error(StatusCode::NotImplemented,
+            "pipeline: this row block cuts a reference tile it shares with a neighbour, so no rank can write that tile alone: "
+            "ShardedPipeline.save_state gathers the state for it, or shard with align = tile_height");
+    return Status::success();
+}
+detail::StateWindow Pipeline::Impl::state_window(std::vector<std::vector<float>>& planes) const {
+    detail::StateWindow w = detail::window_over(planes, hg.state_row0, hg.state_rows);
+    w.own_row0 = hg.own_row0;
+    w.own_row1 = hg.own_row1;
+    return w;
+}
+
+Status Pipeline::Impl::export_window(std::vector<std::vector<float>>& planes, std::vector<uint32_t>& touched) {
+    DeviceScope dev(cfg.cuda_device_id);
+    Status s = define_all_planes();
+    if (!s.ok()) return s;
+    const size_t cells = (size_t)hg.state_rows * hg.width;
+    planes.assign(groups.size() * 4, {});
+    for (auto& gr : groups)
+        if (!(s = unpack_select(gr)).ok()) return s;
+    for (size_t gi = 0; gi < groups.size(); ++gi)
+        for (int p = 0; p < 4; ++p) {
+            if (!(groups[gi].mask & kPlaneBits[p])) continue;
+            planes[gi * 4 + p].resize(cells);
+            s = detail::hip_status(pcr_hip_memcpy_d2h(planes[gi * 4 + p].data(), groups[gi].planes[p].data(), cells * sizeof(float), stream));
+            if (!s.ok()) return s;
+        }
+    uint32_t* d_touched = nullptr;
+    int tx = 0, ty = 0;
+    if (!(s = touched_flags(&d_touched, &tx, &ty)).ok()) return s;
+    touched.resize((size_t)tx * ty);
+    if (!(s = detail::hip_status(pcr_hip_memcpy_d2h(touched.data(), d_touched, touched.size() * 4, stream))).ok()) return s;
+    s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+    if (!state_shared) drop_select_views();
+    return s;
+}
+Status Pipeline::Impl::import_window(const std::vector<std::vector<float>>& planes, const std::vector<uint32_t>& touched) {
+    DeviceScope dev(cfg.cuda_device_id);
+    Status s = bands_stale();
+    if (!s.ok()) return s;
+    const size_t cells = (size_t)hg.state_rows * hg.width;
+    if (planes.size() != groups.size() * 4)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: parked state does not match the pipeline's groups");
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        if (groups[gi].select && !(s = alloc_select_views(groups[gi])).ok()) return s;
+        for (int p = 0; p < 4; ++p) {
+            if (!(groups[gi].mask & kPlaneBits[p])) continue;
+            if (planes[gi * 4 + p].size() != cells)
+                return Status::error(StatusCode::InvalidArgument, "pipeline: parked state does not match the band's window");
+            s = detail::hip_status(pcr_hip_memcpy_h2d(groups[gi].planes[p].data(), planes[gi * 4 + p].data(), cells * sizeof(float), stream));
+            if (!s.ok()) return s;
+        }
+        // (a state that comes from outside is judged by the acceptance rule again: a NaN or <= -FLT_MAX timestamp = empty)
+        if (groups[gi].select && !(s = pack_select(groups[gi])).ok()) return s;
+        state_imported(groups[gi]);
+    }
+    uint32_t* d_touched = nullptr;
+    int tx = 0, ty = 0;
+    if (!(s = touched_flags(&d_touched, &tx, &ty)).ok()) return s;
+    if (touched.size() != (size_t)tx * ty)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: parked touched flags do not match the tile grid");
+    if (!(s = detail::hip_status(pcr_hip_memcpy_h2d(d_touched, touched.data(), touched.size() * 4, stream))).ok()) return s;
+    s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+    if (!state_shared) drop_select_views();
+    return s;
+}
+
+std::vector<detail::StateOutput> Pipeline::Impl::state_outputs() const {
+    std::vector<detail::StateOutput> o;
+    for (const auto& out : outputs) o.push_back({out.group, out.type});
+    return o;
+}
+
+Status Pipeline::Impl::save_state(const std::string& dir_in) {
+    std::string dir;
+    Status s = checkpoint_dir(dir_in, &dir, true);
+    if (!s.ok()) return s;
+    std::vector<std::vector<float>> planes;
+    std::vector<uint32_t> touched;
+    if (!(s = export_window(planes, touched)).ok()) return s;
+    return detail::write_state_tiles(cfg.grid, state_outputs(), state_window(planes), touched, dir);
+}
+
+Status Pipeline::Impl::load_state(const std::string& dir_in) {
+    std::string dir;
+    Status s = checkpoint_dir(dir_in, &dir, false);
+    if (!s.ok()) return s;
+    std::vector<std::vector<float>> planes;
+    std::vector<uint32_t> touched;
+    if (!(s = export_window(planes, touched)).ok()) return s;          // files overlay the current state
+    size_t loaded = 0;
+    if (!(s = detail::read_state_tiles(cfg.grid, state_outputs(), state_window(planes), touched, dir, &loaded)).ok()) return s;
+    if (!loaded) return Status::success();
+    return import_window(planes, touched);                              // (drops bands a scatter stored, marks the planes defined)
+}
+
+ProgressInfo Pipeline::Impl::stats() const {
+    ProgressInfo info;
+    info.collections_processed = collections;
+    info.collections_total = 0;
+    info.points_processed = points;
+    info.tiles_active = 0;
+    DeviceScope dev(cfg.cuda_device_id);
+    uint32_t* d_touched = nullptr;
+    int tx = 0, ty = 0;
+    if (engine && touched_flags(&d_touched, &tx, &ty).ok()) {
+        std::vector<uint32_t> h((size_t)tx * ty);
+        if (pcr_hip_memcpy_d2h(h.data(), d_touched, h.size() * sizeof(uint32_t), stream) == PCR_HIP_OK &&
+            pcr_hip_stream_synchronize(stream) == PCR_HIP_OK)
+            for (uint32_t v : h) info.tiles_active += v ? 1 : 0;
+    }
+    info.elapsed_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
+    return info;
+}
+
+}  // namespace pcr

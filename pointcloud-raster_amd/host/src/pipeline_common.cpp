@@ -1,6 +1,8 @@
 // pipeline_common.cpp -- what the engines behind pcr::Pipeline share: the cloud checks, `.pcrt` tile files of a window of state planes (see pipeline_common.h).
 #include "pipeline_common.h"
 
+#include "buffer.h"
+
 #include "pcr/core/point_cloud.h"
 #include "pcr/core/reproject.h"
 #include "pcr/io/tile_state_io.h"
@@ -41,6 +43,32 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
                 return Status::error(StatusCode::InvalidArgument, "pipeline: timestamp channel must be Float32");
         }
     }
+    return Status::success();
+}
+
+Status marshal_predicates(const FilterSpec& filter, const ChannelLookup& channel, std::vector<pcr_hip_predicate>* out) {
+    out->assign(filter.predicates.size(), pcr_hip_predicate{});
+    for (size_t k = 0; k < out->size(); ++k) {
+        const FilterPredicate& pr = filter.predicates[k];
+        pcr_hip_predicate& hp = (*out)[k];
+        Status s = channel(pr.channel_name, &hp.d_channel);
+        if (!s.ok()) return s;
+        hp.op = static_cast<int32_t>(pr.op);
+        hp.value = pr.value;
+        hp.set_size = static_cast<int32_t>(pr.value_set.size());
+        for (size_t j = 0; j < pr.value_set.size(); ++j) hp.set[j] = pr.value_set[j];
+    }
+    return Status::success();
+}
+
+Status count_survivors(const std::vector<pcr_hip_predicate>& preds, size_t n, void* d_buffer, pcr_hip_stream stream, size_t* kept) {
+    auto* d_count = static_cast<unsigned long long*>(d_buffer);
+    Status s = hip_status(pcr_hip_filter_mask(preds.data(), (int)preds.size(), n, filter_mask_of(d_buffer), d_count, stream));
+    if (!s.ok()) return s;
+    unsigned long long h_count = 0;
+    if (!(s = hip_status(pcr_hip_memcpy_d2h(&h_count, d_count, sizeof h_count, stream))).ok()) return s;
+    if (!(s = hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
+    *kept = (size_t)h_count;
     return Status::success();
 }
 

@@ -163,6 +163,39 @@ struct StateWindow {
     int own_row0 = -1, own_row1 = -1;      // >= 0: only tiles whose rows lie inside [own_row0, own_row1) (a shard with apron rows)
     std::function<float*(int group, int p)> plane;
 };
+/// The window [row0, row0 + rows) over host copies laid out planes[4 g + p] (empty: group g has no plane p).
+inline StateWindow window_over(std::vector<std::vector<float>>& planes, int row0, int rows) {
+    StateWindow w;
+    w.row0 = row0;
+    w.rows = rows;
+    w.plane = [&planes](int g, int p) -> float* {
+        auto& v = planes[(size_t)g * 4 + (size_t)p];
+        return v.empty() ? nullptr : v.data();
+    };
+    return w;
+}
+
+/// The C-ABI's view of a whole grid: own and state rows cover the full height (a shard overrides its rows and halo).
+inline pcr_hip_grid to_hip_grid(const GridConfig& g) {
+    pcr_hip_grid hg{};
+    hg.min_x = g.bounds.min_x; hg.min_y = g.bounds.min_y; hg.max_x = g.bounds.max_x; hg.max_y = g.bounds.max_y;
+    hg.cell_size_x = g.cell_size_x; hg.cell_size_y = g.cell_size_y;
+    hg.width = g.width; hg.height = g.height;
+    hg.tile_width = g.tile_width; hg.tile_height = g.tile_height;
+    hg.own_row0 = 0; hg.own_row1 = g.height;
+    hg.state_row0 = 0; hg.state_rows = g.height;
+    return hg;
+}
+
+// ---- the filter stage on the device (pcr_hip_filter_mask) ----------------------------------------------------------------
+/// Device pointer of a named Float32 channel of the cloud being ingested (null: the cloud has no such channel).
+using ChannelLookup = std::function<Status(const std::string& name, const float** d_channel)>;
+/// The FilterSpec as the C-ABI takes it, its channels resolved through `channel` in the predicates' order.
+Status marshal_predicates(const FilterSpec& filter, const ChannelLookup& channel, std::vector<pcr_hip_predicate>* out);
+/// Evaluates the predicates over n points into d_buffer, laid out [u64 survivor count][n mask bytes] (at least n + 8 bytes of
+/// device memory), waits for the stream and returns the count.  The mask starts at filter_mask_of(d_buffer).
+Status count_survivors(const std::vector<pcr_hip_predicate>& preds, size_t n, void* d_buffer, pcr_hip_stream stream, size_t* kept);
+inline uint8_t* filter_mask_of(void* d_buffer) { return static_cast<uint8_t*>(d_buffer) + 8; }
 
 // ---- reprojection on ingest (PipelineConfig::target_crs / auto_reproject; pcr/core/reproject.h) ---------------------------
 /// CRS -> the C-ABI's descriptor; CrsError when it is unidentified or not supported.  role: "source" / "destination".

@@ -316,11 +316,7 @@ Status ShardedPipeline::ingest_unrouted(const PointCloud& cloud_in, size_t* inge
     std::vector<int32_t> splits((size_t)world_ + 1);
     for (int r = 0; r < world_; ++r) splits[(size_t)r] = row_block(r, world_, height_, align_).first;
     splits[(size_t)world_] = height_;
-    pcr_hip_grid hg{};
-    hg.min_x = grid_.bounds.min_x; hg.min_y = grid_.bounds.min_y; hg.max_x = grid_.bounds.max_x; hg.max_y = grid_.bounds.max_y;
-    hg.cell_size_x = grid_.cell_size_x; hg.cell_size_y = grid_.cell_size_y;
-    hg.width = grid_.width; hg.height = grid_.height; hg.tile_width = grid_.tile_width; hg.tile_height = grid_.tile_height;
-    hg.own_row0 = 0; hg.own_row1 = grid_.height; hg.state_row0 = 0; hg.state_rows = grid_.height;    // the routing sees the whole grid
+    const pcr_hip_grid hg = detail::to_hip_grid(grid_);                 // the routing sees the whole grid
 
     // 1. owner of every point, points per owner
     std::vector<uint64_t> send_counts((size_t)PCR_HIP_MAX_ROUTE_PARTS, 0), recv_counts((size_t)PCR_HIP_MAX_ROUTE_PARTS, 0);

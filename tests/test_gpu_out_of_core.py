@@ -93,6 +93,48 @@ def test_out_of_core_equals_in_core_bit_for_bit(tmp_path, host_cache):
     assert st.points_processed == 240_000 and st.tiles_active > 0
 
 
+def test_out_of_core_in_set_filter_on_a_host_cloud(tmp_path):
+    """An InSet filter over a HOST-resident cloud, out of core: the survivors are counted once for the whole ingest (on the
+    device copy every band reads), points_processed equals the in-core pipeline's and the oracle's, and every band equals the
+    in-core pipeline's bit for bit (integer-valued floats: the sums are exact in any order)."""
+    og = O.make_grid((0, 0, 64, 48), tile=(16, 16))
+    rng = np.random.default_rng(29)
+    n = 2000
+    x, y = rng.uniform(-1, 65, n), rng.uniform(-1, 49, n)
+    v = rng.integers(0, 16, n).astype(np.float32)
+    cls = rng.integers(0, 5, n).astype(np.float32)
+    reds = [spec(t) for t in ("Sum", "Count", "Average", "Max", "Min")]
+
+    def filtered(**kw):
+        cfg = config_for(og, reds, **kw)
+        f = pcr.FilterSpec()
+        f.add_in_set("cls", [1.0, 3.0])
+        cfg.filter = f
+        return cfg
+
+    incore = pcr.Pipeline.create(filtered())
+    assert incore is not None and not incore.out_of_core()
+    # 4 planes + 5 bands per cell = 2304 B per row, 36 KB per 16-row tile row: a 40 KB budget makes three bands of one tile row.
+    # A parked band is 4 planes x 16 x 64 floats + the flags = 16432 B: the third one exceeds 40 KB and spills the first.
+    ooc = pcr.Pipeline.create(filtered(gpu_memory_budget=40000, host_cache_budget=40000, state_dir=str(tmp_path)))
+    assert ooc is not None, pcr.pipeline_create_error()
+    assert ooc.out_of_core()
+    c = cloud_from(x, y, {"value": v, "cls": cls}, "host")
+    incore.ingest(c)
+    ooc.ingest(c)
+    assert os.listdir(ooc.spill_dir()) != []
+    keep = np.isin(cls, [1.0, 3.0])
+    assert ooc.stats().points_processed == incore.stats().points_processed == int(keep.sum())
+    assert ooc.stats().collections_processed == 1
+    incore.finalize()
+    ooc.finalize()
+    a, b = bands_of(incore), bands_of(ooc)
+    assert len(a) == len(b) == 5
+    for k, (u, w) in enumerate(zip(a, b)):
+        assert np.array_equal(u, w, equal_nan=True), f"band {k}: out of core != in core"
+    assert np.array_equal(b[1], O.run(og, O.COUNT, x[keep], y[keep], v[keep]), equal_nan=True)
+
+
 def test_untouched_bands_stay_nan_and_cost_no_parking(tmp_path):
     """Points in the top tile row only: the other bands are never parked (nothing fell there) and finalize to NaN (Q3)."""
     G = 1024

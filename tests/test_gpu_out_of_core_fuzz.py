@@ -1,4 +1,4 @@
-"""Randomised differential test of the out-of-core pipeline (host/src/pipeline.cpp, Pipeline::Banded; replaces the reference's
+"""Randomised differential test of the out-of-core pipeline (host/src/banded_pipeline.cpp, Pipeline::Banded; replaces the reference's
 TileManager LRU + spill, src/engine/tile_manager.cpp:76-138, 183-375): random grids whose height is not a multiple of the tile,
 random sets of reductions over the three glyphs, a device budget that cuts the grid into one to several tile rows per band, a
 host budget that parks all / some / none of the bands as `.pcrt` files, clouds that reach all or a few bands (or none), an

@@ -309,3 +309,38 @@ def test_ingest_file_streams_chunks_and_ingest_async():
         pipe2.ingest_async(c)
     pipe2.finalize()
     np.testing.assert_array_equal(pipe2.result().band_array(0), O.run(og, O.COUNT, x, y, v))
+
+
+def test_glyph_channel_defaults_and_a_filter_on_the_value_channel():
+    """Line and Gaussian groups whose glyph names one channel the cloud has and one it lacks (the GlyphSpec default applies
+    to that one), in a host-resident cloud, behind a filter on the value channel itself: the channel is staged once and read
+    by the filter and by every scatter.  Against the oracle on the kept points, with the neighbours' tolerances."""
+    og = O.make_grid((0, 0, 64, 48), tile=(16, 16))
+    rng = np.random.default_rng(17)
+    n = 2000
+    x, y = rng.uniform(0, 64, n), rng.uniform(0, 48, n)
+    v = rng.uniform(0, 1, n).astype(np.float32)
+    d = rng.uniform(0, np.pi, n).astype(np.float32)
+    sy = rng.uniform(0.6, 1.8, n).astype(np.float32)
+    ln = pcr.line_splat_spec("value", direction_channel="dir", half_length_channel="hl", default_half_length=3.0, max_radius_cells=8.0)
+    lc = pcr.line_splat_spec("value", direction_channel="dir", half_length_channel="hl", default_half_length=3.0, max_radius_cells=8.0)
+    lc.type = pcr.ReductionType.Count
+    gs = pcr.gaussian_splat_spec("value", sigma_x_channel="sx", sigma_y_channel="sy", default_sigma=1.5, max_radius_cells=5.0)
+    cfg = config_for(og, [ln, lc, gs, spec("Count")])
+    f = pcr.FilterSpec()
+    f.add("value", pcr.CompareOp.Greater, 0.25)
+    cfg.filter = f
+    pipe = pcr.Pipeline.create(cfg)
+    assert pipe is not None, pcr.pipeline_create_error()
+    pipe.ingest(cloud_from(x, y, {"value": v, "dir": d, "sy": sy}, "host"))
+    pipe.finalize()
+    keep = v > np.float32(0.25)
+    assert pipe.stats().points_processed == int(keep.sum())
+    x, y, v, d, sy = x[keep], y[keep], v[keep], d[keep], sy[keep]
+    line = O.make_glyph(O.GLYPH_LINE, half_length=3.0, max_radius=8.0)
+    gauss = O.make_glyph(O.GLYPH_GAUSSIAN, sigma_x=1.5, sigma_y=1.5, max_radius=5.0)
+    want = [O.run(og, O.WEIGHTED_AVERAGE, x, y, v, glyph=line, direction=d), O.run(og, O.COUNT, x, y, v, glyph=line, direction=d),
+            O.run(og, O.WEIGHTED_AVERAGE, x, y, v, glyph=gauss, sigma_y=sy), O.run(og, O.COUNT, x, y, v)]
+    tols = [(1e-4, 1e-6), (0, 0), (1e-4, 1e-5), (0, 0)]
+    for b, (w, (rt, at)) in enumerate(zip(want, tols)):
+        assert_band_close(np.array(pipe.result().band_array(b)), w, rtol=rt, atol=at, what=f"band {b}")
