@@ -510,6 +510,21 @@ int pcr_hip_transform_xy_host(const pcr_hip_crs_desc* src, const pcr_hip_crs_des
 int pcr_hip_downsample2(const float* src, int width, int height, int64_t src_stride, float* const* dst, int levels, int mode,
                         pcr_hip_stream s);
 
+/* ---- no-data cells of one band filled from their neighbours (pcr/core/fill_nodata.h: fill_nodata), out of place.
+ *      A cell of src that is not NaN is copied bit for bit.  For a NaN cell at (r, c) the window offsets are visited in
+ *      row-major order, dr = -radius..radius and inside it dc = -radius..radius; an offset is skipped when
+ *      d2 = dr*dr + dc*dc is 0 or greater than radius*radius, when (r+dr, c+dc) is outside the image, or when the source
+ *      cell there is NaN.  Every other offset contributes with w = 1.0f / (float)d2 (correctly rounded binary32) to two
+ *      binary64 sums that start at +0.0: s += (double)w * (double)v; t += (double)w -- the order of the additions is part
+ *      of the contract.  t == 0: the source NaN, bit for bit.  Otherwise (float)(s / t), a true binary64 division rounded
+ *      to nearest even; a NaN result (Inf + -Inf among the neighbours) is 0x7FC00000; +-Inf and denormals are values.
+ *      Every read is of src: filling never chains, a hole wider than 2 * radius keeps a NaN core.
+ *      src, dst: `height` rows of `width` floats, `src_stride` / `dst_stride` floats apart (any 4-byte alignment; rows of
+ *      both that start on 16 bytes take the 16-byte accesses); they must not overlap.  1 <= radius <= 32.  Argument errors
+ *      are reported before any HIP call.  Enqueued on s; nothing is allocated or synchronised. */
+int pcr_hip_fill_nodata(const float* src, float* dst, int width, int height, int64_t src_stride, int64_t dst_stride, int radius,
+                        pcr_hip_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,11 @@ struct PipelineConfig {
     // right default when finalize() follows a single ingest; pipelines that always ingest several clouds save one wasted band
     // store by switching it off.
     bool finalize_with_first_ingest = true;
+    // 1..32: finalize() fills the NaN cells of the Average, WeightedAverage, Min, Max and MostRecent bands from their valid
+    // neighbours within this many cells (pcr/core/fill_nodata.h); Sum and Count bands stay as they are.  result(), the
+    // written GeoTIFF and its overview levels hold the filled bands; the accumulation state is untouched.  0: nothing is
+    // allocated or launched.  A row-block shard lacks its neighbours' rows and refuses it (fill the gathered grid).
+    int fill_nodata_radius = 0;
 };
 
 struct ProgressInfo {

@@ -4,6 +4,7 @@
 
 #include "buffer.h"
 #include "device_pipeline.h"
+#include "fill_nodata.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -160,6 +161,7 @@ std::unique_ptr<Pipeline> Pipeline::Banded::visit(size_t b, Status* st, bool* wa
     c.finalize_with_first_ingest = false;             // (a band's visit ends with its state parked, never with finalize)
     c.shard_halo_rows = -2;                           // whole tile rows: the band's state window is the band
     c.output_path.clear();
+    c.fill_nodata_radius = 0;                         // (a band lacks its neighbours' rows: finalize() fills the assembled grid)
     c.state_dir.clear();
     c.resume = false;
     c.exec_mode = ExecutionMode::GPU;
@@ -321,6 +323,12 @@ Status Pipeline::Banded::finalize() {
         // the host budget holds during finalize as it does during ingest (it used to end with every band in RAM)
         if (from_disk) drop_host_copy(b);
         else if (!(s = evict()).ok()) return s;
+    }
+    if (cfg.fill_nodata_radius > 0) {                 // the result is assembled here, on the host: so is its fill
+        std::vector<ReductionType> types;
+        for (const auto& r : cfg.reductions) types.push_back(r.type);
+        Status fs = detail::fill_result_host(*result, types, cfg.fill_nodata_radius);
+        if (!fs.ok()) return fs;
     }
     finalized = true;
     if (!cfg.output_path.empty()) return write_geotiff(cfg.output_path, *result, cfg.grid, pipeline_output_options(cfg.write_cog));

@@ -4,6 +4,7 @@
 //   * finalize runs on the device; only finalized bands cross PCIe (or stay in HBM).
 #include "device_pipeline.h"
 
+#include "fill_nodata.h"
 #include "overviews.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
@@ -24,6 +25,7 @@ Pipeline::Impl::~Impl() {
     if (engine) pcr_hip_engine_destroy(engine);
     groups.clear();
     d_bands.clear();
+    d_filled.clear();
     staging.clear();
     result.reset();
     if (own_stream && stream) pcr_hip_stream_destroy(stream);
@@ -192,8 +194,17 @@ Status Pipeline::Impl::init() {
 int Pipeline::Impl::own_plane(ReductionType t) {
     return t == ReductionType::Sum ? 0 : t == ReductionType::Count ? 1 : t == ReductionType::Max ? 2 : t == ReductionType::Min ? 3 : -1;
 }
+// The RAW band of output r: what the finalize kernels and a defining scatter store, and what carries deferred planes.
 float* Pipeline::Impl::band_device(size_t r) {
-    return cfg.result_location == MemoryLocation::Device ? result->band_f32((int)r) : static_cast<float*>(d_bands[r].data());
+    return cfg.result_location == MemoryLocation::Device && !filled(r) ? result->band_f32((int)r) : static_cast<float*>(d_bands[r].data());
+}
+// fill_nodata_radius: the bands of these outputs leave the pipeline filled.  The fill reads the raw band and writes a buffer of
+// its own (filled_band_device), so the raw bands stay what the plane-state rules below take them for; it is no plane-state event.
+bool Pipeline::Impl::filled(size_t r) const { return cfg.fill_nodata_radius > 0 && detail::fills_nodata(outputs[r].type); }
+// The band of output r as it leaves the pipeline: result(), result_band_device(), the GeoTIFF and its overview levels.
+float* Pipeline::Impl::filled_band_device(size_t r) {
+    if (!filled(r)) return band_device(r);
+    return cfg.result_location == MemoryLocation::Device ? result->band_f32((int)r) : static_cast<float*>(d_filled[r].data());
 }
 Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
     return detail::hip_status(pcr_hip_engine_tile_touched(engine, d, tx, ty));
@@ -414,7 +425,7 @@ Status Pipeline::Impl::merge_touched(const void* d_union) {
 
 const float* Pipeline::Impl::result_band_device(int band) {
     if (!finalized || !result || band < 0 || band >= (int)outputs.size()) return nullptr;
-    return band_device((size_t)band);
+    return filled_band_device((size_t)band);
 }
 
 Status Pipeline::Impl::synchronize() { return detail::hip_status(pcr_hip_stream_synchronize(stream)); }
@@ -756,6 +767,16 @@ Status Pipeline::Impl::allocate_result() {
             if (!s.ok()) return s;
         }
     }
+    // fill_nodata_radius: a filled output has a raw band and a filled one.  Host result: the filled one is a further device
+    // buffer, which the copy to the host reads.  Device result: the result grid's band is the filled one, the raw band lives
+    // in d_bands.  (radius 0: no output is filled, nothing is allocated)
+    for (size_t r = 0; r < outputs.size(); ++r) {
+        if (!filled(r)) continue;
+        std::vector<detail::Buffer>& extra = on_device ? d_bands : d_filled;
+        if (extra.size() < outputs.size()) extra.resize(outputs.size());
+        Status s = extra[r].allocate((size_t)rows * W * sizeof(float), MemoryLocation::Device);
+        if (!s.ok()) return s;
+    }
     return Status::success();
 }
 
@@ -827,10 +848,16 @@ Status Pipeline::Impl::finalize(bool wait) {
             if (types.size() == PCR_HIP_MAX_FINALIZE_OUTPUTS && !(s = flush()).ok()) return s;
         }
         if (!(s = flush()).ok()) return s;
-        if (!on_device) {
-            for (size_t r : bands_of) {
+        for (size_t r : bands_of) {
+            if (filled(r)) {                 // behind the band's finalize kernel (or the scatter that stored it), raw band -> filled band
                 enqueued = true;
-                s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)r), d_bands[r].data(),
+                s = detail::hip_status(pcr_hip_fill_nodata(band_device(r), filled_band_device(r), W, rows, W, W,
+                                                           cfg.fill_nodata_radius, stream));
+                if (!s.ok()) return s;
+            }
+            if (!on_device) {
+                enqueued = true;
+                s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)r), filled_band_device(r),
                                                           (size_t)rows * W * sizeof(float), stream));
                 if (!s.ok()) return s;
             }
@@ -846,7 +873,7 @@ Status Pipeline::Impl::finalize(bool wait) {
             std::vector<const float*> dev_bands;
             std::vector<BandDesc> descs;
             for (size_t r = 0; r < outputs.size(); ++r) {
-                dev_bands.push_back(band_device(r));
+                dev_bands.push_back(filled_band_device(r));
                 descs.push_back(result->band_desc((int)r));
             }
             std::vector<std::unique_ptr<Grid>> d_levels;

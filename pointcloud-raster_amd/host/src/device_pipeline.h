@@ -72,7 +72,9 @@ struct Pipeline::Impl {
     bool own_stream = false;
     std::vector<Group> groups;
     std::vector<Output> outputs;
-    std::vector<detail::Buffer> d_bands;     // finalized bands on the device (result_location == Host)
+    std::vector<detail::Buffer> d_bands;     // finalized bands on the device (result_location == Host; Device: the raw bands
+                                             // of the outputs fill_nodata_radius fills, whose filled band is the result grid's)
+    std::vector<detail::Buffer> d_filled;    // result_location == Host: the filled bands of those outputs
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
                                              // both sides): the blocking finalize reads it after its synchronise and launches
@@ -132,6 +134,8 @@ struct Pipeline::Impl {
     int own_rows() const { return hg.own_row1 - hg.own_row0; }
     static int own_plane(ReductionType t);
     float* band_device(size_t r);
+    bool filled(size_t r) const;
+    float* filled_band_device(size_t r);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
     bool offer_bands(size_t gi);
     Status unpack_select(Group& gr);

@@ -1,6 +1,7 @@
 // host_pipeline.cpp -- see host_pipeline.h.
 #include "host_pipeline.h"
 
+#include "fill_nodata.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -188,6 +189,12 @@ Status Pipeline::Host::finalize() {
     }
     for (size_t r = 0; r < outputs.size(); ++r)
         engine->finalize(groups[(size_t)outputs[r].group].planes, outputs[r].type, result->band_f32((int)r));
+    if (cfg.fill_nodata_radius > 0) {                                // (the planes are the state: the bands are made anew by every finalize)
+        std::vector<ReductionType> types;
+        for (const auto& o : outputs) types.push_back(o.type);
+        Status fs = detail::fill_result_host(*result, types, cfg.fill_nodata_radius);
+        if (!fs.ok()) return fs;
+    }
     finalized = true;
     if (!cfg.output_path.empty()) return write_geotiff(cfg.output_path, *result, g, pipeline_output_options(cfg.write_cog));    // pipeline.cpp:1351-1361
     return Status::success();

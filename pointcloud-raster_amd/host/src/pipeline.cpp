@@ -43,6 +43,11 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         std::fprintf(stderr, "Error: %s\n", s.message.c_str());    // loud: there is no fallback path
         return std::unique_ptr<Pipeline>();
     };
+    if (config.fill_nodata_radius < 0 || config.fill_nodata_radius > 32)
+        return fail_with(Status::error(StatusCode::InvalidArgument, "pipeline: fill_nodata_radius must be between 0 and 32"));
+    if (config.fill_nodata_radius > 0 && (config.shard_row_begin >= 0 || config.shard_row_end >= 0))
+        return fail_with(Status::error(StatusCode::InvalidArgument,
+            "pipeline: fill_nodata_radius needs the whole grid; fill the gathered grid with fill_nodata"));
     size_t budget = 0;
     if (Banded::needed(config, &budget)) {
         Status bs = Status::success();

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "buffer.h"
+#include "fill_nodata.h"
 #include "pcr/core/grid.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/core/reproject.h"
@@ -56,6 +57,13 @@ std::unique_ptr<ShardedPipeline> ShardedPipeline::create(PipelineConfig cfg, con
     sp->output_path_ = cfg.output_path;
     sp->write_cog_ = cfg.write_cog;
     cfg.output_path.clear();
+    // a row block lacks its neighbours' finished rows: rank 0 fills the gathered grid before it writes it
+    if (cfg.fill_nodata_radius < 0 || cfg.fill_nodata_radius > 32) {
+        g_create_error = "ShardedPipeline: pipeline: fill_nodata_radius must be between 0 and 32";
+        return nullptr;
+    }
+    sp->fill_nodata_radius_ = cfg.fill_nodata_radius;
+    cfg.fill_nodata_radius = 0;
     sp->state_dir_ = cfg.state_dir;
     sp->reductions_ = cfg.reductions;
     sp->target_crs_ = cfg.target_crs;
@@ -154,6 +162,11 @@ Status ShardedPipeline::finalize() {
     std::unique_ptr<Grid> whole;
     if (!(s = gather(0, &whole)).ok()) return s;
     if (rank_ != 0) return s;
+    if (fill_nodata_radius_ > 0) {
+        std::vector<ReductionType> types;
+        for (const auto& r : reductions_) types.push_back(r.type);
+        if (!(s = detail::fill_result_host(*whole, types, fill_nodata_radius_)).ok()) return s;
+    }
     return write_geotiff(output_path_, *whole, grid_, pipeline_output_options(write_cog_));
 }
 

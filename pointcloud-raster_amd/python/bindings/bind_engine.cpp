@@ -102,7 +102,8 @@ void bind_engine(py::module_& m) {
         .def_readwrite("shard_row_end", &PipelineConfig::shard_row_end)
         .def_readwrite("shard_halo_rows", &PipelineConfig::shard_halo_rows)
         .def_readwrite("scatter_path", &PipelineConfig::scatter_path)
-        .def_readwrite("finalize_with_first_ingest", &PipelineConfig::finalize_with_first_ingest);
+        .def_readwrite("finalize_with_first_ingest", &PipelineConfig::finalize_with_first_ingest)
+        .def_readwrite("fill_nodata_radius", &PipelineConfig::fill_nodata_radius);
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
         .def(py::init<>())

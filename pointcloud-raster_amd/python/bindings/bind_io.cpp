@@ -3,6 +3,7 @@
 // LAS/LAZ raise NotImplemented as upstream.
 #include "common.h"
 
+#include "pcr/core/fill_nodata.h"
 #include "pcr/core/grid.h"
 #include "pcr/core/grid_config.h"
 #include "pcr/core/point_cloud.h"
@@ -110,6 +111,15 @@ void bind_io(py::module_& m) {
         raise_if_error(s);
         return out;
     }, py::arg("grid"), py::arg("levels") = -1, py::arg("resampling") = "average");
+    // extension: the NaN cells of a grid's bands filled from their valid neighbours, where the grid lives (a Device grid: in HBM)
+    m.def("fill_nodata", [](const Grid& grid, int radius, py::object bands) {
+        std::vector<int> list;                              // None: every band
+        if (!bands.is_none()) list = bands.cast<std::vector<int>>();
+        Status s;
+        auto out = fill_nodata(grid, radius, list, &s, nullptr);
+        raise_if_error(s);
+        return out;
+    }, py::arg("grid"), py::arg("radius"), py::arg("bands") = py::none());
     m.def("read_geotiff_overviews", [](const std::string& path) {
         std::vector<std::pair<int, int>> sizes;
         raise_if_error(read_geotiff_overviews(path, sizes));

@@ -72,7 +72,7 @@ from ._pcr import (  # noqa: E402,F401
     read_tile_state, tile_state_filename, write_tile_state,
     read_geotiff_band, read_geotiff_band_names, TiledGeoTiffWriter,
     crs_epsg, reproject,
-    build_overviews, read_geotiff_overviews,
+    build_overviews, read_geotiff_overviews, fill_nodata,
 )
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
@@ -170,5 +170,5 @@ __all__ = [
     "read_tile_state", "write_tile_state", "tile_state_filename",
     "read_geotiff_band", "read_geotiff_band_names", "TiledGeoTiffWriter",
     "crs_epsg", "transform_xy", "reproject",
-    "build_overviews", "read_geotiff_overviews",
+    "build_overviews", "read_geotiff_overviews", "fill_nodata",
 ]

@@ -168,6 +168,7 @@ SYMBOLS = {
     "pcr_hip_transform_xy": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64, _VP],
     "pcr_hip_transform_xy_host": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64],
     "pcr_hip_downsample2": [_VP, C.c_int, C.c_int, _I64, C.POINTER(_VP), C.c_int, C.c_int, _VP],
+    "pcr_hip_fill_nodata": [_VP, _VP, C.c_int, C.c_int, _I64, _I64, C.c_int, _VP],
 }
 
 _lib = None

@@ -324,6 +324,10 @@ class ShardedPipeline:
         # src/engine/pipeline.cpp:1351-1361) -- not a strip per rank under the same name
         self.output_path, cfg.output_path = cfg.output_path, ""
         self.write_cog = cfg.write_cog
+        # a row block lacks its neighbours' finished rows: rank 0 fills the gathered grid before it writes it
+        if not 0 <= cfg.fill_nodata_radius <= 32:
+            raise ValueError("pipeline: fill_nodata_radius must be between 0 and 32")
+        self.fill_nodata_radius, cfg.fill_nodata_radius = cfg.fill_nodata_radius, 0
         self._state_dir = cfg.state_dir
         self._rtypes = [r.type for r in cfg.reductions]
         if device_id is not None:
@@ -604,6 +608,12 @@ class ShardedPipeline:
             import pcr
             whole = self.gather(0)
             if self.rank == 0:
+                if self.fill_nodata_radius > 0:
+                    filled = [b for b, t in enumerate(self._rtypes) if t in (
+                        pcr.ReductionType.Average, pcr.ReductionType.WeightedAverage, pcr.ReductionType.Min,
+                        pcr.ReductionType.Max, pcr.ReductionType.MostRecent)]
+                    if filled:
+                        whole = pcr.fill_nodata(whole, self.fill_nodata_radius, filled)
                 opts = pcr.GeoTiffOptions()
                 if self.write_cog:
                     opts.overviews = -1
