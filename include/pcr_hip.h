@@ -37,7 +37,8 @@ extern "C" {
                                  *   + PCR_HIP_MOST_RECENT: select_pack / select_unpack / select_merge / scatter_select / finalize_select,
                                  *     state_floats / state_init / state_merge accept type 8;
                                  *   + engine_defer_planes / engine_planes_deferred / planes_from_bands_if; scatter_stats.reserved_ is now
-                                 *     deferred_planes (same place, 0 unless the hint was sent) */
+                                 *     deferred_planes (same place, 0 unless the hint was sent);
+                                 *   + las_decode / las_decode_host (LAS point records -> SoA cloud) */
 
 typedef enum pcr_hip_status {
     PCR_HIP_OK = 0,
@@ -524,6 +525,42 @@ int pcr_hip_downsample2(const float* src, int width, int height, int64_t src_str
  *      are reported before any HIP call.  Enqueued on s; nothing is allocated or synchronised. */
 int pcr_hip_fill_nodata(const float* src, float* dst, int width, int height, int64_t src_stride, int64_t dst_stride, int radius,
                         pcr_hip_stream s);
+
+/* ---- LAS point records -> the SoA cloud (pcr/io/point_cloud_io.h: LAS input).  No reference counterpart: the reference
+ *      declares the format and reads `.las` tiles through laspy in a script.  ASPRS LAS 1.0-1.4, point data record formats
+ *      0-10, little-endian, array-of-structures: int32 X, Y, Z, then packed attributes (csrc/las_decode.hpp holds the table).
+ *      The raw records cross PCIe (a format-1 record is 28 B, no larger than the cloud it becomes) and are unpacked in HBM.
+ *        x = (double)X * scale[0] + offset[0], likewise y: one multiply, one add, each rounded (never an fma)
+ *        channels are Float32; z = (float)((double)Z * scale[2] + offset[2]); gps_time = (float)(t - gps_time_origin), the
+ *        subtraction in Float64 (Float32 resolves 32 s at 3e8 s); scan_angle in degrees; withheld / overlap 0 or 1
+ *      record_length >= the format's minimum (20, 28, 26, 34, 57, 63, 30, 36, 38, 59, 67); the excess (extra bytes, and the
+ *      wave packets of formats 4, 5, 9, 10) is skipped.
+ *      channels: a HOST array of PCR_HIP_LAS_CH_COUNT output pointers, indexed by PCR_HIP_LAS_CH_*; NULL = not wanted (costs
+ *      neither the field's extraction nor a store); the array itself may be NULL (x and y alone).
+ *      d_records: 16-byte aligned, inside an allocation of at least n * record_length + 16 bytes (the kernel stages a
+ *      workgroup's run of records into LDS with aligned 16-byte loads; the last one may reach into the slack, never past it).
+ *      A workgroup of 256 lanes owns 256 * PCR_HIP_LAS_RECORDS_PER_LANE consecutive records.  Argument errors (null layout,
+ *      format above 10, record_length below the minimum or above 65535, a wanted channel the format lacks, null x / y or
+ *      records with n > 0, misaligned records) are reported before any HIP call; n == 0 launches nothing.
+ *      _host: the same decoder on host arrays (any alignment, no slack), over `threads` threads (< 1: one). */
+typedef struct pcr_hip_las_layout {
+    int32_t point_format;
+    int32_t record_length;
+    double scale[3];
+    double offset[3];
+    double gps_time_origin;
+} pcr_hip_las_layout;
+enum {
+    PCR_HIP_LAS_CH_Z = 0, PCR_HIP_LAS_CH_INTENSITY = 1, PCR_HIP_LAS_CH_RETURN_NUMBER = 2, PCR_HIP_LAS_CH_NUMBER_OF_RETURNS = 3,
+    PCR_HIP_LAS_CH_CLASSIFICATION = 4, PCR_HIP_LAS_CH_WITHHELD = 5, PCR_HIP_LAS_CH_OVERLAP = 6, PCR_HIP_LAS_CH_SCAN_ANGLE = 7,
+    PCR_HIP_LAS_CH_USER_DATA = 8, PCR_HIP_LAS_CH_POINT_SOURCE_ID = 9, PCR_HIP_LAS_CH_GPS_TIME = 10, PCR_HIP_LAS_CH_RED = 11,
+    PCR_HIP_LAS_CH_GREEN = 12, PCR_HIP_LAS_CH_BLUE = 13, PCR_HIP_LAS_CH_NIR = 14, PCR_HIP_LAS_CH_COUNT = 15
+};
+#define PCR_HIP_LAS_RECORDS_PER_LANE 4
+int pcr_hip_las_decode(const pcr_hip_las_layout* layout, const uint8_t* d_records, uint64_t n, double* d_x, double* d_y,
+                       float* const* channels, pcr_hip_stream s);
+int pcr_hip_las_decode_host(const pcr_hip_las_layout* layout, const uint8_t* h_records, uint64_t n, double* h_x, double* h_y,
+                            float* const* channels, int threads);
 
 #ifdef __cplusplus
 }

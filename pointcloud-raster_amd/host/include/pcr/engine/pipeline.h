@@ -22,6 +22,7 @@ namespace pcr {
 
 class PointCloud;
 class Grid;
+struct LasOptions;
 
 struct ReductionSpec {
     std::string value_channel;
@@ -95,6 +96,9 @@ struct PipelineConfig {
     // written GeoTIFF and its overview levels hold the filled bands; the accumulation state is untouched.  0: nothing is
     // allocated or launched.  A row-block shard lacks its neighbours' rows and refuses it (fill the gathered grid).
     int fill_nodata_radius = 0;
+    // ingest_file of a LAS file: subtracted from the GPS time, in Float64, before it becomes the Float32 `gps_time` channel
+    // (LasOptions::gps_time_origin; a MostRecent timestamp needs it: Float32 resolves 32 s at 3e8 s).
+    double las_gps_time_origin = 0.0;
 };
 
 struct ProgressInfo {
@@ -119,8 +123,10 @@ public:
     /// page-locked (HostPinned) or device-resident; the cloud must stay untouched until synchronize() /
     /// finalize().  Pageable host clouds behave as in ingest.
     Status ingest_async(const PointCloud& cloud);
-    /// Extension: streams a PCRP / CSV file through two page-locked chunk buffers -- the file read of chunk
+    /// Extension: streams a PCRP / CSV / LAS file through two page-locked chunk buffers -- the file read of chunk
     /// k+1 overlaps the host-to-device copy and the kernels of chunk k.  `points_read` (optional) = rows read.
+    /// LAS: only the channels the configuration names (reductions, glyphs, filter) are decoded -- one the file's point
+    /// format lacks is InvalidArgument; on the HIP engine the raw records cross PCIe and are unpacked in HBM.
     Status ingest_file(const std::string& path, size_t chunk_points = 4u << 20, size_t* points_read = nullptr);
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
@@ -197,6 +203,7 @@ public:
 
 private:
     Pipeline() = default;
+    Status ingest_las_records(const std::string& path, const LasOptions& options, size_t chunk_points, size_t* points_read);
     struct Impl;
     struct Banded;                       // out-of-core driver: row bands of whole reference-tile rows, one in HBM at a time
     struct Host;                         // the pipeline on the host engine (host/src/host_pipeline.h)

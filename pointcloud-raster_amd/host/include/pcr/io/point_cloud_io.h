@@ -7,7 +7,16 @@
 //     { u16 name_len | char name[name_len] | u8 dtype (DataType) } x num_channels
 //   body, SoA:  f64 x[num_points] | f64 y[num_points] | <dtype> channel[num_points] x num_channels
 // CSV: header row "x,y,<channel>,...", values printed with 15 significant digits; every extra
-// column is read back as Float64 (point_cloud_io.cpp:286-461).  LAS/LAZ: NotImplemented, as upstream.
+// column is read back as Float64 (point_cloud_io.cpp:286-461).
+//
+// LAS input (not in the reference, which declares the format and leaves it NotImplemented): ASPRS LAS 1.0-1.4, point data
+// record formats 0-10, little-endian.  x, y are Float64 ((double)X * scale + offset, one multiply and one add); every
+// attribute the format has becomes a Float32 channel under laspy's name -- z, intensity, return_number, number_of_returns,
+// classification, withheld, overlap, scan_angle (degrees), user_data, point_source_id, gps_time, red, green, blue, nir
+// (include/pcr_hip.h: pcr_hip_las_decode holds the table).  Extra bytes and wave packets are skipped; the CRS comes from the
+// OGC WKT record or the GeoKeyDirectory.  A file that starts with "LASF" is LAS whatever its extension.  A Device read ships
+// the raw records over PCIe and unpacks them in HBM; Host reads run the same decoder on the CPU.  Writing LAS, and LAZ
+// (compressed records) in either direction: NotImplemented, as upstream.
 //
 // Extensions (MI355X build): read_point_cloud can deliver the cloud in page-locked host memory or
 // straight in HBM (`location`), and the streaming reader returns the right rows for every chunk --
@@ -30,7 +39,16 @@ struct PointCloudInfo {
     size_t num_points = 0;
     std::vector<ChannelDesc> channels;
     CRS crs;
-    BBox bounds;                      // empty: neither format stores it
+    BBox bounds;                      // LAS: the header's min / max x, y; empty for PCRP and CSV, which do not store it
+};
+
+/// What a LAS read delivers.  channels: names from the list above, empty = every channel the file's point format has; an
+/// unknown name or one the format lacks is InvalidArgument.  gps_time_origin is subtracted from the GPS time in Float64
+/// before it is narrowed to the Float32 channel (GPS times are ~3e8 s, where Float32 resolves 32 s; over a flight of 1e4 s
+/// it resolves 1 ms).
+struct LasOptions {
+    std::vector<std::string> channels;
+    double gps_time_origin = 0.0;
 };
 
 /// Whole file -> PointCloud (nullptr on any failure, as upstream).  `location`: Host (default),
@@ -38,6 +56,10 @@ struct PointCloudInfo {
 std::unique_ptr<PointCloud> read_point_cloud(const std::string& path,
                                              PointCloudFormat format = PointCloudFormat::Auto,
                                              MemoryLocation location = MemoryLocation::Host);
+
+/// A LAS file with options; `status` (optional) says why nullptr was returned.
+std::unique_ptr<PointCloud> read_las(const std::string& path, const LasOptions& options = LasOptions(),
+                                     MemoryLocation location = MemoryLocation::Host, Status* status = nullptr);
 
 Status read_point_cloud_info(const std::string& path, PointCloudInfo& info,
                              PointCloudFormat format = PointCloudFormat::Auto);
@@ -50,8 +72,10 @@ class PointCloudReader {
 public:
     ~PointCloudReader();
     static std::unique_ptr<PointCloudReader> open(const std::string& path,
-                                                  PointCloudFormat format = PointCloudFormat::Auto);
+                                                  PointCloudFormat format = PointCloudFormat::Auto,
+                                                  const LasOptions* las = nullptr, Status* status = nullptr);
     const PointCloudInfo& info() const;
+    PointCloudFormat format() const;             // what the file turned out to be (never Auto)
     /// Next chunk of up to `max_points` into `cloud` (host-resident, capacity >= max_points; channels
     /// are added on first use).  Returns the number of points read, 0 at end of file.
     size_t read_chunk(PointCloud& cloud, size_t max_points);

@@ -15,6 +15,7 @@
 #include "banded_pipeline.h"
 #include "device_pipeline.h"
 #include "host_pipeline.h"
+#include "las_io.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/point_cloud_io.h"
 
@@ -27,6 +28,35 @@ namespace pcr {
 namespace {
 
 thread_local std::string g_create_error;
+
+// Every channel a configuration reads from its clouds: the reductions' value, weight, timestamp and glyph channels and the
+// filter's -- what a LAS file is decoded into (a Pipeline never looks at any other).
+std::vector<std::string> named_channels(const PipelineConfig& c) {
+    std::vector<std::string> out;
+    auto add = [&out](const std::string& name) {
+        if (!name.empty() && std::find(out.begin(), out.end(), name) == out.end()) out.push_back(name);
+    };
+    for (const auto& r : c.reductions) {
+        add(r.value_channel);
+        add(r.weight_channel);
+        add(r.timestamp_channel);
+        add(r.glyph.direction_channel);
+        add(r.glyph.half_length_channel);
+        add(r.glyph.sigma_x_channel);
+        add(r.glyph.sigma_y_channel);
+        add(r.glyph.rotation_channel);
+    }
+    for (const auto& p : c.filter.predicates) add(p.channel_name);
+    return out;
+}
+
+struct LasFd {
+    int fd;
+    explicit LasFd(const std::string& path) : fd(::open(path.c_str(), O_RDONLY)) {}
+    ~LasFd() { if (fd >= 0) ::close(fd); }
+    LasFd(const LasFd&) = delete;
+    LasFd& operator=(const LasFd&) = delete;
+};
 
 }  // namespace
 
@@ -109,8 +139,21 @@ Status Pipeline::ingest_async(const PointCloud& cloud) {
 Status Pipeline::ingest_file(const std::string& path, size_t chunk_points, size_t* points_read) {
     if (points_read) *points_read = 0;
     if (chunk_points == 0) return Status::error(StatusCode::InvalidArgument, "pipeline: chunk_points must be positive");
-    auto reader = PointCloudReader::open(path);
-    if (!reader) return Status::error(StatusCode::IoError, "pipeline: failed to open point cloud file: " + path);
+    const PipelineConfig& cfg = host_ ? host_->cfg : banded_ ? banded_->cfg : impl_->cfg;
+    LasOptions las;                                          // (only a LAS file looks at it)
+    las.channels = named_channels(cfg);
+    las.gps_time_origin = cfg.las_gps_time_origin;
+    Status opened;
+    auto reader = PointCloudReader::open(path, PointCloudFormat::Auto, &las, &opened);
+    if (!reader)
+        return Status::error(opened.ok() ? StatusCode::IoError : opened.code,
+                             "pipeline: failed to open point cloud file: " + path + (opened.message.empty() ? "" : ": " + opened.message));
+    // The plain HIP engine takes a LAS file as raw records (the host engine and the out-of-core driver read it through the
+    // reader and the host decoder, below)
+    if (impl_ && reader->format() == PointCloudFormat::LAS) {
+        reader.reset();
+        return ingest_las_records(path, las, chunk_points, points_read);
+    }
     chunk_points = std::min(chunk_points, std::max<size_t>(reader->info().num_points, 1));
     const MemoryLocation where = host_ ? MemoryLocation::Host : MemoryLocation::HostPinned;    // (no device: no page-locking either)
     std::unique_ptr<PointCloud> buf[2] = {PointCloud::create(chunk_points, where), PointCloud::create(chunk_points, where)};
@@ -129,6 +172,67 @@ Status Pipeline::ingest_file(const std::string& path, size_t chunk_points, size_
     }
     if (points_read) *points_read = total;
     return Status::success();
+}
+// A LAS file on the HIP engine.  The loop of ingest_file with other buffers: two page-locked buffers of raw records, two
+// device record buffers and two Device clouds that hold only the wanted channels.  Per chunk: one read, one asynchronous
+// host-to-device copy, the decode kernel, then the ingest of the Device cloud -- all on the pipeline's stream, so the decode
+// is ordered before the scatter that reads its output and after the previous scatter that read the same cloud (and nothing
+// of chunk k is reused before the synchronize() that follows the read of chunk k + 1).  A format-1 record is 28 bytes: no
+// more crosses PCIe than the decoded x, y and three channels would.
+Status Pipeline::ingest_las_records(const std::string& path, const LasOptions& options, size_t chunk_points, size_t* points_read) {
+    LasFd file(path);
+    las::Header h;
+    unsigned want = 0;
+    Status s = las::read_header(file.fd, path, &h);
+    if (s.ok()) s = las::wanted_mask(h, options.channels, &want);
+    if (!s.ok()) return s;
+    const pcr_hip_las_layout layout = h.layout(options.gps_time_origin);
+    const size_t n = (size_t)h.num_points, len = h.record_length;
+    if (n == 0) return Status::success();
+    chunk_points = std::min(chunk_points, n);
+    Impl::DeviceScope dev(impl_->cfg.cuda_device_id);
+    detail::Buffer pinned[2], d_records[2];
+    std::unique_ptr<PointCloud> cloud[2];
+    float* out[2][PCR_HIP_LAS_CH_COUNT] = {};
+    for (int b = 0; b < 2; ++b) {
+        // + 16: the decode kernel stages with aligned 16-byte loads, the last of which may reach past the last record
+        if (!(s = pinned[b].allocate(chunk_points * len + 16, MemoryLocation::HostPinned)).ok()) return s;
+        if (!(s = d_records[b].allocate(chunk_points * len + 16, MemoryLocation::Device)).ok()) return s;
+        cloud[b] = PointCloud::create(chunk_points, MemoryLocation::Device);
+        if (!cloud[b]) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate device chunk clouds");
+        cloud[b]->set_crs(h.crs);                            // the file's CRS: ingest reprojects the chunks when it differs from the grid's
+        for (int c = 0; c < PCR_HIP_LAS_CH_COUNT; ++c) {
+            if (!(want & (1u << c))) continue;
+            if (!(s = cloud[b]->add_channel(las::kChannelNames[c], DataType::Float32)).ok()) return s;
+            out[b][c] = cloud[b]->channel_f32(las::kChannelNames[c]);
+        }
+    }
+    auto read_chunk = [&](int b, size_t first) -> size_t {  // records [first, ...) -> pinned[b]; 0 at the end or on a failed read
+        if (first >= n) return 0;
+        const size_t count = std::min(chunk_points, n - first);
+        if (!las::read_bytes(file.fd, pinned[b].data(), count * len, h.data_offset + (uint64_t)first * len)) {
+            s = Status::error(StatusCode::IoError, "pipeline: failed to read the point records of " + path);
+            return 0;
+        }
+        return count;
+    };
+    size_t total = 0;
+    int cur = 0;
+    size_t got = read_chunk(cur, 0);
+    while (got > 0) {
+        Status e = cloud[cur]->resize(got);
+        if (e.ok()) e = detail::hip_status(pcr_hip_memcpy_h2d(d_records[cur].data(), pinned[cur].data(), got * len, impl_->stream));
+        if (e.ok()) e = detail::hip_status(pcr_hip_las_decode(&layout, static_cast<const uint8_t*>(d_records[cur].data()), got,
+                                                              cloud[cur]->x(), cloud[cur]->y(), out[cur], impl_->stream));
+        if (e.ok()) e = ingest_async(*cloud[cur]);           // kernels of this chunk, enqueued
+        if (!e.ok()) { (void)synchronize(); return e; }
+        total += got;
+        got = read_chunk(cur ^ 1, total);                    // overlaps with them
+        if (!(e = synchronize()).ok()) return e;             // the buffers of `cur` are free again
+        cur ^= 1;
+    }
+    if (points_read) *points_read = total;
+    return s;
 }
 Status Pipeline::finalize() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(); }
 Status Pipeline::finalize_async() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(false); }

@@ -1,8 +1,12 @@
-// point_cloud_io.cpp -- PCRP / CSV point-cloud files (see pcr/io/point_cloud_io.h).
+// point_cloud_io.cpp -- PCRP / CSV / LAS point-cloud files (see pcr/io/point_cloud_io.h).
 // Behaviour follows the reference's src/io/point_cloud_io.cpp (format detection :26-48, PCRP
 // :75-283, CSV :291-461, dispatch :484-556, streaming reader :563-763); deliberate differences are
-// listed in the header.
+// listed in the header.  LAS input has no upstream counterpart: las_io.h reads the header block, pcr_hip_las_decode[_host]
+// the records.
 #include "pcr/io/point_cloud_io.h"
+
+#include "buffer.h"
+#include "las_io.h"
 
 #include <algorithm>
 #include <atomic>
@@ -22,23 +26,34 @@ namespace pcr {
 namespace {
 
 constexpr uint32_t kMagicPcrp = 0x50524350u;   // "PCRP"
+constexpr uint32_t kMagicLasf = 0x4653414Cu;   // "LASF"
 constexpr uint32_t kVersion = 1;
 
 bool ends_with(const std::string& s, const std::string& suffix) {
     return s.size() >= suffix.size() && s.compare(s.size() - suffix.size(), suffix.size(), suffix) == 0;
 }
 
-// extension first (case-insensitive), then the magic number, then CSV
-PointCloudFormat detect_format(const std::string& path) {
+std::string lower_case(const std::string& path) {
     std::string lower = path;
     std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+    return lower;
+}
+
+// a file that starts with "LASF" is LAS whatever it is called (a `.laz` name stays LAZ); then the extension
+// (case-insensitive), then the PCRP magic number, then CSV
+PointCloudFormat detect_format(const std::string& path) {
+    const std::string lower = lower_case(path);
+    if (ends_with(lower, ".laz")) return PointCloudFormat::LAZ;
+    uint32_t magic = 0;
+    {
+        std::ifstream f(path, std::ios::binary);
+        if (!f || !f.read(reinterpret_cast<char*>(&magic), 4)) magic = 0;
+    }
+    if (magic == kMagicLasf) return PointCloudFormat::LAS;
     if (ends_with(lower, ".pcrp")) return PointCloudFormat::PCR_Binary;
     if (ends_with(lower, ".csv")) return PointCloudFormat::CSV;
     if (ends_with(lower, ".las")) return PointCloudFormat::LAS;
-    if (ends_with(lower, ".laz")) return PointCloudFormat::LAZ;
-    std::ifstream f(path, std::ios::binary);
-    uint32_t magic = 0;
-    if (f && f.read(reinterpret_cast<char*>(&magic), 4) && magic == kMagicPcrp) return PointCloudFormat::PCR_Binary;
+    if (magic == kMagicPcrp) return PointCloudFormat::PCR_Binary;
     return PointCloudFormat::CSV;
 }
 
@@ -360,7 +375,112 @@ std::unique_ptr<PointCloud> read_csv(const std::string& path, MemoryLocation loc
     return cloud;
 }
 
-const char* kLasMessage = "LAS/LAZ format support not yet implemented";
+const char* kLasMessage = "LAS/LAZ format support not yet implemented";     // writing LAS; LAZ either way
+
+// ---- LAS ---------------------------------------------------------------------------------------
+struct LasFile {
+    std::unique_ptr<Fd> file;
+    las::Header header;
+    unsigned want = 0;                           // PCR_HIP_LAS_CH_* bits delivered
+    pcr_hip_las_layout layout{};
+};
+
+Status open_las(const std::string& path, const LasOptions& options, LasFile* out) {
+    if (ends_with(lower_case(path), ".laz")) return Status::error(StatusCode::NotImplemented, las::kLazMessage);
+    out->file = std::make_unique<Fd>(path);
+    if (out->file->fd < 0)
+        return Status::error(StatusCode::IoError, "failed to open LAS file: " + path + " (note: LAZ support not yet implemented)");
+    Status s = las::read_header(out->file->fd, path, &out->header);
+    if (s.ok()) s = las::wanted_mask(out->header, options.channels, &out->want);
+    out->layout = out->header.layout(options.gps_time_origin);
+    return s;
+}
+
+void las_info(const LasFile& f, PointCloudInfo& info) {
+    info.num_points = (size_t)f.header.num_points;
+    info.channels.clear();
+    for (int c = 0; c < PCR_HIP_LAS_CH_COUNT; ++c) {
+        if (!(f.want & (1u << c))) continue;
+        ChannelDesc d;
+        d.name = las::kChannelNames[c];
+        d.dtype = DataType::Float32;
+        info.channels.push_back(d);
+    }
+    info.crs = f.header.crs;
+    info.bounds = f.header.bounds;
+}
+
+// The cloud's arrays for the wanted channels (added on first use), `at` elements in.
+Status las_outputs(const LasFile& f, PointCloud& cloud, size_t at, float** out) {
+    for (int c = 0; c < PCR_HIP_LAS_CH_COUNT; ++c) {
+        out[c] = nullptr;
+        if (!(f.want & (1u << c))) continue;
+        const std::string name = las::kChannelNames[c];
+        if (!cloud.has_channel(name)) {
+            Status s = cloud.add_channel(name, DataType::Float32);
+            if (!s.ok()) return s;
+        }
+        const ChannelDesc* d = cloud.channel(name);
+        if (!d || d->dtype != DataType::Float32 || !cloud.channel_f32(name))
+            return Status::error(StatusCode::InvalidArgument, "LAS: channel '" + name + "' of the cloud is not Float32");
+        out[c] = cloud.channel_f32(name) + at;
+    }
+    return Status::success();
+}
+
+int las_host_threads() { return (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency())); }
+
+// records [first, first + count) -> elements [at, at + count) of a host-resident cloud, through `raw` (grown as needed)
+Status las_rows_to_host(const LasFile& f, size_t first, size_t count, PointCloud& cloud, size_t at, std::vector<uint8_t>& raw) {
+    float* out[PCR_HIP_LAS_CH_COUNT];
+    Status s = las_outputs(f, cloud, at, out);
+    if (!s.ok() || count == 0) return s;
+    const size_t len = f.header.record_length;
+    if (raw.size() < count * len) raw.resize(count * len);
+    if (!read_segments(f.file->fd, {{reinterpret_cast<char*>(raw.data()), f.header.data_offset + (uint64_t)first * len, count * len}}))
+        return Status::error(StatusCode::IoError, "LAS: failed to read point records");
+    return detail::hip_status(pcr_hip_las_decode_host(&f.layout, raw.data(), count, cloud.x() + at, cloud.y() + at, out, las_host_threads()));
+}
+
+std::unique_ptr<PointCloud> read_las_file(const std::string& path, const LasOptions& options, MemoryLocation location, Status* status) {
+    Status unused;
+    Status& st = status ? *status : unused;
+    LasFile f;
+    if (!(st = open_las(path, options, &f)).ok()) return nullptr;
+    const size_t n = (size_t)f.header.num_points, len = f.header.record_length;
+    auto cloud = PointCloud::create(std::max<size_t>(n, 1), location);
+    if (!cloud) { st = Status::error(StatusCode::OutOfMemory, "LAS: failed to allocate the point cloud"); return nullptr; }
+    cloud->resize(n);
+    cloud->set_crs(f.header.crs);
+    if (location != MemoryLocation::Device) {
+        // in pieces, so that the raw records never take more than 8 M points' worth of memory beside the cloud
+        constexpr size_t kPiece = 8u << 20;
+        std::vector<uint8_t> raw;
+        if (n == 0) st = las_rows_to_host(f, 0, 0, *cloud, 0, raw);
+        for (size_t first = 0; first < n && st.ok(); first += kPiece)
+            st = las_rows_to_host(f, first, std::min(kPiece, n - first), *cloud, first, raw);
+        if (!st.ok()) return nullptr;
+        return cloud;
+    }
+    // Device: the raw records cross PCIe once, out of a page-locked buffer, and are unpacked in HBM
+    float* out[PCR_HIP_LAS_CH_COUNT];
+    if (!(st = las_outputs(f, *cloud, 0, out)).ok()) return nullptr;
+    if (n == 0) return cloud;
+    detail::Buffer pinned, d_records;
+    const size_t bytes = n * len;
+    if (!(st = pinned.allocate(bytes + 16, MemoryLocation::HostPinned)).ok()) return nullptr;
+    if (!(st = d_records.allocate(bytes + 16, MemoryLocation::Device)).ok()) return nullptr;
+    if (!read_segments(f.file->fd, {{static_cast<char*>(pinned.data()), f.header.data_offset, bytes}})) {
+        st = Status::error(StatusCode::IoError, "LAS: failed to read point records");
+        return nullptr;
+    }
+    std::memset(static_cast<char*>(pinned.data()) + bytes, 0, 16);
+    if (!(st = detail::hip_status(pcr_hip_memcpy_h2d(d_records.data(), pinned.data(), bytes + 16, nullptr))).ok()) return nullptr;
+    if (!(st = detail::hip_status(pcr_hip_las_decode(&f.layout, static_cast<const uint8_t*>(d_records.data()), n, cloud->x(),
+                                                     cloud->y(), out, nullptr))).ok()) return nullptr;
+    if (!(st = detail::hip_status(pcr_hip_stream_synchronize(nullptr))).ok()) return nullptr;
+    return cloud;
+}
 
 }  // namespace
 
@@ -370,8 +490,13 @@ std::unique_ptr<PointCloud> read_point_cloud(const std::string& path, PointCloud
     switch (format) {
         case PointCloudFormat::PCR_Binary: return read_pcrp(path, location);
         case PointCloudFormat::CSV: return read_csv(path, location);
-        default: return nullptr;                              // LAS / LAZ: not implemented upstream either
+        case PointCloudFormat::LAS: return read_las_file(path, LasOptions(), location, nullptr);
+        default: return nullptr;                              // LAZ: not implemented upstream either
     }
+}
+
+std::unique_ptr<PointCloud> read_las(const std::string& path, const LasOptions& options, MemoryLocation location, Status* status) {
+    return read_las_file(path, options, location, status);
 }
 
 Status read_point_cloud_info(const std::string& path, PointCloudInfo& info, PointCloudFormat format) {
@@ -382,7 +507,12 @@ Status read_point_cloud_info(const std::string& path, PointCloudInfo& info, Poin
             return read_pcrp_header(ifs, path, info, nullptr);
         }
         case PointCloudFormat::CSV: return read_csv_info(path, info);
-        case PointCloudFormat::LAS:
+        case PointCloudFormat::LAS: {
+            LasFile f;
+            Status s = open_las(path, LasOptions(), &f);
+            if (s.ok()) las_info(f, info);
+            return s;
+        }
         case PointCloudFormat::LAZ: return Status::error(StatusCode::NotImplemented, kLasMessage);
         default: return Status::error(StatusCode::InvalidArgument, "unknown format");
     }
@@ -407,11 +537,18 @@ struct PointCloudReader::Impl {
     PointCloudFormat format = PointCloudFormat::Auto;
     size_t points_read = 0;
     std::unique_ptr<Fd> raw;                     // PCRP body reads (pread, position-independent)
+    LasFile las;                                 // LAS: the open file, its header and the wanted channels
+    std::vector<uint8_t> las_raw;                // LAS: one chunk of records, as read
+    bool is_open() const { return format == PointCloudFormat::LAS ? las.file != nullptr : file.is_open(); }
 };
 
 PointCloudReader::~PointCloudReader() = default;
 
-std::unique_ptr<PointCloudReader> PointCloudReader::open(const std::string& path, PointCloudFormat format) {
+std::unique_ptr<PointCloudReader> PointCloudReader::open(const std::string& path, PointCloudFormat format, const LasOptions* las,
+                                                         Status* status) {
+    Status unused;
+    Status& st = status ? *status : unused;
+    st = Status::error(StatusCode::IoError, "");
     if (format == PointCloudFormat::Auto) format = detect_format(path);
     auto r = std::unique_ptr<PointCloudReader>(new PointCloudReader());
     r->impl_ = std::make_unique<Impl>();
@@ -427,17 +564,31 @@ std::unique_ptr<PointCloudReader> PointCloudReader::open(const std::string& path
         if (!r->impl_->file) return nullptr;
         std::string header;
         std::getline(r->impl_->file, header);
+    } else if (format == PointCloudFormat::LAS) {
+        if (!(st = open_las(path, las ? *las : LasOptions(), &r->impl_->las)).ok()) return nullptr;
+        las_info(r->impl_->las, r->impl_->info);
     } else {
+        if (format == PointCloudFormat::LAZ) st = Status::error(StatusCode::NotImplemented, kLasMessage);
         return nullptr;
     }
+    st = Status::success();
     return r;
 }
 
 const PointCloudInfo& PointCloudReader::info() const { return impl_->info; }
+PointCloudFormat PointCloudReader::format() const { return impl_->format; }
 
 size_t PointCloudReader::read_chunk(PointCloud& cloud, size_t max_points) {
-    if (!impl_ || !impl_->file.is_open() || !host_resident(cloud)) return 0;
+    if (!impl_ || !impl_->is_open() || !host_resident(cloud)) return 0;
     Impl& s = *impl_;
+    if (s.format == PointCloudFormat::LAS) {                     // a contiguous pread of whole records, decoded on the host
+        if (s.points_read >= s.info.num_points) return 0;
+        const size_t n = std::min(max_points, s.info.num_points - s.points_read);
+        if (!cloud.resize(n).ok()) return 0;
+        if (!las_rows_to_host(s.las, s.points_read, n, cloud, 0, s.las_raw).ok()) return 0;
+        s.points_read += n;
+        return n;
+    }
     if (s.format == PointCloudFormat::PCR_Binary) {
         if (s.points_read >= s.info.num_points) return 0;
         const size_t n = std::min(max_points, s.info.num_points - s.points_read);
@@ -454,8 +605,9 @@ size_t PointCloudReader::read_chunk(PointCloud& cloud, size_t max_points) {
 }
 
 Status PointCloudReader::rewind() {
-    if (!impl_ || !impl_->file.is_open()) return Status::error(StatusCode::InvalidArgument, "reader not open");
+    if (!impl_ || !impl_->is_open()) return Status::error(StatusCode::InvalidArgument, "reader not open");
     impl_->points_read = 0;
+    if (impl_->format == PointCloudFormat::LAS) return Status::success();
     impl_->file.clear();
     impl_->file.seekg(0, std::ios::beg);
     if (impl_->format == PointCloudFormat::CSV) {

@@ -103,7 +103,8 @@ void bind_engine(py::module_& m) {
         .def_readwrite("shard_halo_rows", &PipelineConfig::shard_halo_rows)
         .def_readwrite("scatter_path", &PipelineConfig::scatter_path)
         .def_readwrite("finalize_with_first_ingest", &PipelineConfig::finalize_with_first_ingest)
-        .def_readwrite("fill_nodata_radius", &PipelineConfig::fill_nodata_radius);
+        .def_readwrite("fill_nodata_radius", &PipelineConfig::fill_nodata_radius)
+        .def_readwrite("las_gps_time_origin", &PipelineConfig::las_gps_time_origin);
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
         .def(py::init<>())
@@ -131,7 +132,7 @@ void bind_engine(py::module_& m) {
             }
             return n;
         }, py::arg("path"), py::arg("chunk_points") = size_t(4) << 20,
-             "stream a PCRP / CSV file through page-locked double buffers; returns the number of points read")
+             "stream a PCRP / CSV / LAS file through page-locked double buffers; returns the number of points read")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },
              "Device-resident result: the finalize kernels are only enqueued on the pipeline's stream (complete after synchronize()); "

@@ -1,6 +1,7 @@
 // bind_io.cpp -- the reference's I/O layer at the same Python names (python/bindings.cpp:500-640):
 // PCRP / CSV point clouds, GeoTIFF output of finalized grids, `.pcrt` tile-state checkpoints.
-// LAS/LAZ raise NotImplemented as upstream.
+// LAS files are read (read_point_cloud, read_las, PointCloudReader; not in the reference); writing LAS, and LAZ either way,
+// raise NotImplemented as upstream.
 #include "common.h"
 
 #include "pcr/core/fill_nodata.h"
@@ -68,11 +69,17 @@ void bind_io(py::module_& m) {
         .def_readwrite("bounds", &PointCloudInfo::bounds);
 
     py::class_<PointCloudReader>(m, "PointCloudReader")
-        .def_static("open", [](const std::string& path, PointCloudFormat format) {
-            auto r = PointCloudReader::open(path, format);
-            if (!r) throw std::runtime_error("Failed to open point cloud: " + path);
+        .def_static("open", [](const std::string& path, PointCloudFormat format, py::object channels, double gps_time_origin) {
+            LasOptions las;                                     // (only a LAS file looks at it)
+            if (!channels.is_none()) las.channels = channels.cast<std::vector<std::string>>();
+            las.gps_time_origin = gps_time_origin;
+            Status s;
+            auto r = PointCloudReader::open(path, format, &las, &s);
+            if (!r) throw std::runtime_error("Failed to open point cloud: " + path + (s.message.empty() ? "" : ": " + s.message));
             return r;
-        }, py::arg("path"), py::arg("format") = PointCloudFormat::Auto)
+        }, py::arg("path"), py::arg("format") = PointCloudFormat::Auto, py::arg("channels") = py::none(),
+           py::arg("gps_time_origin") = 0.0)
+        .def("format", &PointCloudReader::format)
         .def("info", &PointCloudReader::info, py::return_value_policy::reference_internal)
         .def("read_chunk", &PointCloudReader::read_chunk, py::arg("cloud"), py::arg("max_points"))
         .def("rewind", [](PointCloudReader& r) { raise_if_error(r.rewind()); })
@@ -159,6 +166,17 @@ void bind_io(py::module_& m) {
         if (!c) throw std::runtime_error("Failed to read point cloud: " + path);
         return c;
     }, py::arg("path"), py::arg("format") = PointCloudFormat::Auto, py::arg("location") = MemoryLocation::Host);
+    // extension: a LAS file with a choice of channels (None: all the point format has) and a GPS time origin
+    m.def("read_las", [](const std::string& path, py::object channels, double gps_time_origin, MemoryLocation location) {
+        LasOptions las;
+        if (!channels.is_none()) las.channels = channels.cast<std::vector<std::string>>();
+        las.gps_time_origin = gps_time_origin;
+        Status s;
+        auto c = read_las(path, las, location, &s);
+        if (!c) throw std::runtime_error(s.message.empty() ? "Failed to read point cloud: " + path : s.message);
+        return c;
+    }, py::arg("path"), py::arg("channels") = py::none(), py::arg("gps_time_origin") = 0.0,
+       py::arg("location") = MemoryLocation::Host);
     m.def("write_point_cloud", [](const std::string& path, const PointCloud& cloud, PointCloudFormat format) {
         raise_if_error(write_point_cloud(path, cloud, format));
     }, py::arg("path"), py::arg("cloud"), py::arg("format") = PointCloudFormat::PCR_Binary);

@@ -73,6 +73,7 @@ from ._pcr import (  # noqa: E402,F401
     read_geotiff_band, read_geotiff_band_names, TiledGeoTiffWriter,
     crs_epsg, reproject,
     build_overviews, read_geotiff_overviews, fill_nodata,
+    read_las,
 )
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
@@ -171,4 +172,5 @@ __all__ = [
     "read_geotiff_band", "read_geotiff_band_names", "TiledGeoTiffWriter",
     "crs_epsg", "transform_xy", "reproject",
     "build_overviews", "read_geotiff_overviews", "fill_nodata",
+    "read_las",
 ]

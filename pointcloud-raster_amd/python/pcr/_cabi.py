@@ -78,6 +78,17 @@ class XferGeom(C.Structure):
                 ("reserved_", C.c_int32), ("recv_capacity", C.c_uint64), ("send_counts", C.c_uint64 * 64)]
 
 
+class LasLayout(C.Structure):
+    _fields_ = [("point_format", C.c_int32), ("record_length", C.c_int32), ("scale", C.c_double * 3),
+                ("offset", C.c_double * 3), ("gps_time_origin", C.c_double)]
+
+
+# PCR_HIP_LAS_CH_* in order, under the names the clouds carry; a workgroup of the decode kernel owns 256 * this many records
+LAS_CHANNELS = ("z", "intensity", "return_number", "number_of_returns", "classification", "withheld", "overlap",
+                "scan_angle", "user_data", "point_source_id", "gps_time", "red", "green", "blue", "nir")
+LAS_RECORDS_PER_LANE = 4
+
+
 SYMBOLS = {
     "pcr_hip_last_error": None,
     "pcr_hip_abi_version": [],
@@ -169,6 +180,8 @@ SYMBOLS = {
     "pcr_hip_transform_xy_host": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64],
     "pcr_hip_downsample2": [_VP, C.c_int, C.c_int, _I64, C.POINTER(_VP), C.c_int, C.c_int, _VP],
     "pcr_hip_fill_nodata": [_VP, _VP, C.c_int, C.c_int, _I64, _I64, C.c_int, _VP],
+    "pcr_hip_las_decode": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), _VP],
+    "pcr_hip_las_decode_host": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), C.c_int],
 }
 
 _lib = None
