@@ -526,6 +526,29 @@ int pcr_hip_downsample2(const float* src, int width, int height, int64_t src_str
 int pcr_hip_fill_nodata(const float* src, float* dst, int width, int height, int64_t src_stride, int64_t dst_stride, int radius,
                         pcr_hip_stream s);
 
+/* ---- ground filter: a progressive morphological filter on one band (pcr/core/ground_filter.h: ground_filter; Zhang et al.
+ *      2003), out of place, NaN = no data.
+ *        erode(A, R)(r, c) is the minimum of the non-NaN cells of A in rows r-R..r+R and columns c-R..c+R clipped to the
+ *        image, NaN when there is none; dilate is the same with the maximum.  NaN cells are ignored, never propagated (minNum
+ *        / maxNum).  A0 = src.  For k = 1..levels: Ok = dilate(erode(Ak-1, radii[k]), radii[k]); a cell with non-NaN src
+ *        becomes non-ground when Ak-1(c) - Ok(c) > thresholds[k] (one binary32 subtraction rounded to nearest, a NaN
+ *        difference compares false); then Ak = Ok.  Once non-ground, a cell stays non-ground.
+ *        dst(c) = src(c) bit for bit where src(c) is not NaN and the cell never became non-ground, 0x7FC00000 everywhere
+ *        else.  +-Inf and denormals are values.  The result does not depend on the evaluation order.
+ *      1 <= levels <= 64; 1 <= radii[0] < radii[1] < ... <= 64; every threshold finite and >= 0.  radii and thresholds are
+ *      HOST arrays.  src, dst: `height` rows of `width` floats, `src_stride` / `dst_stride` floats apart (any 4-byte
+ *      alignment; rows that start on 16 bytes take the 16-byte accesses).  d_work: device memory of at least
+ *      pcr_hip_ground_filter_work_bytes(width, height) bytes (three planes; answered without a device).  dst and the
+ *      workspace must not overlap src (nor each other).  Argument errors are reported before any HIP call.  Everything is
+ *      enqueued on s; nothing is allocated or synchronised. */
+int pcr_hip_ground_filter_work_bytes(int width, int height, size_t* bytes);
+int pcr_hip_ground_filter(const float* src, float* dst, int width, int height, int64_t src_stride, int64_t dst_stride, int levels,
+                          const int* radii, const float* thresholds, void* d_work, size_t work_bytes, pcr_hip_stream s);
+/*      Height above ground: dst(c) = top(c) - ground(c), one binary32 subtraction; 0x7FC00000 when an operand or the result
+ *      is NaN.  Strides in floats, any 4-byte alignment; dst may be top or ground.  Enqueued on s. */
+int pcr_hip_band_difference(const float* top, const float* ground, float* dst, int width, int height, int64_t top_stride,
+                            int64_t ground_stride, int64_t dst_stride, pcr_hip_stream s);
+
 /* ---- LAS point records -> the SoA cloud (pcr/io/point_cloud_io.h: LAS input).  No reference counterpart: the reference
  *      declares the format and reads `.las` tiles through laspy in a script.  ASPRS LAS 1.0-1.4, point data record formats
  *      0-10, little-endian, array-of-structures: int32 X, Y, Z, then packed attributes (csrc/las_decode.hpp holds the table).

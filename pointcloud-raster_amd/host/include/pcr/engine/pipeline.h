@@ -9,6 +9,7 @@
 #pragma once
 
 #include "pcr/core/grid_config.h"
+#include "pcr/core/ground_filter.h"
 #include "pcr/core/types.h"
 #include "pcr/engine/filter.h"
 #include "pcr/engine/glyph.h"
@@ -38,6 +39,15 @@ struct ReductionSpec {
 };
 
 enum class ExecutionMode : uint8_t { CPU, GPU, Auto, Hybrid };
+
+/// PipelineConfig::ground: the ground filter (pcr/core/ground_filter.h) at finalize().  Bands are named as the result grid
+/// names them (ReductionSpec::output_band_name, or "{value_channel}_{int(type)}").
+struct GroundFilterConfig : GroundFilterSpec {
+    std::string source_band;             // the band filtered, normally a Min band; empty: off
+    std::string top_band;                // hag = this band - DTM, normally a Max band; empty: no hag band
+    std::string dtm_band_name = "dtm";   // the name of the appended DTM band
+    std::string hag_band_name = "hag";   // the name of the appended hag band
+};
 
 struct PipelineConfig {
     GridConfig grid;
@@ -96,6 +106,13 @@ struct PipelineConfig {
     // written GeoTIFF and its overview levels hold the filled bands; the accumulation state is untouched.  0: nothing is
     // allocated or launched.  A row-block shard lacks its neighbours' rows and refuses it (fill the gathered grid).
     int fill_nodata_radius = 0;
+    // ground.source_band names an output band: finalize() appends a DTM band -- that band with its non-ground cells removed
+    // (NaN) -- and, with ground.top_band, a height-above-ground band, top - DTM.  The filter reads the RAW source band, the
+    // measured minima; with fill_nodata_radius the DTM is then filled like a Min band (filling never chains: a removed
+    // building wider than twice the radius keeps a NaN core) and hag is taken from the bands as they leave the pipeline,
+    // filled.  result(), the GeoTIFF and its overview levels carry the new bands as ordinary bands; the accumulation state
+    // is untouched.  Empty source_band: nothing is allocated or launched.  A row-block shard refuses it.
+    GroundFilterConfig ground;
     // ingest_file of a LAS file: subtracted from the GPS time, in Float64, before it becomes the Float32 `gps_time` channel
     // (LasOptions::gps_time_origin; a MostRecent timestamp needs it: Float32 resolves 32 s at 3e8 s).
     double las_gps_time_origin = 0.0;

@@ -5,6 +5,7 @@
 #include "buffer.h"
 #include "device_pipeline.h"
 #include "fill_nodata.h"
+#include "ground_filter.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -162,6 +163,7 @@ std::unique_ptr<Pipeline> Pipeline::Banded::visit(size_t b, Status* st, bool* wa
     c.shard_halo_rows = -2;                           // whole tile rows: the band's state window is the band
     c.output_path.clear();
     c.fill_nodata_radius = 0;                         // (a band lacks its neighbours' rows: finalize() fills the assembled grid)
+    c.ground = GroundFilterConfig();                  // (... and filters it)
     c.state_dir.clear();
     c.resume = false;
     c.exec_mode = ExecutionMode::GPU;
@@ -297,6 +299,11 @@ Status Pipeline::Banded::finalize() {
         descs.push_back(d);
     }
     if (descs.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+    detail::GroundPlan ground;
+    Status gs = detail::plan_ground(cfg, &ground);
+    if (!gs.ok()) return gs;
+    const size_t n_out = descs.size();                // (the ground filter's bands follow: no band visit makes them)
+    detail::append_ground_bands(ground, descs);
     if (!result) result = Grid::create(g.width, g.height, descs, MemoryLocation::Host);
     if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     tiles_active = 0;
@@ -305,7 +312,7 @@ Status Pipeline::Banded::finalize() {
         if (!parked[b].any) {
             // no point ever had its centre row here: every tile of the band is untouched, every band NaN (Q3) -- no visit
             const size_t first = (size_t)bands[b].first * g.width, cells = (size_t)(bands[b].second - bands[b].first) * g.width;
-            for (size_t o = 0; o < descs.size(); ++o)
+            for (size_t o = 0; o < n_out; ++o)
                 std::fill_n(result->band_f32((int)o) + first, cells, std::numeric_limits<float>::quiet_NaN());
             continue;
         }
@@ -316,7 +323,7 @@ Status Pipeline::Banded::finalize() {
         const Grid* part = sub->result();
         const int rows = bands[b].second - bands[b].first;
         if (!part || part->rows() != rows) return Status::error(StatusCode::CudaError, "pipeline: out-of-core band returned no result");
-        for (size_t o = 0; o < descs.size(); ++o)
+        for (size_t o = 0; o < n_out; ++o)
             std::copy_n(part->band_f32((int)o), (size_t)rows * g.width, result->band_f32((int)o) + (size_t)bands[b].first * g.width);
         for (uint32_t t : parked[b].touched) tiles_active += t ? 1 : 0;
         // finalize changes no state: a band that was read back from its files goes back to being "on disk" at once, and
@@ -324,10 +331,10 @@ Status Pipeline::Banded::finalize() {
         if (from_disk) drop_host_copy(b);
         else if (!(s = evict()).ok()) return s;
     }
-    if (cfg.fill_nodata_radius > 0) {                 // the result is assembled here, on the host: so is its fill
+    {                                                 // the result is assembled here, on the host: so are its ground filter and its fill
         std::vector<ReductionType> types;
         for (const auto& r : cfg.reductions) types.push_back(r.type);
-        Status fs = detail::fill_result_host(*result, types, cfg.fill_nodata_radius);
+        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground);
         if (!fs.ok()) return fs;
     }
     finalized = true;

@@ -5,6 +5,7 @@
 #include "device_pipeline.h"
 
 #include "fill_nodata.h"
+#include "ground_filter.h"
 #include "overviews.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
@@ -26,6 +27,8 @@ Pipeline::Impl::~Impl() {
     groups.clear();
     d_bands.clear();
     d_filled.clear();
+    for (auto& b : d_ground) b.release();
+    d_ground_work.release();
     staging.clear();
     result.reset();
     if (own_stream && stream) pcr_hip_stream_destroy(stream);
@@ -131,6 +134,7 @@ Status Pipeline::Impl::init() {
             ? r.value_channel + "_" + std::to_string(static_cast<int>(r.type)) : r.output_band_name;
         outputs.push_back(o);
     }
+    if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
 
     // row window of this device
     int r0 = 0, r1 = g.height;
@@ -205,6 +209,46 @@ bool Pipeline::Impl::filled(size_t r) const { return cfg.fill_nodata_radius > 0 
 float* Pipeline::Impl::filled_band_device(size_t r) {
     if (!filled(r)) return band_device(r);
     return cfg.result_location == MemoryLocation::Device ? result->band_f32((int)r) : static_cast<float*>(d_filled[r].data());
+}
+// PipelineConfig::ground: the DTM (i = 0) and the hag band (i = 1) as they leave the pipeline; raw: the DTM as the filter stores
+// it, which fill_nodata_radius fills into the one that leaves.  Like the filled bands they live in buffers of their own: the
+// filter reads a raw band and is no plane-state event.
+float* Pipeline::Impl::ground_band_device(int i, bool raw) {
+    if (raw && cfg.fill_nodata_radius > 0) return static_cast<float*>(d_ground[0].data());
+    return cfg.result_location == MemoryLocation::Device ? result->band_f32((int)outputs.size() + i)
+                                                         : static_cast<float*>(d_ground[1 + i].data());
+}
+// Behind the finalize kernels and the fills of every group, on the pipeline's stream: the filter on the RAW source band, the
+// DTM filled like a Min band, hag from the top band and the DTM as they leave the pipeline.
+Status Pipeline::Impl::finalize_ground(bool* enqueued) {
+    if (!ground.on) return Status::success();
+    const int rows = own_rows(), W = hg.width;
+    size_t bytes = 0;
+    Status s = detail::hip_status(pcr_hip_ground_filter_work_bytes(W, rows, &bytes));
+    if (!s.ok()) return s;
+    if (d_ground_work.bytes() < bytes && !(s = d_ground_work.allocate(bytes, MemoryLocation::Device)).ok()) return s;
+    *enqueued = true;
+    s = detail::hip_status(pcr_hip_ground_filter(band_device((size_t)ground.source), ground_band_device(0, true), W, rows, W, W,
+                                                 (int)ground.radii.size(), ground.radii.data(), ground.thresholds.data(),
+                                                 d_ground_work.data(), d_ground_work.bytes(), stream));
+    if (!s.ok()) return s;
+    if (cfg.fill_nodata_radius > 0) {
+        s = detail::hip_status(pcr_hip_fill_nodata(ground_band_device(0, true), ground_band_device(0), W, rows, W, W,
+                                                   cfg.fill_nodata_radius, stream));
+        if (!s.ok()) return s;
+    }
+    if (ground.top >= 0) {
+        s = detail::hip_status(pcr_hip_band_difference(filled_band_device((size_t)ground.top), ground_band_device(0),
+                                                       ground_band_device(1), W, rows, W, W, W, stream));
+        if (!s.ok()) return s;
+    }
+    if (cfg.result_location != MemoryLocation::Device)
+        for (int i = 0; i < ground.extra_bands(); ++i) {
+            s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)outputs.size() + i), ground_band_device(i),
+                                                      (size_t)rows * W * sizeof(float), stream));
+            if (!s.ok()) return s;
+        }
+    return Status::success();
 }
 Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
     return detail::hip_status(pcr_hip_engine_tile_touched(engine, d, tx, ty));
@@ -424,7 +468,8 @@ Status Pipeline::Impl::merge_touched(const void* d_union) {
 }
 
 const float* Pipeline::Impl::result_band_device(int band) {
-    if (!finalized || !result || band < 0 || band >= (int)outputs.size()) return nullptr;
+    if (!finalized || !result || band < 0 || band >= (int)outputs.size() + ground.extra_bands()) return nullptr;
+    if (band >= (int)outputs.size()) return ground_band_device(band - (int)outputs.size());
     return filled_band_device((size_t)band);
 }
 
@@ -755,6 +800,7 @@ Status Pipeline::Impl::allocate_result() {
         bands.push_back(b);
     }
     if (bands.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+    detail::append_ground_bands(ground, bands);
     if (rows <= 0) { result.reset(); return Status::success(); }
     const bool on_device = cfg.result_location == MemoryLocation::Device;
     result = on_device ? Grid::create(W, rows, bands, MemoryLocation::Device)
@@ -775,6 +821,14 @@ Status Pipeline::Impl::allocate_result() {
         std::vector<detail::Buffer>& extra = on_device ? d_bands : d_filled;
         if (extra.size() < outputs.size()) extra.resize(outputs.size());
         Status s = extra[r].allocate((size_t)rows * W * sizeof(float), MemoryLocation::Device);
+        if (!s.ok()) return s;
+    }
+    // ground: the bands that leave the pipeline are the result grid's (Device) or two more device buffers (Host); a DTM that
+    // leaves filled has its raw self in a buffer besides.  (off: nothing is allocated)
+    for (int i = 0; i < 3 && ground.on; ++i) {
+        const bool wanted = i == 0 ? cfg.fill_nodata_radius > 0 : !on_device && i - 1 < ground.extra_bands();
+        if (!wanted) continue;
+        Status s = d_ground[i].allocate((size_t)rows * W * sizeof(float), MemoryLocation::Device);
         if (!s.ok()) return s;
     }
     return Status::success();
@@ -863,6 +917,7 @@ Status Pipeline::Impl::finalize(bool wait) {
             }
         }
     }
+    if (!(s = finalize_ground(&enqueued)).ok()) return s;
     // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
     // kernels on the same stream; only the levels (a third of the data) cross the bus, the host never halves the grid.
     std::vector<std::unique_ptr<Grid>> levels;
@@ -875,6 +930,10 @@ Status Pipeline::Impl::finalize(bool wait) {
             for (size_t r = 0; r < outputs.size(); ++r) {
                 dev_bands.push_back(filled_band_device(r));
                 descs.push_back(result->band_desc((int)r));
+            }
+            for (int i = 0; i < ground.extra_bands(); ++i) {
+                dev_bands.push_back(ground_band_device(i));
+                descs.push_back(result->band_desc((int)outputs.size() + i));
             }
             std::vector<std::unique_ptr<Grid>> d_levels;
             s = detail::build_overviews_device(dev_bands, W, rows, descs, n, detail::overview_mode(out_opt.overview_resampling),

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "buffer.h"
+#include "ground_filter.h"
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
@@ -75,6 +76,10 @@ struct Pipeline::Impl {
     std::vector<detail::Buffer> d_bands;     // finalized bands on the device (result_location == Host; Device: the raw bands
                                              // of the outputs fill_nodata_radius fills, whose filled band is the result grid's)
     std::vector<detail::Buffer> d_filled;    // result_location == Host: the filled bands of those outputs
+    detail::GroundPlan ground;               // PipelineConfig::ground, planned at init
+    detail::Buffer d_ground[3];              // its bands: [0] the raw DTM where the DTM leaves the pipeline filled; [1], [2] the DTM
+                                             // and the hag band as they leave it (result_location == Host; Device: the result grid's)
+    detail::Buffer d_ground_work;            // its workspace, allocated by the first finalize, grow-only
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
                                              // both sides): the blocking finalize reads it after its synchronise and launches
@@ -136,6 +141,8 @@ struct Pipeline::Impl {
     float* band_device(size_t r);
     bool filled(size_t r) const;
     float* filled_band_device(size_t r);
+    float* ground_band_device(int i, bool raw = false);      // i: 0 the DTM, 1 the hag band
+    Status finalize_ground(bool* enqueued);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
     bool offer_bands(size_t gi);
     Status unpack_select(Group& gr);

@@ -2,6 +2,7 @@
 #include "host_pipeline.h"
 
 #include "fill_nodata.h"
+#include "ground_filter.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -175,6 +176,9 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
 Status Pipeline::Host::finalize() {
     if (outputs.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     const GridConfig& g = cfg.grid;
+    detail::GroundPlan ground;
+    Status gs = detail::plan_ground(cfg, &ground);
+    if (!gs.ok()) return gs;
     if (!result) {
         std::vector<BandDesc> bands;
         for (const auto& o : outputs) {                              // band naming: pipeline.cpp:1175-1186
@@ -184,15 +188,16 @@ Status Pipeline::Host::finalize() {
             b.is_state = false;
             bands.push_back(b);
         }
+        detail::append_ground_bands(ground, bands);
         result = Grid::create(g.width, g.height, bands, MemoryLocation::Host);
         if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     }
     for (size_t r = 0; r < outputs.size(); ++r)
         engine->finalize(groups[(size_t)outputs[r].group].planes, outputs[r].type, result->band_f32((int)r));
-    if (cfg.fill_nodata_radius > 0) {                                // (the planes are the state: the bands are made anew by every finalize)
+    {                                                                // (the planes are the state: the bands are made anew by every finalize)
         std::vector<ReductionType> types;
         for (const auto& o : outputs) types.push_back(o.type);
-        Status fs = detail::fill_result_host(*result, types, cfg.fill_nodata_radius);
+        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground);
         if (!fs.ok()) return fs;
     }
     finalized = true;

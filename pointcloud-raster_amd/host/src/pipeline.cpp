@@ -14,6 +14,7 @@
 
 #include "banded_pipeline.h"
 #include "device_pipeline.h"
+#include "ground_filter.h"
 #include "host_pipeline.h"
 #include "las_io.h"
 #include "pcr/core/point_cloud.h"
@@ -78,6 +79,11 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
     if (config.fill_nodata_radius > 0 && (config.shard_row_begin >= 0 || config.shard_row_end >= 0))
         return fail_with(Status::error(StatusCode::InvalidArgument,
             "pipeline: fill_nodata_radius needs the whole grid; fill the gathered grid with fill_nodata"));
+    {
+        detail::GroundPlan plan;                      // (every engine plans again for itself: here only the refusals)
+        const Status gs = detail::plan_ground(config, &plan);
+        if (!gs.ok()) return fail_with(gs);
+    }
     size_t budget = 0;
     if (Banded::needed(config, &budget)) {
         Status bs = Status::success();

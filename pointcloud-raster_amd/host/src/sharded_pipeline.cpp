@@ -3,11 +3,13 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "buffer.h"
 #include "fill_nodata.h"
+#include "ground_filter.h"
 #include "pcr/core/grid.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/core/reproject.h"
@@ -64,6 +66,19 @@ std::unique_ptr<ShardedPipeline> ShardedPipeline::create(PipelineConfig cfg, con
     }
     sp->fill_nodata_radius_ = cfg.fill_nodata_radius;
     cfg.fill_nodata_radius = 0;
+    {
+        // ... and so does the ground filter: planned here on the whole grid, taken off the ranks' configuration
+        PipelineConfig whole = cfg;
+        whole.shard_row_begin = whole.shard_row_end = -1;
+        detail::GroundPlan plan;
+        const Status gs = detail::plan_ground(whole, &plan);
+        if (!gs.ok()) {
+            g_create_error = "ShardedPipeline: " + gs.message;
+            return nullptr;
+        }
+        sp->ground_ = cfg.ground;
+        cfg.ground = GroundFilterConfig();
+    }
     sp->state_dir_ = cfg.state_dir;
     sp->reductions_ = cfg.reductions;
     sp->target_crs_ = cfg.target_crs;
@@ -162,10 +177,13 @@ Status ShardedPipeline::finalize() {
     std::unique_ptr<Grid> whole;
     if (!(s = gather(0, &whole)).ok()) return s;
     if (rank_ != 0) return s;
-    if (fill_nodata_radius_ > 0) {
-        std::vector<ReductionType> types;
-        for (const auto& r : reductions_) types.push_back(r.type);
-        if (!(s = detail::fill_result_host(*whole, types, fill_nodata_radius_)).ok()) return s;
+    {
+        PipelineConfig whole_cfg;                     // what the unsharded pipeline does behind its finalize kernels
+        whole_cfg.grid = grid_;
+        whole_cfg.reductions = reductions_;
+        whole_cfg.fill_nodata_radius = fill_nodata_radius_;
+        whole_cfg.ground = ground_;
+        if (!(s = detail::finish_gathered_host(whole, whole_cfg)).ok()) return s;
     }
     return write_geotiff(output_path_, *whole, grid_, pipeline_output_options(write_cog_));
 }

@@ -3,6 +3,7 @@
 
 #include "pcr/core/grid.h"
 #include "pcr/core/grid_config.h"
+#include "pcr/core/ground_filter.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/core/reproject.h"
 #include "pcr/engine/pipeline.h"
@@ -125,6 +126,15 @@ void bind_core(py::module_& m) {
         .def(py::init<>())
         .def_readwrite("name", &BandDesc::name).def_readwrite("dtype", &BandDesc::dtype)
         .def_readwrite("is_state", &BandDesc::is_state);
+
+    // extension: the level schedule of the ground filter (pcr.ground_filter, PipelineConfig.ground)
+    py::class_<GroundFilterSpec>(m, "GroundFilterSpec")
+        .def(py::init<>())
+        .def_readwrite("max_radius_cells", &GroundFilterSpec::max_radius_cells)
+        .def_readwrite("exponential", &GroundFilterSpec::exponential)
+        .def_readwrite("slope", &GroundFilterSpec::slope)
+        .def_readwrite("initial_distance", &GroundFilterSpec::initial_distance)
+        .def_readwrite("max_distance", &GroundFilterSpec::max_distance);
 
     py::class_<GridConfig>(m, "GridConfig")
         .def(py::init<>())

@@ -7,6 +7,7 @@
 #include "pcr/engine/glyph.h"
 #include "pcr/engine/pipeline.h"
 #include "pcr/engine/sharded_pipeline.h"
+#include "../../host/src/ground_filter.h"
 
 using namespace pcr;
 
@@ -74,6 +75,14 @@ void bind_engine(py::module_& m) {
         .def_readwrite("output_band_name", &ReductionSpec::output_band_name)
         .def_readwrite("glyph", &ReductionSpec::glyph);
 
+    py::class_<GroundFilterConfig, GroundFilterSpec>(m, "GroundFilterConfig")
+        .def(py::init<>())
+        .def(py::init<const GroundFilterConfig&>())
+        .def_readwrite("source_band", &GroundFilterConfig::source_band)
+        .def_readwrite("top_band", &GroundFilterConfig::top_band)
+        .def_readwrite("dtm_band_name", &GroundFilterConfig::dtm_band_name)
+        .def_readwrite("hag_band_name", &GroundFilterConfig::hag_band_name);
+
     py::class_<PipelineConfig>(m, "PipelineConfig")
         .def(py::init<>())
         .def_readwrite("grid", &PipelineConfig::grid)
@@ -104,6 +113,7 @@ void bind_engine(py::module_& m) {
         .def_readwrite("scatter_path", &PipelineConfig::scatter_path)
         .def_readwrite("finalize_with_first_ingest", &PipelineConfig::finalize_with_first_ingest)
         .def_readwrite("fill_nodata_radius", &PipelineConfig::fill_nodata_radius)
+        .def_readwrite("ground", &PipelineConfig::ground)
         .def_readwrite("las_gps_time_origin", &PipelineConfig::las_gps_time_origin);
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
@@ -208,6 +218,18 @@ void bind_engine(py::module_& m) {
         .def("out_of_core", &Pipeline::out_of_core,
              "True when the grid's state exceeds gpu_memory_budget and the pipeline sweeps it in row bands of whole reference-tile rows");
 
+    // pcr.distributed: what rank 0 does to the gathered grid -- PipelineConfig.ground, then fill_nodata_radius -- and the check
+    // of PipelineConfig.ground that Pipeline.create makes (the ranks' own configurations carry neither field)
+    m.def("_finish_gathered", [](const Grid& gathered, const PipelineConfig& whole_cfg) {
+        std::unique_ptr<Grid> whole = gathered.to(MemoryLocation::Host);
+        if (!whole) throw std::runtime_error("pipeline: failed to copy the gathered grid");
+        raise_if_error(detail::finish_gathered_host(whole, whole_cfg));
+        return whole;
+    }, py::arg("gathered"), py::arg("whole_cfg"));
+    m.def("_check_ground", [](const PipelineConfig& whole_cfg) {
+        detail::GroundPlan plan;
+        raise_if_error(detail::plan_ground(whole_cfg, &plan));
+    }, py::arg("whole_cfg"));
     m.def("pipeline_create_error", &pipeline_create_error,
           "Why the last Pipeline.create() on this thread returned None");
     m.def("device_count", &cuda_device_count);

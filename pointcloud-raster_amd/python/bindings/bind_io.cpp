@@ -7,10 +7,12 @@
 #include "pcr/core/fill_nodata.h"
 #include "pcr/core/grid.h"
 #include "pcr/core/grid_config.h"
+#include "pcr/core/ground_filter.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 #include "pcr/io/point_cloud_io.h"
 #include "pcr/io/tile_state_io.h"
+#include "../../host/src/ground_filter.h"
 
 #include <vector>
 
@@ -127,6 +129,34 @@ void bind_io(py::module_& m) {
         raise_if_error(s);
         return out;
     }, py::arg("grid"), py::arg("radius"), py::arg("bands") = py::none());
+    // extension: the ground filter (a DTM band, and height above ground) of a grid's band, where the grid lives
+    m.def("ground_filter", [](const Grid& grid, int band, py::object spec, double cell_size, py::object top_band) {
+        Status s;
+        auto out = ground_filter(grid, band, spec.is_none() ? GroundFilterSpec() : spec.cast<GroundFilterSpec>(), cell_size,
+                                 top_band.is_none() ? -1 : top_band.cast<int>(), &s, nullptr);
+        raise_if_error(s);
+        return out;
+    }, py::arg("grid"), py::arg("band") = 0, py::arg("spec") = py::none(), py::arg("cell_size") = 1.0, py::arg("top_band") = py::none());
+    m.def("ground_filter_levels", [](const GroundFilterSpec& spec, double cell_size) {
+        std::vector<int> radii;
+        std::vector<float> thresholds;
+        raise_if_error(ground_filter_levels(spec, cell_size, &radii, &thresholds));
+        return py::make_tuple(radii, thresholds);
+    }, py::arg("spec"), py::arg("cell_size") = 1.0);
+    // (tests, tools) the host loop on an array with explicit levels, which the kernels are compared with level by level
+    m.def("_ground_filter_host", [](py::array_t<float, py::array::c_style | py::array::forcecast> src, const std::vector<int>& radii,
+                                    const std::vector<float>& thresholds) {
+        if (src.ndim() != 2 || src.shape(0) < 1 || src.shape(1) < 1) throw std::invalid_argument("ground_filter: a 2-D array is needed");
+        if (radii.empty() || radii.size() != thresholds.size() || radii.size() > 64)
+            throw std::invalid_argument("ground_filter: levels must be between 1 and 64");
+        for (size_t k = 0; k < radii.size(); ++k)
+            if (radii[k] < 1 || radii[k] > 64 || (k && radii[k] <= radii[k - 1]) || !(thresholds[k] >= 0.0f) || !std::isfinite(thresholds[k]))
+                throw std::invalid_argument("ground_filter: invalid level");
+        const int h = (int)src.shape(0), w = (int)src.shape(1);
+        py::array_t<float> out({h, w});
+        detail::ground_filter_host(src.data(), out.mutable_data(), w, h, w, w, (int)radii.size(), radii.data(), thresholds.data());
+        return out;
+    }, py::arg("src"), py::arg("radii"), py::arg("thresholds"));
     m.def("read_geotiff_overviews", [](const std::string& path) {
         std::vector<std::pair<int, int>> sizes;
         raise_if_error(read_geotiff_overviews(path, sizes));

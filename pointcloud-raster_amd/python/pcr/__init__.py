@@ -74,6 +74,7 @@ from ._pcr import (  # noqa: E402,F401
     crs_epsg, reproject,
     build_overviews, read_geotiff_overviews, fill_nodata,
     read_las,
+    GroundFilterSpec, GroundFilterConfig, ground_filter, ground_filter_levels,
 )
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
@@ -173,4 +174,5 @@ __all__ = [
     "crs_epsg", "transform_xy", "reproject",
     "build_overviews", "read_geotiff_overviews", "fill_nodata",
     "read_las",
+    "GroundFilterSpec", "GroundFilterConfig", "ground_filter", "ground_filter_levels",
 ]

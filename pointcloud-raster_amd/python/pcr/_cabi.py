@@ -180,6 +180,10 @@ SYMBOLS = {
     "pcr_hip_transform_xy_host": [C.POINTER(CrsDesc), C.POINTER(CrsDesc), _VP, _VP, _VP, _VP, _U64],
     "pcr_hip_downsample2": [_VP, C.c_int, C.c_int, _I64, C.POINTER(_VP), C.c_int, C.c_int, _VP],
     "pcr_hip_fill_nodata": [_VP, _VP, C.c_int, C.c_int, _I64, _I64, C.c_int, _VP],
+    "pcr_hip_ground_filter_work_bytes": [C.c_int, C.c_int, C.POINTER(_SZ)],
+    "pcr_hip_ground_filter": [_VP, _VP, C.c_int, C.c_int, _I64, _I64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), _VP, _SZ,
+                              _VP],
+    "pcr_hip_band_difference": [_VP, _VP, _VP, C.c_int, C.c_int, _I64, _I64, _I64, _VP],
     "pcr_hip_las_decode": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), _VP],
     "pcr_hip_las_decode_host": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), C.c_int],
 }

@@ -319,6 +319,11 @@ class ShardedPipeline:
         self.exchange_ms = None              # set by exchange(timed=True)
         self.blocks = [row_block(r, world, cfg.grid.height, align) for r in range(world)]
         self.own = self.blocks[rank]
+        # a row block lacks its neighbours' rows: rank 0 applies the ground filter to the gathered grid, before it fills it
+        from . import _pcr
+        _pcr._check_ground(cfg)                      # (RuntimeError with Pipeline.create's message)
+        self.ground, cfg.ground = pcr.GroundFilterConfig(cfg.ground), pcr.GroundFilterConfig()
+        self._reductions = list(cfg.reductions)
         cfg.shard_row_begin, cfg.shard_row_end = self.own
         # ONE file for the whole grid, written by rank 0 from the gathered strips (the reference writes one file,
         # src/engine/pipeline.cpp:1351-1361) -- not a strip per rank under the same name
@@ -607,7 +612,17 @@ class ShardedPipeline:
         if self.output_path:
             import pcr
             whole = self.gather(0)
-            if self.rank == 0:
+            if self.rank == 0 and self.ground.source_band:
+                from . import _pcr
+                whole_cfg = pcr.PipelineConfig()
+                whole_cfg.grid, whole_cfg.reductions, whole_cfg.ground = self.grid, self._reductions, self.ground
+                whole_cfg.fill_nodata_radius = self.fill_nodata_radius
+                whole = _pcr._finish_gathered(whole, whole_cfg)
+                opts = pcr.GeoTiffOptions()
+                if self.write_cog:
+                    opts.overviews = -1
+                pcr.write_geotiff(self.output_path, whole, self.grid, opts)
+            elif self.rank == 0:
                 if self.fill_nodata_radius > 0:
                     filled = [b for b, t in enumerate(self._rtypes) if t in (
                         pcr.ReductionType.Average, pcr.ReductionType.WeightedAverage, pcr.ReductionType.Min,
