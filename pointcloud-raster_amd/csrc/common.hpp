@@ -145,6 +145,8 @@ __device__ __forceinline__ bool world_to_cell(const GridDev& g, double wx, doubl
 typedef double pcr_d2v __attribute__((ext_vector_type(2)));
 typedef unsigned pcr_u4v __attribute__((ext_vector_type(4)));
 typedef unsigned pcr_u2v __attribute__((ext_vector_type(2)));
+typedef float pcr_f4v __attribute__((ext_vector_type(4)));
+typedef float pcr_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double2 stream_load(const double2* p) {
     const pcr_d2v t = __builtin_nontemporal_load(reinterpret_cast<const pcr_d2v*>(p));
     return make_double2(t.x, t.y);
@@ -154,7 +156,6 @@ __device__ __forceinline__ uint4 stream_load(const uint4* p) {
     return make_uint4(t.x, t.y, t.z, t.w);
 }
 __device__ __forceinline__ float4 stream_load(const float4* p) {
-    typedef float pcr_f4v __attribute__((ext_vector_type(4)));
     const pcr_f4v t = __builtin_nontemporal_load(reinterpret_cast<const pcr_f4v*>(p));
     return make_float4(t.x, t.y, t.z, t.w);
 }

@@ -19,7 +19,7 @@
 // LDS is sized by the radius class RMAX (8, 16, 32: the smallest that holds R), because the LDS a workgroup reserves decides
 // how many hole-free tiles a CU copies at a time: (32 + 2 RMAX) rows x (64 + 2 RMAX) floats + the list (4 KB) + the weights
 // = 19.8 / 29.9 / 57.8 KB, i.e. 8 / 5 / 2 workgroups per CU.
-#include "common.hpp"
+#include "band_pass.hpp"
 #include "fill_nodata.hpp"
 
 namespace pcrhip {
@@ -28,8 +28,6 @@ namespace {
 using namespace fill;
 
 constexpr int kTileW = 64, kTileH = 32;
-
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 struct FillArgs {
     const float* src;
@@ -104,7 +102,7 @@ __global__ __launch_bounds__(256) void k_fill_nodata(const FillArgs a) {
         const unsigned in4 = (inside >> (4 * p)) & 0xFu;
         const bool whole = v[p][0] == v[p][0] && v[p][1] == v[p][1] && v[p][2] == v[p][2] && v[p][3] == v[p][3];
         if (VEC && in4 == 0xFu && whole) {
-            __builtin_nontemporal_store(f4v{v[p][0], v[p][1], v[p][2], v[p][3]}, reinterpret_cast<f4v*>(row + c));
+            __builtin_nontemporal_store(pcr_f4v{v[p][0], v[p][1], v[p][2], v[p][3]}, reinterpret_cast<pcr_f4v*>(row + c));
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -137,7 +135,7 @@ __global__ __launch_bounds__(256) void k_fill_nodata(const FillArgs a) {
             const int r = r0 - R + lr, gc = c0 - Ra + 4 * q;
             if (r >= r0 && r < r0 + kTileH && gc >= c0 && gc < c0 + kTileW) continue;      // the tile itself
             float4 x = make_float4(out, out, out, out);
-            if (r >= 0 && r < a.h) {
+            if (r >= 0 && r < a.h) {                             // (band::load_quad by hand: the compiler schedules the call otherwise)
                 const float* row = a.src + (int64_t)r * a.src_stride;
                 if (VEC && gc >= 0 && gc + 4 <= a.w) {
                     x = *reinterpret_cast<const float4*>(row + gc);
@@ -179,19 +177,12 @@ using namespace pcrhip;
 
 extern "C" int pcr_hip_fill_nodata(const float* src, float* dst, int width, int height, int64_t src_stride, int64_t dst_stride,
                                    int radius, pcr_hip_stream s) {
-    PCR_REQUIRE(src && dst, "fill_nodata: null argument");
-    PCR_REQUIRE(width > 0 && height > 0, "fill_nodata: width and height must be positive");
-    PCR_REQUIRE(src_stride >= width, "fill_nodata: src_stride smaller than width");
-    PCR_REQUIRE(dst_stride >= width, "fill_nodata: dst_stride smaller than width");
+    if (int rc = band::check_bands("fill_nodata", width, height, {{"src", src, src_stride}, {"dst", dst, dst_stride}})) return rc;
     PCR_REQUIRE(radius >= 1 && radius <= fill::kMaxRadius, "fill_nodata: radius must be between 1 and 32");
-    {
-        // the bytes either side spans, first cell to last: the fill reads src after it has stored dst cells
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
-        const uintptr_t s1 = s0 + ((uintptr_t)(height - 1) * (uintptr_t)src_stride + (uintptr_t)width) * 4;
-        const uintptr_t d1 = d0 + ((uintptr_t)(height - 1) * (uintptr_t)dst_stride + (uintptr_t)width) * 4;
-        PCR_REQUIRE(s1 <= d0 || d1 <= s0, "fill_nodata: dst overlaps src");
-    }
-    PCR_REQUIRE((height + kTileH - 1) / kTileH <= 65535, "fill_nodata: more than 65535 tile rows");
+    // (the fill reads src after it has stored dst cells)
+    PCR_REQUIRE(!band::overlap(band::span_of(src, width, height, src_stride), band::span_of(dst, width, height, dst_stride)),
+                "fill_nodata: dst overlaps src");
+    if (int rc = band::check_tile_rows("fill_nodata", height, kTileH)) return rc;
     FillArgs a;
     a.src = src;
     a.dst = dst;
@@ -200,8 +191,7 @@ extern "C" int pcr_hip_fill_nodata(const float* src, float* dst, int width, int 
     a.src_stride = src_stride;
     a.dst_stride = dst_stride;
     a.R = radius;
-    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && src_stride % 4 == 0 &&
-                     dst_stride % 4 == 0;
+    const bool vec = band::aligned16(src, src_stride) && band::aligned16(dst, dst_stride);
     const dim3 grid((width + kTileW - 1) / kTileW, (height + kTileH - 1) / kTileH);
     hipStream_t st = static_cast<hipStream_t>(s);
     if (radius <= 8) {

@@ -19,19 +19,19 @@
 // A(k-1), which nobody else reads.  Workspace: A and two temporaries, three planes with rows padded to whole quads.
 // LDS is dynamic, sized by R: 64 x (64 + 2R [+ 1]) floats = 17 KB at R = 1, 24 KB at R = 16, 48 KB at R = 64, so the waves a CU
 // holds fall from 9 to 3 as the apron grows.  No atomics, no scratch.  Measured: profiles/ground_filter.md.
-#include "common.hpp"
+#include "band_pass.hpp"
 #include "ground_filter.hpp"
 
 namespace pcrhip {
 namespace {
 
 using namespace ground;
+using band::aligned16;
+using band::load_quad;
 
 constexpr int kLines = 64;                                       // lines of a tile = lanes of its wave
 constexpr int kTile = 64;                                        // cells of a tile along the pass's axis
 constexpr int kBatch = 8;                                        // global loads a lane keeps in flight while it stages
-
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 struct PassArgs {
     const float* in;                 // the plane the windows are taken of
@@ -46,23 +46,6 @@ struct PassArgs {
 };
 
 __device__ __forceinline__ int pad4(int R) { return (R + 3) & ~3; }
-
-// cells c .. c + 3 of an image row (null: a row outside the image), cells outside the image as NaN
-template <bool VEC>
-__device__ __forceinline__ float4 load_quad(const float* row, int c, int w) {
-    const float out = nodata();
-    float4 x = make_float4(out, out, out, out);
-    if (!row) return x;
-    if (VEC && c >= 0 && c + 4 <= w) return *reinterpret_cast<const float4*>(row + c);
-    if (c >= 0 && c < w) x.x = row[c];
-    if (c + 1 >= 0 && c + 1 < w) x.y = row[c + 1];
-    if (c + 2 >= 0 && c + 2 < w) x.z = row[c + 2];
-    if (c + 3 >= 0 && c + 3 < w) x.w = row[c + 3];
-    return x;
-}
-__device__ __forceinline__ float4 load_quad(const float* row, int c, int w, int vec) {
-    return vec ? load_quad<true>(row, c, w) : load_quad<false>(row, c, w);
-}
 
 // ---- a row pass: the tile's lines are image rows r0 .. r0 + 63, its cells columns c0 .. c0 + 63
 template <bool MAX, bool VEC>                                    // VEC: the rows of `in` start on 16 bytes
@@ -96,7 +79,7 @@ __global__ __launch_bounds__(kLines) void k_ground_rows(const PassArgs a) {
             if (a.dst && r < a.h && c >= c0 && c < c0 + kTile && c < a.w) {
                 float* d = a.dst + (int64_t)r * a.dst_stride + c;
                 if (a.dst_vec && c + 4 <= a.w) {
-                    *reinterpret_cast<f4v*>(d) = f4v{y.x, y.y, y.z, y.w};
+                    *reinterpret_cast<pcr_f4v*>(d) = pcr_f4v{y.x, y.y, y.z, y.w};
                 } else {
                     d[0] = y.x;
                     if (c + 1 < a.w) d[1] = y.y;
@@ -116,7 +99,7 @@ __global__ __launch_bounds__(kLines) void k_ground_rows(const PassArgs a) {
         const int r = r0 + rr, c = c0 + 4 * q;
         if (r >= a.h || c >= a.w) continue;
         const float* l = lds + rr * pitch + (Ra - R) + 4 * q;
-        *reinterpret_cast<f4v*>(a.out + (int64_t)r * a.out_stride + c) = f4v{l[0], l[1], l[2], l[3]};
+        *reinterpret_cast<pcr_f4v*>(a.out + (int64_t)r * a.out_stride + c) = pcr_f4v{l[0], l[1], l[2], l[3]};
     }
 }
 
@@ -175,7 +158,7 @@ __global__ __launch_bounds__(kLines) void k_ground_cols(const PassArgs a) {
                 if (c + 3 < a.w && non_ground(A[u].w, o.w, a.t)) d[3] = out;
                 if (!a.out) continue;                            // the last level: nobody reads Ok
             }
-            *reinterpret_cast<f4v*>(a.out + (int64_t)r * a.out_stride + c) = f4v{o.x, o.y, o.z, o.w};
+            *reinterpret_cast<pcr_f4v*>(a.out + (int64_t)r * a.out_stride + c) = pcr_f4v{o.x, o.y, o.z, o.w};
         }
     }
 }
@@ -197,8 +180,8 @@ __global__ __launch_bounds__(256) void k_band_difference(const DiffArgs a) {
         const float4 g = load_quad<VEC>(a.gnd + (int64_t)r * a.gnd_stride, c, a.w);
         float* d = a.dst + (int64_t)r * a.dst_stride + c;
         if (VEC && c + 4 <= a.w) {
-            __builtin_nontemporal_store(f4v{difference(t.x, g.x), difference(t.y, g.y), difference(t.z, g.z), difference(t.w, g.w)},
-                                        reinterpret_cast<f4v*>(d));
+            __builtin_nontemporal_store(pcr_f4v{difference(t.x, g.x), difference(t.y, g.y), difference(t.z, g.z), difference(t.w, g.w)},
+                                        reinterpret_cast<pcr_f4v*>(d));
         } else {
             d[0] = difference(t.x, g.x);
             if (c + 1 < a.w) d[1] = difference(t.y, g.y);
@@ -211,22 +194,13 @@ __global__ __launch_bounds__(256) void k_band_difference(const DiffArgs a) {
 int64_t work_pitch(int width) { return ((int64_t)width + 3) & ~(int64_t)3; }
 size_t work_bytes_of(int width, int height) { return (size_t)3 * (size_t)work_pitch(width) * (size_t)height * 4 + 16; }
 
-bool aligned16(const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && stride % 4 == 0; }
-
-// [p, p + the bytes `height` rows of `width` floats `stride` apart span)
-void span_of(const void* p, int width, int height, int64_t stride, uintptr_t* b, uintptr_t* e) {
-    *b = reinterpret_cast<uintptr_t>(p);
-    *e = *b + ((uintptr_t)(height - 1) * (uintptr_t)stride + (uintptr_t)width) * 4;
-}
-
 }  // namespace
 }  // namespace pcrhip
 
 using namespace pcrhip;
 
 extern "C" int pcr_hip_ground_filter_work_bytes(int width, int height, size_t* bytes) {
-    PCR_REQUIRE(bytes, "ground_filter_work_bytes: null argument");
-    PCR_REQUIRE(width > 0 && height > 0, "ground_filter_work_bytes: width and height must be positive");
+    if (int rc = band::check_extent("ground_filter_work_bytes", bytes != nullptr, width, height)) return rc;
     *bytes = work_bytes_of(width, height);
     return PCR_HIP_OK;
 }
@@ -234,10 +208,8 @@ extern "C" int pcr_hip_ground_filter_work_bytes(int width, int height, size_t* b
 extern "C" int pcr_hip_ground_filter(const float* src, float* dst, int width, int height, int64_t src_stride, int64_t dst_stride,
                                      int levels, const int* radii, const float* thresholds, void* d_work, size_t work_bytes,
                                      pcr_hip_stream s) {
-    PCR_REQUIRE(src && dst && radii && thresholds && d_work, "ground_filter: null argument");
-    PCR_REQUIRE(width > 0 && height > 0, "ground_filter: width and height must be positive");
-    PCR_REQUIRE(src_stride >= width, "ground_filter: src_stride smaller than width");
-    PCR_REQUIRE(dst_stride >= width, "ground_filter: dst_stride smaller than width");
+    if (int rc = band::check_bands("ground_filter", width, height, {{"src", src, src_stride}, {"dst", dst, dst_stride}},
+                                   radii && thresholds && d_work)) return rc;
     PCR_REQUIRE(levels >= 1 && levels <= ground::kMaxLevels, "ground_filter: levels must be between 1 and 64");
     for (int k = 0; k < levels; ++k) {
         PCR_REQUIRE(radii[k] >= 1 && radii[k] <= ground::kMaxRadius, "ground_filter: a radius must be between 1 and 64");
@@ -246,15 +218,13 @@ extern "C" int pcr_hip_ground_filter(const float* src, float* dst, int width, in
     }
     PCR_REQUIRE(work_bytes >= work_bytes_of(width, height), "ground_filter: work_bytes too small (pcr_hip_ground_filter_work_bytes)");
     {
-        uintptr_t s0, s1, d0, d1;
-        span_of(src, width, height, src_stride, &s0, &s1);
-        span_of(dst, width, height, dst_stride, &d0, &d1);
-        const uintptr_t w0 = reinterpret_cast<uintptr_t>(d_work), w1 = w0 + work_bytes;
-        PCR_REQUIRE(s1 <= d0 || d1 <= s0, "ground_filter: dst overlaps src");
-        PCR_REQUIRE(s1 <= w0 || w1 <= s0, "ground_filter: the workspace overlaps src");
-        PCR_REQUIRE(d1 <= w0 || w1 <= d0, "ground_filter: the workspace overlaps dst");
+        const band::Span sb = band::span_of(src, width, height, src_stride), db = band::span_of(dst, width, height, dst_stride);
+        const band::Span wb = band::span_of(d_work, work_bytes);
+        PCR_REQUIRE(!band::overlap(sb, db), "ground_filter: dst overlaps src");
+        PCR_REQUIRE(!band::overlap(sb, wb), "ground_filter: the workspace overlaps src");
+        PCR_REQUIRE(!band::overlap(db, wb), "ground_filter: the workspace overlaps dst");
     }
-    PCR_REQUIRE((height + kLines - 1) / kLines <= 65535, "ground_filter: more than 65535 tile rows");
+    if (int rc = band::check_tile_rows("ground_filter", height, kLines)) return rc;
 
     const int64_t pitch = work_pitch(width);
     float* base = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~(uintptr_t)15);
@@ -309,11 +279,8 @@ extern "C" int pcr_hip_ground_filter(const float* src, float* dst, int width, in
 
 extern "C" int pcr_hip_band_difference(const float* top, const float* ground, float* dst, int width, int height, int64_t top_stride,
                                        int64_t ground_stride, int64_t dst_stride, pcr_hip_stream s) {
-    PCR_REQUIRE(top && ground && dst, "band_difference: null argument");
-    PCR_REQUIRE(width > 0 && height > 0, "band_difference: width and height must be positive");
-    PCR_REQUIRE(top_stride >= width, "band_difference: top_stride smaller than width");
-    PCR_REQUIRE(ground_stride >= width, "band_difference: ground_stride smaller than width");
-    PCR_REQUIRE(dst_stride >= width, "band_difference: dst_stride smaller than width");
+    if (int rc = band::check_bands("band_difference", width, height,
+                                   {{"top", top, top_stride}, {"ground", ground, ground_stride}, {"dst", dst, dst_stride}})) return rc;
     DiffArgs a;
     a.top = top;
     a.gnd = ground;

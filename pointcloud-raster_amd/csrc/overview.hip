@@ -9,7 +9,7 @@
 // six levels: the launch function starts the kernel again on level 6, 12, ... on the same stream.  Cells outside the source are
 // NaN (invalid, overview.hpp); a level cell outside its level is computed and never stored.
 // The scalar variant (VEC = false) serves rows that do not start on 16 bytes.
-#include "common.hpp"
+#include "band_pass.hpp"
 #include "overview.hpp"
 
 namespace pcrhip {
@@ -103,14 +103,13 @@ using namespace pcrhip;
 
 extern "C" int pcr_hip_downsample2(const float* src, int width, int height, int64_t src_stride, float* const* dst, int levels,
                                    int mode, pcr_hip_stream s) {
-    PCR_REQUIRE(src && dst, "downsample2: null argument");
-    PCR_REQUIRE(width > 0 && height > 0, "downsample2: width and height must be positive");
+    if (int rc = band::check_extent("downsample2", src && dst, width, height)) return rc;
     PCR_REQUIRE(levels > 0, "downsample2: levels must be positive");
-    PCR_REQUIRE(src_stride >= width, "downsample2: src_stride smaller than width");
+    if (int rc = band::check_stride("downsample2", "src", src_stride, width)) return rc;
     PCR_REQUIRE(mode == overview::kAverage || mode == overview::kNearest, "downsample2: unknown mode (0 average, 1 nearest)");
     PCR_REQUIRE(levels <= overview::max_levels(width, height), "downsample2: more levels than halvings down to 1x1");
     for (int k = 0; k < levels; ++k) PCR_REQUIRE(dst[k], "downsample2: null level pointer");
-    PCR_REQUIRE((height + overview::kTile - 1) / overview::kTile <= 65535, "downsample2: more than 65535 tile rows");
+    if (int rc = band::check_tile_rows("downsample2", height, overview::kTile)) return rc;
     hipStream_t st = static_cast<hipStream_t>(s);
     int w = width, h = height;
     int64_t stride = src_stride;
@@ -124,7 +123,7 @@ extern "C" int pcr_hip_downsample2(const float* src, int width, int height, int6
         a.mode = mode;
         for (int k = 0; k < overview::kLevelsPerPass; ++k) a.dst[k] = k < a.levels ? dst[done + k] : nullptr;
         a.pair_stores = overview::level_extent(w, 1) % 2 == 0 && (reinterpret_cast<uintptr_t>(a.dst[0]) & 7) == 0;
-        const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0 && stride % 4 == 0;
+        const bool vec = band::aligned16(src, stride);
         const dim3 grid((w + overview::kTile - 1) / overview::kTile, (h + overview::kTile - 1) / overview::kTile);
         if (vec) hipLaunchKernelGGL(k_downsample2<true>, grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_downsample2<false>, grid, dim3(256), 0, st, a);

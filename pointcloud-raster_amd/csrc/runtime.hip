@@ -184,7 +184,6 @@ int pcr_hip_memcpy_d2d(void* d_dst, const void* d_src, size_t bytes, pcr_hip_str
 // /opt/skills/guides/MI355X_MICROARCH.md quotes 6.29 TB/s for.  bench.py reports it as `measured_copy_GBps`, the practical
 // roof of THIS box, next to torch's copy_ (the runtime's blit kernel) and the 8 TB/s data-sheet peak.
 namespace {
-typedef float pcr_f4v __attribute__((ext_vector_type(4)));
 template <bool NT>
 __global__ void __launch_bounds__(256)
 k_copy_f4(pcr_f4v* __restrict__ dst, const pcr_f4v* __restrict__ src, size_t n4) {

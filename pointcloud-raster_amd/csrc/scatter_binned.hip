@@ -792,7 +792,6 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
                        ((MASK & 4) ? reinterpret_cast<uintptr_t>(pl.mx) : 0) | ((MASK & 8) ? reinterpret_cast<uintptr_t>(pl.mn) : 0)) & 15) == 0;
     // one lane = 4 consecutive cells of a row (wide LDS reads, float4 global accesses).  A tile row is 32 such quads, so a
     // lane keeps its columns and moves down 32 rows per iteration: no division anywhere.
-    typedef float f4v __attribute__((ext_vector_type(4)));
     const int lx = (threadIdx.x & 31) << 2, ly0 = threadIdx.x >> 5;
     if (vec && full) {
         // Every cell is stored (the planes are undefined: nothing is read), and FUSED the bands with them.  What a band
@@ -808,7 +807,7 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
         const unsigned defer = FUSED ? fo.defer : 0u;
         // (as integers, and stored through global-address-space pointers made from them: a pointer that has been through the
         // pin below is a generic one to the compiler, and its stores came out as flat_store)
-        typedef __attribute__((address_space(1))) f4v* gf4p;
+        typedef __attribute__((address_space(1))) pcr_f4v* gf4p;
         uintptr_t p_sum = (defer & 1u) ? 0 : reinterpret_cast<uintptr_t>(pl.sum);
         uintptr_t p_wgt = (defer & 2u) ? 0 : reinterpret_cast<uintptr_t>(pl.wgt);
         uintptr_t p_max = (defer & 4u) ? 0 : reinterpret_cast<uintptr_t>(pl.mx);
@@ -885,13 +884,13 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
             if (FUSED && (MASK & 4)) asm volatile("" : "+s"(p_max));
             if (FUSED && (MASK & 8)) asm volatile("" : "+s"(p_min));
             if (FUSED) {
-                if ((MASK & 1) && p_sum) __builtin_nontemporal_store(f4v{s4[0], s4[1], s4[2], s4[3]}, (gf4p)(p_sum + 4 * (uintptr_t)cell));
-                if ((MASK & 2) && p_wgt) __builtin_nontemporal_store(f4v{w4[0], w4[1], w4[2], w4[3]}, (gf4p)(p_wgt + 4 * (uintptr_t)cell));
-                if ((MASK & 4) && p_max) *(gf4p)(p_max + 4 * (uintptr_t)cell) = f4v{x4[0], x4[1], x4[2], x4[3]};
-                if ((MASK & 8) && p_min) *(gf4p)(p_min + 4 * (uintptr_t)cell) = f4v{m4[0], m4[1], m4[2], m4[3]};
+                if ((MASK & 1) && p_sum) __builtin_nontemporal_store(pcr_f4v{s4[0], s4[1], s4[2], s4[3]}, (gf4p)(p_sum + 4 * (uintptr_t)cell));
+                if ((MASK & 2) && p_wgt) __builtin_nontemporal_store(pcr_f4v{w4[0], w4[1], w4[2], w4[3]}, (gf4p)(p_wgt + 4 * (uintptr_t)cell));
+                if ((MASK & 4) && p_max) *(gf4p)(p_max + 4 * (uintptr_t)cell) = pcr_f4v{x4[0], x4[1], x4[2], x4[3]};
+                if ((MASK & 8) && p_min) *(gf4p)(p_min + 4 * (uintptr_t)cell) = pcr_f4v{m4[0], m4[1], m4[2], m4[3]};
             } else {
-                if (MASK & 1) __builtin_nontemporal_store(f4v{s4[0], s4[1], s4[2], s4[3]}, reinterpret_cast<f4v*>(pl.sum + cell));
-                if (MASK & 2) __builtin_nontemporal_store(f4v{w4[0], w4[1], w4[2], w4[3]}, reinterpret_cast<f4v*>(pl.wgt + cell));
+                if (MASK & 1) __builtin_nontemporal_store(pcr_f4v{s4[0], s4[1], s4[2], s4[3]}, reinterpret_cast<pcr_f4v*>(pl.sum + cell));
+                if (MASK & 2) __builtin_nontemporal_store(pcr_f4v{w4[0], w4[1], w4[2], w4[3]}, reinterpret_cast<pcr_f4v*>(pl.wgt + cell));
                 if (MASK & 4) *reinterpret_cast<float4*>(pl.mx + cell) = make_float4(x4[0], x4[1], x4[2], x4[3]);
                 if (MASK & 8) *reinterpret_cast<float4*>(pl.mn + cell) = make_float4(m4[0], m4[1], m4[2], m4[3]);
             }
@@ -912,7 +911,7 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
                         f = is_sum ? s4[k] : f;
                         v[k] = ((q.live >> (live_shift + k)) & 1u) ? f : NAN;
                     }
-                    __builtin_nontemporal_store(f4v{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4v*>(band[o] + cell));
+                    __builtin_nontemporal_store(pcr_f4v{v[0], v[1], v[2], v[3]}, reinterpret_cast<pcr_f4v*>(band[o] + cell));
                 }
             }
         }
@@ -953,9 +952,9 @@ k_tile_accum(GridDev g, BinGeom b, PlanesDev pl, const uint2* __restrict__ recor
             }
             // (non-temporal, as above)
             if ((MASK & 1) && n1) { g1.x += a1.x; g1.y += a1.y; g1.z += a1.z; g1.w += a1.w;
-                __builtin_nontemporal_store(f4v{g1.x, g1.y, g1.z, g1.w}, reinterpret_cast<f4v*>(pl.sum + cell)); }
+                __builtin_nontemporal_store(pcr_f4v{g1.x, g1.y, g1.z, g1.w}, reinterpret_cast<pcr_f4v*>(pl.sum + cell)); }
             if ((MASK & 2) && n2) { g2.x += a2.x; g2.y += a2.y; g2.z += a2.z; g2.w += a2.w;
-                __builtin_nontemporal_store(f4v{g2.x, g2.y, g2.z, g2.w}, reinterpret_cast<f4v*>(pl.wgt + cell)); }
+                __builtin_nontemporal_store(pcr_f4v{g2.x, g2.y, g2.z, g2.w}, reinterpret_cast<pcr_f4v*>(pl.wgt + cell)); }
             if ((MASK & 4) && n4) { g4.x = fmaxf(g4.x, a4.x); g4.y = fmaxf(g4.y, a4.y); g4.z = fmaxf(g4.z, a4.z); g4.w = fmaxf(g4.w, a4.w); *reinterpret_cast<float4*>(pl.mx + cell) = g4; }
             if ((MASK & 8) && n8) { g8.x = fminf(g8.x, a8.x); g8.y = fminf(g8.y, a8.y); g8.z = fminf(g8.z, a8.z); g8.w = fminf(g8.w, a8.w); *reinterpret_cast<float4*>(pl.mn + cell) = g8; }
         }

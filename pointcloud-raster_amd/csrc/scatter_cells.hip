@@ -110,7 +110,6 @@ struct CellGauss {
     int cap;                       // records per work item
 };
 
-typedef float pcr_f2 __attribute__((ext_vector_type(2)));
 
 // lane i <- lane i - 1 (lane 0 <- 0): the compiler folds it into v_add_f32_dpp wave_shr:1
 __device__ __forceinline__ float wave_shr1(float v) {

@@ -53,7 +53,6 @@ __device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) &
 // ---- binning: the shared front-end (bin16.hpp) on records {local cell, value, s'x, s'y} -----------------------
 // s' = the reference's f32 sub-cell offset, recentred to [-1/2, 1/2).  A point whose value is not finite, or whose
 // centre cell is not the routed cell (grid edge), cannot be represented by moments: it goes to the list.
-typedef float pcr_f2 __attribute__((ext_vector_type(2)));
 
 struct MomentMaker {
     static constexpr bool kVectorGeometry = false;     // k_b16_scatter: grid and bin geometry in vector registers (bin16.hpp)
@@ -390,7 +389,6 @@ k_conv_col(GridDev g, int K, int r, int yblocks_per_tile, const float* __restric
 // the FMA rate.  Operand lane maps (one f32 per lane): A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15],
 // C[row = 4 (lane >> 4) + reg][col = lane & 15].
 // LDS rows are 80 floats apart: the four source rows a B operand touches then fall on disjoint banks.
-typedef float pcr_f4 __attribute__((ext_vector_type(4)));
 constexpr int kColStride = 80;
 
 // Staging (NI > 0; needs W % 4 == 0): a lane moves FOUR consecutive columns of one row per load (16-byte global
@@ -422,9 +420,9 @@ k_conv_col_mfma(GridDev g, int K, int r, int yblocks_per_tile, const float* __re
     const int tap_w = 2 * r + 1 + 2 * kPad;
     float* lds_taps = lds_f + nalloc * kColStride;
     for (int i = threadIdx.x; i < (K + 1) * tap_w; i += kT) lds_taps[i] = taps_y[i];
-    pcr_f4 acc[4];
+    pcr_f4v acc[4];
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb) acc[cb] = pcr_f4{0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < 4; ++cb) acc[cb] = pcr_f4v{0.f, 0.f, 0.f, 0.f};
     const bool xin = x < g.W;
     const bool active = Y0 + wave * 16 < t_hi;
     const int j16 = lane & 15, kg = lane >> 4;
@@ -433,7 +431,7 @@ k_conv_col_mfma(GridDev g, int K, int r, int yblocks_per_tile, const float* __re
     const int srow0 = 4 * wave + kg, c4 = 4 * j16;
     const bool cin = blockIdx.x * 64 + c4 < g.W;       // W % 4 == 0: the four columns are inside together
     const int lo_s = t_lo - (Y0 - r), hi_s = min(t_hi - (Y0 - r), nsrc);       // valid LDS rows [lo_s, hi_s)
-    pcr_f4 pre[NI > 0 ? NI : 1];
+    pcr_f4v pre[NI > 0 ? NI : 1];
     auto issue = [&](int pair) {                       // moment planes are stored in the order the pairs are visited
         const float* __restrict__ base = mom + (int64_t)pair * plane_stride + (int64_t)(Y0 - r + srow0) * g.W +
                                          (blockIdx.x * 64 + c4);
@@ -441,7 +439,7 @@ k_conv_col_mfma(GridDev g, int K, int r, int yblocks_per_tile, const float* __re
         for (int it = 0; it < NI; ++it) {
             const int sr = srow0 + kRowsIt * it;
             const bool ok = cin && sr >= lo_s && sr < hi_s;
-            pre[it] = ok ? *reinterpret_cast<const pcr_f4*>(base + (int64_t)kRowsIt * it * g.W) : pcr_f4{0.f, 0.f, 0.f, 0.f};
+            pre[it] = ok ? *reinterpret_cast<const pcr_f4v*>(base + (int64_t)kRowsIt * it * g.W) : pcr_f4v{0.f, 0.f, 0.f, 0.f};
         }
     };
     // One workgroup walks ALL pairs (k, l), l = 0..K-k, of its 64 x 64 outputs: the load of the next plane is always
@@ -455,7 +453,7 @@ k_conv_col_mfma(GridDev g, int K, int r, int yblocks_per_tile, const float* __re
             float* dst = lds_f + srow0 * kColStride + c4;
 #pragma unroll
             for (int it = 0; it < NI; ++it)
-                if (srow0 + kRowsIt * it < nalloc) *reinterpret_cast<pcr_f4*>(dst + kRowsIt * it * kColStride) = pre[it];
+                if (srow0 + kRowsIt * it < nalloc) *reinterpret_cast<pcr_f4v*>(dst + kRowsIt * it * kColStride) = pre[it];
         } else {
             const float* __restrict__ plane = mom + (int64_t)pair * plane_stride;
             const int xc = xin ? x : 0;
@@ -521,7 +519,7 @@ k_conv_col_mfma(GridDev g, int K, int r, int yblocks_per_tile, const float* __re
             for (int cb = 0; cb < 4; ++cb) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) ob[q * kColStride + cb * 16] = acc[cb][q];
-                acc[cb] = pcr_f4{0.f, 0.f, 0.f, 0.f};
+                acc[cb] = pcr_f4v{0.f, 0.f, 0.f, 0.f};
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();

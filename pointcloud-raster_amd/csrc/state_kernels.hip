@@ -164,8 +164,7 @@ k_finalize_group(GridDev g, PlanesDev pl, unsigned need, const uint32_t* __restr
             for (int k = 0; k < VEC; ++k) v[k] = live[k] ? finalize_rt(fo.rtype[o], s[k], w[k], mx[k], mn[k]) : NAN;
             if (VEC == 4) {
                 // finished bands: written once, read by nobody on the device (C2 step -1.5 % against plain stores)
-                typedef float f4v __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(f4v{v[0], v[1], v[2], v[3]}, reinterpret_cast<f4v*>(fo.out[o] + oi));
+                __builtin_nontemporal_store(pcr_f4v{v[0], v[1], v[2], v[3]}, reinterpret_cast<pcr_f4v*>(fo.out[o] + oi));
             } else fo.out[o][oi] = v[0];
         }
     }

@@ -25,9 +25,8 @@ using detail::same_glyph;
 Pipeline::Impl::~Impl() {
     if (engine) pcr_hip_engine_destroy(engine);
     groups.clear();
-    d_bands.clear();
-    d_filled.clear();
-    for (auto& b : d_ground) b.release();
+    bands.clear();
+    band_buffers.clear();
     d_ground_work.release();
     staging.clear();
     result.reset();
@@ -198,57 +197,42 @@ Status Pipeline::Impl::init() {
 int Pipeline::Impl::own_plane(ReductionType t) {
     return t == ReductionType::Sum ? 0 : t == ReductionType::Count ? 1 : t == ReductionType::Max ? 2 : t == ReductionType::Min ? 3 : -1;
 }
-// The RAW band of output r: what the finalize kernels and a defining scatter store, and what carries deferred planes.
-float* Pipeline::Impl::band_device(size_t r) {
-    return cfg.result_location == MemoryLocation::Device && !filled(r) ? result->band_f32((int)r) : static_cast<float*>(d_bands[r].data());
-}
-// fill_nodata_radius: the bands of these outputs leave the pipeline filled.  The fill reads the raw band and writes a buffer of
-// its own (filled_band_device), so the raw bands stay what the plane-state rules below take them for; it is no plane-state event.
-bool Pipeline::Impl::filled(size_t r) const { return cfg.fill_nodata_radius > 0 && detail::fills_nodata(outputs[r].type); }
-// The band of output r as it leaves the pipeline: result(), result_band_device(), the GeoTIFF and its overview levels.
-float* Pipeline::Impl::filled_band_device(size_t r) {
-    if (!filled(r)) return band_device(r);
-    return cfg.result_location == MemoryLocation::Device ? result->band_f32((int)r) : static_cast<float*>(d_filled[r].data());
-}
-// PipelineConfig::ground: the DTM (i = 0) and the hag band (i = 1) as they leave the pipeline; raw: the DTM as the filter stores
-// it, which fill_nodata_radius fills into the one that leaves.  Like the filled bands they live in buffers of their own: the
-// filter reads a raw band and is no plane-state event.
-float* Pipeline::Impl::ground_band_device(int i, bool raw) {
-    if (raw && cfg.fill_nodata_radius > 0) return static_cast<float*>(d_ground[0].data());
-    return cfg.result_location == MemoryLocation::Device ? result->band_f32((int)outputs.size() + i)
-                                                         : static_cast<float*>(d_ground[1 + i].data());
+// Band b of the table leaves the pipeline, behind whatever stored its raw self on the pipeline's stream: a filled band is
+// filled from `raw` into `out`, and a host-resident result gets its copy of `out`.
+Status Pipeline::Impl::band_leaves(size_t b, bool* enqueued) {
+    const int rows = own_rows(), W = hg.width;
+    const LeavingBand& lb = bands[b];
+    Status s = Status::success();
+    if (lb.out != lb.raw) {
+        *enqueued = true;
+        s = detail::hip_status(pcr_hip_fill_nodata(lb.raw, lb.out, W, rows, W, W, cfg.fill_nodata_radius, stream));
+        if (!s.ok()) return s;
+    }
+    if (cfg.result_location != MemoryLocation::Device) {
+        *enqueued = true;
+        s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)b), lb.out, (size_t)rows * W * sizeof(float), stream));
+    }
+    return s;
 }
 // Behind the finalize kernels and the fills of every group, on the pipeline's stream: the filter on the RAW source band, the
-// DTM filled like a Min band, hag from the top band and the DTM as they leave the pipeline.
+// DTM leaves (filled like a Min band), hag from the top band and the DTM as they leave the pipeline, hag leaves.
 Status Pipeline::Impl::finalize_ground(bool* enqueued) {
     if (!ground.on) return Status::success();
     const int rows = own_rows(), W = hg.width;
+    const size_t dtm = outputs.size(), hag = dtm + 1;
     size_t bytes = 0;
     Status s = detail::hip_status(pcr_hip_ground_filter_work_bytes(W, rows, &bytes));
     if (!s.ok()) return s;
     if (d_ground_work.bytes() < bytes && !(s = d_ground_work.allocate(bytes, MemoryLocation::Device)).ok()) return s;
     *enqueued = true;
-    s = detail::hip_status(pcr_hip_ground_filter(band_device((size_t)ground.source), ground_band_device(0, true), W, rows, W, W,
+    s = detail::hip_status(pcr_hip_ground_filter(bands[(size_t)ground.source].raw, bands[dtm].raw, W, rows, W, W,
                                                  (int)ground.radii.size(), ground.radii.data(), ground.thresholds.data(),
                                                  d_ground_work.data(), d_ground_work.bytes(), stream));
     if (!s.ok()) return s;
-    if (cfg.fill_nodata_radius > 0) {
-        s = detail::hip_status(pcr_hip_fill_nodata(ground_band_device(0, true), ground_band_device(0), W, rows, W, W,
-                                                   cfg.fill_nodata_radius, stream));
-        if (!s.ok()) return s;
-    }
-    if (ground.top >= 0) {
-        s = detail::hip_status(pcr_hip_band_difference(filled_band_device((size_t)ground.top), ground_band_device(0),
-                                                       ground_band_device(1), W, rows, W, W, W, stream));
-        if (!s.ok()) return s;
-    }
-    if (cfg.result_location != MemoryLocation::Device)
-        for (int i = 0; i < ground.extra_bands(); ++i) {
-            s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)outputs.size() + i), ground_band_device(i),
-                                                      (size_t)rows * W * sizeof(float), stream));
-            if (!s.ok()) return s;
-        }
-    return Status::success();
+    if (!(s = band_leaves(dtm, enqueued)).ok() || ground.top < 0) return s;
+    s = detail::hip_status(pcr_hip_band_difference(bands[(size_t)ground.top].out, bands[dtm].out, bands[hag].raw, W, rows, W, W, W,
+                                                   stream));
+    return s.ok() ? band_leaves(hag, enqueued) : s;
 }
 Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
     return detail::hip_status(pcr_hip_engine_tile_touched(engine, d, tx, ty));
@@ -271,7 +255,7 @@ bool Pipeline::Impl::offer_bands(size_t gi) {
         if (outputs[r].group != (int)gi) continue;
         if (n == PCR_HIP_MAX_FINALIZE_OUTPUTS) return false;
         types[n] = static_cast<int>(outputs[r].type);
-        dsts[n++] = band_device(r);
+        dsts[n++] = bands[r].raw;
         if (own_plane(outputs[r].type) >= 0) own |= kPlaneBits[own_plane(outputs[r].type)];
     }
     if (n == 0) return false;
@@ -305,7 +289,7 @@ Status Pipeline::Impl::restore_planes(size_t gi, bool* enqueued) {
     const float* src[4] = {nullptr, nullptr, nullptr, nullptr};
     for (size_t r = 0; r < outputs.size(); ++r) {
         const int p = outputs[r].group == (int)gi ? own_plane(outputs[r].type) : -1;
-        if (p >= 0 && (m & kPlaneBits[p])) src[p] = band_device(r);
+        if (p >= 0 && (m & kPlaneBits[p])) src[p] = bands[r].raw;
     }
     uint32_t* d_touched = nullptr;
     Status s = touched_flags(&d_touched);
@@ -468,9 +452,8 @@ Status Pipeline::Impl::merge_touched(const void* d_union) {
 }
 
 const float* Pipeline::Impl::result_band_device(int band) {
-    if (!finalized || !result || band < 0 || band >= (int)outputs.size() + ground.extra_bands()) return nullptr;
-    if (band >= (int)outputs.size()) return ground_band_device(band - (int)outputs.size());
-    return filled_band_device((size_t)band);
+    if (!finalized || !result || band < 0 || band >= (int)bands.size()) return nullptr;
+    return bands[(size_t)band].out;
 }
 
 Status Pipeline::Impl::synchronize() { return detail::hip_status(pcr_hip_stream_synchronize(stream)); }
@@ -786,52 +769,44 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     return Status::success();
 }
 
-// The result grid (and, for a host-resident result, its device-side band buffers) is allocated
+// The result grid, the table of leaving bands and the device buffers behind it are allocated
 // once, at create: finalize only launches kernels.
 Status Pipeline::Impl::allocate_result() {
     const int rows = own_rows();
     const int W = hg.width;
-    std::vector<BandDesc> bands;
+    std::vector<BandDesc> descs;
     for (const auto& o : outputs) {
         BandDesc b;
         b.name = o.band_name;
         b.dtype = DataType::Float32;
         b.is_state = false;
-        bands.push_back(b);
+        descs.push_back(b);
     }
-    if (bands.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
-    detail::append_ground_bands(ground, bands);
+    if (descs.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+    detail::append_ground_bands(ground, descs);
     if (rows <= 0) { result.reset(); return Status::success(); }
     const bool on_device = cfg.result_location == MemoryLocation::Device;
-    result = on_device ? Grid::create(W, rows, bands, MemoryLocation::Device)
-                       : Grid::create_host_page_locked(W, rows, bands);
+    result = on_device ? Grid::create(W, rows, descs, MemoryLocation::Device)
+                       : Grid::create_host_page_locked(W, rows, descs);
     if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
-    if (!on_device) {
-        d_bands.resize(outputs.size());
-        for (auto& b : d_bands) {
-            Status s = b.allocate((size_t)rows * W * sizeof(float), MemoryLocation::Device);
-            if (!s.ok()) return s;
-        }
+    // the table of leaving bands and the buffers behind it: the rule (device_pipeline.h, LeavingBand) applied once
+    const size_t n_out = outputs.size();
+    bands.assign(n_out + (size_t)ground.extra_bands(), LeavingBand{});
+    band_buffers.clear();
+    Status s = Status::success();
+    auto owned = [&]() -> float* {
+        if (!s.ok()) return nullptr;
+        band_buffers.emplace_back();
+        s = band_buffers.back().allocate((size_t)rows * W * sizeof(float), MemoryLocation::Device);
+        return static_cast<float*>(band_buffers.back().data());
+    };
+    for (size_t b = 0; b < bands.size() && s.ok(); ++b) {
+        const bool filled = cfg.fill_nodata_radius > 0 && (b < n_out ? detail::fills_nodata(outputs[b].type) : b == n_out);
+        float* const grid_band = on_device ? result->band_f32((int)b) : nullptr;
+        bands[b].raw = on_device && !filled ? grid_band : owned();
+        bands[b].out = !filled ? bands[b].raw : on_device ? grid_band : owned();
     }
-    // fill_nodata_radius: a filled output has a raw band and a filled one.  Host result: the filled one is a further device
-    // buffer, which the copy to the host reads.  Device result: the result grid's band is the filled one, the raw band lives
-    // in d_bands.  (radius 0: no output is filled, nothing is allocated)
-    for (size_t r = 0; r < outputs.size(); ++r) {
-        if (!filled(r)) continue;
-        std::vector<detail::Buffer>& extra = on_device ? d_bands : d_filled;
-        if (extra.size() < outputs.size()) extra.resize(outputs.size());
-        Status s = extra[r].allocate((size_t)rows * W * sizeof(float), MemoryLocation::Device);
-        if (!s.ok()) return s;
-    }
-    // ground: the bands that leave the pipeline are the result grid's (Device) or two more device buffers (Host); a DTM that
-    // leaves filled has its raw self in a buffer besides.  (off: nothing is allocated)
-    for (int i = 0; i < 3 && ground.on; ++i) {
-        const bool wanted = i == 0 ? cfg.fill_nodata_radius > 0 : !on_device && i - 1 < ground.extra_bands();
-        if (!wanted) continue;
-        Status s = d_ground[i].allocate((size_t)rows * W * sizeof(float), MemoryLocation::Device);
-        if (!s.ok()) return s;
-    }
-    return Status::success();
+    return s;
 }
 
 Status Pipeline::Impl::finalize(bool wait) {
@@ -890,32 +865,20 @@ Status Pipeline::Impl::finalize(bool wait) {
             if (outputs[r].group != (int)gi) continue;
             if (groups[gi].select) {
                 s = detail::hip_status(pcr_hip_finalize_select(&hg, static_cast<const uint64_t*>(groups[gi].packed.data()), d_touched,
-                                                               band_device(r), stream));
+                                                               bands[r].raw, stream));
                 if (!s.ok()) return s;
                 enqueued = true;
                 bands_of.push_back(r);
                 continue;
             }
             types.push_back(static_cast<int>(outputs[r].type));
-            dsts.push_back(band_device(r));
+            dsts.push_back(bands[r].raw);
             bands_of.push_back(r);
             if (types.size() == PCR_HIP_MAX_FINALIZE_OUTPUTS && !(s = flush()).ok()) return s;
         }
         if (!(s = flush()).ok()) return s;
-        for (size_t r : bands_of) {
-            if (filled(r)) {                 // behind the band's finalize kernel (or the scatter that stored it), raw band -> filled band
-                enqueued = true;
-                s = detail::hip_status(pcr_hip_fill_nodata(band_device(r), filled_band_device(r), W, rows, W, W,
-                                                           cfg.fill_nodata_radius, stream));
-                if (!s.ok()) return s;
-            }
-            if (!on_device) {
-                enqueued = true;
-                s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)r), filled_band_device(r),
-                                                          (size_t)rows * W * sizeof(float), stream));
-                if (!s.ok()) return s;
-            }
-        }
+        for (size_t r : bands_of)            // behind the band's finalize kernel (or the scatter that stored it)
+            if (!(s = band_leaves(r, &enqueued)).ok()) return s;
     }
     if (!(s = finalize_ground(&enqueued)).ok()) return s;
     // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
@@ -927,13 +890,9 @@ Status Pipeline::Impl::finalize(bool wait) {
         if (n > 0) {
             std::vector<const float*> dev_bands;
             std::vector<BandDesc> descs;
-            for (size_t r = 0; r < outputs.size(); ++r) {
-                dev_bands.push_back(filled_band_device(r));
-                descs.push_back(result->band_desc((int)r));
-            }
-            for (int i = 0; i < ground.extra_bands(); ++i) {
-                dev_bands.push_back(ground_band_device(i));
-                descs.push_back(result->band_desc((int)outputs.size() + i));
+            for (size_t b = 0; b < bands.size(); ++b) {
+                dev_bands.push_back(bands[b].out);
+                descs.push_back(result->band_desc((int)b));
             }
             std::vector<std::unique_ptr<Grid>> d_levels;
             s = detail::build_overviews_device(dev_bands, W, rows, descs, n, detail::overview_mode(out_opt.overview_resampling),

@@ -73,12 +73,21 @@ struct Pipeline::Impl {
     bool own_stream = false;
     std::vector<Group> groups;
     std::vector<Output> outputs;
-    std::vector<detail::Buffer> d_bands;     // finalized bands on the device (result_location == Host; Device: the raw bands
-                                             // of the outputs fill_nodata_radius fills, whose filled band is the result grid's)
-    std::vector<detail::Buffer> d_filled;    // result_location == Host: the filled bands of those outputs
+    // Which memory a band is.  One row per band of the result grid -- the outputs, then the DTM, then the hag band -- built
+    // once by allocate_result(); everything else only reads it.  A band is FILLED iff fill_nodata_radius > 0 and it is an
+    // output with fills_nodata(type), or it is the DTM; the hag band never is.  Device result: `out` is the result grid's
+    // band, `raw` is `out` unless the band is filled, then an owned buffer.  Host result: `raw` is an owned buffer, `out` is
+    // `raw` unless the band is filled, then a second owned buffer.  The fill and the ground filter read a raw band and write
+    // another buffer, so the raw bands stay what the plane-state rules take them for: the table is no plane-state event.
+    struct LeavingBand {
+        float* raw = nullptr;                // device: what the finalize kernels, a defining scatter or the ground filter store;
+                                             // for an output, also what carries its deferred planes
+        float* out = nullptr;                // device: the band as it leaves the pipeline: result(), result_band_device(), the
+                                             // GeoTIFF and its overview levels (== raw unless it is filled)
+    };
+    std::vector<LeavingBand> bands;
+    std::vector<detail::Buffer> band_buffers;    // the owned buffers behind the table; a buffer's role is its place in the table
     detail::GroundPlan ground;               // PipelineConfig::ground, planned at init
-    detail::Buffer d_ground[3];              // its bands: [0] the raw DTM where the DTM leaves the pipeline filled; [1], [2] the DTM
-                                             // and the hag band as they leave it (result_location == Host; Device: the result grid's)
     detail::Buffer d_ground_work;            // its workspace, allocated by the first finalize, grow-only
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
@@ -138,10 +147,7 @@ struct Pipeline::Impl {
     // ---- the rest
     int own_rows() const { return hg.own_row1 - hg.own_row0; }
     static int own_plane(ReductionType t);
-    float* band_device(size_t r);
-    bool filled(size_t r) const;
-    float* filled_band_device(size_t r);
-    float* ground_band_device(int i, bool raw = false);      // i: 0 the DTM, 1 the hag band
+    Status band_leaves(size_t b, bool* enqueued);
     Status finalize_ground(bool* enqueued);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
     bool offer_bands(size_t gi);

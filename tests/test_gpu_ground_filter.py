@@ -247,6 +247,36 @@ def test_pipeline_equals_the_host_engine(pipe_case, location, wait, radius):
             M.bits_equal(got[b], raw[1][b], f"raw band {b} is what a pipeline without ground holds")
 
 
+@pytest.fixture(scope="module")
+def no_top_case(pipe_case):
+    c1, c2 = pipe_case[:2]
+    return c1, c2, {r: host_pipeline_bands([c1, c2], radius=r, top=False) for r in (0, RP)}
+
+
+@pytest.mark.parametrize("radius", [0, RP])
+@pytest.mark.parametrize("location", LOCATIONS)
+def test_pipeline_without_a_top_band_equals_the_host_engine(no_top_case, location, radius):
+    """A ground plan without a top band: one extra band, the DTM, and no hag band behind it.  Min and Max live in their bands
+    as deferred planes after the first ingest, so the second ingest has to find them in the raw bands, not in the filled ones."""
+    c1, c2, want = no_top_case
+    pipe = create(gpu_cfg(location, radius=radius, top=False))
+    A = load_cabi()
+    for k, c in enumerate((c1, c2)):
+        pipe.ingest(c)
+        pipe.finalize()
+        res = pipe.result()
+        assert [res.band_desc(b).name for b in range(res.num_bands())] == list(G.BANDS) + ["dtm"]
+        got = result_bands(pipe)
+        assert len(got) == 4
+        for b in range(4):
+            M.bits_equal(got[b], want[radius][k][b], f"finalize {k + 1}, band {b}")
+            back = np.empty((HP, WP), np.float32)
+            A.check(A.lib().pcr_hip_memcpy_d2h(back.ctypes.data, C.c_void_p(pipe.result_band_device_ptr(b)), back.nbytes, None))
+            A.check(A.lib().pcr_hip_stream_synchronize(None))
+            M.bits_equal(back, want[radius][k][b], f"finalize {k + 1}, result_band_device {b}")
+        assert pipe.result_band_device_ptr(4) == 0
+
+
 def test_state_saved_after_a_filtered_finalize_is_the_plain_state(tmp_path, pipe_case):
     c1, _, want, raw = pipe_case
     pipe = create(gpu_cfg())
