@@ -1,0 +1,853 @@
+"""Operation-sequence fuzz of one pipeline against an exact model (tests/test_sequence_fuzz_host.py on the host engine,
+tests/test_gpu_sequence_fuzz.py on the HIP engine).
+
+build(seed) draws a grid, a set of Point reductions, a finalize plan and a SEQUENCE of operations on one pipeline: ingests of
+every kind, finalizes between them, plane and touched-flag pointers handed out (and written through), flag unions, checkpoints
+that a new pipeline with another plan or flavour resumes from (or that a later load_state lays over whatever the state is
+then).  check_sequence() runs the sequence and compares, after every
+finalize, every band the pipeline hands out with the Model below, bit for bit and NaN payloads included.  No tolerance is
+needed because of how the values are chosen: channel `a` holds multiples of 1/8, channel `b` small integers, and the generator
+itself checks that no cell's sum of magnitudes reaches 2^24 units over all clouds of the case -- every partial sum is exact in
+binary32 in any order, Average is one binary32 division of two exact numbers, Max / Min / MostRecent select.
+
+The generator uses NumPy only (a seed means the same case on every machine).  The model uses no engine code except the host
+twins of the finishing steps, which the CPU suite holds to their own NumPy models: pcr.ground_filter, pcr.fill_nodata,
+overviews_common.pyramid; and the `.pcrt` writer for the reference checkpoint."""
+import filecmp
+import os
+
+import numpy as np
+
+FLT_MAX = np.float32(3.4028234663852886e38)
+TYPES = ("Sum", "Count", "Average", "Max", "Min", "MostRecent")
+MAX_FINALIZE_OUTPUTS = 8                   # PCR_HIP_MAX_FINALIZE_OUTPUTS: a larger group flushes in the middle
+EXACT_UNITS = 1 << 23                      # the clouds stay below this per cell and channel (units: 1/8 for `a`, 1 for `b`)
+PATCH_UNITS = 64                           # a plane patch adds at most this many units to a cell: k/8 on an `a` plane, an integer on a `b` or Count plane
+SPLIT_RECORDS = 1 << 17                    # kPointItemRecords: the scan splits a bin that holds more records
+HOT_W, HOT_H = 128, 56                     # every Point LDS tile is 128 columns wide and at least 56 rows tall (20 B per cell), from cell (0, 0)
+FILL_TYPES = ("Average", "Max", "Min", "MostRecent")
+OPS8 = ("Equal", "NotEqual", "Less", "LessEqual", "Greater", "GreaterEqual", "InSet", "NotInSet")
+# planes a reduction needs / its checkpoint holds, as slots (0 sum, 1 count, 2 max, 3 min; MostRecent: 0 value, 1 timestamp)
+PLANES_OF = {"Sum": (0,), "Count": (1,), "Max": (2,), "Min": (3,), "Average": (0, 1), "MostRecent": (0, 1)}
+
+# Seeds of the suite.  (a failing seed of a soak joins the list with a one-line comment)
+# 0..31, and the further seeds that the situations and the marks of tests/test_sequence_fuzz_host.py needed more of; 75 is a
+# second seed on which import_window without its bands_stale() fails
+DEFAULT_SEEDS = list(range(32)) + [47, 48, 49, 51, 54, 64, 75, 76]
+
+
+def seeds_from_env(name="PCR_SEQ_FUZZ_SEEDS"):
+    env = os.environ.get(name)
+    if env and ":" in env:
+        a, b = env.split(":")
+        return list(range(int(a), int(b)))
+    if env:
+        return [int(v) for v in env.split(",")]
+    return list(DEFAULT_SEEDS)
+
+
+# ---- the generator (NumPy only) ------------------------------------------------------------------------------------------------
+def cells_of(g, x, y):
+    """Flat cell of every point by the oracle's world_to_cell (inclusive bounds, floor of the TRUE binary64 division, clamp),
+    -1 outside the bounds.  The same IEEE operations as oracle/pcr_oracle.c, vectorised; the host test checks it against
+    pcr_oracle_py.world_to_cell point by point on a sample."""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    ok = (x >= g["min_x"]) & (x <= g["max_x"]) & (y >= g["min_y"]) & (y <= g["max_y"])
+    col = np.clip(np.floor((x - g["min_x"]) / g["cs"]), 0, g["W"] - 1).astype(np.int64)
+    row = np.clip(np.floor((y - g["max_y"]) / -g["cs"]), 0, g["H"] - 1).astype(np.int64)
+    return np.where(ok, row * g["W"] + col, -1)
+
+
+def groups_of(specs):
+    """Accumulation groups as every engine forms them: same value channel (MostRecent: and timestamp channel, a group of its own)."""
+    groups = []
+    for i, s in enumerate(specs):
+        key = (s["ch"], s["type"] == "MostRecent")
+        for gr in groups:
+            if gr["key"] == key:
+                break
+        else:
+            gr = dict(key=key, ch=s["ch"], select=key[1], slots=set(), outs=[])
+            groups.append(gr)
+        gr["slots"].update(PLANES_OF[s["type"]])
+        gr["outs"].append(i)
+        s["group"] = groups.index(gr)
+    return groups
+
+
+def _draw_plan(rng, specs, ooc, big):
+    types = [s["type"] for s in specs]
+    ground = None
+    if "Min" in types:
+        kind = str(rng.choice(["off", "dtm", "hag"], p=[0.4, 0.3, 0.3]))
+        if kind == "hag" and "Max" not in types:
+            kind = "dtm"
+        if kind != "off":
+            ground = dict(source=types.index("Min"), top=types.index("Max") if kind == "hag" else None, maxr=int(rng.choice([4, 8])))
+    out = bool(rng.uniform() < (0.8 if big else 0.3))
+    return dict(fill=int(rng.choice([0, 0, 1, 3, 8])), ground=ground,
+                loc="Host" if ooc else str(rng.choice(["Host", "Device"])), out=out, cog=out and bool(rng.uniform() < (0.9 if big else 0.5)))
+
+
+def _draw_flavour(rng):
+    ooc = bool(rng.uniform() < 0.25)
+    return dict(ooc=ooc, bands=int(rng.choice([2, 3])), host_budget=int(rng.choice([1, 1 << 30])))
+
+
+def _draw_cloud(rng, g, shape, filt=None):
+    W, H, cs = g["W"], g["H"], g["cs"]
+    n = int(rng.integers(1, 60001))
+    if shape == "all":                                           # one cell beyond the bounds, and onto them
+        x, y = rng.uniform(g["min_x"] - cs, g["max_x"] + cs, n), rng.uniform(g["min_y"] - cs, g["max_y"] + cs, n)
+        k = n // 12
+        x[:k] = rng.choice([g["min_x"], g["max_x"]], k)
+        y[k:2 * k] = rng.choice([g["min_y"], g["max_y"]], k)
+    elif shape == "strip":                                       # a few rows
+        y0 = rng.uniform(g["min_y"], g["max_y"])
+        x, y = rng.uniform(g["min_x"], g["max_x"], n), rng.uniform(y0, min(g["max_y"], y0 + 6 * cs), n)
+    elif shape == "cluster":                                     # on a reference-tile corner
+        cx = g["min_x"] + min(g["tw"], W) * cs * int(rng.integers(0, max(1, W // g["tw"]) + 1))
+        cy = g["max_y"] - min(g["th"], H) * cs * int(rng.integers(0, max(1, H // g["th"]) + 1))
+        x, y = rng.normal(cx, 6 * cs, n), rng.normal(cy, 6 * cs, n)
+    elif shape == "outside":
+        x, y = rng.uniform(g["max_x"] + cs, g["max_x"] + 50 * cs, n), rng.uniform(g["min_y"], g["max_y"], n)
+    elif shape == "hot":                                         # > 2^17 points inside the first 128 x 56 cells: one LDS tile of any group
+        n = SPLIT_RECORDS + int(rng.integers(2000, 9000))
+        x = rng.uniform(g["min_x"], g["min_x"] + min(W, HOT_W) * cs, n)
+        y = rng.uniform(g["max_y"] - min(H, HOT_H) * cs, g["max_y"], n)
+    else:                                                        # "empty"
+        n = 0
+        x = y = np.zeros(0)
+    t = rng.integers(0, 6, n).astype(np.float32)                 # many ties
+    if n:
+        idx = rng.integers(0, n, n // 20 + 1)
+        t[idx] = np.array([np.nan, -FLT_MAX], np.float32)[rng.integers(0, 2, len(idx))]
+    cls = rng.integers(0, 4, n).astype(np.float32)
+    if shape == "hot":                                           # the records must reach the bin: classes the filter keeps
+        kept = np.arange(4, dtype=np.float32)[keep_mask(filt, np.arange(4, dtype=np.float32))]
+        cls = kept[rng.integers(0, len(kept), n)]
+    return dict(shape=shape, x=x, y=y, a=(rng.integers(-512, 513, n) / 8.0).astype(np.float32),
+                b=rng.integers(0, 4096, n).astype(np.float32), t=t, cls=cls)
+
+
+def hot_records(case, c):
+    """Records of a cloud that reach the first LDS tile of every group (columns < 128, rows < 56) past the filter and the bounds."""
+    g = case["grid"]
+    cell = cells_of(g, c["x"], c["y"])
+    ok = keep_mask(case["filt"], c["cls"]) & (cell >= 0)
+    return int((ok & (cell // g["W"] < HOT_H) & (cell % g["W"] < HOT_W)).sum())
+
+
+def _thin(c, keep):
+    for k in ("x", "y", "a", "b", "t", "cls"):
+        c[k] = c[k][keep]
+
+
+def build(seed):
+    rng = np.random.default_rng(91000 + seed)
+    # How the sequence opens.  "union": what a row-block shard does -- one sparse cloud, the other ranks' flags merged in, finalize.
+    # "overlay": a checkpoint of an earlier pipeline loaded over the first ingest of a new one.  "hot": the hot spot as the first
+    # ingest of an in-core pipeline that is offered the bands, a blocking finalize behind it.  Else: anything.
+    opening = str(rng.choice(["any", "union", "overlay", "hot"], p=[0.62, 0.14, 0.14, 0.10]))
+    big = bool(rng.uniform() < 0.1)
+    if big:
+        W, H = 520, 512                                          # write_cog's rule yields a level only from 512 cells a side
+    else:
+        W, H = int(rng.integers(33, 301)), int(rng.integers(33, 261))
+        if rng.uniform() < 0.3:
+            W = max(36, W - W % 4)
+    cs = float(rng.choice([0.5, 1.0, 2.0]))
+    min_x, min_y = float(rng.integers(1, 40)) * cs * float(rng.choice([-1.0, 1.0])), float(rng.integers(1, 40)) * cs
+    flavour = _draw_flavour(rng)
+    if opening == "hot":
+        W, flavour = max(36, W - W % 4), dict(flavour, ooc=False)
+    g = dict(W=W, H=H, cs=cs, min_x=min_x, min_y=min_y, max_x=min_x + W * cs, max_y=min_y + H * cs,
+             tw=int(rng.choice([16, 32, 64, 4096])), th=int(rng.choice([16, 48, 64, 4096])))
+    if flavour["ooc"] and H <= g["th"]:                          # out of core: at least two rows of reference tiles
+        g["th"] = 16
+
+    # reductions
+    specs = []
+    wide = bool(rng.uniform() < 0.15)
+    if wide:                                                     # one group with more than 8 outputs
+        specs = [dict(type=str(rng.choice(TYPES[:5])), ch="a") for _ in range(int(rng.integers(9, 11)))]
+    for _ in range(int(rng.integers(0 if wide else 1, 11 - len(specs)))):
+        specs.append(dict(type=str(rng.choice(TYPES, p=[0.15, 0.15, 0.15, 0.15, 0.22, 0.18])), ch=str(rng.choice(["a", "b"]))))
+    order = rng.permutation(len(specs))
+    specs = [specs[i] for i in order]
+    groups = groups_of(specs)
+
+    filt = None
+    if rng.uniform() < 0.4:
+        op = str(rng.choice(OPS8))
+        filt = dict(op=op, value=float(rng.integers(1, 3)), set=[float(v) for v in rng.choice(4, int(rng.integers(1, 4)), replace=False)])
+
+    plan = _draw_plan(rng, specs, flavour["ooc"], big)
+    fwfi = bool(rng.uniform() < 0.8)
+    path = int(rng.choice([0, 1, 2], p=[0.25, 0.15, 0.6]))
+
+    # the sequence
+    n_ops = int(rng.integers(4, 13))
+    writable = [i for i, s in enumerate(specs) if s["type"] in ("Sum", "Count", "Average")]
+    ops, n_ingest, cur_flavour, checkpoints = [], 0, flavour, []
+
+    def tiles(k):
+        tx, ty = -(-W // g["tw"]), -(-H // g["th"])
+        return [(int(rng.integers(0, ty)), int(rng.integers(0, tx))) for _ in range(k)]
+
+    def draw_ingest():
+        how = str(rng.choice(["host", "device", "async_pinned", "async_device", "file"], p=[0.3, 0.25, 0.17, 0.17, 0.11]))
+        return dict(op="ingest", how=how, sync=bool(rng.uniform() < 0.5), chunk_frac=float(rng.choice([0.13, 0.4, 1.0])))
+
+    def draw_planes_write():
+        r = int(rng.choice(writable))
+        slot = int(rng.choice(PLANES_OF[specs[r]["type"]]))
+        h, w = int(rng.integers(1, 21)), int(rng.integers(1, 21))
+        r0, c0 = int(rng.integers(0, H - min(h, H) + 1)), int(rng.integers(0, W - min(w, W) + 1))
+        if slot == 1:                                            # a Count plane: a few more points
+            value = float(rng.integers(1, 4))
+        elif specs[r]["ch"] == "b":                              # the sums of `b` are integers up to 2^23: so is the patch
+            value = float(rng.integers(-PATCH_UNITS, PATCH_UNITS + 1))
+        else:
+            value = float(rng.integers(-PATCH_UNITS, PATCH_UNITS + 1)) / 8.0
+        return dict(op="planes_write", group=specs[r]["group"], slot=slot, rect=(r0, c0, min(h, H), min(w, W)), value=value)
+
+    if opening != "any":                                         # (as a shard runs: the option on, the path left to the engine or binned)
+        fwfi, path = True, int(rng.choice([0, 2]))
+    if opening == "union":
+        ops += [draw_ingest(), dict(op="merge", extra=tiles(int(rng.integers(1, 3)))), dict(op="finalize", wait=bool(rng.uniform() < 0.6))]
+    elif opening == "hot":
+        ops += [dict(draw_ingest(), how=str(rng.choice(["host", "device", "async_pinned", "async_device"]))), dict(op="finalize", wait=True)]
+    elif opening == "overlay":
+        ops += [draw_ingest(), dict(op="checkpoint", then="fresh", plan=None, flavour=None), draw_ingest(), dict(op="reload", of=1),
+                dict(op="finalize", wait=bool(rng.uniform() < 0.6))]
+        checkpoints.append(1)
+    elif rng.uniform() < 0.2:                                    # a pointer handed out before the first ingest
+        ops.append(dict(op="flags", readonly=False, extra=tiles(int(rng.integers(0, 2)))))
+    elif rng.uniform() < 0.1:
+        ops.append(dict(op="planes_read"))
+    n_ingest = sum(o["op"] == "ingest" for o in ops)
+    n_ops = min(12, max(n_ops, len(ops) + 2))
+    while len(ops) < n_ops - 1:
+        prev = ops[-1]["op"] if ops else None
+        fresh = prev == "checkpoint" and ops[-1]["then"] == "fresh"
+        if n_ingest == 0 or fresh or (prev == "checkpoint" and rng.uniform() < 0.6):
+            kind = "ingest"
+        elif checkpoints and rng.uniform() < (0.6 if len(ops) > 1 and ops[-2]["op"] == "checkpoint" and ops[-2]["then"] == "fresh" else 0.06):
+            kind = "reload"                                      # an earlier checkpoint (of any pipeline of the case) laid over the state
+        elif prev == "ingest":                                   # what may come between an ingest and its finalize
+            kind = str(rng.choice(["finalize", "ingest", "planes_read", "planes_write", "flags_ro", "flags_rw", "merge", "checkpoint"],
+                                  p=[0.4, 0.1, 0.1, 0.1, 0.05, 0.05, 0.08, 0.12]))
+        else:
+            kind = str(rng.choice(["finalize", "ingest", "planes_read", "planes_write", "flags_ro", "flags_rw", "merge", "checkpoint"],
+                                  p=[0.2, 0.4, 0.04, 0.07, 0.04, 0.04, 0.11, 0.1]))
+        if kind == "ingest":
+            ops.append(draw_ingest())
+            n_ingest += 1
+        elif kind == "finalize":
+            ops.append(dict(op="finalize", wait=bool(rng.uniform() < 0.6)))
+        elif kind == "planes_write" and writable:
+            ops.append(draw_planes_write())
+        elif kind in ("planes_read", "planes_write"):
+            ops.append(dict(op="planes_read"))
+        elif kind in ("flags_ro", "flags_rw"):
+            ops.append(dict(op="flags", readonly=kind == "flags_ro", extra=[] if kind == "flags_ro" else tiles(int(rng.integers(0, 2)))))
+        elif kind == "merge":
+            ops.append(dict(op="merge", extra=tiles(int(rng.integers(1, 3)))))
+        elif kind == "reload":
+            ops.append(dict(op="reload", of=int(checkpoints[-1] if rng.uniform() < 0.7 else rng.choice(checkpoints))))
+        else:
+            then = str(rng.choice(["go_on", "resume", "load", "fresh"], p=[0.25, 0.32, 0.25, 0.18]))
+            o = dict(op="checkpoint", then=then, plan=None, flavour=None)
+            if then != "go_on":                                  # the new pipeline: maybe another flavour, maybe another plan
+                if rng.uniform() < 0.4:
+                    o["flavour"] = dict(cur_flavour, ooc=not cur_flavour["ooc"] and H > g["th"])
+                    cur_flavour = o["flavour"]
+                if rng.uniform() < 0.6:
+                    o["plan"] = _draw_plan(rng, specs, cur_flavour["ooc"], big)
+            checkpoints.append(len(ops))
+            ops.append(o)
+    ops.append(dict(op="finalize", wait=bool(rng.uniform() < 0.6)))
+
+    # clouds: one per ingest, thinned where a cell's sums would leave the exact range
+    hot = bool(rng.uniform() < 0.12)
+    shapes = [str(rng.choice(["all", "strip", "cluster", "outside", "empty"], p=[0.45, 0.2, 0.2, 0.08, 0.07])) for _ in range(n_ingest)]
+    if shapes[0] in ("outside", "empty") and rng.uniform() < 0.7:
+        shapes[0] = "all"
+    if opening == "union":
+        shapes[0] = str(rng.choice(["strip", "cluster"]))
+    if opening == "hot":
+        shapes[0] = "hot"
+    if hot:
+        shapes[int(rng.integers(0, n_ingest))] = "hot"
+    clouds = []
+    units_a, units_b = np.zeros(W * H), np.zeros(W * H)
+    for shape in shapes:
+        c = _draw_cloud(rng, g, shape, filt)
+        while True:
+            cell = cells_of(g, c["x"], c["y"])
+            m = cell >= 0
+            ua = units_a + np.bincount(cell[m], np.abs(c["a"][m].astype(np.float64)) * 8.0, W * H)
+            ub = units_b + np.bincount(cell[m], c["b"][m].astype(np.float64), W * H)
+            if max(ua.max(), ub.max()) < EXACT_UNITS:
+                break
+            _thin(c, np.arange(len(c["x"])) % 2 == 0)            # (a cloud that would break the condition is thinned)
+        units_a, units_b = ua, ub
+        clouds.append(c)
+    # the condition on the inputs: every sum of every cell is exact in binary32, in any order -- the plane patches included
+    # (units of 1/8 on an `a` plane, of 1 on a `b` plane, like the clouds'; a Count never exceeds the points of a cell)
+    patched = PATCH_UNITS * sum(o["op"] == "planes_write" for o in ops)
+    assert units_a.max() + patched < 1 << 24 and units_b.max() + patched < 1 << 24
+    k = 0
+    for o in ops:
+        if o["op"] == "ingest":
+            o["cloud"] = k
+            if len(clouds[k]["x"]) == 0 and o["how"] != "host":   # (an empty cloud has no file and no device copy)
+                o["how"] = "host"
+            k += 1
+
+    case = dict(seed=seed, grid=g, specs=specs, groups=groups, filt=filt, plan=plan, flavour=flavour, fwfi=fwfi, path=path,
+                ops=ops, clouds=clouds, big=big, wide=wide)
+    first = clouds[next(o for o in ops if o["op"] == "ingest")["cloud"]]
+    offered = _first_ingest_is_offered(case)
+    case["marked"] = offered and first["shape"] != "hot"
+    # ... or is offered them and splits a bin, so that the device's done word says no: the blocking finalize behind it reads 0
+    case["split_first"] = offered and opening == "hot" and hot_records(case, first) > SPLIT_RECORDS
+    return case
+
+
+def keep_mask(filt, cls):
+    if filt is None:
+        return np.ones(len(cls), bool)
+    v, op = np.float32(filt["value"]), filt["op"]
+    if op in ("InSet", "NotInSet"):
+        inside = np.isin(cls, np.array(filt["set"], np.float32))
+        return inside if op == "InSet" else ~inside
+    return {"Equal": cls == v, "NotEqual": cls != v, "Less": cls < v, "LessEqual": cls <= v, "Greater": cls > v,
+            "GreaterEqual": cls >= v}[op]
+
+
+def _first_ingest_is_offered(case):
+    """The first ingest is certain to be offered the bands and (case["marked"]: unless it is the hot spot) to store them -- Pipeline::Impl::offer_bands and the engine's
+    finalize_taken (binned_point: define_all and fused): in core, the option on, no pointer handed out and no state imported
+    before it (it is the first op, or only a read-only flag pointer precedes it), one cloud in one scatter that the filter
+    leaves points of, the binned path taken (forced, or chosen by the engine: cells <= 16 n), whole float4 groups
+    (W % 4 == 0), and a non-select group of at most 8 outputs."""
+    g, ops = case["grid"], case["ops"]
+    first = next(i for i, o in enumerate(ops) if o["op"] == "ingest")
+    if any(not (o["op"] == "flags" and o["readonly"]) for o in ops[:first]):
+        return False
+    o, c = ops[first], case["clouds"][ops[first]["cloud"]]
+    n = len(c["x"])
+    if case["flavour"]["ooc"] or not case["fwfi"] or o["how"] == "file" or n == 0 or g["W"] % 4:
+        return False
+    if not keep_mask(case["filt"], c["cls"]).any():
+        return False
+    if not (case["path"] == 2 or (case["path"] == 0 and n * 16 >= g["W"] * g["H"])):
+        return False
+    return any(not gr["select"] and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS for gr in case["groups"])
+
+
+def defers_for_sure(case):
+    """... and leaves a plane in its band: an own-plane reduction (Sum, Count, Max, Min) is an output of such a group."""
+    return (case["marked"] or case["split_first"]) and any(not gr["select"] and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS and
+                                  any(case["specs"][r]["type"] in ("Sum", "Count", "Max", "Min") for r in gr["outs"])
+                                  for gr in case["groups"])
+
+
+def segments(case):
+    """The sequence cut at every checkpoint that a new pipeline resumes from: [(plan, flavour, ops, resumed plan differs)]."""
+    out, plan, flavour, cur, differs = [], case["plan"], case["flavour"], [], False
+    for o in case["ops"]:
+        cur.append(o)
+        if o["op"] == "checkpoint" and o["then"] != "go_on":
+            out.append((plan, flavour, cur, differs))
+            differs = o["plan"] is not None and any(o["plan"][k] != plan[k] for k in ("fill", "ground", "loc"))
+            plan, flavour, cur = o["plan"] or plan, o["flavour"] or flavour, []
+    out.append((plan, flavour, cur, differs))
+    return out
+
+
+def situations(case):
+    """Which of the situations the fuzz is for occur in a case (tests/test_sequence_fuzz_host.py counts them over the seeds).
+    Only what runs on the HIP engine counts: pointer ops in in-core segments, a hot spot that is binned."""
+    found = set()
+    types = [s["type"] for s in case["specs"]]
+    real = lambda o: o["op"] == "ingest" and len(case["clouds"][o["cloud"]]["x"]) > 0
+    if case["split_first"]:
+        found.add("a split bin in the offered first ingest")
+    if any(len(gr["outs"]) > MAX_FINALIZE_OUTPUTS for gr in case["groups"]):
+        found.add("more than 8 outputs in a group")
+    for s, (plan, flavour, ops, differs) in enumerate(segments(case)):
+        ingests = finalizes = 0
+        for i, o in enumerate(ops):
+            prev = ops[i - 1] if i else None
+            if o["op"] == "finalize":
+                if case["fwfi"] and ingests == 1 and prev is not None and real(prev):
+                    found.add("finalize right after the only ingest, finalize_with_first_ingest on")
+                if plan["ground"] and plan["fill"] > 0 and ingests >= 2 and finalizes >= 1 and prev is not None and real(prev):
+                    found.add("ground + fill + a second ingest")
+                if case["big"] and plan["out"] and plan["cog"]:
+                    found.add("write_cog level")
+                finalizes += 1
+            elif real(o):
+                # (the binned path of an in-core pipeline: more than 2^17 records past the filter in one LDS tile)
+                if not flavour["ooc"] and case["path"] != 1 and hot_records(case, case["clouds"][o["cloud"]]) > SPLIT_RECORDS:
+                    found.add("hot spot")
+                if finalizes:
+                    found.add("ingest after a finalize")
+                ingests += 1
+            elif o["op"] in ("planes_read", "planes_write", "flags", "merge") and flavour["ooc"]:
+                pass                                             # (out of core hands out no pointers: the runner drops the op)
+            elif o["op"] in ("planes_read", "planes_write"):
+                if o["op"] == "planes_write":
+                    found.add("plane write")
+                if prev is not None and real(prev) and any(q["op"] == "finalize" for q in ops[i:]):
+                    found.add("state_planes() between an ingest and its finalize")
+            elif o["op"] == "flags" and not o["readonly"] and s == 0 and ingests == 0:
+                found.add("writable flag pointer before the first ingest")
+            elif o["op"] == "merge" and finalizes:
+                found.add("merge_touched after a finalize")
+            elif o["op"] == "checkpoint" and ingests == 1:
+                found.add("checkpoint after a single ingest")
+            elif o["op"] == "reload" and ingests and any(q["op"] == "finalize" for q in ops[i:]):
+                found.add("load_state over a state that was ingested into")
+        if differs:
+            found.add("resume under a different finalize plan")
+        if flavour["ooc"] and any(o["op"] == "finalize" for o in ops):
+            if "MostRecent" in types:
+                found.add("out of core with MostRecent")
+            if plan["ground"] or plan["fill"] > 0:
+                found.add("out of core with ground or fill")
+    return found
+
+
+SITUATIONS = ("finalize right after the only ingest, finalize_with_first_ingest on", "ingest after a finalize",
+              "state_planes() between an ingest and its finalize", "plane write", "writable flag pointer before the first ingest",
+              "merge_touched after a finalize", "checkpoint after a single ingest", "resume under a different finalize plan",
+              "hot spot", "ground + fill + a second ingest", "write_cog level", "more than 8 outputs in a group",
+              "out of core with MostRecent", "out of core with ground or fill", "load_state over a state that was ingested into",
+              "a split bin in the offered first ingest")
+
+
+# ---- the model -------------------------------------------------------------------------------------------------------------------
+class Model:
+    """Per group four float32 planes (sum, count, max, min) or the MostRecent word plane of most_recent_common; one touched-tile
+    set; the count of the filter's survivors since the pipeline was created."""
+    IDENTITY = (np.float32(0.0), np.float32(0.0), -FLT_MAX, FLT_MAX)
+
+    def __init__(self, case):
+        g = case["grid"]
+        self.case, self.g, self.W, self.H = case, g, g["W"], g["H"]
+        self.tx, self.ty = -(-g["W"] // g["tw"]), -(-g["H"] // g["th"])
+        self.touched = np.zeros((self.ty, self.tx), bool)
+        self.survivors = 0
+        self.planes = []
+        for gr in case["groups"]:
+            if gr["select"]:
+                self.planes.append(np.zeros(self.W * self.H, np.uint64))
+            else:
+                self.planes.append([np.full(self.W * self.H, self.IDENTITY[p], np.float32) for p in range(4)])
+
+    def touched_cells(self):
+        g = self.g
+        return np.repeat(np.repeat(self.touched, g["th"], 0), g["tw"], 1)[:self.H, :self.W].reshape(-1)
+
+    def ingest(self, c):
+        import most_recent_common as MR
+        keep = keep_mask(self.case["filt"], c["cls"])
+        self.survivors += int(keep.sum())
+        cell = cells_of(self.g, c["x"], c["y"])
+        ok = keep & (cell >= 0)
+        cell_ok = cell[ok]
+        rows, cols = cell_ok // self.W, cell_ok % self.W
+        self.touched[rows // self.g["th"], cols // self.g["tw"]] = True
+        for gr, pl in zip(self.case["groups"], self.planes):
+            v = c[gr["ch"]]
+            if gr["select"]:
+                MR.fold_words(cell, v, c["t"], self.W * self.H, keep=keep, words=pl)
+                continue
+            # (binary64 holds every partial sum exactly, and the total is a binary32 number: the condition of build())
+            pl[0][:] = (pl[0].astype(np.float64) + np.bincount(cell_ok, v[ok].astype(np.float64), self.W * self.H)).astype(np.float32)
+            pl[1][:] = (pl[1].astype(np.float64) + np.bincount(cell_ok, minlength=self.W * self.H)).astype(np.float32)
+            np.maximum.at(pl[2], cell_ok, v[ok])
+            np.minimum.at(pl[3], cell_ok, v[ok])
+
+    def patch(self, o):
+        r0, c0, h, w = o["rect"]
+        pl = self.planes[o["group"]][o["slot"]].reshape(self.H, self.W)
+        pl[r0:r0 + h, c0:c0 + w] += np.float32(o["value"])
+
+    def flag(self, tiles):
+        for r, c in tiles:
+            self.touched[r, c] = True
+
+    def snapshot(self):
+        """What save_state writes: the planes of the touched tiles."""
+        return [pl.copy() if gr["select"] else [q.copy() for q in pl] for gr, pl in zip(self.case["groups"], self.planes)], self.touched.copy()
+
+    def overlay(self, snap):
+        """load_state: the tiles of the checkpoint replace the state's, their flags are set; every other tile stays."""
+        planes, touched = snap
+        g = self.g
+        cells = np.repeat(np.repeat(touched, g["th"], 0), g["tw"], 1)[:self.H, :self.W].reshape(-1)
+        for gr, pl, src in zip(self.case["groups"], self.planes, planes):
+            if gr["select"]:
+                pl[cells] = src[cells]
+            else:
+                for p in range(4):
+                    pl[p][cells] = src[p][cells]
+        self.touched |= touched
+
+    def carried_over(self):
+        """What a checkpoint carries into a new pipeline: the touched tiles.  A cell of an untouched tile is the identity again."""
+        gone = ~self.touched_cells()
+        for gr, pl in zip(self.case["groups"], self.planes):
+            if gr["select"]:
+                pl[gone] = 0
+            else:
+                for p in range(4):
+                    pl[p][gone] = self.IDENTITY[p]
+        self.survivors = 0
+
+    def state_planes(self):
+        """{(group, slot): the plane as state_planes() and the checkpoints show it}"""
+        import most_recent_common as MR
+        out = {}
+        for gi, (gr, pl) in enumerate(zip(self.case["groups"], self.planes)):
+            if gr["select"]:
+                out[(gi, 0)], out[(gi, 1)] = MR.state_of_words(pl, (self.H, self.W))
+            else:
+                for p in sorted(gr["slots"]):
+                    out[(gi, p)] = pl[p].reshape(self.H, self.W)
+        return out
+
+    def raw_bands(self):
+        """finalize_rt: Sum as is; Count and Average NaN where the count is 0; Max and Min NaN at the identity; Average one
+        binary32 division; every cell of an unflagged tile NaN."""
+        import most_recent_common as MR
+        live = self.touched_cells()
+        out = []
+        for s in self.case["specs"]:
+            pl = self.planes[s["group"]]
+            if s["type"] == "MostRecent":
+                band = MR.band_of_words(pl, (self.W * self.H,))
+            else:
+                sm, ct, mx, mn = pl
+                with np.errstate(all="ignore"):
+                    band = {"Sum": lambda: sm.copy(), "Count": lambda: np.where(ct > 0, ct, np.float32(np.nan)),
+                            "Average": lambda: np.where(ct > 0, sm / ct, np.float32(np.nan)),
+                            "Max": lambda: np.where(mx == -FLT_MAX, np.float32(np.nan), mx),
+                            "Min": lambda: np.where(mn == FLT_MAX, np.float32(np.nan), mn)}[s["type"]]()
+            band = np.where(live, band, np.float32(np.nan)).astype(np.float32)
+            out.append(band.reshape(self.H, self.W))
+        return out
+
+    def leaving_bands(self, plan):
+        """finalize()'s documented order: the filter on the RAW source band; the fill of the Average / Max / Min / MostRecent
+        bands and of the DTM; hag from the bands as they leave.  -> (names, bands)"""
+        import ground_filter_common as G
+        import pcr
+        raw = self.raw_bands()
+        names = [band_name(i, s) for i, s in enumerate(self.case["specs"])]
+        out = list(raw)
+        fills = [i for i, s in enumerate(self.case["specs"]) if s["type"] in FILL_TYPES]
+        if plan["fill"] > 0 and fills:
+            filled = G.grid_bands(pcr.fill_nodata(G.make_grid(raw), plan["fill"], fills))
+            out = [filled[i] if i in fills else raw[i] for i in range(len(raw))]
+        if plan["ground"]:
+            spec = pcr.GroundFilterSpec()
+            spec.max_radius_cells = plan["ground"]["maxr"]
+            dtm = G.grid_bands(pcr.ground_filter(G.make_grid([raw[plan["ground"]["source"]]]), 0, spec, self.g["cs"]))[0]
+            if plan["fill"] > 0:
+                dtm = G.grid_bands(pcr.fill_nodata(G.make_grid([dtm]), plan["fill"]))[0]
+            out.append(dtm)
+            names.append("dtm")
+            if plan["ground"]["top"] is not None:
+                out.append(G.difference(out[plan["ground"]["top"]], dtm))
+                names.append("hag")
+        return names, out
+
+    def write_checkpoint(self, dirname):
+        """The model's state as `.pcrt` files in the pipelines' layout: one file per touched tile and reduction."""
+        import pcr
+        planes = self.state_planes()
+        specs, g = self.case["specs"], self.g
+        for r, s in enumerate(specs):
+            rdir = dirname if len(specs) == 1 else os.path.join(dirname, f"reduction_{r}")
+            os.makedirs(rdir, exist_ok=True)
+            for tr, tc in np.argwhere(self.touched):
+                r0, c0 = tr * g["th"], tc * g["tw"]
+                state = np.stack([planes[(s["group"], p)][r0:r0 + g["th"], c0:c0 + g["tw"]] for p in PLANES_OF[s["type"]]])
+                pcr.write_tile_state(pcr.tile_state_filename(rdir, int(tr), int(tc)), int(tr), int(tc),
+                                     np.ascontiguousarray(state, np.float32), getattr(pcr.ReductionType, s["type"]))
+
+
+def band_name(i, s):
+    return f"r{i}_{s['type']}_{s['ch']}"
+
+
+def overview_level_count(W, H):
+    n, f = 0, 2
+    while min(W, H) // f >= 256:                                 # write_cog's rule (the reference's): levels 2, 4, ... while min(W, H) / level >= 256
+        n, f = n + 1, f * 2
+    return n
+
+
+# ---- the runner ------------------------------------------------------------------------------------------------------------------
+def bytes_per_row(case):
+    """Pipeline::Banded::bytes_per_row: 4 B per cell and plane (a MostRecent group: its two slots), + the finalized bands."""
+    return case["grid"]["W"] * 4 * (sum(len(gr["slots"]) for gr in case["groups"]) + len(case["specs"]))
+
+
+def make_config(case, plan, flavour, exec_mode, engine, tmp_path, state_dir=None):
+    import pcr
+    g = case["grid"]
+    cfg = pcr.PipelineConfig()
+    cfg.grid.bounds = pcr.BBox(g["min_x"], g["min_y"], g["max_x"], g["max_y"])
+    cfg.grid.cell_size_x, cfg.grid.cell_size_y = g["cs"], -g["cs"]
+    cfg.grid.tile_width, cfg.grid.tile_height = g["tw"], g["th"]
+    cfg.grid.compute_dimensions()
+    assert (cfg.grid.width, cfg.grid.height) == (g["W"], g["H"])
+    cfg.exec_mode = exec_mode
+    reds = []
+    for i, s in enumerate(case["specs"]):
+        r = pcr.ReductionSpec()
+        r.value_channel, r.type, r.output_band_name = s["ch"], getattr(pcr.ReductionType, s["type"]), band_name(i, s)
+        if s["type"] == "MostRecent":
+            r.timestamp_channel = "t"
+        reds.append(r)
+    cfg.reductions = reds
+    if case["filt"]:
+        f = pcr.FilterSpec()
+        if case["filt"]["op"] in ("InSet", "NotInSet"):
+            pr = pcr.FilterPredicate()
+            pr.channel_name, pr.op, pr.value_set = "cls", getattr(pcr.CompareOp, case["filt"]["op"]), case["filt"]["set"]
+            f.predicates = [pr]
+        else:
+            f.add("cls", getattr(pcr.CompareOp, case["filt"]["op"]), case["filt"]["value"])
+        cfg.filter = f
+    cfg.fill_nodata_radius = plan["fill"]
+    if plan["ground"]:
+        cfg.ground.source_band = band_name(plan["ground"]["source"], case["specs"][plan["ground"]["source"]])
+        if plan["ground"]["top"] is not None:
+            cfg.ground.top_band = band_name(plan["ground"]["top"], case["specs"][plan["ground"]["top"]])
+        cfg.ground.max_radius_cells = plan["ground"]["maxr"]
+    ooc = flavour["ooc"] and engine == "hip"
+    if plan["loc"] == "Device" and engine == "hip" and not ooc:
+        cfg.result_location = pcr.MemoryLocation.Device
+    if plan["out"]:
+        cfg.output_path, cfg.write_cog = str(tmp_path / "out.tif"), plan["cog"]
+    cfg.finalize_with_first_ingest = case["fwfi"]
+    cfg.scatter_path = case["path"]
+    if ooc:                                                      # a device budget of two or three row bands of whole tile rows
+        tile_rows = -(-g["H"] // g["th"])
+        cfg.gpu_memory_budget = bytes_per_row(case) * g["th"] * -(-tile_rows // flavour["bands"]) + 64
+        cfg.host_cache_budget = flavour["host_budget"]
+        cfg.state_dir = str(tmp_path / "work")
+    if state_dir is not None:
+        cfg.state_dir, cfg.resume = state_dir, True
+    return cfg
+
+
+def _cloud(c, where):
+    import pcr
+    n = len(c["x"])
+    loc = pcr.MemoryLocation.HostPinned if where == "pinned" else pcr.MemoryLocation.Host
+    cloud = pcr.PointCloud.create(max(n, 1), loc)
+    cloud.set_x_array(np.asarray(c["x"], np.float64))
+    cloud.set_y_array(np.asarray(c["y"], np.float64))
+    cloud.resize(n)
+    for name in ("a", "b", "t", "cls"):
+        cloud.add_channel(name, pcr.DataType.Float32)
+        if n:
+            cloud.set_channel_array_f32(name, c[name])
+    return cloud.to_device() if where == "device" else cloud
+
+
+def _same_tree(got_dir, want_dir, what):
+    def files(d):
+        return sorted(os.path.relpath(os.path.join(r, f), d) for r, _, fs in os.walk(d) for f in fs)
+    got, want = files(got_dir), files(want_dir)
+    assert got == want, f"{what}: files {sorted(set(got) ^ set(want))[:4]} are in one checkpoint only"
+    for f in got:
+        assert filecmp.cmp(os.path.join(got_dir, f), os.path.join(want_dir, f), shallow=False), f"{what}: {f} differs from the host engine's file"
+
+
+def check_sequence(seed, exec_mode, engine, tmp_path):
+    """Runs case `seed` on one engine and holds it to the model after every finalize, plane read and checkpoint."""
+    import ctypes as C
+
+    import overviews_common as M
+    import pcr
+    from conftest import load_cabi
+
+    case = build(seed)
+    model = Model(case)
+    hip = engine == "hip"
+    A = load_cabi() if hip else None
+    W, H = case["grid"]["W"], case["grid"]["H"]
+    plan, flavour = case["plan"], case["flavour"]
+    alive = []                                                   # clouds and unions a stream may still read
+    snaps = {}                                                   # op index of a checkpoint -> the model's state then
+
+    def create(state_dir=None):
+        p = pcr.Pipeline.create(make_config(case, plan, flavour, exec_mode, engine, tmp_path, state_dir))
+        assert p is not None, f"seed {seed}: create: {pcr.pipeline_create_error()}"
+        assert p.engine() == engine, f"seed {seed}: engine {p.engine()}"
+        assert p.out_of_core() == (hip and flavour["ooc"]), f"seed {seed}: out_of_core() is {p.out_of_core()}"
+        return p
+
+    def d2h(ptr, shape, dtype=np.float32):
+        out = np.empty(shape, dtype)
+        A.check(A.lib().pcr_hip_memcpy_d2h(out.ctypes.data, C.c_void_p(ptr), out.nbytes, None))
+        A.check(A.lib().pcr_hip_stream_synchronize(None))
+        return out
+
+    def h2d(ptr, a):
+        a = np.ascontiguousarray(a)
+        A.check(A.lib().pcr_hip_memcpy_h2d(C.c_void_p(ptr), a.ctypes.data, a.nbytes, None))
+        A.check(A.lib().pcr_hip_stream_synchronize(None))
+
+    p = create()
+    first_ingest, expect_deferred = True, False
+    for k, o in enumerate(case["ops"]):
+        at = f"seed {seed}, op {k} ({o['op']})"
+        in_core_hip = hip and not p.out_of_core()
+        if o["op"] == "ingest":
+            c = case["clouds"][o["cloud"]]
+            how = o["how"]
+            if how == "file":
+                path = str(tmp_path / f"cloud{k}.pcrp")
+                pcr.write_point_cloud(path, _cloud(c, "host"))
+                chunk = max(1, int(len(c["x"]) * o["chunk_frac"]))
+                assert p.ingest_file(path, chunk_points=chunk) == len(c["x"]), f"{at}: points read"
+            elif how in ("host", "device"):
+                cloud = _cloud(c, how if hip else "host")         # (the host engine: the same cloud from host memory)
+                alive.append(cloud)
+                p.ingest(cloud)
+            else:
+                cloud = _cloud(c, ("pinned" if how == "async_pinned" else "device") if hip else "host")
+                alive.append(cloud)
+                p.ingest_async(cloud)
+                if o["sync"]:
+                    p.synchronize()
+            model.ingest(c)
+            if first_ingest and hip and (case["marked"] or case["split_first"]):      # the fuzz reaches the code it is for
+                info = p.last_scatter()
+                assert info["bands_with_scatter"] > 0, f"{at}: the first ingest stored no bands: {info}"
+                if defers_for_sure(case):
+                    assert info["deferred_planes"] != 0, f"{at}: the first ingest left no plane in its bands: {info}"
+                expect_deferred = defers_for_sure(case) and case["ops"][k + 1] == dict(op="finalize", wait=True)
+            first_ingest = False
+        elif o["op"] == "finalize":
+            if o["wait"]:
+                p.finalize()
+            else:
+                p.finalize_async()
+                p.synchronize()
+            if expect_deferred:
+                # the blocking finalize right behind the offered ingest has read the done word: 1 (the bands are the scatter's,
+                # the planes stay in them) -- or 0 where the scan split a bin: the finalize pass ran, every plane was stored
+                left = p.last_scatter()["deferred_planes"]
+                assert (left == 0) == case["split_first"], f"{at}: deferred_planes {left} behind a {'split' if case['split_first'] else 'whole'} first ingest"
+            expect_deferred = False
+            names, want = model.leaving_bands(plan)
+            res = p.result()
+            assert res is not None, f"{at}: no result"
+            host = res if res.location() != pcr.MemoryLocation.Device else res.to_host()
+            assert [host.band_desc(b).name for b in range(host.num_bands())] == names, f"{at}: band names"
+            for b, name in enumerate(names):
+                M.bits_equal(np.array(host.band_array(b)), want[b], f"{at}, band {b} ({name}) of result()")
+            for b, name in enumerate(names if in_core_hip else []):
+                ptr = p.result_band_device_ptr(b)
+                assert ptr != 0, f"{at}: result_band_device_ptr({b})"
+                M.bits_equal(d2h(ptr, (H, W)), want[b], f"{at}, band {b} ({name}) of result_band_device_ptr")
+            if plan["out"]:
+                tif = str(tmp_path / "out.tif")
+                levels = overview_level_count(W, H) if plan["cog"] else 0
+                assert pcr.read_geotiff_band_names(tif) == names, f"{at}: GeoTIFF band names"
+                assert len(pcr.read_geotiff_overviews(tif)) == levels, f"{at}: GeoTIFF levels"
+                for b, name in enumerate(names):
+                    M.bits_equal(pcr.read_geotiff_band(tif, b), want[b], f"{at}, band {b} ({name}) of the GeoTIFF")
+                    for lv, lw in enumerate(M.pyramid(want[b], levels)):
+                        M.bits_equal(pcr.read_geotiff_band(tif, b, lv + 1), lw, f"{at}, band {b} ({name}), level {lv + 1} of the GeoTIFF")
+            assert p.stats().points_processed == model.survivors, \
+                f"{at}: points_processed {p.stats().points_processed} != {model.survivors} survivors of the filter"
+        elif o["op"] in ("planes_read", "planes_write"):
+            if not in_core_hip:
+                continue                                         # (no plane pointers out of core or on the host engine)
+            p.synchronize()                                      # the caller's part: the scatters it enqueued itself
+            views = {(group, {1: 0, 2: 1, 4: 2, 8: 3}[kind]): ptr for ptr, kind, group in p.state_planes()}
+            want = model.state_planes()
+            assert set(views) == set(want), f"{at}: planes {sorted(views)} != {sorted(want)}"
+            assert p.state_row_count() == H
+            for key in sorted(views):
+                M.bits_equal(d2h(views[key], (H, W)), want[key], f"{at}, plane {key}")
+            if o["op"] == "planes_write":                        # from outside: the rectangle read, the patch added, its rows written back
+                r0, c0, h, w = o["rect"]
+                ptr = views[(o["group"], o["slot"])]
+                for r in range(r0, r0 + h):
+                    at_row = ptr + 4 * (r * W + c0)
+                    h2d(at_row, d2h(at_row, (w,)) + np.float32(o["value"]))
+                model.patch(o)
+        elif o["op"] == "flags":
+            if not in_core_hip:
+                continue
+            p.synchronize()
+            ptr, tx, ty = p.tile_touched_ptr(readonly=o["readonly"])
+            assert (tx, ty) == (model.tx, model.ty) and ptr != 0, at
+            got = d2h(ptr, (ty, tx), np.uint32)
+            assert np.array_equal(got != 0, model.touched), f"{at}: touched flags differ"
+            for r, c in o["extra"]:                              # written through the pointer, as the shard exchange does
+                h2d(ptr + 4 * (r * tx + c), np.ones(1, np.uint32))
+            model.flag(o["extra"])
+        elif o["op"] == "merge":
+            if not in_core_hip:
+                continue
+            model.flag(o["extra"])
+            union = A.DeviceBuffer.from_numpy(model.touched.astype(np.uint32))
+            alive.append(union)
+            p.merge_touched(union.ptr.value)
+        elif o["op"] == "reload":                                # an earlier checkpoint laid over the state as it is
+            p.load_state(str(tmp_path / f"ck{o['of']}"))
+            model.overlay(snaps[o["of"]])
+        else:                                                    # checkpoint
+            ck = str(tmp_path / f"ck{k}")
+            p.save_state(ck)
+            # the files a host-engine pipeline writes for the same state
+            src, ref = str(tmp_path / f"ck{k}_model"), str(tmp_path / f"ck{k}_host")
+            os.makedirs(src)
+            model.write_checkpoint(src)
+            hcfg = make_config(case, dict(fill=0, ground=None, loc="Host", out=False, cog=False), dict(ooc=False), pcr.ExecutionMode.CPU,
+                               "host", tmp_path, src)
+            hp = pcr.Pipeline.create(hcfg)
+            assert hp is not None and hp.engine() == "host", f"{at}: {pcr.pipeline_create_error()}"
+            os.makedirs(ref)
+            hp.save_state(ref)
+            del hp
+            if not os.path.isdir(ck):
+                os.makedirs(ck)                                  # (nothing touched: nothing written)
+            _same_tree(ck, ref, at)
+            snaps[k] = model.snapshot()
+            if o["then"] == "go_on":
+                continue
+            plan, flavour = o["plan"] or plan, o["flavour"] or flavour
+            if hip:
+                p.synchronize()
+            del p
+            if o["then"] == "fresh":                             # a new pipeline that does not take the state (a later op may load it)
+                model = Model(case)
+                p = create()
+                continue
+            model.carried_over()
+            if o["then"] == "resume":
+                p = create(ck)
+            else:
+                p = create()
+                p.load_state(ck)
+            first_ingest = False
+    assert case["ops"][-1]["op"] == "finalize"
+    if hip:
+        p.synchronize()
+    del p

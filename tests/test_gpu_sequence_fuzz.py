@@ -1,0 +1,18 @@
+"""The operation-sequence fuzz (tests/sequence_fuzz_common.py) on the HIP engine: random sequences of ingests, finalizes, plane
+and flag pointers, flag unions and checkpoints on one pipeline, in core and out of core, held bit for bit to the model that
+tests/test_sequence_fuzz_host.py has pinned on the host engine.  What it is for is the layer that decides which buffer a kernel
+reads and whether it runs at all (the plane-state block of host/src/device_pipeline.cpp, LeavingBand{raw, out}): on the seeds
+the generator marks, the first ingest must have stored its bands (and left planes in them), so the sequence behind it walks the
+stale-band and plane-restore paths.  The 40 default seeds in the suite; PCR_SEQ_FUZZ_SEEDS=a:b soaks a range (or a,b,c: those
+seeds).  A failure names its seed, the index of the op and the band."""
+import pytest
+
+import pcr
+import sequence_fuzz_common as S
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("seed", S.seeds_from_env())
+def test_sequence_on_the_hip_engine_equals_the_model(seed, tmp_path):
+    S.check_sequence(seed, pcr.ExecutionMode.GPU, "hip", tmp_path)
