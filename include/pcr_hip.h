@@ -476,9 +476,12 @@ int pcr_hip_finalize_select(const pcr_hip_grid* g, const uint64_t* d_packed, con
  *        UTM          32601-32660 / 32701-32760 (WGS 84, north / south), 26901-26923 (NAD83), 25828-25838 (ETRS89):
  *                     Krueger's series to n^6 (Karney 2011), k0 0.9996, FE 500 000, FN 0 / 10 000 000
  *      WGS 84, NAD83 and ETRS89 are one datum here (no datum shift: PROJ's "ballpark" transformation without grids).
- *      A point outside the domain becomes NaN on both axes: |latitude| > 90, |lon - lon0| >= 90 degrees for UTM, the poles
- *      for 3857.  Two descriptors of the same code copy the coordinates bit for bit; two geographic ones copy them too
- *      (NaN where |latitude| > 90).  out_x / out_y are either x / y themselves (in place) or do not overlap them. */
+ *      A point outside the domain becomes NaN on both axes: a non-finite coordinate on either axis, |latitude| > 90, the
+ *      poles for 3857, and for UTM, in both directions, |eta'| > 1 with eta' = atanh(cos(conformal latitude) sin(lon - lon0))
+ *      -- about 50 degrees from the central meridian on the equator, any |lon - lon0| < 90 near the poles (the poles
+ *      themselves at any longitude); the inverse also refuses northings beyond the pole.  Inside, UTM is within 1e-6 m
+ *      (forward) and 1e-10 degrees (inverse) of the exact Gauss-Krueger map.  Two descriptors of the same code
+ *      copy the coordinates bit for bit; two geographic ones copy them too (NaN where |latitude| > 90 or non-finite).  out_x / out_y are either x / y themselves (in place) or do not overlap them. */
 enum { PCR_HIP_CRS_GEOGRAPHIC = 1, PCR_HIP_CRS_WEB_MERCATOR = 2, PCR_HIP_CRS_TRANSVERSE_MERCATOR = 3 };
 typedef struct pcr_hip_crs_desc {
     int32_t epsg;

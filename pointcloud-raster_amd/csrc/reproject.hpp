@@ -7,7 +7,8 @@
 // transcendental call where an identity gives it.  Transverse Mercator is Krueger's series to n^6 in the form of
 // C. F. F. Karney, "Transverse Mercator with an accuracy of a few nanometers", J. Geodesy 85 (2011) 475-485: forward
 // eqs. (7)-(11) with the alpha series, inverse with the beta series and the conformal -> geodetic latitude series (delta),
-// both evaluated by Clenshaw summation on the complex argument.  f64 throughout; out-of-domain points become NaN.
+// both evaluated by Clenshaw summation on the complex argument.  f64 throughout; out-of-domain points (kTmEtaMax below for
+// Transverse Mercator) and non-finite input become NaN on both axes.
 #pragma once
 
 #include <cmath>
@@ -26,6 +27,13 @@ namespace crs {
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kD2R = kPi / 180.0;
 constexpr double kR2D = 180.0 / kPi;
+
+// Transverse Mercator is accepted where |eta'| <= kTmEtaMax, eta' = atanh(cos chi sin(lambda - lambda0)) the Gauss-Schreiber
+// easting (chi the conformal latitude): the n^7 term the series drops grows like sinh(14 eta'), and at this cut the host
+// form is within 2.5e-7 m of the exact map.  About 50 degrees from the central meridian on the equator, any
+// |lambda - lambda0| < 90 near the poles.  The forward direction tests z = sinh(eta'), the inverse the beta-corrected eta'.
+constexpr double kTmEtaMax = 1.0;
+constexpr double kTmSinhEtaMax = 1.1752011936438014;     // sinh(kTmEtaMax)
 
 // longitude difference in degrees -> (-180, 180]
 PCR_HD inline double norm_deg(double d) {
@@ -83,7 +91,7 @@ PCR_HD inline void sinh_cosh(double x, double* sh, double* ch) {
 PCR_HD inline bool decode(const pcr_hip_crs_desc& d, int kind, double x, double y, bool need_phi, Geo* g) {
     switch (kind) {
         case PCR_HIP_CRS_GEOGRAPHIC: {
-            if (!(fabs(y) <= 90.0)) return false;
+            if (!(fabs(y) <= 90.0) || !(fabs(x) < INFINITY)) return false;
             g->lon = x;
             g->phi = y * kD2R;
             sincos(g->phi, &g->s, &g->c);
@@ -94,16 +102,20 @@ PCR_HD inline bool decode(const pcr_hip_crs_desc& d, int kind, double x, double 
             // with E = exp(-|psi|): tanh|psi| = (1 - E^2) / (1 + E^2), 1 / cosh psi = 2 E / (1 + E^2); 1 - E^2 from expm1, so
             // that neither cancels (near the equator 1 - E^2, near the poles anything derived from 1 - E)
             const double psi = y / d.a;
+            if (!(fabs(x) < INFINITY) || !(fabs(psi) < INFINITY)) return false;
             const double em = expm1(-fabs(psi)), E = exp(-fabs(psi));
             const double iq = 1.0 / (1.0 + E * E);
             g->s = copysign(-em * (2.0 + em) * iq, psi);
             g->c = 2.0 * E * iq;
             g->lon = x / d.a * kR2D;
             if (need_phi) g->phi = atan2(g->s, g->c);
-            return x == x && psi == psi;
+            return true;
         }
         default: {                                                          // Transverse Mercator, inverse
             const double ika = 1.0 / d.ka, xi = (y - d.fn) * ika, eta = (x - d.fe) * ika;
+            // far outside, the beta series is garbage that can fall back inside the cut; up to here eta' rises with eta
+            // (NaN and infinite eastings fail too).  The domain tests only gather in `ok`: one branch, at the end
+            bool ok = fabs(eta) <= 2.0 * kTmEtaMax;
             double s2x, c2x;
             sincos(2.0 * xi, &s2x, &c2x);
             const double e2 = exp(2.0 * eta);
@@ -111,8 +123,12 @@ PCR_HD inline bool decode(const pcr_hip_crs_desc& d, int kind, double x, double 
             double dr, di;
             clenshaw_sin(d.beta, s2x, c2x, sh2y, ch2y, &dr, &di);
             const double xip = xi - dr, etap = eta - di;                    // zeta' = zeta - sum beta_j sin(2 j zeta)
+            // what the forward direction refuses, and northings beyond the pole (a few ulp of slack: the pole row itself,
+            // rounded up, is the pole); NaN and infinite northings fail here
+            ok = ok && fabs(etap) <= kTmEtaMax && fabs(xip) <= 0.5 * kPi * (1.0 + 1e-15);
             double sxp, cxp;
             sincos(xip, &sxp, &cxp);
+            cxp = fabs(cxp);                                                // (below zero only within that slack)
             double shp, chp;
             sinh_cosh(etap, &shp, &chp);
             // conformal latitude chi: sin chi = sin xi' / cosh eta', cos chi = sqrt(sinh^2 eta' + cos^2 xi') / cosh eta'
@@ -129,8 +145,9 @@ PCR_HD inline bool decode(const pcr_hip_crs_desc& d, int kind, double x, double 
                 b1 = t;
             }
             g->phi = chi + s2c * b1;
-            g->lon = norm_deg(d.lon0 + atan2(shp, cxp) * kR2D);
-            if (!(fabs(g->phi) <= 0.5 * kPi)) return false;                 // (NaN in, NaN out)
+            const double dl = atan2(shp, cxp) * kR2D;
+            g->lon = norm_deg(d.lon0 + dl);
+            if (!(ok && fabs(dl) < 90.0 && fabs(g->phi) <= 0.5 * kPi)) return false;
             sincos(g->phi, &g->s, &g->c);
             return true;
         }
@@ -153,7 +170,8 @@ PCR_HD inline bool encode(const pcr_hip_crs_desc& d, int kind, const Geo& g, dou
         }
         default: {                                                          // Transverse Mercator, forward
             const double dl = norm_deg(g.lon - d.lon0);
-            if (!(fabs(dl) < 90.0)) return false;
+            // 90 degrees and more from the central meridian (the poles: at any longitude)
+            if (!(fabs(dl) < 90.0) && !(fabs(g.s) == 1.0 && dl == dl)) return false;
             double sl, cl;
             sincos(dl * kD2R, &sl, &cl);
             // tau' = tan(conformal latitude) = tau cosh(sigma) - sinh(sigma) sqrt(1 + tau^2), sigma = e atanh(e sin phi);
@@ -176,7 +194,8 @@ PCR_HD inline bool encode(const pcr_hip_crs_desc& d, int kind, const Geo& g, dou
             clenshaw_sin(d.alpha, s2x, c2x, sh2y, ch2y, &dr, &di);
             *x = d.fe + d.ka * (etap + di);
             *y = d.fn + d.ka * (xip + dr);
-            return true;
+            return fabs(z) <= kTmSinhEtaMax;                                // the cut on eta' = asinh(z): a compare on what
+                                                                            // is already there, no branch ahead of the series
         }
     }
 }
@@ -187,7 +206,7 @@ PCR_HD inline void transform_point(const pcr_hip_crs_desc& src, const pcr_hip_cr
                                    double* ox, double* oy) {
     double u = NAN, v = NAN;
     if (sk == PCR_HIP_CRS_GEOGRAPHIC && dk == PCR_HIP_CRS_GEOGRAPHIC) {
-        if (fabs(y) <= 90.0) { u = x; v = y; }
+        if (fabs(y) <= 90.0 && fabs(x) < INFINITY) { u = x; v = y; }
     } else {
         Geo g;
         if (!decode(src, sk, x, y, dk == PCR_HIP_CRS_GEOGRAPHIC, &g) || !encode(dst, dk, g, &u, &v)) u = v = NAN;

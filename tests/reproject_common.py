@@ -1,4 +1,4 @@
-"""Shared by the reprojection tests: an exact Gauss-Krueger oracle in mpmath, a numpy restatement of the UTM inverse, and
+"""Shared by the reprojection tests: an exact Gauss-Krueger oracle in mpmath (and its recorded lattice), a numpy restatement of the UTM inverse, and
 the pipeline case the engines are checked on (points near the cell centres of a UTM 18N grid, fed in lon/lat)."""
 import numpy as np
 
@@ -13,30 +13,97 @@ def utm_lon0(zone):
 
 
 # ---- exact oracle -----------------------------------------------------------------------------------------------------
-def oracle_tm(lat_deg, dlon_deg, dps=30):
-    """(x, y) of the exact Gauss-Krueger map on WGS 84, k0 = 0.9996, no false easting / northing: solve
-    psi(phi_c) = psi(phi) + i lambda for the complex latitude phi_c, then y + i x = k0 M(phi_c), with M the meridian arc
-    continued analytically.  Independent of any series."""
+INVF = {"WGS84": "298.257223563", "GRS80": "298.257222101"}   # inverse flattenings, as EPSG states them
+ORACLE_DPS = 50
+ORACLE_RESIDUAL = 1e-30
+
+
+def _ellipsoid(mp, ellipsoid):
+    a, f = mp.mpf(WGS84_A), 1 / mp.mpf(INVF[ellipsoid])
+    e2 = f * (2 - f)
+    return a, e2, mp.sqrt(e2)
+
+
+def oracle_quarter_meridian(ellipsoid="WGS84", dps=ORACLE_DPS):
+    """k0 times the meridian arc from the equator to the pole, by quadrature (an mpf)."""
     import mpmath as mp
     with mp.workdps(dps):
-        a, f = mp.mpf(WGS84_A), 1 / mp.mpf("298.257223563")
-        e2 = f * (2 - f)
-        e = mp.sqrt(e2)
+        a, e2, _ = _ellipsoid(mp, ellipsoid)
+        return mp.mpf(K0) * mp.quad(lambda s: a * (1 - e2) * (1 - e2 * mp.sin(s) ** 2) ** mp.mpf(-1.5), [0, mp.pi / 2])
+
+
+def oracle_tm(lat_deg, dlon_deg, dps=ORACLE_DPS, ellipsoid="WGS84"):
+    """(x, y) of the exact Gauss-Krueger map on the ellipsoid, k0 = 0.9996, no false easting / northing: solve
+    psi(phi_c) = psi(phi) + i lambda for the complex latitude phi_c, then y + i x = k0 M(phi_c), with M the meridian arc
+    continued analytically.  Independent of any series.  The root search starts from the Gauss-Schreiber point (the
+    answer on the sphere); the residual of the root it returns is asserted, so the start cannot influence the answer.
+    |lat| = 90 exactly is the pole row: x = 0, y = +-k0 (quarter meridian)."""
+    import mpmath as mp
+    with mp.workdps(dps):
+        if abs(lat_deg) == 90.0:
+            return 0.0, float(mp.sign(lat_deg) * oracle_quarter_meridian(ellipsoid, dps))
+        a, e2, e = _ellipsoid(mp, ellipsoid)
 
         def psi(p):
             return mp.asinh(mp.tan(p)) - e * mp.atanh(e * mp.sin(p))
 
         phi, lam = mp.radians(mp.mpf(lat_deg)), mp.radians(mp.mpf(dlon_deg))
         target = psi(phi) + 1j * lam
-        pc = mp.findroot(lambda z: psi(z) - target, mp.mpc(phi, lam * mp.cos(phi)))
+        start = mp.mpc(mp.atan2(mp.tan(phi), mp.cos(lam)), mp.atanh(mp.cos(phi) * mp.sin(lam)))
+        pc = mp.findroot(lambda z: psi(z) - target, start, tol=mp.mpf(10) ** (-2 * dps), verify=False, maxsteps=100)
+        residual = abs(psi(pc) - target)
+        assert residual <= ORACLE_RESIDUAL, f"oracle_tm({lat_deg}, {dlon_deg}, {ellipsoid}): residual {mp.nstr(residual, 5)}"
         m = pc * mp.quad(lambda s: a * (1 - e2) * (1 - e2 * mp.sin(s * pc) ** 2) ** mp.mpf(-1.5), [0, 1])
         w = mp.mpf(K0) * m
         return float(w.imag), float(w.real)
 
 
-def oracle_utm(lat_deg, lon_deg, zone, south=False):
-    x, y = oracle_tm(lat_deg, lon_deg - utm_lon0(zone))
+def oracle_wm(lat_deg, lon_deg, dps=ORACLE_DPS):
+    """(x, y) of Web Mercator (EPSG:3857) by its closed forms on the sphere of radius a: x = a lambda, y = a atanh(sin phi)."""
+    import mpmath as mp
+    with mp.workdps(dps):
+        a = mp.mpf(WGS84_A)
+        return float(a * mp.radians(mp.mpf(lon_deg))), float(a * mp.atanh(mp.sin(mp.radians(mp.mpf(lat_deg)))))
+
+
+def oracle_utm(lat_deg, lon_deg, zone, south=False, ellipsoid="WGS84"):
+    x, y = oracle_tm(lat_deg, lon_deg - utm_lon0(zone), ellipsoid=ellipsoid)
     return FE + x, y + (10000000.0 if south else 0.0)
+
+
+# ---- the recorded oracle (tests/golden/make_reproject_lattice.py) -----------------------------------------------------
+def eta_prime(lat_deg, dlon_deg):
+    """|eta'| = atanh(cos(chi) sin|dlon|), chi the conformal latitude (WGS 84; GRS80 differs by 1e-11 relative): the
+    Gauss-Schreiber easting the transform puts its cut on."""
+    e = np.sqrt(WGS84_F * (2 - WGS84_F))
+    phi = np.radians(np.asarray(lat_deg, float))
+    psi = np.arcsinh(np.tan(phi)) - e * np.arctanh(e * np.sin(phi))
+    return np.arctanh(np.sin(np.radians(np.abs(dlon_deg))) / np.cosh(psi))
+
+
+def load_lattice():
+    """The arrays of tests/golden/reproject_lattice.npz plus eta (the Gauss-Schreiber easting of each point) and inside
+    (eta below the cut: the points the transform accepts)."""
+    import os
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reproject_lattice.npz"))
+    L = {k: z[k] for k in z.files}
+    L["eta"] = eta_prime(L["lat"], L["dlon"])
+    L["inside"] = L["eta"] < float(L["eta_cut"])
+    return L
+
+
+def edge_inputs():
+    """Exact inputs at the edges of the domain, as (lon offset from the central meridian, lat): the poles and the next
+    double beyond them, either side of the cut on the equator (1e-9 relative away from it), 90 degrees - 1e-6 from the
+    central meridian, and NaN / +-inf on each axis."""
+    cut = np.degrees(np.arcsin(np.tanh(1.0)))
+    inf, nan = np.inf, np.nan
+    dl = [0.0, 7.0, 0.0, 7.0, 0.0, 0.0, cut * (1 - 1e-9), cut * (1 + 1e-9), -cut * (1 - 1e-9), -cut * (1 + 1e-9),
+          90.0 - 1e-6, 90.0 - 1e-6, nan, 1.0, inf, -inf, 1.0, 1.0]
+    lat = [90.0, -90.0, np.nextafter(90.0, inf), np.nextafter(-90.0, -inf), 90.5, -91.0, 0.0, 0.0, 0.0, 0.0,
+           0.0, 89.0, 10.0, nan, 10.0, 10.0, inf, -inf]
+    ok = [True, True, False, False, False, False, True, False, True, False, False, True] + [False] * 6
+    return np.array(dl), np.array(lat), np.array(ok)
 
 
 # ---- numpy restatement of the inverse (Karney 2011: beta series, then Newton on the conformal latitude) ---------------

@@ -90,9 +90,17 @@ def test_chains_through_web_mercator_and_geographic():
     # the three geographic codes are one datum: coordinates pass unchanged
     gx, gy = tr(4326, 4269, lon, lat)
     assert np.array_equal(gx, lon) and np.array_equal(gy, lat)
-    # NAD83 / ETRS89 UTM: GRS80, within a fraction of a millimetre of WGS 84 UTM
-    nx, ny = tr(4326, 26918, lon, lat)
-    assert np.max(np.abs(nx - ux)) < 1e-3 and np.max(np.abs(ny - uy)) < 1e-3
+
+
+def test_grs80_codes_use_their_own_flattening():
+    # 45 N, 3 degrees off the meridian: the northings of the two ellipsoids differ by 1.2e-4 m
+    wy = R.oracle_tm(45.0, 3.0, ellipsoid="WGS84")[1]
+    gx, gy = R.oracle_tm(45.0, 3.0, ellipsoid="GRS80")
+    assert abs(abs(gy - wy) - 1.2e-4) < 1e-5
+    for code, lon0 in ((26918, -75.0), (25832, 9.0)):
+        x, y = tr(4326, code, [lon0 + 3.0], [45.0])
+        assert abs(x[0] - R.FE - gx) <= 1e-6 and abs(y[0] - gy) <= 1e-6, (code, x[0] - R.FE - gx, y[0] - gy)
+        assert abs(y[0] - wy) > 5e-5, (code, y[0] - wy)
 
 
 def test_zone_to_zone_against_the_oracle():
@@ -110,8 +118,13 @@ def test_zone_to_zone_against_the_oracle():
 def test_outside_the_domain_is_nan():
     x, y = tr(4326, 32618, [-75.0, -75.0, -75.0 + 90.0, -75.0 + 89.0, 105.0, float("nan")],
               [90.5, -91.0, 10.0, 10.0, 10.0, 10.0])
-    assert np.isnan(x[[0, 1, 2, 4, 5]]).all() and np.isnan(y[[0, 1, 2, 4, 5]]).all()
-    assert np.isfinite(x[3]) and np.isfinite(y[3])              # |lon - lon0| < 90: inside
+    assert np.isnan(x).all() and np.isnan(y).all()              # 89 degrees off at latitude 10: far beyond the cut
+    # just inside the cut (eta' = 0.999999 at latitude 5): within the pin of the exact map
+    L = R.load_lattice()
+    i = int(np.argmax(np.where(L["inside"] & (L["lat"] == 5.0), L["eta"], -1.0)))
+    assert 0.99999 < L["eta"][i] < 1.0
+    x, y = tr(4326, 32618, [-75.0 + L["dlon"][i]], [5.0])
+    assert abs(x[0] - R.FE - L["tm_wgs84"][i, 0]) <= 1e-6 and abs(y[0] - L["tm_wgs84"][i, 1]) <= 1e-6
     x, y = tr(4326, 3857, [0.0, 0.0, 0.0], [90.0, -90.0, 89.0])
     assert np.isnan(x[:2]).all() and np.isnan(y[:2]).all() and np.isfinite(y[2])
     x, y = tr(4326, 4258, [10.0, 10.0], [91.0, 45.0])
@@ -195,3 +208,161 @@ def test_c_abi_descriptor_and_host_entry_point():
     A.check(L.pcr_hip_transform_xy_host(C.byref(s), C.byref(t), x.ctypes.data, y.ctypes.data, x.ctypes.data, y.ctypes.data, 2))
     ex, ey = R.oracle_utm(40.0, -74.0, 18)
     assert x[0] == 500000.0 and abs(x[1] - ex) < 1e-6 and abs(y[1] - ey) < 1e-6
+
+
+# ---- the whole domain, against the recorded oracle (tests/golden/reproject_lattice.npz) ---------------------------------
+@pytest.fixture(scope="module")
+def lattice():
+    return R.load_lattice()
+
+
+def test_the_cut_of_the_header_is_the_one_the_lattice_was_made_for(lattice):
+    import os
+    import re
+    hpp = os.path.join(os.path.dirname(R.__file__), "..", "pointcloud-raster_amd", "csrc", "reproject.hpp")
+    text = open(hpp).read()
+    cut = float(re.search(r"kTmEtaMax = ([0-9.eE+-]+);", text).group(1))
+    sinh_cut = float(re.search(r"kTmSinhEtaMax = ([0-9.eE+-]+);", text).group(1))
+    assert cut == float(lattice["eta_cut"]) and sinh_cut == float(mp.sinh(cut))
+    assert np.all(np.abs(lattice["eta"] / cut - 1.0) >= 0.999e-6)           # no point within 1e-6 (relative) of the cut
+
+
+def test_lattice_file_is_fresh(lattice):
+    # every 16th point recomputed live, bit for bit
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("make_reproject_lattice",
+                                                  os.path.join(os.path.dirname(R.__file__), "golden", "make_reproject_lattice.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    lat, dl = gen.points()
+    assert lat.tobytes() == lattice["lat"].tobytes() and dl.tobytes() == lattice["dlon"].tobytes()
+    idx = range(0, len(lat), 16)
+    live = gen.compute(lat, dl, idx)
+    for k, v in live.items():
+        assert v[::16].tobytes() == lattice[k][::16].tobytes(), k
+
+
+LATTICE_CODES = [(32631, "tm_wgs84", 3.0, False), (32731, "tm_wgs84", 3.0, True), (26918, "tm_grs80", -75.0, False),
+                 (25832, "tm_grs80", 9.0, False)]
+
+
+@pytest.mark.parametrize("code,key,lon0,south", LATTICE_CODES)
+def test_forward_and_inverse_against_the_lattice(lattice, code, key, lon0, south):
+    L = lattice
+    lat, dl, want = L["lat"], L["dlon"], L[key]
+    fn = 10000000.0 if south else 0.0
+    x, y = tr(4326, code, lon0 + dl, lat)
+    inside = L["inside"]
+    assert np.array_equal(np.isnan(x), ~inside) and np.array_equal(np.isnan(y), ~inside), "accepted region differs"
+    assert not np.isnan(want[inside]).any()
+    ex, ey = np.abs(x - R.FE - want[:, 0])[inside], np.abs(y - fn - want[:, 1])[inside]
+    worst = max(ex.max(), ey.max())
+    assert worst <= 1e-6, f"forward: worst {worst} m"
+    assert worst <= 2.5e-7, f"forward: worst {worst} m on the host: the cut leaves a factor 4 for another libm"
+    # inverse, from the oracle's coordinates: where the forward direction refuses the point, so does the inverse
+    have = L["oracle"]
+    lon2, lat2 = tr(code, 4326, R.FE + want[have, 0], fn + want[have, 1])
+    ins = inside[have]
+    assert np.array_equal(np.isnan(lon2), ~ins) and np.array_equal(np.isnan(lat2), ~ins), "inverse: accepted region differs"
+    dlon2 = (lon2 - lon0 - dl[have])[ins] * np.cos(np.radians(lat[have][ins]))
+    dlat2 = (lat2 - lat[have])[ins]
+    worst = max(np.abs(dlon2).max(), np.abs(dlat2).max())
+    assert worst <= 1e-10, f"inverse: worst {worst} degrees"
+    assert np.all((lon2[ins] > -180.0) & (lon2[ins] <= 180.0))
+
+
+def test_descriptors_of_every_supported_code():
+    import ctypes as C
+    from pcr import _cabi as A
+    lib = A.lib()
+    fw, fg = 1.0 / 298.257223563, 1.0 / 298.257222101
+    table = [(c, 3, -183.0 + 6.0 * (c - 32600), 0.0, fw) for c in range(32601, 32661)]
+    table += [(c, 3, -183.0 + 6.0 * (c - 32700), 10000000.0, fw) for c in range(32701, 32761)]
+    table += [(c, 3, -183.0 + 6.0 * (c - 26900), 0.0, fg) for c in range(26901, 26924)]
+    table += [(c, 3, -183.0 + 6.0 * (c - 25800), 0.0, fg) for c in range(25828, 25839)]
+    table += [(4326, 1, 0.0, 0.0, fw), (4269, 1, 0.0, 0.0, fg), (4258, 1, 0.0, 0.0, fg), (3857, 2, 0.0, 0.0, 0.0)]
+    for code, kind, lon0, fn, f in table:
+        d = A.CrsDesc()
+        assert lib.pcr_hip_crs_from_epsg(code, C.byref(d)) == 0, code
+        assert (d.epsg, d.kind, d.lon0, d.fn, d.f, d.a) == (code, kind, lon0, fn, f, 6378137.0), code
+        if kind == 3:
+            assert d.k0 == 0.9996 and d.fe == 500000.0 and abs(d.e - math.sqrt(f * (2 - f))) < 1e-17, code
+    for code in (32600, 32661, 32700, 32761, 26900, 26924, 25827, 25839):
+        d = A.CrsDesc()
+        assert lib.pcr_hip_crs_from_epsg(code, C.byref(d)) == 6, code       # PCR_HIP_NOT_IMPLEMENTED
+        assert str(code).encode() in lib.pcr_hip_last_error()
+
+
+def test_the_antimeridian():
+    for code, zone in ((32601, 1), (32660, 60)):
+        lon0 = R.utm_lon0(zone)
+        for lon in (179.5, -179.5):
+            dl = (lon - lon0 + 180.0) % 360.0 - 180.0
+            assert abs(dl) in (2.5, 3.5)
+            x, y = tr(4326, code, [lon], [40.0])
+            ex, ey = R.oracle_tm(40.0, dl)
+            assert abs(x[0] - R.FE - ex) <= 1e-6 and abs(y[0] - ey) <= 1e-6, (code, lon)
+            lon2, lat2 = tr(code, 4326, [R.FE + ex], [ey])
+            assert -180.0 < lon2[0] <= 180.0 and abs(lon2[0] - lon) <= 1e-10 and abs(lat2[0] - 40.0) <= 1e-10, (code, lon, lon2)
+    # 32601 -> 32660 across the seam
+    ax, ay = R.oracle_tm(40.0, -3.5)
+    bx, by = R.oracle_tm(40.0, 2.5)
+    x, y = tr(32601, 32660, [R.FE + ax], [ay])
+    assert abs(x[0] - R.FE - bx) <= 1e-6 and abs(y[0] - by) <= 1e-6
+
+
+def test_the_poles():
+    for ell, code in (("WGS84", 32631), ("GRS80", 25832)):
+        q = float(R.oracle_quarter_meridian(ell))
+        x, y = tr(4326, code, [3.0, -120.0, 179.0, 9.0], [90.0, 90.0, 90.0, 90.0])
+        assert np.max(np.abs(x - R.FE)) <= 1e-6 and np.max(np.abs(y - q)) <= 1e-6, (x - R.FE, y - q)
+        lon2, lat2 = tr(code, 4326, [R.FE], [q])
+        assert abs(lat2[0] - 90.0) <= 1e-10
+    q = float(R.oracle_quarter_meridian("WGS84"))
+    x, y = tr(4326, 32731, [3.0, 77.0], [-90.0, -90.0])
+    assert np.max(np.abs(x - R.FE)) <= 1e-6 and np.max(np.abs(y - (10000000.0 - q))) <= 1e-6
+    x, y = tr(4326, 3857, [3.0, 3.0], [90.0, -90.0])
+    assert np.isnan(x).all() and np.isnan(y).all()
+    # beyond the pole, and far beyond the series: the inverse refuses what the forward direction would
+    lon2, lat2 = tr(32631, 4326, [500000.0, 2e7, 500000.0, 600000.0], [1.2e7, 0.0, -1.2e7, q + 1.0])
+    assert np.isnan(lon2).all() and np.isnan(lat2).all(), (lon2, lat2)
+
+
+WM_Y_RTOL = 1.4e-12  # beyond 85 degrees: 4 x the worst relative error of the host form against mpmath, 3.33e-13 at 89.999
+
+
+def test_web_mercator_against_the_lattice(lattice):
+    L = lattice
+    m = ~np.isnan(L["wm"][:, 0])
+    lat, lon, want = L["lat"][m], float(L["wm_lon0"]) + L["dlon"][m], L["wm"][m]
+    x, y = tr(4326, 3857, lon, lat)
+    assert np.max(np.abs(x - want[:, 0])) <= 1e-8
+    low = np.abs(lat) <= 85.0
+    assert np.max(np.abs(y - want[:, 1])[low]) <= 1e-7
+    rel = np.abs(y[~low] / want[~low, 1] - 1.0)
+    assert (~low).sum() >= 100 and rel.max() <= WM_Y_RTOL, f"worst relative error of y beyond 85 degrees: {rel.max()}"
+    lon2, lat2 = tr(3857, 4326, want[:, 0], want[:, 1])
+    assert np.max(np.abs(lon2 - lon)) <= 1e-11 and np.max(np.abs(lat2 - lat)) <= 1e-11
+
+
+PAIRS = [(4326, 32631), (32631, 4326), (32631, 32632), (4326, 3857), (3857, 4326), (3857, 32631), (32631, 3857), (4326, 4269)]
+
+
+@pytest.mark.parametrize("src,dst", PAIRS)
+def test_non_finite_input_is_nan_on_both_axes(src, dst):
+    good = {4326: (4.0, 40.0), 3857: (445277.96, 4865942.28), 32631: (585360.46, 4428236.06)}[src]
+    for bad in (float("nan"), float("inf"), float("-inf")):
+        for axis in (0, 1):
+            p = list(good)
+            p[axis] = bad
+            x, y = tr(src, dst, [good[0], p[0]], [good[1], p[1]])
+            assert np.isfinite(x[0]) and np.isfinite(y[0])
+            assert math.isnan(x[1]) and math.isnan(y[1]), (src, dst, bad, axis, x[1], y[1])
+
+
+def test_the_domain_edges_by_exact_inputs():
+    dl, lat, ok = R.edge_inputs()
+    for code, lon0 in ((32631, 3.0), (32601, -177.0)):
+        x, y = tr(4326, code, lon0 + dl, lat)
+        assert np.array_equal(np.isfinite(x), ok) and np.array_equal(np.isfinite(y), ok), (code, x, y)
