@@ -552,6 +552,41 @@ int pcr_hip_ground_filter(const float* src, float* dst, int width, int height, i
 int pcr_hip_band_difference(const float* top, const float* ground, float* dst, int width, int height, int64_t top_stride,
                             int64_t ground_stride, int64_t dst_stride, pcr_hip_stream s);
 
+/* ---- terrain bands of one band (pcr/core/terrain.h: terrain; what gdaldem derives from a DEM), every product asked for in
+ *      one launch that reads src once.  a b c / d e f / g h i is the 3 x 3 window around cell e, row a b c being image row
+ *      r - 1.  NaN is "no data"; every NaN stored is 0x7FC00000.  A neighbour outside the image or NaN is missing: with
+ *      edges = 0 (gdaldem's default) a cell with any missing neighbour is NaN, with edges = 1 (gdaldem -compute_edges) a
+ *      missing neighbour takes e's value; e NaN gives NaN in both.
+ *        Gradients (Horn), binary64, additions in this order, never fused:  GX = ((c + 2f) + i) - ((a + 2d) + g),
+ *        GY = ((a + 2b) + c) - ((g + 2h) + i), p = GX * kx with kx = z_factor / (8.0 * cell_size_x), q = GY * ky with
+ *        ky = z_factor / (-8.0 * cell_size_y), s2 = p*p + q*q.  The cell sizes are signed: on a north-up grid
+ *        (cell_size_y < 0) p is dz/dEast and q is dz/dNorth.
+ *        SLOPE_DEGREES  atan_deg((float)sqrt(s2));  SLOPE_PERCENT  (float)(100.0 * sqrt(s2))
+ *        ASPECT         compass bearing of the downslope direction (-p, -q) in [0, 360), -1.0f where p == 0 and q == 0:
+ *                       t = atan_deg((float)(|p| / |q|)); q <= 0: p > 0 ? 360 - t : t; q > 0: p > 0 ? 180 + t : 180 - t, in
+ *                       binary32; 360 becomes 0
+ *        HILLSHADE      L = (sin_alt - (p * ls + q * lc)) / sqrt(1.0 + s2); 1.0f when L <= 0, else (float)(1.0 + 254.0 * L);
+ *                       ls = cos_alt * sin_az, lc = cos_alt * cos_az (pcr::terrain_light: the device evaluates no sine)
+ *        TRI            (float)((|a-e| + |b-e| + |c-e| + |d-e| + |f-e| + |g-e| + |h-e| + |i-e|) / 8.0), binary64, left to right
+ *        TPI            (float)(e - (a + b + c + d + f + g + h + i) / 8.0), binary64, left to right
+ *        ROUGHNESS      max9 - min9, one binary32 subtraction; the maximum starts at a and takes b .. i in turn when greater,
+ *                       the minimum when less
+ *        sqrt and / are correctly rounded; atan_deg is Cephes' atanf (reduction at tan pi/8 and tan 3pi/8, 4-term odd
+ *        polynomial) times 57.29577951308232f in binary32 multiplications, additions and divisions, each rounded
+ *        (csrc/terrain.hpp).  +-Inf and denormals are values.
+ *      products: a HOST array of n_products (1..7) distinct PCR_HIP_TERRAIN_* ids; dsts, dst_strides: HOST arrays, the band of
+ *      each.  src and every dst: `height` rows of `width` floats, strides in floats (any 4-byte alignment; when the rows of all
+ *      of them start on 16 bytes the 16-byte accesses are taken).  No dst may overlap src or another dst.  cell sizes and
+ *      z_factor finite and not zero.  Argument errors are reported before any HIP call.  Enqueued on s; nothing is allocated
+ *      or synchronised. */
+enum {
+    PCR_HIP_TERRAIN_SLOPE_DEGREES = 0, PCR_HIP_TERRAIN_SLOPE_PERCENT = 1, PCR_HIP_TERRAIN_ASPECT = 2, PCR_HIP_TERRAIN_HILLSHADE = 3,
+    PCR_HIP_TERRAIN_TRI = 4, PCR_HIP_TERRAIN_TPI = 5, PCR_HIP_TERRAIN_ROUGHNESS = 6, PCR_HIP_TERRAIN_COUNT = 7
+};
+int pcr_hip_terrain(const float* src, int width, int height, int64_t src_stride, int n_products, const int* products,
+                    float* const* dsts, const int64_t* dst_strides, double cell_size_x, double cell_size_y, double z_factor,
+                    int edges, double sin_alt, double ls, double lc, pcr_hip_stream s);
+
 /* ---- LAS point records -> the SoA cloud (pcr/io/point_cloud_io.h: LAS input).  No reference counterpart: the reference
  *      declares the format and reads `.las` tiles through laspy in a script.  ASPRS LAS 1.0-1.4, point data record formats
  *      0-10, little-endian, array-of-structures: int32 X, Y, Z, then packed attributes (csrc/las_decode.hpp holds the table).

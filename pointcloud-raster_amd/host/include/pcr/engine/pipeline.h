@@ -10,6 +10,7 @@
 
 #include "pcr/core/grid_config.h"
 #include "pcr/core/ground_filter.h"
+#include "pcr/core/terrain.h"
 #include "pcr/core/types.h"
 #include "pcr/engine/filter.h"
 #include "pcr/engine/glyph.h"
@@ -47,6 +48,13 @@ struct GroundFilterConfig : GroundFilterSpec {
     std::string top_band;                // hag = this band - DTM, normally a Max band; empty: no hag band
     std::string dtm_band_name = "dtm";   // the name of the appended DTM band
     std::string hag_band_name = "hag";   // the name of the appended hag band
+};
+
+/// One entry of PipelineConfig::terrain: one terrain band (pcr/core/terrain.h) appended at finalize().
+struct TerrainBandConfig : TerrainSpec {
+    std::string source_band;             // any band of the result by name, the ground filter's DTM and hag bands included
+    TerrainProduct product = TerrainProduct::Hillshade;
+    std::string band_name;               // default "{source_band}_{terrain_product_name(product)}"
 };
 
 struct PipelineConfig {
@@ -113,6 +121,13 @@ struct PipelineConfig {
     // filled.  result(), the GeoTIFF and its overview levels carry the new bands as ordinary bands; the accumulation state
     // is untouched.  Empty source_band: nothing is allocated or launched.  A row-block shard refuses it.
     GroundFilterConfig ground;
+    // Terrain bands: finalize() appends, behind the ground filter's bands and in list order, one band per entry -- a product of
+    // pcr/core/terrain.h of the named band AS IT LEAVES the pipeline (filled: a hillshade of the filled DTM is the product
+    // wanted), with the grid's signed cell sizes.  The new bands are never filled themselves.  Entries that share source,
+    // z_factor and compute_edges cost one sweep over the source.  result(), the GeoTIFF and its overview levels carry them as
+    // ordinary bands ("average" overviews of an aspect band are not meaningful near north); the accumulation state is
+    // untouched.  Empty: nothing is allocated or launched.  A row-block shard refuses it.
+    std::vector<TerrainBandConfig> terrain;
     // ingest_file of a LAS file: subtracted from the GPS time, in Float64, before it becomes the Float32 `gps_time` channel
     // (LasOptions::gps_time_origin; a MostRecent timestamp needs it: Float32 resolves 32 s at 3e8 s).
     double las_gps_time_origin = 0.0;

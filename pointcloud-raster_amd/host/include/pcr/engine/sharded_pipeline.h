@@ -84,6 +84,7 @@ private:
     bool write_cog_ = false;          // ... with overview levels
     int fill_nodata_radius_ = 0;      // ... its NaN cells filled first (PipelineConfig::fill_nodata_radius, taken off the ranks' configuration)
     GroundFilterConfig ground_;       // ... and the ground filter applied before the fill (PipelineConfig::ground, taken off likewise)
+    std::vector<TerrainBandConfig> terrain_;   // ... and the terrain bands derived behind the fill (PipelineConfig::terrain, likewise)
     std::string state_dir_;
     std::vector<ReductionSpec> reductions_;
     CRS target_crs_;                  // with auto_reproject_: ingest_unrouted reprojects before it routes

@@ -6,6 +6,7 @@
 #include "device_pipeline.h"
 #include "fill_nodata.h"
 #include "ground_filter.h"
+#include "terrain.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -164,6 +165,7 @@ std::unique_ptr<Pipeline> Pipeline::Banded::visit(size_t b, Status* st, bool* wa
     c.output_path.clear();
     c.fill_nodata_radius = 0;                         // (a band lacks its neighbours' rows: finalize() fills the assembled grid)
     c.ground = GroundFilterConfig();                  // (... and filters it)
+    c.terrain.clear();                                // (... and derives the terrain bands)
     c.state_dir.clear();
     c.resume = false;
     c.exec_mode = ExecutionMode::GPU;
@@ -302,8 +304,11 @@ Status Pipeline::Banded::finalize() {
     detail::GroundPlan ground;
     Status gs = detail::plan_ground(cfg, &ground);
     if (!gs.ok()) return gs;
-    const size_t n_out = descs.size();                // (the ground filter's bands follow: no band visit makes them)
+    detail::TerrainPlan terrain;
+    if (!(gs = detail::plan_terrain(cfg, ground, &terrain)).ok()) return gs;
+    const size_t n_out = descs.size();                // (the ground filter's and the terrain bands follow: no band visit makes them)
     detail::append_ground_bands(ground, descs);
+    detail::append_terrain_bands(terrain, descs);
     if (!result) result = Grid::create(g.width, g.height, descs, MemoryLocation::Host);
     if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     tiles_active = 0;
@@ -334,7 +339,7 @@ Status Pipeline::Banded::finalize() {
     {                                                 // the result is assembled here, on the host: so are its ground filter and its fill
         std::vector<ReductionType> types;
         for (const auto& r : cfg.reductions) types.push_back(r.type);
-        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground);
+        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground, terrain);
         if (!fs.ok()) return fs;
     }
     finalized = true;

@@ -134,6 +134,7 @@ Status Pipeline::Impl::init() {
         outputs.push_back(o);
     }
     if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
+    if (!(s = detail::plan_terrain(cfg, ground, &terrain)).ok()) return s;
 
     // row window of this device
     int r0 = 0, r1 = g.height;
@@ -233,6 +234,34 @@ Status Pipeline::Impl::finalize_ground(bool* enqueued) {
     s = detail::hip_status(pcr_hip_band_difference(bands[(size_t)ground.top].out, bands[dtm].out, bands[hag].raw, W, rows, W, W, W,
                                                    stream));
     return s.ok() ? band_leaves(hag, enqueued) : s;
+}
+// Behind everything that makes a source band, on the pipeline's stream: one launch per group of entries, reading the source
+// band as it leaves the pipeline (`out`: filled) and storing the new bands, which then leave as they are.
+Status Pipeline::Impl::finalize_terrain(bool* enqueued) {
+    const int rows = own_rows(), W = hg.width;
+    const size_t first = outputs.size() + (size_t)ground.extra_bands();
+    for (const auto& l : terrain.launches) {
+        const auto& f = terrain.bands[(size_t)l.front()];
+        const TerrainSpec& spec = terrain.spec_of(l);
+        const TerrainLight light = terrain_light((double)spec.azimuth, (double)spec.altitude);
+        std::vector<int> products;
+        std::vector<float*> dsts;
+        std::vector<int64_t> strides;
+        for (int m : l) {
+            products.push_back(terrain.bands[(size_t)m].product);
+            dsts.push_back(bands[first + (size_t)m].raw);
+            strides.push_back(W);
+        }
+        *enqueued = true;
+        Status s = detail::hip_status(pcr_hip_terrain(bands[(size_t)f.source].out, W, rows, W, (int)l.size(), products.data(),
+                                                      dsts.data(), strides.data(), terrain.cell_size_x, terrain.cell_size_y,
+                                                      (double)f.spec.z_factor, f.spec.compute_edges ? 1 : 0, light.sin_alt, light.ls,
+                                                      light.lc, stream));
+        for (int m : l)
+            if (s.ok()) s = band_leaves(first + (size_t)m, enqueued);
+        if (!s.ok()) return s;
+    }
+    return Status::success();
 }
 Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
     return detail::hip_status(pcr_hip_engine_tile_touched(engine, d, tx, ty));
@@ -784,6 +813,7 @@ Status Pipeline::Impl::allocate_result() {
     }
     if (descs.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     detail::append_ground_bands(ground, descs);
+    detail::append_terrain_bands(terrain, descs);
     if (rows <= 0) { result.reset(); return Status::success(); }
     const bool on_device = cfg.result_location == MemoryLocation::Device;
     result = on_device ? Grid::create(W, rows, descs, MemoryLocation::Device)
@@ -791,7 +821,7 @@ Status Pipeline::Impl::allocate_result() {
     if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     // the table of leaving bands and the buffers behind it: the rule (device_pipeline.h, LeavingBand) applied once
     const size_t n_out = outputs.size();
-    bands.assign(n_out + (size_t)ground.extra_bands(), LeavingBand{});
+    bands.assign(n_out + (size_t)ground.extra_bands() + (size_t)terrain.extra_bands(), LeavingBand{});
     band_buffers.clear();
     Status s = Status::success();
     auto owned = [&]() -> float* {
@@ -881,6 +911,7 @@ Status Pipeline::Impl::finalize(bool wait) {
             if (!(s = band_leaves(r, &enqueued)).ok()) return s;
     }
     if (!(s = finalize_ground(&enqueued)).ok()) return s;
+    if (!(s = finalize_terrain(&enqueued)).ok()) return s;
     // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
     // kernels on the same stream; only the levels (a third of the data) cross the bus, the host never halves the grid.
     std::vector<std::unique_ptr<Grid>> levels;

@@ -8,6 +8,7 @@
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
+#include "terrain.h"
 
 #include <chrono>
 #include <map>
@@ -73,9 +74,10 @@ struct Pipeline::Impl {
     bool own_stream = false;
     std::vector<Group> groups;
     std::vector<Output> outputs;
-    // Which memory a band is.  One row per band of the result grid -- the outputs, then the DTM, then the hag band -- built
-    // once by allocate_result(); everything else only reads it.  A band is FILLED iff fill_nodata_radius > 0 and it is an
-    // output with fills_nodata(type), or it is the DTM; the hag band never is.  Device result: `out` is the result grid's
+    // Which memory a band is.  One row per band of the result grid -- the outputs, then the DTM, then the hag band, then the
+    // terrain bands -- built once by allocate_result(); everything else only reads it.  A band is FILLED iff
+    // fill_nodata_radius > 0 and it is an output with fills_nodata(type), or it is the DTM; the hag band and the terrain bands
+    // never are.  Device result: `out` is the result grid's
     // band, `raw` is `out` unless the band is filled, then an owned buffer.  Host result: `raw` is an owned buffer, `out` is
     // `raw` unless the band is filled, then a second owned buffer.  The fill and the ground filter read a raw band and write
     // another buffer, so the raw bands stay what the plane-state rules take them for: the table is no plane-state event.
@@ -89,6 +91,7 @@ struct Pipeline::Impl {
     std::vector<detail::Buffer> band_buffers;    // the owned buffers behind the table; a buffer's role is its place in the table
     detail::GroundPlan ground;               // PipelineConfig::ground, planned at init
     detail::Buffer d_ground_work;            // its workspace, allocated by the first finalize, grow-only
+    detail::TerrainPlan terrain;             // PipelineConfig::terrain, planned at init
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
                                              // both sides): the blocking finalize reads it after its synchronise and launches
@@ -149,6 +152,7 @@ struct Pipeline::Impl {
     static int own_plane(ReductionType t);
     Status band_leaves(size_t b, bool* enqueued);
     Status finalize_ground(bool* enqueued);
+    Status finalize_terrain(bool* enqueued);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
     bool offer_bands(size_t gi);
     Status unpack_select(Group& gr);

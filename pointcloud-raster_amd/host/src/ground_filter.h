@@ -173,11 +173,13 @@ inline void append_ground_bands(const GroundPlan& plan, std::vector<BandDesc>& b
 
 /// What follows the finalized bands of a host-resident result whose ground bands (if any) are its last: the ground filter on
 /// the RAW source band, fill_nodata (the DTM is filled like a Min band), then hag from the bands as they leave the pipeline.
-inline Status finish_result_host(Grid& grid, std::vector<ReductionType> types, int fill_radius, const GroundPlan& plan) {
+/// more_bands: bands that follow the ground filter's and are none of this function's business (terrain.h).
+inline Status finish_result_host(Grid& grid, std::vector<ReductionType> types, int fill_radius, const GroundPlan& plan,
+                                 int more_bands = 0) {
     const int w = grid.cols(), h = grid.rows();
     const int dtm = (int)types.size();
     if (plan.on) {
-        if (grid.num_bands() != dtm + plan.extra_bands() || !grid.band_f32(plan.source) || !grid.band_f32(dtm))
+        if (grid.num_bands() != dtm + plan.extra_bands() + more_bands || !grid.band_f32(plan.source) || !grid.band_f32(dtm))
             return Status::error(StatusCode::InvalidArgument, "pipeline: the result grid lacks the ground filter's bands");
         ground_filter_host(grid.band_f32(plan.source), grid.band_f32(dtm), w, h, w, w, (int)plan.radii.size(), plan.radii.data(),
                            plan.thresholds.data());
@@ -188,27 +190,6 @@ inline Status finish_result_host(Grid& grid, std::vector<ReductionType> types, i
     if (plan.on && plan.top >= 0)
         band_difference_host(grid.band_f32(plan.top), grid.band_f32(dtm), grid.band_f32(dtm + 1), w, h, w, w, w);
     return Status::success();
-}
-
-/// The gathered grid of a sharded run on rank 0 (the reductions' bands, on the host) as the unsharded pipeline `whole_cfg`
-/// would return it: the ground filter's bands appended, then finish_result_host.
-inline Status finish_gathered_host(std::unique_ptr<Grid>& whole, const PipelineConfig& whole_cfg) {
-    GroundPlan ground;
-    Status s = plan_ground(whole_cfg, &ground);
-    if (!s.ok()) return s;
-    if (ground.on) {
-        std::vector<BandDesc> descs;
-        for (int b = 0; b < whole->num_bands(); ++b) descs.push_back(whole->band_desc(b));
-        append_ground_bands(ground, descs);
-        std::unique_ptr<Grid> wider = Grid::create(whole->cols(), whole->rows(), descs, MemoryLocation::Host);
-        if (!wider) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate the ground filter's bands");
-        for (int b = 0; b < whole->num_bands(); ++b)
-            std::memcpy(wider->band_f32(b), whole->band_f32(b), (size_t)whole->cell_count() * sizeof(float));
-        whole = std::move(wider);
-    }
-    std::vector<ReductionType> types;
-    for (const auto& r : whole_cfg.reductions) types.push_back(r.type);
-    return finish_result_host(*whole, types, whole_cfg.fill_nodata_radius, ground);
 }
 
 }  // namespace detail

@@ -3,6 +3,7 @@
 
 #include "fill_nodata.h"
 #include "ground_filter.h"
+#include "terrain.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -179,6 +180,8 @@ Status Pipeline::Host::finalize() {
     detail::GroundPlan ground;
     Status gs = detail::plan_ground(cfg, &ground);
     if (!gs.ok()) return gs;
+    detail::TerrainPlan terrain;
+    if (!(gs = detail::plan_terrain(cfg, ground, &terrain)).ok()) return gs;
     if (!result) {
         std::vector<BandDesc> bands;
         for (const auto& o : outputs) {                              // band naming: pipeline.cpp:1175-1186
@@ -189,6 +192,7 @@ Status Pipeline::Host::finalize() {
             bands.push_back(b);
         }
         detail::append_ground_bands(ground, bands);
+        detail::append_terrain_bands(terrain, bands);
         result = Grid::create(g.width, g.height, bands, MemoryLocation::Host);
         if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     }
@@ -197,7 +201,7 @@ Status Pipeline::Host::finalize() {
     {                                                                // (the planes are the state: the bands are made anew by every finalize)
         std::vector<ReductionType> types;
         for (const auto& o : outputs) types.push_back(o.type);
-        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground);
+        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground, terrain);
         if (!fs.ok()) return fs;
     }
     finalized = true;

@@ -15,6 +15,7 @@
 #include "banded_pipeline.h"
 #include "device_pipeline.h"
 #include "ground_filter.h"
+#include "terrain.h"
 #include "host_pipeline.h"
 #include "las_io.h"
 #include "pcr/core/point_cloud.h"
@@ -83,6 +84,9 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         detail::GroundPlan plan;                      // (every engine plans again for itself: here only the refusals)
         const Status gs = detail::plan_ground(config, &plan);
         if (!gs.ok()) return fail_with(gs);
+        detail::TerrainPlan terrain;
+        const Status ts = detail::plan_terrain(config, plan, &terrain);
+        if (!ts.ok()) return fail_with(ts);
     }
     size_t budget = 0;
     if (Banded::needed(config, &budget)) {

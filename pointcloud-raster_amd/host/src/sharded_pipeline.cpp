@@ -10,6 +10,7 @@
 #include "buffer.h"
 #include "fill_nodata.h"
 #include "ground_filter.h"
+#include "terrain.h"
 #include "pcr/core/grid.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/core/reproject.h"
@@ -76,8 +77,17 @@ std::unique_ptr<ShardedPipeline> ShardedPipeline::create(PipelineConfig cfg, con
             g_create_error = "ShardedPipeline: " + gs.message;
             return nullptr;
         }
+        // ... and the terrain bands, which are derived from the gathered, filtered and filled grid
+        detail::TerrainPlan terrain;
+        const Status ts = detail::plan_terrain(whole, plan, &terrain);
+        if (!ts.ok()) {
+            g_create_error = "ShardedPipeline: " + ts.message;
+            return nullptr;
+        }
         sp->ground_ = cfg.ground;
         cfg.ground = GroundFilterConfig();
+        sp->terrain_ = cfg.terrain;
+        cfg.terrain.clear();
     }
     sp->state_dir_ = cfg.state_dir;
     sp->reductions_ = cfg.reductions;
@@ -183,6 +193,7 @@ Status ShardedPipeline::finalize() {
         whole_cfg.reductions = reductions_;
         whole_cfg.fill_nodata_radius = fill_nodata_radius_;
         whole_cfg.ground = ground_;
+        whole_cfg.terrain = terrain_;
         if (!(s = detail::finish_gathered_host(whole, whole_cfg)).ok()) return s;
     }
     return write_geotiff(output_path_, *whole, grid_, pipeline_output_options(write_cog_));

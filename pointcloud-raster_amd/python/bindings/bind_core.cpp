@@ -6,11 +6,15 @@
 #include "pcr/core/ground_filter.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/core/reproject.h"
+#include "pcr/core/terrain.h"
 #include "pcr/engine/pipeline.h"
 #include "pcr_hip.h"
 #include "../../host/src/pipeline_common.h"
+#include "../../host/src/terrain.h"
 
 #include <cstring>
+
+#include <omp.h>
 
 using namespace pcr;
 
@@ -135,6 +139,23 @@ void bind_core(py::module_& m) {
         .def_readwrite("slope", &GroundFilterSpec::slope)
         .def_readwrite("initial_distance", &GroundFilterSpec::initial_distance)
         .def_readwrite("max_distance", &GroundFilterSpec::max_distance);
+
+    // extension: the terrain bands (pcr.terrain, PipelineConfig.terrain)
+    py::enum_<TerrainProduct>(m, "TerrainProduct")
+        .value("SlopeDegrees", TerrainProduct::SlopeDegrees).value("SlopePercent", TerrainProduct::SlopePercent)
+        .value("Aspect", TerrainProduct::Aspect).value("Hillshade", TerrainProduct::Hillshade)
+        .value("TRI", TerrainProduct::TRI).value("TPI", TerrainProduct::TPI).value("Roughness", TerrainProduct::Roughness);
+    py::class_<TerrainSpec>(m, "TerrainSpec")
+        .def(py::init<>())
+        .def_readwrite("z_factor", &TerrainSpec::z_factor)
+        .def_readwrite("compute_edges", &TerrainSpec::compute_edges)
+        .def_readwrite("azimuth", &TerrainSpec::azimuth)
+        .def_readwrite("altitude", &TerrainSpec::altitude);
+    m.def("terrain_light", [](double azimuth, double altitude) {
+        const TerrainLight l = terrain_light(azimuth, altitude);
+        return py::make_tuple(l.sin_alt, l.ls, l.lc);
+    }, py::arg("azimuth") = 315.0, py::arg("altitude") = 45.0,
+       "(sin_alt, cos_alt * sin_az, cos_alt * cos_az): the binary64 hillshade constants every engine uses");
 
     py::class_<GridConfig>(m, "GridConfig")
         .def(py::init<>())
@@ -358,4 +379,47 @@ void bind_core(py::module_& m) {
         if (!rp.needed) return py::none();
         return py::cast(rp.dst_crs);
     });
+
+    // extension: the terrain bands of a grid's band, where the grid lives (a Device grid: in HBM)
+    m.def("terrain", [](const Grid& grid, int band, const std::vector<TerrainProduct>& products, py::object spec, double cell_size_x,
+                        double cell_size_y) {
+        Status s;
+        auto out = terrain(grid, band, products, spec.is_none() ? TerrainSpec() : spec.cast<TerrainSpec>(), cell_size_x, cell_size_y,
+                           &s, nullptr);
+        raise_if_error(s);
+        return out;
+    }, py::arg("grid"), py::arg("band"), py::arg("products"), py::arg("spec") = py::none(), py::arg("cell_size_x") = 1.0,
+       py::arg("cell_size_y") = -1.0);
+    // (tests, tools) the host loop on an array, which the kernel is compared with; -> [len(products), h, w]
+    m.def("_terrain_host", [](py::array_t<float, py::array::c_style | py::array::forcecast> src, const std::vector<TerrainProduct>& products,
+                              py::object spec_in, double cell_size_x, double cell_size_y, int threads) {
+        if (src.ndim() != 2 || src.shape(0) < 1 || src.shape(1) < 1) throw std::invalid_argument("terrain: a 2-D array is needed");
+        const TerrainSpec spec = spec_in.is_none() ? TerrainSpec() : spec_in.cast<TerrainSpec>();
+        const std::string bad = detail::terrain_spec_error(spec);
+        if (!bad.empty()) throw std::invalid_argument("terrain: " + bad);
+        if (!detail::terrain_cell_sizes_ok(cell_size_x, cell_size_y)) throw std::invalid_argument("terrain: cell sizes must be finite and not zero");
+        unsigned mask = 0;
+        std::vector<int> ids;
+        for (TerrainProduct p : products) {
+            if (!terrain_product_name(p)[0] || (mask & (1u << (int)p))) throw std::invalid_argument("terrain: unknown or duplicate product");
+            mask |= 1u << (int)p;
+            ids.push_back((int)p);
+        }
+        if (ids.empty()) throw std::invalid_argument("terrain: no product asked for");
+        const int h = (int)src.shape(0), w = (int)src.shape(1);
+        py::array_t<float> out({(py::ssize_t)ids.size(), (py::ssize_t)h, (py::ssize_t)w});
+        std::vector<float*> dsts;
+        std::vector<int64_t> strides;
+        for (size_t k = 0; k < ids.size(); ++k) {
+            dsts.push_back(out.mutable_data() + k * (size_t)h * w);
+            strides.push_back(w);
+        }
+        const int before = omp_get_max_threads();
+        if (threads > 0) omp_set_num_threads(threads);
+        detail::terrain_host(src.data(), w, h, w, (int)ids.size(), ids.data(), dsts.data(), strides.data(),
+                             detail::terrain_consts(spec, cell_size_x, cell_size_y), spec.compute_edges ? 1 : 0);
+        omp_set_num_threads(before);
+        return out;
+    }, py::arg("src"), py::arg("products"), py::arg("spec") = py::none(), py::arg("cell_size_x") = 1.0, py::arg("cell_size_y") = -1.0,
+       py::arg("threads") = 0);
 }

@@ -8,6 +8,7 @@
 #include "pcr/engine/pipeline.h"
 #include "pcr/engine/sharded_pipeline.h"
 #include "../../host/src/ground_filter.h"
+#include "../../host/src/terrain.h"
 
 using namespace pcr;
 
@@ -83,6 +84,13 @@ void bind_engine(py::module_& m) {
         .def_readwrite("dtm_band_name", &GroundFilterConfig::dtm_band_name)
         .def_readwrite("hag_band_name", &GroundFilterConfig::hag_band_name);
 
+    py::class_<TerrainBandConfig, TerrainSpec>(m, "TerrainBandConfig")
+        .def(py::init<>())
+        .def(py::init<const TerrainBandConfig&>())
+        .def_readwrite("source_band", &TerrainBandConfig::source_band)
+        .def_readwrite("product", &TerrainBandConfig::product)
+        .def_readwrite("band_name", &TerrainBandConfig::band_name);
+
     py::class_<PipelineConfig>(m, "PipelineConfig")
         .def(py::init<>())
         .def_readwrite("grid", &PipelineConfig::grid)
@@ -114,6 +122,7 @@ void bind_engine(py::module_& m) {
         .def_readwrite("finalize_with_first_ingest", &PipelineConfig::finalize_with_first_ingest)
         .def_readwrite("fill_nodata_radius", &PipelineConfig::fill_nodata_radius)
         .def_readwrite("ground", &PipelineConfig::ground)
+        .def_readwrite("terrain", &PipelineConfig::terrain)
         .def_readwrite("las_gps_time_origin", &PipelineConfig::las_gps_time_origin);
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
@@ -218,8 +227,9 @@ void bind_engine(py::module_& m) {
         .def("out_of_core", &Pipeline::out_of_core,
              "True when the grid's state exceeds gpu_memory_budget and the pipeline sweeps it in row bands of whole reference-tile rows");
 
-    // pcr.distributed: what rank 0 does to the gathered grid -- PipelineConfig.ground, then fill_nodata_radius -- and the check
-    // of PipelineConfig.ground that Pipeline.create makes (the ranks' own configurations carry neither field)
+    // pcr.distributed: what rank 0 does to the gathered grid -- PipelineConfig.ground, then fill_nodata_radius, then
+    // PipelineConfig.terrain -- and the checks of PipelineConfig.ground and .terrain that Pipeline.create makes (the ranks' own
+    // configurations carry none of these fields)
     m.def("_finish_gathered", [](const Grid& gathered, const PipelineConfig& whole_cfg) {
         std::unique_ptr<Grid> whole = gathered.to(MemoryLocation::Host);
         if (!whole) throw std::runtime_error("pipeline: failed to copy the gathered grid");
@@ -229,6 +239,12 @@ void bind_engine(py::module_& m) {
     m.def("_check_ground", [](const PipelineConfig& whole_cfg) {
         detail::GroundPlan plan;
         raise_if_error(detail::plan_ground(whole_cfg, &plan));
+    }, py::arg("whole_cfg"));
+    m.def("_check_terrain", [](const PipelineConfig& whole_cfg) {
+        detail::GroundPlan ground;
+        detail::TerrainPlan plan;
+        raise_if_error(detail::plan_ground(whole_cfg, &ground));
+        raise_if_error(detail::plan_terrain(whole_cfg, ground, &plan));
     }, py::arg("whole_cfg"));
     m.def("pipeline_create_error", &pipeline_create_error,
           "Why the last Pipeline.create() on this thread returned None");

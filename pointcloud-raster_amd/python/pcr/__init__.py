@@ -75,6 +75,7 @@ from ._pcr import (  # noqa: E402,F401
     build_overviews, read_geotiff_overviews, fill_nodata,
     read_las,
     GroundFilterSpec, GroundFilterConfig, ground_filter, ground_filter_levels,
+    TerrainProduct, TerrainSpec, TerrainBandConfig, terrain, terrain_light,
 )
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
@@ -175,4 +176,5 @@ __all__ = [
     "build_overviews", "read_geotiff_overviews", "fill_nodata",
     "read_las",
     "GroundFilterSpec", "GroundFilterConfig", "ground_filter", "ground_filter_levels",
+    "TerrainProduct", "TerrainSpec", "TerrainBandConfig", "terrain", "terrain_light",
 ]

@@ -184,6 +184,8 @@ SYMBOLS = {
     "pcr_hip_ground_filter": [_VP, _VP, C.c_int, C.c_int, _I64, _I64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float), _VP, _SZ,
                               _VP],
     "pcr_hip_band_difference": [_VP, _VP, _VP, C.c_int, C.c_int, _I64, _I64, _I64, _VP],
+    "pcr_hip_terrain": [_VP, C.c_int, C.c_int, _I64, C.c_int, C.POINTER(C.c_int), C.POINTER(_VP), C.POINTER(_I64),
+                        C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, _VP],
     "pcr_hip_las_decode": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), _VP],
     "pcr_hip_las_decode_host": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), C.c_int],
 }

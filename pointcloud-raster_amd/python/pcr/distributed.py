@@ -322,7 +322,10 @@ class ShardedPipeline:
         # a row block lacks its neighbours' rows: rank 0 applies the ground filter to the gathered grid, before it fills it
         from . import _pcr
         _pcr._check_ground(cfg)                      # (RuntimeError with Pipeline.create's message)
+        _pcr._check_terrain(cfg)
         self.ground, cfg.ground = pcr.GroundFilterConfig(cfg.ground), pcr.GroundFilterConfig()
+        # ... and derives the terrain bands from it, behind the fill
+        self.terrain, cfg.terrain = [pcr.TerrainBandConfig(t) for t in cfg.terrain], []
         self._reductions = list(cfg.reductions)
         cfg.shard_row_begin, cfg.shard_row_end = self.own
         # ONE file for the whole grid, written by rank 0 from the gathered strips (the reference writes one file,
@@ -612,10 +615,11 @@ class ShardedPipeline:
         if self.output_path:
             import pcr
             whole = self.gather(0)
-            if self.rank == 0 and self.ground.source_band:
+            if self.rank == 0 and (self.ground.source_band or self.terrain):
                 from . import _pcr
                 whole_cfg = pcr.PipelineConfig()
                 whole_cfg.grid, whole_cfg.reductions, whole_cfg.ground = self.grid, self._reductions, self.ground
+                whole_cfg.terrain = self.terrain
                 whole_cfg.fill_nodata_radius = self.fill_nodata_radius
                 whole = _pcr._finish_gathered(whole, whole_cfg)
                 opts = pcr.GeoTiffOptions()
