@@ -831,7 +831,8 @@ Status Pipeline::Impl::allocate_result() {
         return static_cast<float*>(band_buffers.back().data());
     };
     for (size_t b = 0; b < bands.size() && s.ok(); ++b) {
-        const bool filled = cfg.fill_nodata_radius > 0 && (b < n_out ? detail::fills_nodata(outputs[b].type) : b == n_out);
+        // (behind the outputs only the DTM is filled: without a ground plan band n_out is the first terrain band)
+        const bool filled = cfg.fill_nodata_radius > 0 && (b < n_out ? detail::fills_nodata(outputs[b].type) : ground.on && b == n_out);
         float* const grid_band = on_device ? result->band_f32((int)b) : nullptr;
         bands[b].raw = on_device && !filled ? grid_band : owned();
         bands[b].out = !filled ? bands[b].raw : on_device ? grid_band : owned();

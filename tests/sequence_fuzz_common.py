@@ -12,7 +12,12 @@ binary32 in any order, Average is one binary32 division of two exact numbers, Ma
 
 The generator uses NumPy only (a seed means the same case on every machine).  The model uses no engine code except the host
 twins of the finishing steps, which the CPU suite holds to their own NumPy models: pcr.ground_filter, pcr.fill_nodata,
-overviews_common.pyramid; and the `.pcrt` writer for the reference checkpoint."""
+overviews_common.pyramid; and the `.pcrt` writer for the reference checkpoint.
+
+Every finalize plan also draws PipelineConfig::terrain (0 to 6 entries on any band that leaves, _draw_terrain): the model
+appends those bands by terrain_common.terrain, the NumPy restatement of the contract -- not pcr.terrain, so that the host-engine
+run holds the host loop's plumbing to something that shares no code with it.  Since every source band is exact here, the
+terrain bands of an Average source are held to the model on both engines too."""
 import filecmp
 import os
 
@@ -29,11 +34,30 @@ FILL_TYPES = ("Average", "Max", "Min", "MostRecent")
 OPS8 = ("Equal", "NotEqual", "Less", "LessEqual", "Greater", "GreaterEqual", "InSet", "NotInSet")
 # planes a reduction needs / its checkpoint holds, as slots (0 sum, 1 count, 2 max, 3 min; MostRecent: 0 value, 1 timestamp)
 PLANES_OF = {"Sum": (0,), "Count": (1,), "Max": (2,), "Min": (3,), "Average": (0, 1), "MostRecent": (0, 1)}
+# PipelineConfig::terrain: the products by terrain_product_name in TerrainProduct's order, and parameters that create accepts
+TERRAIN_PRODUCTS = ("slope", "slope_percent", "aspect", "hillshade", "tri", "tpi", "roughness")
+TERRAIN_Z = (1.0, 1.0, 2.0, 0.37)
+TERRAIN_LIGHTS = ((315.0, 45.0), (90.0, 30.0), (10.0, 80.0), (200.0, 60.0))
 
 # Seeds of the suite.  (a failing seed of a soak joins the list with a one-line comment)
 # 0..31, and the further seeds that the situations and the marks of tests/test_sequence_fuzz_host.py needed more of; 75 is a
 # second seed on which import_window without its bands_stale() fails
-DEFAULT_SEEDS = list(range(32)) + [47, 48, 49, 51, 54, 64, 75, 76]
+FIRST_SEEDS = list(range(32)) + [47, 48, 49, 51, 54, 64, 75, 76]     # (tests/golden/sequence_fuzz_cases.json pins what they mean)
+# ... and the seeds that the terrain situations needed more of (TERRAIN_SITUATIONS below)
+DEFAULT_SEEDS = FIRST_SEEDS + [
+    34,     # terrain of hag (none of the seeds before draws it), of the filled dtm and of a Min band, fill 3, in core
+    80,    # terrain bands in a GeoTIFF with a write_cog level; a terrain source in a group of 10 outputs, after a plane write
+    100,    # slope of the filled dtm (fill 8); two tri bands of one Count band under two names
+    123,    # out of core: terrain of hag with fill 3, finalized five times between merges
+    181,    # a slope_percent, aspect, hillshade (light 200 / 60) launch on a Sum band in a group of 10 outputs, Device result
+    255,    # 520 x 512 out of core: terrain bands in the write_cog level, hillshade second of its launch
+    265,    # write_cog level; the resuming pipeline's plan drops the five terrain bands
+    280,    # out of core: terrain of dtm with fill, a launch with its hillshade last, finalized again after load_state
+    538,    # the loading pipeline's plan turns hag and fill on: terrain of hag, Device result, another terrain list
+    640,    # terrain of a band that the first ingest stored, the finalize right behind it; hillshade not first of its launch
+    1076,   # terrain of a stored band, finalize right behind the first ingest, then again after a plane write
+    1088,   # terrain of a stored band and of the filled dtm, finalize right behind the first ingest
+]
 
 
 def seeds_from_env(name="PCR_SEQ_FUZZ_SEEDS"):
@@ -87,6 +111,52 @@ def _draw_plan(rng, specs, ooc, big):
     out = bool(rng.uniform() < (0.8 if big else 0.3))
     return dict(fill=int(rng.choice([0, 0, 1, 3, 8])), ground=ground,
                 loc="Host" if ooc else str(rng.choice(["Host", "Device"])), out=out, cog=out and bool(rng.uniform() < (0.9 if big else 0.5)))
+
+
+def terrain_band_name(t):
+    return t["name"] or f"{t['source']}_{t['product']}"
+
+
+def _draw_terrain(rng, specs, plan):
+    """PipelineConfig::terrain of a plan: 0 to 6 entries (none in four plans of ten), each a product of any band that leaves
+    under the plan.  Half of the entries copy source, z_factor and compute_edges from the entry before, so that launches of
+    several products form -- also ones whose Hillshade entry is not the first and has a light of its own.  Every entry draws
+    all its numbers, used or not: what one entry draws does not move the next."""
+    sources = [band_name(i, s) for i, s in enumerate(specs)]
+    if plan["ground"]:
+        sources += ["dtm"] + (["hag"] if plan["ground"]["top"] is not None else [])
+    n = 0 if rng.uniform() < 0.4 else int(rng.integers(1, 7))
+    out, taken = [], set(sources)
+    for k in range(n):
+        share = bool(rng.uniform() < 0.5) and k > 0
+        source, product = sources[int(rng.integers(0, len(sources)))], TERRAIN_PRODUCTS[int(rng.integers(0, 7))]
+        z, edges = TERRAIN_Z[int(rng.integers(0, 4))], bool(rng.uniform() < 0.5)
+        azimuth, altitude = TERRAIN_LIGHTS[int(rng.integers(0, 4))]
+        explicit = bool(rng.uniform() < 1 / 3)
+        if share:
+            source, z, edges = out[-1]["source"], out[-1]["z_factor"], out[-1]["edges"]
+        t = dict(source=source, product=product, name="", z_factor=z, edges=edges, azimuth=azimuth, altitude=altitude)
+        if explicit or terrain_band_name(t) in taken:                # (the same source and product under another light or z_factor)
+            t["name"] = f"t{k}"
+        taken.add(terrain_band_name(t))
+        out.append(t)
+    return out
+
+
+def terrain_launches(terrain):
+    """plan_terrain's launches: entries that share source, z_factor and compute_edges and name different products, each entry
+    into the first launch that takes it.  -> lists of indices"""
+    launches = []
+    for i, t in enumerate(terrain):
+        for l in launches:
+            f = terrain[l[0]]
+            if (f["source"], f["z_factor"], f["edges"]) == (t["source"], t["z_factor"], t["edges"]) and \
+                    all(terrain[m]["product"] != t["product"] for m in l):
+                l.append(i)
+                break
+        else:
+            launches.append([i])
+    return launches
 
 
 def _draw_flavour(rng):
@@ -313,7 +383,40 @@ def build(seed):
     case["marked"] = offered and first["shape"] != "hot"
     # ... or is offered them and splits a bin, so that the device's done word says no: the blocking finalize behind it reads 0
     case["split_first"] = offered and opening == "hot" and hot_records(case, first) > SPLIT_RECORDS
+    # the terrain bands of every plan, last and from generators of their own: no draw above moves, a seed stays the case it was
+    # (tests/golden/sequence_fuzz_cases.json).  k = 0: the opening plan; k = index + 1: the plan of the checkpoint at ops[index]
+    plan["terrain"] = _draw_terrain(np.random.default_rng((93000, seed, 0)), specs, plan)
+    for i, o in enumerate(ops):
+        if o["op"] == "checkpoint" and o["plan"] is not None:
+            o["plan"]["terrain"] = _draw_terrain(np.random.default_rng((93000, seed, i + 1)), specs, o["plan"])
     return case
+
+
+def case_digest(case):
+    """SHA-256 of what a seed means apart from the terrain lists: grid, specs, filter, flavour, fwfi, path, the opening plan and
+    the ops (with their plans) as sorted-key JSON, every cloud array's dtype and bytes, `marked` and `split_first`.
+    tests/golden/sequence_fuzz_cases.json holds it for the 40 seeds that were the suite before terrain was drawn."""
+    import hashlib
+    import json
+
+    def plain(v):
+        if isinstance(v, dict):
+            return {k: plain(w) for k, w in v.items() if k != "terrain"}
+        if isinstance(v, (list, tuple)):
+            return [plain(w) for w in v]
+        assert v is None or type(v) in (bool, int, float, str), type(v)
+        return v
+
+    h = hashlib.sha256()
+    head = {k: plain(case[k]) for k in ("grid", "specs", "filt", "flavour", "fwfi", "path", "plan", "ops", "marked", "split_first")}
+    h.update(json.dumps(head, sort_keys=True, allow_nan=False).encode())
+    for c in case["clouds"]:
+        h.update(c["shape"].encode())
+        for k in ("x", "y", "a", "b", "t", "cls"):
+            a = np.ascontiguousarray(c[k])
+            h.update(f"{k}:{a.dtype.str}:{a.shape}".encode())
+            h.update(a.tobytes())
+    return h.hexdigest()
 
 
 def keep_mask(filt, cls):
@@ -356,15 +459,17 @@ def defers_for_sure(case):
 
 
 def segments(case):
-    """The sequence cut at every checkpoint that a new pipeline resumes from: [(plan, flavour, ops, resumed plan differs)]."""
-    out, plan, flavour, cur, differs = [], case["plan"], case["flavour"], [], False
+    """The sequence cut at every checkpoint that a new pipeline resumes from: [(plan, flavour, ops, resumed plan differs,
+    the pipeline took the checkpoint (resume or load) under another terrain list)]."""
+    out, plan, flavour, cur, differs, terrain_differs = [], case["plan"], case["flavour"], [], False, False
     for o in case["ops"]:
         cur.append(o)
         if o["op"] == "checkpoint" and o["then"] != "go_on":
-            out.append((plan, flavour, cur, differs))
+            out.append((plan, flavour, cur, differs, terrain_differs))
             differs = o["plan"] is not None and any(o["plan"][k] != plan[k] for k in ("fill", "ground", "loc"))
+            terrain_differs = o["plan"] is not None and o["then"] in ("resume", "load") and o["plan"]["terrain"] != plan["terrain"]
             plan, flavour, cur = o["plan"] or plan, o["flavour"] or flavour, []
-    out.append((plan, flavour, cur, differs))
+    out.append((plan, flavour, cur, differs, terrain_differs))
     return out
 
 
@@ -378,10 +483,44 @@ def situations(case):
         found.add("a split bin in the offered first ingest")
     if any(len(gr["outs"]) > MAX_FINALIZE_OUTPUTS for gr in case["groups"]):
         found.add("more than 8 outputs in a group")
-    for s, (plan, flavour, ops, differs) in enumerate(segments(case)):
+    stored = [not gr["select"] and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS for gr in case["groups"]]
+    names = [band_name(i, sp) for i, sp in enumerate(case["specs"])]
+    for s, (plan, flavour, ops, differs, terrain_differs) in enumerate(segments(case)):
         ingests = finalizes = 0
+        terrain = plan["terrain"]
+        of_specs = [case["specs"][names.index(t["source"])] for t in terrain if t["source"] in names]
+        disturbed = False                                        # the state was changed from outside since this pipeline's last finalize
         for i, o in enumerate(ops):
             prev = ops[i - 1] if i else None
+            if o["op"] == "finalize" and terrain:
+                if case["marked"] and s == 0 and ingests == 1 and prev is not None and real(prev) and any(stored[sp["group"]] for sp in of_specs):
+                    found.add("terrain of a band that the first ingest stored, finalize right behind it")
+                if plan["fill"] > 0 and any(sp["type"] in FILL_TYPES for sp in of_specs):
+                    found.add("terrain of a filled band")
+                if plan["fill"] > 0 and any(t["source"] in ("dtm", "hag") for t in terrain):
+                    found.add("terrain of dtm or hag, filled")
+                for l in terrain_launches(terrain):
+                    hs = [m for m in l if terrain[m]["product"] == "hillshade"]
+                    light = lambda m: (terrain[m]["azimuth"], terrain[m]["altitude"])
+                    # (a light that is neither the default nor the first entry's: taking either instead shows)
+                    if len(l) >= 2 and hs and hs[0] != l[0] and light(hs[0]) not in (TERRAIN_LIGHTS[0], light(l[0])):
+                        found.add("a launch whose hillshade entry is not its first, light not the default")
+                if flavour["ooc"]:
+                    found.add("terrain out of core")
+                elif plan["loc"] == "Device":
+                    found.add("terrain with a Device result")
+                if case["big"] and plan["out"] and plan["cog"]:
+                    found.add("terrain in a GeoTIFF with a write_cog level")
+                if finalizes and disturbed:
+                    found.add("terrain finalized again after a plane write, merge_touched or load_state")
+                if any(len(case["groups"][sp["group"]]["outs"]) > MAX_FINALIZE_OUTPUTS for sp in of_specs):
+                    found.add("terrain source in a group of more than 8 outputs")
+            if o["op"] == "finalize":
+                if terrain_differs:                              # (bands added, dropped or changed: an empty list counts)
+                    found.add("resume or load under another terrain list")
+                disturbed = False
+            elif o["op"] in ("planes_write", "merge") and not flavour["ooc"] or o["op"] == "reload" and ingests:
+                disturbed = True
             if o["op"] == "finalize":
                 if case["fwfi"] and ingests == 1 and prev is not None and real(prev):
                     found.add("finalize right after the only ingest, finalize_with_first_ingest on")
@@ -428,6 +567,13 @@ SITUATIONS = ("finalize right after the only ingest, finalize_with_first_ingest 
               "hot spot", "ground + fill + a second ingest", "write_cog level", "more than 8 outputs in a group",
               "out of core with MostRecent", "out of core with ground or fill", "load_state over a state that was ingested into",
               "a split bin in the offered first ingest")
+TERRAIN_SITUATIONS = ("terrain of a band that the first ingest stored, finalize right behind it", "terrain of a filled band",
+                      "terrain of dtm or hag, filled", "a launch whose hillshade entry is not its first, light not the default",
+                      "terrain out of core", "resume or load under another terrain list",
+                      "terrain in a GeoTIFF with a write_cog level",
+                      "terrain finalized again after a plane write, merge_touched or load_state",
+                      "terrain source in a group of more than 8 outputs", "terrain with a Device result")
+SITUATIONS += TERRAIN_SITUATIONS
 
 
 # ---- the model -------------------------------------------------------------------------------------------------------------------
@@ -566,6 +712,16 @@ class Model:
             if plan["ground"]["top"] is not None:
                 out.append(G.difference(out[plan["ground"]["top"]], dtm))
                 names.append("hag")
+        # the terrain bands, in list order behind dtm / hag: each from its source band as it leaves (filled), by the NumPy
+        # restatement of the contract (no engine code but the light constants, which are the contract), never filled themselves
+        if plan.get("terrain"):
+            import terrain_common as T
+            leaving = dict(zip(names, out))
+            for t in plan["terrain"]:
+                out.append(T.terrain(leaving[t["source"]], [T.PRODUCTS[TERRAIN_PRODUCTS.index(t["product"])]], z_factor=t["z_factor"],
+                                     edges=t["edges"], azimuth=t["azimuth"], altitude=t["altitude"], cell_size_x=self.g["cs"],
+                                     cell_size_y=-self.g["cs"])[0])
+                names.append(terrain_band_name(t))
         return names, out
 
     def write_checkpoint(self, dirname):
@@ -633,6 +789,10 @@ def make_config(case, plan, flavour, exec_mode, engine, tmp_path, state_dir=None
         if plan["ground"]["top"] is not None:
             cfg.ground.top_band = band_name(plan["ground"]["top"], case["specs"][plan["ground"]["top"]])
         cfg.ground.max_radius_cells = plan["ground"]["maxr"]
+    if plan.get("terrain"):
+        import terrain_common as T
+        cfg.terrain = [T.band_cfg(t["source"], T.PRODUCTS[TERRAIN_PRODUCTS.index(t["product"])], t["name"], z_factor=t["z_factor"],
+                                  compute_edges=t["edges"], azimuth=t["azimuth"], altitude=t["altitude"]) for t in plan["terrain"]]
     ooc = flavour["ooc"] and engine == "hip"
     if plan["loc"] == "Device" and engine == "hip" and not ooc:
         cfg.result_location = pcr.MemoryLocation.Device
@@ -763,6 +923,8 @@ def check_sequence(seed, exec_mode, engine, tmp_path):
                 ptr = p.result_band_device_ptr(b)
                 assert ptr != 0, f"{at}: result_band_device_ptr({b})"
                 M.bits_equal(d2h(ptr, (H, W)), want[b], f"{at}, band {b} ({name}) of result_band_device_ptr")
+            if in_core_hip:
+                assert p.result_band_device_ptr(len(names)) == 0, f"{at}: result_band_device_ptr answers one past the last band"
             if plan["out"]:
                 tif = str(tmp_path / "out.tif")
                 levels = overview_level_count(W, H) if plan["cog"] else 0

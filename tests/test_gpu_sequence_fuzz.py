@@ -3,8 +3,10 @@ and flag pointers, flag unions and checkpoints on one pipeline, in core and out 
 tests/test_sequence_fuzz_host.py has pinned on the host engine.  What it is for is the layer that decides which buffer a kernel
 reads and whether it runs at all (the plane-state block of host/src/device_pipeline.cpp, LeavingBand{raw, out}): on the seeds
 the generator marks, the first ingest must have stored its bands (and left planes in them), so the sequence behind it walks the
-stale-band and plane-restore paths.  The 40 default seeds in the suite; PCR_SEQ_FUZZ_SEEDS=a:b soaks a range (or a,b,c: those
-seeds).  A failure names its seed, the index of the op and the band."""
+stale-band and plane-restore paths.  Every finalize plan carries a drawn PipelineConfig.terrain list, so the last rows of that
+table -- terrain bands of every kind of source, in core and out of core -- are held to the NumPy model of the contract too; the
+list does not switch the offer off, and the assertions on the marked seeds stand.  The 52 default seeds in the suite;
+PCR_SEQ_FUZZ_SEEDS=a:b soaks a range (or a,b,c: those seeds).  A failure names its seed, the index of the op and the band."""
 import pytest
 
 import pcr

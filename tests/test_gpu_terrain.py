@@ -253,6 +253,31 @@ def test_an_empty_list_changes_nothing(pipe_case, location):
 
 
 @pytest.mark.parametrize("location", LOCATIONS)
+def test_without_a_ground_plan_the_first_terrain_band_is_not_filled(location):
+    """fill_nodata_radius > 0 and no ground plan: the band behind the outputs is then the first terrain band, not the DTM, and
+    leaves as the kernel stored it (the table of leaving bands once took it for the DTM and filled it: seed 0 of the
+    operation-sequence fuzz).  Sparse points, so that no-data cells lie within the radius of valid ones; 72 x 40 is more than
+    one terrain tile each way."""
+    W, H = 72, 40
+    cfg = G.pipeline_cfg(W, H, GPU, ground=False, radius=2)
+    cfg.result_location = location
+    cfg.terrain = [T.band_cfg(G.BANDS[2], P.TRI, compute_edges=True), T.band_cfg(G.BANDS[1], P.SlopeDegrees, compute_edges=True),
+                   T.band_cfg(G.BANDS[2], P.Roughness)]
+    pipe = create(cfg)
+    pipe.ingest(G.cloud(W, H, 700, seed=84))
+    pipe.finalize()
+    names, got = names_of(pipe), result_bands(pipe)
+    assert names == list(G.BANDS) + [f"{G.BANDS[2]}_tri", f"{G.BANDS[1]}_slope", f"{G.BANDS[2]}_roughness"]
+    want = T.expect_bands(dict(zip(names[:3], got[:3])), cfg)
+    for b in range(3, 6):
+        M.bits_equal(got[b], want[b - 3], f"band {b} ({names[b]}) is the host loop of the source as it leaves")
+    # with compute_edges a cell is no data exactly where its source is: the Count band is not filled, so neither is its TRI
+    count_nan = np.isnan(got[2])
+    assert np.array_equal(np.isnan(got[3]), count_nan) and count_nan[:, :int(W * 0.9)].sum() > 200
+    assert np.isnan(got[0]).sum() < count_nan.sum()              # (the fill did run on the Min band)
+
+
+@pytest.mark.parametrize("location", LOCATIONS)
 def test_geotiff_and_overview_levels_hold_the_new_bands(tmp_path, location):
     Wc, Hc = 520, 512                                              # write_cog's rule gives a level only from 512 cells a side
     pts = G.cloud(Wc, Hc, 200_000, seed=83)
