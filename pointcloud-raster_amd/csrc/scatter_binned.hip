@@ -313,7 +313,32 @@ k_bin_scan(int nbins, int nvx, unsigned item_records, unsigned* __restrict__ bin
 // (C2), 27 % at 2816 bins (a C5 shard) and 35 % at 4096 bins (Gaussian index records).  Two 512-thread workgroups
 // per CU (same chunk, window 8192 or 4096) did NOT help: the load and write phases already run at the CU's
 // fair share of HBM, what is left is the sub-line write pattern itself.
-template <int THREADS, int PER_THREAD, int WINDOW, bool VEC, bool INDEX>
+// The reservation of one trip: a lane's kRes bins (interleaved over the workgroup), the atomics issued back to back, and --
+// separately, so that other loads can be put in flight in between -- the LDS words that turn a rank into a global slot.
+constexpr int kRes = 4;
+template <int THREADS>
+__device__ __forceinline__ void reserve_issue(int i0, int nbins, const unsigned* hist, unsigned* __restrict__ cursor,
+                                              unsigned (&c)[kRes], unsigned (&gpos)[kRes]) {
+#pragma unroll
+    for (int u = 0; u < kRes; ++u) {
+        const int i = i0 + u * THREADS;
+        c[u] = i < nbins ? hist[i] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < kRes; ++u) {
+        gpos[u] = 0;
+        if (c[u]) gpos[u] = atomicAdd(&cursor[i0 + u * THREADS], c[u]);
+    }
+}
+template <int THREADS>
+__device__ __forceinline__ void reserve_store(int i0, unsigned* hist, const unsigned* loff, const unsigned (&c)[kRes],
+                                              const unsigned (&gpos)[kRes]) {
+#pragma unroll
+    for (int u = 0; u < kRes; ++u)
+        if (c[u]) hist[i0 + u * THREADS] = gpos[u] - loff[i0 + u * THREADS];
+}
+
+template <int THREADS, int PER_THREAD, int WINDOW, bool VEC, bool INDEX, bool VALUE>
 __device__ __forceinline__ void
 bin_scatter_chunk(unsigned char* lds_raw, const BinGeom& b, uint64_t base, const unsigned* __restrict__ keys,
                   const float* __restrict__ v, uint64_t n, unsigned* __restrict__ cursor, uint2* __restrict__ records) {
@@ -331,8 +356,7 @@ bin_scatter_chunk(unsigned char* lds_raw, const BinGeom& b, uint64_t base, const
 
     unsigned key[PER_THREAD], pos[PER_THREAD], val[PER_THREAD];
     // keys first: the values are only needed when the records are staged, so their loads are issued after the
-    // scan (below) and complete behind the reservation atomics -- and the registers they need are not live while the
-    // keys are ranked
+    // scan (below), behind the reservation atomics -- and the registers they need are not live while the keys are ranked
     if (VEC) {
         const uint4* k4 = reinterpret_cast<const uint4*>(keys + base);
 #pragma unroll
@@ -344,7 +368,8 @@ bin_scatter_chunk(unsigned char* lds_raw, const BinGeom& b, uint64_t base, const
 #pragma unroll
         for (int k = 0; k < PER_THREAD; ++k) {
             uint64_t i = base + (uint64_t)k * THREADS + threadIdx.x;
-            key[k] = i < n ? keys[i] : 0xFFFFFFFFu;
+            const unsigned kk = keys[i < n ? i : n - 1];               // (a tail block starts below n: n >= 1)
+            key[k] = i < n ? kk : 0xFFFFFFFFu;
         }
     }
 #pragma unroll
@@ -378,6 +403,17 @@ bin_scatter_chunk(unsigned char* lds_raw, const BinGeom& b, uint64_t base, const
     for (int w = 0; w < kWaves; ++w) total += wave_tot[w];
     __syncthreads();
 
+    // every non-empty (block, bin) run reserves its place in the bin's global range: bins are dealt to lanes
+    // INTERLEAVED (a wave's atomics hit 64 consecutive words) and a lane's atomics are issued back to back --
+    // with consecutive ownership they were strided over the cursor array and each waited for the one before.
+    // The first trip (all of them while nbins <= kRes * THREADS) is peeled: its atomics go out, the value loads go out
+    // behind them, and since vmcnt retires in order the atomics are waited for with a counted wait while the values stay in
+    // flight until the records are staged -- one exposed round trip for both groups.
+    unsigned rc[kRes], rpos[kRes];
+    reserve_issue<THREADS>(threadIdx.x, b.nbins, hist, cursor, rc, rpos);
+
+    // the values: no control flow and no wait between the loads (VALUE is a property of the instantiation; a test of
+    // the pointer per load compiled to a branch and a full wait around every one of them)
     if (VEC) {
         const uint4* v4 = reinterpret_cast<const uint4*>(v + base);
 #pragma unroll
@@ -386,44 +422,28 @@ bin_scatter_chunk(unsigned char* lds_raw, const BinGeom& b, uint64_t base, const
             if (INDEX) {
                 unsigned i0 = (unsigned)base + 4u * p;
                 val[4 * q + 0] = i0; val[4 * q + 1] = i0 + 1; val[4 * q + 2] = i0 + 2; val[4 * q + 3] = i0 + 3;
-            } else {
-                uint4 vv = v ? stream_load(v4 + p) : make_uint4(0u, 0u, 0u, 0u);
+            } else if (VALUE) {
+                uint4 vv = stream_load(v4 + p);
                 val[4 * q + 0] = vv.x; val[4 * q + 1] = vv.y; val[4 * q + 2] = vv.z; val[4 * q + 3] = vv.w;
+            } else {
+                val[4 * q + 0] = 0u; val[4 * q + 1] = 0u; val[4 * q + 2] = 0u; val[4 * q + 3] = 0u;
             }
         }
     } else {
 #pragma unroll
         for (int k = 0; k < PER_THREAD; ++k) {
             uint64_t i = base + (uint64_t)k * THREADS + threadIdx.x;
-            val[k] = 0u;
-            if (i < n) {
-                if (INDEX) val[k] = (unsigned)i;
-                else if (v) val[k] = __float_as_uint(v[i]);
-            }
+            if (INDEX) val[k] = (unsigned)i;
+            else if (VALUE) val[k] = __float_as_uint(v[i < n ? i : n - 1]);        // (past the end: the key is the sentinel, never staged)
+            else val[k] = 0u;
         }
     }
 
-    // every non-empty (block, bin) run reserves its place in the bin's global range: bins are dealt to lanes
-    // INTERLEAVED (a wave's atomics hit 64 consecutive words) and a lane's atomics are issued back to back --
-    // with consecutive ownership they were strided over the cursor array and each waited for the one before
-    {
-        constexpr int kRes = 4;
-        for (int i0 = threadIdx.x; i0 < b.nbins; i0 += kRes * THREADS) {
-            unsigned c[kRes], gpos[kRes];
-#pragma unroll
-            for (int u = 0; u < kRes; ++u) {
-                const int i = i0 + u * THREADS;
-                c[u] = i < b.nbins ? hist[i] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < kRes; ++u) {
-                gpos[u] = 0;
-                if (c[u]) gpos[u] = atomicAdd(&cursor[i0 + u * THREADS], c[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < kRes; ++u)
-                if (c[u]) hist[i0 + u * THREADS] = gpos[u] - loff[i0 + u * THREADS];
-        }
+    reserve_store<THREADS>(threadIdx.x, hist, loff, rc, rpos);
+    for (int i0 = threadIdx.x + kRes * THREADS; i0 < b.nbins; i0 += kRes * THREADS) {
+        unsigned c[kRes], gpos[kRes];
+        reserve_issue<THREADS>(i0, b.nbins, hist, cursor, c, gpos);
+        reserve_store<THREADS>(i0, hist, loff, c, gpos);
     }
     // rank inside the bin -> position inside the block's sorted order (loff is final since the last barrier)
 #pragma unroll
@@ -440,6 +460,8 @@ bin_scatter_chunk(unsigned char* lds_raw, const BinGeom& b, uint64_t base, const
         }
         __syncthreads();
         // write out: consecutive staged records of a bin go to consecutive global slots
+        // (one record per trip, two dependent LDS reads each: four per trip with the reads grouped was measured and is
+        // no faster -- DESIGN section 9 -- the other workgroup of the CU covers these waits)
         const unsigned cnt = min((unsigned)WINDOW, total - w0);
         for (unsigned j = threadIdx.x; j < cnt; j += THREADS) {
             uint2 rec = stage[j];
@@ -453,22 +475,24 @@ bin_scatter_chunk(unsigned char* lds_raw, const BinGeom& b, uint64_t base, const
 
 // Blocks [0, full_blocks) take a full chunk each (16-byte loads); the blocks after them share the ragged end of the
 // cloud in 4096-point chunks through the scalar-load body: one launch (a second, tiny launch was ~10 us of latency).
-template <int THREADS, int PER_THREAD, int WINDOW, bool INDEX>
+template <int THREADS, int PER_THREAD, int WINDOW, bool INDEX, bool VALUE>
 __global__ void __launch_bounds__(THREADS, 4)          // <= 128 VGPRs
 k_bin_scatter(BinGeom b, unsigned full_blocks, int nvx, const unsigned* __restrict__ keys, const float* __restrict__ v,
               uint64_t n, unsigned* __restrict__ cursor, uint2* __restrict__ records, TailFill fill) {
     extern __shared__ unsigned char lds_dyn[];
     cursor += (size_t)(blockIdx.x & (unsigned)(nvx - 1)) * b.nbins;      // this workgroup's virtual XCD (bin_points)
+    // (the scan's verdict, read at the head, where it is a scalar load next to the arguments': at the end it was a round trip of its own)
+    const unsigned split = fill.n_items ? fill.n_items[1] : 0u;
     if (blockIdx.x < full_blocks) {
-        bin_scatter_chunk<THREADS, PER_THREAD, WINDOW, true, INDEX>(lds_dyn, b, (uint64_t)blockIdx.x * (THREADS * PER_THREAD), keys, v, n,
+        bin_scatter_chunk<THREADS, PER_THREAD, WINDOW, true, INDEX, VALUE>(lds_dyn, b, (uint64_t)blockIdx.x * (THREADS * PER_THREAD), keys, v, n,
                                                                     cursor, records);
     } else {
         const uint64_t base = (uint64_t)full_blocks * (THREADS * PER_THREAD) + (uint64_t)(blockIdx.x - full_blocks) * 4096;
-        bin_scatter_chunk<THREADS, 4096 / THREADS, WINDOW, false, INDEX>(lds_dyn, b, base, keys, v, n, cursor, records);
+        bin_scatter_chunk<THREADS, 4096 / THREADS, WINDOW, false, INDEX, VALUE>(lds_dyn, b, base, keys, v, n, cursor, records);
     }
     // (engine.hpp, TailFill: the scan split a bin and the tile pass merges into undefined planes -- the kernel boundary orders
     // these stores before it)
-    if (fill.n_items && fill.n_items[1] != 0u) {
+    if (split != 0u) {
         const long long stride = (long long)gridDim.x * THREADS;
         for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < fill.n16; i += stride)
 #pragma unroll
@@ -488,6 +512,10 @@ k_bin_scatter(BinGeom b, unsigned full_blocks, int nvx, const unsigned* __restri
 // and on a C5 shard (16384 x 2048, 2 816 bins, 125 M points; step ms): 1024 x 28: 1.495, 512 x 24: 1.553 (runs of four
 // records), 1024 x 16 with a 16384-record window: 1.428.  So: few bins -> two 512-thread workgroups per CU, whose phases
 // overlap; more bins -> the longer chunk of one 1024-thread workgroup, staged in ONE round while the LDS has the room.
+// Measured again once the value loads of a chunk were in flight together (profiles/point_scatter_loads.md, one call, five
+// repeats each; pass ms / step ms): C2 512 x 24 0.151-0.158 / 0.474-0.486, 512 x 20 0.156-0.163 / 0.475-0.484, 512 x 16
+// 0.156-0.160 / 0.469-0.489, 1024 x 16, 16384 0.169-0.174 / 0.483-0.491; the C5 shard (step ms) 1024 x 16, 16384 1.161-1.195,
+// 512 x 24 1.229-1.264, 512 x 20 1.260-1.272, 512 x 16 1.316-1.336.  No shape is outside the range of the rule's: no change.
 struct ScatterShape {
     int threads, per, window;
     int chunk() const { return threads * per; }
@@ -518,9 +546,15 @@ void launch_bin_scatter(pcr_hip_engine* e, const BinGeom& b, int nvx, const unsi
         hipLaunchKernelGGL(kernel, dim3((unsigned)full_blocks + tail_blocks), dim3(threads), lds, e->stream, b, (unsigned)full_blocks, nvx,
                            d_keys, v, n, d_cursor, d_rec, fill);
     };
-    if (sh.threads == 512) go(&k_bin_scatter<512, 24, 8192, INDEX>, 512);
-    else if (sh.window == 16384) go(&k_bin_scatter<1024, 16, 16384, INDEX>, 1024);
-    else go(&k_bin_scatter<1024, 24, 8192, INDEX>, 1024);
+    auto shapes = [&](auto value) {                              // value records load v (null only for Count-only pipelines)
+        constexpr bool VALUE = decltype(value)::value;
+        if (sh.threads == 512) go(&k_bin_scatter<512, 24, 8192, INDEX, VALUE>, 512);
+        else if (sh.window == 16384) go(&k_bin_scatter<1024, 16, 16384, INDEX, VALUE>, 1024);
+        else go(&k_bin_scatter<1024, 24, 8192, INDEX, VALUE>, 1024);
+    };
+    if constexpr (INDEX) shapes(std::false_type{});
+    else if (v) shapes(std::true_type{});
+    else shapes(std::false_type{});
     e->stats_scatter_chunk = (int)chunk;
 }
 
