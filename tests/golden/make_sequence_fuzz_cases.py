@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Writes tests/golden/sequence_fuzz_cases.json: one SHA-256 per seed (sequence_fuzz_common.case_digest) of the 40 cases that
-were the operation-sequence fuzz's suite before it drew terrain bands, recorded with the generator of that commit.
+were the operation-sequence fuzz's suite before it drew terrain bands, recorded with the generator of that commit, and under
+the key `sha256_line` one per seed of LINE_SEEDS (the line cases: the digest covers the glyphs and the `dir` / `hl` arrays).
 
     python tests/golden/make_sequence_fuzz_cases.py
 
@@ -14,6 +15,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle"))      # (a line case is thinned by the oracle)
 import sequence_fuzz_common as S  # noqa: E402
 
 SEEDS = list(range(32)) + [47, 48, 49, 51, 54, 64, 75, 76]
@@ -21,11 +23,19 @@ OUT = os.path.join(HERE, "sequence_fuzz_cases.json")
 
 
 def main():
-    rec = {str(seed): S.case_digest(S.build(seed)) for seed in SEEDS}
+    def digest(seed):
+        case = S.build(seed)
+        for plan in [case["plan"]] + [o["plan"] for o in case["ops"] if o["op"] == "checkpoint" and o["plan"] is not None]:
+            del plan["terrain"]
+        return S.case_digest(case)
+
+    rec = {str(seed): digest(seed) for seed in SEEDS}
+    line = {str(seed): digest(seed) for seed in S.LINE_SEEDS}
     with open(OUT, "w") as f:
-        json.dump(dict(what="sequence_fuzz_common.case_digest(build(seed)) per seed, before terrain was drawn", sha256=rec), f, indent=1)
+        json.dump(dict(what="sequence_fuzz_common.case_digest(build(seed)) per seed, before terrain was drawn", sha256=rec,
+                       sha256_line=line), f, indent=1)
         f.write("\n")
-    print(f"{OUT}: {len(rec)} seeds")
+    print(f"{OUT}: {len(rec)} + {len(line)} seeds")
 
 
 if __name__ == "__main__":

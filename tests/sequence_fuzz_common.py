@@ -17,7 +17,17 @@ overviews_common.pyramid; and the `.pcrt` writer for the reference checkpoint.
 Every finalize plan also draws PipelineConfig::terrain (0 to 6 entries on any band that leaves, _draw_terrain): the model
 appends those bands by terrain_common.terrain, the NumPy restatement of the contract -- not pcr.terrain, so that the host-engine
 run holds the host loop's plumbing to something that shares no code with it.  Since every source band is exact here, the
-terrain bands of an Average source are held to the model on both engines too."""
+terrain bands of an Average source are held to the model on both engines too.
+
+Line cases: a seed from LINE_SEED_BASE on appends Line-glyph reductions (Sum, Count, Average, WeightedAverage; plane masks 1, 2
+and 3; one glyph or two that differ in one parameter) and maybe a Point WeightedAverage to what the seed draws, gives every
+cloud a `dir` and an `hl` channel, and may replace clouds by a hot Line tile or by late-large values for a packed item
+(_line_pass, last and from generators of its own: a seed below LINE_SEED_BASE stays the case it is).  A Line visit has weight
+1, so with these values a group's sum plane is an exact sum and its weight plane an integer: the model adds the oracle's
+footprint (oracle/pcr_oracle.c through pcr_oracle_py, the one thing here that is not NumPy) in binary64 and needs no
+tolerance.  _line_pass checks the exactness condition for the Line sums with the oracle's binary64 mode on |v| and thins a
+cloud that would break it.  Gaussian groups are not drawn: their weights are expf values and their sums depend on the order
+of addition."""
 import filecmp
 import os
 
@@ -30,10 +40,21 @@ EXACT_UNITS = 1 << 23                      # the clouds stay below this per cell
 PATCH_UNITS = 64                           # a plane patch adds at most this many units to a cell: k/8 on an `a` plane, an integer on a `b` or Count plane
 SPLIT_RECORDS = 1 << 17                    # kPointItemRecords: the scan splits a bin that holds more records
 HOT_W, HOT_H = 128, 56                     # every Point LDS tile is 128 columns wide and at least 56 rows tall (20 B per cell), from cell (0, 0)
-FILL_TYPES = ("Average", "Max", "Min", "MostRecent")
+FILL_TYPES = ("Average", "WeightedAverage", "Max", "Min", "MostRecent")     # fill_nodata.h: fills_nodata
 OPS8 = ("Equal", "NotEqual", "Less", "LessEqual", "Greater", "GreaterEqual", "InSet", "NotInSet")
 # planes a reduction needs / its checkpoint holds, as slots (0 sum, 1 count, 2 max, 3 min; MostRecent: 0 value, 1 timestamp)
-PLANES_OF = {"Sum": (0,), "Count": (1,), "Max": (2,), "Min": (3,), "Average": (0, 1), "MostRecent": (0, 1)}
+PLANES_OF = {"Sum": (0,), "Count": (1,), "Max": (2,), "Min": (3,), "Average": (0, 1), "WeightedAverage": (0, 1), "MostRecent": (0, 1)}
+# Line cases: a seed from LINE_SEED_BASE on appends Line-glyph reductions (and maybe a Point WeightedAverage) to what the seed
+# draws anyway, from generators of their own (_line_pass); a seed below it stays the case it is
+LINE_SEED_BASE = 2000
+LINE_TYPES = ("Sum", "Count", "Average", "WeightedAverage")    # pipeline_common.h: glyph_reduction_ok
+LINE_MAX_RADIUS = (2.0, 16.0, 32.0)
+LINE_CORNER = 32                           # no Line LDS tile is smaller than 32 x 32 cells (glyph_tile): a corner of one tile whatever the glyph
+LINE_ITEM_RECORDS = 65535                  # binned_glyph's item_points: k_tile_line_rec counts a cell's visits in 16 bits
+LINE_LONG_CELLS = 40000.0                  # a half_length beyond the int16 offsets of the end-point records: the listed path (k_line_list)
+# k_tile_line_rec's LDS layout (csrc/scatter_binned_glyph.hip): count plane from byte 16, sum plane from byte 65 528, the list of
+# left-out segments between them; at most 12 288 cells; packed words (both planes kept) accept 8 exponents
+LINE_COUNT_BASE, LINE_SUM_BASE, LINE_MAX_CELLS, LINE_PACKED_WINDOW = 16, 65528, 12288, 7
 # PipelineConfig::terrain: the products by terrain_product_name in TerrainProduct's order, and parameters that create accepts
 TERRAIN_PRODUCTS = ("slope", "slope_percent", "aspect", "hillshade", "tri", "tpi", "roughness")
 TERRAIN_Z = (1.0, 1.0, 2.0, 0.37)
@@ -67,10 +88,10 @@ def seeds_from_env(name="PCR_SEQ_FUZZ_SEEDS"):
         return list(range(int(a), int(b)))
     if env:
         return [int(v) for v in env.split(",")]
-    return list(DEFAULT_SEEDS)
+    return list(DEFAULT_SEEDS) + list(LINE_SEEDS)
 
 
-# ---- the generator (NumPy only) ------------------------------------------------------------------------------------------------
+# ---- the generator (NumPy only; a line case: and the oracle) ------------------------------------------------------------------------------------------------
 def cells_of(g, x, y):
     """Flat cell of every point by the oracle's world_to_cell (inclusive bounds, floor of the TRUE binary64 division, clamp),
     -1 outside the bounds.  The same IEEE operations as oracle/pcr_oracle.c, vectorised; the host test checks it against
@@ -83,15 +104,17 @@ def cells_of(g, x, y):
 
 
 def groups_of(specs):
-    """Accumulation groups as every engine forms them: same value channel (MostRecent: and timestamp channel, a group of its own)."""
+    """Accumulation groups as every engine forms them (pipeline_common.h: same_group): same value channel through the same
+    glyph -- every parameter of it, same_glyph -- (MostRecent: and timestamp channel, a group of its own)."""
     groups = []
     for i, s in enumerate(specs):
-        key = (s["ch"], s["type"] == "MostRecent")
+        gl = s.get("glyph")
+        key = (s["ch"], s["type"] == "MostRecent", None if gl is None else tuple(sorted(gl.items())))
         for gr in groups:
             if gr["key"] == key:
                 break
         else:
-            gr = dict(key=key, ch=s["ch"], select=key[1], slots=set(), outs=[])
+            gr = dict(key=key, ch=s["ch"], select=key[1], glyph=gl, slots=set(), outs=[])
             groups.append(gr)
         gr["slots"].update(PLANES_OF[s["type"]])
         gr["outs"].append(i)
@@ -208,9 +231,244 @@ def hot_records(case, c):
     return int((ok & (cell // g["W"] < HOT_H) & (cell % g["W"] < HOT_W)).sum())
 
 
+CLOUD_KEYS = ("x", "y", "a", "b", "t", "cls")
+LINE_CLOUD_KEYS = ("dir", "hl")            # only the clouds of a line case have them
+
+
+def cloud_keys(c):
+    return CLOUD_KEYS + (LINE_CLOUD_KEYS if "dir" in c else ())
+
+
 def _thin(c, keep):
-    for k in ("x", "y", "a", "b", "t", "cls"):
+    for k in cloud_keys(c):
         c[k] = c[k][keep]
+
+
+def point_units(g, clouds):
+    """Per channel (`a` in units of 1/8, `b` in units of 1) and cell, the sum of |v| over the points of the clouds whose centre
+    cell it is: what a Point group's sum plane can reach at most.  -> (2, W * H)"""
+    units = np.zeros((2, g["W"] * g["H"]))
+    for c in clouds:
+        cell = cells_of(g, c["x"], c["y"])
+        m = cell >= 0
+        units[0] += np.bincount(cell[m], np.abs(c["a"][m].astype(np.float64)) * 8.0, g["W"] * g["H"])
+        units[1] += np.bincount(cell[m], c["b"][m].astype(np.float64), g["W"] * g["H"])
+    return units
+
+
+# ---- line cases --------------------------------------------------------------------------------------------------------------
+def oracle_grid(g):
+    import pcr_oracle_py as O
+    og = O.make_grid((g["min_x"], g["min_y"], g["max_x"], g["max_y"]), cell=(g["cs"], -g["cs"]), tile=(g["tw"], g["th"]))
+    assert (og.width, og.height) == (g["W"], g["H"])
+    return og
+
+
+def oracle_line(og, gl, rtype, c, ch_values, sel, wide=False):
+    """One oracle band of the points `sel` of a cloud through the Line glyph `gl`: the footprint of the model."""
+    import pcr_oracle_py as O
+    kw = dict(direction=c["dir"][sel])
+    if gl["hl_ch"]:
+        kw["half_length"] = c["hl"][sel]
+    ogl = O.make_glyph(O.GLYPH_LINE, half_length=gl["hl"], max_radius=gl["maxr"])
+    return O.run(og, rtype, c["x"][sel], c["y"][sel], ch_values[sel], glyph=ogl, wide=wide, **kw)
+
+
+def line_tile(g, gl, mask):
+    """glyph_tile and binned_glyph of csrc/scatter_binned_glyph.hip for a Line glyph on a grid that one sweep bins: the side S of
+    the LDS tiles (they start at cell (0, 0) of an in-core pipeline), the apron, whether the walk-state records and
+    k_tile_line_rec are used, and how many left-out segments that kernel's list holds."""
+    f32 = np.float32
+    cell_bytes = (8 if mask & 1 else 0) + (4 if mask & 2 else 0)
+    side = int(np.floor(np.sqrt(150 * 1024 // max(cell_bytes, 4)))) & ~1
+    cap = min(max(gl["maxr"], 0.0), 4096.0)
+    if gl["hl_ch"]:
+        need = int(np.ceil(cap)) + 1
+    else:
+        hx, hy = f32(gl["hl"]) * f32(1.0 / g["cs"]), f32(gl["hl"]) * f32(-1.0 / g["cs"])
+        ax, ay = (cap if h > gl["maxr"] else min(abs(float(h)), 4096.0) for h in (hx, hy))
+        need = int(np.ceil(max(ax, ay))) + 1
+    S = min(128, (side - 2 * need) & ~7)
+    if not gl["hl_ch"] and 110 - 2 * need >= 32:
+        S = min(S, (110 - 2 * need) & ~7)
+    S = max(S, 32)
+    apron = max(0, min(need, (side - S) // 2))
+    lw = S + 2 * apron
+    rec = apron >= need and not gl["hl_ch"] and lw <= 127 and lw * lw <= LINE_MAX_CELLS
+    return dict(S=S, apron=apron, need=need, state_records=rec, list_cap=(LINE_SUM_BASE - LINE_COUNT_BASE) // 4 - lw * lw)
+
+
+def line_tile_records(case, c, gr):
+    """Mask of the records of a cloud that reach the FIRST LDS tile of Line group `gr` of an in-core pipeline: past the filter,
+    centre cell inside the bounds and inside [0, S) x [0, S)."""
+    g = case["grid"]
+    S = line_tile(g, gr["glyph"], sum(1 << p for p in gr["slots"]))["S"]
+    cell = cells_of(g, c["x"], c["y"])
+    return keep_mask(case["filt"], c["cls"]) & (cell >= 0) & (cell // g["W"] < S) & (cell % g["W"] < S)
+
+
+def line_list_load(case, c, gr):
+    """For a packed k_tile_line_rec item made of the records of line_tile_records: how many of them lie outside the window of
+    8 exponents, whichever record's exponent the first 1024 make the window's top (the bins are filled by atomics: no order
+    is promised).  -> (fewest, most, list_cap, records), or None where the group is not packed or takes another kernel."""
+    t = line_tile(case["grid"], gr["glyph"], sum(1 << p for p in gr["slots"]))
+    if gr["slots"] != {0, 1} or not t["state_records"]:
+        return None
+    m = line_tile_records(case, c, gr)
+    v = np.abs(c[gr["ch"]][m])
+    e = np.frexp(v[v > 0])[1]
+    if len(e) == 0:
+        return None
+    outs = [int(((e < top - LINE_PACKED_WINDOW) | (e > top)).sum()) for top in np.unique(e)]
+    return min(outs), max(outs), t["list_cap"], int(m.sum())
+
+
+def _draw_line_specs(rl):
+    """The reductions a line case appends behind the Point ones: maybe a Point WeightedAverage, then 1 to 4 Line reductions in
+    one or two groups whose plane masks are drawn (1: Sum; 2: Count; 3: both planes), through one Line glyph or through two
+    that differ in exactly one parameter."""
+    out = []
+    if rl.uniform() < 0.4:
+        out.append(dict(type="WeightedAverage", ch=str(rl.choice(["a", "b"]))))
+    gl = dict(hl_ch="hl" if rl.uniform() < 0.4 else "", hl_cells=float(np.round(rl.uniform(0.5, 6.0), 3)),
+              maxr=float(rl.choice(LINE_MAX_RADIUS)))
+    glyphs = [gl]
+    two_groups = bool(rl.uniform() < 0.6)
+    if two_groups and rl.uniform() < 0.6:
+        which = str(rl.choice(["hl_ch", "hl_cells", "maxr"]))
+        other = dict(gl)
+        if which == "hl_ch":
+            other["hl_ch"] = "" if gl["hl_ch"] else "hl"
+        elif which == "hl_cells":
+            other["hl_cells"] = float(np.round(gl["hl_cells"] + rl.uniform(0.6, 2.0), 3))
+        else:
+            other["maxr"] = float(rl.choice([r for r in LINE_MAX_RADIUS if r != gl["maxr"]]))
+        glyphs.append(other)
+    ch0 = str(rl.choice(["a", "b"]))
+    chans = [ch0]
+    if two_groups and len(glyphs) == 1:                          # one glyph: the second group is the other channel's
+        chans.append("b" if ch0 == "a" else "a")
+    elif two_groups and rl.uniform() < 0.7:                      # two glyphs: mostly on ONE channel, so that only same_glyph keeps them apart
+        chans.append(ch0)
+    elif two_groups:
+        chans.append(str(rl.choice(["a", "b"])))
+    forms = {1: [["Sum"]], 2: [["Count"]],
+             3: [["Average"], ["WeightedAverage"], ["Sum", "Count"], ["WeightedAverage", "Sum"], ["Average", "Count"]]}
+    lines = []
+    for k, ch in enumerate(chans):
+        mask = int(rl.choice([1, 2, 3], p=[0.3, 0.2, 0.5]))
+        form = forms[mask][int(rl.integers(0, len(forms[mask])))]
+        lines += [dict(type=t, ch=ch, glyph=k if len(glyphs) == 2 else 0) for t in form]
+    return out, [lines[i] for i in rl.permutation(len(lines))], glyphs
+
+
+def _draw_line_channels(rl, g, c):
+    """`dir` and `hl` of a cloud (float32, finite): directions in [-7, 7], a share beyond +-64 rad (where line_params_fast
+    declines), a share of exact multiples of pi / 4; half lengths of 0 to 8 cells with zeros and negative entries (hy is
+    negative on these north-up grids and never capped: quirk Q7), and in some clouds up to 8 entries of 40 000 cells."""
+    n, cs = len(c["x"]), g["cs"]
+    d = rl.uniform(-7.0, 7.0, n)
+    far = rl.uniform(size=n) < 0.1
+    d[far] = rl.uniform(64.0, 80.0, int(far.sum())) * rl.choice([-1.0, 1.0], int(far.sum()))
+    d[far] = np.where(np.abs(d[far]) <= 64.0, 80.0, d[far])                     # (64, 80]
+    diag = rl.uniform(size=n) < 0.1
+    d[diag] = rl.integers(-8, 9, int(diag.sum())) * (np.pi / 4)
+    hl = rl.uniform(0.0, 8.0, n) * cs
+    kind = rl.uniform(size=n)
+    hl[kind < 0.1] = 0.0
+    hl[kind > 0.9] *= -1.0
+    k = int(rl.integers(1, 9)) if rl.uniform() < 0.35 else 0
+    if n and k:
+        hl[rl.integers(0, n, k)] = LINE_LONG_CELLS * cs
+    c["dir"], c["hl"] = d.astype(np.float32), hl.astype(np.float32)
+
+
+def _draw_line_cloud(rl, g, kind, filt):
+    """The clouds only a line case has, all inside the first 32 x 32 cells (one LDS tile of any Line group, in core):
+    "hot_line": more than 65 535 records, so the tile is more than one item, small values so that thinning never halves it;
+    "late_overflow": ~3000 points with |a| <= 1/4, then as many of |a| = 1/8 and of |a| >= 32 as no list of left-out segments
+    holds -- a packed window of 8 exponents leaves one of the two kinds out wherever its top lies, and in the cloud's own
+    order the large ones arrive after the window is fixed;  "late_used": the ~3000, then a handful of larger values (half of
+    them one exponent above the small ones' window), so that the list is used and never full."""
+    cs = g["cs"]
+    small = lambda k: rl.integers(-2, 3, k) / 8.0
+    sign = lambda k: rl.choice([-1.0, 1.0], k)
+    if kind == "hot_line":
+        n = LINE_ITEM_RECORDS + int(rl.integers(2000, 9000))
+        a = rl.integers(-16, 17, n) / 8.0
+    elif kind == "late_overflow":
+        cap = (LINE_SUM_BASE - LINE_COUNT_BASE) // 4             # (no list is longer)
+        k = cap + cap // 3
+        late = np.concatenate([sign(k) / 8.0, sign(k) * rl.integers(256, 513, k) / 8.0])
+        a = np.concatenate([small(3000), late[rl.permutation(2 * k)]])
+    else:
+        k = int(rl.integers(8, 41))
+        late = np.concatenate([sign(k) * rl.integers(4, 8, k) / 8.0, sign(k) * rl.integers(256, 513, k) / 8.0])
+        a = np.concatenate([small(3000), late[rl.permutation(2 * k)]])
+    n = len(a)
+    x = rl.uniform(g["min_x"], g["min_x"] + LINE_CORNER * cs, n)
+    y = rl.uniform(g["max_y"] - LINE_CORNER * cs, g["max_y"], n)
+    if kind == "late_used" and g["W"] >= 48:
+        # the handful lies beside the corner, in columns 32 to 87 of the same tile (a tile of k_tile_line_rec is at least 88
+        # wide) where nothing else of the cloud falls: in a packed word a value that was wrongly taken into the window is put
+        # right by any two other visits of its cell (each adds 2^31 + q > 2^30), so only a cell that it has to itself shows it
+        x[3000:] = rl.uniform(g["min_x"] + LINE_CORNER * cs, g["min_x"] + min(g["W"], 88) * cs, n - 3000)
+    kept = np.arange(4, dtype=np.float32)[keep_mask(filt, np.arange(4, dtype=np.float32))]
+    return dict(shape=kind, x=x, y=y, a=a.astype(np.float32), b=rl.integers(0, 64, n).astype(np.float32),
+                t=rl.integers(0, 6, n).astype(np.float32), cls=kept[rl.integers(0, len(kept), n)])
+
+
+def _line_pass(seed, g, specs, ops, clouds, filt):
+    """What makes a seed >= LINE_SEED_BASE a line case, drawn last and from generators of its own (94000, seed, k): k = 0 the
+    appended reductions, the plane writes turned onto them and which clouds are replaced by a Line cloud; k = 1 + i the
+    replacement and the `dir` / `hl` channels of cloud i.  Then the exactness condition for the Line groups: per group and
+    cell, the oracle's binary64 sum of |v| over the footprints of every cloud, plus the patches, stays below 2^24 units --
+    a cloud that would break it is thinned."""
+    import pcr_oracle_py as O
+    rl = np.random.default_rng((94000, seed, 0))
+    W, H = g["W"], g["H"]
+    point_wa, lines, glyphs = _draw_line_specs(rl)
+    for gl in glyphs:                                            # as the ReductionSpec holds it: world units, binary32
+        gl["hl"] = float(np.float32(gl.pop("hl_cells") * g["cs"]))
+    specs += point_wa + [dict(type=s["type"], ch=s["ch"], glyph=dict(glyphs[s["glyph"]])) for s in lines]
+    groups = groups_of(specs)
+    # plane writes: most of them go to a plane of an appended reduction (a Line group's sum or weight plane, a WeightedAverage's)
+    targets = [i for i, s in enumerate(specs) if "glyph" in s or s["type"] == "WeightedAverage"]
+    for k, o in enumerate(ops):
+        turn = rl.uniform() < (0.7 if o["op"] == "planes_write" else 0.35 if o["op"] == "planes_read" else 0.0)
+        r, h, w = int(rl.choice(targets)), int(rl.integers(1, 21)), int(rl.integers(1, 21))
+        r0, c0, u = int(rl.integers(0, H - min(h, H) + 1)), int(rl.integers(0, W - min(w, W) + 1)), int(rl.integers(-PATCH_UNITS, PATCH_UNITS + 1))
+        slot = int(rl.choice(PLANES_OF[specs[r]["type"]]))
+        if turn:
+            value = float(1 + abs(u) % 3) if slot == 1 else float(u) if specs[r]["ch"] == "b" else u / 8.0
+            ops[k] = dict(op="planes_write", group=specs[r]["group"], slot=slot, rect=(r0, c0, min(h, H), min(w, W)), value=value)
+    # clouds: some are replaced by a Line cloud (never the hot spot of the opening, which the marks are about), all get dir and hl
+    for kind in ("hot_line", "late_overflow", "late_used"):
+        i = int(rl.integers(0, len(clouds)))
+        if rl.uniform() < 0.22 and clouds[i]["shape"] != "hot":
+            clouds[i] = dict(shape=kind)
+    og = oracle_grid(g)
+    line_groups = [gr for gr in groups if gr["glyph"] is not None]
+    units = [np.zeros(W * H) for _ in line_groups]
+    points = np.zeros((2, W * H))                                # the Point sums too: a replaced cloud is new to them
+    for i, c in enumerate(clouds):
+        rc = np.random.default_rng((94000, seed, 1 + i))
+        if len(c) == 1:
+            c = clouds[i] = _draw_line_cloud(rc, g, c["shape"], filt)
+        _draw_line_channels(rc, g, c)
+        while len(c["x"]):
+            inside = cells_of(g, c["x"], c["y"]) >= 0
+            mag = {"a": np.abs(c["a"]) * np.float32(8.0), "b": c["b"]}
+            new = [u + np.nan_to_num(oracle_line(og, gr["glyph"], O.SUM, c, mag[gr["ch"]], inside, wide=True)).reshape(-1).astype(np.float64)
+                   for u, gr in zip(units, line_groups)] if inside.any() else units
+            if max(u.max() for u in new) < EXACT_UNITS and (points + point_units(g, [c])).max() < EXACT_UNITS:
+                units = new
+                break
+            _thin(c, np.arange(len(c["x"])) % 2 == 0)
+        points += point_units(g, [c])
+    patched = PATCH_UNITS * sum(o["op"] == "planes_write" for o in ops)
+    assert max(u.max() for u in units) + patched < 1 << 24
+    return groups
 
 
 def build(seed):
@@ -368,6 +626,12 @@ def build(seed):
     # (units of 1/8 on an `a` plane, of 1 on a `b` plane, like the clouds'; a Count never exceeds the points of a cell)
     patched = PATCH_UNITS * sum(o["op"] == "planes_write" for o in ops)
     assert units_a.max() + patched < 1 << 24 and units_b.max() + patched < 1 << 24
+    line = seed >= LINE_SEED_BASE
+    if line:
+        # (it replaces clouds, thins others and adds plane writes: the Point condition again, on the clouds as they are now --
+        # _line_pass holds the replaced clouds to it as it holds them to the Line condition)
+        groups = _line_pass(seed, g, specs, ops, clouds, filt)
+        assert point_units(g, clouds).max() + PATCH_UNITS * sum(o["op"] == "planes_write" for o in ops) < 1 << 24
     k = 0
     for o in ops:
         if o["op"] == "ingest":
@@ -377,7 +641,7 @@ def build(seed):
             k += 1
 
     case = dict(seed=seed, grid=g, specs=specs, groups=groups, filt=filt, plan=plan, flavour=flavour, fwfi=fwfi, path=path,
-                ops=ops, clouds=clouds, big=big, wide=wide)
+                ops=ops, clouds=clouds, big=big, wide=wide, line=line)
     first = clouds[next(o for o in ops if o["op"] == "ingest")["cloud"]]
     offered = _first_ingest_is_offered(case)
     case["marked"] = offered and first["shape"] != "hot"
@@ -393,9 +657,10 @@ def build(seed):
 
 
 def case_digest(case):
-    """SHA-256 of what a seed means apart from the terrain lists: grid, specs, filter, flavour, fwfi, path, the opening plan and
-    the ops (with their plans) as sorted-key JSON, every cloud array's dtype and bytes, `marked` and `split_first`.
-    tests/golden/sequence_fuzz_cases.json holds it for the 40 seeds that were the suite before terrain was drawn."""
+    """SHA-256 of what a seed means apart from the terrain lists: grid, specs (a line case: with their glyphs), filter, flavour,
+    fwfi, path, the opening plan and the ops (with their plans) as sorted-key JSON, every cloud array's dtype and bytes (a line
+    case: `dir` and `hl` too), `marked` and `split_first`.  tests/golden/sequence_fuzz_cases.json holds it for the 40 seeds that
+    were the suite before terrain was drawn, and for LINE_SEEDS."""
     import hashlib
     import json
 
@@ -412,7 +677,7 @@ def case_digest(case):
     h.update(json.dumps(head, sort_keys=True, allow_nan=False).encode())
     for c in case["clouds"]:
         h.update(c["shape"].encode())
-        for k in ("x", "y", "a", "b", "t", "cls"):
+        for k in cloud_keys(c):
             a = np.ascontiguousarray(c[k])
             h.update(f"{k}:{a.dtype.str}:{a.shape}".encode())
             h.update(a.tobytes())
@@ -448,12 +713,17 @@ def _first_ingest_is_offered(case):
         return False
     if not (case["path"] == 2 or (case["path"] == 0 and n * 16 >= g["W"] * g["H"])):
         return False
-    return any(not gr["select"] and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS for gr in case["groups"])
+    return any(point_accumulation(gr) and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS for gr in case["groups"])
+
+
+def point_accumulation(gr):
+    """A group that offer_bands may offer the bands of: not MostRecent, and the Point glyph (it refuses glyph groups)."""
+    return not gr["select"] and gr["glyph"] is None
 
 
 def defers_for_sure(case):
     """... and leaves a plane in its band: an own-plane reduction (Sum, Count, Max, Min) is an output of such a group."""
-    return (case["marked"] or case["split_first"]) and any(not gr["select"] and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS and
+    return (case["marked"] or case["split_first"]) and any(point_accumulation(gr) and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS and
                                   any(case["specs"][r]["type"] in ("Sum", "Count", "Max", "Min") for r in gr["outs"])
                                   for gr in case["groups"])
 
@@ -483,7 +753,7 @@ def situations(case):
         found.add("a split bin in the offered first ingest")
     if any(len(gr["outs"]) > MAX_FINALIZE_OUTPUTS for gr in case["groups"]):
         found.add("more than 8 outputs in a group")
-    stored = [not gr["select"] and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS for gr in case["groups"]]
+    stored = [point_accumulation(gr) and len(gr["outs"]) <= MAX_FINALIZE_OUTPUTS for gr in case["groups"]]
     names = [band_name(i, sp) for i, sp in enumerate(case["specs"])]
     for s, (plan, flavour, ops, differs, terrain_differs) in enumerate(segments(case)):
         ingests = finalizes = 0
@@ -558,8 +828,124 @@ def situations(case):
                 found.add("out of core with MostRecent")
             if plan["ground"] or plan["fill"] > 0:
                 found.add("out of core with ground or fill")
+    return found | (line_situations(case) if case["line"] else set())
+
+
+def line_binned(case, o):
+    """The Line scatters of this ingest into an in-core pipeline go through the tile kernels as ONE scatter: the binned path
+    forced, or chosen by the engine (binned_glyph_supported: 64 n >= cells).  A file ingest scatters chunk by chunk."""
+    n, g = len(case["clouds"][o["cloud"]]["x"]), case["grid"]
+    return o["how"] != "file" and (case["path"] == 2 or (case["path"] == 0 and n * 64 >= g["W"] * g["H"]))
+
+
+def line_situations(case):
+    """The LINE_SITUATIONS that occur in a line case, from the case alone (as situations(): only what runs on the HIP engine)."""
+    found = set()
+    g, specs, groups = case["grid"], case["specs"], case["groups"]
+    lines = [gr for gr in groups if gr["glyph"] is not None]
+    names = [band_name(i, s) for i, s in enumerate(specs)]
+    line_bands = [names[i] for i, s in enumerate(specs) if "glyph" in s]
+    if any(gr["glyph"] is None and gr["ch"] == lg["ch"] for gr in groups for lg in lines):
+        found.add("a Line group and a Point group on one value channel")
+    if any(a["ch"] == b["ch"] and sum(a["glyph"][k] != b["glyph"][k] for k in a["glyph"]) == 1 for a in lines for b in lines):
+        found.add("two Line groups on one channel that differ in one glyph parameter")
+    for lg in lines:
+        found.add(f"Line mask {sum(1 << p for p in lg['slots'])}")
+    if any(s["type"] == "WeightedAverage" and "glyph" not in s for s in specs):
+        found.add("a WeightedAverage Point reduction")
+    per_point = any(lg["glyph"]["hl_ch"] for lg in lines)
+    segs = segments(case)
+    ever = False                                                 # a Line state that holds something
+    for s, (plan, flavour, ops, differs, terrain_differs) in enumerate(segs):
+        ingests = finalizes = 0
+        undefined, ooc = s == 0, flavour["ooc"]
+        written = set()
+        for i, o in enumerate(ops):
+            prev = ops[i - 1] if i else None
+            c = case["clouds"][o["cloud"]] if o["op"] == "ingest" else None
+            inside = c is not None and len(c["x"]) > 0 and cells_of(g, c["x"], c["y"]) >= 0
+            kept = inside & keep_mask(case["filt"], c["cls"]) if c is not None and len(c["x"]) else np.zeros(0, bool)
+            if o["op"] == "ingest" and not kept.any():
+                continue                                         # (nothing is scattered)
+            if o["op"] == "ingest":
+                binned = not ooc and line_binned(case, o)
+                if per_point and (c["hl"][kept] < 0).any() and (c["hl"][kept] == 0).any():
+                    found.add("a per-point hl with negative and zero entries")
+                if (np.abs(c["dir"][kept]) > 64).any():
+                    found.add("directions beyond +-64 rad")
+                if per_point and binned and (c["hl"][kept] >= np.float32(LINE_LONG_CELLS * g["cs"])).any():
+                    found.add("a segment beyond the record range")
+                if undefined and not ooc and binned:
+                    found.add("a first Line ingest into undefined planes, binned")
+                elif undefined and not ooc and o["how"] != "file" and not line_binned(case, o):
+                    found.add("a first Line ingest into undefined planes, direct")
+                if finalizes:
+                    found.add("a Line ingest after a finalize")
+                if ooc and c["shape"] == "cluster" and any(q["op"] == "finalize" for q in ops[i:]):
+                    found.add("out of core with a Line group and a cloud clustered on a reference-tile corner")
+                if case["filt"] and kept.sum() < inside.sum():
+                    found.add("a filter that removes points of a Line cloud")
+                for lg in lines if binned else []:
+                    if line_tile_records(case, c, lg).sum() > LINE_ITEM_RECORDS:
+                        found.add("a hot Line tile")
+                    load = line_list_load(case, c, lg)
+                    # (a segment whose clipped part is empty is not listed: at most a few in a hundred, a quarter is allowed for)
+                    if load and load[3] <= LINE_ITEM_RECORDS and load[0] * 4 >= load[2] * 5:
+                        found.add("late-large values in a packed item: the list overflown")
+                    elif load and load[3] <= LINE_ITEM_RECORDS and load[0] >= 8 and load[1] <= load[2]:
+                        found.add("late-large values in a packed item: the list used")
+                ingests, ever = ingests + 1, True
+            elif o["op"] == "finalize":
+                if case["marked"] and s == 0 and ingests == 1 and prev is not None and prev["op"] == "ingest":
+                    found.add("a Line group next to a Point group whose bands the first ingest stored, finalize right behind it")
+                if (plan["fill"] > 0 and any("glyph" in sp and sp["type"] in FILL_TYPES for sp in specs)) or \
+                        any(t["source"] in line_bands for t in plan["terrain"]):
+                    found.add("fill or terrain on a Line band")
+                found |= written
+                written = set()
+                finalizes += 1
+            elif o["op"] == "planes_write" and not ooc and groups[o["group"]]["glyph"] is not None:
+                written.add(f"a plane write into a Line group's {'weight' if o['slot'] else 'sum'} plane, then a finalize")
+            elif o["op"] == "checkpoint" and o["then"] in ("resume", "load") and o["flavour"] is not None and o["flavour"]["ooc"] != ooc and \
+                    ever and any(q["op"] == "finalize" for q in segs[s + 1][2]):
+                found.add("a Line checkpoint of an out-of-core pipeline taken in core" if ooc else "a Line checkpoint of an in-core pipeline taken out of core")
+            elif o["op"] == "reload" and ingests and any(q["op"] == "finalize" for q in ops[i:]):
+                found.add("load_state over a Line state that was ingested into")
+            undefined = False
     return found
 
+
+LINE_SITUATIONS = ("a Line group and a Point group on one value channel", "two Line groups on one channel that differ in one glyph parameter",
+                   "Line mask 1", "Line mask 2", "Line mask 3", "a per-point hl with negative and zero entries",
+                   "directions beyond +-64 rad", "a segment beyond the record range",
+                   "a Line group next to a Point group whose bands the first ingest stored, finalize right behind it",
+                   "a first Line ingest into undefined planes, binned", "a first Line ingest into undefined planes, direct",
+                   "a Line ingest after a finalize", "a plane write into a Line group's sum plane, then a finalize",
+                   "a plane write into a Line group's weight plane, then a finalize",
+                   "a Line checkpoint of an in-core pipeline taken out of core", "a Line checkpoint of an out-of-core pipeline taken in core",
+                   "load_state over a Line state that was ingested into",
+                   "out of core with a Line group and a cloud clustered on a reference-tile corner", "a hot Line tile",
+                   "late-large values in a packed item: the list used", "late-large values in a packed item: the list overflown",
+                   "a filter that removes points of a Line cloud", "a WeightedAverage Point reduction", "fill or terrain on a Line band")
+# The line cases of the suite: the smallest list of seeds >= LINE_SEED_BASE in which every entry above occurs three times
+# (greedy cover of 2000..2399, cheaper cases first; tests/test_sequence_fuzz_host.py counts).  A failing seed of a soak joins it.
+LINE_SEEDS = [
+    2009,   # mask 1 beside a Point group on its channel; an out-of-core checkpoint taken in core
+    2056,   # 520 x 512: two glyphs on one channel, masks 1 and 3, a hot Line tile, a segment of 40 000 cells, a filter
+    2071,   # out of core first, then in core: a cluster on a tile corner, a write into a weight plane
+    2113,   # 520 x 512: Line groups beside stored Point bands, the finalize right behind the first ingest; masks 2 and 3
+    2133,   # a first Line ingest on the direct path; writes into the sum and the weight plane of a mask-3 group
+    2136,   # a packed item whose list overflows and one whose list is used; stored Point bands beside the Line groups
+    2213,   # in core, then resumed out of core; stored Point bands beside masks 1 and 3
+    2251,   # a direct first ingest; the checkpoint taken out of core, a cluster on a tile corner there
+    2272,   # mask 1 alone: a direct first ingest, a write into its sum plane
+    2275,   # two glyphs on one channel; load_state over an ingested Line state; in core to out of core, a cluster there
+    2297,   # a packed item whose list overflows, ingested after a finalize; fill on a WeightedAverage Line band
+    2328,   # two glyphs on one channel, both late-large clouds: the list overflown and the list used
+    2331,   # mask 2; in core to out of core and back
+    2344,   # a hot Line tile, the list used, writes into both planes, load_state over the state
+    2385,   # masks 2 and 3: a hot Line tile, the list used, a write into a weight plane
+]
 
 SITUATIONS = ("finalize right after the only ingest, finalize_with_first_ingest on", "ingest after a finalize",
               "state_planes() between an ingest and its finalize", "plane write", "writable flag pointer before the first ingest",
@@ -588,6 +974,7 @@ class Model:
         self.tx, self.ty = -(-g["W"] // g["tw"]), -(-g["H"] // g["th"])
         self.touched = np.zeros((self.ty, self.tx), bool)
         self.survivors = 0
+        self.og = oracle_grid(g) if case["line"] else None
         self.planes = []
         for gr in case["groups"]:
             if gr["select"]:
@@ -601,6 +988,7 @@ class Model:
 
     def ingest(self, c):
         import most_recent_common as MR
+        import pcr_oracle_py as O
         keep = keep_mask(self.case["filt"], c["cls"])
         self.survivors += int(keep.sum())
         cell = cells_of(self.g, c["x"], c["y"])
@@ -612,6 +1000,15 @@ class Model:
             v = c[gr["ch"]]
             if gr["select"]:
                 MR.fold_words(cell, v, c["t"], self.W * self.H, keep=keep, words=pl)
+                continue
+            if gr["glyph"] is not None:
+                # a Line group: the oracle's Sum and Count bands of the kept points through the group's glyph (a NaN: nothing
+                # here) added to planes 0 and 1 -- in binary64, exact by the condition of _line_pass.  Nothing else: the
+                # footprint is clipped to the centre cell's reference tile (Q4), whose flag is set above
+                for p, rtype in ((0, O.SUM), (1, O.COUNT)):
+                    if p in gr["slots"] and ok.any():
+                        band = np.nan_to_num(oracle_line(self.og, gr["glyph"], rtype, c, v, ok)).reshape(-1)
+                        pl[p][:] = (pl[p].astype(np.float64) + band.astype(np.float64)).astype(np.float32)
                 continue
             # (binary64 holds every partial sum exactly, and the total is a binary32 number: the condition of build())
             pl[0][:] = (pl[0].astype(np.float64) + np.bincount(cell_ok, v[ok].astype(np.float64), self.W * self.H)).astype(np.float32)
@@ -683,6 +1080,7 @@ class Model:
                 with np.errstate(all="ignore"):
                     band = {"Sum": lambda: sm.copy(), "Count": lambda: np.where(ct > 0, ct, np.float32(np.nan)),
                             "Average": lambda: np.where(ct > 0, sm / ct, np.float32(np.nan)),
+                            "WeightedAverage": lambda: np.where(ct > 0, sm / ct, np.float32(np.nan)),      # (weight 1 a visit)
                             "Max": lambda: np.where(mx == -FLT_MAX, np.float32(np.nan), mx),
                             "Min": lambda: np.where(mn == FLT_MAX, np.float32(np.nan), mn)}[s["type"]]()
             band = np.where(live, band, np.float32(np.nan)).astype(np.float32)
@@ -772,6 +1170,11 @@ def make_config(case, plan, flavour, exec_mode, engine, tmp_path, state_dir=None
         r.value_channel, r.type, r.output_band_name = s["ch"], getattr(pcr.ReductionType, s["type"]), band_name(i, s)
         if s["type"] == "MostRecent":
             r.timestamp_channel = "t"
+        if "glyph" in s:
+            gl = pcr.GlyphSpec()
+            gl.type, gl.direction_channel, gl.half_length_channel = pcr.GlyphType.Line, "dir", s["glyph"]["hl_ch"]
+            gl.default_half_length, gl.max_radius_cells = s["glyph"]["hl"], s["glyph"]["maxr"]
+            r.glyph = gl
         reds.append(r)
     cfg.reductions = reds
     if case["filt"]:
@@ -818,7 +1221,7 @@ def _cloud(c, where):
     cloud.set_x_array(np.asarray(c["x"], np.float64))
     cloud.set_y_array(np.asarray(c["y"], np.float64))
     cloud.resize(n)
-    for name in ("a", "b", "t", "cls"):
+    for name in cloud_keys(c)[2:]:
         cloud.add_channel(name, pcr.DataType.Float32)
         if n:
             cloud.set_channel_array_f32(name, c[name])
@@ -900,6 +1303,16 @@ def check_sequence(seed, exec_mode, engine, tmp_path):
                     assert info["deferred_planes"] != 0, f"{at}: the first ingest left no plane in its bands: {info}"
                 expect_deferred = defers_for_sure(case) and case["ops"][k + 1] == dict(op="finalize", wait=True)
             first_ingest = False
+            # a line case: the Line groups are the last to scatter, so last_scatter() is the last Line group's.  Where the binned
+            # path is forced it was taken, and a hot or late-large cloud went through the tile kernels by the engine's own rule
+            # too -- in tiles of the side that line_tile_records and line_list_load count with
+            special = c["shape"] in ("hot_line", "late_overflow", "late_used") and line_binned(case, o)
+            if case["line"] and in_core_hip and (case["path"] == 2 or special) and (keep_mask(case["filt"], c["cls"]) & (cells_of(case["grid"], c["x"], c["y"]) >= 0)).any():
+                info = p.last_scatter()
+                assert info["path"] == "binned", f"{at}: the Line scatter of a {c['shape']} cloud took the {info['path']} path: {info}"
+                last = [gr for gr in case["groups"] if gr["glyph"] is not None][-1]
+                side = line_tile(case["grid"], last["glyph"], sum(1 << q for q in last["slots"]))["S"]
+                assert info["lds_tile"] == (side, side), f"{at}: Line tiles {info['lds_tile']}, the generator counts with {side}"
         elif o["op"] == "finalize":
             if o["wait"]:
                 p.finalize()

@@ -6,7 +6,14 @@ the generator marks, the first ingest must have stored its bands (and left plane
 stale-band and plane-restore paths.  Every finalize plan carries a drawn PipelineConfig.terrain list, so the last rows of that
 table -- terrain bands of every kind of source, in core and out of core -- are held to the NumPy model of the contract too; the
 list does not switch the offer off, and the assertions on the marked seeds stand.  The 52 default seeds in the suite;
-PCR_SEQ_FUZZ_SEEDS=a:b soaks a range (or a,b,c: those seeds).  A failure names its seed, the index of the op and the band."""
+PCR_SEQ_FUZZ_SEEDS=a:b soaks a range (or a,b,c: those seeds).  A failure names its seed, the index of the op and the band.
+
+The line cases (LINE_SEEDS; any seed from LINE_SEED_BASE on, so PCR_SEQ_FUZZ_SEEDS=2000:2400 soaks them) add Line groups and
+a Point WeightedAverage: exact sums again (a visit has weight 1), so the Line tile kernels' fixed-point window, list and rescan,
+the listed and the direct path and the plane-state rules for glyph groups are held to the oracle's footprint bit for bit.
+Gaussian groups are not drawn (expf weights: no exact model).  The generator's _line_pass keeps every Line sum exact.
+last_scatter() reports the last scatter of an ingest, which in a line case is the last Line group's: where the binned path is
+forced, and on the hot and late-large clouds, check_sequence asserts that it went through the tile kernels."""
 import pytest
 
 import pcr

@@ -3,7 +3,13 @@
 The existing suites hold the host engine to the oracle, so where the model and the host engine disagree the model is wrong: this
 run pins the model on a machine without a GPU, before tests/test_gpu_sequence_fuzz.py holds the HIP engine to it.  The host
 engine hands out no plane or flag pointers and has one flavour; the runner drops those ops, the generator draws them all the same
--- test_the_default_seeds_cover_the_situations looks at what was drawn."""
+-- test_the_default_seeds_cover_the_situations looks at what was drawn.
+
+Line cases (seeds from LINE_SEED_BASE on; LINE_SEEDS in the suite) append Line-glyph reductions and a Point WeightedAverage to
+what a seed draws: their sums are exact too (a visit has weight 1), so the model -- the oracle's footprint, added in binary64 --
+needs no tolerance.  Gaussian groups are not drawn: their weights are expf values and their sums depend on the order of
+addition.  _line_pass checks the exactness condition for the Line sums with the oracle's binary64 mode; the test of the
+generator below checks it again."""
 import json
 import os
 
@@ -17,7 +23,7 @@ import terrain_common as T
 from conftest import GOLDEN
 
 
-@pytest.mark.parametrize("seed", S.DEFAULT_SEEDS)
+@pytest.mark.parametrize("seed", S.DEFAULT_SEEDS + S.LINE_SEEDS)
 def test_sequence_on_the_host_engine_equals_the_model(seed, tmp_path):
     S.check_sequence(seed, pcr.ExecutionMode.CPU, "host", tmp_path)
 
@@ -46,6 +52,32 @@ def test_the_default_seeds_cover_the_situations():
     assert 12 <= len(mult4) <= 28, f"W % 4 == 0 in {len(mult4)} of 40 seeds"
 
 
+def test_the_line_seeds_cover_the_line_situations():
+    """Every situation the line cases are for occurs in at least three of LINE_SEEDS, recognised from the case alone; no seed
+    of the list is idle, and what a line case is holds for each."""
+    assert all(seed >= S.LINE_SEED_BASE for seed in S.LINE_SEEDS) and max(S.DEFAULT_SEEDS) < S.LINE_SEED_BASE
+    assert S.seeds_from_env("PCR_SEQ_FUZZ_NO_SUCH_VARIABLE") == S.DEFAULT_SEEDS + S.LINE_SEEDS
+    seen = {name: [] for name in S.LINE_SITUATIONS}
+    for seed in S.LINE_SEEDS:
+        case = S.build(seed)
+        assert case["line"] and case["ops"][-1]["op"] == "finalize" and 4 <= len(case["ops"]) <= 12, seed
+        lines = [s for s in case["specs"] if "glyph" in s]
+        assert 1 <= len(lines) <= 4 and case["specs"][-len(lines):] == lines and len(case["specs"]) <= 15, seed
+        assert all(s["type"] in S.LINE_TYPES and s["glyph"]["maxr"] in S.LINE_MAX_RADIUS for s in lines), seed
+        assert 1 <= len({tuple(sorted(s["glyph"].items())) for s in lines}) <= 2, seed
+        assert all(gr["glyph"] is None or set(gr["slots"]) <= {0, 1} for gr in case["groups"]), seed
+        found = S.situations(case)
+        assert found <= set(S.SITUATIONS) | set(S.LINE_SITUATIONS)
+        for name in found & set(S.LINE_SITUATIONS):
+            seen[name].append(seed)
+    for name in S.LINE_SITUATIONS:
+        assert len(seen[name]) >= 3, f"'{name}' occurs in seeds {seen[name]} only"
+    for seed in S.LINE_SEEDS:                                     # the smallest list: no seed can go
+        rest = [s for s in S.LINE_SEEDS if s != seed]
+        assert any(sum(s in seen[name] for s in rest) < 3 for name in S.LINE_SITUATIONS), f"seed {seed} adds nothing"
+    assert not any(S.build(seed)["line"] for seed in S.DEFAULT_SEEDS[:3])
+
+
 def test_the_first_40_seeds_are_the_cases_they_were():
     """Terrain is drawn last and from generators of its own: without every plan's terrain list a seed is, digest for digest,
     the case it was before the fuzz drew terrain (tests/golden/sequence_fuzz_cases.json, make_sequence_fuzz_cases.py)."""
@@ -57,6 +89,19 @@ def test_the_first_40_seeds_are_the_cases_they_were():
         for plan in [case["plan"]] + [o["plan"] for o in case["ops"] if o["op"] == "checkpoint" and o["plan"] is not None]:
             del plan["terrain"]
         assert S.case_digest(case) == want[str(seed)], f"seed {seed} is another case than it was"
+
+
+def test_the_line_seeds_are_the_cases_they_were():
+    """... and LINE_SEEDS are pinned the same way under a key of their own: the digest of a line case covers the glyphs of its
+    specs and the `dir` / `hl` arrays of its clouds."""
+    with open(os.path.join(GOLDEN, "sequence_fuzz_cases.json")) as f:
+        want = json.load(f)["sha256_line"]
+    assert sorted(int(s) for s in want) == sorted(S.LINE_SEEDS)
+    for seed in S.LINE_SEEDS:
+        case = S.build(seed)
+        for plan in [case["plan"]] + [o["plan"] for o in case["ops"] if o["op"] == "checkpoint" and o["plan"] is not None]:
+            del plan["terrain"]
+        assert S.case_digest(case) == want[str(seed)], f"line seed {seed} is another case than it was"
 
 
 def test_the_terrain_draw():
@@ -117,3 +162,66 @@ def test_the_models_cells_are_the_oracles():
             for i in pick:
                 col, row, ok = O.world_to_cell(og, float(c["x"][i]), float(c["y"][i]))
                 assert cell[i] == (row * g["W"] + col if ok else -1), f"seed {seed}: point {i}"
+
+
+def test_the_generator_is_deterministic_for_line_seeds_and_keeps_every_line_sum_exact():
+    """Two builds of a line seed are one case, `dir` and `hl` included; the channels are what the draw promises; and per Line
+    group and cell the sum of |v| over every visit of every cloud, from the oracle in its binary64 mode, stays below 2^24
+    units with every plane patch of the case added (units of 1/8 on `a`, of 1 on `b`)."""
+    for seed in S.LINE_SEEDS[:6]:
+        a, b = S.build(seed), S.build(seed)
+        assert a["ops"] == b["ops"] and a["specs"] == b["specs"] and a["grid"] == b["grid"] and a["plan"] == b["plan"]
+        assert S.case_digest(a) == S.case_digest(b)
+        g = a["grid"]
+        og = S.oracle_grid(g)
+        lines = [gr for gr in a["groups"] if gr["glyph"] is not None]
+        units = [np.zeros((g["H"], g["W"])) for _ in lines]
+        for ca, cb in zip(a["clouds"], b["clouds"]):
+            assert S.cloud_keys(ca) == S.CLOUD_KEYS + S.LINE_CLOUD_KEYS
+            for k in S.cloud_keys(ca):
+                assert np.array_equal(ca[k], cb[k], equal_nan=True) and len(ca[k]) == len(ca["x"])
+            assert ca["dir"].dtype == ca["hl"].dtype == np.float32 and np.isfinite(ca["dir"]).all() and np.isfinite(ca["hl"]).all()
+            assert np.abs(ca["dir"]).max(initial=0) <= 80 and np.abs(ca["hl"]).max(initial=0) <= S.LINE_LONG_CELLS * g["cs"]
+            assert np.array_equal(ca["a"] * 8, np.round(ca["a"] * 8)) and np.abs(ca["a"]).max(initial=0) <= 64
+            assert np.array_equal(ca["b"], np.round(ca["b"])) and ca["b"].min(initial=0) >= 0 and ca["b"].max(initial=0) <= 4095
+            inside = S.cells_of(g, ca["x"], ca["y"]) >= 0
+            if not inside.any():
+                continue
+            mag = {"a": np.abs(ca["a"]) * np.float32(8), "b": ca["b"]}
+            for u, gr in zip(units, lines):
+                u += np.nan_to_num(S.oracle_line(og, gr["glyph"], O.SUM, ca, mag[gr["ch"]], inside, wide=True)).astype(np.float64)
+        patched = S.PATCH_UNITS * sum(o["op"] == "planes_write" for o in a["ops"])
+        assert max(u.max() for u in units) + patched < 1 << 24, seed
+        # ... and the Point groups' sums, from the clouds as the line pass left them (it replaces some)
+        assert S.point_units(g, a["clouds"]).max() + patched < 1 << 24, seed
+
+
+def test_the_models_line_footprint_and_touched_tiles_are_the_oracles():
+    """Cloud by cloud on six line seeds.  What carries weight: the tiles Model.ingest flags -- the centre cells' tiles, by
+    cells_of -- are the tiles the oracle touched, and the oracle's Sum band is a number exactly in the flagged tiles (the
+    footprint is clipped to them, Q4: no visit leaves a flagged tile, none lands in another).  The comparison of the planes
+    themselves only pins the model's plumbing (filter, channels, NaN -> 0, which plane): both sides are the same oracle, so it
+    is no independent check of the footprint -- the oracle is the footprint, held to the reference by its own tests."""
+    for seed in S.LINE_SEEDS[:6]:
+        case = S.build(seed)
+        g = case["grid"]
+        og = S.oracle_grid(g)
+        for c in case["clouds"]:
+            model = S.Model(case)
+            model.ingest(c)
+            sel = S.keep_mask(case["filt"], c["cls"])
+            for gr, pl in zip(case["groups"], model.planes):
+                if gr["glyph"] is None:
+                    continue
+                ogl = O.make_glyph(O.GLYPH_LINE, half_length=gr["glyph"]["hl"], max_radius=gr["glyph"]["maxr"])
+                kw = dict(half_length=c["hl"][sel]) if gr["glyph"]["hl_ch"] else {}
+                red = {p: O.Reduction(og, rtype, ogl) for p, rtype in ((0, O.SUM), (1, O.COUNT)) if p in gr["slots"]}
+                for p, r in red.items():
+                    r.ingest(c["x"][sel], c["y"][sel], c[gr["ch"]][sel], direction=c["dir"][sel], **kw)
+                    band = r.finalize()
+                    assert np.array_equal(np.nan_to_num(band).reshape(-1), pl[p]), f"seed {seed}: plane {p} of a {c['shape']} cloud"
+                    touched = np.array([[r.tile_touched(tr, tc) for tc in range(model.tx)] for tr in range(model.ty)])
+                    assert np.array_equal(touched, model.touched), f"seed {seed}: touched tiles of a {c['shape']} cloud"
+                    if p == 0:
+                        assert np.array_equal(~np.isnan(band).reshape(-1), model.touched_cells()), f"seed {seed}: NaN mask"
+                    r.close()
