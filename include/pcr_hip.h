@@ -302,6 +302,30 @@ int pcr_hip_filter_mask(const pcr_hip_predicate* preds, int n_pred, uint64_t n, 
 /* Points with d_mask[i] == 0 are ignored by every following scatter on this engine; NULL clears it. */
 int pcr_hip_engine_set_point_mask(pcr_hip_engine* e, const uint8_t* d_mask);
 
+/* ---- per-reduction point filters (ReductionSpec::filter; no reference counterpart).  Several reductions of one ingest each
+ *      see their own subset of the points: ONE sweep evaluates a table of DISTINCT predicates and stores one byte mask per
+ *      filter CLASS, each in the layout pcr_hip_engine_set_point_mask takes.
+ *   preds[0 .. n_pred)        the distinct predicates, at most PCR_HIP_MAX_CLASS_PREDICATES (they travel as kernel arguments:
+ *                             32 x 80 B fit the 4 KB a kernel may take; a longer table would have to live in device memory)
+ *   class_predicates[j]       bit k set: class j ANDs preds[k]; 0: the class keeps every point; 1..PCR_HIP_MAX_FILTER_CLASSES
+ *                             classes.  By convention class 0 is PipelineConfig::filter alone when one is asked for.
+ *   d_masks + j * mask_stride class j's mask, n bytes (1 = keep); mask_stride >= n
+ *   d_counts                  optional, n_classes device u64 zeroed by the call: survivors per class
+ *      A channel is loaded once per point however many classes read it and a predicate evaluated once; with 16-byte aligned
+ *      channels and 4-byte aligned masks (base and stride) the sweep loads 16 bytes per lane and channel and stores the four
+ *      mask bytes of a lane packed.  Semantics are pcr_hip_filter_mask's: a NaN fails every op but NotEqual and NotInSet.
+ *      Argument errors (null tables, 0 or more than 8 classes, a class naming a predicate outside the table) are answered on
+ *      the host with PCR_HIP_INVALID_ARGUMENT before anything touches a device. */
+#define PCR_HIP_MAX_FILTER_CLASSES 8
+#define PCR_HIP_MAX_CLASS_PREDICATES 32
+int pcr_hip_filter_classes(const pcr_hip_predicate* preds, int n_pred, const uint32_t* class_predicates, int n_classes, uint64_t n,
+                           uint8_t* d_masks, uint64_t mask_stride, unsigned long long* d_counts, pcr_hip_stream s);
+/* Sets the engine's touched-tile flags from the points its current point mask keeps -- exactly the flags a
+ * pcr_hip_scatter_point of the same points would set (bounds, owned rows, the one-tile case, division as in world_to_cell)
+ * -- on the engine's stream, and writes no plane.  For an ingest none of whose groups is unfiltered: the touched flags of a
+ * pipeline come from PipelineConfig::filter's survivors, never from a reduction's own filter. */
+int pcr_hip_engine_touch(pcr_hip_engine* e, const double* d_x, const double* d_y, uint64_t n);
+
 /* ---- multi-GPU routing of an unpartitioned cloud.  No reference counterpart: the reference is single-device and
  *      its 1 B-point protocol feeds one pipeline (scripts/benchmarks/benchmark_billion_points.py:221-345).  With the
  *      grid row-block sharded over GPUs, a rank groups the points it was handed by OWNER (the part whose row range

@@ -37,6 +37,17 @@ struct ReductionSpec {
     float percentile = 0.5f;
     std::string output_band_name;      // default "{value_channel}_{int(type)}"
     GlyphSpec glyph;
+    // Extension (not in the reference; empty = reference behaviour): this reduction folds only the points that pass
+    // PipelineConfig::filter AND this filter -- a DTM (Min of z over class 2), a DSM (Max of z over first returns) and an
+    // intensity average over single returns come out of ONE ingest.  Any glyph.  Specs group into one pass only when their
+    // filters are equal too (the same predicates in the same order).  The pipeline keeps ONE set of touched-tile flags, set by
+    // PipelineConfig::filter's survivors alone: this filter never sets or clears a flag, so a filtered Sum is 0 -- not NaN,
+    // as a pipeline of its own would say -- in a tile that only other points touched (Count, Average, Max, Min and MostRecent
+    // are NaN in empty cells either way), and the shards' flag all-reduce, the `.pcrt` "touched tile" rule and merge_touched
+    // stay as they are.  stats().points_processed counts PipelineConfig::filter's survivors; checkpoints record no filter.
+    // create() refuses more than 8 distinct non-empty filters, a conjunction (pipeline filter + this one) of more than 16
+    // predicates and more than 32 distinct predicates in all; ingest() checks the channels like PipelineConfig::filter's.
+    FilterSpec filter;
 };
 
 enum class ExecutionMode : uint8_t { CPU, GPU, Auto, Hybrid };

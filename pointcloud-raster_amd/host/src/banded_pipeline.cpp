@@ -38,6 +38,8 @@ std::unique_ptr<Pipeline::Banded> Pipeline::Banded::create(const PipelineConfig&
     const GridConfig& g = config.grid;
     const size_t per_row = bytes_per_row(config);
     if (!(*st = detail::check_reduction_specs(config.reductions)).ok()) return nullptr;
+    detail::FilterPlan filters;                       // (the bands' sub-pipelines plan again: here the refusals and any())
+    if (!(*st = detail::plan_filters(config, &filters)).ok()) return nullptr;
     const int th = g.tile_height;
     const size_t fit = budget / std::max<size_t>(per_row * (size_t)th, 1);          // whole tile rows that fit
     const int band_rows = (int)std::min<size_t>(std::max<size_t>(fit, 1) * (size_t)th, (size_t)g.height + th);
@@ -51,6 +53,7 @@ std::unique_ptr<Pipeline::Banded> Pipeline::Banded::create(const PipelineConfig&
     Banded& bd = *made;
     bd.cfg = config;
     bd.grouping = detail::group_reductions(config.reductions);
+    bd.spec_filters = filters.any();
     for (int r0 = 0; r0 < g.height; r0 += band_rows) bd.bands.push_back({r0, std::min(r0 + band_rows, g.height)});
     bd.parked.resize(bd.bands.size());
     bd.host_budget = config.host_cache_budget;
@@ -269,9 +272,12 @@ Status Pipeline::Banded::ingest(const PointCloud& cloud) {
         const ScatterInfo here = sub->last_scatter();
         valid_total += here.points_valid;
         last = here;
-        if (!parked[b].any && here.points_valid == 0) continue;        // nothing of this cloud (or any before) fell here
+        // With spec filters the last scatter's count is its own class's: a group before it, or the touched flags, may have
+        // taken points where it took none -- every band the cloud reaches counts as changed then
+        const bool changed = here.points_valid != 0 || spec_filters;
+        if (!parked[b].any && !changed) continue;                        // nothing of this cloud (or any before) fell here
         Parked& k = parked[b];
-        if (here.points_valid == 0 && k.any) {                           // unchanged: the parked copy (and its files) stay current
+        if (!changed && k.any) {                                         // unchanged: the parked copy (and its files) stay current
             if (from_disk) drop_host_copy(b);
             else if (!(s = evict()).ok()) return s;
             continue;

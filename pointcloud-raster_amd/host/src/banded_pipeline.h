@@ -30,6 +30,7 @@ struct Pipeline::Banded {
     PipelineConfig cfg;                                   // the WHOLE grid, as the caller gave it
     std::vector<std::pair<int, int>> bands;               // [r0, r1), multiples of the tile height
     detail::Grouping grouping;                            // groups' plane masks, one StateOutput per ReductionSpec
+    bool spec_filters = false;                            // some ReductionSpec has a filter of its own (detail::FilterPlan::any)
     struct Parked {
         bool any = false, on_disk = false;
         std::vector<std::vector<float>> planes;           // [4 g + p]: the band's window of plane p of group g (empty: no such plane)

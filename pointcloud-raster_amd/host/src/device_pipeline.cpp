@@ -41,6 +41,7 @@ Status Pipeline::Impl::init() {
         return Status::error(StatusCode::InvalidArgument, "pipeline: tile dimensions must be positive");
     {
         Status ok = detail::check_reduction_specs(cfg.reductions);
+        if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
         if (!ok.ok()) return ok;
     }
 
@@ -109,11 +110,13 @@ Status Pipeline::Impl::init() {
     }
 
     // accumulation groups + outputs
-    for (const auto& r : cfg.reductions) {
+    for (size_t ri = 0; ri < cfg.reductions.size(); ++ri) {
+        const ReductionSpec& r = cfg.reductions[ri];
         int gi = -1;
         for (size_t k = 0; k < groups.size(); ++k)
             if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph) &&
-                groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel))
+                groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel) &&
+                detail::same_filter(groups[k].filter, r.filter))
                 gi = (int)k;                                 // (detail::same_group)
         if (gi < 0) {
             groups.emplace_back();
@@ -122,6 +125,8 @@ Status Pipeline::Impl::init() {
             groups[gi].glyph = r.glyph;
             groups[gi].select = detail::is_select(r.type);
             if (groups[gi].select) groups[gi].key_channel = r.timestamp_channel;
+            groups[gi].filter = r.filter;
+            groups[gi].cls = filters.class_of[ri];
         }
         // a glyph reduction of an unsupported type is rejected at ingest (as in the reference);
         // it still gets planes so that finalize has something to read.
@@ -273,6 +278,9 @@ Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
 bool Pipeline::Impl::offer_bands(size_t gi) {
     const Group& gr = groups[gi];
     if (gr.select) return false;                   // (its tile pass stores no bands: finalize_select always runs)
+    // A group with a filter of its own: the fused tile pass judges "touched" from its OWN scatter's points, the pipeline's
+    // flags come from PipelineConfig::filter's survivors -- its bands are made by finalize (the known cost of a spec filter)
+    if (gr.cls != 0) return false;
     if (!cfg.finalize_with_first_ingest || gr.defined || gr.glyph.type != GlyphType::Point || state_shared || !result ||
         !d_bands_done.data()) return false;
     if (hg.own_row0 != hg.state_row0 || own_rows() != hg.state_rows || own_rows() <= 0) return false;
@@ -661,6 +669,45 @@ Status Pipeline::Impl::marshal_glyph(const GlyphSpec& gl, const detail::ChannelL
     return s;
 }
 
+// ReductionSpec::filter: ONE sweep over the points (pcr_hip_filter_classes) makes the mask of every filter class, into the
+// "filter:mask" staging buffer laid out [128 B: u64 survivor counts][class masks, each a multiple of 16 bytes apart].
+// (*masks)[k]: class k's mask; null for class 0 when there is no cfg.filter (every point is kept).  *kept: cfg.filter's
+// survivors -- read back, with the one host wait count_survivors always had, only when there is a cfg.filter; an ingest
+// without one enqueues the sweep and waits for nothing.  (Nine masks -- cfg.filter and eight spec filters -- take a second
+// call for the ninth: the C-ABI sweeps eight classes at a time.)
+Status Pipeline::Impl::sweep_filter_classes(const detail::ChannelLookup& channel, size_t n, std::vector<const uint8_t*>* masks, size_t* kept) {
+    FilterSpec table;
+    table.predicates = filters.table;
+    std::vector<pcr_hip_predicate> preds;
+    Status s = detail::marshal_predicates(table, channel, &preds);
+    if (!s.ok()) return s;
+    const bool with_cfg = !cfg.filter.empty();
+    const size_t first = with_cfg ? 0 : 1, n_cls = filters.classes.size();
+    const size_t stride = (n + 15) & ~(size_t)15, header = 128;
+    detail::Buffer& mb = staging["filter:mask"];
+    if (mb.bytes() < header + (n_cls - first) * stride) {
+        if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;     // (chunks in flight may still read the old block)
+        if (!(s = mb.allocate(header + (n_cls - first) * (stride + stride / 8 + 16), MemoryLocation::Device)).ok()) return s;
+    }
+    uint8_t* const base = static_cast<uint8_t*>(mb.data()) + header;
+    auto* const d_counts = static_cast<unsigned long long*>(mb.data());
+    masks->assign(n_cls, nullptr);
+    for (size_t c = first; c < n_cls; c += PCR_HIP_MAX_FILTER_CLASSES) {
+        const int m = (int)std::min<size_t>(PCR_HIP_MAX_FILTER_CLASSES, n_cls - c);
+        s = detail::hip_status(pcr_hip_filter_classes(preds.data(), (int)preds.size(), filters.words.data() + c, m, n,
+                                                      base + (c - first) * stride, stride, with_cfg && c == 0 ? d_counts : nullptr, stream));
+        if (!s.ok()) return s;
+        for (int k = 0; k < m; ++k) (*masks)[c + (size_t)k] = base + (c - first + (size_t)k) * stride;
+    }
+    *kept = n;
+    if (!with_cfg) return Status::success();
+    unsigned long long h_count = 0;
+    if (!(s = detail::hip_status(pcr_hip_memcpy_d2h(&h_count, d_counts, sizeof h_count, stream))).ok()) return s;
+    if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
+    *kept = (size_t)h_count;
+    return Status::success();
+}
+
 Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     const size_t n = cloud.count();
     if (n == 0) return Status::success();
@@ -721,7 +768,14 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     // here a filtered-out point simply does not exist for any reduction.)
     size_t kept = n;
     const uint8_t* active_mask = nullptr;
-    if (!cfg.filter.empty()) {
+    // ReductionSpec::filter: every group scatters under the mask of its class; class 0 is cfg.filter alone (active_mask)
+    std::vector<const uint8_t*> class_mask;
+    if (filters.any()) {
+        if (!(s = sweep_filter_classes(f32_channel, n, &class_mask, &kept)).ok()) return s;
+        if (kept == 0) return Status::success();                 // pipeline.cpp:349-353: cfg.filter keeps nothing
+        active_mask = class_mask[0];
+        pcr_hip_engine_set_point_mask(engine, active_mask);
+    } else if (!cfg.filter.empty()) {
         std::vector<pcr_hip_predicate> preds;
         if (!(s = detail::marshal_predicates(cfg.filter, f32_channel, &preds)).ok()) return s;
         detail::Buffer& mb = staging["filter:mask"];
@@ -748,18 +802,27 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
         const float* hl = nullptr;
         if (!(s = f32_channel(gr.glyph.half_length_channel, &hl)).ok()) return s;
         int rows = 0;
-        if (!(s = line_reach_rows(gr.glyph, hl, active_mask, n, &rows)).ok()) return s;
+        if (!(s = line_reach_rows(gr.glyph, hl, filters.any() ? class_mask[(size_t)gr.cls] : active_mask, n, &rows)).ok()) return s;
         reach_needed = std::max(reach_needed, rows);
     }
     if (reach_needed > halo) return reach_error(reach_needed);
 
     // (this cloud's points change the planes and the touched flags)
     if (!(s = bands_stale()).ok()) return s;
+    // The touched flags are cfg.filter's survivors', whatever the groups' own filters keep.  An unfiltered group's scatter
+    // sets exactly those; when every group is filtered a pass of its own does, ahead of the first scatter.
+    bool flags_by_scatter = !filters.any();
+    for (const auto& gr : groups) flags_by_scatter = flags_by_scatter || gr.cls == 0;
+    if (!flags_by_scatter) {
+        s = detail::hip_status(pcr_hip_engine_touch(engine, static_cast<const double*>(dx), static_cast<const double*>(dy), n));
+        if (!s.ok()) return s;
+    }
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         Group& gr = groups[gi];
         const float* dv = nullptr;
         s = f32_channel(gr.value_channel, &dv);
         if (!s.ok()) return s;
+        if (filters.any()) pcr_hip_engine_set_point_mask(engine, class_mask[(size_t)gr.cls]);
         pcr_hip_engine_planes_fresh(engine, scatter_mode(gr));
         bool offered = false;
         if (gr.select) {                             // (Point glyph: validate_cloud refused anything else)

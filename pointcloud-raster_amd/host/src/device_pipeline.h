@@ -32,6 +32,8 @@ struct Pipeline::Impl {
         bool select = false;
         std::string key_channel;
         detail::Buffer packed;
+        FilterSpec filter;               // ReductionSpec::filter of the group's specs (part of the grouping key)
+        int cls = 0;                     // its filter class (detail::FilterPlan): 0 = PipelineConfig::filter alone
         bool fresh = true;               // nothing has been accumulated yet: the first Point merge may store
         bool defined = false;            // the planes hold values (identity or accumulated).  They are NOT filled at create:
                                          // the first scatter defines them inside ingest, as the reference initialises its tile
@@ -92,6 +94,7 @@ struct Pipeline::Impl {
     detail::GroundPlan ground;               // PipelineConfig::ground, planned at init
     detail::Buffer d_ground_work;            // its workspace, allocated by the first finalize, grow-only
     detail::TerrainPlan terrain;             // PipelineConfig::terrain, planned at init
+    detail::FilterPlan filters;              // ReductionSpec::filter of every spec, planned at init
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
                                              // both sides): the blocking finalize reads it after its synchronise and launches
@@ -164,6 +167,7 @@ struct Pipeline::Impl {
     Status line_reach_rows(const GlyphSpec& gl, const void* d_half_length, const uint8_t* d_mask, size_t n, int* rows_needed);
     Status reach_error(int rows) const;
     Status device_array(const void* src, MemoryLocation loc, size_t bytes, const std::string& key, const void** out);
+    Status sweep_filter_classes(const detail::ChannelLookup& channel, size_t n, std::vector<const uint8_t*>* masks, size_t* kept);
     Status marshal_glyph(const GlyphSpec& gl, const detail::ChannelLookup& channel, pcr_hip_glyph* out) const;
     Status allocate_result();
     Status checkpoint_dir(const std::string& dir_in, std::string* dir, bool writing) const;

@@ -229,12 +229,12 @@ void HostEngine::build_lists(std::vector<uint32_t>& list, std::vector<size_t>& f
     }
 }
 
-void HostEngine::scatter_point(HostPlanes& p, const float* v) {
+void HostEngine::scatter_point(HostPlanes& p, const float* v, const uint8_t* keep) {
     if (n_ == 0) return;
     std::vector<uint32_t> list;
     std::vector<size_t> first;
     build_lists(list, first, [&](size_t i, Span& sp) {
-        if (row_[i] < 0) return false;
+        if (row_[i] < 0 || (keep && !keep[i])) return false;
         sp.lo = sp.hi = row_[i];
         return true;
     });
@@ -257,12 +257,12 @@ void HostEngine::scatter_point(HostPlanes& p, const float* v) {
     }
 }
 
-void HostEngine::scatter_select(HostPlanes& p, const float* v, const float* key) {
+void HostEngine::scatter_select(HostPlanes& p, const float* v, const float* key, const uint8_t* keep) {
     if (n_ == 0 || !v || !key) return;
     std::vector<uint32_t> list;
     std::vector<size_t> first;
     build_lists(list, first, [&](size_t i, Span& sp) {
-        if (row_[i] < 0 || !select_accepts(key[i])) return false;
+        if (row_[i] < 0 || (keep && !keep[i]) || !select_accepts(key[i])) return false;
         sp.lo = sp.hi = row_[i];
         return true;
     });
@@ -288,7 +288,7 @@ void HostEngine::normalize_select(HostPlanes& p) const {
     for (int64_t i = 0; i < cells; ++i) select_state_of_word(select_word_of_state(val[i], ts[i]), &val[i], &ts[i]);
 }
 
-void HostEngine::scatter_glyph(HostPlanes& p, const GlyphSpec& glyph, const HostGlyphArrays& arr, const float* v) {
+void HostEngine::scatter_glyph(HostPlanes& p, const GlyphSpec& glyph, const HostGlyphArrays& arr, const float* v, const uint8_t* keep) {
     if (n_ == 0) return;
     float* sum = (p.mask & 1u) ? p.plane[0].data() : nullptr;
     float* wgt = (p.mask & 2u) ? p.plane[1].data() : nullptr;
@@ -297,7 +297,7 @@ void HostEngine::scatter_glyph(HostPlanes& p, const GlyphSpec& glyph, const Host
     const GridConfig& g = g_;
     if (glyph.type == GlyphType::Gaussian) {
         build_lists(list, first, [&](size_t i, Span& sp) {
-            if (row_[i] < 0) return false;
+            if (row_[i] < 0 || (keep && !keep[i])) return false;
             const Splat s = make_splat(g, glyph, arr, i, x_[i], y_[i], col_[i], row_[i]);
             if (!s.ok) return false;
             sp.lo = (int)std::max<int64_t>((int64_t)s.icy - s.r, s.clip.r0);
@@ -336,7 +336,7 @@ void HostEngine::scatter_glyph(HostPlanes& p, const GlyphSpec& glyph, const Host
     }
     if (glyph.type != GlyphType::Line) return;
     build_lists(list, first, [&](size_t i, Span& sp) {
-        if (row_[i] < 0) return false;
+        if (row_[i] < 0 || (keep && !keep[i])) return false;
         const Segment s = make_segment(g, glyph, arr, i, x_[i], y_[i], col_[i], row_[i]);
         if (!s.ok) return false;
         sp.lo = std::max(std::min(s.iy0, s.iy1), s.clip.r0);

@@ -54,15 +54,17 @@ public:
     /// Routes one cloud (at most 2^31 points): cell of every point, touched tiles.  keep[i] == 0: point i does not exist
     /// (the filter stage); keep may be null.  Returns the points inside the grid.  The scatter calls below fold THIS cloud.
     size_t route(const double* x, const double* y, const uint8_t* keep, size_t n);
-    void scatter_point(HostPlanes& p, const float* v);
+    /// keep (optional, in every scatter below): the mask of the group's own filter (ReductionSpec::filter) over the routed cloud --
+    /// keep[i] == 0: the group does not fold point i; routing and the touched flags are not its business.
+    void scatter_point(HostPlanes& p, const float* v, const uint8_t* keep = nullptr);
     /// MostRecent: per stripe, the maximum word(key, v) of the accepted points of every cell (include/pcr_hip.h); the same
     /// bits as the HIP engine whatever the thread count -- the fold is commutative and idempotent.
-    void scatter_select(HostPlanes& p, const float* v, const float* key);
+    void scatter_select(HostPlanes& p, const float* v, const float* key, const uint8_t* keep = nullptr);
     /// A select group's planes as a checkpoint left them -> the canonical form a fold leaves (a NaN or <= -FLT_MAX timestamp
     /// means empty: {NaN, -FLT_MAX}; a -0.0 timestamp is +0.0).
     void normalize_select(HostPlanes& p) const;
     /// Planes 0 / 1 only (glyph reductions are Sum, Count, Average, WeightedAverage).
-    void scatter_glyph(HostPlanes& p, const GlyphSpec& glyph, const HostGlyphArrays& arr, const float* v);
+    void scatter_glyph(HostPlanes& p, const GlyphSpec& glyph, const HostGlyphArrays& arr, const float* v, const uint8_t* keep = nullptr);
 
     /// Op::finalize per cell where the reference tile is touched, NaN elsewhere (src/engine/pipeline.cpp:1204-1222).
     void finalize(const HostPlanes& p, ReductionType type, float* band) const;

@@ -25,6 +25,7 @@ Status Pipeline::Host::init() {
         return Status::error(StatusCode::InvalidArgument, "pipeline: tile dimensions must be positive");
     {
         Status ok = detail::check_reduction_specs(cfg.reductions);
+        if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
         if (!ok.ok()) return ok;
     }
     if (cfg.shard_row_begin >= 0 || cfg.shard_row_end >= 0)
@@ -32,11 +33,13 @@ Status Pipeline::Host::init() {
     if (cfg.result_location == MemoryLocation::Device)
         return Status::error(StatusCode::InvalidArgument, "pipeline: the CPU engine's result lives in host memory (result_location = Device asked)");
     engine = std::make_unique<detail::HostEngine>(g, (int)cfg.cpu_threads);        // cpu_threads = 0: every core (pipeline.h:78)
-    for (const auto& r : cfg.reductions) {
+    for (size_t ri = 0; ri < cfg.reductions.size(); ++ri) {
+        const ReductionSpec& r = cfg.reductions[ri];
         int gi = -1;
         for (size_t k = 0; k < groups.size(); ++k)
             if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph) &&
-                groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel))
+                groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel) &&
+                detail::same_filter(groups[k].filter, r.filter))
                 gi = (int)k;                                         // (detail::same_group)
         if (gi < 0) {
             groups.emplace_back();
@@ -45,6 +48,8 @@ Status Pipeline::Host::init() {
             groups[(size_t)gi].glyph = r.glyph;
             groups[(size_t)gi].select = detail::is_select(r.type);
             if (groups[(size_t)gi].select) groups[(size_t)gi].key_channel = r.timestamp_channel;
+            groups[(size_t)gi].filter = r.filter;
+            groups[(size_t)gi].cls = filters.class_of[ri];
         }
         groups[(size_t)gi].mask |= planes_for(r.type);
         Output o;
@@ -99,11 +104,12 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
 
     // Filter stage: AND of the predicates (evaluate_predicate, src/engine/filter.cpp:34-56).  As in the HIP pipeline a
     // filtered-out point does not exist for any reduction (the reference routes the unfiltered cloud: DESIGN section 1).
-    std::vector<uint8_t> keep;
-    size_t kept = n;
-    if (!cfg.filter.empty()) {
+    // ReductionSpec::filter: `keep` (cfg.filter) routes the cloud and sets the touched flags; a group with a filter of its own
+    // folds only the points its class keeps on top of that (class_keep[k], the spec filter alone: a point cfg.filter drops is
+    // routed nowhere).  Byte masks, so the bits are the same at any thread count.
+    auto apply = [&](const FilterSpec& filter, std::vector<uint8_t>& keep) {
         keep.assign(n, 1);
-        for (const auto& pr : cfg.filter.predicates) {
+        for (const auto& pr : filter.predicates) {
             const float* ch = cloud->channel_f32(pr.channel_name);
             const int team = engine->threads();
 #pragma omp parallel for num_threads(team) schedule(static)
@@ -128,10 +134,18 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
                 if (!ok) keep[(size_t)i] = 0;
             }
         }
+    };
+    std::vector<uint8_t> keep;
+    size_t kept = n;
+    if (!cfg.filter.empty()) {
+        apply(cfg.filter, keep);
         kept = 0;
         for (uint8_t k : keep) kept += k;
         if (kept == 0) return Status::success();                     // pipeline.cpp:349-353
     }
+    std::vector<std::vector<uint8_t>> class_keep(filters.classes.size());
+    for (size_t k = 1; k < filters.classes.size(); ++k) apply(filters.classes[k], class_keep[k]);
+    auto keep_of = [&](const Group& gr, size_t i0) -> const uint8_t* { return gr.cls ? class_keep[(size_t)gr.cls].data() + i0 : nullptr; };
 
     // the engine indexes a cloud with 32 bits: larger ones go in slices
     const size_t slice = (size_t)1 << 31;
@@ -142,9 +156,9 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         for (auto& gr : groups) {
             const float* v = f32(gr.value_channel);
             if (gr.select) {                                         // (Point glyph: validate_cloud refused anything else)
-                engine->scatter_select(gr.planes, v + i0, f32(gr.key_channel) + i0);
+                engine->scatter_select(gr.planes, v + i0, f32(gr.key_channel) + i0, keep_of(gr, i0));
             } else if (gr.glyph.type == GlyphType::Point) {
-                engine->scatter_point(gr.planes, v + i0);
+                engine->scatter_point(gr.planes, v + i0, keep_of(gr, i0));
             } else {
                 detail::HostGlyphArrays arr;
                 auto at = [&](const std::string& name) { const float* p = f32(name); return p ? p + i0 : nullptr; };
@@ -156,7 +170,7 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
                 detail::HostPlanes& pl = gr.planes;
                 const uint32_t keep_mask = pl.mask;
                 pl.mask &= 3u;                                        // glyph reductions feed the sum and weight planes only
-                engine->scatter_glyph(pl, gr.glyph, arr, v + i0);
+                engine->scatter_glyph(pl, gr.glyph, arr, v + i0, keep_of(gr, i0));
                 pl.mask = keep_mask;
             }
         }

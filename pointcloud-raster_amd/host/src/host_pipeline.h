@@ -23,6 +23,8 @@ struct Pipeline::Host {
         GlyphSpec glyph;
         detail::HostPlanes planes;
         uint32_t mask = 0;
+        FilterSpec filter;               // ReductionSpec::filter of the group's specs (part of the grouping key)
+        int cls = 0;                     // its filter class (detail::FilterPlan): 0 = PipelineConfig::filter alone
     };
     struct Output {
         int group = 0;
@@ -34,6 +36,7 @@ struct Pipeline::Host {
     std::unique_ptr<detail::HostEngine> engine;
     std::vector<Group> groups;
     std::vector<Output> outputs;
+    detail::FilterPlan filters;          // ReductionSpec::filter of every spec, planned at init
     std::unique_ptr<Grid> result;
     bool finalized = false;
     ProgressCallback callback;

@@ -31,8 +31,8 @@ namespace {
 
 thread_local std::string g_create_error;
 
-// Every channel a configuration reads from its clouds: the reductions' value, weight, timestamp and glyph channels and the
-// filter's -- what a LAS file is decoded into (a Pipeline never looks at any other).
+// Every channel a configuration reads from its clouds: the reductions' value, weight, timestamp and glyph channels, their own
+// filters' and the pipeline filter's -- what a LAS file is decoded into (a Pipeline never looks at any other).
 std::vector<std::string> named_channels(const PipelineConfig& c) {
     std::vector<std::string> out;
     auto add = [&out](const std::string& name) {
@@ -47,6 +47,7 @@ std::vector<std::string> named_channels(const PipelineConfig& c) {
         add(r.glyph.sigma_x_channel);
         add(r.glyph.sigma_y_channel);
         add(r.glyph.rotation_channel);
+        for (const auto& p : r.filter.predicates) add(p.channel_name);
     }
     for (const auto& p : c.filter.predicates) add(p.channel_name);
     return out;

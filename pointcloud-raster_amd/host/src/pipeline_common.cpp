@@ -14,18 +14,25 @@ namespace pcr {
 namespace detail {
 
 Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t max_set, size_t max_predicates) {
-    for (const auto& pr : cfg.filter.predicates) {
-        if (!cloud.channel_data(pr.channel_name))
-            return Status::error(StatusCode::InvalidArgument, "filter_points: channel not found: " + pr.channel_name);
-        const ChannelDesc* d = cloud.channel(pr.channel_name);
-        if (!d || d->dtype != DataType::Float32)
-            return Status::error(StatusCode::InvalidArgument, "filter_points: only Float32 channels supported for filtering");
-        if (max_set && pr.value_set.size() > max_set)
-            return Status::error(StatusCode::InvalidArgument,
-                                 "filter_points: value_set larger than " + std::to_string(max_set) + " entries is not supported on the device");
-    }
+    auto check_filter = [&](const FilterSpec& filter) -> Status {
+        for (const auto& pr : filter.predicates) {
+            if (!cloud.channel_data(pr.channel_name))
+                return Status::error(StatusCode::InvalidArgument, "filter_points: channel not found: " + pr.channel_name);
+            const ChannelDesc* d = cloud.channel(pr.channel_name);
+            if (!d || d->dtype != DataType::Float32)
+                return Status::error(StatusCode::InvalidArgument, "filter_points: only Float32 channels supported for filtering");
+            if (max_set && pr.value_set.size() > max_set)
+                return Status::error(StatusCode::InvalidArgument,
+                                     "filter_points: value_set larger than " + std::to_string(max_set) + " entries is not supported on the device");
+        }
+        return Status::success();
+    };
+    Status fs = check_filter(cfg.filter);
+    if (!fs.ok()) return fs;
     if (max_predicates && cfg.filter.predicates.size() > max_predicates)
         return Status::error(StatusCode::InvalidArgument, "filter_points: more than " + std::to_string(max_predicates) + " predicates");
+    for (const auto& r : cfg.reductions)                       // ReductionSpec::filter: the same checks, the same messages
+        if (!(fs = check_filter(r.filter)).ok()) return fs;
     for (const auto& r : cfg.reductions) {
         if (!cloud.channel_data(r.value_channel))
             return Status::error(StatusCode::InvalidArgument, "pipeline: value channel not found: " + r.value_channel);
@@ -42,6 +49,53 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
             if (!t || t->dtype != DataType::Float32)
                 return Status::error(StatusCode::InvalidArgument, "pipeline: timestamp channel must be Float32");
         }
+    }
+    return Status::success();
+}
+
+Status plan_filters(const PipelineConfig& cfg, FilterPlan* out) {
+    *out = FilterPlan{};
+    out->classes.emplace_back();
+    for (const auto& r : cfg.reductions) {
+        int cls = 0;
+        if (!r.filter.empty()) {
+            for (size_t k = 1; k < out->classes.size() && !cls; ++k)
+                if (same_filter(out->classes[k], r.filter)) cls = (int)k;
+            if (!cls) {
+                out->classes.push_back(r.filter);
+                cls = (int)out->classes.size() - 1;
+            }
+        }
+        out->class_of.push_back(cls);
+    }
+    if (!out->any()) { out->words.assign(1, 0u); return Status::success(); }
+    if (out->classes.size() - 1 > kMaxSpecFilters)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(kMaxSpecFilters) +
+                                                          " distinct reduction filters in one pipeline");
+    for (size_t k = 1; k < out->classes.size(); ++k)
+        if (cfg.filter.predicates.size() + out->classes[k].predicates.size() > PCR_HIP_MAX_FILTER_PREDICATES)
+            return Status::error(StatusCode::InvalidArgument,
+                "pipeline: a reduction filter and the pipeline's filter together hold more than " +
+                std::to_string(PCR_HIP_MAX_FILTER_PREDICATES) + " predicates");
+    auto place = [out](const FilterPredicate& pr) {
+        for (size_t t = 0; t < out->table.size(); ++t)
+            if (same_predicate(out->table[t], pr)) return t;
+        out->table.push_back(pr);
+        return out->table.size() - 1;
+    };
+    std::vector<std::vector<size_t>> at(out->classes.size());
+    for (const auto& pr : cfg.filter.predicates) at[0].push_back(place(pr));
+    for (size_t k = 1; k < out->classes.size(); ++k) {
+        at[k] = at[0];
+        for (const auto& pr : out->classes[k].predicates) at[k].push_back(place(pr));
+    }
+    if (out->table.size() > PCR_HIP_MAX_CLASS_PREDICATES)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(PCR_HIP_MAX_CLASS_PREDICATES) +
+                                                          " distinct filter predicates in one pipeline");
+    for (const auto& list : at) {
+        uint32_t w = 0;
+        for (size_t t : list) w |= 1u << t;
+        out->words.push_back(w);
     }
     return Status::success();
 }

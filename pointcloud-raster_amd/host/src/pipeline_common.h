@@ -136,11 +136,22 @@ struct Grouping {
     std::vector<uint8_t> select;             // per group: a MostRecent group (planes 0 / 1 = value / timestamp)
     std::vector<StateOutput> outputs;        // per ReductionSpec
 };
-// A MostRecent spec is keyed by (value channel, timestamp channel) and never shares a group with the accumulations.
+// ReductionSpec::filter: equal means the same predicates in the same order, field by field.
+inline bool same_predicate(const FilterPredicate& a, const FilterPredicate& b) {
+    return a.channel_name == b.channel_name && a.op == b.op && a.value == b.value && a.value_set == b.value_set;
+}
+inline bool same_filter(const FilterSpec& a, const FilterSpec& b) {
+    if (a.predicates.size() != b.predicates.size()) return false;
+    for (size_t k = 0; k < a.predicates.size(); ++k)
+        if (!same_predicate(a.predicates[k], b.predicates[k])) return false;
+    return true;
+}
+// A MostRecent spec is keyed by (value channel, timestamp channel) and never shares a group with the accumulations; specs
+// with different filters see different points and never share a group either.
 inline bool same_group(const ReductionSpec& a, const ReductionSpec& b) {
     if (is_select(a.type) != is_select(b.type)) return false;
     if (is_select(a.type) && a.timestamp_channel != b.timestamp_channel) return false;
-    return a.value_channel == b.value_channel && same_glyph(a.glyph, b.glyph);
+    return a.value_channel == b.value_channel && same_glyph(a.glyph, b.glyph) && same_filter(a.filter, b.filter);
 }
 inline Grouping group_reductions(const std::vector<ReductionSpec>& reductions) {
     Grouping out;
@@ -196,6 +207,23 @@ Status marshal_predicates(const FilterSpec& filter, const ChannelLookup& channel
 /// device memory), waits for the stream and returns the count.  The mask starts at filter_mask_of(d_buffer).
 Status count_survivors(const std::vector<pcr_hip_predicate>& preds, size_t n, void* d_buffer, pcr_hip_stream stream, size_t* kept);
 inline uint8_t* filter_mask_of(void* d_buffer) { return static_cast<uint8_t*>(d_buffer) + 8; }
+
+// ---- per-reduction filters (ReductionSpec::filter), planned at create on every engine ----------------------------------------
+// Class 0 is PipelineConfig::filter alone (the specs with an empty filter); class k >= 1 is the k-th distinct non-empty spec
+// filter in order of first appearance.  A point contributes to a spec when it passes PipelineConfig::filter AND the spec's
+// class: words[k] is that conjunction as bits of `table`, the distinct predicates of the whole configuration.
+constexpr size_t kMaxSpecFilters = 8;
+struct FilterPlan {
+    std::vector<FilterSpec> classes;         // [0] is empty
+    std::vector<int> class_of;               // per ReductionSpec
+    std::vector<FilterPredicate> table;      // PipelineConfig::filter's predicates first
+    std::vector<uint32_t> words;             // per class
+    bool any() const { return classes.size() > 1; }
+};
+/// InvalidArgument, with the same message on every engine, for more than kMaxSpecFilters distinct non-empty spec filters, a
+/// conjunction longer than PCR_HIP_MAX_FILTER_PREDICATES, or more than PCR_HIP_MAX_CLASS_PREDICATES distinct predicates.  A
+/// configuration without spec filters is planned as it always was: one class, nothing refused here.
+Status plan_filters(const PipelineConfig& cfg, FilterPlan* out);
 
 // ---- reprojection on ingest (PipelineConfig::target_crs / auto_reproject; pcr/core/reproject.h) ---------------------------
 /// CRS -> the C-ABI's descriptor; CrsError when it is unidentified or not supported.  role: "source" / "destination".

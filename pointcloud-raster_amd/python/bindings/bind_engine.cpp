@@ -74,7 +74,11 @@ void bind_engine(py::module_& m) {
                        "greater value wins, so the result does not depend on order, engine or chunking. Required for MostRecent.")
         .def_readwrite("percentile", &ReductionSpec::percentile)
         .def_readwrite("output_band_name", &ReductionSpec::output_band_name)
-        .def_readwrite("glyph", &ReductionSpec::glyph);
+        .def_readwrite("glyph", &ReductionSpec::glyph)
+        .def_readwrite("filter", &ReductionSpec::filter,
+                       "This reduction folds only the points that pass PipelineConfig.filter AND this FilterSpec (empty: every "
+                       "survivor of the pipeline's filter). spec.filter.add(...) works in place. The touched-tile flags come from "
+                       "PipelineConfig.filter's survivors alone: a filtered Sum is 0, not NaN, in a tile other points touched.");
 
     py::class_<GroundFilterConfig, GroundFilterSpec>(m, "GroundFilterConfig")
         .def(py::init<>())

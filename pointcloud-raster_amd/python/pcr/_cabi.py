@@ -165,6 +165,8 @@ SYMBOLS = {
     "pcr_hip_engine_tile_touched": [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "pcr_hip_filter_mask": [C.POINTER(Predicate), C.c_int, _U64, _VP, _VP, _VP],
     "pcr_hip_engine_set_point_mask": [_VP, _VP],
+    "pcr_hip_filter_classes": [C.POINTER(Predicate), C.c_int, C.POINTER(_U32), C.c_int, _U64, _VP, _U64, _VP, _VP],
+    "pcr_hip_engine_touch": [_VP, _VP, _VP, _U64],
     "pcr_hip_engine_profile_enable": [_VP, C.c_int],
     "pcr_hip_engine_profile_only": [_VP, C.c_char_p],
     "pcr_hip_engine_profile_read": [_VP, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int), C.c_int],
