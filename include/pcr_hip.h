@@ -647,6 +647,38 @@ int pcr_hip_las_decode(const pcr_hip_las_layout* layout, const uint8_t* d_record
 int pcr_hip_las_decode_host(const pcr_hip_las_layout* layout, const uint8_t* h_records, uint64_t n, double* h_x, double* h_y,
                             float* const* channels, int threads);
 
+/* ---- a band sampled at the points of a cloud: the way back from a raster to the points (pcr/core/sample_grid.h,
+ *      PipelineConfig::surface_channels).  No reference counterpart.  The contract is written once, in csrc/sample_grid.hpp,
+ *      which the kernel and the host twin both compile with contraction off: they agree bit for bit.
+ *        surface   the band's OWN geometry (bounds, signed cell sizes, width, height; tiles and row windows as
+ *                  pcr_hip_engine_create wants them, unused here); d_band: height rows of width floats, band_stride floats
+ *                  apart.  It need not be the grid the points are rasterised into.
+ *        outside   a point outside the inclusive bounds, or with a NaN coordinate, samples NaN; every NaN that leaves is
+ *                  0x7FC00000
+ *        own cell  (col, row) as the routing answers for that geometry: floor of the true binary64 quotient, then clamp
+ *        NEAREST   the own cell's value e
+ *        BILINEAR  between cell centres, binary64: qx = (x - min_x) / cell_size_x, tx = (qx - col) - 0.5; tx < 0: neighbour
+ *                  column col - 1 with weight wx = -tx, else col + 1 with wx = tx; rows likewise from
+ *                  qy = (y - max_y) / cell_size_y.  A neighbour column or row outside the band is replaced by e's own (so
+ *                  within half a cell of the border the sample is the 1-D interpolation along the edge); of the cells
+ *                  then read (h horizontal, v vertical, d diagonal) a NaN one takes e's value; e NaN: NaN.
+ *                  s = ((1-wx)*(1-wy))*e + (wx*(1-wy))*h + ((1-wx)*wy)*v + (wx*wy)*d, added left to right, never an fma
+ *        out       d_value == NULL: (float)s (NEAREST: e's bits).  Else (float)((double)value - s), one rounding: the height
+ *                  above the surface; a NaN value gives NaN.  +-Inf and denormals are values.
+ *      d_out == d_value (in place, z -> height above ground) is allowed; no other overlap of d_out with an input is.  Any
+ *      4-byte / 8-byte alignment: when x, y, value and out all start on 16 bytes the 16-byte accesses are taken.  A workgroup
+ *      of 256 lanes owns 256 * PCR_HIP_SAMPLE_POINTS_PER_LANE consecutive points.  Argument errors (a grid the engine would
+ *      refuse, non-finite geometry, unknown mode, band_stride < width, null band / x / y / out with n > 0, n > 2^40, overlap)
+ *      are reported before any HIP call; n == 0 launches nothing.  Enqueued on s; nothing is allocated or synchronised.
+ *      _host: the same on host arrays, one thread (callers share the points out: every point is independent). */
+#define PCR_HIP_SAMPLE_NEAREST 0
+#define PCR_HIP_SAMPLE_BILINEAR 1
+#define PCR_HIP_SAMPLE_POINTS_PER_LANE 4
+int pcr_hip_sample_grid(const pcr_hip_grid* surface, const float* d_band, int64_t band_stride, const double* d_x,
+                        const double* d_y, const float* d_value, uint64_t n, int mode, float* d_out, pcr_hip_stream s);
+int pcr_hip_sample_grid_host(const pcr_hip_grid* surface, const float* h_band, int64_t band_stride, const double* h_x,
+                             const double* h_y, const float* h_value, uint64_t n, int mode, float* h_out);
+
 #ifdef __cplusplus
 }
 #endif

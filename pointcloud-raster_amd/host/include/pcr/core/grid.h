@@ -58,6 +58,13 @@ public:
 
     std::vector<uint8_t> valid_mask(int band_index = 0) const;
 
+    /// Extension: where the cells lie in the world -- bounds, signed cell sizes, CRS -- for what carries a raster back to
+    /// points (pcr/core/sample_grid.h, Pipeline::set_surface).  A grid is created without one; a pipeline tags the result()
+    /// of a whole (unsharded) grid with its own, and to() / to_device_async() carry it along.  InvalidArgument when the
+    /// geometry's width and height are not this grid's cols() and rows().  geometry(): nullptr when none was set.
+    Status set_geometry(const GridConfig& geometry);
+    const GridConfig* geometry() const;
+
 private:
     struct Impl;
     std::unique_ptr<Impl> impl_;

@@ -10,6 +10,7 @@
 
 #include "pcr/core/grid_config.h"
 #include "pcr/core/ground_filter.h"
+#include "pcr/core/sample_grid.h"
 #include "pcr/core/terrain.h"
 #include "pcr/core/types.h"
 #include "pcr/engine/filter.h"
@@ -66,6 +67,15 @@ struct TerrainBandConfig : TerrainSpec {
     std::string source_band;             // any band of the result by name, the ground filter's DTM and hag bands included
     TerrainProduct product = TerrainProduct::Hillshade;
     std::string band_name;               // default "{source_band}_{terrain_product_name(product)}"
+};
+
+/// One entry of PipelineConfig::surface_channels: a per-point Float32 channel the pipeline derives at ingest from a finished
+/// band (Pipeline::set_surface) -- the band's sample at the point, or, with a value_channel, that channel minus the sample
+/// (z and a DTM: the height above ground).  The contract is pcr/core/sample_grid.h's.
+struct SurfaceChannelConfig {
+    std::string name;                    // the channel's name: whatever names a Float32 channel may name it
+    std::string value_channel;           // a Float32 channel of the cloud; empty: the sample itself
+    SampleMode mode = SampleMode::Bilinear;
 };
 
 struct PipelineConfig {
@@ -142,6 +152,18 @@ struct PipelineConfig {
     // ingest_file of a LAS file: subtracted from the GPS time, in Float64, before it becomes the Float32 `gps_time` channel
     // (LasOptions::gps_time_origin; a MostRecent timestamp needs it: Float32 resolves 32 s at 3e8 s).
     double las_gps_time_origin = 0.0;
+    // Surface channels: per-point channels derived from a band at every ingest (every chunk of ingest_file), after the
+    // reprojection -- the reprojected coordinates are sampled, so the surface is in the grid's CRS -- and before the filters,
+    // which may test them.  A name works wherever the configuration names a Float32 channel: a reduction's value_channel or
+    // timestamp_channel, a glyph's per-point channels, a predicate of `filter` or of a ReductionSpec::filter ("hag > 2").  A
+    // NaN sample (a point outside the surface, over a NaN cell, with a NaN value) is a NaN channel value like one a cloud
+    // brings: reductions treat it as they do, every predicate on it is false.  On the HIP engine the channel is gathered in
+    // HBM on the pipeline's stream -- ingest_file of a LAS tile still ships raw records -- and a configuration gives the same
+    // channel bits on both engines.  Each name needs its surface before the first ingest (Pipeline::set_surface); checkpoints
+    // record no surface.  create() refuses an empty or duplicate name, a value_channel that is itself a surface channel, more
+    // than 8 entries, a row-block shard and a pipeline that has to run out of core.  Empty: nothing is allocated, launched or
+    // validated differently.
+    std::vector<SurfaceChannelConfig> surface_channels;
 };
 
 struct ProgressInfo {
@@ -171,6 +193,14 @@ public:
     /// LAS: only the channels the configuration names (reductions, glyphs, filter) are decoded -- one the file's point
     /// format lacks is InvalidArgument; on the HIP engine the raw records cross PCIe and are unpacked in HBM.
     Status ingest_file(const std::string& path, size_t chunk_points = 4u << 20, size_t* points_read = nullptr);
+    /// Extension: gives the surface channel `name` (PipelineConfig::surface_channels) its surface -- band `band` of `grid`,
+    /// which carries its geometry (Grid::set_geometry; result() of another pipeline over a whole grid does) and need not be
+    /// this pipeline's grid.  The band and the geometry are copied into memory the pipeline owns (HBM on the HIP engine), so
+    /// the caller's grid may die or change afterwards; a Device grid's band must be complete (after finalize(), or
+    /// finalize_async() + synchronize()).  May be called again between ingests; on the HIP engine it waits for the pipeline's
+    /// stream first.  InvalidArgument for an unknown name, a grid without geometry, a band outside the grid or not Float32;
+    /// CrsError when the surface's CRS and the grid's are both identified and differ.
+    Status set_surface(const std::string& name, const Grid& grid, int band = 0);
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
     /// the finalize kernels are only ENQUEUED on the pipeline's stream -- result() is valid at once, its bands are complete

@@ -1,6 +1,7 @@
 // banded_pipeline.cpp -- Pipeline::Banded (banded_pipeline.h): band planning at create, the visits of ingest and finalize,
 // the host cache with its `.pcrt` spill, checkpoints of the whole pipeline.
 #include "banded_pipeline.h"
+#include "sample_grid.h"
 
 #include "buffer.h"
 #include "device_pipeline.h"
@@ -317,6 +318,7 @@ Status Pipeline::Banded::finalize() {
     detail::append_terrain_bands(terrain, descs);
     if (!result) result = Grid::create(g.width, g.height, descs, MemoryLocation::Host);
     if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+    (void)result->set_geometry(detail::result_geometry(cfg));
     tiles_active = 0;
     for (size_t b = 0; b < bands.size(); ++b) {
         Status s = Status::success();

@@ -24,6 +24,7 @@ using detail::same_glyph;
 
 Pipeline::Impl::~Impl() {
     if (engine) pcr_hip_engine_destroy(engine);
+    surfaces.clear();
     groups.clear();
     bands.clear();
     band_buffers.clear();
@@ -140,6 +141,8 @@ Status Pipeline::Impl::init() {
     }
     if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
     if (!(s = detail::plan_terrain(cfg, ground, &terrain)).ok()) return s;
+    if (!(s = detail::plan_surfaces(cfg)).ok()) return s;
+    surfaces.resize(cfg.surface_channels.size());
 
     // row window of this device
     int r0 = 0, r1 = g.height;
@@ -708,11 +711,27 @@ Status Pipeline::Impl::sweep_filter_classes(const detail::ChannelLookup& channel
     return Status::success();
 }
 
+// PipelineConfig::surface_channels: the band and its geometry into HBM the pipeline owns.  Chunks in flight may still read the
+// old band: the stream is waited for first (store_surface waits for the copy, so the caller's grid is free on return).
+Status Pipeline::Impl::set_surface(const std::string& name, const Grid& grid, int band) {
+    int index = -1;
+    pcr_hip_grid geom{};
+    Status s = detail::check_surface(cfg, name, grid, band, &index, &geom);
+    if (!s.ok()) return s;
+    DeviceScope dev(cfg.cuda_device_id);
+    if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
+    return detail::store_surface(grid, band, geom, MemoryLocation::Device, stream, &surfaces[(size_t)index]);
+}
+
 Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     const size_t n = cloud.count();
     if (n == 0) return Status::success();
     DeviceScope dev(cfg.cuda_device_id);
     // validate every predicate and reduction before touching state (pipeline_common.cpp: the reference's checks and messages)
+    if (!surfaces.empty()) {
+        Status ok = detail::validate_surfaces(cfg, cloud, surfaces);
+        if (!ok.ok()) return ok;
+    }
     {
         Status ok = detail::validate_cloud(cfg, cloud, PCR_HIP_MAX_FILTER_SET, PCR_HIP_MAX_FILTER_PREDICATES);
         if (!ok.ok()) return ok;
@@ -752,15 +771,36 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     const detail::ChannelLookup f32_channel = [&](const std::string& name, const float** out) -> Status {
         *out = nullptr;
         if (name.empty()) return Status::success();
+        auto hit = staged.find(name);                                         // (a surface channel is staged before any lookup)
+        if (hit != staged.end()) { *out = hit->second; return Status::success(); }
         const ChannelDesc* d = cloud.channel(name);
         if (!d || d->dtype != DataType::Float32) return Status::success();   // -> GlyphSpec default
-        auto hit = staged.find(name);
-        if (hit != staged.end()) { *out = hit->second; return Status::success(); }
         const void* p = nullptr;
         Status st = device_array(cloud.channel_data(name), loc, n * sizeof(float), "ch:" + name, &p);
         if (st.ok()) staged[name] = *out = static_cast<const float*>(p);
         return st;
     };
+
+    // Surface channels: each gathered once, for all n points, from its band in HBM at the (reprojected) coordinates, into a
+    // staging buffer of its own that the lookup above then answers with -- the filters, the glyph marshalling, the Line reach
+    // check and every scatter below pick it up like a channel the cloud brought.  On the pipeline's stream, no host wait.
+    for (size_t k = 0; k < surfaces.size(); ++k) {
+        const SurfaceChannelConfig& sc = cfg.surface_channels[k];
+        const float* dz = nullptr;
+        if (!(s = f32_channel(sc.value_channel, &dz)).ok()) return s;
+        detail::Buffer& sb = staging["surface:" + sc.name];
+        if (sb.bytes() < n * sizeof(float)) {
+            // earlier kernels (chunks of ingest_async / ingest_file still in flight) may still read the old block
+            if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
+            if (!(s = sb.allocate((n + n / 8) * sizeof(float), MemoryLocation::Device)).ok()) return s;
+        }
+        const detail::Surface& sf = surfaces[k];
+        s = detail::hip_status(pcr_hip_sample_grid(&sf.geom, static_cast<const float*>(sf.band.data()), sf.geom.width,
+                                                   static_cast<const double*>(dx), static_cast<const double*>(dy), dz, n,
+                                                   (int)sc.mode, static_cast<float*>(sb.data()), stream));
+        if (!s.ok()) return s;
+        staged[sc.name] = static_cast<const float*>(sb.data());
+    }
 
     // Filter stage, on the device: a byte mask evaluated once per ingest and honoured by every
     // routing kernel.  (The reference gathers values by filter index but routes the UNFILTERED
@@ -882,6 +922,7 @@ Status Pipeline::Impl::allocate_result() {
     result = on_device ? Grid::create(W, rows, descs, MemoryLocation::Device)
                        : Grid::create_host_page_locked(W, rows, descs);
     if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+    if (rows == cfg.grid.height) (void)result->set_geometry(detail::result_geometry(cfg));     // (a shard's block is no grid of its own)
     // the table of leaving bands and the buffers behind it: the rule (device_pipeline.h, LeavingBand) applied once
     const size_t n_out = outputs.size();
     bands.assign(n_out + (size_t)ground.extra_bands() + (size_t)terrain.extra_bands(), LeavingBand{});

@@ -8,6 +8,7 @@
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
+#include "sample_grid.h"
 #include "terrain.h"
 
 #include <chrono>
@@ -95,6 +96,7 @@ struct Pipeline::Impl {
     detail::Buffer d_ground_work;            // its workspace, allocated by the first finalize, grow-only
     detail::TerrainPlan terrain;             // PipelineConfig::terrain, planned at init
     detail::FilterPlan filters;              // ReductionSpec::filter of every spec, planned at init
+    std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in HBM (set_surface)
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
                                              // both sides): the blocking finalize reads it after its synchronise and launches
@@ -115,6 +117,7 @@ struct Pipeline::Impl {
     Status init();
     Status ingest(const PointCloud& cloud, bool wait = true);
     Status finalize(bool wait = true);
+    Status set_surface(const std::string& name, const Grid& grid, int band);
     Status save_state(const std::string& dir);
     Status load_state(const std::string& dir);
     ProgressInfo stats() const;

@@ -14,6 +14,8 @@ struct Grid::Impl {
     MemoryLocation loc = MemoryLocation::Host;         // what location() reports
     std::vector<BandDesc> descs;
     std::vector<detail::Buffer> bands;
+    bool has_geometry = false;
+    GridConfig geometry;
 };
 
 Grid::~Grid() = default;
@@ -122,6 +124,8 @@ std::unique_ptr<Grid> Grid::to(MemoryLocation dst) const {
     if (!impl_) return nullptr;
     auto g = create(cols(), rows(), impl_->descs, dst);
     if (!g || !g->copy_from(*this, nullptr).ok()) return nullptr;
+    g->impl_->has_geometry = impl_->has_geometry;
+    g->impl_->geometry = impl_->geometry;
     return g;
 }
 
@@ -129,8 +133,22 @@ std::unique_ptr<Grid> Grid::to_device_async(void* stream) const {
     if (!impl_) return nullptr;
     auto g = create(cols(), rows(), impl_->descs, MemoryLocation::Device);
     if (!g || !g->copy_from(*this, stream).ok()) return nullptr;
+    g->impl_->has_geometry = impl_->has_geometry;
+    g->impl_->geometry = impl_->geometry;
     return g;
 }
+
+Status Grid::set_geometry(const GridConfig& geometry) {
+    if (!impl_) return Status::error(StatusCode::InvalidArgument, "Grid not initialized");
+    if (geometry.width != cols() || geometry.height != rows())
+        return Status::error(StatusCode::InvalidArgument,
+                             "grid: a geometry of " + std::to_string(geometry.width) + " x " + std::to_string(geometry.height) +
+                             " cells does not describe a grid of " + std::to_string(cols()) + " x " + std::to_string(rows()));
+    impl_->geometry = geometry;
+    impl_->has_geometry = true;
+    return Status::success();
+}
+const GridConfig* Grid::geometry() const { return impl_ && impl_->has_geometry ? &impl_->geometry : nullptr; }
 
 std::vector<uint8_t> Grid::valid_mask(int band) const {
     std::vector<uint8_t> mask;

@@ -32,6 +32,11 @@ Status Pipeline::Host::init() {
         return Status::error(StatusCode::InvalidArgument, "pipeline: row-block shards run on the GPU engine only (one process per GPU)");
     if (cfg.result_location == MemoryLocation::Device)
         return Status::error(StatusCode::InvalidArgument, "pipeline: the CPU engine's result lives in host memory (result_location = Device asked)");
+    {
+        Status ok = detail::plan_surfaces(cfg);
+        if (!ok.ok()) return ok;
+        surfaces.resize(cfg.surface_channels.size());
+    }
     engine = std::make_unique<detail::HostEngine>(g, (int)cfg.cpu_threads);        // cpu_threads = 0: every core (pipeline.h:78)
     for (size_t ri = 0; ri < cfg.reductions.size(); ++ri) {
         const ReductionSpec& r = cfg.reductions[ri];
@@ -63,6 +68,14 @@ Status Pipeline::Host::init() {
     return Status::success();
 }
 
+// PipelineConfig::surface_channels: the band and its geometry into host memory the pipeline owns.
+Status Pipeline::Host::set_surface(const std::string& name, const Grid& grid, int band) {
+    int index = -1;
+    pcr_hip_grid geom{};
+    Status s = detail::check_surface(cfg, name, grid, band, &index, &geom);
+    return s.ok() ? detail::store_surface(grid, band, geom, MemoryLocation::Host, nullptr, &surfaces[(size_t)index]) : s;
+}
+
 Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     const size_t n = cloud_in.count();
     if (n == 0) return Status::success();                            // pipeline.cpp:284-287
@@ -74,6 +87,10 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         cloud = copy.get();
     }
     // the reference's checks and messages (pipeline_common.cpp; no device limits on the host)
+    if (!surfaces.empty()) {
+        Status ok = detail::validate_surfaces(cfg, *cloud, surfaces);
+        if (!ok.ok()) return ok;
+    }
     {
         Status ok = detail::validate_cloud(cfg, *cloud, 0, 0);
         if (!ok.ok()) return ok;
@@ -95,8 +112,23 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         px = rx.data();
         py = ry.data();
     }
+    // Surface channels: each gathered once, for all n points, at the (reprojected) coordinates -- the host loop of the C-ABI, so
+    // the bits are the HIP engine's -- and then found by name like a channel the cloud brought.
+    std::map<std::string, std::vector<float>> derived;
+    for (size_t k = 0; k < surfaces.size(); ++k) {
+        const SurfaceChannelConfig& sc = cfg.surface_channels[k];
+        std::vector<float>& out = derived[sc.name];
+        out.resize(n);
+        const detail::Surface& sf = surfaces[k];
+        Status ok = detail::sample_host(sf.geom, static_cast<const float*>(sf.band.data()), sf.geom.width, px, py,
+                                        sc.value_channel.empty() ? nullptr : cloud->channel_f32(sc.value_channel), n, sc.mode,
+                                        out.data(), engine->threads());
+        if (!ok.ok()) return ok;
+    }
     auto f32 = [&](const std::string& name) -> const float* {
         if (name.empty()) return nullptr;
+        const auto hit = derived.find(name);
+        if (hit != derived.end()) return hit->second.data();
         const ChannelDesc* d = cloud->channel(name);
         if (!d || d->dtype != DataType::Float32) return nullptr;     // -> GlyphSpec default
         return cloud->channel_f32(name);
@@ -110,7 +142,7 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     auto apply = [&](const FilterSpec& filter, std::vector<uint8_t>& keep) {
         keep.assign(n, 1);
         for (const auto& pr : filter.predicates) {
-            const float* ch = cloud->channel_f32(pr.channel_name);
+            const float* ch = f32(pr.channel_name);
             const int team = engine->threads();
 #pragma omp parallel for num_threads(team) schedule(static)
             for (int64_t i = 0; i < (int64_t)n; ++i) {
@@ -209,6 +241,7 @@ Status Pipeline::Host::finalize() {
         detail::append_terrain_bands(terrain, bands);
         result = Grid::create(g.width, g.height, bands, MemoryLocation::Host);
         if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
+        (void)result->set_geometry(detail::result_geometry(cfg));
     }
     for (size_t r = 0; r < outputs.size(); ++r)
         engine->finalize(groups[(size_t)outputs[r].group].planes, outputs[r].type, result->band_f32((int)r));

@@ -7,6 +7,7 @@
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
+#include "sample_grid.h"
 
 #include <chrono>
 #include <memory>
@@ -37,6 +38,7 @@ struct Pipeline::Host {
     std::vector<Group> groups;
     std::vector<Output> outputs;
     detail::FilterPlan filters;          // ReductionSpec::filter of every spec, planned at init
+    std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in host memory
     std::unique_ptr<Grid> result;
     bool finalized = false;
     ProgressCallback callback;
@@ -47,6 +49,7 @@ struct Pipeline::Host {
     Status init();
     Status ingest(const PointCloud& cloud);
     Status finalize();
+    Status set_surface(const std::string& name, const Grid& grid, int band);
     Status save_state(const std::string& dir);
     Status load_state(const std::string& dir);
     ProgressInfo stats() const;

@@ -20,6 +20,7 @@
 #include "las_io.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/point_cloud_io.h"
+#include "sample_grid.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -32,11 +33,13 @@ namespace {
 thread_local std::string g_create_error;
 
 // Every channel a configuration reads from its clouds: the reductions' value, weight, timestamp and glyph channels, their own
-// filters' and the pipeline filter's -- what a LAS file is decoded into (a Pipeline never looks at any other).
+// filters' and the pipeline filter's -- what a LAS file is decoded into (a Pipeline never looks at any other).  A surface
+// channel is derived, never read: its name is dropped and its value_channel added (`hag` alone decodes `z`).
 std::vector<std::string> named_channels(const PipelineConfig& c) {
     std::vector<std::string> out;
-    auto add = [&out](const std::string& name) {
-        if (!name.empty() && std::find(out.begin(), out.end(), name) == out.end()) out.push_back(name);
+    auto add = [&out, &c](const std::string& name) {
+        if (name.empty() || detail::surface_index(c, name) >= 0) return;
+        if (std::find(out.begin(), out.end(), name) == out.end()) out.push_back(name);
     };
     for (const auto& r : c.reductions) {
         add(r.value_channel);
@@ -50,6 +53,7 @@ std::vector<std::string> named_channels(const PipelineConfig& c) {
         for (const auto& p : r.filter.predicates) add(p.channel_name);
     }
     for (const auto& p : c.filter.predicates) add(p.channel_name);
+    for (const auto& sc : c.surface_channels) add(sc.value_channel);
     return out;
 }
 
@@ -89,8 +93,13 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         const Status ts = detail::plan_terrain(config, plan, &terrain);
         if (!ts.ok()) return fail_with(ts);
     }
+    {
+        const Status ss = detail::plan_surfaces(config);
+        if (!ss.ok()) return fail_with(ss);
+    }
     size_t budget = 0;
     if (Banded::needed(config, &budget)) {
+        if (!config.surface_channels.empty()) return fail_with(detail::surfaces_out_of_core_error());
         Status bs = Status::success();
         p->banded_ = Banded::create(config, p.get(), budget, &bs);
         if (!p->banded_) return fail_with(bs);
@@ -244,6 +253,11 @@ Status Pipeline::ingest_las_records(const std::string& path, const LasOptions& o
     }
     if (points_read) *points_read = total;
     return s;
+}
+Status Pipeline::set_surface(const std::string& name, const Grid& grid, int band) {
+    if (host_) return host_->set_surface(name, grid, band);
+    if (banded_) return Status::error(StatusCode::InvalidArgument, "pipeline: set_surface: '" + name + "' names no surface channel of this pipeline");
+    return impl_->set_surface(name, grid, band);
 }
 Status Pipeline::finalize() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(); }
 Status Pipeline::finalize_async() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(false); }

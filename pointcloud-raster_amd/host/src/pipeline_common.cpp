@@ -2,6 +2,7 @@
 #include "pipeline_common.h"
 
 #include "buffer.h"
+#include "sample_grid.h"
 
 #include "pcr/core/point_cloud.h"
 #include "pcr/core/reproject.h"
@@ -14,8 +15,11 @@ namespace pcr {
 namespace detail {
 
 Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t max_set, size_t max_predicates) {
+    // (a surface channel is a Float32 channel the pipeline derives itself: validate_surfaces has checked it)
+    auto derived = [&cfg](const std::string& name) { return surface_index(cfg, name) >= 0; };
     auto check_filter = [&](const FilterSpec& filter) -> Status {
         for (const auto& pr : filter.predicates) {
+            if (derived(pr.channel_name)) continue;
             if (!cloud.channel_data(pr.channel_name))
                 return Status::error(StatusCode::InvalidArgument, "filter_points: channel not found: " + pr.channel_name);
             const ChannelDesc* d = cloud.channel(pr.channel_name);
@@ -34,15 +38,17 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
     for (const auto& r : cfg.reductions)                       // ReductionSpec::filter: the same checks, the same messages
         if (!(fs = check_filter(r.filter)).ok()) return fs;
     for (const auto& r : cfg.reductions) {
-        if (!cloud.channel_data(r.value_channel))
-            return Status::error(StatusCode::InvalidArgument, "pipeline: value channel not found: " + r.value_channel);
-        const ChannelDesc* d = cloud.channel(r.value_channel);
-        if (!d || d->dtype != DataType::Float32)
-            return Status::error(StatusCode::InvalidArgument, "pipeline: value channel must be Float32");
+        if (!derived(r.value_channel)) {
+            if (!cloud.channel_data(r.value_channel))
+                return Status::error(StatusCode::InvalidArgument, "pipeline: value channel not found: " + r.value_channel);
+            const ChannelDesc* d = cloud.channel(r.value_channel);
+            if (!d || d->dtype != DataType::Float32)
+                return Status::error(StatusCode::InvalidArgument, "pipeline: value channel must be Float32");
+        }
         if (r.glyph.type != GlyphType::Point && !glyph_reduction_ok(r.type))
             return Status::error(StatusCode::NotImplemented,
                 "pipeline: glyph splatting only supports WeightedAverage, Average, Sum, or Count reduction types");
-        if (is_select(r.type)) {
+        if (is_select(r.type) && !derived(r.timestamp_channel)) {
             if (!cloud.channel_data(r.timestamp_channel))
                 return Status::error(StatusCode::InvalidArgument, "pipeline: timestamp channel not found: " + r.timestamp_channel);
             const ChannelDesc* t = cloud.channel(r.timestamp_channel);

@@ -6,6 +6,7 @@
 #include "pcr/core/ground_filter.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/core/reproject.h"
+#include "pcr/core/sample_grid.h"
 #include "pcr/core/terrain.h"
 #include "pcr/engine/pipeline.h"
 #include "pcr_hip.h"
@@ -241,6 +242,13 @@ void bind_core(py::module_& m) {
             if (!d) throw std::runtime_error("Failed to copy the grid (HIP out of memory or no usable GPU)");
             return d;
         }, py::arg("location"), "A copy of the grid in `location` (MemoryLocation.Device: in GPU memory)")
+        // extension: where the cells lie in the world (pcr.sample_grid, Pipeline.set_surface)
+        .def("set_geometry", [](Grid& g, const GridConfig& gc) { raise_if_error(g.set_geometry(gc)); }, py::arg("geometry"),
+             "Tags the grid with the GridConfig its cells are laid over (width and height must be cols() and rows())")
+        .def("geometry", [](const Grid& g) -> py::object {
+            const GridConfig* gc = g.geometry();
+            return gc ? py::cast(*gc) : py::none();
+        }, "The GridConfig the grid was tagged with (a pipeline tags result() of a whole grid), or None")
         .def("__repr__", [](const Grid& g) {
             return "Grid(cols=" + std::to_string(g.cols()) + ", rows=" + std::to_string(g.rows()) +
                    ", bands=" + std::to_string(g.num_bands()) + ")";
@@ -379,6 +387,21 @@ void bind_core(py::module_& m) {
         if (!rp.needed) return py::none();
         return py::cast(rp.dst_crs);
     });
+
+    // extension: a band sampled at the points of a cloud, where the cloud lives (a Device cloud: in HBM)
+    py::enum_<SampleMode>(m, "SampleMode").value("Nearest", SampleMode::Nearest).value("Bilinear", SampleMode::Bilinear);
+    m.def("sample_grid", [](PointCloud& cloud, const Grid& grid, int band, const std::string& channel, py::object value_channel,
+                            SampleMode mode) {
+        const std::string value = value_channel.is_none() ? std::string() : value_channel.cast<std::string>();
+        Status s;
+        {
+            py::gil_scoped_release nogil;
+            s = sample_grid(cloud, grid, band, channel, value, mode);
+        }
+        raise_if_error(s);
+    }, py::arg("cloud"), py::arg("grid"), py::arg("band") = 0, py::arg("channel") = "sample", py::arg("value_channel") = py::none(),
+       py::arg("mode") = SampleMode::Bilinear,
+       "Adds (or overwrites) the Float32 channel `channel`: the band's sample at every point, or value_channel minus it");
 
     // extension: the terrain bands of a grid's band, where the grid lives (a Device grid: in HBM)
     m.def("terrain", [](const Grid& grid, int band, const std::vector<TerrainProduct>& products, py::object spec, double cell_size_x,

@@ -95,6 +95,20 @@ void bind_engine(py::module_& m) {
         .def_readwrite("product", &TerrainBandConfig::product)
         .def_readwrite("band_name", &TerrainBandConfig::band_name);
 
+    py::class_<SurfaceChannelConfig>(m, "SurfaceChannelConfig")
+        .def(py::init<>())
+        .def(py::init<const SurfaceChannelConfig&>())
+        .def(py::init([](const std::string& name, const std::string& value_channel, SampleMode mode) {
+            SurfaceChannelConfig c;
+            c.name = name;
+            c.value_channel = value_channel;
+            c.mode = mode;
+            return c;
+        }), py::arg("name"), py::arg("value_channel") = "", py::arg("mode") = SampleMode::Bilinear)
+        .def_readwrite("name", &SurfaceChannelConfig::name)
+        .def_readwrite("value_channel", &SurfaceChannelConfig::value_channel)
+        .def_readwrite("mode", &SurfaceChannelConfig::mode);
+
     py::class_<PipelineConfig>(m, "PipelineConfig")
         .def(py::init<>())
         .def_readwrite("grid", &PipelineConfig::grid)
@@ -127,7 +141,10 @@ void bind_engine(py::module_& m) {
         .def_readwrite("fill_nodata_radius", &PipelineConfig::fill_nodata_radius)
         .def_readwrite("ground", &PipelineConfig::ground)
         .def_readwrite("terrain", &PipelineConfig::terrain)
-        .def_readwrite("las_gps_time_origin", &PipelineConfig::las_gps_time_origin);
+        .def_readwrite("las_gps_time_origin", &PipelineConfig::las_gps_time_origin)
+        .def_readwrite("surface_channels", &PipelineConfig::surface_channels,
+                       "Per-point Float32 channels derived at every ingest from a band given with Pipeline.set_surface (assign a "
+                       "list of SurfaceChannelConfig): usable wherever a channel is named");
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
         .def(py::init<>())
@@ -156,6 +173,10 @@ void bind_engine(py::module_& m) {
             return n;
         }, py::arg("path"), py::arg("chunk_points") = size_t(4) << 20,
              "stream a PCRP / CSV / LAS file through page-locked double buffers; returns the number of points read")
+        .def("set_surface", [](Pipeline& p, const std::string& name, const Grid& grid, int band) {
+            raise_if_error(p.set_surface(name, grid, band));
+        }, py::arg("name"), py::arg("grid"), py::arg("band") = 0,
+             "Gives the surface channel `name` its surface: band `band` of a grid that carries its geometry, copied into the pipeline")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },
              "Device-resident result: the finalize kernels are only enqueued on the pipeline's stream (complete after synchronize()); "

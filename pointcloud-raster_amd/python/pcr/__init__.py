@@ -76,6 +76,7 @@ from ._pcr import (  # noqa: E402,F401
     read_las,
     GroundFilterSpec, GroundFilterConfig, ground_filter, ground_filter_levels,
     TerrainProduct, TerrainSpec, TerrainBandConfig, terrain, terrain_light,
+    SampleMode, SurfaceChannelConfig, sample_grid,
 )
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
@@ -177,4 +178,5 @@ __all__ = [
     "read_las",
     "GroundFilterSpec", "GroundFilterConfig", "ground_filter", "ground_filter_levels",
     "TerrainProduct", "TerrainSpec", "TerrainBandConfig", "terrain", "terrain_light",
+    "SampleMode", "SurfaceChannelConfig", "sample_grid",
 ]

@@ -87,6 +87,8 @@ class LasLayout(C.Structure):
 LAS_CHANNELS = ("z", "intensity", "return_number", "number_of_returns", "classification", "withheld", "overlap",
                 "scan_angle", "user_data", "point_source_id", "gps_time", "red", "green", "blue", "nir")
 LAS_RECORDS_PER_LANE = 4
+SAMPLE_NEAREST, SAMPLE_BILINEAR = 0, 1
+SAMPLE_POINTS_PER_LANE = 4
 
 
 SYMBOLS = {
@@ -190,6 +192,8 @@ SYMBOLS = {
                         C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, _VP],
     "pcr_hip_las_decode": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), _VP],
     "pcr_hip_las_decode_host": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), C.c_int],
+    "pcr_hip_sample_grid": [C.POINTER(Grid), _VP, _I64, _VP, _VP, _VP, _U64, C.c_int, _VP, _VP],
+    "pcr_hip_sample_grid_host": [C.POINTER(Grid), _VP, _I64, _VP, _VP, _VP, _U64, C.c_int, _VP],
 }
 
 _lib = None
