@@ -679,6 +679,45 @@ int pcr_hip_sample_grid(const pcr_hip_grid* surface, const float* d_band, int64_
 int pcr_hip_sample_grid_host(const pcr_hip_grid* surface, const float* h_band, int64_t band_stride, const double* h_x,
                              const double* h_y, const float* h_value, uint64_t n, int mode, float* h_out);
 
+/* ---- per-cell histograms: a mergeable piece of state beside the reductions (PipelineConfig::histograms), from which
+ *      percentile bands (p95 canopy height, the median) and strata counts come.  No reference counterpart.  The fold is
+ *      integer addition: the same bits on both engines and both device paths, for any order, chunking or number of
+ *      scatters, with no tolerance anywhere.  The arithmetic is written once, in csrc/histogram.hpp, which the kernels,
+ *      the host twin and the host engine compile with contraction off.
+ *        accepted   a point is accepted when it is routed to a cell by the rule of the Point glyph (inclusive bounds, the
+ *                   floor of the true binary64 quotient, clamp; the owned rows of the engine's grid), is kept by the point
+ *                   mask (pcr_hip_engine_set_point_mask), and its value is not NaN.
+ *        bin        binary64: the caller computes inv_w = (double)bins / ((double)hi - (double)lo) once;
+ *                   t = ((double)v - lo) * inv_w; b = 0 if t < 0, bins - 1 if t >= bins, else (int)t.  Values outside
+ *                   [lo, hi) and +-Inf are clamped into the end bins: counted, not dropped.  One subtraction and one
+ *                   multiplication: nothing can contract.
+ *        state      each accepted point adds 1 to count[b][cell], uint32: a cube of `bins` planes in the state window's
+ *                   layout ([bins][state_rows * width]), which the caller zeroes once.  A counter wraps at 2^32: a limit
+ *                   that is documented, not checked.
+ *        percentile for q, per cell of the owned rows, with N = sum of count[b]: NaN (0x7FC00000) where N == 0 -- the
+ *                   touched-tile flags play no part.  Else k = min(max((int64)ceil((double)q * (double)N), 1), N), b the
+ *                   smallest bin whose cumulative count C_b >= k, and
+ *                   band = (float)(lo + w * ((double)b + ((double)(k - C_{b-1}) - 0.5) / (double)count[b])),
+ *                   w = ((double)hi - (double)lo) / bins computed by the caller once, every operation rounded on its own.
+ *                   One point in a bin gives the bin's centre; the band is monotone in q.
+ *      scatter_histogram honours pcr_hip_engine_set_point_mask and pcr_hip_engine_set_path: 1 direct -- one 32-bit global
+ *      atomic add without return per accepted point; 2 binned -- the Point front end on 8-byte records whose value slot
+ *      carries the bin, folded in LDS tiles of 128 x h cells x S bin planes, ceil(bins / S) tile launches over records
+ *      sorted once; 0 the binned path where it applies, else the direct one.  It sets the touched flags of the tiles its
+ *      points are routed to and reports through pcr_hip_engine_stats like pcr_hip_scatter_point.
+ *      histogram_percentiles writes n_q bands (own rows x width floats each, d_outs[j] for q[j]; q and d_outs are HOST
+ *      arrays) in one launch on s, reading the cube at most twice.  _host: the same lines on host arrays, one thread.
+ *      Argument errors -- a null pointer, bins outside 1..256, n_q outside 1..16, q outside [0, 1], non-finite lo, w or
+ *      inv_w -- are reported before any HIP call. */
+#define PCR_HIP_HISTOGRAM_MAX_BINS 256
+#define PCR_HIP_HISTOGRAM_MAX_PERCENTILES 16
+int pcr_hip_scatter_histogram(pcr_hip_engine* e, uint32_t* d_counts, int bins, double lo, double inv_w, const double* d_x,
+                              const double* d_y, const float* d_value, uint64_t n);
+int pcr_hip_histogram_percentiles(const pcr_hip_grid* g, const uint32_t* d_counts, int bins, double lo, double w, int n_q,
+                                  const float* q, float* const* d_outs, pcr_hip_stream s);
+int pcr_hip_histogram_percentiles_host(const pcr_hip_grid* g, const uint32_t* h_counts, int bins, double lo, double w, int n_q,
+                                       const float* q, float* const* h_outs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,10 @@ int pcr_hip_engine_create(pcr_hip_engine** out, const pcr_hip_grid* g, size_t sc
         if (v >= 1 && v < kMaxBins) e->max_bins = v;
     }
     if (const char* dbg = std::getenv("PCR_HIP_DEBUG_TWO_LEVEL")) e->two_level = std::atoi(dbg) != 0;
+    if (const char* dbg = std::getenv("PCR_HIP_DEBUG_HIST_SLAB")) {
+        const int v = std::atoi(dbg);
+        if (v == 8 || v == 16 || v == 32) e->hist_slab = v;
+    }
     hipError_t err = hipGetDevice(&e->device);
     hipDeviceProp_t prop;
     if (err == hipSuccess) err = hipGetDeviceProperties(&prop, e->device);
@@ -268,6 +272,7 @@ int pcr_hip_engine_destroy(pcr_hip_engine* e) {
     if (e->d_touched) (void)hipFree(e->d_touched);
     if (e->d_counters) (void)hipFree(e->d_counters);
     if (e->d_bin_counts) (void)hipFree(e->d_bin_counts);
+    if (e->d_hist_words) (void)hipFree(e->d_hist_words);
     delete e;              // the scratch arena is device-wide and outlives engines
     return PCR_HIP_OK;
 }
@@ -470,6 +475,37 @@ int pcr_hip_scatter_select(pcr_hip_engine* e, uint64_t* d_packed, const double* 
     rc = binned_select(e, packed, d_x, d_y, d_value, d_key, n);
     e->publish_counters = false;
     e->planes_fresh = 0;                                  // the hint covers one scatter
+    release_scratch(e);
+    return rc;
+}
+
+int pcr_hip_scatter_histogram(pcr_hip_engine* e, uint32_t* d_counts, int bins, double lo, double inv_w, const double* d_x,
+                              const double* d_y, const float* d_value, uint64_t n) {
+    PCR_REQUIRE(e, "scatter_histogram: null engine");
+    e->fused_outs.n = 0;                                  // (a pending finalize-with-scatter hint does not apply here)
+    e->fused_done = nullptr;
+    e->fused_taken = false;
+    e->defer_planes = e->deferred_taken = 0;
+    e->planes_fresh = 0;                                  // (the cube is zero at create and only ever added to)
+    PCR_REQUIRE(d_counts, "scatter_histogram: null cube");
+    PCR_REQUIRE(bins >= 1 && bins <= PCR_HIP_HISTOGRAM_MAX_BINS, "scatter_histogram: bins must be between 1 and 256");
+    PCR_REQUIRE(std::isfinite(lo) && std::isfinite(inv_w) && inv_w > 0.0, "scatter_histogram: lo and inv_w must be finite, inv_w positive");
+    if (n == 0) return PCR_HIP_OK;                       // empty cloud is a no-op, as for pcr_hip_scatter_point
+    PCR_REQUIRE(n < ((uint64_t)1 << 40), "scatter_histogram: too many points in one call");
+    PCR_REQUIRE(d_x && d_y && d_value, "scatter_histogram: null point array");
+    DeviceGuard dev(e->device);
+    int rc = begin_scatter(e, n);
+    if (rc) return rc;
+    const bool can_bin = binned_hist_supported(e);
+    if (e->forced_path == 2 && !can_bin)
+        return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_histogram: binned path forced but not applicable to this grid");
+    if (e->forced_path == 1 || !can_bin) {
+        if ((rc = zero_counters(e)) != PCR_HIP_OK) return rc;
+        return direct_hist(e, d_counts, bins, lo, inv_w, d_x, d_y, d_value, n);
+    }
+    if ((rc = begin_published(e)) != PCR_HIP_OK) return rc;
+    rc = binned_hist(e, d_counts, bins, lo, inv_w, d_x, d_y, d_value, n);
+    e->publish_counters = false;
     release_scratch(e);
     return rc;
 }

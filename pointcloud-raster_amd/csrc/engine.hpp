@@ -61,6 +61,13 @@ struct pcr_hip_engine {
     std::vector<Pending> pending;
     std::map<std::string, std::pair<uint32_t, double>> kernel_ms;
 
+    // pcr_hip_scatter_histogram, binned path (histogram.hip): the points' bin words, grow-only, the engine's own (the scratch
+    // arena is carved anew by every pass of a sweep), and S, the bin planes an LDS tile holds (PCR_HIP_DEBUG_HIST_SLAB: 8, 16
+    // or 32, for the measurement that chose the default)
+    uint32_t* d_hist_words = nullptr;
+    size_t hist_words_cap = 0;                 // words
+    int hist_slab = 16;                        // chosen by measurement: profiles/histogram.md
+
     // scratch of the binned / moment paths: borrowed per scatter from the device-wide arena (engine.hip)
     char* d_scratch = nullptr;
     size_t scratch_cap = 0;
@@ -214,6 +221,14 @@ int direct_select(pcr_hip_engine* e, unsigned long long* packed, const double* x
 bool binned_select_supported(const pcr_hip_engine* e);
 int binned_select(pcr_hip_engine* e, unsigned long long* packed, const double* x, const double* y, const float* v,
                   const float* key, uint64_t n);
+
+// Per-cell histograms (pcr_hip_scatter_histogram): a cube count[bins][state window] of uint32, histogram.hip.  direct: one
+// global atomic add per accepted point; binned: VALUE records {local cell, bin} through the Point front end (sweep_tiles).
+int direct_hist(pcr_hip_engine* e, uint32_t* counts, int bins, double lo, double inv_w, const double* x, const double* y,
+                const float* v, uint64_t n);
+bool binned_hist_supported(const pcr_hip_engine* e);
+int binned_hist(pcr_hip_engine* e, uint32_t* counts, int bins, double lo, double inv_w, const double* x, const double* y,
+                const float* v, uint64_t n);
 
 // Gaussian cell tiles on 16-byte value records (default-sigma, unrotated, r <= 3), scatter_cells.hip
 bool cells_gauss_supported(const pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask);

@@ -78,6 +78,31 @@ struct SurfaceChannelConfig {
     SampleMode mode = SampleMode::Bilinear;
 };
 
+/// One entry of PipelineConfig::histograms: a per-cell histogram of one channel, accumulated at ingest beside the reductions,
+/// and the percentile bands finalize() walks out of it.  The contract (include/pcr_hip.h, "per-cell histograms"):
+///   accepted   a point is accepted when it is routed to a cell by the rule of the Point glyph (inclusive bounds, true-division
+///              routing, after reprojection and surface channels), is kept by PipelineConfig::filter AND by `filter`, and its
+///              value is not NaN.
+///   bin        binary64: inv_w = (double)bins / ((double)hi - (double)lo) is computed once; t = ((double)v - (double)lo) * inv_w;
+///              b = 0 if t < 0, bins - 1 if t >= bins, else (int)t.  Out-of-range values and +-Inf are clamped into the end
+///              bins: counted, not dropped.
+///   state      each accepted point adds 1 to count[b][cell], uint32: a cube of bin planes in the state window's layout, zero
+///              at create.  A counter wraps at 2^32 (documented, not checked).
+///   band for q per cell, with N = sum of count[b]: NaN where N == 0 (touched-tile flags play no part); else
+///              k = min(max((int64)ceil((double)q * (double)N), 1), N), b the smallest bin with cumulative count C_b >= k, and
+///              band = (float)((double)lo + w * ((double)b + ((double)(k - C_{b-1}) - 0.5) / (double)count[b])) with
+///              w = ((double)hi - (double)lo) / bins computed once, every operation rounded on its own.  A single point in a
+///              bin gives the bin's centre; the band is monotone in q.
+/// Both engines and both device paths give the same bits for any order, chunking or number of ingests.
+struct HistogramConfig {
+    std::string value_channel;           // any Float32 channel, a surface channel ("hag") included
+    float lo = 0.f, hi = 64.f;           // bin b covers [lo + b*w, lo + (b+1)*w), w = (hi-lo)/bins
+    int bins = 32;                       // 1..256
+    FilterSpec filter;                   // like ReductionSpec::filter: AND PipelineConfig::filter
+    std::vector<float> percentiles;      // each in [0,1]; one band per entry, in order; may be empty
+    std::vector<std::string> band_names; // default "{value_channel}_p{round(q*100)}", e.g. "hag_p95"
+};
+
 struct PipelineConfig {
     GridConfig grid;
     std::vector<ReductionSpec> reductions;
@@ -164,6 +189,19 @@ struct PipelineConfig {
     // than 8 entries, a row-block shard and a pipeline that has to run out of core.  Empty: nothing is allocated, launched or
     // validated differently.
     std::vector<SurfaceChannelConfig> surface_channels;
+    // Per-cell histograms (HistogramConfig): every ingest also counts each entry's channel into its cube -- on the HIP engine
+    // in HBM, bins * cells * 4 bytes that count towards gpu_memory_budget -- and finalize() appends its percentile bands BEHIND
+    // the reductions' bands and AHEAD of the DTM, hag and terrain bands: with fill_nodata_radius they are filled like a Max
+    // band, ground.source_band, ground.top_band and terrain[].source_band may name them, result(), the GeoTIFF and its
+    // overview levels carry them like any other band.  The cube persists like the plane state: finalize() may be called again
+    // after more ingests; Pipeline::histogram_counts reads it at any time.  Each filter joins the plan of the ReductionSpec
+    // filters and counts against its limits (8 distinct filters, 16 predicates per conjunction, 32 in all).  create() refuses
+    // more than 4 entries, bins outside 1..256, non-finite bounds or lo >= hi, more than 16 percentiles, a percentile outside
+    // [0, 1] or NaN, an empty value_channel, band_names longer than percentiles, a band name that collides with any other
+    // leaving band, a row-block shard and a pipeline that has to run out of core; save_state, load_state and resume answer
+    // NotImplemented while the list is non-empty (a checkpoint that silently lost the cube would be a wrong result later).
+    // Empty: nothing is allocated, launched or validated differently.
+    std::vector<HistogramConfig> histograms;
 };
 
 struct ProgressInfo {
@@ -201,6 +239,12 @@ public:
     /// stream first.  InvalidArgument for an unknown name, a grid without geometry, a band outside the grid or not Float32;
     /// CrsError when the surface's CRS and the grid's are both identified and differ.
     Status set_surface(const std::string& name, const Grid& grid, int band = 0);
+    /// Extension: the cube of PipelineConfig::histograms[i] as a host copy, [bins][rows][width] counters, after synchronising
+    /// with the pipeline's stream.  Valid after any ingest (all zero before the first); finalize() is not needed.  Height strata
+    /// and canopy cover above any threshold are sums of its bin planes.  InvalidArgument for an index outside the list.
+    Status histogram_counts(int i, std::vector<uint32_t>* out) const;
+    /// ... and its shape: bins planes of rows x width cells.
+    Status histogram_shape(int i, int* bins, int* rows, int* width) const;
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
     /// the finalize kernels are only ENQUEUED on the pipeline's stream -- result() is valid at once, its bands are complete

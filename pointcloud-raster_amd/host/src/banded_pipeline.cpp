@@ -98,6 +98,8 @@ size_t Pipeline::Banded::bytes_per_row(const PipelineConfig& c) {
     size_t planes = 0;
     for (uint32_t m : g.masks)
         for (int p = 0; p < 4; ++p) planes += (m & kPlaneBits[p]) ? 1 : 0;
+    // (PipelineConfig::histograms: a cube's bin planes and its percentile bands count like any other plane and band)
+    for (const auto& h : c.histograms) planes += (size_t)std::max(h.bins, 0) + h.percentiles.size();
     return (size_t)c.grid.width * 4 * (planes + c.reductions.size());
 }
 

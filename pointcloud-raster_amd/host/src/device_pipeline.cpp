@@ -25,6 +25,7 @@ using detail::same_glyph;
 Pipeline::Impl::~Impl() {
     if (engine) pcr_hip_engine_destroy(engine);
     surfaces.clear();
+    cubes.clear();
     groups.clear();
     bands.clear();
     band_buffers.clear();
@@ -42,6 +43,7 @@ Status Pipeline::Impl::init() {
         return Status::error(StatusCode::InvalidArgument, "pipeline: tile dimensions must be positive");
     {
         Status ok = detail::check_reduction_specs(cfg.reductions);
+        if (ok.ok()) ok = detail::check_histograms(cfg);
         if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
         if (!ok.ok()) return ok;
     }
@@ -139,6 +141,18 @@ Status Pipeline::Impl::init() {
             ? r.value_channel + "_" + std::to_string(static_cast<int>(r.type)) : r.output_band_name;
         outputs.push_back(o);
     }
+    // PipelineConfig::histograms: one output per percentile band, behind the reductions' and ahead of the DTM, hag and terrain bands
+    hist = detail::plan_histograms(cfg, filters);
+    for (size_t h = 0; h < hist.entries.size(); ++h)
+        for (size_t j = 0; j < hist.entries[h].q.size(); ++j) {
+            Output o;
+            o.group = -1;
+            o.type = ReductionType::Max;
+            o.band_name = detail::histogram_band_name(cfg.histograms[h], j);
+            o.hist = (int)h;
+            o.q = (int)j;
+            outputs.push_back(o);
+        }
     if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
     if (!(s = detail::plan_terrain(cfg, ground, &terrain)).ok()) return s;
     if (!(s = detail::plan_surfaces(cfg)).ok()) return s;
@@ -196,6 +210,12 @@ Status Pipeline::Impl::init() {
         gr.view.d_max = static_cast<float*>(gr.planes[2].data());
         gr.view.d_min = static_cast<float*>(gr.planes[3].data());
     }
+    cubes.resize(hist.entries.size());
+    for (size_t h = 0; h < cubes.size(); ++h) {
+        const size_t bytes = hist.entries[h].cube_cells((size_t)std::max<int64_t>(cells, 1)) * sizeof(uint32_t);
+        if (!(s = cubes[h].allocate(bytes, MemoryLocation::Device)).ok()) return s;
+        if (!(s = detail::hip_status(pcr_hip_memset(cubes[h].data(), 0, bytes, stream))).ok()) return s;
+    }
     if (!outputs.empty() && !(s = allocate_result()).ok()) return s;
     if (!(s = d_bands_done.allocate(std::max<size_t>(groups.size(), 1) * sizeof(uint32_t), MemoryLocation::HostPinned)).ok()) return s;
     std::memset(d_bands_done.data(), 0, d_bands_done.bytes());
@@ -222,6 +242,34 @@ Status Pipeline::Impl::band_leaves(size_t b, bool* enqueued) {
         s = detail::hip_status(pcr_hip_memcpy_d2h(result->band_f32((int)b), lb.out, (size_t)rows * W * sizeof(float), stream));
     }
     return s;
+}
+// Behind the finalize kernels of every group, on the pipeline's stream, and ahead of the ground filter, which may read a
+// percentile band: one walk per histogram writes all of its raw bands, which then leave like a Max band (filled when asked).
+Status Pipeline::Impl::finalize_histograms(bool* enqueued) {
+    size_t r = cfg.reductions.size();
+    for (size_t h = 0; h < hist.entries.size(); ++h) {
+        const detail::HistogramEntry& e = hist.entries[h];
+        if (e.q.empty()) continue;
+        std::vector<float*> dsts;
+        for (size_t j = 0; j < e.q.size(); ++j) dsts.push_back(bands[r + j].raw);
+        *enqueued = true;
+        Status s = detail::hip_status(pcr_hip_histogram_percentiles(&hg, static_cast<const uint32_t*>(cubes[h].data()), e.bins, e.lo, e.w,
+                                                                    (int)e.q.size(), e.q.data(), dsts.data(), stream));
+        for (size_t j = 0; j < e.q.size() && s.ok(); ++j) s = band_leaves(r + j, enqueued);
+        if (!s.ok()) return s;
+        r += e.q.size();
+    }
+    return Status::success();
+}
+// The cube of histogram i as a host copy, behind everything on the pipeline's stream.
+Status Pipeline::Impl::histogram_counts(int i, std::vector<uint32_t>* out) {
+    if (i < 0 || (size_t)i >= cubes.size() || !out)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: histogram_counts: no histogram " + std::to_string(i));
+    DeviceScope dev(cfg.cuda_device_id);
+    out->assign(hist.entries[(size_t)i].cube_cells((size_t)hg.state_rows * hg.width), 0u);
+    if (out->empty()) return Status::success();
+    Status s = detail::hip_status(pcr_hip_memcpy_d2h(out->data(), cubes[(size_t)i].data(), out->size() * sizeof(uint32_t), stream));
+    return s.ok() ? detail::hip_status(pcr_hip_stream_synchronize(stream)) : s;
 }
 // Behind the finalize kernels and the fills of every group, on the pipeline's stream: the filter on the RAW source band, the
 // DTM leaves (filled like a Min band), hag from the top band and the DTM as they leave the pipeline, hag leaves.
@@ -450,7 +498,8 @@ std::vector<Pipeline::PlaneView> Pipeline::Impl::state_planes() {
 
 std::vector<int> Pipeline::Impl::reduction_groups() const {
     std::vector<int> out;
-    for (const auto& o : outputs) out.push_back(o.group);
+    for (const auto& o : outputs)
+        if (o.group >= 0) out.push_back(o.group);
     return out;
 }
 
@@ -884,6 +933,17 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
         scatter_done(gr, offered, s.ok());
         if (!s.ok()) return s;
     }
+    // PipelineConfig::histograms: each cube counts the points its class keeps.  The touched flags it sets are among those the
+    // scatters (or the touch pass) above set already: no band a scatter stored goes stale, no plane is read or written.
+    for (size_t h = 0; h < hist.entries.size(); ++h) {
+        const detail::HistogramEntry& e = hist.entries[h];
+        const float* dv = nullptr;
+        if (!(s = f32_channel(e.value_channel, &dv)).ok()) return s;
+        pcr_hip_engine_set_point_mask(engine, filters.any() ? class_mask[(size_t)e.cls] : active_mask);
+        s = detail::hip_status(pcr_hip_scatter_histogram(engine, static_cast<uint32_t*>(cubes[h].data()), e.bins, e.lo, e.inv_w,
+                                                         static_cast<const double*>(dx), static_cast<const double*>(dy), dv, n));
+        if (!s.ok()) return s;
+    }
     // host arrays may be reused by the caller as soon as we return (ingest_async: page-locked arrays are
     // read by the DMA engine later, the caller keeps them alive until synchronize())
     if (loc != MemoryLocation::Device && (wait || loc != MemoryLocation::HostPinned)) {
@@ -1015,6 +1075,7 @@ Status Pipeline::Impl::finalize(bool wait) {
         for (size_t r : bands_of)            // behind the band's finalize kernel (or the scatter that stored it)
             if (!(s = band_leaves(r, &enqueued)).ok()) return s;
     }
+    if (!(s = finalize_histograms(&enqueued)).ok()) return s;
     if (!(s = finalize_ground(&enqueued)).ok()) return s;
     if (!(s = finalize_terrain(&enqueued)).ok()) return s;
     // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
@@ -1153,11 +1214,13 @@ Status Pipeline::Impl::import_window(const std::vector<std::vector<float>>& plan
 
 std::vector<detail::StateOutput> Pipeline::Impl::state_outputs() const {
     std::vector<detail::StateOutput> o;
-    for (const auto& out : outputs) o.push_back({out.group, out.type});
+    for (const auto& out : outputs)
+        if (out.group >= 0) o.push_back({out.group, out.type});
     return o;
 }
 
 Status Pipeline::Impl::save_state(const std::string& dir_in) {
+    if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     std::string dir;
     Status s = checkpoint_dir(dir_in, &dir, true);
     if (!s.ok()) return s;
@@ -1168,6 +1231,7 @@ Status Pipeline::Impl::save_state(const std::string& dir_in) {
 }
 
 Status Pipeline::Impl::load_state(const std::string& dir_in) {
+    if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     std::string dir;
     Status s = checkpoint_dir(dir_in, &dir, false);
     if (!s.ok()) return s;

@@ -5,6 +5,7 @@
 
 #include "buffer.h"
 #include "ground_filter.h"
+#include "histogram.h"
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
@@ -50,10 +51,12 @@ struct Pipeline::Impl {
                                          // pipeline's alone to write: result() hands out a const Grid*, result_band_device() a
                                          // const float*.
     };
-    struct Output {                      // one ReductionSpec -> one band
-        int group = 0;
+    struct Output {                      // one band finalize makes from the state: a ReductionSpec's, or a percentile band
+        int group = 0;                   // -1: a percentile band of histogram `hist` (no group reads or writes it; its type is
+                                         // Max, so that the table fills it like a Max band)
         ReductionType type = ReductionType::Sum;
         std::string band_name;
+        int hist = -1, q = 0;            // the histogram and which of its percentiles
     };
 
     // The pipeline's device is made current for the duration of a call that launches or allocates, whatever the
@@ -96,6 +99,9 @@ struct Pipeline::Impl {
     detail::Buffer d_ground_work;            // its workspace, allocated by the first finalize, grow-only
     detail::TerrainPlan terrain;             // PipelineConfig::terrain, planned at init
     detail::FilterPlan filters;              // ReductionSpec::filter of every spec, planned at init
+    detail::HistogramPlan hist;              // PipelineConfig::histograms, planned at init
+    std::vector<detail::Buffer> cubes;       // entry by entry: count[bins][state_rows * width] in HBM, zeroed at create and only
+                                             // ever added to: no part in the plane-state rules
     std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in HBM (set_surface)
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
@@ -157,6 +163,8 @@ struct Pipeline::Impl {
     int own_rows() const { return hg.own_row1 - hg.own_row0; }
     static int own_plane(ReductionType t);
     Status band_leaves(size_t b, bool* enqueued);
+    Status finalize_histograms(bool* enqueued);
+    Status histogram_counts(int i, std::vector<uint32_t>* out);
     Status finalize_ground(bool* enqueued);
     Status finalize_terrain(bool* enqueued);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;

@@ -131,8 +131,7 @@ inline Status plan_ground(const PipelineConfig& cfg, GroundPlan* plan) {
     auto refuse = [](const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: " + msg); };
     if (cfg.shard_row_begin >= 0 || cfg.shard_row_end >= 0)
         return refuse("ground filter needs the whole grid; filter the gathered grid with ground_filter");
-    std::vector<std::string> names;
-    for (const auto& r : cfg.reductions) names.push_back(default_band_name(r));
+    std::vector<std::string> names = output_band_names(cfg);
     auto index_of = [&names](const std::string& n) {
         const auto it = std::find(names.begin(), names.end(), n);
         return it == names.end() ? -1 : (int)(it - names.begin());

@@ -1,6 +1,7 @@
 // host_engine.cpp -- see host_engine.h.  Arithmetic after the reference's CPU path, cited at each step; structure ours.
 #include "host_engine.h"
 
+#include "../../csrc/histogram.hpp"
 #include "pipeline_common.h"
 
 #include <algorithm>
@@ -275,6 +276,26 @@ void HostEngine::scatter_select(HostPlanes& p, const float* v, const float* key,
             const size_t cell = (size_t)row_[i] * W_ + (size_t)col_[i];
             const uint64_t w = select_word(key[i], v[i]);
             if (w > select_word_of_state(val[cell], ts[cell])) select_state_of_word(w, &val[cell], &ts[cell]);
+        }
+    }
+}
+
+void HostEngine::scatter_histogram(uint32_t* counts, int bins, double lo, double inv_w, const float* v, const uint8_t* keep) {
+    if (n_ == 0 || !v || !counts) return;
+    std::vector<uint32_t> list;
+    std::vector<size_t> first;
+    build_lists(list, first, [&](size_t i, Span& sp) {
+        if (row_[i] < 0 || (keep && !keep[i]) || v[i] != v[i]) return false;
+        sp.lo = sp.hi = row_[i];
+        return true;
+    });
+    const size_t plane_cells = (size_t)W_ * H_;
+#pragma omp parallel for num_threads(threads_) schedule(dynamic, 1)
+    for (int s = 0; s < nstripes_; ++s) {
+        for (size_t k = first[(size_t)s]; k < first[(size_t)s + 1]; ++k) {
+            const uint32_t i = list[k];
+            const uint32_t b = pcrhip::hist::bin_of(v[i], lo, inv_w, bins);
+            counts[(size_t)b * plane_cells + (size_t)row_[i] * W_ + (size_t)col_[i]] += 1u;
         }
     }
 }

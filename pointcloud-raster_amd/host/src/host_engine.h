@@ -60,6 +60,10 @@ public:
     /// MostRecent: per stripe, the maximum word(key, v) of the accepted points of every cell (include/pcr_hip.h); the same
     /// bits as the HIP engine whatever the thread count -- the fold is commutative and idempotent.
     void scatter_select(HostPlanes& p, const float* v, const float* key, const uint8_t* keep = nullptr);
+    /// PipelineConfig::histograms: count[bin][cell] += 1 for every routed point the keep mask keeps whose value is not NaN, the
+    /// bin by csrc/histogram.hpp (include/pcr_hip.h, "per-cell histograms").  counts: [bins][height * width].  Stripe-owned like
+    /// the other folds, no atomics; integer addition, so the bits are the same at any thread count.
+    void scatter_histogram(uint32_t* counts, int bins, double lo, double inv_w, const float* v, const uint8_t* keep = nullptr);
     /// A select group's planes as a checkpoint left them -> the canonical form a fold leaves (a NaN or <= -FLT_MAX timestamp
     /// means empty: {NaN, -FLT_MAX}; a -0.0 timestamp is +0.0).
     void normalize_select(HostPlanes& p) const;

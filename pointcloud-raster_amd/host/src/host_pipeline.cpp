@@ -25,6 +25,7 @@ Status Pipeline::Host::init() {
         return Status::error(StatusCode::InvalidArgument, "pipeline: tile dimensions must be positive");
     {
         Status ok = detail::check_reduction_specs(cfg.reductions);
+        if (ok.ok()) ok = detail::check_histograms(cfg);
         if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
         if (!ok.ok()) return ok;
     }
@@ -62,6 +63,20 @@ Status Pipeline::Host::init() {
         o.type = r.type;
         o.band_name = detail::default_band_name(r);
         outputs.push_back(o);
+    }
+    // PipelineConfig::histograms: the cubes, and one output per percentile band behind the reductions'
+    hist = detail::plan_histograms(cfg, filters);
+    for (size_t h = 0; h < hist.entries.size(); ++h) {
+        cubes.emplace_back(hist.entries[h].cube_cells((size_t)g.width * g.height), 0u);
+        for (size_t j = 0; j < hist.entries[h].q.size(); ++j) {
+            Output o;
+            o.group = -1;
+            o.type = ReductionType::Max;
+            o.band_name = detail::histogram_band_name(cfg.histograms[h], j);
+            o.hist = (int)h;
+            o.q = (int)j;
+            outputs.push_back(o);
+        }
     }
     // Tile state is identity-initialised (src/engine/tile_manager.cpp:183-260); here for the whole grid at once.
     for (auto& gr : groups) engine->init_planes(gr.planes, gr.mask, gr.select);
@@ -178,6 +193,7 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     std::vector<std::vector<uint8_t>> class_keep(filters.classes.size());
     for (size_t k = 1; k < filters.classes.size(); ++k) apply(filters.classes[k], class_keep[k]);
     auto keep_of = [&](const Group& gr, size_t i0) -> const uint8_t* { return gr.cls ? class_keep[(size_t)gr.cls].data() + i0 : nullptr; };
+    auto hist_keep = [&](const detail::HistogramEntry& e, size_t i0) -> const uint8_t* { return e.cls ? class_keep[(size_t)e.cls].data() + i0 : nullptr; };
 
     // the engine indexes a cloud with 32 bits: larger ones go in slices
     const size_t slice = (size_t)1 << 31;
@@ -205,6 +221,10 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
                 engine->scatter_glyph(pl, gr.glyph, arr, v + i0, keep_of(gr, i0));
                 pl.mask = keep_mask;
             }
+        }
+        for (size_t h = 0; h < hist.entries.size(); ++h) {
+            const detail::HistogramEntry& e = hist.entries[h];
+            engine->scatter_histogram(cubes[h].data(), e.bins, e.lo, e.inv_w, f32(e.value_channel) + i0, hist_keep(e, i0));
         }
     }
     last = ScatterInfo{};
@@ -244,7 +264,14 @@ Status Pipeline::Host::finalize() {
         (void)result->set_geometry(detail::result_geometry(cfg));
     }
     for (size_t r = 0; r < outputs.size(); ++r)
-        engine->finalize(groups[(size_t)outputs[r].group].planes, outputs[r].type, result->band_f32((int)r));
+        if (outputs[r].group >= 0) engine->finalize(groups[(size_t)outputs[r].group].planes, outputs[r].type, result->band_f32((int)r));
+    for (size_t h = 0, r = cfg.reductions.size(); h < hist.entries.size(); r += hist.entries[h].q.size(), ++h) {
+        // (one walk per histogram: its bands are consecutive outputs)
+        std::vector<float*> dsts;
+        for (size_t j = 0; j < hist.entries[h].q.size(); ++j) dsts.push_back(result->band_f32((int)(r + j)));
+        Status hs = detail::percentiles_host(hist.entries[h], cubes[h].data(), g.width, g.height, dsts.data(), engine->threads());
+        if (!hs.ok()) return hs;
+    }
     {                                                                // (the planes are the state: the bands are made anew by every finalize)
         std::vector<ReductionType> types;
         for (const auto& o : outputs) types.push_back(o.type);
@@ -258,11 +285,13 @@ Status Pipeline::Host::finalize() {
 
 std::vector<detail::StateOutput> Pipeline::Host::state_outputs() const {
     std::vector<detail::StateOutput> o;
-    for (const auto& out : outputs) o.push_back({out.group, out.type});
+    for (const auto& out : outputs)
+        if (out.group >= 0) o.push_back({out.group, out.type});
     return o;
 }
 
 Status Pipeline::Host::save_state(const std::string& dir_in) {
+    if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     detail::StateWindow w;
@@ -273,6 +302,7 @@ Status Pipeline::Host::save_state(const std::string& dir_in) {
 }
 
 Status Pipeline::Host::load_state(const std::string& dir_in) {
+    if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     detail::StateWindow w;

@@ -3,6 +3,7 @@
 // Same validation, messages, band naming, progress callback and `.pcrt` checkpoints as the HIP pipeline.
 #pragma once
 
+#include "histogram.h"
 #include "host_engine.h"
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
@@ -27,10 +28,11 @@ struct Pipeline::Host {
         FilterSpec filter;               // ReductionSpec::filter of the group's specs (part of the grouping key)
         int cls = 0;                     // its filter class (detail::FilterPlan): 0 = PipelineConfig::filter alone
     };
-    struct Output {
-        int group = 0;
+    struct Output {                      // one band finalize makes from the state: a ReductionSpec's, or a percentile band
+        int group = 0;                   // -1: a percentile band of histogram `hist` (its type is Max: filled like a Max band)
         ReductionType type = ReductionType::Sum;
         std::string band_name;
+        int hist = -1, q = 0;            // the histogram and which of its percentiles
     };
 
     PipelineConfig cfg;
@@ -39,6 +41,8 @@ struct Pipeline::Host {
     std::vector<Output> outputs;
     detail::FilterPlan filters;          // ReductionSpec::filter of every spec, planned at init
     std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in host memory
+    detail::HistogramPlan hist;          // PipelineConfig::histograms, planned at init
+    std::vector<std::vector<uint32_t>> cubes;    // entry by entry: count[bins][height * width], zero at create
     std::unique_ptr<Grid> result;
     bool finalized = false;
     ProgressCallback callback;

@@ -15,6 +15,7 @@
 #include "banded_pipeline.h"
 #include "device_pipeline.h"
 #include "ground_filter.h"
+#include "histogram.h"
 #include "terrain.h"
 #include "host_pipeline.h"
 #include "las_io.h"
@@ -53,6 +54,10 @@ std::vector<std::string> named_channels(const PipelineConfig& c) {
         for (const auto& p : r.filter.predicates) add(p.channel_name);
     }
     for (const auto& p : c.filter.predicates) add(p.channel_name);
+    for (const auto& h : c.histograms) {
+        add(h.value_channel);
+        for (const auto& p : h.filter.predicates) add(p.channel_name);
+    }
     for (const auto& sc : c.surface_channels) add(sc.value_channel);
     return out;
 }
@@ -86,6 +91,10 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         return fail_with(Status::error(StatusCode::InvalidArgument,
             "pipeline: fill_nodata_radius needs the whole grid; fill the gathered grid with fill_nodata"));
     {
+        const Status hs = detail::check_histograms(config);     // (ahead of the ground and terrain plans, which may name its bands)
+        if (!hs.ok()) return fail_with(hs);
+    }
+    {
         detail::GroundPlan plan;                      // (every engine plans again for itself: here only the refusals)
         const Status gs = detail::plan_ground(config, &plan);
         if (!gs.ok()) return fail_with(gs);
@@ -100,6 +109,7 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
     size_t budget = 0;
     if (Banded::needed(config, &budget)) {
         if (!config.surface_channels.empty()) return fail_with(detail::surfaces_out_of_core_error());
+        if (!config.histograms.empty()) return fail_with(detail::histograms_out_of_core_error());
         Status bs = Status::success();
         p->banded_ = Banded::create(config, p.get(), budget, &bs);
         if (!p->banded_) return fail_with(bs);
@@ -258,6 +268,22 @@ Status Pipeline::set_surface(const std::string& name, const Grid& grid, int band
     if (host_) return host_->set_surface(name, grid, band);
     if (banded_) return Status::error(StatusCode::InvalidArgument, "pipeline: set_surface: '" + name + "' names no surface channel of this pipeline");
     return impl_->set_surface(name, grid, band);
+}
+Status Pipeline::histogram_counts(int i, std::vector<uint32_t>* out) const {
+    if (impl_) return impl_->histogram_counts(i, out);
+    if (!host_ || i < 0 || (size_t)i >= host_->cubes.size() || !out)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: histogram_counts: no histogram " + std::to_string(i));
+    *out = host_->cubes[(size_t)i];
+    return Status::success();
+}
+Status Pipeline::histogram_shape(int i, int* bins, int* rows, int* width) const {
+    const PipelineConfig* c = host_ ? &host_->cfg : impl_ ? &impl_->cfg : nullptr;
+    if (!c || i < 0 || (size_t)i >= c->histograms.size() || !bins || !rows || !width)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: histogram_counts: no histogram " + std::to_string(i));
+    *bins = c->histograms[(size_t)i].bins;
+    *rows = c->grid.height;                                  // (a row-block shard is refused: the window is the grid)
+    *width = c->grid.width;
+    return Status::success();
 }
 Status Pipeline::finalize() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(); }
 Status Pipeline::finalize_async() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(false); }

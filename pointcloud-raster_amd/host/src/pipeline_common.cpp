@@ -37,6 +37,15 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
         return Status::error(StatusCode::InvalidArgument, "filter_points: more than " + std::to_string(max_predicates) + " predicates");
     for (const auto& r : cfg.reductions)                       // ReductionSpec::filter: the same checks, the same messages
         if (!(fs = check_filter(r.filter)).ok()) return fs;
+    for (const auto& h : cfg.histograms) {                     // PipelineConfig::histograms: like a reduction's filter and value
+        if (!(fs = check_filter(h.filter)).ok()) return fs;
+        if (derived(h.value_channel)) continue;
+        if (!cloud.channel_data(h.value_channel))
+            return Status::error(StatusCode::InvalidArgument, "pipeline: histogram value channel not found: " + h.value_channel);
+        const ChannelDesc* d = cloud.channel(h.value_channel);
+        if (!d || d->dtype != DataType::Float32)
+            return Status::error(StatusCode::InvalidArgument, "pipeline: histogram value channel must be Float32");
+    }
     for (const auto& r : cfg.reductions) {
         if (!derived(r.value_channel)) {
             if (!cloud.channel_data(r.value_channel))
@@ -62,18 +71,20 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
 Status plan_filters(const PipelineConfig& cfg, FilterPlan* out) {
     *out = FilterPlan{};
     out->classes.emplace_back();
-    for (const auto& r : cfg.reductions) {
+    auto class_for = [out](const FilterSpec& filter) {
         int cls = 0;
-        if (!r.filter.empty()) {
+        if (!filter.empty()) {
             for (size_t k = 1; k < out->classes.size() && !cls; ++k)
-                if (same_filter(out->classes[k], r.filter)) cls = (int)k;
+                if (same_filter(out->classes[k], filter)) cls = (int)k;
             if (!cls) {
-                out->classes.push_back(r.filter);
+                out->classes.push_back(filter);
                 cls = (int)out->classes.size() - 1;
             }
         }
-        out->class_of.push_back(cls);
-    }
+        return cls;
+    };
+    for (const auto& r : cfg.reductions) out->class_of.push_back(class_for(r.filter));
+    for (const auto& h : cfg.histograms) out->hist_class_of.push_back(class_for(h.filter));   // (a histogram's filter is one more class)
     if (!out->any()) { out->words.assign(1, 0u); return Status::success(); }
     if (out->classes.size() - 1 > kMaxSpecFilters)
         return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(kMaxSpecFilters) +

@@ -6,6 +6,7 @@
 #include "pcr/engine/pipeline.h"
 #include "pcr_hip.h"
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -124,6 +125,22 @@ inline std::string default_band_name(const ReductionSpec& r) {
     return r.output_band_name.empty() ? r.value_channel + "_" + std::to_string(static_cast<int>(r.type)) : r.output_band_name;
 }
 
+// PipelineConfig::histograms: the name of entry h's j-th percentile band, "{value_channel}_p{round(q * 100)}" unless given.
+inline std::string histogram_band_name(const HistogramConfig& h, size_t j) {
+    if (j < h.band_names.size() && !h.band_names[j].empty()) return h.band_names[j];
+    return h.value_channel + "_p" + std::to_string(std::lround((double)h.percentiles[j] * 100.0));
+}
+// The bands finalize makes from the accumulated state, in the result grid's order: one per ReductionSpec, then the histograms'
+// percentile bands entry by entry.  What ground.source_band, ground.top_band and terrain[].source_band may name (the DTM, hag
+// and terrain bands follow them).
+inline std::vector<std::string> output_band_names(const PipelineConfig& cfg) {
+    std::vector<std::string> names;
+    for (const auto& r : cfg.reductions) names.push_back(default_band_name(r));
+    for (const auto& h : cfg.histograms)
+        for (size_t j = 0; j < h.percentiles.size(); ++j) names.push_back(histogram_band_name(h, j));
+    return names;
+}
+
 // One ReductionSpec as the checkpoint code sees it.
 struct StateOutput {
     int group;
@@ -216,6 +233,7 @@ constexpr size_t kMaxSpecFilters = 8;
 struct FilterPlan {
     std::vector<FilterSpec> classes;         // [0] is empty
     std::vector<int> class_of;               // per ReductionSpec
+    std::vector<int> hist_class_of;          // per entry of PipelineConfig::histograms: its filter joins the same plan
     std::vector<FilterPredicate> table;      // PipelineConfig::filter's predicates first
     std::vector<uint32_t> words;             // per class
     bool any() const { return classes.size() > 1; }

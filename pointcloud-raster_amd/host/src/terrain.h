@@ -99,8 +99,7 @@ inline Status plan_terrain(const PipelineConfig& cfg, const GroundPlan& ground, 
     auto refuse = [](const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: " + msg); };
     if (cfg.shard_row_begin >= 0 || cfg.shard_row_end >= 0)
         return refuse("terrain bands need the whole grid; derive them from the gathered grid with terrain");
-    std::vector<std::string> names;
-    for (const auto& r : cfg.reductions) names.push_back(default_band_name(r));
+    std::vector<std::string> names = output_band_names(cfg);
     if (ground.on) {
         names.push_back(ground.dtm_name);
         if (ground.top >= 0) names.push_back(ground.hag_name);

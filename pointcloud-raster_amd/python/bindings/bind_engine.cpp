@@ -109,6 +109,28 @@ void bind_engine(py::module_& m) {
         .def_readwrite("value_channel", &SurfaceChannelConfig::value_channel)
         .def_readwrite("mode", &SurfaceChannelConfig::mode);
 
+    py::class_<HistogramConfig>(m, "HistogramConfig",
+                                "One per-cell histogram of a Float32 channel (a surface channel included) and its percentile bands")
+        .def(py::init<>())
+        .def(py::init<const HistogramConfig&>())
+        .def(py::init([](const std::string& value_channel, float lo, float hi, int bins, const std::vector<float>& percentiles) {
+            HistogramConfig h;
+            h.value_channel = value_channel;
+            h.lo = lo;
+            h.hi = hi;
+            h.bins = bins;
+            h.percentiles = percentiles;
+            return h;
+        }), py::arg("value_channel"), py::arg("lo") = 0.0f, py::arg("hi") = 64.0f, py::arg("bins") = 32,
+            py::arg("percentiles") = std::vector<float>())
+        .def_readwrite("value_channel", &HistogramConfig::value_channel)
+        .def_readwrite("lo", &HistogramConfig::lo)
+        .def_readwrite("hi", &HistogramConfig::hi)
+        .def_readwrite("bins", &HistogramConfig::bins)
+        .def_readwrite("filter", &HistogramConfig::filter)
+        .def_readwrite("percentiles", &HistogramConfig::percentiles)
+        .def_readwrite("band_names", &HistogramConfig::band_names);
+
     py::class_<PipelineConfig>(m, "PipelineConfig")
         .def(py::init<>())
         .def_readwrite("grid", &PipelineConfig::grid)
@@ -144,7 +166,10 @@ void bind_engine(py::module_& m) {
         .def_readwrite("las_gps_time_origin", &PipelineConfig::las_gps_time_origin)
         .def_readwrite("surface_channels", &PipelineConfig::surface_channels,
                        "Per-point Float32 channels derived at every ingest from a band given with Pipeline.set_surface (assign a "
-                       "list of SurfaceChannelConfig): usable wherever a channel is named");
+                       "list of SurfaceChannelConfig): usable wherever a channel is named")
+        .def_readwrite("histograms", &PipelineConfig::histograms,
+                       "Per-cell histograms counted at every ingest and the percentile bands finalize() appends behind the "
+                       "reductions' bands (assign a list of HistogramConfig)");
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
         .def(py::init<>())
@@ -177,6 +202,17 @@ void bind_engine(py::module_& m) {
             raise_if_error(p.set_surface(name, grid, band));
         }, py::arg("name"), py::arg("grid"), py::arg("band") = 0,
              "Gives the surface channel `name` its surface: band `band` of a grid that carries its geometry, copied into the pipeline")
+        .def("histogram", [](const Pipeline& p, int i) {
+            std::vector<uint32_t> counts;
+            raise_if_error(p.histogram_counts(i, &counts));
+            int bins = 0, rows = 0, width = 0;
+            raise_if_error(p.histogram_shape(i, &bins, &rows, &width));
+            py::array_t<uint32_t> out({(py::ssize_t)bins, (py::ssize_t)rows, (py::ssize_t)width});
+            if (counts.size() != (size_t)out.size()) throw std::runtime_error("pipeline: histogram: unexpected cube size");
+            std::memcpy(out.mutable_data(), counts.data(), counts.size() * sizeof(uint32_t));
+            return out;
+        }, py::arg("i") = 0,
+             "The cube of histogram i as a numpy.uint32 array (bins, height, width): a host copy, valid after any ingest")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },
              "Device-resident result: the finalize kernels are only enqueued on the pipeline's stream (complete after synchronize()); "

@@ -194,6 +194,9 @@ SYMBOLS = {
     "pcr_hip_las_decode_host": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), C.c_int],
     "pcr_hip_sample_grid": [C.POINTER(Grid), _VP, _I64, _VP, _VP, _VP, _U64, C.c_int, _VP, _VP],
     "pcr_hip_sample_grid_host": [C.POINTER(Grid), _VP, _I64, _VP, _VP, _VP, _U64, C.c_int, _VP],
+    "pcr_hip_scatter_histogram": [_VP, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _U64],
+    "pcr_hip_histogram_percentiles": [C.POINTER(Grid), _VP, C.c_int, C.c_double, C.c_double, C.c_int, _VP, C.POINTER(_VP), _VP],
+    "pcr_hip_histogram_percentiles_host": [C.POINTER(Grid), _VP, C.c_int, C.c_double, C.c_double, C.c_int, _VP, C.POINTER(_VP)],
 }
 
 _lib = None
