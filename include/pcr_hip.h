@@ -308,7 +308,9 @@ int pcr_hip_engine_set_point_mask(pcr_hip_engine* e, const uint8_t* d_mask);
  *   preds[0 .. n_pred)        the distinct predicates, at most PCR_HIP_MAX_CLASS_PREDICATES (they travel as kernel arguments:
  *                             32 x 80 B fit the 4 KB a kernel may take; a longer table would have to live in device memory)
  *   class_predicates[j]       bit k set: class j ANDs preds[k]; 0: the class keeps every point; 1..PCR_HIP_MAX_FILTER_CLASSES
- *                             classes.  By convention class 0 is PipelineConfig::filter alone when one is asked for.
+ *                             classes.  By convention class 0 is PipelineConfig::filter alone when one is asked for: the
+ *                             pipelines' one caller (detail::sweep_filter_classes) runs every filtered ingest through this
+ *                             sweep, a pipeline with PipelineConfig::filter and no spec filter as the table of one class.
  *   d_masks + j * mask_stride class j's mask, n bytes (1 = keep); mask_stride >= n
  *   d_counts                  optional, n_classes device u64 zeroed by the call: survivors per class
  *      A channel is loaded once per point however many classes read it and a predicate evaluated once; with 16-byte aligned

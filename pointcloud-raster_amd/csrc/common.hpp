@@ -255,6 +255,30 @@ __device__ __forceinline__ float select_value(unsigned long long w) { return __u
 __device__ __forceinline__ float select_key(unsigned long long w) { return __uint_as_float(select_unord((unsigned)(w >> 32))); }
 constexpr unsigned kSelectEmptyValueBits = 0x7FC00000u;        // the identity's NaN (MostRecentOp::identity)
 
+// One filter predicate on one channel value (evaluate_predicate, src/engine/filter.cpp:34-56), for k_filter_mask and
+// k_filter_classes alike: a NaN fails every comparison but NotEqual and NotInSet.
+__device__ __forceinline__ bool eval_pred(const pcr_hip_predicate& pr, float v) {
+    switch (pr.op) {
+        case PCR_HIP_CMP_EQUAL: return v == pr.value;
+        case PCR_HIP_CMP_NOT_EQUAL: return v != pr.value;
+        case PCR_HIP_CMP_LESS: return v < pr.value;
+        case PCR_HIP_CMP_LESS_EQUAL: return v <= pr.value;
+        case PCR_HIP_CMP_GREATER: return v > pr.value;
+        case PCR_HIP_CMP_GREATER_EQUAL: return v >= pr.value;
+        case PCR_HIP_CMP_IN_SET: {
+            bool in = false;
+            for (int k = 0; k < pr.set_size; ++k) in = in || (v == pr.set[k]);
+            return in;
+        }
+        case PCR_HIP_CMP_NOT_IN_SET: {
+            bool in = false;
+            for (int k = 0; k < pr.set_size; ++k) in = in || (v == pr.set[k]);
+            return !in;
+        }
+    }
+    return false;
+}
+
 // Mark the reference tile of (row, col) as having state (pipeline.cpp:688-691, 1220).
 __device__ __forceinline__ void touch_tile(const GridDev& g, uint32_t* touched, int row, int col) {
     int t = fast_div(row, g.th) * g.tiles_x + fast_div(col, g.tw);

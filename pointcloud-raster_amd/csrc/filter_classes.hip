@@ -1,4 +1,5 @@
-// filter_classes.hip -- per-reduction point filters (ReductionSpec::filter): pcr_hip_filter_classes, pcr_hip_engine_touch.
+// filter_classes.hip -- the pipelines' filter stage (PipelineConfig::filter as class 0, ReductionSpec::filter as the classes
+// behind it): pcr_hip_filter_classes, pcr_hip_engine_touch.
 //
 //   k_filter_classes   ONE sweep over the points evaluates a table of DISTINCT predicates and stores one byte mask per filter
 //                      CLASS (a class = the set of predicates it ANDs), in the layout pcr_hip_engine_set_point_mask takes.  A
@@ -31,30 +32,6 @@ struct ClassSweep {
     pcr_hip_predicate p[PCR_HIP_MAX_CLASS_PREDICATES];
 };
 static_assert(sizeof(ClassSweep) + 64 <= 4096, "the sweep's table must fit the kernel arguments");
-
-// evaluate_predicate (src/engine/filter.cpp:34-56), as k_filter_mask evaluates it: a NaN fails every comparison but
-// NotEqual and NotInSet.
-__device__ __forceinline__ bool eval_pred(const pcr_hip_predicate& pr, float v) {
-    switch (pr.op) {
-        case PCR_HIP_CMP_EQUAL: return v == pr.value;
-        case PCR_HIP_CMP_NOT_EQUAL: return v != pr.value;
-        case PCR_HIP_CMP_LESS: return v < pr.value;
-        case PCR_HIP_CMP_LESS_EQUAL: return v <= pr.value;
-        case PCR_HIP_CMP_GREATER: return v > pr.value;
-        case PCR_HIP_CMP_GREATER_EQUAL: return v >= pr.value;
-        case PCR_HIP_CMP_IN_SET: {
-            bool in = false;
-            for (int k = 0; k < pr.set_size; ++k) in = in || (v == pr.set[k]);
-            return in;
-        }
-        case PCR_HIP_CMP_NOT_IN_SET: {
-            bool in = false;
-            for (int k = 0; k < pr.set_size; ++k) in = in || (v == pr.set[k]);
-            return !in;
-        }
-    }
-    return false;
-}
 
 // Bit k of fail[j]: point j of the lane's four fails predicate k.
 __device__ __forceinline__ void eval_channel(const ClassSweep& t, int c, const float (&v)[4], unsigned (&fail)[4]) {

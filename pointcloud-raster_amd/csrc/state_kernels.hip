@@ -311,33 +311,11 @@ k_finalize_select(GridDev g, const unsigned long long* __restrict__ packed, cons
     }
 }
 
-// FilterSpec evaluation: AND of predicates (evaluate_predicate, src/engine/filter.cpp:34-56).
+// FilterSpec evaluation: AND of predicates (eval_pred, common.hpp).
 struct PredSet {
     int n;
     pcr_hip_predicate p[PCR_HIP_MAX_FILTER_PREDICATES];
 };
-
-__device__ __forceinline__ bool eval_pred(const pcr_hip_predicate& pr, float v) {
-    switch (pr.op) {
-        case PCR_HIP_CMP_EQUAL: return v == pr.value;
-        case PCR_HIP_CMP_NOT_EQUAL: return v != pr.value;
-        case PCR_HIP_CMP_LESS: return v < pr.value;
-        case PCR_HIP_CMP_LESS_EQUAL: return v <= pr.value;
-        case PCR_HIP_CMP_GREATER: return v > pr.value;
-        case PCR_HIP_CMP_GREATER_EQUAL: return v >= pr.value;
-        case PCR_HIP_CMP_IN_SET: {
-            bool in = false;
-            for (int k = 0; k < pr.set_size; ++k) in = in || (v == pr.set[k]);
-            return in;
-        }
-        case PCR_HIP_CMP_NOT_IN_SET: {
-            bool in = false;
-            for (int k = 0; k < pr.set_size; ++k) in = in || (v == pr.set[k]);
-            return !in;
-        }
-    }
-    return false;
-}
 
 __global__ void __launch_bounds__(kBlock)
 k_filter_mask(PredSet ps, uint64_t n, unsigned char* __restrict__ mask, unsigned long long* __restrict__ pass_count) {

@@ -53,7 +53,7 @@ std::unique_ptr<Pipeline::Banded> Pipeline::Banded::create(const PipelineConfig&
     auto made = std::make_unique<Banded>();
     Banded& bd = *made;
     bd.cfg = config;
-    bd.grouping = detail::group_reductions(config.reductions);
+    bd.plan = detail::plan_groups(config);
     bd.spec_filters = filters.any();
     for (int r0 = 0; r0 < g.height; r0 += band_rows) bd.bands.push_back({r0, std::min(r0 + band_rows, g.height)});
     bd.parked.resize(bd.bands.size());
@@ -94,10 +94,9 @@ Pipeline::Banded::~Banded() {
 // bytes of device memory one grid row costs: 4 B per cell and plane (a MostRecent group's packed words: 8 B per cell,
 // its two slots), + the finalized bands a sub-pipeline keeps
 size_t Pipeline::Banded::bytes_per_row(const PipelineConfig& c) {
-    const detail::Grouping g = detail::group_reductions(c.reductions);
     size_t planes = 0;
-    for (uint32_t m : g.masks)
-        for (int p = 0; p < 4; ++p) planes += (m & kPlaneBits[p]) ? 1 : 0;
+    for (const auto& gr : detail::plan_groups(c).groups)
+        for (int p = 0; p < 4; ++p) planes += (gr.mask & kPlaneBits[p]) ? 1 : 0;
     // (PipelineConfig::histograms: a cube's bin planes and its percentile bands count like any other plane and band)
     for (const auto& h : c.histograms) planes += (size_t)std::max(h.bins, 0) + h.percentiles.size();
     return (size_t)c.grid.width * 4 * (planes + c.reductions.size());
@@ -106,18 +105,18 @@ size_t Pipeline::Banded::bytes_per_row(const PipelineConfig& c) {
 // a band nobody has touched yet: identity planes, no flags
 void Pipeline::Banded::blank(size_t b, Parked& k) const {
     const size_t cells = (size_t)(bands[b].second - bands[b].first) * (size_t)cfg.grid.width;
-    k.planes.assign(grouping.masks.size() * 4, {});
-    for (size_t g = 0; g < grouping.masks.size(); ++g)
+    k.planes.assign(plan.groups.size() * 4, {});
+    for (size_t g = 0; g < plan.groups.size(); ++g)
         for (int p = 0; p < 4; ++p)
-            if (grouping.masks[g] & kPlaneBits[p])
-                k.planes[g * 4 + (size_t)p].assign(cells, detail::plane_identity(grouping.select[g] != 0, p));
+            if (plan.groups[g].mask & kPlaneBits[p])
+                k.planes[g * 4 + (size_t)p].assign(cells, detail::plane_identity(plan.groups[g].select, p));
     const GridConfig& g = cfg.grid;
     k.touched.assign((size_t)((g.width + g.tile_width - 1) / g.tile_width) * (size_t)((g.height + g.tile_height - 1) / g.tile_height), 0u);
 }
 
 Status Pipeline::Banded::spill(size_t b) {
     Parked& k = parked[b];
-    Status s = detail::write_state_tiles(cfg.grid, grouping.outputs, window_of(b, k), k.touched, spill_dir);
+    Status s = detail::write_state_tiles(cfg.grid, plan.outputs, window_of(b, k), k.touched, spill_dir);
     if (!s.ok()) return s;
     host_used -= k.release();
     ++spills;
@@ -128,7 +127,7 @@ Status Pipeline::Banded::reload(size_t b) {
     Parked& k = parked[b];
     blank(b, k);
     size_t loaded = 0;
-    Status s = detail::read_state_tiles(cfg.grid, grouping.outputs, window_of(b, k), k.touched, spill_dir, &loaded);
+    Status s = detail::read_state_tiles(cfg.grid, plan.outputs, window_of(b, k), k.touched, spill_dir, &loaded);
     if (!s.ok()) return s;
     k.on_disk = false;
     host_used += k.bytes;
@@ -192,22 +191,23 @@ std::unique_ptr<Pipeline> Pipeline::Banded::visit(size_t b, Status* st, bool* wa
     return sub;
 }
 
-// Survivors of the filter, as the bands' own ingests will count them (the same kernel on the same channels): what
-// points_processed grows by (src/engine/pipeline.cpp:749), whether or not any band is visited.
+// Survivors of PipelineConfig::filter, as the bands' own ingests will count them (the same sweep on the same channels, class 0
+// alone): what points_processed grows by (src/engine/pipeline.cpp:749), whether or not any band is visited.
 Status Pipeline::Banded::count_kept(const PointCloud& dev, size_t* kept) {
     const size_t n = dev.count();
-    *kept = n;
-    if (cfg.filter.empty()) return Status::success();
     Impl::DeviceScope scope(cfg.cuda_device_id);
-    std::vector<pcr_hip_predicate> preds;
-    Status s = detail::marshal_predicates(cfg.filter, [&dev](const std::string& name, const float** out) {
+    PipelineConfig alone;
+    alone.filter = cfg.filter;
+    detail::FilterPlan class0;
+    Status s = detail::plan_filters(alone, &class0);
+    detail::Buffer mb;
+    if (s.ok()) s = mb.allocate(detail::filter_stage_bytes(class0, n), MemoryLocation::Device);
+    if (!s.ok()) return s;
+    std::vector<const uint8_t*> masks;
+    return detail::sweep_filter_classes(class0, [&dev](const std::string& name, const float** out) {
         *out = static_cast<const float*>(dev.channel_data(name));
         return Status::success();
-    }, &preds);
-    if (!s.ok()) return s;
-    detail::Buffer mb;
-    if (!(s = mb.allocate(n + 16, MemoryLocation::Device)).ok()) return s;
-    return detail::count_survivors(preds, n, mb.data(), nullptr, kept);
+    }, n, mb.data(), nullptr, &masks, kept);
 }
 
 Status Pipeline::Banded::ingest(const PointCloud& cloud) {
@@ -370,7 +370,7 @@ Status Pipeline::Banded::save_state(const std::string& dir_in) {
             if (!(s = reload(b)).ok()) return s;
             from_disk = true;
         }
-        if (!(s = detail::write_state_tiles(cfg.grid, grouping.outputs, window_of(b, k), k.touched, dir)).ok()) return s;
+        if (!(s = detail::write_state_tiles(cfg.grid, plan.outputs, window_of(b, k), k.touched, dir)).ok()) return s;
         if (from_disk) drop_host_copy(b);
     }
     return Status::success();
@@ -391,7 +391,7 @@ Status Pipeline::Banded::load_state(const std::string& dir_in) {
             into = &fresh;
         }
         size_t loaded = 0;
-        if (!(s = detail::read_state_tiles(cfg.grid, grouping.outputs, window_of(b, *into), into->touched, dir, &loaded)).ok()) return s;
+        if (!(s = detail::read_state_tiles(cfg.grid, plan.outputs, window_of(b, *into), into->touched, dir, &loaded)).ok()) return s;
         if (!loaded) continue;                                          // a reloaded band stays in host memory here
         if (into == &fresh) { k.planes = std::move(fresh.planes); k.touched = std::move(fresh.touched); }
         if (!(s = account(b)).ok()) return s;

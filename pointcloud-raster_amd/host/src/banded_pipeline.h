@@ -29,7 +29,7 @@ namespace pcr {
 struct Pipeline::Banded {
     PipelineConfig cfg;                                   // the WHOLE grid, as the caller gave it
     std::vector<std::pair<int, int>> bands;               // [r0, r1), multiples of the tile height
-    detail::Grouping grouping;                            // groups' plane masks, one StateOutput per ReductionSpec
+    detail::GroupPlan plan;                               // the groups and outputs of every band's sub-pipeline (parked planes[4 g + p])
     bool spec_filters = false;                            // some ReductionSpec has a filter of its own (detail::FilterPlan::any)
     struct Parked {
         bool any = false, on_disk = false;

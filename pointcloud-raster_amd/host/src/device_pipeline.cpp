@@ -19,8 +19,6 @@
 namespace pcr {
 
 using detail::kPlaneBits;
-using detail::planes_for;
-using detail::same_glyph;
 
 Pipeline::Impl::~Impl() {
     if (engine) pcr_hip_engine_destroy(engine);
@@ -112,47 +110,14 @@ Status Pipeline::Impl::init() {
         own_stream = true;
     }
 
-    // accumulation groups + outputs
-    for (size_t ri = 0; ri < cfg.reductions.size(); ++ri) {
-        const ReductionSpec& r = cfg.reductions[ri];
-        int gi = -1;
-        for (size_t k = 0; k < groups.size(); ++k)
-            if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph) &&
-                groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel) &&
-                detail::same_filter(groups[k].filter, r.filter))
-                gi = (int)k;                                 // (detail::same_group)
-        if (gi < 0) {
-            groups.emplace_back();
-            gi = (int)groups.size() - 1;
-            groups[gi].value_channel = r.value_channel;
-            groups[gi].glyph = r.glyph;
-            groups[gi].select = detail::is_select(r.type);
-            if (groups[gi].select) groups[gi].key_channel = r.timestamp_channel;
-            groups[gi].filter = r.filter;
-            groups[gi].cls = filters.class_of[ri];
-        }
-        // a glyph reduction of an unsupported type is rejected at ingest (as in the reference);
-        // it still gets planes so that finalize has something to read.
-        groups[gi].mask |= planes_for(r.type);
-        Output o;
-        o.group = gi;
-        o.type = r.type;
-        o.band_name = r.output_band_name.empty()
-            ? r.value_channel + "_" + std::to_string(static_cast<int>(r.type)) : r.output_band_name;
-        outputs.push_back(o);
+    // accumulation groups + outputs (the percentile bands behind the reductions' and ahead of the DTM, hag and terrain bands)
+    {
+        detail::GroupPlan plan = detail::plan_groups(cfg);
+        groups.resize(plan.groups.size());
+        for (size_t gi = 0; gi < groups.size(); ++gi) static_cast<detail::GroupSpec&>(groups[gi]) = plan.groups[gi];
+        outputs = std::move(plan.outputs);
     }
-    // PipelineConfig::histograms: one output per percentile band, behind the reductions' and ahead of the DTM, hag and terrain bands
     hist = detail::plan_histograms(cfg, filters);
-    for (size_t h = 0; h < hist.entries.size(); ++h)
-        for (size_t j = 0; j < hist.entries[h].q.size(); ++j) {
-            Output o;
-            o.group = -1;
-            o.type = ReductionType::Max;
-            o.band_name = detail::histogram_band_name(cfg.histograms[h], j);
-            o.hist = (int)h;
-            o.q = (int)j;
-            outputs.push_back(o);
-        }
     if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
     if (!(s = detail::plan_terrain(cfg, ground, &terrain)).ok()) return s;
     if (!(s = detail::plan_surfaces(cfg)).ok()) return s;
@@ -632,16 +597,14 @@ Status Pipeline::Impl::line_reach_rows(const GlyphSpec& gl, const void* d_half_l
     *rows_needed = 0;
     if (gl.type != GlyphType::Line || !d_half_length) return Status::success();
     if (own_rows() == hg.height || block_is_whole_tiles()) return Status::success();
-    detail::Buffer& word = staging["line_reach:word"];           // the reduction's device word, kept for the pipeline's life
-    if (word.bytes() < 4) {
-        Status a = word.allocate(256, MemoryLocation::Device);
-        if (!a.ok()) return a;
-    }
+    detail::Buffer* word = nullptr;                              // the reduction's device words, kept for the pipeline's life
+    Status s = staging_at_least("line_reach:word", 8, &word);
+    if (!s.ok()) return s;
     // hy = half_length / cell_size_y goes through std::min(hy, cap) (glyph_kernels.cu:228-234): the sign of half_length
     // that makes hy positive is capped by max_radius_cells, the other one reaches |half_length / cell_size_y| rows
     float max_pos = 0.f, max_neg = 0.f;
-    Status s = detail::hip_status(pcr_hip_signed_max_f32_masked(static_cast<const float*>(d_half_length), d_mask, n,
-                                                                static_cast<uint32_t*>(word.data()), &max_pos, &max_neg, stream));
+    s = detail::hip_status(pcr_hip_signed_max_f32_masked(static_cast<const float*>(d_half_length), d_mask, n,
+                                                         static_cast<uint32_t*>(word->data()), &max_pos, &max_neg, stream));
     if (!s.ok()) return s;
     const double acsy = std::fabs(cfg.grid.cell_size_y);
     const float capped_side = cfg.grid.cell_size_y > 0 ? max_pos : max_neg;
@@ -662,21 +625,28 @@ Status Pipeline::Impl::reach_error(int rows) const {
         std::to_string((long long)rows) + " on every rank, or use tile-aligned row blocks");
 }
 
+// The staging buffer `key`, at least `bytes` large: the one way such a buffer grows.  One that is large enough costs nothing and
+// waits for nothing; one that has to grow is replaced, with an eighth of slack, once the stream is done with the old block
+// (chunks of ingest_async / ingest_file still in flight may read it).
+Status Pipeline::Impl::staging_at_least(const std::string& key, size_t bytes, detail::Buffer** out) {
+    detail::Buffer& b = staging[key];
+    *out = &b;
+    if (b.bytes() >= bytes) return Status::success();
+    if (b.data()) {
+        Status s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+        if (!s.ok()) return s;
+    }
+    return b.allocate(bytes + bytes / 8, MemoryLocation::Device);
+}
+
 // Device pointer of a named array of the cloud; host-resident arrays are staged to HBM.
 Status Pipeline::Impl::device_array(const void* src, MemoryLocation loc, size_t bytes, const std::string& key, const void** out) {
     if (loc == MemoryLocation::Device) { *out = src; return Status::success(); }
-    detail::Buffer& b = staging[key];
-    if (b.bytes() < bytes) {
-        // earlier kernels may still read the old block
-        Status s = detail::hip_status(pcr_hip_stream_synchronize(stream));
-        if (!s.ok()) return s;
-        s = b.allocate(bytes + bytes / 8, MemoryLocation::Device);
-        if (!s.ok()) return s;
-    }
-    Status s = detail::hip_status(pcr_hip_memcpy_h2d(b.data(), src, bytes, stream));
-    if (!s.ok()) return s;
-    *out = b.data();
-    return Status::success();
+    detail::Buffer* b = nullptr;
+    Status s = staging_at_least(key, bytes, &b);
+    if (s.ok()) s = detail::hip_status(pcr_hip_memcpy_h2d(b->data(), src, bytes, stream));
+    if (s.ok()) *out = b->data();
+    return s;
 }
 
 // Rows the Line groups of this pipeline need beyond a centre row for THIS cloud (0 when no check applies): what
@@ -721,45 +691,6 @@ Status Pipeline::Impl::marshal_glyph(const GlyphSpec& gl, const detail::ChannelL
     return s;
 }
 
-// ReductionSpec::filter: ONE sweep over the points (pcr_hip_filter_classes) makes the mask of every filter class, into the
-// "filter:mask" staging buffer laid out [128 B: u64 survivor counts][class masks, each a multiple of 16 bytes apart].
-// (*masks)[k]: class k's mask; null for class 0 when there is no cfg.filter (every point is kept).  *kept: cfg.filter's
-// survivors -- read back, with the one host wait count_survivors always had, only when there is a cfg.filter; an ingest
-// without one enqueues the sweep and waits for nothing.  (Nine masks -- cfg.filter and eight spec filters -- take a second
-// call for the ninth: the C-ABI sweeps eight classes at a time.)
-Status Pipeline::Impl::sweep_filter_classes(const detail::ChannelLookup& channel, size_t n, std::vector<const uint8_t*>* masks, size_t* kept) {
-    FilterSpec table;
-    table.predicates = filters.table;
-    std::vector<pcr_hip_predicate> preds;
-    Status s = detail::marshal_predicates(table, channel, &preds);
-    if (!s.ok()) return s;
-    const bool with_cfg = !cfg.filter.empty();
-    const size_t first = with_cfg ? 0 : 1, n_cls = filters.classes.size();
-    const size_t stride = (n + 15) & ~(size_t)15, header = 128;
-    detail::Buffer& mb = staging["filter:mask"];
-    if (mb.bytes() < header + (n_cls - first) * stride) {
-        if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;     // (chunks in flight may still read the old block)
-        if (!(s = mb.allocate(header + (n_cls - first) * (stride + stride / 8 + 16), MemoryLocation::Device)).ok()) return s;
-    }
-    uint8_t* const base = static_cast<uint8_t*>(mb.data()) + header;
-    auto* const d_counts = static_cast<unsigned long long*>(mb.data());
-    masks->assign(n_cls, nullptr);
-    for (size_t c = first; c < n_cls; c += PCR_HIP_MAX_FILTER_CLASSES) {
-        const int m = (int)std::min<size_t>(PCR_HIP_MAX_FILTER_CLASSES, n_cls - c);
-        s = detail::hip_status(pcr_hip_filter_classes(preds.data(), (int)preds.size(), filters.words.data() + c, m, n,
-                                                      base + (c - first) * stride, stride, with_cfg && c == 0 ? d_counts : nullptr, stream));
-        if (!s.ok()) return s;
-        for (int k = 0; k < m; ++k) (*masks)[c + (size_t)k] = base + (c - first + (size_t)k) * stride;
-    }
-    *kept = n;
-    if (!with_cfg) return Status::success();
-    unsigned long long h_count = 0;
-    if (!(s = detail::hip_status(pcr_hip_memcpy_d2h(&h_count, d_counts, sizeof h_count, stream))).ok()) return s;
-    if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
-    *kept = (size_t)h_count;
-    return Status::success();
-}
-
 // PipelineConfig::surface_channels: the band and its geometry into HBM the pipeline owns.  Chunks in flight may still read the
 // old band: the stream is waited for first (store_surface waits for the copy, so the caller's grid is free on return).
 Status Pipeline::Impl::set_surface(const std::string& name, const Grid& grid, int band) {
@@ -772,186 +703,179 @@ Status Pipeline::Impl::set_surface(const std::string& name, const Grid& grid, in
     return detail::store_surface(grid, band, geom, MemoryLocation::Device, stream, &surfaces[(size_t)index]);
 }
 
-Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
-    const size_t n = cloud.count();
-    if (n == 0) return Status::success();
-    DeviceScope dev(cfg.cuda_device_id);
-    // validate every predicate and reduction before touching state (pipeline_common.cpp: the reference's checks and messages)
-    if (!surfaces.empty()) {
-        Status ok = detail::validate_surfaces(cfg, cloud, surfaces);
-        if (!ok.ok()) return ok;
-    }
-    {
-        Status ok = detail::validate_cloud(cfg, cloud, PCR_HIP_MAX_FILTER_SET, PCR_HIP_MAX_FILTER_PREDICATES);
-        if (!ok.ok()) return ok;
-    }
-    detail::Reprojection rp;
-    {
-        Status ok = detail::plan_reprojection(cfg, cloud, &rp);
-        if (!ok.ok()) return ok;
-    }
+// ---- ingest: the steps, in the order ingest() takes them ---------------------------------------------------------------------
+// Device pointer of a named Float32 channel (Ingest::channel): a surface channel as sample_surfaces left it, a channel of the
+// cloud staged once; null for no name or no such channel (-> the GlyphSpec's default).
+Status Pipeline::Impl::channel_of(Ingest& in, const std::string& name, const float** out) {
+    *out = nullptr;
+    if (name.empty()) return Status::success();
+    auto hit = in.staged.find(name);
+    if (hit != in.staged.end()) { *out = hit->second; return Status::success(); }
+    const ChannelDesc* d = in.cloud.channel(name);
+    if (!d || d->dtype != DataType::Float32) return Status::success();
+    const void* p = nullptr;
+    Status st = device_array(in.cloud.channel_data(name), in.cloud.location(), in.n * sizeof(float), "ch:" + name, &p);
+    if (st.ok()) in.staged[name] = *out = static_cast<const float*>(p);
+    return st;
+}
 
-    const MemoryLocation loc = cloud.location();
-    const void *dx = nullptr, *dy = nullptr;
-    Status s = device_array(cloud.x(), loc, n * sizeof(double), "x", &dx);
-    if (!s.ok()) return s;
-    s = device_array(cloud.y(), loc, n * sizeof(double), "y", &dy);
-    if (!s.ok()) return s;
-    // A cloud in another CRS than the grid's: x, y transformed into a staging buffer of their own (the caller's device
-    // arrays are only read), which every kernel below reads instead
-    if (rp.needed) {
-        detail::Buffer& rb = staging["reproject:xy"];
-        if (rb.bytes() < 2 * n * sizeof(double)) {
-            // earlier kernels (chunks of ingest_async / ingest_file still in flight) may still read the old block
-            if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
-            if (!(s = rb.allocate(2 * (n + n / 8) * sizeof(double), MemoryLocation::Device)).ok()) return s;
-        }
-        const size_t cap = rb.bytes() / (2 * sizeof(double));
-        double* rx = static_cast<double*>(rb.data());
-        double* ry = rx + cap;
-        s = detail::hip_status(pcr_hip_transform_xy(&rp.src, &rp.dst, static_cast<const double*>(dx),
-                                                    static_cast<const double*>(dy), rx, ry, n, stream));
-        if (!s.ok()) return s;
-        dx = rx;
-        dy = ry;
-    }
+// x and y on the device.  A cloud in another CRS than the grid's: transformed into a staging buffer of their own (the caller's
+// device arrays are only read), which every kernel below reads instead.
+Status Pipeline::Impl::stage_xy(Ingest& in, const detail::Reprojection& rp) {
+    const MemoryLocation loc = in.cloud.location();
+    Status s = device_array(in.cloud.x(), loc, in.n * sizeof(double), "x", &in.dx);
+    if (s.ok()) s = device_array(in.cloud.y(), loc, in.n * sizeof(double), "y", &in.dy);
+    if (!s.ok() || !rp.needed) return s;
+    detail::Buffer* rb = nullptr;
+    if (!(s = staging_at_least("reproject:xy", 2 * in.n * sizeof(double), &rb)).ok()) return s;
+    double* rx = static_cast<double*>(rb->data());
+    double* ry = rx + rb->bytes() / (2 * sizeof(double));
+    s = detail::hip_status(pcr_hip_transform_xy(&rp.src, &rp.dst, static_cast<const double*>(in.dx),
+                                                static_cast<const double*>(in.dy), rx, ry, in.n, stream));
+    in.dx = rx;
+    in.dy = ry;
+    return s;
+}
 
-    std::map<std::string, const float*> staged;      // a channel is staged once per ingest, whoever asks first
-    const detail::ChannelLookup f32_channel = [&](const std::string& name, const float** out) -> Status {
-        *out = nullptr;
-        if (name.empty()) return Status::success();
-        auto hit = staged.find(name);                                         // (a surface channel is staged before any lookup)
-        if (hit != staged.end()) { *out = hit->second; return Status::success(); }
-        const ChannelDesc* d = cloud.channel(name);
-        if (!d || d->dtype != DataType::Float32) return Status::success();   // -> GlyphSpec default
-        const void* p = nullptr;
-        Status st = device_array(cloud.channel_data(name), loc, n * sizeof(float), "ch:" + name, &p);
-        if (st.ok()) staged[name] = *out = static_cast<const float*>(p);
-        return st;
-    };
-
-    // Surface channels: each gathered once, for all n points, from its band in HBM at the (reprojected) coordinates, into a
-    // staging buffer of its own that the lookup above then answers with -- the filters, the glyph marshalling, the Line reach
-    // check and every scatter below pick it up like a channel the cloud brought.  On the pipeline's stream, no host wait.
+// Surface channels: each gathered once, for all n points, from its band in HBM at the (reprojected) coordinates, into a
+// staging buffer of its own that the lookup then answers with -- the filters, the glyph marshalling, the Line reach check and
+// every scatter pick it up like a channel the cloud brought.  On the pipeline's stream, no host wait.
+Status Pipeline::Impl::sample_surfaces(Ingest& in) {
     for (size_t k = 0; k < surfaces.size(); ++k) {
         const SurfaceChannelConfig& sc = cfg.surface_channels[k];
         const float* dz = nullptr;
-        if (!(s = f32_channel(sc.value_channel, &dz)).ok()) return s;
-        detail::Buffer& sb = staging["surface:" + sc.name];
-        if (sb.bytes() < n * sizeof(float)) {
-            // earlier kernels (chunks of ingest_async / ingest_file still in flight) may still read the old block
-            if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
-            if (!(s = sb.allocate((n + n / 8) * sizeof(float), MemoryLocation::Device)).ok()) return s;
-        }
+        Status s = in.channel(sc.value_channel, &dz);
+        if (!s.ok()) return s;
+        detail::Buffer* sb = nullptr;
+        if (!(s = staging_at_least("surface:" + sc.name, in.n * sizeof(float), &sb)).ok()) return s;
         const detail::Surface& sf = surfaces[k];
         s = detail::hip_status(pcr_hip_sample_grid(&sf.geom, static_cast<const float*>(sf.band.data()), sf.geom.width,
-                                                   static_cast<const double*>(dx), static_cast<const double*>(dy), dz, n,
-                                                   (int)sc.mode, static_cast<float*>(sb.data()), stream));
+                                                   static_cast<const double*>(in.dx), static_cast<const double*>(in.dy), dz, in.n,
+                                                   (int)sc.mode, static_cast<float*>(sb->data()), stream));
         if (!s.ok()) return s;
-        staged[sc.name] = static_cast<const float*>(sb.data());
+        in.staged[sc.name] = static_cast<const float*>(sb->data());
     }
+    return Status::success();
+}
 
-    // Filter stage, on the device: a byte mask evaluated once per ingest and honoured by every
-    // routing kernel.  (The reference gathers values by filter index but routes the UNFILTERED
-    // cloud, pipeline.cpp:436-438 vs :662, which is why its own WithFilter test is disabled;
-    // here a filtered-out point simply does not exist for any reduction.)
-    size_t kept = n;
-    const uint8_t* active_mask = nullptr;
-    // ReductionSpec::filter: every group scatters under the mask of its class; class 0 is cfg.filter alone (active_mask)
-    std::vector<const uint8_t*> class_mask;
-    if (filters.any()) {
-        if (!(s = sweep_filter_classes(f32_channel, n, &class_mask, &kept)).ok()) return s;
-        if (kept == 0) return Status::success();                 // pipeline.cpp:349-353: cfg.filter keeps nothing
-        active_mask = class_mask[0];
-        pcr_hip_engine_set_point_mask(engine, active_mask);
-    } else if (!cfg.filter.empty()) {
-        std::vector<pcr_hip_predicate> preds;
-        if (!(s = detail::marshal_predicates(cfg.filter, f32_channel, &preds)).ok()) return s;
-        detail::Buffer& mb = staging["filter:mask"];
-        if (mb.bytes() < n + 8) {
-            if (!(s = detail::hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
-            if (!(s = mb.allocate(n + n / 8 + 16, MemoryLocation::Device)).ok()) return s;
-        }
-        if (!(s = detail::count_survivors(preds, n, mb.data(), stream, &kept)).ok()) return s;
-        if (kept == 0) return Status::success();             // pipeline.cpp:349-353
-        active_mask = detail::filter_mask_of(mb.data());
-        pcr_hip_engine_set_point_mask(engine, active_mask);
-    }
-    struct MaskGuard {
-        pcr_hip_engine* e;
-        ~MaskGuard() { pcr_hip_engine_set_point_mask(e, nullptr); }
-    } mask_guard{engine};
+// Filter stage, on the device: one byte mask per filter class, evaluated once per ingest (detail::sweep_filter_classes) and
+// honoured by every routing kernel.  Class 0 is PipelineConfig::filter alone; every group scatters under the mask of its
+// class.  (The reference gathers values by filter index but routes the UNFILTERED cloud, pipeline.cpp:436-438 vs :662,
+// which is why its own WithFilter test is disabled; here a filtered-out point simply does not exist for any reduction.)
+Status Pipeline::Impl::filter_stage(Ingest& in) {
+    detail::Buffer* mb = nullptr;
+    Status s = staging_at_least("filter:mask", detail::filter_stage_bytes(filters, in.n), &mb);
+    return s.ok() ? detail::sweep_filter_classes(filters, in.channel, in.n, mb->data(), stream, &in.class_mask, &in.kept) : s;
+}
 
-    // Row-block shards: every Line group's reach is checked BEFORE the first scatter of this ingest, so a refused
-    // cloud leaves no group half-accumulated (and, sharded, every rank can agree on the verdict first:
-    // Pipeline::line_reach_rows + pcr.distributed.ShardedPipeline.ingest).
+// Row-block shards: every Line group's reach is checked BEFORE the first scatter of this ingest, so a refused
+// cloud leaves no group half-accumulated (and, sharded, every rank can agree on the verdict first:
+// Pipeline::line_reach_rows + pcr.distributed.ShardedPipeline.ingest).
+Status Pipeline::Impl::check_line_reach(Ingest& in) {
     int reach_needed = 0;
     for (const auto& gr : groups) {
         if (gr.glyph.type != GlyphType::Line) continue;
         const float* hl = nullptr;
-        if (!(s = f32_channel(gr.glyph.half_length_channel, &hl)).ok()) return s;
+        Status s = in.channel(gr.glyph.half_length_channel, &hl);
+        if (!s.ok()) return s;
         int rows = 0;
-        if (!(s = line_reach_rows(gr.glyph, hl, filters.any() ? class_mask[(size_t)gr.cls] : active_mask, n, &rows)).ok()) return s;
+        if (!(s = line_reach_rows(gr.glyph, hl, in.class_mask[(size_t)gr.cls], in.n, &rows)).ok()) return s;
         reach_needed = std::max(reach_needed, rows);
     }
-    if (reach_needed > halo) return reach_error(reach_needed);
+    return reach_needed > halo ? reach_error(reach_needed) : Status::success();
+}
 
-    // (this cloud's points change the planes and the touched flags)
-    if (!(s = bands_stale()).ok()) return s;
-    // The touched flags are cfg.filter's survivors', whatever the groups' own filters keep.  An unfiltered group's scatter
-    // sets exactly those; when every group is filtered a pass of its own does, ahead of the first scatter.
-    bool flags_by_scatter = !filters.any();
-    for (const auto& gr : groups) flags_by_scatter = flags_by_scatter || gr.cls == 0;
-    if (!flags_by_scatter) {
-        s = detail::hip_status(pcr_hip_engine_touch(engine, static_cast<const double*>(dx), static_cast<const double*>(dy), n));
-        if (!s.ok()) return s;
-    }
+// One scatter per group, under the mask of its class.
+Status Pipeline::Impl::scatter_groups(Ingest& in) {
+    const double* dx = static_cast<const double*>(in.dx);
+    const double* dy = static_cast<const double*>(in.dy);
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         Group& gr = groups[gi];
         const float* dv = nullptr;
-        s = f32_channel(gr.value_channel, &dv);
+        Status s = in.channel(gr.value_channel, &dv);
         if (!s.ok()) return s;
-        if (filters.any()) pcr_hip_engine_set_point_mask(engine, class_mask[(size_t)gr.cls]);
+        pcr_hip_engine_set_point_mask(engine, in.class_mask[(size_t)gr.cls]);
         pcr_hip_engine_planes_fresh(engine, scatter_mode(gr));
         bool offered = false;
         if (gr.select) {                             // (Point glyph: validate_cloud refused anything else)
             const float* dk = nullptr;
-            if (!(s = f32_channel(gr.key_channel, &dk)).ok()) return s;
-            s = detail::hip_status(pcr_hip_scatter_select(
-                engine, static_cast<uint64_t*>(gr.packed.data()), static_cast<const double*>(dx), static_cast<const double*>(dy), dv, dk, n));
+            if (!(s = in.channel(gr.key_channel, &dk)).ok()) return s;
+            s = detail::hip_status(pcr_hip_scatter_select(engine, static_cast<uint64_t*>(gr.packed.data()), dx, dy, dv, dk, in.n));
         } else if (gr.glyph.type == GlyphType::Point) {
             offered = offer_bands(gi);
-            s = detail::hip_status(pcr_hip_scatter_point(
-                engine, gr.mask, &gr.view, static_cast<const double*>(dx), static_cast<const double*>(dy), dv, n));
+            s = detail::hip_status(pcr_hip_scatter_point(engine, gr.mask, &gr.view, dx, dy, dv, in.n));
         } else {
             pcr_hip_glyph hgph{};
-            if (!(s = marshal_glyph(gr.glyph, f32_channel, &hgph)).ok()) return s;
-            s = detail::hip_status(pcr_hip_scatter_glyph(
-                engine, &hgph, gr.mask & (PCR_HIP_PLANE_SUM | PCR_HIP_PLANE_WGT), &gr.view,
-                static_cast<const double*>(dx), static_cast<const double*>(dy), dv, n));
+            if (!(s = marshal_glyph(gr.glyph, in.channel, &hgph)).ok()) return s;
+            s = detail::hip_status(pcr_hip_scatter_glyph(engine, &hgph, gr.mask & (PCR_HIP_PLANE_SUM | PCR_HIP_PLANE_WGT), &gr.view,
+                                                         dx, dy, dv, in.n));
         }
         scatter_done(gr, offered, s.ok());
         if (!s.ok()) return s;
     }
-    // PipelineConfig::histograms: each cube counts the points its class keeps.  The touched flags it sets are among those the
-    // scatters (or the touch pass) above set already: no band a scatter stored goes stale, no plane is read or written.
+    return Status::success();
+}
+
+// PipelineConfig::histograms: each cube counts the points its class keeps.  The touched flags it sets are among those the
+// scatters (or the touch pass) set already: no band a scatter stored goes stale, no plane is read or written.
+Status Pipeline::Impl::scatter_histograms(Ingest& in) {
     for (size_t h = 0; h < hist.entries.size(); ++h) {
         const detail::HistogramEntry& e = hist.entries[h];
         const float* dv = nullptr;
-        if (!(s = f32_channel(e.value_channel, &dv)).ok()) return s;
-        pcr_hip_engine_set_point_mask(engine, filters.any() ? class_mask[(size_t)e.cls] : active_mask);
+        Status s = in.channel(e.value_channel, &dv);
+        if (!s.ok()) return s;
+        pcr_hip_engine_set_point_mask(engine, in.class_mask[(size_t)e.cls]);
         s = detail::hip_status(pcr_hip_scatter_histogram(engine, static_cast<uint32_t*>(cubes[h].data()), e.bins, e.lo, e.inv_w,
-                                                         static_cast<const double*>(dx), static_cast<const double*>(dy), dv, n));
+                                                         static_cast<const double*>(in.dx), static_cast<const double*>(in.dy), dv, in.n));
         if (!s.ok()) return s;
     }
+    return Status::success();
+}
+
+Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
+    Ingest in{cloud, cloud.count()};
+    if (in.n == 0) return Status::success();
+    DeviceScope dev(cfg.cuda_device_id);
+    // validate every predicate and reduction before touching state (pipeline_common.cpp: the reference's checks and messages)
+    Status s = surfaces.empty() ? Status::success() : detail::validate_surfaces(cfg, cloud, surfaces);
+    if (s.ok()) s = detail::validate_cloud(cfg, cloud, PCR_HIP_MAX_FILTER_SET, PCR_HIP_MAX_FILTER_PREDICATES);
+    detail::Reprojection rp;
+    if (s.ok()) s = detail::plan_reprojection(cfg, cloud, &rp);
+    if (!s.ok()) return s;
+    in.channel = [this, &in](const std::string& name, const float** out) { return channel_of(in, name, out); };
+
+    if (!(s = stage_xy(in, rp)).ok()) return s;
+    if (!(s = sample_surfaces(in)).ok()) return s;
+    if (!(s = filter_stage(in)).ok()) return s;
+    if (in.kept == 0) return Status::success();                  // pipeline.cpp:349-353: PipelineConfig::filter keeps nothing
+    pcr_hip_engine_set_point_mask(engine, in.class_mask[0]);
+    struct MaskGuard {
+        pcr_hip_engine* e;
+        ~MaskGuard() { pcr_hip_engine_set_point_mask(e, nullptr); }
+    } mask_guard{engine};
+    if (!(s = check_line_reach(in)).ok()) return s;
+
+    // (this cloud's points change the planes and the touched flags)
+    if (!(s = bands_stale()).ok()) return s;
+    // The touched flags are PipelineConfig::filter's survivors', whatever the groups' own filters keep.  An unfiltered group's
+    // scatter sets exactly those; when every group is filtered a pass of its own does, ahead of the first scatter.
+    bool flags_by_scatter = !filters.any();
+    for (const auto& gr : groups) flags_by_scatter = flags_by_scatter || gr.cls == 0;
+    if (!flags_by_scatter) {
+        s = detail::hip_status(pcr_hip_engine_touch(engine, static_cast<const double*>(in.dx), static_cast<const double*>(in.dy), in.n));
+        if (!s.ok()) return s;
+    }
+    if (!(s = scatter_groups(in)).ok()) return s;
+    if (!(s = scatter_histograms(in)).ok()) return s;
     // host arrays may be reused by the caller as soon as we return (ingest_async: page-locked arrays are
     // read by the DMA engine later, the caller keeps them alive until synchronize())
+    const MemoryLocation loc = cloud.location();
     if (loc != MemoryLocation::Device && (wait || loc != MemoryLocation::HostPinned)) {
         s = detail::hip_status(pcr_hip_stream_synchronize(stream));
         if (!s.ok()) return s;
     }
 
-    points += kept;                 // points_processed += filtered_count (pipeline.cpp:749)
+    points += in.kept;              // points_processed += filtered_count (pipeline.cpp:749)
     collections++;
     if (callback) {
         ProgressInfo info = stats();
@@ -1212,13 +1136,6 @@ Status Pipeline::Impl::import_window(const std::vector<std::vector<float>>& plan
     return s;
 }
 
-std::vector<detail::StateOutput> Pipeline::Impl::state_outputs() const {
-    std::vector<detail::StateOutput> o;
-    for (const auto& out : outputs)
-        if (out.group >= 0) o.push_back({out.group, out.type});
-    return o;
-}
-
 Status Pipeline::Impl::save_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     std::string dir;
@@ -1227,7 +1144,7 @@ Status Pipeline::Impl::save_state(const std::string& dir_in) {
     std::vector<std::vector<float>> planes;
     std::vector<uint32_t> touched;
     if (!(s = export_window(planes, touched)).ok()) return s;
-    return detail::write_state_tiles(cfg.grid, state_outputs(), state_window(planes), touched, dir);
+    return detail::write_state_tiles(cfg.grid, detail::state_outputs(outputs), state_window(planes), touched, dir);
 }
 
 Status Pipeline::Impl::load_state(const std::string& dir_in) {
@@ -1239,7 +1156,7 @@ Status Pipeline::Impl::load_state(const std::string& dir_in) {
     std::vector<uint32_t> touched;
     if (!(s = export_window(planes, touched)).ok()) return s;          // files overlay the current state
     size_t loaded = 0;
-    if (!(s = detail::read_state_tiles(cfg.grid, state_outputs(), state_window(planes), touched, dir, &loaded)).ok()) return s;
+    if (!(s = detail::read_state_tiles(cfg.grid, detail::state_outputs(outputs), state_window(planes), touched, dir, &loaded)).ok()) return s;
     if (!loaded) return Status::success();
     return import_window(planes, touched);                              // (drops bands a scatter stored, marks the planes defined)
 }

@@ -21,21 +21,14 @@
 namespace pcr {
 
 struct Pipeline::Impl {
-    struct Group {                       // one pass over the points
-        std::string value_channel;
-        GlyphSpec glyph;
-        uint32_t mask = 0;
+    struct Group : detail::GroupSpec {   // one pass over the points (detail::plan_groups) and what this engine keeps for it
         detail::Buffer planes[4];
         pcr_hip_planes view{};
-        // A MostRecent group (detail::is_select): its state on the device is ONE plane of packed 64-bit words (`packed`, 8 B per
+        // A MostRecent group (select): its state on the device is ONE plane of packed 64-bit words (`packed`, 8 B per
         // cell, include/pcr_hip.h "MostRecent").  mask names slots 0 / 1, the two float planes (value, timestamp) the state is
         // at the host-visible boundary: planes[0] / planes[1] only exist while a checkpoint, a parked band or a shard's
         // state_planes() needs that view (select_unpack / select_pack).
-        bool select = false;
-        std::string key_channel;
         detail::Buffer packed;
-        FilterSpec filter;               // ReductionSpec::filter of the group's specs (part of the grouping key)
-        int cls = 0;                     // its filter class (detail::FilterPlan): 0 = PipelineConfig::filter alone
         bool fresh = true;               // nothing has been accumulated yet: the first Point merge may store
         bool defined = false;            // the planes hold values (identity or accumulated).  They are NOT filled at create:
                                          // the first scatter defines them inside ingest, as the reference initialises its tile
@@ -51,12 +44,16 @@ struct Pipeline::Impl {
                                          // pipeline's alone to write: result() hands out a const Grid*, result_band_device() a
                                          // const float*.
     };
-    struct Output {                      // one band finalize makes from the state: a ReductionSpec's, or a percentile band
-        int group = 0;                   // -1: a percentile band of histogram `hist` (no group reads or writes it; its type is
-                                         // Max, so that the table fills it like a Max band)
-        ReductionType type = ReductionType::Sum;
-        std::string band_name;
-        int hist = -1, q = 0;            // the histogram and which of its percentiles
+    using Output = detail::Output;
+    // What the steps of one ingest share.
+    struct Ingest {
+        const PointCloud& cloud;
+        size_t n;
+        const void *dx = nullptr, *dy = nullptr;             // the coordinates every kernel reads (reprojected when need be)
+        std::map<std::string, const float*> staged;          // a channel is staged once per ingest, whoever asks first
+        detail::ChannelLookup channel;                       // Impl::channel_of over `staged`
+        std::vector<const uint8_t*> class_mask;              // the filter stage's masks, per class (detail::sweep_filter_classes)
+        size_t kept = 0;                                     // PipelineConfig::filter's survivors
     };
 
     // The pipeline's device is made current for the duration of a call that launches or allocates, whatever the
@@ -98,7 +95,7 @@ struct Pipeline::Impl {
     detail::GroundPlan ground;               // PipelineConfig::ground, planned at init
     detail::Buffer d_ground_work;            // its workspace, allocated by the first finalize, grow-only
     detail::TerrainPlan terrain;             // PipelineConfig::terrain, planned at init
-    detail::FilterPlan filters;              // ReductionSpec::filter of every spec, planned at init
+    detail::FilterPlan filters;              // PipelineConfig::filter (class 0) and every ReductionSpec::filter, planned at init
     detail::HistogramPlan hist;              // PipelineConfig::histograms, planned at init
     std::vector<detail::Buffer> cubes;       // entry by entry: count[bins][state_rows * width] in HBM, zeroed at create and only
                                              // ever added to: no part in the plane-state rules
@@ -110,7 +107,9 @@ struct Pipeline::Impl {
     bool state_shared = false;               // plane / touched-flag pointers have left the pipeline: never finalize with a scatter
     std::unique_ptr<Grid> result;
     bool finalized = false;                  // result() is null until the first finalize, as in the reference
-    std::map<std::string, detail::Buffer> staging;   // device copies of host-resident arrays, grow-only
+    std::map<std::string, detail::Buffer> staging;   // by name, grow-only (staging_at_least alone touches it): device copies of
+                                             // host-resident arrays, the reprojected x / y, the surface samples, the filter
+                                             // stage's masks, the Line-reach words
     int halo = 0;
     size_t collections = 0;
     size_t points = 0;
@@ -177,13 +176,20 @@ struct Pipeline::Impl {
     bool block_is_whole_tiles() const;
     Status line_reach_rows(const GlyphSpec& gl, const void* d_half_length, const uint8_t* d_mask, size_t n, int* rows_needed);
     Status reach_error(int rows) const;
+    Status staging_at_least(const std::string& key, size_t bytes, detail::Buffer** out);
     Status device_array(const void* src, MemoryLocation loc, size_t bytes, const std::string& key, const void** out);
-    Status sweep_filter_classes(const detail::ChannelLookup& channel, size_t n, std::vector<const uint8_t*>* masks, size_t* kept);
+    // ---- the steps of ingest(), in its order
+    Status channel_of(Ingest& in, const std::string& name, const float** out);
+    Status stage_xy(Ingest& in, const detail::Reprojection& rp);
+    Status sample_surfaces(Ingest& in);
+    Status filter_stage(Ingest& in);
+    Status check_line_reach(Ingest& in);
+    Status scatter_groups(Ingest& in);
+    Status scatter_histograms(Ingest& in);
     Status marshal_glyph(const GlyphSpec& gl, const detail::ChannelLookup& channel, pcr_hip_glyph* out) const;
     Status allocate_result();
     Status checkpoint_dir(const std::string& dir_in, std::string* dir, bool writing) const;
     detail::StateWindow state_window(std::vector<std::vector<float>>& planes) const;
-    std::vector<detail::StateOutput> state_outputs() const;
 };
 
 }  // namespace pcr

@@ -12,11 +12,6 @@
 
 namespace pcr {
 
-using detail::glyph_reduction_ok;
-using detail::planes_for;
-using detail::registered;
-using detail::same_glyph;
-
 Status Pipeline::Host::init() {
     const GridConfig& g = cfg.grid;
     if (g.width <= 0 || g.height <= 0)
@@ -39,45 +34,15 @@ Status Pipeline::Host::init() {
         surfaces.resize(cfg.surface_channels.size());
     }
     engine = std::make_unique<detail::HostEngine>(g, (int)cfg.cpu_threads);        // cpu_threads = 0: every core (pipeline.h:78)
-    for (size_t ri = 0; ri < cfg.reductions.size(); ++ri) {
-        const ReductionSpec& r = cfg.reductions[ri];
-        int gi = -1;
-        for (size_t k = 0; k < groups.size(); ++k)
-            if (groups[k].value_channel == r.value_channel && same_glyph(groups[k].glyph, r.glyph) &&
-                groups[k].select == detail::is_select(r.type) && (!groups[k].select || groups[k].key_channel == r.timestamp_channel) &&
-                detail::same_filter(groups[k].filter, r.filter))
-                gi = (int)k;                                         // (detail::same_group)
-        if (gi < 0) {
-            groups.emplace_back();
-            gi = (int)groups.size() - 1;
-            groups[(size_t)gi].value_channel = r.value_channel;
-            groups[(size_t)gi].glyph = r.glyph;
-            groups[(size_t)gi].select = detail::is_select(r.type);
-            if (groups[(size_t)gi].select) groups[(size_t)gi].key_channel = r.timestamp_channel;
-            groups[(size_t)gi].filter = r.filter;
-            groups[(size_t)gi].cls = filters.class_of[ri];
-        }
-        groups[(size_t)gi].mask |= planes_for(r.type);
-        Output o;
-        o.group = gi;
-        o.type = r.type;
-        o.band_name = detail::default_band_name(r);
-        outputs.push_back(o);
+    {
+        detail::GroupPlan plan = detail::plan_groups(cfg);
+        groups.resize(plan.groups.size());
+        for (size_t gi = 0; gi < groups.size(); ++gi) static_cast<detail::GroupSpec&>(groups[gi]) = plan.groups[gi];
+        outputs = std::move(plan.outputs);
     }
-    // PipelineConfig::histograms: the cubes, and one output per percentile band behind the reductions'
+    // PipelineConfig::histograms: the cubes
     hist = detail::plan_histograms(cfg, filters);
-    for (size_t h = 0; h < hist.entries.size(); ++h) {
-        cubes.emplace_back(hist.entries[h].cube_cells((size_t)g.width * g.height), 0u);
-        for (size_t j = 0; j < hist.entries[h].q.size(); ++j) {
-            Output o;
-            o.group = -1;
-            o.type = ReductionType::Max;
-            o.band_name = detail::histogram_band_name(cfg.histograms[h], j);
-            o.hist = (int)h;
-            o.q = (int)j;
-            outputs.push_back(o);
-        }
-    }
+    for (size_t h = 0; h < hist.entries.size(); ++h) cubes.emplace_back(hist.entries[h].cube_cells((size_t)g.width * g.height), 0u);
     // Tile state is identity-initialised (src/engine/tile_manager.cpp:183-260); here for the whole grid at once.
     for (auto& gr : groups) engine->init_planes(gr.planes, gr.mask, gr.select);
     return Status::success();
@@ -283,13 +248,6 @@ Status Pipeline::Host::finalize() {
     return Status::success();
 }
 
-std::vector<detail::StateOutput> Pipeline::Host::state_outputs() const {
-    std::vector<detail::StateOutput> o;
-    for (const auto& out : outputs)
-        if (out.group >= 0) o.push_back({out.group, out.type});
-    return o;
-}
-
 Status Pipeline::Host::save_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
@@ -298,7 +256,7 @@ Status Pipeline::Host::save_state(const std::string& dir_in) {
     w.row0 = 0;
     w.rows = cfg.grid.height;
     w.plane = [&](int g, int p) -> float* { auto& v = groups[(size_t)g].planes.plane[p]; return v.empty() ? nullptr : v.data(); };
-    return detail::write_state_tiles(cfg.grid, state_outputs(), w, engine->touched(), dir);
+    return detail::write_state_tiles(cfg.grid, detail::state_outputs(outputs), w, engine->touched(), dir);
 }
 
 Status Pipeline::Host::load_state(const std::string& dir_in) {
@@ -309,7 +267,7 @@ Status Pipeline::Host::load_state(const std::string& dir_in) {
     w.row0 = 0;
     w.rows = cfg.grid.height;
     w.plane = [&](int g, int p) -> float* { auto& v = groups[(size_t)g].planes.plane[p]; return v.empty() ? nullptr : v.data(); };
-    Status s = detail::read_state_tiles(cfg.grid, state_outputs(), w, engine->touched(), dir, nullptr);
+    Status s = detail::read_state_tiles(cfg.grid, detail::state_outputs(outputs), w, engine->touched(), dir, nullptr);
     for (auto& gr : groups) engine->normalize_select(gr.planes);     // a state read from a file is judged by the acceptance rule again
     return s;
 }

@@ -18,22 +18,10 @@
 namespace pcr {
 
 struct Pipeline::Host {
-    struct Group {                       // one pass over the points: same grouping as the HIP pipeline
-        std::string value_channel;
-        std::string key_channel;         // a MostRecent group: its timestamp channel
-        bool select = false;
-        GlyphSpec glyph;
+    struct Group : detail::GroupSpec {   // one pass over the points (detail::plan_groups) and its planes
         detail::HostPlanes planes;
-        uint32_t mask = 0;
-        FilterSpec filter;               // ReductionSpec::filter of the group's specs (part of the grouping key)
-        int cls = 0;                     // its filter class (detail::FilterPlan): 0 = PipelineConfig::filter alone
     };
-    struct Output {                      // one band finalize makes from the state: a ReductionSpec's, or a percentile band
-        int group = 0;                   // -1: a percentile band of histogram `hist` (its type is Max: filled like a Max band)
-        ReductionType type = ReductionType::Sum;
-        std::string band_name;
-        int hist = -1, q = 0;            // the histogram and which of its percentiles
-    };
+    using Output = detail::Output;
 
     PipelineConfig cfg;
     std::unique_ptr<detail::HostEngine> engine;
@@ -57,7 +45,6 @@ struct Pipeline::Host {
     Status save_state(const std::string& dir);
     Status load_state(const std::string& dir);
     ProgressInfo stats() const;
-    std::vector<detail::StateOutput> state_outputs() const;
 };
 
 }  // namespace pcr

@@ -1,4 +1,5 @@
-// pipeline_common.cpp -- what the engines behind pcr::Pipeline share: the cloud checks, `.pcrt` tile files of a window of state planes (see pipeline_common.h).
+// pipeline_common.cpp -- what the engines behind pcr::Pipeline share: the cloud checks, the filter plan and its sweep on the
+// device, the grouping plan, `.pcrt` tile files of a window of state planes (see pipeline_common.h).
 #include "pipeline_common.h"
 
 #include "buffer.h"
@@ -85,7 +86,6 @@ Status plan_filters(const PipelineConfig& cfg, FilterPlan* out) {
     };
     for (const auto& r : cfg.reductions) out->class_of.push_back(class_for(r.filter));
     for (const auto& h : cfg.histograms) out->hist_class_of.push_back(class_for(h.filter));   // (a histogram's filter is one more class)
-    if (!out->any()) { out->words.assign(1, 0u); return Status::success(); }
     if (out->classes.size() - 1 > kMaxSpecFilters)
         return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(kMaxSpecFilters) +
                                                           " distinct reduction filters in one pipeline");
@@ -106,9 +106,13 @@ Status plan_filters(const PipelineConfig& cfg, FilterPlan* out) {
         at[k] = at[0];
         for (const auto& pr : out->classes[k].predicates) at[k].push_back(place(pr));
     }
-    if (out->table.size() > PCR_HIP_MAX_CLASS_PREDICATES)
-        return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(PCR_HIP_MAX_CLASS_PREDICATES) +
-                                                          " distinct filter predicates in one pipeline");
+    if (out->table.size() > PCR_HIP_MAX_CLASS_PREDICATES) {
+        if (out->any())
+            return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(PCR_HIP_MAX_CLASS_PREDICATES) +
+                                                              " distinct filter predicates in one pipeline");
+        out->table.clear();                // PipelineConfig::filter alone: no bit for every predicate, no table, and no refusal here
+        return Status::success();
+    }
     for (const auto& list : at) {
         uint32_t w = 0;
         for (size_t t : list) w |= 1u << t;
@@ -132,15 +136,87 @@ Status marshal_predicates(const FilterSpec& filter, const ChannelLookup& channel
     return Status::success();
 }
 
-Status count_survivors(const std::vector<pcr_hip_predicate>& preds, size_t n, void* d_buffer, pcr_hip_stream stream, size_t* kept) {
-    auto* d_count = static_cast<unsigned long long*>(d_buffer);
-    Status s = hip_status(pcr_hip_filter_mask(preds.data(), (int)preds.size(), n, filter_mask_of(d_buffer), d_count, stream));
+namespace {
+constexpr size_t kSweepHeader = 128;                                   // the survivor counts, ahead of the masks
+size_t sweep_stride(size_t n) { return (n + 15) & ~(size_t)15; }
+// classes that get a mask: all of them, class 0 only when there is a PipelineConfig::filter
+size_t first_masked(const FilterPlan& plan) { return !plan.words.empty() && plan.words[0] ? 0 : 1; }
+}  // namespace
+
+size_t filter_stage_bytes(const FilterPlan& plan, size_t n) {
+    const size_t masked = plan.classes.size() - first_masked(plan);
+    return masked ? kSweepHeader + masked * sweep_stride(n) : 0;
+}
+
+Status sweep_filter_classes(const FilterPlan& plan, const ChannelLookup& channel, size_t n, void* d_buffer, pcr_hip_stream stream,
+                            std::vector<const uint8_t*>* masks, size_t* kept) {
+    const size_t first = first_masked(plan), n_cls = plan.classes.size(), stride = sweep_stride(n);
+    masks->assign(n_cls, nullptr);
+    *kept = n;
+    if (first == n_cls) return Status::success();
+    FilterSpec table;
+    table.predicates = plan.table;
+    std::vector<pcr_hip_predicate> preds;
+    Status s = marshal_predicates(table, channel, &preds);
     if (!s.ok()) return s;
+    uint8_t* const base = static_cast<uint8_t*>(d_buffer) + kSweepHeader;
+    auto* const d_counts = static_cast<unsigned long long*>(d_buffer);
+    for (size_t c = first; c < n_cls; c += PCR_HIP_MAX_FILTER_CLASSES) {
+        const int m = (int)std::min<size_t>(PCR_HIP_MAX_FILTER_CLASSES, n_cls - c);
+        s = hip_status(pcr_hip_filter_classes(preds.data(), (int)preds.size(), plan.words.data() + c, m, n, base + (c - first) * stride,
+                                              stride, c == 0 ? d_counts : nullptr, stream));
+        if (!s.ok()) return s;
+        for (int k = 0; k < m; ++k) (*masks)[c + (size_t)k] = base + (c - first + (size_t)k) * stride;
+    }
+    if (first != 0) return Status::success();
     unsigned long long h_count = 0;
-    if (!(s = hip_status(pcr_hip_memcpy_d2h(&h_count, d_count, sizeof h_count, stream))).ok()) return s;
+    if (!(s = hip_status(pcr_hip_memcpy_d2h(&h_count, d_counts, sizeof h_count, stream))).ok()) return s;
     if (!(s = hip_status(pcr_hip_stream_synchronize(stream))).ok()) return s;
     *kept = (size_t)h_count;
     return Status::success();
+}
+
+GroupPlan plan_groups(const PipelineConfig& cfg) {
+    GroupPlan plan;
+    FilterPlan filters;
+    (void)plan_filters(cfg, &filters);                  // (the classes are numbered whatever it refuses)
+    std::vector<const ReductionSpec*> first;
+    for (size_t ri = 0; ri < cfg.reductions.size(); ++ri) {
+        const ReductionSpec& r = cfg.reductions[ri];
+        int gi = -1;
+        for (size_t k = 0; k < first.size(); ++k)
+            if (same_group(*first[k], r)) gi = (int)k;
+        if (gi < 0) {
+            first.push_back(&r);
+            gi = (int)first.size() - 1;
+            GroupSpec gs;
+            gs.value_channel = r.value_channel;
+            gs.glyph = r.glyph;
+            gs.select = is_select(r.type);
+            if (gs.select) gs.key_channel = r.timestamp_channel;
+            gs.filter = r.filter;
+            gs.cls = filters.class_of[ri];
+            plan.groups.push_back(gs);
+        }
+        // (a glyph reduction of an unsupported type is refused at ingest, as in the reference: it still gets its planes)
+        plan.groups[(size_t)gi].mask |= planes_for(r.type);
+        Output o;
+        o.group = gi;
+        o.type = r.type;
+        o.band_name = default_band_name(r);
+        plan.outputs.push_back(o);
+    }
+    for (size_t h = 0; h < cfg.histograms.size(); ++h)
+        for (size_t j = 0; j < cfg.histograms[h].percentiles.size(); ++j) {
+            Output o;
+            o.group = -1;
+            o.type = ReductionType::Max;
+            o.band_name = histogram_band_name(cfg.histograms[h], j);
+            o.hist = (int)h;
+            o.q = (int)j;
+            plan.outputs.push_back(o);
+        }
+    return plan;
 }
 
 Status plan_reprojection(const PipelineConfig& cfg, const PointCloud& cloud, Reprojection* out) {
@@ -176,7 +252,7 @@ TileRect tile_rect(const GridConfig& g, const StateWindow& w, int tx, int ty) {
 }
 }  // namespace
 
-Status write_state_tiles(const GridConfig& g, const std::vector<StateOutput>& outputs, const StateWindow& w,
+Status write_state_tiles(const GridConfig& g, const std::vector<Output>& outputs, const StateWindow& w,
                          const std::vector<uint32_t>& touched, const std::string& dir, std::vector<std::string>* written) {
     const int tiles_x = (g.width + g.tile_width - 1) / g.tile_width;
     const int tiles_y = (g.height + g.tile_height - 1) / g.tile_height;
@@ -212,7 +288,7 @@ Status write_state_tiles(const GridConfig& g, const std::vector<StateOutput>& ou
     return Status::success();
 }
 
-Status read_state_tiles(const GridConfig& g, const std::vector<StateOutput>& outputs, const StateWindow& w,
+Status read_state_tiles(const GridConfig& g, const std::vector<Output>& outputs, const StateWindow& w,
                         std::vector<uint32_t>& touched, const std::string& dir, size_t* loaded) {
     const int tiles_x = (g.width + g.tile_width - 1) / g.tile_width;
     const int tiles_y = (g.height + g.tile_height - 1) / g.tile_height;

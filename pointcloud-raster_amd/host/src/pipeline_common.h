@@ -1,5 +1,6 @@
 // pipeline_common.h -- (internal) what the engines behind Pipeline share: which reductions exist, which planes they
-// need, how ReductionSpecs are grouped into passes over the points, and the `.pcrt` tile files of a state window.
+// need, the grouping plan (which ReductionSpecs share a pass over the points, which bands come out), the filter stage (its plan
+// and its one sweep on the device), and the `.pcrt` tile files of a state window.
 #pragma once
 
 #include "pcr/core/grid_config.h"
@@ -130,29 +131,6 @@ inline std::string histogram_band_name(const HistogramConfig& h, size_t j) {
     if (j < h.band_names.size() && !h.band_names[j].empty()) return h.band_names[j];
     return h.value_channel + "_p" + std::to_string(std::lround((double)h.percentiles[j] * 100.0));
 }
-// The bands finalize makes from the accumulated state, in the result grid's order: one per ReductionSpec, then the histograms'
-// percentile bands entry by entry.  What ground.source_band, ground.top_band and terrain[].source_band may name (the DTM, hag
-// and terrain bands follow them).
-inline std::vector<std::string> output_band_names(const PipelineConfig& cfg) {
-    std::vector<std::string> names;
-    for (const auto& r : cfg.reductions) names.push_back(default_band_name(r));
-    for (const auto& h : cfg.histograms)
-        for (size_t j = 0; j < h.percentiles.size(); ++j) names.push_back(histogram_band_name(h, j));
-    return names;
-}
-
-// One ReductionSpec as the checkpoint code sees it.
-struct StateOutput {
-    int group;
-    ReductionType type;
-};
-
-// ReductionSpecs -> accumulation groups (same value channel through the same glyph = one pass, one set of planes).
-struct Grouping {
-    std::vector<uint32_t> masks;             // per group: planes it keeps
-    std::vector<uint8_t> select;             // per group: a MostRecent group (planes 0 / 1 = value / timestamp)
-    std::vector<StateOutput> outputs;        // per ReductionSpec
-};
 // ReductionSpec::filter: equal means the same predicates in the same order, field by field.
 inline bool same_predicate(const FilterPredicate& a, const FilterPredicate& b) {
     return a.channel_name == b.channel_name && a.op == b.op && a.value == b.value && a.value_set == b.value_set;
@@ -163,25 +141,51 @@ inline bool same_filter(const FilterSpec& a, const FilterSpec& b) {
         if (!same_predicate(a.predicates[k], b.predicates[k])) return false;
     return true;
 }
-// A MostRecent spec is keyed by (value channel, timestamp channel) and never shares a group with the accumulations; specs
-// with different filters see different points and never share a group either.
+// The grouping key: ReductionSpecs that read the same value channel through the same glyph share one pass over the points and
+// one set of planes.  A MostRecent spec is keyed by its timestamp channel too and never shares a group with the accumulations;
+// specs with different filters see different points and never share a group either.
 inline bool same_group(const ReductionSpec& a, const ReductionSpec& b) {
     if (is_select(a.type) != is_select(b.type)) return false;
     if (is_select(a.type) && a.timestamp_channel != b.timestamp_channel) return false;
     return a.value_channel == b.value_channel && same_glyph(a.glyph, b.glyph) && same_filter(a.filter, b.filter);
 }
-inline Grouping group_reductions(const std::vector<ReductionSpec>& reductions) {
-    Grouping out;
-    std::vector<const ReductionSpec*> first;
-    for (const auto& r : reductions) {
-        int gi = -1;
-        for (size_t k = 0; k < first.size(); ++k)
-            if (same_group(*first[k], r)) gi = (int)k;
-        if (gi < 0) { first.push_back(&r); out.masks.push_back(0u); out.select.push_back(is_select(r.type) ? 1 : 0); gi = (int)first.size() - 1; }
-        out.masks[(size_t)gi] |= planes_for(r.type);
-        out.outputs.push_back({gi, r.type});
-    }
-    return out;
+
+// ---- the grouping plan: a configuration's accumulation groups and outputs, the same on every engine ------------------------
+struct GroupSpec {                       // one pass over the points, one set of planes
+    std::string value_channel;
+    GlyphSpec glyph;
+    bool select = false;                 // a MostRecent group (plane slots 0 / 1 = value / timestamp)
+    std::string key_channel;             // ... and its timestamp channel
+    FilterSpec filter;                   // ReductionSpec::filter of the group's specs
+    int cls = 0;                         // its filter class (FilterPlan): 0 = PipelineConfig::filter alone
+    uint32_t mask = 0;                   // kPlaneBits of the planes it keeps
+};
+struct Output {                          // one band finalize makes from the state: a ReductionSpec's, or a percentile band
+    int group = 0;                       // -1: a percentile band of histogram `hist` (no group reads or writes it; its type is
+                                         // Max, so that it is filled like a Max band)
+    ReductionType type = ReductionType::Sum;
+    std::string band_name;
+    int hist = -1, q = 0;                // the histogram and which of its percentiles
+};
+struct GroupPlan {
+    std::vector<GroupSpec> groups;       // in order of first appearance among the ReductionSpecs: reduction_groups(), state_planes(),
+                                         // parked windows (planes[4 g + p]) and the `.pcrt` directories all count them this way
+    std::vector<Output> outputs;         // the result grid's order: one per ReductionSpec, then the histograms' percentile bands entry
+                                         // by entry.  What ground.source_band, ground.top_band and terrain[].source_band may name
+                                         // (the DTM, hag and terrain bands follow them)
+};
+GroupPlan plan_groups(const PipelineConfig& cfg);
+// The outputs a checkpoint carries (write_state_tiles, read_state_tiles): those with a group.
+inline std::vector<Output> state_outputs(const std::vector<Output>& outputs) {
+    std::vector<Output> o;
+    for (const auto& out : outputs)
+        if (out.group >= 0) o.push_back(out);
+    return o;
+}
+inline std::vector<std::string> output_band_names(const PipelineConfig& cfg) {
+    std::vector<std::string> names;
+    for (const auto& o : plan_groups(cfg).outputs) names.push_back(o.band_name);
+    return names;
 }
 
 // Host copies of state planes over the row WINDOW [row0, row0 + rows) of the grid (whole tile rows for everything below):
@@ -215,17 +219,7 @@ inline pcr_hip_grid to_hip_grid(const GridConfig& g) {
     return hg;
 }
 
-// ---- the filter stage on the device (pcr_hip_filter_mask) ----------------------------------------------------------------
-/// Device pointer of a named Float32 channel of the cloud being ingested (null: the cloud has no such channel).
-using ChannelLookup = std::function<Status(const std::string& name, const float** d_channel)>;
-/// The FilterSpec as the C-ABI takes it, its channels resolved through `channel` in the predicates' order.
-Status marshal_predicates(const FilterSpec& filter, const ChannelLookup& channel, std::vector<pcr_hip_predicate>* out);
-/// Evaluates the predicates over n points into d_buffer, laid out [u64 survivor count][n mask bytes] (at least n + 8 bytes of
-/// device memory), waits for the stream and returns the count.  The mask starts at filter_mask_of(d_buffer).
-Status count_survivors(const std::vector<pcr_hip_predicate>& preds, size_t n, void* d_buffer, pcr_hip_stream stream, size_t* kept);
-inline uint8_t* filter_mask_of(void* d_buffer) { return static_cast<uint8_t*>(d_buffer) + 8; }
-
-// ---- per-reduction filters (ReductionSpec::filter), planned at create on every engine ----------------------------------------
+// ---- the filter stage, planned at create on every engine --------------------------------------------------------------------
 // Class 0 is PipelineConfig::filter alone (the specs with an empty filter); class k >= 1 is the k-th distinct non-empty spec
 // filter in order of first appearance.  A point contributes to a spec when it passes PipelineConfig::filter AND the spec's
 // class: words[k] is that conjunction as bits of `table`, the distinct predicates of the whole configuration.
@@ -235,13 +229,29 @@ struct FilterPlan {
     std::vector<int> class_of;               // per ReductionSpec
     std::vector<int> hist_class_of;          // per entry of PipelineConfig::histograms: its filter joins the same plan
     std::vector<FilterPredicate> table;      // PipelineConfig::filter's predicates first
-    std::vector<uint32_t> words;             // per class
+    std::vector<uint32_t> words;             // per class; words[0] == 0: no PipelineConfig::filter
     bool any() const { return classes.size() > 1; }
 };
 /// InvalidArgument, with the same message on every engine, for more than kMaxSpecFilters distinct non-empty spec filters, a
 /// conjunction longer than PCR_HIP_MAX_FILTER_PREDICATES, or more than PCR_HIP_MAX_CLASS_PREDICATES distinct predicates.  A
-/// configuration without spec filters is planned as it always was: one class, nothing refused here.
+/// configuration without spec filters is refused nothing: a PipelineConfig::filter of more distinct predicates than the table
+/// holds gets no table and no words (the host engine reads `classes` alone; validate_cloud refuses it on the device, at ingest).
 Status plan_filters(const PipelineConfig& cfg, FilterPlan* out);
+
+// ---- the filter stage on the device (pcr_hip_filter_classes) ---------------------------------------------------------------
+/// Device pointer of a named Float32 channel of the cloud being ingested (null: the cloud has no such channel).
+using ChannelLookup = std::function<Status(const std::string& name, const float** d_channel)>;
+/// The FilterSpec as the C-ABI takes it, its channels resolved through `channel` in the predicates' order.
+Status marshal_predicates(const FilterSpec& filter, const ChannelLookup& channel, std::vector<pcr_hip_predicate>* out);
+/// Device memory the stage needs for n points, laid out [128 B: u64 survivor counts][class masks, each a multiple of 16 bytes
+/// apart; no mask for class 0 without a PipelineConfig::filter].  0: the plan filters nothing.
+size_t filter_stage_bytes(const FilterPlan& plan, size_t n);
+/// ONE sweep over the points (pcr_hip_filter_classes; eight classes per call, so nine masks take a second one) makes the mask of
+/// every class of the plan in d_buffer.  (*masks)[k]: class k's mask; null for class 0 when there is no PipelineConfig::filter
+/// (every point is kept).  *kept: PipelineConfig::filter's survivors, read back with one host wait -- only when there is such a
+/// filter; without one the sweep is enqueued and nothing waited for.  A plan that filters nothing launches nothing.
+Status sweep_filter_classes(const FilterPlan& plan, const ChannelLookup& channel, size_t n, void* d_buffer, pcr_hip_stream stream,
+                            std::vector<const uint8_t*>* masks, size_t* kept);
 
 // ---- reprojection on ingest (PipelineConfig::target_crs / auto_reproject; pcr/core/reproject.h) ---------------------------
 /// CRS -> the C-ABI's descriptor; CrsError when it is unidentified or not supported.  role: "source" / "destination".
@@ -270,12 +280,12 @@ std::string reduction_state_dir(const std::string& dir, size_t r, size_t n_outpu
 Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t max_set, size_t max_predicates);
 /// One `.pcrt` file per touched reference tile inside the window and per output (src/io/tile_state_io.cpp:45-95;
 /// file name src/io/tile_state_io.cpp:197-211).  touched: tiles_x * tiles_y flags of the whole grid.
-Status write_state_tiles(const GridConfig& g, const std::vector<StateOutput>& outputs, const StateWindow& w,
+Status write_state_tiles(const GridConfig& g, const std::vector<Output>& outputs, const StateWindow& w,
                          const std::vector<uint32_t>& touched, const std::string& dir, std::vector<std::string>* written = nullptr);
 /// The reverse: every matching file inside the window is copied into the planes and its tile marked touched; files that do
 /// not describe their tile of their reduction are ignored like the reference's tile manager ignores them
 /// (src/engine/tile_manager.cpp:272-320).  *loaded = files taken.
-Status read_state_tiles(const GridConfig& g, const std::vector<StateOutput>& outputs, const StateWindow& w,
+Status read_state_tiles(const GridConfig& g, const std::vector<Output>& outputs, const StateWindow& w,
                         std::vector<uint32_t>& touched, const std::string& dir, size_t* loaded);
 
 }  // namespace detail

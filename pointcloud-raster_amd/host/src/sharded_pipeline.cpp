@@ -210,16 +210,18 @@ Status ShardedPipeline::save_state(const std::string& dir_in) {
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     void* stream = pipe_->stream_handle();
     const std::vector<Pipeline::PlaneView> views = pipe_->state_planes();
-    const detail::Grouping grouping = detail::group_reductions(reductions_);
+    PipelineConfig grouped;                    // (the grouping reads the reductions alone)
+    grouped.reductions = reductions_;
+    const detail::GroupPlan plan = detail::plan_groups(grouped);
     const uint64_t strip = (uint64_t)(r1_ - r0_) * (uint64_t)width_, whole = (uint64_t)height_ * (uint64_t)width_;
     const bool root = rank_ == 0;
-    std::vector<std::vector<float>> planes(grouping.masks.size() * 4);
+    std::vector<std::vector<float>> planes(plan.groups.size() * 4);
     detail::Buffer landing;
     Status local = root ? landing.allocate((size_t)whole * sizeof(float), MemoryLocation::Device) : Status::success();
     for (const auto& v : views) {
         int p = 0;
         while (p < 4 && detail::kPlaneBits[p] != (uint32_t)v.plane_kind) ++p;
-        if (p == 4 || v.group < 0 || (size_t)v.group >= grouping.masks.size())
+        if (p == 4 || v.group < 0 || (size_t)v.group >= plan.groups.size())
             return Status::error(StatusCode::InvalidArgument, "ShardedPipeline::save_state: unknown plane");
         const void* send[1] = {static_cast<const float*>(v.device_ptr) + (size_t)(r0_ - pipe_->state_row_begin()) * (size_t)width_};
         void* recv[1] = {root && local.ok() ? landing.data() : nullptr};
@@ -247,7 +249,7 @@ Status ShardedPipeline::save_state(const std::string& dir_in) {
         auto& v = planes[(size_t)g * 4 + (size_t)p];
         return v.empty() ? nullptr : v.data();
     };
-    return detail::write_state_tiles(grid_, grouping.outputs, w, touched, dir);
+    return detail::write_state_tiles(grid_, plan.outputs, w, touched, dir);
 }
 
 Status ShardedPipeline::gather(int dst_rank, std::unique_ptr<Grid>* out) {

@@ -250,12 +250,82 @@ def run_case(mode, specs, cfg_filt, n, seed, g=GRID, **kw):
     return p, model, c
 
 
-def check_mixed(mode, n, **kw):
-    p, model, _ = run_case(mode, MIXED, (), n, 100 + n, **kw)
+def check_mixed(mode, n, tmp_path=None, **kw):
+    p, model, c = run_case(mode, MIXED, (), n, 100 + n, **kw)
     if mode == "gpu":
         assert list(p.reduction_groups()) == MIXED_GROUPS
     assert_model(p, model, f"mixed pipeline, {n} points, {mode}")
+    if mode == "gpu" and tmp_path is not None:
+        # The grouping plan is one: a checkpoint the out-of-core driver writes from its parked planes (planes[4 g + p], two
+        # bands under this budget: test_gpu_reduction_filters.py::test_out_of_core_row_bands) is the in-core pipeline's own
+        ck = str(tmp_path / "ck")
+        banded = create(mode, MIXED, (), gpu_memory_budget=60000, host_cache_budget=1 << 20, state_dir=str(tmp_path), **kw)
+        assert banded.out_of_core()
+        banded.ingest(make_cloud(c, "cpu"))
+        banded.save_state(ck)
+        q = create(mode, MIXED, (), state_dir=ck, resume=True, **kw)
+        assert not q.out_of_core()
+        q.finalize()
+        for b, (u, w) in enumerate(zip(bands(q), bands(p))):
+            assert_bits(u, w, f"band {b}: saved out of core, loaded in core, against the in-core pipeline, {n} points")
     return p
+
+
+# PipelineConfig.filter alone: class 0 of the plan through the same sweep, at the sizes where that kernel changes shape (below,
+# at and past one 4-point group, one 64-lane wave, one 256-thread workgroup plus a tail).
+CFG_ONLY_SPECS = [S("Sum"), S("Count"), S("Min"), S("MostRecent")]
+CFG_ONLY_SIZES = (1, 3, 4, 5, 63, 64, 65, 259, 1027)
+CFG_ONLY_NONE = [("ret", "Greater", 7.0)]
+CFG_ONLY_PREDS = {
+    "one": [("ret", "LessEqual", 2.0)],
+    "the same twice": [("ret", "LessEqual", 2.0), ("ret", "LessEqual", 2.0)],                       # (the table collapses it)
+    "five channels": [("a", "GreaterEqual", -6.0), ("t", "Less", 5.0), ("cls", "NotEqual", 6.0), ("ret", "LessEqual", 2.0),
+                      ("q", "GreaterEqual", 2.0)],                                                  # (a NaN in q fails)
+    "sixteen": [("a", "NotEqual", k / 8.0) for k in range(12)] + [("t", "NotEqual", 0.0), ("ret", "LessEqual", 2.0),
+                                                                  ("cls", "NotEqual", 1.0), ("q", "NotInSet", [1.0])],
+    "none": CFG_ONLY_NONE,
+}
+SEVENTEEN = CFG_ONLY_PREDS["sixteen"] + [("t", "NotEqual", 1.0)]
+
+
+def cfg_only_points(n):
+    return make_points(n, 600 + n)
+
+
+def check_cfg_filter_only(mode, n, preds, resident="device", **kw):
+    c = cfg_only_points(n)
+    model = Model(CFG_ONLY_SPECS, preds)
+    p = create(mode, CFG_ONLY_SPECS, preds, **kw)
+    p.ingest(make_cloud(c, mode if resident == "device" else "cpu"))
+    p.finalize()
+    model.ingest(c)
+    what = f"cfg.filter alone ({len(preds)} predicates), {n} points, {mode}, {resident}-resident cloud"
+    assert_model(p, model, what)
+    assert p.stats().points_processed == model.survivors == int(conj_mask(c, preds).sum()), what
+    if preds is CFG_ONLY_NONE:                                   # a successful no-op
+        assert (p.stats().points_processed, p.stats().collections_processed) == (0, 0), what
+        assert all(np.isnan(b).all() for b in bands(p)), what
+    return p
+
+
+def check_cfg_filter_too_long(mode):
+    """17 predicates in PipelineConfig.filter: create refuses nothing; the device refuses the cloud at ingest, before any state
+    changes (the host engine has no such limit and ingests it)."""
+    import pytest
+    c = cfg_only_points(259)
+    p = create(mode, CFG_ONLY_SPECS, SEVENTEEN)
+    if mode == "cpu":
+        p.ingest(make_cloud(c, mode))
+        p.finalize()
+        model = Model(CFG_ONLY_SPECS, SEVENTEEN)
+        model.ingest(c)
+        assert_model(p, model, "17 predicates on the host engine")
+        return
+    with pytest.raises(RuntimeError, match="filter_points: more than 16 predicates"):
+        p.ingest(make_cloud(c, mode))
+    assert (p.stats().points_processed, p.stats().collections_processed) == (0, 0)
+    p.finalize()
+    assert all(np.isnan(b).all() for b in bands(p))
 
 
 def check_all_filtered(mode, n, **kw):

@@ -17,9 +17,21 @@ PATHS = pytest.mark.parametrize("path", [1, 2], ids=["direct", "binned"])
 
 @PATHS
 @pytest.mark.parametrize("n", RF.SIZES)
-def test_mixed_pipeline(n, path):
-    p = RF.check_mixed("gpu", n, scatter_path=path)
+def test_mixed_pipeline(n, path, tmp_path):
+    p = RF.check_mixed("gpu", n, tmp_path=tmp_path, scatter_path=path)
     assert p.last_scatter()["path"] == ("direct" if path == 1 else "binned")
+
+
+@PATHS
+@pytest.mark.parametrize("n", RF.CFG_ONLY_SIZES)
+def test_a_pipeline_filter_alone(n, path):
+    for preds in RF.CFG_ONLY_PREDS.values():
+        for resident in ("device", "host"):
+            RF.check_cfg_filter_only("gpu", n, preds, resident=resident, scatter_path=path)
+
+
+def test_a_pipeline_filter_of_17_predicates():
+    RF.check_cfg_filter_too_long("gpu")
 
 
 @pytest.mark.parametrize("n", RF.SIZES)

@@ -44,6 +44,33 @@ def test_with_a_pipeline_filter_as_well(n):
     RF.check_with_cfg_filter("cpu", n)
 
 
+@pytest.mark.parametrize("name", list(RF.CFG_ONLY_PREDS))
+@pytest.mark.parametrize("n", RF.CFG_ONLY_SIZES)
+def test_a_pipeline_filter_alone(n, name):
+    RF.check_cfg_filter_only("cpu", n, RF.CFG_ONLY_PREDS[name])
+
+
+def test_no_case_of_a_pipeline_filter_alone_passes_vacuously():
+    for n in RF.CFG_ONLY_SIZES:
+        c = RF.cfg_only_points(n)
+        inside = RF.cells_of(RF.GRID, c["x"], c["y"]) >= 0
+        for name, preds in RF.CFG_ONLY_PREDS.items():
+            keep = RF.conj_mask(c, preds)
+            if name == "none":
+                assert not keep.any()
+            elif n >= 63:
+                assert (keep & inside).any() and not keep.all(), f"{name}, {n} points"
+    c = RF.cfg_only_points(259)
+    assert (RF.conj_mask(c, RF.SEVENTEEN) & (RF.cells_of(RF.GRID, c["x"], c["y"]) >= 0)).any()
+    assert len({p[:2] + (str(p[2]),) for p in RF.CFG_ONLY_PREDS["sixteen"]}) == 16 and len(RF.SEVENTEEN) == 17
+    assert {p[0] for p in RF.CFG_ONLY_PREDS["five channels"]} == set(RF.CHANNELS)
+    assert np.isnan(RF.cfg_only_points(63)["q"]).any()
+
+
+def test_a_pipeline_filter_of_17_predicates():
+    RF.check_cfg_filter_too_long("cpu")
+
+
 def test_predicate_edge_cases():
     RF.check_predicate_edges("cpu")
 
