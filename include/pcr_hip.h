@@ -720,6 +720,50 @@ int pcr_hip_histogram_percentiles(const pcr_hip_grid* g, const uint32_t* d_count
 int pcr_hip_histogram_percentiles_host(const pcr_hip_grid* g, const uint32_t* h_counts, int bins, double lo, double w, int n_q,
                                        const float* q, float* const* h_outs);
 
+/* ---- per-cell extremes: the k lowest (or highest) distinct values of a cell, a mergeable piece of state beside the
+ *      reductions (PipelineConfig::extremes), from which an outlier-free Min or Max band comes.  No reference counterpart.
+ *      "The k smallest distinct keys" is a set: the same bits on both engines and both device paths, for any order,
+ *      chunking or number of scatters, with no tolerance anywhere.  The arithmetic is written once, in csrc/extremes.hpp,
+ *      which the kernels, the host twin and the host engine compile with contraction off.
+ *        accepted   as for the histograms: a point is accepted when it is routed to a cell by the rule of the Point glyph
+ *                   (inclusive bounds, the floor of the true binary64 quotient, clamp; the owned rows of the engine's grid),
+ *                   is kept by the point mask (pcr_hip_engine_set_point_mask), and its value is not NaN.  +-Inf are values.
+ *        key        the bits of v, -0.0 folded to +0.0 on the bits, then ord(b) = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000)
+ *                   for LOWEST, ~ord(b) for HIGHEST: the smaller the key the more extreme the value.  Every real value's key
+ *                   lies in [0x007FFFFF, 0xFF800000] on either side; EMPTY = 0xFFFFFFFF is above all of them.
+ *        state      k planes of uint32 keys in the state window's layout ([k][state_rows * width]), which the caller sets
+ *                   to EMPTY once (a byte fill with 0xFF).  After any sequence of scatters plane j of a cell holds the
+ *                   (j+1)-th smallest DISTINCT key among the cell's accepted points, or EMPTY.  Distinct values, not
+ *                   points: that makes the state a set, hence order-independent; two noise returns at one height count
+ *                   as one level.
+ *        band       per cell of the owned rows, with n the number of filled slots and v[i] the decoded floats: NaN
+ *                   (0x7FC00000) where n == 0 -- the touched-tile flags play no part.  Else start at i = 0 and advance
+ *                   while i + 1 < n and d > max_gap, d being ONE binary32 subtraction, v[i+1] - v[i] for LOWEST and
+ *                   v[i] - v[i+1] for HIGHEST (distinct keys: never NaN); the band is v[i].  max_gap = +Inf gives the plain
+ *                   Min or Max.  A cell whose k kept values are all more than max_gap apart yields the k-th.
+ *      scatter_extremes honours pcr_hip_engine_set_point_mask and pcr_hip_engine_set_path: 1 direct -- a displacement
+ *      chain of returning 32-bit global atomic minima (at slot j, old = min-exchange of the carried key; stop on a
+ *      duplicate; carry the larger of the two on), behind one read of slot k-1 that ends every key that cannot enter;
+ *      2 binned -- the Point front end on 8-byte records whose value slot carries the key, the chain on LDS tiles of
+ *      128 x h cells x k planes, merged into the state with plain reads and writes where a tile has one owner; 0 the binned
+ *      path where it applies, else the direct one.  It sets the touched flags of the tiles its points are routed to and
+ *      reports through pcr_hip_engine_stats like pcr_hip_scatter_point.
+ *      extremes_band writes the band (own rows x width floats) in one launch on s and, when d_values is not null, the k
+ *      decoded planes behind each other ([k][own rows * width] floats, NaN for an empty slot: ascending for LOWEST,
+ *      descending for HIGHEST).  _host: the same lines on host arrays, one thread.
+ *      Argument errors -- a null pointer, k outside 2..8, an unknown side, a negative or NaN max_gap -- are reported
+ *      before any HIP call. */
+#define PCR_HIP_EXTREMES_MIN_K 2
+#define PCR_HIP_EXTREMES_MAX_K 8
+#define PCR_HIP_EXTREMES_LOWEST 0
+#define PCR_HIP_EXTREMES_HIGHEST 1
+int pcr_hip_scatter_extremes(pcr_hip_engine* e, uint32_t* d_keys, int k, int side, const double* d_x, const double* d_y,
+                             const float* d_value, uint64_t n);
+int pcr_hip_extremes_band(const pcr_hip_grid* g, const uint32_t* d_keys, int k, int side, float max_gap, float* d_out,
+                          float* d_values, pcr_hip_stream s);
+int pcr_hip_extremes_band_host(const pcr_hip_grid* g, const uint32_t* h_keys, int k, int side, float max_gap, float* h_out,
+                               float* h_values);
+
 #ifdef __cplusplus
 }
 #endif

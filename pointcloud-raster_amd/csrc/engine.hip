@@ -510,6 +510,37 @@ int pcr_hip_scatter_histogram(pcr_hip_engine* e, uint32_t* d_counts, int bins, d
     return rc;
 }
 
+int pcr_hip_scatter_extremes(pcr_hip_engine* e, uint32_t* d_keys, int k, int side, const double* d_x, const double* d_y,
+                             const float* d_value, uint64_t n) {
+    PCR_REQUIRE(e, "scatter_extremes: null engine");
+    e->fused_outs.n = 0;                                  // (a pending finalize-with-scatter hint does not apply here)
+    e->fused_done = nullptr;
+    e->fused_taken = false;
+    e->defer_planes = e->deferred_taken = 0;
+    e->planes_fresh = 0;                                  // (the key planes are all-empty at create and only ever lowered)
+    PCR_REQUIRE(d_keys, "scatter_extremes: null key planes");
+    PCR_REQUIRE(k >= PCR_HIP_EXTREMES_MIN_K && k <= PCR_HIP_EXTREMES_MAX_K, "scatter_extremes: k must be between 2 and 8");
+    PCR_REQUIRE(side == PCR_HIP_EXTREMES_LOWEST || side == PCR_HIP_EXTREMES_HIGHEST, "scatter_extremes: side must be 0 (lowest) or 1 (highest)");
+    if (n == 0) return PCR_HIP_OK;                       // empty cloud is a no-op, as for pcr_hip_scatter_point
+    PCR_REQUIRE(n < ((uint64_t)1 << 40), "scatter_extremes: too many points in one call");
+    PCR_REQUIRE(d_x && d_y && d_value, "scatter_extremes: null point array");
+    DeviceGuard dev(e->device);
+    int rc = begin_scatter(e, n);
+    if (rc) return rc;
+    const bool can_bin = binned_extremes_supported(e, k);
+    if (e->forced_path == 2 && !can_bin)
+        return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_extremes: binned path forced but not applicable to this grid");
+    if (e->forced_path == 1 || !can_bin) {
+        if ((rc = zero_counters(e)) != PCR_HIP_OK) return rc;
+        return direct_extremes(e, d_keys, k, side, d_x, d_y, d_value, n);
+    }
+    if ((rc = begin_published(e)) != PCR_HIP_OK) return rc;
+    rc = binned_extremes(e, d_keys, k, side, d_x, d_y, d_value, n);
+    e->publish_counters = false;
+    release_scratch(e);
+    return rc;
+}
+
 int pcr_hip_scatter_glyph(pcr_hip_engine* e, const pcr_hip_glyph* glyph, uint32_t plane_mask,
                           const pcr_hip_planes* planes,
                           const double* d_x, const double* d_y, const float* d_value, uint64_t n) {

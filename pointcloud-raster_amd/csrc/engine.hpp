@@ -63,7 +63,8 @@ struct pcr_hip_engine {
 
     // pcr_hip_scatter_histogram, binned path (histogram.hip): the points' bin words, grow-only, the engine's own (the scratch
     // arena is carved anew by every pass of a sweep), and S, the bin planes an LDS tile holds (PCR_HIP_DEBUG_HIST_SLAB: 8, 16
-    // or 32, for the measurement that chose the default)
+    // or 32, for the measurement that chose the default).  pcr_hip_scatter_extremes (extremes.hip) keeps its key words in the
+    // same buffer: one scatter is in the making at a time, and the stream orders their uses.
     uint32_t* d_hist_words = nullptr;
     size_t hist_words_cap = 0;                 // words
     int hist_slab = 16;                        // chosen by measurement: profiles/histogram.md
@@ -229,6 +230,13 @@ int direct_hist(pcr_hip_engine* e, uint32_t* counts, int bins, double lo, double
 bool binned_hist_supported(const pcr_hip_engine* e);
 int binned_hist(pcr_hip_engine* e, uint32_t* counts, int bins, double lo, double inv_w, const double* x, const double* y,
                 const float* v, uint64_t n);
+
+// Per-cell extremes (pcr_hip_scatter_extremes): k planes keys[k][state window] of uint32, extremes.hip.  direct: the
+// displacement chain with returning global atomics; binned: VALUE records {local cell, key} through the Point front end
+// (sweep_tiles), the key words in d_hist_words.
+int direct_extremes(pcr_hip_engine* e, uint32_t* keys, int k, int side, const double* x, const double* y, const float* v, uint64_t n);
+bool binned_extremes_supported(const pcr_hip_engine* e, int k);
+int binned_extremes(pcr_hip_engine* e, uint32_t* keys, int k, int side, const double* x, const double* y, const float* v, uint64_t n);
 
 // Gaussian cell tiles on 16-byte value records (default-sigma, unrotated, r <= 3), scatter_cells.hip
 bool cells_gauss_supported(const pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask);

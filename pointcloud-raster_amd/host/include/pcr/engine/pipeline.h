@@ -103,6 +103,34 @@ struct HistogramConfig {
     std::vector<std::string> band_names; // default "{value_channel}_p{round(q*100)}", e.g. "hag_p95"
 };
 
+/// Which end of a cell's values an ExtremesConfig keeps.
+enum class ExtremeSide : int { Lowest = 0, Highest = 1 };
+
+/// One entry of PipelineConfig::extremes: the k lowest (or highest) DISTINCT values of one channel per cell, kept at ingest
+/// beside the reductions, and the outlier-free Min (Max) band finalize() walks out of them -- what PDAL's filters.elm
+/// (extended local minimum) does ahead of a ground filter, as a band.  The contract (include/pcr_hip.h, "per-cell extremes"):
+///   accepted   exactly the histograms' rule: routed to a cell by the rule of the Point glyph (after reprojection and surface
+///              channels), kept by PipelineConfig::filter AND by `filter`, value not NaN.  +-Inf are values.
+///   key        the bits of v, -0.0 folded to +0.0 on the bits, then ord() (the MostRecent fold's order-preserving map) for
+///              Lowest, ~ord() for Highest.  Every real value's key lies in [0x007FFFFF, 0xFF800000]; EMPTY = 0xFFFFFFFF.
+///   state      k planes of uint32 keys in the state window's layout, all EMPTY at create; plane j of a cell holds the (j+1)-th
+///              smallest distinct key among the cell's accepted points, or EMPTY.  Distinct values, not points: the state is
+///              a set, hence order-independent, and two noise returns at one height count as one level.
+///   band       with n filled slots and v[i] the decoded floats: NaN where n == 0 (touched-tile flags play no part); else
+///              start at i = 0 and advance while i + 1 < n and d > max_gap, d being one binary32 subtraction (v[i+1] - v[i]
+///              for Lowest, v[i] - v[i+1] for Highest); the band is v[i].  max_gap = +Inf gives the plain Min or Max.  A cell
+///              whose k kept values are ALL more than max_gap apart yields the k-th: with k - 1 or more isolated outliers in
+///              one cell the band is the last value kept, whatever it is -- raise k where that can happen.
+/// Both engines and both device paths give the same bits for any order, chunking or number of ingests.
+struct ExtremesConfig {
+    std::string value_channel;           // any Float32 channel, a surface channel ("hag") included
+    ExtremeSide side = ExtremeSide::Lowest;
+    int k = 4;                           // 2..8 values kept per cell
+    float max_gap = 1.0f;                // >= 0; +Inf: the plain Min / Max
+    FilterSpec filter;                   // like ReductionSpec::filter: AND PipelineConfig::filter
+    std::string band_name;               // default "{value_channel}_low" / "{value_channel}_high"
+};
+
 struct PipelineConfig {
     GridConfig grid;
     std::vector<ReductionSpec> reductions;
@@ -202,6 +230,18 @@ struct PipelineConfig {
     // NotImplemented while the list is non-empty (a checkpoint that silently lost the cube would be a wrong result later).
     // Empty: nothing is allocated, launched or validated differently.
     std::vector<HistogramConfig> histograms;
+    // Per-cell extremes (ExtremesConfig): every ingest also folds each entry's channel into its k key planes -- on the HIP
+    // engine in HBM, k * cells * 4 bytes that count towards gpu_memory_budget -- and finalize() appends one band per entry
+    // BEHIND the percentile bands and AHEAD of the DTM, hag and terrain bands: with fill_nodata_radius it is filled like a Min
+    // band (Lowest) or a Max band (Highest), ground.source_band, ground.top_band and terrain[].source_band may name it (a DTM
+    // from "z_low" starts from outlier-free minima), result(), the GeoTIFF and its overview levels carry it like any other
+    // band.  The planes persist like the plane state: finalize() may be called again after more ingests;
+    // Pipeline::extremes_values reads them at any time.  Each filter joins the plan of the ReductionSpec filters and counts
+    // against its limits (8 distinct filters, 16 predicates per conjunction, 32 in all).  create() refuses more than 4 entries,
+    // k outside 2..8, a negative or NaN max_gap, an empty value_channel, an unknown side, a band name that collides with any
+    // other leaving band, a row-block shard and a pipeline that has to run out of core; save_state, load_state and resume
+    // answer NotImplemented while the list is non-empty.  Empty: nothing is allocated, launched or validated differently.
+    std::vector<ExtremesConfig> extremes;
 };
 
 struct ProgressInfo {
@@ -245,6 +285,12 @@ public:
     Status histogram_counts(int i, std::vector<uint32_t>* out) const;
     /// ... and its shape: bins planes of rows x width cells.
     Status histogram_shape(int i, int* bins, int* rows, int* width) const;
+    /// Extension: the values PipelineConfig::extremes[i] keeps as a host copy, [k][rows][width] floats -- ascending for Lowest,
+    /// descending for Highest, NaN for an empty slot -- after synchronising with the pipeline's stream.  Valid after any ingest
+    /// (all NaN before the first); finalize() is not needed.  InvalidArgument for an index outside the list.
+    Status extremes_values(int i, std::vector<float>* out) const;
+    /// ... and its shape: k planes of rows x width cells.
+    Status extremes_shape(int i, int* k, int* rows, int* width) const;
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
     /// the finalize kernels are only ENQUEUED on the pipeline's stream -- result() is valid at once, its bands are complete

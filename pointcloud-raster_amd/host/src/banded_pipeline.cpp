@@ -99,6 +99,8 @@ size_t Pipeline::Banded::bytes_per_row(const PipelineConfig& c) {
         for (int p = 0; p < 4; ++p) planes += (gr.mask & kPlaneBits[p]) ? 1 : 0;
     // (PipelineConfig::histograms: a cube's bin planes and its percentile bands count like any other plane and band)
     for (const auto& h : c.histograms) planes += (size_t)std::max(h.bins, 0) + h.percentiles.size();
+    // (PipelineConfig::extremes: k key planes and one band per entry)
+    for (const auto& e : c.extremes) planes += (size_t)std::max(e.k, 0) + 1;
     return (size_t)c.grid.width * 4 * (planes + c.reductions.size());
 }
 

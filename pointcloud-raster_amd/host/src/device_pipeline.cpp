@@ -24,6 +24,7 @@ Pipeline::Impl::~Impl() {
     if (engine) pcr_hip_engine_destroy(engine);
     surfaces.clear();
     cubes.clear();
+    ext_keys.clear();
     groups.clear();
     bands.clear();
     band_buffers.clear();
@@ -42,6 +43,7 @@ Status Pipeline::Impl::init() {
     {
         Status ok = detail::check_reduction_specs(cfg.reductions);
         if (ok.ok()) ok = detail::check_histograms(cfg);
+        if (ok.ok()) ok = detail::check_extremes(cfg);
         if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
         if (!ok.ok()) return ok;
     }
@@ -118,6 +120,7 @@ Status Pipeline::Impl::init() {
         outputs = std::move(plan.outputs);
     }
     hist = detail::plan_histograms(cfg, filters);
+    ext = detail::plan_extremes(cfg, filters);
     if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
     if (!(s = detail::plan_terrain(cfg, ground, &terrain)).ok()) return s;
     if (!(s = detail::plan_surfaces(cfg)).ok()) return s;
@@ -181,6 +184,12 @@ Status Pipeline::Impl::init() {
         if (!(s = cubes[h].allocate(bytes, MemoryLocation::Device)).ok()) return s;
         if (!(s = detail::hip_status(pcr_hip_memset(cubes[h].data(), 0, bytes, stream))).ok()) return s;
     }
+    ext_keys.resize(ext.entries.size());
+    for (size_t x = 0; x < ext_keys.size(); ++x) {                // every slot EMPTY (0xFFFFFFFF)
+        const size_t bytes = ext.entries[x].state_cells((size_t)std::max<int64_t>(cells, 1)) * sizeof(uint32_t);
+        if (!(s = ext_keys[x].allocate(bytes, MemoryLocation::Device)).ok()) return s;
+        if (!(s = detail::hip_status(pcr_hip_memset(ext_keys[x].data(), 0xFF, bytes, stream))).ok()) return s;
+    }
     if (!outputs.empty() && !(s = allocate_result()).ok()) return s;
     if (!(s = d_bands_done.allocate(std::max<size_t>(groups.size(), 1) * sizeof(uint32_t), MemoryLocation::HostPinned)).ok()) return s;
     std::memset(d_bands_done.data(), 0, d_bands_done.bytes());
@@ -235,6 +244,40 @@ Status Pipeline::Impl::histogram_counts(int i, std::vector<uint32_t>* out) {
     if (out->empty()) return Status::success();
     Status s = detail::hip_status(pcr_hip_memcpy_d2h(out->data(), cubes[(size_t)i].data(), out->size() * sizeof(uint32_t), stream));
     return s.ok() ? detail::hip_status(pcr_hip_stream_synchronize(stream)) : s;
+}
+// Behind the percentile bands and ahead of the ground filter, which may read an extremes band ("z_low"): one walk per entry
+// writes its raw band, which then leaves like a Min (Lowest) or Max (Highest) band (filled when asked).
+Status Pipeline::Impl::finalize_extremes(bool* enqueued) {
+    size_t r = cfg.reductions.size() + (size_t)hist.extra_bands();
+    for (size_t x = 0; x < ext.entries.size(); ++x, ++r) {
+        const detail::ExtremesEntry& e = ext.entries[x];
+        *enqueued = true;
+        Status s = detail::hip_status(pcr_hip_extremes_band(&hg, static_cast<const uint32_t*>(ext_keys[x].data()), e.k, e.side, e.max_gap,
+                                                            bands[r].raw, nullptr, stream));
+        if (s.ok()) s = band_leaves(r, enqueued);
+        if (!s.ok()) return s;
+    }
+    return Status::success();
+}
+// The values entry i keeps as a host copy, [k][rows * width], behind everything on the pipeline's stream: decoded on the device
+// by the band kernel into memory of the call's own (the band it also writes is dropped).
+Status Pipeline::Impl::extremes_values(int i, std::vector<float>* out) {
+    if (i < 0 || (size_t)i >= ext_keys.size() || !out)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: extremes_values: no extremes entry " + std::to_string(i));
+    DeviceScope dev(cfg.cuda_device_id);
+    const detail::ExtremesEntry& e = ext.entries[(size_t)i];
+    const size_t cells = (size_t)std::max(own_rows(), 0) * (size_t)hg.width;
+    out->assign(e.state_cells(cells), 0.0f);
+    if (out->empty()) return Status::success();
+    detail::Buffer d_tmp;                                         // [band][k value planes]
+    Status s = d_tmp.allocate((e.state_cells(cells) + cells) * sizeof(float), MemoryLocation::Device);
+    if (!s.ok()) return s;
+    float* d_band = static_cast<float*>(d_tmp.data());
+    s = detail::hip_status(pcr_hip_extremes_band(&hg, static_cast<const uint32_t*>(ext_keys[(size_t)i].data()), e.k, e.side, e.max_gap,
+                                                 d_band, d_band + cells, stream));
+    if (s.ok()) s = detail::hip_status(pcr_hip_memcpy_d2h(out->data(), d_band + cells, out->size() * sizeof(float), stream));
+    const Status w = detail::hip_status(pcr_hip_stream_synchronize(stream));      // (d_tmp is released behind the kernel)
+    return s.ok() ? w : s;
 }
 // Behind the finalize kernels and the fills of every group, on the pipeline's stream: the filter on the RAW source band, the
 // DTM leaves (filled like a Min band), hag from the top band and the DTM as they leave the pipeline, hag leaves.
@@ -832,6 +875,21 @@ Status Pipeline::Impl::scatter_histograms(Ingest& in) {
     return Status::success();
 }
 
+// PipelineConfig::extremes: each entry's key planes take the points its class keeps, under the same argument about the flags.
+Status Pipeline::Impl::scatter_extremes(Ingest& in) {
+    for (size_t x = 0; x < ext.entries.size(); ++x) {
+        const detail::ExtremesEntry& e = ext.entries[x];
+        const float* dv = nullptr;
+        Status s = in.channel(e.value_channel, &dv);
+        if (!s.ok()) return s;
+        pcr_hip_engine_set_point_mask(engine, in.class_mask[(size_t)e.cls]);
+        s = detail::hip_status(pcr_hip_scatter_extremes(engine, static_cast<uint32_t*>(ext_keys[x].data()), e.k, e.side,
+                                                        static_cast<const double*>(in.dx), static_cast<const double*>(in.dy), dv, in.n));
+        if (!s.ok()) return s;
+    }
+    return Status::success();
+}
+
 Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     Ingest in{cloud, cloud.count()};
     if (in.n == 0) return Status::success();
@@ -867,6 +925,7 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     }
     if (!(s = scatter_groups(in)).ok()) return s;
     if (!(s = scatter_histograms(in)).ok()) return s;
+    if (!(s = scatter_extremes(in)).ok()) return s;
     // host arrays may be reused by the caller as soon as we return (ingest_async: page-locked arrays are
     // read by the DMA engine later, the caller keeps them alive until synchronize())
     const MemoryLocation loc = cloud.location();
@@ -1000,6 +1059,7 @@ Status Pipeline::Impl::finalize(bool wait) {
             if (!(s = band_leaves(r, &enqueued)).ok()) return s;
     }
     if (!(s = finalize_histograms(&enqueued)).ok()) return s;
+    if (!(s = finalize_extremes(&enqueued)).ok()) return s;
     if (!(s = finalize_ground(&enqueued)).ok()) return s;
     if (!(s = finalize_terrain(&enqueued)).ok()) return s;
     // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
@@ -1138,6 +1198,7 @@ Status Pipeline::Impl::import_window(const std::vector<std::vector<float>>& plan
 
 Status Pipeline::Impl::save_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
+    if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
     std::string dir;
     Status s = checkpoint_dir(dir_in, &dir, true);
     if (!s.ok()) return s;
@@ -1149,6 +1210,7 @@ Status Pipeline::Impl::save_state(const std::string& dir_in) {
 
 Status Pipeline::Impl::load_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
+    if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
     std::string dir;
     Status s = checkpoint_dir(dir_in, &dir, false);
     if (!s.ok()) return s;

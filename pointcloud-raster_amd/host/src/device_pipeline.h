@@ -4,6 +4,7 @@
 #pragma once
 
 #include "buffer.h"
+#include "extremes.h"
 #include "ground_filter.h"
 #include "histogram.h"
 #include "pcr/core/grid.h"
@@ -99,6 +100,9 @@ struct Pipeline::Impl {
     detail::HistogramPlan hist;              // PipelineConfig::histograms, planned at init
     std::vector<detail::Buffer> cubes;       // entry by entry: count[bins][state_rows * width] in HBM, zeroed at create and only
                                              // ever added to: no part in the plane-state rules
+    detail::ExtremesPlan ext;                // PipelineConfig::extremes, planned at init
+    std::vector<detail::Buffer> ext_keys;    // entry by entry: keys[k][state_rows * width] in HBM, all EMPTY at create and only
+                                             // ever lowered: no part in the plane-state rules
     std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in HBM (set_surface)
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
@@ -164,6 +168,8 @@ struct Pipeline::Impl {
     Status band_leaves(size_t b, bool* enqueued);
     Status finalize_histograms(bool* enqueued);
     Status histogram_counts(int i, std::vector<uint32_t>* out);
+    Status finalize_extremes(bool* enqueued);
+    Status extremes_values(int i, std::vector<float>* out);
     Status finalize_ground(bool* enqueued);
     Status finalize_terrain(bool* enqueued);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
@@ -186,6 +192,7 @@ struct Pipeline::Impl {
     Status check_line_reach(Ingest& in);
     Status scatter_groups(Ingest& in);
     Status scatter_histograms(Ingest& in);
+    Status scatter_extremes(Ingest& in);
     Status marshal_glyph(const GlyphSpec& gl, const detail::ChannelLookup& channel, pcr_hip_glyph* out) const;
     Status allocate_result();
     Status checkpoint_dir(const std::string& dir_in, std::string* dir, bool writing) const;

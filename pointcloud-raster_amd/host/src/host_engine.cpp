@@ -1,6 +1,7 @@
 // host_engine.cpp -- see host_engine.h.  Arithmetic after the reference's CPU path, cited at each step; structure ours.
 #include "host_engine.h"
 
+#include "../../csrc/extremes.hpp"
 #include "../../csrc/histogram.hpp"
 #include "pipeline_common.h"
 
@@ -296,6 +297,25 @@ void HostEngine::scatter_histogram(uint32_t* counts, int bins, double lo, double
             const uint32_t i = list[k];
             const uint32_t b = pcrhip::hist::bin_of(v[i], lo, inv_w, bins);
             counts[(size_t)b * plane_cells + (size_t)row_[i] * W_ + (size_t)col_[i]] += 1u;
+        }
+    }
+}
+
+void HostEngine::scatter_extremes(uint32_t* keys, int k, int side, const float* v, const uint8_t* keep) {
+    if (n_ == 0 || !v || !keys) return;
+    std::vector<uint32_t> list;
+    std::vector<size_t> first;
+    build_lists(list, first, [&](size_t i, Span& sp) {
+        if (row_[i] < 0 || (keep && !keep[i]) || v[i] != v[i]) return false;
+        sp.lo = sp.hi = row_[i];
+        return true;
+    });
+    const int64_t plane_cells = (int64_t)W_ * H_;
+#pragma omp parallel for num_threads(threads_) schedule(dynamic, 1)
+    for (int s = 0; s < nstripes_; ++s) {
+        for (size_t j = first[(size_t)s]; j < first[(size_t)s + 1]; ++j) {
+            const uint32_t i = list[j];
+            pcrhip::ext::insert_sorted(keys + ((size_t)row_[i] * W_ + (size_t)col_[i]), plane_cells, k, pcrhip::ext::key_of(v[i], side));
         }
     }
 }

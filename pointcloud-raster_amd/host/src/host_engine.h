@@ -64,6 +64,11 @@ public:
     /// bin by csrc/histogram.hpp (include/pcr_hip.h, "per-cell histograms").  counts: [bins][height * width].  Stripe-owned like
     /// the other folds, no atomics; integer addition, so the bits are the same at any thread count.
     void scatter_histogram(uint32_t* counts, int bins, double lo, double inv_w, const float* v, const uint8_t* keep = nullptr);
+    /// PipelineConfig::extremes: every routed point the keep mask keeps whose value is not NaN is inserted, by its key, into the
+    /// sorted distinct list of its cell (csrc/extremes.hpp; include/pcr_hip.h, "per-cell extremes").  keys: [k][height * width].
+    /// Stripe-owned like the other folds, no atomics; the k smallest distinct keys of a set, so the bits are the same at any
+    /// thread count.
+    void scatter_extremes(uint32_t* keys, int k, int side, const float* v, const uint8_t* keep = nullptr);
     /// A select group's planes as a checkpoint left them -> the canonical form a fold leaves (a NaN or <= -FLT_MAX timestamp
     /// means empty: {NaN, -FLT_MAX}; a -0.0 timestamp is +0.0).
     void normalize_select(HostPlanes& p) const;

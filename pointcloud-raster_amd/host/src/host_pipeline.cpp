@@ -21,6 +21,7 @@ Status Pipeline::Host::init() {
     {
         Status ok = detail::check_reduction_specs(cfg.reductions);
         if (ok.ok()) ok = detail::check_histograms(cfg);
+        if (ok.ok()) ok = detail::check_extremes(cfg);
         if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
         if (!ok.ok()) return ok;
     }
@@ -43,6 +44,9 @@ Status Pipeline::Host::init() {
     // PipelineConfig::histograms: the cubes
     hist = detail::plan_histograms(cfg, filters);
     for (size_t h = 0; h < hist.entries.size(); ++h) cubes.emplace_back(hist.entries[h].cube_cells((size_t)g.width * g.height), 0u);
+    // PipelineConfig::extremes: the key planes, all EMPTY
+    ext = detail::plan_extremes(cfg, filters);
+    for (const auto& e : ext.entries) ext_keys.emplace_back(e.state_cells((size_t)g.width * g.height), 0xFFFFFFFFu);
     // Tile state is identity-initialised (src/engine/tile_manager.cpp:183-260); here for the whole grid at once.
     for (auto& gr : groups) engine->init_planes(gr.planes, gr.mask, gr.select);
     return Status::success();
@@ -159,6 +163,7 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     for (size_t k = 1; k < filters.classes.size(); ++k) apply(filters.classes[k], class_keep[k]);
     auto keep_of = [&](const Group& gr, size_t i0) -> const uint8_t* { return gr.cls ? class_keep[(size_t)gr.cls].data() + i0 : nullptr; };
     auto hist_keep = [&](const detail::HistogramEntry& e, size_t i0) -> const uint8_t* { return e.cls ? class_keep[(size_t)e.cls].data() + i0 : nullptr; };
+    auto ext_keep = [&](const detail::ExtremesEntry& e, size_t i0) -> const uint8_t* { return e.cls ? class_keep[(size_t)e.cls].data() + i0 : nullptr; };
 
     // the engine indexes a cloud with 32 bits: larger ones go in slices
     const size_t slice = (size_t)1 << 31;
@@ -190,6 +195,10 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         for (size_t h = 0; h < hist.entries.size(); ++h) {
             const detail::HistogramEntry& e = hist.entries[h];
             engine->scatter_histogram(cubes[h].data(), e.bins, e.lo, e.inv_w, f32(e.value_channel) + i0, hist_keep(e, i0));
+        }
+        for (size_t x = 0; x < ext.entries.size(); ++x) {
+            const detail::ExtremesEntry& e = ext.entries[x];
+            engine->scatter_extremes(ext_keys[x].data(), e.k, e.side, f32(e.value_channel) + i0, ext_keep(e, i0));
         }
     }
     last = ScatterInfo{};
@@ -237,6 +246,11 @@ Status Pipeline::Host::finalize() {
         Status hs = detail::percentiles_host(hist.entries[h], cubes[h].data(), g.width, g.height, dsts.data(), engine->threads());
         if (!hs.ok()) return hs;
     }
+    for (size_t x = 0, r = cfg.reductions.size() + (size_t)hist.extra_bands(); x < ext.entries.size(); ++x, ++r) {
+        Status es = detail::extremes_band_host(ext.entries[x], ext_keys[x].data(), g.width, g.height, result->band_f32((int)r), nullptr,
+                                               engine->threads());
+        if (!es.ok()) return es;
+    }
     {                                                                // (the planes are the state: the bands are made anew by every finalize)
         std::vector<ReductionType> types;
         for (const auto& o : outputs) types.push_back(o.type);
@@ -250,6 +264,7 @@ Status Pipeline::Host::finalize() {
 
 Status Pipeline::Host::save_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
+    if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     detail::StateWindow w;
@@ -261,6 +276,7 @@ Status Pipeline::Host::save_state(const std::string& dir_in) {
 
 Status Pipeline::Host::load_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
+    if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     detail::StateWindow w;

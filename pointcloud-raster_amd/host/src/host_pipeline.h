@@ -3,6 +3,7 @@
 // Same validation, messages, band naming, progress callback and `.pcrt` checkpoints as the HIP pipeline.
 #pragma once
 
+#include "extremes.h"
 #include "histogram.h"
 #include "host_engine.h"
 #include "pcr/core/grid.h"
@@ -31,6 +32,8 @@ struct Pipeline::Host {
     std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in host memory
     detail::HistogramPlan hist;          // PipelineConfig::histograms, planned at init
     std::vector<std::vector<uint32_t>> cubes;    // entry by entry: count[bins][height * width], zero at create
+    detail::ExtremesPlan ext;            // PipelineConfig::extremes, planned at init
+    std::vector<std::vector<uint32_t>> ext_keys; // entry by entry: keys[k][height * width], all EMPTY (0xFFFFFFFF) at create
     std::unique_ptr<Grid> result;
     bool finalized = false;
     ProgressCallback callback;

@@ -15,6 +15,7 @@
 #include "banded_pipeline.h"
 #include "device_pipeline.h"
 #include "ground_filter.h"
+#include "extremes.h"
 #include "histogram.h"
 #include "terrain.h"
 #include "host_pipeline.h"
@@ -58,6 +59,10 @@ std::vector<std::string> named_channels(const PipelineConfig& c) {
         add(h.value_channel);
         for (const auto& p : h.filter.predicates) add(p.channel_name);
     }
+    for (const auto& e : c.extremes) {
+        add(e.value_channel);
+        for (const auto& p : e.filter.predicates) add(p.channel_name);
+    }
     for (const auto& sc : c.surface_channels) add(sc.value_channel);
     return out;
 }
@@ -93,6 +98,8 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
     {
         const Status hs = detail::check_histograms(config);     // (ahead of the ground and terrain plans, which may name its bands)
         if (!hs.ok()) return fail_with(hs);
+        const Status es = detail::check_extremes(config);       // (likewise)
+        if (!es.ok()) return fail_with(es);
     }
     {
         detail::GroundPlan plan;                      // (every engine plans again for itself: here only the refusals)
@@ -110,6 +117,7 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
     if (Banded::needed(config, &budget)) {
         if (!config.surface_channels.empty()) return fail_with(detail::surfaces_out_of_core_error());
         if (!config.histograms.empty()) return fail_with(detail::histograms_out_of_core_error());
+        if (!config.extremes.empty()) return fail_with(detail::extremes_out_of_core_error());
         Status bs = Status::success();
         p->banded_ = Banded::create(config, p.get(), budget, &bs);
         if (!p->banded_) return fail_with(bs);
@@ -281,6 +289,26 @@ Status Pipeline::histogram_shape(int i, int* bins, int* rows, int* width) const 
     if (!c || i < 0 || (size_t)i >= c->histograms.size() || !bins || !rows || !width)
         return Status::error(StatusCode::InvalidArgument, "pipeline: histogram_counts: no histogram " + std::to_string(i));
     *bins = c->histograms[(size_t)i].bins;
+    *rows = c->grid.height;                                  // (a row-block shard is refused: the window is the grid)
+    *width = c->grid.width;
+    return Status::success();
+}
+Status Pipeline::extremes_values(int i, std::vector<float>* out) const {
+    if (impl_) return impl_->extremes_values(i, out);
+    if (!host_ || i < 0 || (size_t)i >= host_->ext_keys.size() || !out)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: extremes_values: no extremes entry " + std::to_string(i));
+    const PipelineConfig& c = host_->cfg;
+    const size_t cells = (size_t)c.grid.width * c.grid.height;
+    out->assign(host_->ext.entries[(size_t)i].state_cells(cells), 0.0f);
+    std::vector<float> band(cells);                          // (the twin writes the band too: dropped)
+    return detail::extremes_band_host(host_->ext.entries[(size_t)i], host_->ext_keys[(size_t)i].data(), c.grid.width, c.grid.height,
+                                      band.data(), out->data(), host_->engine->threads());
+}
+Status Pipeline::extremes_shape(int i, int* k, int* rows, int* width) const {
+    const PipelineConfig* c = host_ ? &host_->cfg : impl_ ? &impl_->cfg : nullptr;
+    if (!c || i < 0 || (size_t)i >= c->extremes.size() || !k || !rows || !width)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: extremes_values: no extremes entry " + std::to_string(i));
+    *k = c->extremes[(size_t)i].k;
     *rows = c->grid.height;                                  // (a row-block shard is refused: the window is the grid)
     *width = c->grid.width;
     return Status::success();

@@ -47,6 +47,15 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
         if (!d || d->dtype != DataType::Float32)
             return Status::error(StatusCode::InvalidArgument, "pipeline: histogram value channel must be Float32");
     }
+    for (const auto& e : cfg.extremes) {                       // PipelineConfig::extremes: likewise
+        if (!(fs = check_filter(e.filter)).ok()) return fs;
+        if (derived(e.value_channel)) continue;
+        if (!cloud.channel_data(e.value_channel))
+            return Status::error(StatusCode::InvalidArgument, "pipeline: extremes value channel not found: " + e.value_channel);
+        const ChannelDesc* d = cloud.channel(e.value_channel);
+        if (!d || d->dtype != DataType::Float32)
+            return Status::error(StatusCode::InvalidArgument, "pipeline: extremes value channel must be Float32");
+    }
     for (const auto& r : cfg.reductions) {
         if (!derived(r.value_channel)) {
             if (!cloud.channel_data(r.value_channel))
@@ -86,6 +95,7 @@ Status plan_filters(const PipelineConfig& cfg, FilterPlan* out) {
     };
     for (const auto& r : cfg.reductions) out->class_of.push_back(class_for(r.filter));
     for (const auto& h : cfg.histograms) out->hist_class_of.push_back(class_for(h.filter));   // (a histogram's filter is one more class)
+    for (const auto& e : cfg.extremes) out->ext_class_of.push_back(class_for(e.filter));      // (and so is an extremes entry's)
     if (out->classes.size() - 1 > kMaxSpecFilters)
         return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(kMaxSpecFilters) +
                                                           " distinct reduction filters in one pipeline");
@@ -216,6 +226,14 @@ GroupPlan plan_groups(const PipelineConfig& cfg) {
             o.q = (int)j;
             plan.outputs.push_back(o);
         }
+    for (size_t i = 0; i < cfg.extremes.size(); ++i) {
+        Output o;
+        o.group = -1;
+        o.type = cfg.extremes[i].side == ExtremeSide::Highest ? ReductionType::Max : ReductionType::Min;
+        o.band_name = extremes_band_name(cfg.extremes[i]);
+        o.ext = (int)i;
+        plan.outputs.push_back(o);
+    }
     return plan;
 }
 

@@ -131,6 +131,11 @@ inline std::string histogram_band_name(const HistogramConfig& h, size_t j) {
     if (j < h.band_names.size() && !h.band_names[j].empty()) return h.band_names[j];
     return h.value_channel + "_p" + std::to_string(std::lround((double)h.percentiles[j] * 100.0));
 }
+// PipelineConfig::extremes: the name of an entry's band, "{value_channel}_low" / "{value_channel}_high" unless given.
+inline std::string extremes_band_name(const ExtremesConfig& e) {
+    if (!e.band_name.empty()) return e.band_name;
+    return e.value_channel + (e.side == ExtremeSide::Highest ? "_high" : "_low");
+}
 // ReductionSpec::filter: equal means the same predicates in the same order, field by field.
 inline bool same_predicate(const FilterPredicate& a, const FilterPredicate& b) {
     return a.channel_name == b.channel_name && a.op == b.op && a.value == b.value && a.value_set == b.value_set;
@@ -160,19 +165,22 @@ struct GroupSpec {                       // one pass over the points, one set of
     int cls = 0;                         // its filter class (FilterPlan): 0 = PipelineConfig::filter alone
     uint32_t mask = 0;                   // kPlaneBits of the planes it keeps
 };
-struct Output {                          // one band finalize makes from the state: a ReductionSpec's, or a percentile band
+struct Output {                          // one band finalize makes from the state: a ReductionSpec's, a percentile band or an
+                                         // extremes band
     int group = 0;                       // -1: a percentile band of histogram `hist` (no group reads or writes it; its type is
-                                         // Max, so that it is filled like a Max band)
+                                         // Max, so that it is filled like a Max band), or the band of extremes entry `ext` (its
+                                         // type is Min for Lowest, Max for Highest, for the same reason)
     ReductionType type = ReductionType::Sum;
     std::string band_name;
     int hist = -1, q = 0;                // the histogram and which of its percentiles
+    int ext = -1;                        // the extremes entry
 };
 struct GroupPlan {
     std::vector<GroupSpec> groups;       // in order of first appearance among the ReductionSpecs: reduction_groups(), state_planes(),
                                          // parked windows (planes[4 g + p]) and the `.pcrt` directories all count them this way
     std::vector<Output> outputs;         // the result grid's order: one per ReductionSpec, then the histograms' percentile bands entry
-                                         // by entry.  What ground.source_band, ground.top_band and terrain[].source_band may name
-                                         // (the DTM, hag and terrain bands follow them)
+                                         // by entry, then one band per extremes entry.  What ground.source_band, ground.top_band
+                                         // and terrain[].source_band may name (the DTM, hag and terrain bands follow them)
 };
 GroupPlan plan_groups(const PipelineConfig& cfg);
 // The outputs a checkpoint carries (write_state_tiles, read_state_tiles): those with a group.
@@ -228,6 +236,7 @@ struct FilterPlan {
     std::vector<FilterSpec> classes;         // [0] is empty
     std::vector<int> class_of;               // per ReductionSpec
     std::vector<int> hist_class_of;          // per entry of PipelineConfig::histograms: its filter joins the same plan
+    std::vector<int> ext_class_of;           // per entry of PipelineConfig::extremes: likewise
     std::vector<FilterPredicate> table;      // PipelineConfig::filter's predicates first
     std::vector<uint32_t> words;             // per class; words[0] == 0: no PipelineConfig::filter
     bool any() const { return classes.size() > 1; }

@@ -131,6 +131,35 @@ void bind_engine(py::module_& m) {
         .def_readwrite("percentiles", &HistogramConfig::percentiles)
         .def_readwrite("band_names", &HistogramConfig::band_names);
 
+    py::enum_<ExtremeSide>(m, "ExtremeSide")
+        .value("Lowest", ExtremeSide::Lowest)
+        .value("Highest", ExtremeSide::Highest);
+
+    py::class_<ExtremesConfig>(m, "ExtremesConfig",
+                               "The k lowest (or highest) distinct values of a Float32 channel per cell (a surface channel included) "
+                               "and the outlier-free Min (Max) band walked out of them")
+        .def(py::init<>())
+        .def(py::init<const ExtremesConfig&>())
+        .def(py::init([](const std::string& value_channel, ExtremeSide side, int k, float max_gap) {
+            ExtremesConfig e;
+            e.value_channel = value_channel;
+            e.side = side;
+            e.k = k;
+            e.max_gap = max_gap;
+            return e;
+        }), py::arg("value_channel"), py::arg("side") = ExtremeSide::Lowest, py::arg("k") = 4, py::arg("max_gap") = 1.0f)
+        .def_readwrite("value_channel", &ExtremesConfig::value_channel)
+        // (an integer is taken as it is, so that a configuration written elsewhere with a side this build does not know is
+        // refused by Pipeline.create with its message, not by the setter)
+        .def_property("side", [](const ExtremesConfig& e) { return e.side; },
+                      [](ExtremesConfig& e, const py::object& side) {
+                          e.side = py::isinstance<ExtremeSide>(side) ? side.cast<ExtremeSide>() : static_cast<ExtremeSide>(side.cast<int>());
+                      })
+        .def_readwrite("k", &ExtremesConfig::k)
+        .def_readwrite("max_gap", &ExtremesConfig::max_gap)
+        .def_readwrite("filter", &ExtremesConfig::filter)
+        .def_readwrite("band_name", &ExtremesConfig::band_name);
+
     py::class_<PipelineConfig>(m, "PipelineConfig")
         .def(py::init<>())
         .def_readwrite("grid", &PipelineConfig::grid)
@@ -169,7 +198,10 @@ void bind_engine(py::module_& m) {
                        "list of SurfaceChannelConfig): usable wherever a channel is named")
         .def_readwrite("histograms", &PipelineConfig::histograms,
                        "Per-cell histograms counted at every ingest and the percentile bands finalize() appends behind the "
-                       "reductions' bands (assign a list of HistogramConfig)");
+                       "reductions' bands (assign a list of HistogramConfig)")
+        .def_readwrite("extremes", &PipelineConfig::extremes,
+                       "Per-cell k lowest / highest distinct values kept at every ingest and the outlier-free Min / Max band "
+                       "finalize() appends behind the percentile bands (assign a list of ExtremesConfig)");
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
         .def(py::init<>())
@@ -213,6 +245,18 @@ void bind_engine(py::module_& m) {
             return out;
         }, py::arg("i") = 0,
              "The cube of histogram i as a numpy.uint32 array (bins, height, width): a host copy, valid after any ingest")
+        .def("extremes", [](const Pipeline& p, int i) {
+            std::vector<float> values;
+            raise_if_error(p.extremes_values(i, &values));
+            int k = 0, rows = 0, width = 0;
+            raise_if_error(p.extremes_shape(i, &k, &rows, &width));
+            py::array_t<float> out({(py::ssize_t)k, (py::ssize_t)rows, (py::ssize_t)width});
+            if (values.size() != (size_t)out.size()) throw std::runtime_error("pipeline: extremes: unexpected size");
+            std::memcpy(out.mutable_data(), values.data(), values.size() * sizeof(float));
+            return out;
+        }, py::arg("i") = 0,
+             "The values extremes entry i keeps as a numpy.float32 array (k, height, width), ascending (Lowest) or descending "
+             "(Highest), NaN for an empty slot: a host copy, valid after any ingest")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },
              "Device-resident result: the finalize kernels are only enqueued on the pipeline's stream (complete after synchronize()); "

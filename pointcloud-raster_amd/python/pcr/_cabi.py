@@ -197,6 +197,9 @@ SYMBOLS = {
     "pcr_hip_scatter_histogram": [_VP, _VP, C.c_int, C.c_double, C.c_double, _VP, _VP, _VP, _U64],
     "pcr_hip_histogram_percentiles": [C.POINTER(Grid), _VP, C.c_int, C.c_double, C.c_double, C.c_int, _VP, C.POINTER(_VP), _VP],
     "pcr_hip_histogram_percentiles_host": [C.POINTER(Grid), _VP, C.c_int, C.c_double, C.c_double, C.c_int, _VP, C.POINTER(_VP)],
+    "pcr_hip_scatter_extremes": [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, _U64],
+    "pcr_hip_extremes_band": [C.POINTER(Grid), _VP, C.c_int, C.c_int, C.c_float, _VP, _VP, _VP],
+    "pcr_hip_extremes_band_host": [C.POINTER(Grid), _VP, C.c_int, C.c_int, C.c_float, _VP, _VP],
 }
 
 _lib = None
