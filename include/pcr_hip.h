@@ -764,6 +764,54 @@ int pcr_hip_extremes_band(const pcr_hip_grid* g, const uint32_t* d_keys, int k, 
 int pcr_hip_extremes_band_host(const pcr_hip_grid* g, const uint32_t* h_keys, int k, int side, float max_gap, float* h_out,
                                float* h_values);
 
+/* ---- per-cell stats: the exact mean, variance and standard deviation of a channel per cell, a mergeable piece of state
+ *      beside the reductions (PipelineConfig::cell_stats).  No reference counterpart.  The state is three INTEGER planes, so
+ *      the fold is integer addition: the same bits on both engines and both device paths, for any order, chunking or number
+ *      of scatters, with no tolerance anywhere.  The arithmetic is written once, in csrc/cell_stats.hpp, which the kernels,
+ *      the host twin and the host engine compile with contraction off.
+ *        accepted   as for the histograms: a point is accepted when it is routed to a cell by the rule of the Point glyph
+ *                   (inclusive bounds, the floor of the true binary64 quotient, clamp; the owned rows of the engine's grid),
+ *                   is kept by the point mask (pcr_hip_engine_set_point_mask), and its value is not NaN.
+ *        step       inv_res = 1.0 / resolution, computed once by the caller.  t = ((double)v - origin) * inv_res, binary64;
+ *                   with Q = 2^21: q = -Q if t <= -Q, Q if t >= Q, else (int32)rint(t), ties to even.  Values out of range
+ *                   and +-Inf are clamped and COUNTED, like the histogram's end bins.  At a 1 cm step the range is +-20.9 km
+ *                   around origin.
+ *        state      three planes in the state window's layout ([state_rows * width] each), which the caller zeroes once:
+ *                   N (uint32, += 1), S1 (int64, += q), S2 (uint64, += q * q).  S1 cannot wrap while N has not; S2 is exact
+ *                   for at least 2^22 accepted points per cell, for 2^32 when |q| <= 2^16; N wraps at 2^32 -- documented,
+ *                   not checked, as for the histogram's counters.
+ *        bands      per cell of the owned rows, each NaN (0x7FC00000) where N == 0 -- the touched-tile flags play no part:
+ *                     MEAN      (float)(origin + resolution * ((double)S1 / (double)N))
+ *                     VARIANCE, STDDEV  NaN where N <= ddof; else with D = N * S2 - S1^2, an exact unsigned 128-bit integer
+ *                               (hi, lo) (non-negative by Cauchy-Schwarz while nothing has wrapped):
+ *                               dd = (double)hi * 0x1p64 + (double)lo;  den = (double)N * (double)(N - ddof);  vq = dd / den;
+ *                               VARIANCE = (float)((resolution * resolution) * vq), the product of resolutions computed once;
+ *                               STDDEV = (float)(resolution * sqrt(vq)).
+ *                   Every operation is rounded on its own; sqrt and / are the correctly rounded binary64 operations.
+ *      scatter_cell_stats honours pcr_hip_engine_set_point_mask and pcr_hip_engine_set_path exactly as
+ *      pcr_hip_scatter_histogram does: 1 direct -- three no-return global atomic adds per accepted point; 2 binned -- the
+ *      Point front end on 8-byte records whose value slot carries the step, two 64-bit LDS atomic adds per record on tiles of
+ *      128 x 72 cells, merged into the planes with plain wide reads and writes where a tile has one owner; 0 the binned path
+ *      where it applies, else the direct one.  It sets the touched flags of the tiles its points are routed to and reports
+ *      through pcr_hip_engine_stats like pcr_hip_scatter_point.
+ *      cell_stats_bands writes n_products bands (own rows x width floats each; products[j] names the band d_outs[j] gets) in
+ *      one launch on s: one lane per cell reads the three planes coalesced.  _host: the same lines on host arrays, one thread.
+ *      Argument errors -- a null pointer, a non-finite origin, a resolution (inv_res) that is not finite and positive, ddof
+ *      other than 0 or 1, n_products outside 1..3, an unknown product -- are reported before any HIP call. */
+#define PCR_HIP_CELL_STAT_MEAN 0
+#define PCR_HIP_CELL_STAT_VARIANCE 1
+#define PCR_HIP_CELL_STAT_STDDEV 2
+#define PCR_HIP_CELL_STATS_MAX_PRODUCTS 3
+#define PCR_HIP_CELL_STATS_Q (1 << 21)
+int pcr_hip_scatter_cell_stats(pcr_hip_engine* e, uint32_t* d_n, long long* d_s1, unsigned long long* d_s2, double origin,
+                               double inv_res, const double* d_x, const double* d_y, const float* d_value, uint64_t n);
+int pcr_hip_cell_stats_bands(const pcr_hip_grid* g, const uint32_t* d_n, const long long* d_s1, const unsigned long long* d_s2,
+                             double origin, double resolution, int ddof, int n_products, const int* products, float* const* d_outs,
+                             pcr_hip_stream s);
+int pcr_hip_cell_stats_bands_host(const pcr_hip_grid* g, const uint32_t* h_n, const long long* h_s1, const unsigned long long* h_s2,
+                                  double origin, double resolution, int ddof, int n_products, const int* products,
+                                  float* const* h_outs);
+
 #ifdef __cplusplus
 }
 #endif

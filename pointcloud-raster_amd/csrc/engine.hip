@@ -541,6 +541,37 @@ int pcr_hip_scatter_extremes(pcr_hip_engine* e, uint32_t* d_keys, int k, int sid
     return rc;
 }
 
+int pcr_hip_scatter_cell_stats(pcr_hip_engine* e, uint32_t* d_n, long long* d_s1, unsigned long long* d_s2, double origin,
+                               double inv_res, const double* d_x, const double* d_y, const float* d_value, uint64_t n) {
+    PCR_REQUIRE(e, "scatter_cell_stats: null engine");
+    e->fused_outs.n = 0;                                  // (a pending finalize-with-scatter hint does not apply here)
+    e->fused_done = nullptr;
+    e->fused_taken = false;
+    e->defer_planes = e->deferred_taken = 0;
+    e->planes_fresh = 0;                                  // (the three planes are zero at create and only ever added to)
+    PCR_REQUIRE(d_n && d_s1 && d_s2, "scatter_cell_stats: null state plane");
+    PCR_REQUIRE(std::isfinite(origin) && std::isfinite(inv_res) && inv_res > 0.0,
+                "scatter_cell_stats: origin and inv_res must be finite, inv_res positive");
+    if (n == 0) return PCR_HIP_OK;                       // empty cloud is a no-op, as for pcr_hip_scatter_point
+    PCR_REQUIRE(n < ((uint64_t)1 << 40), "scatter_cell_stats: too many points in one call");
+    PCR_REQUIRE(d_x && d_y && d_value, "scatter_cell_stats: null point array");
+    DeviceGuard dev(e->device);
+    int rc = begin_scatter(e, n);
+    if (rc) return rc;
+    const bool can_bin = binned_cell_stats_supported(e);
+    if (e->forced_path == 2 && !can_bin)
+        return fail(PCR_HIP_INVALID_ARGUMENT, "scatter_cell_stats: binned path forced but not applicable to this grid");
+    if (e->forced_path == 1 || !can_bin) {
+        if ((rc = zero_counters(e)) != PCR_HIP_OK) return rc;
+        return direct_cell_stats(e, d_n, d_s1, d_s2, origin, inv_res, d_x, d_y, d_value, n);
+    }
+    if ((rc = begin_published(e)) != PCR_HIP_OK) return rc;
+    rc = binned_cell_stats(e, d_n, d_s1, d_s2, origin, inv_res, d_x, d_y, d_value, n);
+    e->publish_counters = false;
+    release_scratch(e);
+    return rc;
+}
+
 int pcr_hip_scatter_glyph(pcr_hip_engine* e, const pcr_hip_glyph* glyph, uint32_t plane_mask,
                           const pcr_hip_planes* planes,
                           const double* d_x, const double* d_y, const float* d_value, uint64_t n) {

@@ -238,6 +238,15 @@ int direct_extremes(pcr_hip_engine* e, uint32_t* keys, int k, int side, const do
 bool binned_extremes_supported(const pcr_hip_engine* e, int k);
 int binned_extremes(pcr_hip_engine* e, uint32_t* keys, int k, int side, const double* x, const double* y, const float* v, uint64_t n);
 
+// Per-cell stats (pcr_hip_scatter_cell_stats): three integer planes N, S1, S2 over the state window, cell_stats.hip.  direct:
+// three no-return global atomic adds per accepted point; binned: VALUE records {local cell, step} through the Point front end
+// (sweep_tiles), the step words in d_hist_words (as the extremes' key words: one scatter is in the making at a time).
+int direct_cell_stats(pcr_hip_engine* e, uint32_t* pn, long long* ps1, unsigned long long* ps2, double origin, double inv_res,
+                      const double* x, const double* y, const float* v, uint64_t n);
+bool binned_cell_stats_supported(const pcr_hip_engine* e);
+int binned_cell_stats(pcr_hip_engine* e, uint32_t* pn, long long* ps1, unsigned long long* ps2, double origin, double inv_res,
+                      const double* x, const double* y, const float* v, uint64_t n);
+
 // Gaussian cell tiles on 16-byte value records (default-sigma, unrotated, r <= 3), scatter_cells.hip
 bool cells_gauss_supported(const pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask);
 int cells_gauss(pcr_hip_engine* e, const GlyphDev& gl, uint32_t mask, const PlanesDev& pl,

@@ -131,6 +131,33 @@ struct ExtremesConfig {
     std::string band_name;               // default "{value_channel}_low" / "{value_channel}_high"
 };
 
+/// A band a CellStatsConfig makes.
+enum class CellStat : int { Mean = 0, Variance = 1, StdDev = 2 };
+
+/// One entry of PipelineConfig::cell_stats: the exact mean, variance and standard deviation of one channel per cell -- surface
+/// roughness, canopy structure (lidR's zsd), the vertical noise a survey's QA asks for.  A float32 Sum(v^2)/N - mean^2 is wrong
+/// by metres for z ~ 1500 m, sigma ~ 0.1 m; lidar values are fixed-point at the source, so the value is quantized to an integer
+/// step and N, the sum and the sum of squares are kept in integers.  The contract (include/pcr_hip.h, "per-cell stats"):
+///   accepted   exactly the histograms' rule: routed to a cell by the rule of the Point glyph (after reprojection and surface
+///              channels), kept by PipelineConfig::filter AND by `filter`, value not NaN.
+///   step       t = ((double)v - origin) * (1.0 / resolution); with Q = 2^21: q = -Q if t <= -Q, Q if t >= Q, else rint(t), ties
+///              to even.  Values out of range and +-Inf are clamped and counted.  At the default 1 cm step: +-20.9 km.
+///   state      three planes in the state window's layout, zero at create: N (uint32), S1 = sum q (int64), S2 = sum q^2
+///              (uint64).  S2 is exact for at least 2^22 accepted points per cell, N wraps at 2^32: documented, not checked.
+///   bands      NaN where N == 0.  Mean = (float)(origin + resolution * ((double)S1 / (double)N)).  Variance and StdDev: NaN where
+///              N <= ddof; else D = N * S2 - S1^2, an exact 128-bit integer, vq = (double)D / ((double)N * (double)(N - ddof)),
+///              Variance = (float)(resolution^2 * vq), StdDev = (float)(resolution * sqrt(vq)).
+/// Both engines and both device paths give the same bits for any order, chunking or number of ingests.
+struct CellStatsConfig {
+    std::string value_channel;           // any Float32 channel, a surface channel ("hag") included
+    double origin = 0.0;                 // finite; the value whose step is 0
+    double resolution = 0.01;            // finite, > 0: the step
+    std::vector<CellStat> products{CellStat::StdDev};    // 1..3, no duplicate: one band each, in this order
+    int ddof = 0;                        // 0 population, 1 sample
+    FilterSpec filter;                   // like ReductionSpec::filter: AND PipelineConfig::filter
+    std::vector<std::string> band_names; // default "{value_channel}_mean" / "_var" / "_std"
+};
+
 struct PipelineConfig {
     GridConfig grid;
     std::vector<ReductionSpec> reductions;
@@ -242,6 +269,19 @@ struct PipelineConfig {
     // other leaving band, a row-block shard and a pipeline that has to run out of core; save_state, load_state and resume
     // answer NotImplemented while the list is non-empty.  Empty: nothing is allocated, launched or validated differently.
     std::vector<ExtremesConfig> extremes;
+    // Per-cell stats (CellStatsConfig): every ingest also folds each entry's channel into its three integer planes -- on the HIP
+    // engine in HBM, 20 bytes per cell that count towards gpu_memory_budget -- and finalize() appends one band per product
+    // BEHIND the extremes' bands and AHEAD of the DTM, hag and terrain bands.  With fill_nodata_radius a Mean band is filled like
+    // an Average band; Variance and StdDev bands are never filled (a spread made up from the neighbours' is no measurement).
+    // ground.source_band, ground.top_band and terrain[].source_band may name the bands ("z_mean"); result(), the GeoTIFF and its
+    // overview levels carry them like any other band.  The planes persist like the plane state: finalize() may be called again
+    // after more ingests; Pipeline::cell_stats_state reads them at any time.  Each filter joins the plan of the ReductionSpec
+    // filters and counts against its limits.  create() refuses more than 4 entries, an empty value_channel, a resolution that is
+    // not finite and positive (or whose reciprocal is not finite), a non-finite origin, products empty, longer than 3 or with a
+    // duplicate, ddof other than 0 or 1, band_names longer than products, a band name that collides with any other leaving
+    // band, a row-block shard and a pipeline that has to run out of core; save_state, load_state and resume answer
+    // NotImplemented while the list is non-empty.  Empty: nothing is allocated, launched or validated differently.
+    std::vector<CellStatsConfig> cell_stats;
 };
 
 struct ProgressInfo {
@@ -291,6 +331,12 @@ public:
     Status extremes_values(int i, std::vector<float>* out) const;
     /// ... and its shape: k planes of rows x width cells.
     Status extremes_shape(int i, int* k, int* rows, int* width) const;
+    /// Extension: the three planes of PipelineConfig::cell_stats[i] as host copies, rows x width each -- N, S1 (the sum of the
+    /// steps) and S2 (the sum of their squares) -- after synchronising with the pipeline's stream.  Valid after any ingest (all
+    /// zero before the first); finalize() is not needed.  InvalidArgument for an index outside the list.
+    Status cell_stats_state(int i, std::vector<uint32_t>* n, std::vector<int64_t>* s1, std::vector<uint64_t>* s2) const;
+    /// ... and its shape.
+    Status cell_stats_shape(int i, int* rows, int* width) const;
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
     /// the finalize kernels are only ENQUEUED on the pipeline's stream -- result() is valid at once, its bands are complete

@@ -101,6 +101,8 @@ size_t Pipeline::Banded::bytes_per_row(const PipelineConfig& c) {
     for (const auto& h : c.histograms) planes += (size_t)std::max(h.bins, 0) + h.percentiles.size();
     // (PipelineConfig::extremes: k key planes and one band per entry)
     for (const auto& e : c.extremes) planes += (size_t)std::max(e.k, 0) + 1;
+    // (PipelineConfig::cell_stats: 20 bytes of state per cell -- five 4-byte planes' worth -- and one band per product)
+    for (const auto& s : c.cell_stats) planes += 5 + s.products.size();
     return (size_t)c.grid.width * 4 * (planes + c.reductions.size());
 }
 

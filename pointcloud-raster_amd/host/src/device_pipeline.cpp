@@ -25,6 +25,7 @@ Pipeline::Impl::~Impl() {
     surfaces.clear();
     cubes.clear();
     ext_keys.clear();
+    stat_planes.clear();
     groups.clear();
     bands.clear();
     band_buffers.clear();
@@ -44,6 +45,7 @@ Status Pipeline::Impl::init() {
         Status ok = detail::check_reduction_specs(cfg.reductions);
         if (ok.ok()) ok = detail::check_histograms(cfg);
         if (ok.ok()) ok = detail::check_extremes(cfg);
+        if (ok.ok()) ok = detail::check_cell_stats(cfg);
         if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
         if (!ok.ok()) return ok;
     }
@@ -121,6 +123,7 @@ Status Pipeline::Impl::init() {
     }
     hist = detail::plan_histograms(cfg, filters);
     ext = detail::plan_extremes(cfg, filters);
+    cstats = detail::plan_cell_stats(cfg, filters);
     if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
     if (!(s = detail::plan_terrain(cfg, ground, &terrain)).ok()) return s;
     if (!(s = detail::plan_surfaces(cfg)).ok()) return s;
@@ -189,6 +192,16 @@ Status Pipeline::Impl::init() {
         const size_t bytes = ext.entries[x].state_cells((size_t)std::max<int64_t>(cells, 1)) * sizeof(uint32_t);
         if (!(s = ext_keys[x].allocate(bytes, MemoryLocation::Device)).ok()) return s;
         if (!(s = detail::hip_status(pcr_hip_memset(ext_keys[x].data(), 0xFF, bytes, stream))).ok()) return s;
+    }
+    stat_planes.resize(cstats.entries.size());
+    for (auto& p : stat_planes) {                                 // all zero
+        const size_t c = (size_t)std::max<int64_t>(cells, 1);
+        detail::Buffer* bufs[3] = {&p.n, &p.s1, &p.s2};
+        const size_t bytes[3] = {c * sizeof(uint32_t), c * sizeof(int64_t), c * sizeof(uint64_t)};
+        for (int k = 0; k < 3; ++k) {
+            if (!(s = bufs[k]->allocate(bytes[k], MemoryLocation::Device)).ok()) return s;
+            if (!(s = detail::hip_status(pcr_hip_memset(bufs[k]->data(), 0, bytes[k], stream))).ok()) return s;
+        }
     }
     if (!outputs.empty() && !(s = allocate_result()).ok()) return s;
     if (!(s = d_bands_done.allocate(std::max<size_t>(groups.size(), 1) * sizeof(uint32_t), MemoryLocation::HostPinned)).ok()) return s;
@@ -277,6 +290,43 @@ Status Pipeline::Impl::extremes_values(int i, std::vector<float>* out) {
                                                  d_band, d_band + cells, stream));
     if (s.ok()) s = detail::hip_status(pcr_hip_memcpy_d2h(out->data(), d_band + cells, out->size() * sizeof(float), stream));
     const Status w = detail::hip_status(pcr_hip_stream_synchronize(stream));      // (d_tmp is released behind the kernel)
+    return s.ok() ? w : s;
+}
+// Behind the extremes' bands and ahead of the ground filter, which may read a cell-stats band ("z_mean"): one launch per entry
+// writes all of its raw bands; a Mean band then leaves like an Average band (filled when asked), the spread bands as they are.
+Status Pipeline::Impl::finalize_cell_stats(bool* enqueued) {
+    size_t r = cfg.reductions.size() + (size_t)hist.extra_bands() + (size_t)ext.extra_bands();
+    for (size_t x = 0; x < cstats.entries.size(); ++x) {
+        const detail::CellStatsEntry& e = cstats.entries[x];
+        std::vector<float*> dsts;
+        for (size_t j = 0; j < e.products.size(); ++j) dsts.push_back(bands[r + j].raw);
+        *enqueued = true;
+        Status s = detail::hip_status(pcr_hip_cell_stats_bands(&hg, static_cast<const uint32_t*>(stat_planes[x].n.data()),
+                                                               static_cast<const long long*>(stat_planes[x].s1.data()),
+                                                               static_cast<const unsigned long long*>(stat_planes[x].s2.data()), e.origin,
+                                                               e.resolution, e.ddof, (int)e.products.size(), e.products.data(), dsts.data(),
+                                                               stream));
+        for (size_t j = 0; j < e.products.size() && s.ok(); ++j) s = band_leaves(r + j, enqueued);
+        if (!s.ok()) return s;
+        r += e.products.size();
+    }
+    return Status::success();
+}
+// The three planes of entry i as host copies, behind everything on the pipeline's stream.
+Status Pipeline::Impl::cell_stats_state(int i, std::vector<uint32_t>* n, std::vector<int64_t>* s1, std::vector<uint64_t>* s2) {
+    if (i < 0 || (size_t)i >= stat_planes.size() || !n || !s1 || !s2)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: cell_stats_state: no cell_stats entry " + std::to_string(i));
+    DeviceScope dev(cfg.cuda_device_id);
+    const size_t cells = (size_t)hg.state_rows * hg.width;
+    n->assign(cells, 0u);
+    s1->assign(cells, 0);
+    s2->assign(cells, 0u);
+    if (cells == 0) return Status::success();
+    const StatPlanes& p = stat_planes[(size_t)i];
+    Status s = detail::hip_status(pcr_hip_memcpy_d2h(n->data(), p.n.data(), cells * sizeof(uint32_t), stream));
+    if (s.ok()) s = detail::hip_status(pcr_hip_memcpy_d2h(s1->data(), p.s1.data(), cells * sizeof(int64_t), stream));
+    if (s.ok()) s = detail::hip_status(pcr_hip_memcpy_d2h(s2->data(), p.s2.data(), cells * sizeof(uint64_t), stream));
+    const Status w = detail::hip_status(pcr_hip_stream_synchronize(stream));
     return s.ok() ? w : s;
 }
 // Behind the finalize kernels and the fills of every group, on the pipeline's stream: the filter on the RAW source band, the
@@ -890,6 +940,23 @@ Status Pipeline::Impl::scatter_extremes(Ingest& in) {
     return Status::success();
 }
 
+// PipelineConfig::cell_stats: each entry's three planes take the points its class keeps, likewise.
+Status Pipeline::Impl::scatter_cell_stats(Ingest& in) {
+    for (size_t x = 0; x < cstats.entries.size(); ++x) {
+        const detail::CellStatsEntry& e = cstats.entries[x];
+        const float* dv = nullptr;
+        Status s = in.channel(e.value_channel, &dv);
+        if (!s.ok()) return s;
+        pcr_hip_engine_set_point_mask(engine, in.class_mask[(size_t)e.cls]);
+        s = detail::hip_status(pcr_hip_scatter_cell_stats(engine, static_cast<uint32_t*>(stat_planes[x].n.data()),
+                                                          static_cast<long long*>(stat_planes[x].s1.data()),
+                                                          static_cast<unsigned long long*>(stat_planes[x].s2.data()), e.origin, e.inv_res,
+                                                          static_cast<const double*>(in.dx), static_cast<const double*>(in.dy), dv, in.n));
+        if (!s.ok()) return s;
+    }
+    return Status::success();
+}
+
 Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     Ingest in{cloud, cloud.count()};
     if (in.n == 0) return Status::success();
@@ -926,6 +993,7 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     if (!(s = scatter_groups(in)).ok()) return s;
     if (!(s = scatter_histograms(in)).ok()) return s;
     if (!(s = scatter_extremes(in)).ok()) return s;
+    if (!(s = scatter_cell_stats(in)).ok()) return s;
     // host arrays may be reused by the caller as soon as we return (ingest_async: page-locked arrays are
     // read by the DMA engine later, the caller keeps them alive until synchronize())
     const MemoryLocation loc = cloud.location();
@@ -1060,6 +1128,7 @@ Status Pipeline::Impl::finalize(bool wait) {
     }
     if (!(s = finalize_histograms(&enqueued)).ok()) return s;
     if (!(s = finalize_extremes(&enqueued)).ok()) return s;
+    if (!(s = finalize_cell_stats(&enqueued)).ok()) return s;
     if (!(s = finalize_ground(&enqueued)).ok()) return s;
     if (!(s = finalize_terrain(&enqueued)).ok()) return s;
     // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
@@ -1199,6 +1268,7 @@ Status Pipeline::Impl::import_window(const std::vector<std::vector<float>>& plan
 Status Pipeline::Impl::save_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
+    if (!cfg.cell_stats.empty()) return detail::cell_stats_checkpoint_error();
     std::string dir;
     Status s = checkpoint_dir(dir_in, &dir, true);
     if (!s.ok()) return s;
@@ -1211,6 +1281,7 @@ Status Pipeline::Impl::save_state(const std::string& dir_in) {
 Status Pipeline::Impl::load_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
+    if (!cfg.cell_stats.empty()) return detail::cell_stats_checkpoint_error();
     std::string dir;
     Status s = checkpoint_dir(dir_in, &dir, false);
     if (!s.ok()) return s;

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "buffer.h"
+#include "cell_stats.h"
 #include "extremes.h"
 #include "ground_filter.h"
 #include "histogram.h"
@@ -103,6 +104,10 @@ struct Pipeline::Impl {
     detail::ExtremesPlan ext;                // PipelineConfig::extremes, planned at init
     std::vector<detail::Buffer> ext_keys;    // entry by entry: keys[k][state_rows * width] in HBM, all EMPTY at create and only
                                              // ever lowered: no part in the plane-state rules
+    detail::CellStatsPlan cstats;             // PipelineConfig::cell_stats, planned at init
+    struct StatPlanes { detail::Buffer n, s1, s2; };
+    std::vector<StatPlanes> stat_planes;     // entry by entry: N (uint32), S1 (int64), S2 (uint64) over state_rows * width in HBM,
+                                             // zeroed at create and only ever added to: no part in the plane-state rules
     std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in HBM (set_surface)
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
@@ -170,6 +175,8 @@ struct Pipeline::Impl {
     Status histogram_counts(int i, std::vector<uint32_t>* out);
     Status finalize_extremes(bool* enqueued);
     Status extremes_values(int i, std::vector<float>* out);
+    Status finalize_cell_stats(bool* enqueued);
+    Status cell_stats_state(int i, std::vector<uint32_t>* n, std::vector<int64_t>* s1, std::vector<uint64_t>* s2);
     Status finalize_ground(bool* enqueued);
     Status finalize_terrain(bool* enqueued);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
@@ -193,6 +200,7 @@ struct Pipeline::Impl {
     Status scatter_groups(Ingest& in);
     Status scatter_histograms(Ingest& in);
     Status scatter_extremes(Ingest& in);
+    Status scatter_cell_stats(Ingest& in);
     Status marshal_glyph(const GlyphSpec& gl, const detail::ChannelLookup& channel, pcr_hip_glyph* out) const;
     Status allocate_result();
     Status checkpoint_dir(const std::string& dir_in, std::string* dir, bool writing) const;

@@ -1,6 +1,7 @@
 // host_engine.cpp -- see host_engine.h.  Arithmetic after the reference's CPU path, cited at each step; structure ours.
 #include "host_engine.h"
 
+#include "../../csrc/cell_stats.hpp"
 #include "../../csrc/extremes.hpp"
 #include "../../csrc/histogram.hpp"
 #include "pipeline_common.h"
@@ -316,6 +317,29 @@ void HostEngine::scatter_extremes(uint32_t* keys, int k, int side, const float* 
         for (size_t j = first[(size_t)s]; j < first[(size_t)s + 1]; ++j) {
             const uint32_t i = list[j];
             pcrhip::ext::insert_sorted(keys + ((size_t)row_[i] * W_ + (size_t)col_[i]), plane_cells, k, pcrhip::ext::key_of(v[i], side));
+        }
+    }
+}
+
+void HostEngine::scatter_cell_stats(uint32_t* n, int64_t* s1, uint64_t* s2, double origin, double inv_res, const float* v,
+                                    const uint8_t* keep) {
+    if (n_ == 0 || !v || !n || !s1 || !s2) return;
+    std::vector<uint32_t> list;
+    std::vector<size_t> first;
+    build_lists(list, first, [&](size_t i, Span& sp) {
+        if (row_[i] < 0 || (keep && !keep[i]) || v[i] != v[i]) return false;
+        sp.lo = sp.hi = row_[i];
+        return true;
+    });
+#pragma omp parallel for num_threads(threads_) schedule(dynamic, 1)
+    for (int s = 0; s < nstripes_; ++s) {
+        for (size_t j = first[(size_t)s]; j < first[(size_t)s + 1]; ++j) {
+            const uint32_t i = list[j];
+            const int64_t q = pcrhip::cs::step_of(v[i], origin, inv_res);
+            const size_t cell = (size_t)row_[i] * W_ + (size_t)col_[i];
+            n[cell] += 1u;
+            s1[cell] += q;
+            s2[cell] += (uint64_t)(q * q);
         }
     }
 }

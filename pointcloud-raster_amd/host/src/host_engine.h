@@ -69,6 +69,11 @@ public:
     /// Stripe-owned like the other folds, no atomics; the k smallest distinct keys of a set, so the bits are the same at any
     /// thread count.
     void scatter_extremes(uint32_t* keys, int k, int side, const float* v, const uint8_t* keep = nullptr);
+    /// PipelineConfig::cell_stats: every routed point the keep mask keeps whose value is not NaN adds 1, its step q and q * q
+    /// to the three planes of its cell (csrc/cell_stats.hpp; include/pcr_hip.h, "per-cell stats").  n, s1, s2: height * width
+    /// each.  Stripe-owned like the other folds, no atomics; integer addition, so the bits are the same at any thread count.
+    void scatter_cell_stats(uint32_t* n, int64_t* s1, uint64_t* s2, double origin, double inv_res, const float* v,
+                            const uint8_t* keep = nullptr);
     /// A select group's planes as a checkpoint left them -> the canonical form a fold leaves (a NaN or <= -FLT_MAX timestamp
     /// means empty: {NaN, -FLT_MAX}; a -0.0 timestamp is +0.0).
     void normalize_select(HostPlanes& p) const;

@@ -22,6 +22,7 @@ Status Pipeline::Host::init() {
         Status ok = detail::check_reduction_specs(cfg.reductions);
         if (ok.ok()) ok = detail::check_histograms(cfg);
         if (ok.ok()) ok = detail::check_extremes(cfg);
+        if (ok.ok()) ok = detail::check_cell_stats(cfg);
         if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
         if (!ok.ok()) return ok;
     }
@@ -47,6 +48,14 @@ Status Pipeline::Host::init() {
     // PipelineConfig::extremes: the key planes, all EMPTY
     ext = detail::plan_extremes(cfg, filters);
     for (const auto& e : ext.entries) ext_keys.emplace_back(e.state_cells((size_t)g.width * g.height), 0xFFFFFFFFu);
+    // PipelineConfig::cell_stats: the three planes, zero
+    cstats = detail::plan_cell_stats(cfg, filters);
+    stat_planes.resize(cstats.entries.size());
+    for (auto& p : stat_planes) {
+        p.n.assign((size_t)g.width * g.height, 0u);
+        p.s1.assign((size_t)g.width * g.height, 0);
+        p.s2.assign((size_t)g.width * g.height, 0u);
+    }
     // Tile state is identity-initialised (src/engine/tile_manager.cpp:183-260); here for the whole grid at once.
     for (auto& gr : groups) engine->init_planes(gr.planes, gr.mask, gr.select);
     return Status::success();
@@ -164,6 +173,7 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     auto keep_of = [&](const Group& gr, size_t i0) -> const uint8_t* { return gr.cls ? class_keep[(size_t)gr.cls].data() + i0 : nullptr; };
     auto hist_keep = [&](const detail::HistogramEntry& e, size_t i0) -> const uint8_t* { return e.cls ? class_keep[(size_t)e.cls].data() + i0 : nullptr; };
     auto ext_keep = [&](const detail::ExtremesEntry& e, size_t i0) -> const uint8_t* { return e.cls ? class_keep[(size_t)e.cls].data() + i0 : nullptr; };
+    auto stat_keep = [&](const detail::CellStatsEntry& e, size_t i0) -> const uint8_t* { return e.cls ? class_keep[(size_t)e.cls].data() + i0 : nullptr; };
 
     // the engine indexes a cloud with 32 bits: larger ones go in slices
     const size_t slice = (size_t)1 << 31;
@@ -199,6 +209,11 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         for (size_t x = 0; x < ext.entries.size(); ++x) {
             const detail::ExtremesEntry& e = ext.entries[x];
             engine->scatter_extremes(ext_keys[x].data(), e.k, e.side, f32(e.value_channel) + i0, ext_keep(e, i0));
+        }
+        for (size_t x = 0; x < cstats.entries.size(); ++x) {
+            const detail::CellStatsEntry& e = cstats.entries[x];
+            StatPlanes& p = stat_planes[x];
+            engine->scatter_cell_stats(p.n.data(), p.s1.data(), p.s2.data(), e.origin, e.inv_res, f32(e.value_channel) + i0, stat_keep(e, i0));
         }
     }
     last = ScatterInfo{};
@@ -251,6 +266,15 @@ Status Pipeline::Host::finalize() {
                                                engine->threads());
         if (!es.ok()) return es;
     }
+    for (size_t x = 0, r = cfg.reductions.size() + (size_t)hist.extra_bands() + (size_t)ext.extra_bands(); x < cstats.entries.size(); ++x) {
+        const detail::CellStatsEntry& e = cstats.entries[x];
+        std::vector<float*> dsts;
+        for (size_t j = 0; j < e.products.size(); ++j) dsts.push_back(result->band_f32((int)(r + j)));
+        Status cs = detail::cell_stats_bands_host(e, stat_planes[x].n.data(), stat_planes[x].s1.data(), stat_planes[x].s2.data(), g.width,
+                                                  g.height, dsts.data(), engine->threads());
+        if (!cs.ok()) return cs;
+        r += e.products.size();
+    }
     {                                                                // (the planes are the state: the bands are made anew by every finalize)
         std::vector<ReductionType> types;
         for (const auto& o : outputs) types.push_back(o.type);
@@ -265,6 +289,7 @@ Status Pipeline::Host::finalize() {
 Status Pipeline::Host::save_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
+    if (!cfg.cell_stats.empty()) return detail::cell_stats_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     detail::StateWindow w;
@@ -277,6 +302,7 @@ Status Pipeline::Host::save_state(const std::string& dir_in) {
 Status Pipeline::Host::load_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
+    if (!cfg.cell_stats.empty()) return detail::cell_stats_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     detail::StateWindow w;

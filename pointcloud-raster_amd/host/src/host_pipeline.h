@@ -3,6 +3,7 @@
 // Same validation, messages, band naming, progress callback and `.pcrt` checkpoints as the HIP pipeline.
 #pragma once
 
+#include "cell_stats.h"
 #include "extremes.h"
 #include "histogram.h"
 #include "host_engine.h"
@@ -34,6 +35,13 @@ struct Pipeline::Host {
     std::vector<std::vector<uint32_t>> cubes;    // entry by entry: count[bins][height * width], zero at create
     detail::ExtremesPlan ext;            // PipelineConfig::extremes, planned at init
     std::vector<std::vector<uint32_t>> ext_keys; // entry by entry: keys[k][height * width], all EMPTY (0xFFFFFFFF) at create
+    detail::CellStatsPlan cstats;         // PipelineConfig::cell_stats, planned at init
+    struct StatPlanes {                  // entry by entry: N, S1, S2 over height * width, zero at create
+        std::vector<uint32_t> n;
+        std::vector<int64_t> s1;
+        std::vector<uint64_t> s2;
+    };
+    std::vector<StatPlanes> stat_planes;
     std::unique_ptr<Grid> result;
     bool finalized = false;
     ProgressCallback callback;

@@ -15,6 +15,7 @@
 #include "banded_pipeline.h"
 #include "device_pipeline.h"
 #include "ground_filter.h"
+#include "cell_stats.h"
 #include "extremes.h"
 #include "histogram.h"
 #include "terrain.h"
@@ -63,6 +64,10 @@ std::vector<std::string> named_channels(const PipelineConfig& c) {
         add(e.value_channel);
         for (const auto& p : e.filter.predicates) add(p.channel_name);
     }
+    for (const auto& s : c.cell_stats) {
+        add(s.value_channel);
+        for (const auto& p : s.filter.predicates) add(p.channel_name);
+    }
     for (const auto& sc : c.surface_channels) add(sc.value_channel);
     return out;
 }
@@ -100,6 +105,8 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         if (!hs.ok()) return fail_with(hs);
         const Status es = detail::check_extremes(config);       // (likewise)
         if (!es.ok()) return fail_with(es);
+        const Status cs = detail::check_cell_stats(config);     // (likewise)
+        if (!cs.ok()) return fail_with(cs);
     }
     {
         detail::GroundPlan plan;                      // (every engine plans again for itself: here only the refusals)
@@ -118,6 +125,7 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         if (!config.surface_channels.empty()) return fail_with(detail::surfaces_out_of_core_error());
         if (!config.histograms.empty()) return fail_with(detail::histograms_out_of_core_error());
         if (!config.extremes.empty()) return fail_with(detail::extremes_out_of_core_error());
+        if (!config.cell_stats.empty()) return fail_with(detail::cell_stats_out_of_core_error());
         Status bs = Status::success();
         p->banded_ = Banded::create(config, p.get(), budget, &bs);
         if (!p->banded_) return fail_with(bs);
@@ -309,6 +317,23 @@ Status Pipeline::extremes_shape(int i, int* k, int* rows, int* width) const {
     if (!c || i < 0 || (size_t)i >= c->extremes.size() || !k || !rows || !width)
         return Status::error(StatusCode::InvalidArgument, "pipeline: extremes_values: no extremes entry " + std::to_string(i));
     *k = c->extremes[(size_t)i].k;
+    *rows = c->grid.height;                                  // (a row-block shard is refused: the window is the grid)
+    *width = c->grid.width;
+    return Status::success();
+}
+Status Pipeline::cell_stats_state(int i, std::vector<uint32_t>* n, std::vector<int64_t>* s1, std::vector<uint64_t>* s2) const {
+    if (impl_) return impl_->cell_stats_state(i, n, s1, s2);
+    if (!host_ || i < 0 || (size_t)i >= host_->stat_planes.size() || !n || !s1 || !s2)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: cell_stats_state: no cell_stats entry " + std::to_string(i));
+    *n = host_->stat_planes[(size_t)i].n;
+    *s1 = host_->stat_planes[(size_t)i].s1;
+    *s2 = host_->stat_planes[(size_t)i].s2;
+    return Status::success();
+}
+Status Pipeline::cell_stats_shape(int i, int* rows, int* width) const {
+    const PipelineConfig* c = host_ ? &host_->cfg : impl_ ? &impl_->cfg : nullptr;
+    if (!c || i < 0 || (size_t)i >= c->cell_stats.size() || !rows || !width)
+        return Status::error(StatusCode::InvalidArgument, "pipeline: cell_stats_state: no cell_stats entry " + std::to_string(i));
     *rows = c->grid.height;                                  // (a row-block shard is refused: the window is the grid)
     *width = c->grid.width;
     return Status::success();

@@ -56,6 +56,15 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
         if (!d || d->dtype != DataType::Float32)
             return Status::error(StatusCode::InvalidArgument, "pipeline: extremes value channel must be Float32");
     }
+    for (const auto& c : cfg.cell_stats) {                     // PipelineConfig::cell_stats: likewise
+        if (!(fs = check_filter(c.filter)).ok()) return fs;
+        if (derived(c.value_channel)) continue;
+        if (!cloud.channel_data(c.value_channel))
+            return Status::error(StatusCode::InvalidArgument, "pipeline: cell_stats value channel not found: " + c.value_channel);
+        const ChannelDesc* d = cloud.channel(c.value_channel);
+        if (!d || d->dtype != DataType::Float32)
+            return Status::error(StatusCode::InvalidArgument, "pipeline: cell_stats value channel must be Float32");
+    }
     for (const auto& r : cfg.reductions) {
         if (!derived(r.value_channel)) {
             if (!cloud.channel_data(r.value_channel))
@@ -96,6 +105,7 @@ Status plan_filters(const PipelineConfig& cfg, FilterPlan* out) {
     for (const auto& r : cfg.reductions) out->class_of.push_back(class_for(r.filter));
     for (const auto& h : cfg.histograms) out->hist_class_of.push_back(class_for(h.filter));   // (a histogram's filter is one more class)
     for (const auto& e : cfg.extremes) out->ext_class_of.push_back(class_for(e.filter));      // (and so is an extremes entry's)
+    for (const auto& c : cfg.cell_stats) out->stat_class_of.push_back(class_for(c.filter));   // (and a cell-stats entry's)
     if (out->classes.size() - 1 > kMaxSpecFilters)
         return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(kMaxSpecFilters) +
                                                           " distinct reduction filters in one pipeline");
@@ -234,6 +244,16 @@ GroupPlan plan_groups(const PipelineConfig& cfg) {
         o.ext = (int)i;
         plan.outputs.push_back(o);
     }
+    for (size_t i = 0; i < cfg.cell_stats.size(); ++i)
+        for (size_t j = 0; j < cfg.cell_stats[i].products.size(); ++j) {
+            Output o;
+            o.group = -1;
+            o.type = cfg.cell_stats[i].products[j] == CellStat::Mean ? ReductionType::Average : ReductionType::Sum;
+            o.band_name = cell_stats_band_name(cfg.cell_stats[i], j);
+            o.stat = (int)i;
+            o.product = (int)j;
+            plan.outputs.push_back(o);
+        }
     return plan;
 }
 

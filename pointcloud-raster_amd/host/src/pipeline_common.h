@@ -136,6 +136,12 @@ inline std::string extremes_band_name(const ExtremesConfig& e) {
     if (!e.band_name.empty()) return e.band_name;
     return e.value_channel + (e.side == ExtremeSide::Highest ? "_high" : "_low");
 }
+// PipelineConfig::cell_stats: the name of band j of an entry, "{value_channel}_mean" / "_var" / "_std" unless given.
+inline std::string cell_stats_band_name(const CellStatsConfig& c, size_t j) {
+    if (j < c.band_names.size() && !c.band_names[j].empty()) return c.band_names[j];
+    const CellStat p = j < c.products.size() ? c.products[j] : CellStat::StdDev;
+    return c.value_channel + (p == CellStat::Mean ? "_mean" : p == CellStat::Variance ? "_var" : "_std");
+}
 // ReductionSpec::filter: equal means the same predicates in the same order, field by field.
 inline bool same_predicate(const FilterPredicate& a, const FilterPredicate& b) {
     return a.channel_name == b.channel_name && a.op == b.op && a.value == b.value && a.value_set == b.value_set;
@@ -174,13 +180,18 @@ struct Output {                          // one band finalize makes from the sta
     std::string band_name;
     int hist = -1, q = 0;                // the histogram and which of its percentiles
     int ext = -1;                        // the extremes entry
+    int stat = -1, product = 0;          // the cell-stats entry and which of its products (group -1 too; the type is Average for
+                                         // a Mean band, filled like an Average band, and Sum for Variance and StdDev, which
+                                         // fills_nodata rejects: a spread is never filled.  The type of a group -1 output decides
+                                         // nothing but that)
 };
 struct GroupPlan {
     std::vector<GroupSpec> groups;       // in order of first appearance among the ReductionSpecs: reduction_groups(), state_planes(),
                                          // parked windows (planes[4 g + p]) and the `.pcrt` directories all count them this way
     std::vector<Output> outputs;         // the result grid's order: one per ReductionSpec, then the histograms' percentile bands entry
-                                         // by entry, then one band per extremes entry.  What ground.source_band, ground.top_band
-                                         // and terrain[].source_band may name (the DTM, hag and terrain bands follow them)
+                                         // by entry, then one band per extremes entry, then the cell-stats bands entry by entry.
+                                         // What ground.source_band, ground.top_band and terrain[].source_band may name (the DTM,
+                                         // hag and terrain bands follow them)
 };
 GroupPlan plan_groups(const PipelineConfig& cfg);
 // The outputs a checkpoint carries (write_state_tiles, read_state_tiles): those with a group.
@@ -237,6 +248,7 @@ struct FilterPlan {
     std::vector<int> class_of;               // per ReductionSpec
     std::vector<int> hist_class_of;          // per entry of PipelineConfig::histograms: its filter joins the same plan
     std::vector<int> ext_class_of;           // per entry of PipelineConfig::extremes: likewise
+    std::vector<int> stat_class_of;          // per entry of PipelineConfig::cell_stats: likewise
     std::vector<FilterPredicate> table;      // PipelineConfig::filter's predicates first
     std::vector<uint32_t> words;             // per class; words[0] == 0: no PipelineConfig::filter
     bool any() const { return classes.size() > 1; }

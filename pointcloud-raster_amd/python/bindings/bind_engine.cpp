@@ -160,6 +160,34 @@ void bind_engine(py::module_& m) {
         .def_readwrite("filter", &ExtremesConfig::filter)
         .def_readwrite("band_name", &ExtremesConfig::band_name);
 
+    py::enum_<CellStat>(m, "CellStat")
+        .value("Mean", CellStat::Mean)
+        .value("Variance", CellStat::Variance)
+        .value("StdDev", CellStat::StdDev);
+
+    py::class_<CellStatsConfig>(m, "CellStatsConfig",
+                                "The exact mean, variance and standard deviation of a Float32 channel per cell (a surface channel "
+                                "included), from integer sums of the value quantized to a step")
+        .def(py::init<>())
+        .def(py::init<const CellStatsConfig&>())
+        .def(py::init([](const std::string& value_channel, double origin, double resolution, const std::vector<CellStat>& products, int ddof) {
+            CellStatsConfig c;
+            c.value_channel = value_channel;
+            c.origin = origin;
+            c.resolution = resolution;
+            c.products = products;
+            c.ddof = ddof;
+            return c;
+        }), py::arg("value_channel"), py::arg("origin") = 0.0, py::arg("resolution") = 0.01,
+            py::arg("products") = std::vector<CellStat>{CellStat::StdDev}, py::arg("ddof") = 0)
+        .def_readwrite("value_channel", &CellStatsConfig::value_channel)
+        .def_readwrite("origin", &CellStatsConfig::origin)
+        .def_readwrite("resolution", &CellStatsConfig::resolution)
+        .def_readwrite("products", &CellStatsConfig::products)
+        .def_readwrite("ddof", &CellStatsConfig::ddof)
+        .def_readwrite("filter", &CellStatsConfig::filter)
+        .def_readwrite("band_names", &CellStatsConfig::band_names);
+
     py::class_<PipelineConfig>(m, "PipelineConfig")
         .def(py::init<>())
         .def_readwrite("grid", &PipelineConfig::grid)
@@ -201,7 +229,10 @@ void bind_engine(py::module_& m) {
                        "reductions' bands (assign a list of HistogramConfig)")
         .def_readwrite("extremes", &PipelineConfig::extremes,
                        "Per-cell k lowest / highest distinct values kept at every ingest and the outlier-free Min / Max band "
-                       "finalize() appends behind the percentile bands (assign a list of ExtremesConfig)");
+                       "finalize() appends behind the percentile bands (assign a list of ExtremesConfig)")
+        .def_readwrite("cell_stats", &PipelineConfig::cell_stats,
+                       "Per-cell integer sums kept at every ingest and the exact Mean / Variance / StdDev bands finalize() appends "
+                       "behind the extremes' bands (assign a list of CellStatsConfig)");
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
         .def(py::init<>())
@@ -257,6 +288,25 @@ void bind_engine(py::module_& m) {
         }, py::arg("i") = 0,
              "The values extremes entry i keeps as a numpy.float32 array (k, height, width), ascending (Lowest) or descending "
              "(Highest), NaN for an empty slot: a host copy, valid after any ingest")
+        .def("cell_stats", [](const Pipeline& p, int i) {
+            std::vector<uint32_t> n;
+            std::vector<int64_t> s1;
+            std::vector<uint64_t> s2;
+            raise_if_error(p.cell_stats_state(i, &n, &s1, &s2));
+            int rows = 0, width = 0;
+            raise_if_error(p.cell_stats_shape(i, &rows, &width));
+            py::array_t<uint32_t> an({(py::ssize_t)rows, (py::ssize_t)width});
+            py::array_t<int64_t> a1({(py::ssize_t)rows, (py::ssize_t)width});
+            py::array_t<uint64_t> a2({(py::ssize_t)rows, (py::ssize_t)width});
+            if (n.size() != (size_t)an.size() || s1.size() != n.size() || s2.size() != n.size())
+                throw std::runtime_error("pipeline: cell_stats: unexpected size");
+            std::memcpy(an.mutable_data(), n.data(), n.size() * sizeof(uint32_t));
+            std::memcpy(a1.mutable_data(), s1.data(), s1.size() * sizeof(int64_t));
+            std::memcpy(a2.mutable_data(), s2.data(), s2.size() * sizeof(uint64_t));
+            return py::make_tuple(an, a1, a2);
+        }, py::arg("i") = 0,
+             "The state of cell_stats entry i as (N, S1, S2): numpy uint32, int64 and uint64 arrays (height, width) -- the count, "
+             "the sum of the steps and the sum of their squares: host copies, valid after any ingest")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },
              "Device-resident result: the finalize kernels are only enqueued on the pipeline's stream (complete after synchronize()); "

@@ -77,7 +77,7 @@ from ._pcr import (  # noqa: E402,F401
     GroundFilterSpec, GroundFilterConfig, ground_filter, ground_filter_levels,
     TerrainProduct, TerrainSpec, TerrainBandConfig, terrain, terrain_light,
     SampleMode, SurfaceChannelConfig, sample_grid,
-    HistogramConfig, ExtremeSide, ExtremesConfig,
+    HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig,
 )
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
@@ -180,5 +180,5 @@ __all__ = [
     "GroundFilterSpec", "GroundFilterConfig", "ground_filter", "ground_filter_levels",
     "TerrainProduct", "TerrainSpec", "TerrainBandConfig", "terrain", "terrain_light",
     "SampleMode", "SurfaceChannelConfig", "sample_grid",
-    "HistogramConfig", "ExtremeSide", "ExtremesConfig",
+    "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig",
 ]

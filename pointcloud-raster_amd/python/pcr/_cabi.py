@@ -200,6 +200,11 @@ SYMBOLS = {
     "pcr_hip_scatter_extremes": [_VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, _U64],
     "pcr_hip_extremes_band": [C.POINTER(Grid), _VP, C.c_int, C.c_int, C.c_float, _VP, _VP, _VP],
     "pcr_hip_extremes_band_host": [C.POINTER(Grid), _VP, C.c_int, C.c_int, C.c_float, _VP, _VP],
+    "pcr_hip_scatter_cell_stats": [_VP, _VP, _VP, _VP, C.c_double, C.c_double, _VP, _VP, _VP, _U64],
+    "pcr_hip_cell_stats_bands": [C.POINTER(Grid), _VP, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                 C.POINTER(_VP), _VP],
+    "pcr_hip_cell_stats_bands_host": [C.POINTER(Grid), _VP, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                      C.POINTER(_VP)],
 }
 
 _lib = None
