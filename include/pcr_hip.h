@@ -613,6 +613,58 @@ int pcr_hip_terrain(const float* src, int width, int height, int64_t src_stride,
                     float* const* dsts, const int64_t* dst_strides, double cell_size_x, double cell_size_y, double z_factor,
                     int edges, double sin_alt, double ls, double lc, pcr_hip_stream s);
 
+/* ---- individual trees of a canopy band (pcr/core/trees.h: segment_trees; lidR's locate_trees(lmf(ws)) followed by a seeded
+ *      descent in the manner of segment_trees(dalponte2016())).  No reference counterpart.  The contract is written once, in
+ *      csrc/trees.hpp, which the kernels and the host twin both compile with contraction off; it is comparisons and integer
+ *      arithmetic throughout, so they agree bit for bit.
+ *        input    one Float32 band H, width x height; a cell that is not finite (NaN, +-Inf) is no data, every other a data
+ *                 cell; idx(r, c) = r * width + c; width * height < 2^31
+ *        consts   cell = max(|cell_size_x|, |cell_size_y|); k = 0.5 / cell (refused unless finite); M = -1 when
+ *                 max_crown_radius is +Inf, else (int64)min(floor((double)max_crown_radius / cell), 2^31 - 1)
+ *        order    a beats b when H[a] > H[b], or H[a] == H[b] and idx(a) < idx(b) (binary32 comparisons; -0.0 == +0.0)
+ *        window   d = (double)window_base + (double)window_slope * (double)H[c], two rounded operations; rho = d * k;
+ *                 R(c) = max_radius_cells if rho >= max_radius_cells, 0 if !(rho >= 1), else (int)rho.  The disc of c: the data
+ *                 cells at dr*dr + dc*dc <= R*R inside the image; best(c): its greatest cell, c included
+ *        top      a data cell with H[c] >= min_height and best(c) == c; tops are numbered 1..T in increasing idx
+ *        crown    set: the tops and every data cell with H[c] >= min_crown_height
+ *        parent   of a crown cell: a top is its own; else the greatest of its eight neighbours that are data cells and beat c;
+ *                 if there is none, best(c) when that is not c, else c.  root(c): the fixpoint of parent
+ *        label    id(root) when root is a top, and c == root or H[c] >= crown_ratio * H[root] (one binary32 multiplication),
+ *                 and M < 0 or dr*dr + dc*dc <= M*M in 64-bit integers, (dr, dc) from c to its root; else none
+ *        bands    id_dst (float)id, height_dst H[root] bit for bit, both 0x7FC00000 without a label.  Ids above 2^24 are not
+ *                 exact in Float32: cells of such trees are 0x7FC00000 in both bands
+ *        table    per top in id order: row, col, height = H[top], crown_cells = the cells whose label is the id
+ *      Parameter ranges: min_height, min_crown_height finite; window_base, window_slope finite and >= 0; max_radius_cells
+ *      1..32; crown_ratio in [0, 1]; max_crown_radius > 0 or +Inf.  Bands: `height` rows of `width` floats, strides in floats,
+ *      any 4-byte alignment (rows on 16 bytes take the 16-byte accesses); height_dst may be NULL.  No dst may overlap src, the
+ *      other dst or the work area.  d_work: device memory of at least pcr_hip_trees_work_bytes(width, height) bytes (about
+ *      12 bytes per cell; answered without a device), the caller's; it carries T, the ids and the crown counts from
+ *      pcr_hip_trees to _count and _table.  Argument errors are reported before any HIP call.
+ *      pcr_hip_trees: everything is enqueued on s, ceil(log2(width * height)) + 1 pointer-jumping rounds included (a round
+ *      returns at once when the one before changed nothing); nothing is allocated or synchronised.
+ *      pcr_hip_trees_count: T (and, when asked, how many jumping rounds changed a pointer), after synchronising with s.
+ *      pcr_hip_trees_table: rows 0 .. n - 1 of the table into device arrays (any may be NULL), enqueued on s.
+ *      pcr_hip_trees_host: the host twin on host arrays, bands and table in one call: *n = T, the first min(T, capacity) rows
+ *      are written (n and the arrays may be NULL). */
+typedef struct pcr_hip_tree_params {
+    float min_height, window_base, window_slope;
+    int32_t max_radius_cells;
+    float min_crown_height, crown_ratio, max_crown_radius;
+    int32_t stop_after;              /* 0: everything.  k = 1..4: pcr_hip_trees enqueues only its first k phases (cells, discs,
+                                        numbering, jumping; the labels are the fifth) -- for timing them by difference
+                                        (tools/trees_time.py); the bands are then not written */
+    double cell_size_x, cell_size_y;
+} pcr_hip_tree_params;
+int pcr_hip_trees_work_bytes(int width, int height, size_t* bytes);
+int pcr_hip_trees(const float* src, int width, int height, int64_t src_stride, const pcr_hip_tree_params* params, float* id_dst,
+                  int64_t id_stride, float* height_dst, int64_t height_stride, void* d_work, size_t work_bytes, pcr_hip_stream s);
+int pcr_hip_trees_count(const void* d_work, size_t work_bytes, int64_t* n, int* rounds_worked, pcr_hip_stream s);
+int pcr_hip_trees_table(const float* src, int width, int height, int64_t src_stride, const void* d_work, size_t work_bytes,
+                        int64_t n, int32_t* d_rows, int32_t* d_cols, float* d_heights, int32_t* d_crown_cells, pcr_hip_stream s);
+int pcr_hip_trees_host(const float* src, int width, int height, int64_t src_stride, const pcr_hip_tree_params* params,
+                       float* id_dst, int64_t id_stride, float* height_dst, int64_t height_stride, int64_t* n, int64_t capacity,
+                       int32_t* rows, int32_t* cols, float* heights, int32_t* crown_cells);
+
 /* ---- LAS point records -> the SoA cloud (pcr/io/point_cloud_io.h: LAS input).  No reference counterpart: the reference
  *      declares the format and reads `.las` tiles through laspy in a script.  ASPRS LAS 1.0-1.4, point data record formats
  *      0-10, little-endian, array-of-structures: int32 X, Y, Z, then packed attributes (csrc/las_decode.hpp holds the table).

@@ -73,6 +73,7 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "csrc", "fill_nodata.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "ground_filter.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "terrain.hpp"))
+    hdrs.append(os.path.join(HERE, "csrc", "trees.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "las_decode.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "histogram.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "extremes.hpp"))

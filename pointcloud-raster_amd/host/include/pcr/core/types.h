@@ -26,7 +26,8 @@ enum class ReductionType : uint8_t {
 enum class MemoryLocation : uint8_t { Host, HostPinned, Device };
 
 enum class StatusCode : uint8_t {
-    Ok, InvalidArgument, OutOfMemory, CudaError, IoError, CrsError, NotImplemented
+    Ok, InvalidArgument, OutOfMemory, CudaError, IoError, CrsError, NotImplemented,
+    OutOfRange                      // extension: a result too large for its representation (pcr/core/trees.h)
 };
 
 struct Status {

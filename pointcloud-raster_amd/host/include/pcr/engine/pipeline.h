@@ -12,6 +12,7 @@
 #include "pcr/core/ground_filter.h"
 #include "pcr/core/sample_grid.h"
 #include "pcr/core/terrain.h"
+#include "pcr/core/trees.h"
 #include "pcr/core/types.h"
 #include "pcr/engine/filter.h"
 #include "pcr/engine/glyph.h"
@@ -67,6 +68,13 @@ struct TerrainBandConfig : TerrainSpec {
     std::string source_band;             // any band of the result by name, the ground filter's DTM and hag bands included
     TerrainProduct product = TerrainProduct::Hillshade;
     std::string band_name;               // default "{source_band}_{terrain_product_name(product)}"
+};
+
+/// One entry of PipelineConfig::trees: the tree_id and tree_height bands (pcr/core/trees.h) of one band, appended at finalize().
+struct TreeBandConfig : TreeSpec {
+    std::string source_band;             // a reduction, percentile, extremes or cell-stats band, the DTM or the hag band, by name
+    std::string id_band_name;            // default "{source_band}_tree_id"
+    std::string height_band_name;        // default "{source_band}_tree_height"
 };
 
 /// One entry of PipelineConfig::surface_channels: a per-point Float32 channel the pipeline derives at ingest from a finished
@@ -229,6 +237,15 @@ struct PipelineConfig {
     // ordinary bands ("average" overviews of an aspect band are not meaningful near north); the accumulation state is
     // untouched.  Empty: nothing is allocated or launched.  A row-block shard refuses it.
     std::vector<TerrainBandConfig> terrain;
+    // Individual trees: finalize() appends, behind the terrain bands and in list order, two bands per entry -- tree_id and
+    // tree_height of pcr/core/trees.h of the named band AS IT LEAVES the pipeline (filled), with the grid's cell sizes; the
+    // canopy height model is a Max of a "hag" surface channel.  The new bands are never filled.  A source is any reduction,
+    // percentile, extremes or cell-stats band, the DTM or the hag band; terrain and tree bands are none.  result(), the GeoTIFF
+    // and its overview levels carry the bands as ordinary bands ("average" overviews of an id band are not meaningful);
+    // Pipeline::trees reads an entry's table.  The accumulation state is untouched.  create() refuses more than 4 entries, an
+    // unknown source, a band name that collides with any other leaving band, a parameter outside its range and a row-block
+    // shard, each naming the entry.  Empty: nothing is allocated, launched or validated differently.
+    std::vector<TreeBandConfig> trees;
     // ingest_file of a LAS file: subtracted from the GPS time, in Float64, before it becomes the Float32 `gps_time` channel
     // (LasOptions::gps_time_origin; a MostRecent timestamp needs it: Float32 resolves 32 s at 3e8 s).
     double las_gps_time_origin = 0.0;
@@ -337,6 +354,11 @@ public:
     Status cell_stats_state(int i, std::vector<uint32_t>* n, std::vector<int64_t>* s1, std::vector<uint64_t>* s2) const;
     /// ... and its shape.
     Status cell_stats_shape(int i, int* rows, int* width) const;
+    /// Extension: the table of PipelineConfig::trees[i] as the last finalize() left it -- one row per tree, ids 1..size(), the
+    /// cell centres by the grid's geometry.  Valid after a finalize (also finalize_async: on the HIP engine the call waits for
+    /// the pipeline's stream and fetches the table then); a later finalize replaces it.  InvalidArgument for an index outside
+    /// the list or before the first finalize; OutOfRange for more than 2^24 trees.
+    Status trees(int i, TreeTable* out) const;
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
     /// the finalize kernels are only ENQUEUED on the pipeline's stream -- result() is valid at once, its bands are complete

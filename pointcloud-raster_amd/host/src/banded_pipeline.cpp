@@ -8,6 +8,7 @@
 #include "fill_nodata.h"
 #include "ground_filter.h"
 #include "terrain.h"
+#include "trees.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -175,6 +176,7 @@ std::unique_ptr<Pipeline> Pipeline::Banded::visit(size_t b, Status* st, bool* wa
     c.fill_nodata_radius = 0;                         // (a band lacks its neighbours' rows: finalize() fills the assembled grid)
     c.ground = GroundFilterConfig();                  // (... and filters it)
     c.terrain.clear();                                // (... and derives the terrain bands)
+    c.trees.clear();                                  // (... and the tree bands)
     c.state_dir.clear();
     c.resume = false;
     c.exec_mode = ExecutionMode::GPU;
@@ -319,9 +321,12 @@ Status Pipeline::Banded::finalize() {
     if (!gs.ok()) return gs;
     detail::TerrainPlan terrain;
     if (!(gs = detail::plan_terrain(cfg, ground, &terrain)).ok()) return gs;
+    detail::TreesPlan trees;
+    if (!(gs = detail::plan_trees(cfg, ground, terrain, &trees)).ok()) return gs;
     const size_t n_out = descs.size();                // (the ground filter's and the terrain bands follow: no band visit makes them)
     detail::append_ground_bands(ground, descs);
     detail::append_terrain_bands(terrain, descs);
+    detail::append_tree_bands(trees, descs);
     if (!result) result = Grid::create(g.width, g.height, descs, MemoryLocation::Host);
     if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     (void)result->set_geometry(detail::result_geometry(cfg));
@@ -353,7 +358,7 @@ Status Pipeline::Banded::finalize() {
     {                                                 // the result is assembled here, on the host: so are its ground filter and its fill
         std::vector<ReductionType> types;
         for (const auto& r : cfg.reductions) types.push_back(r.type);
-        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground, terrain);
+        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground, terrain, trees, &tree_tables, &tree_status);
         if (!fs.ok()) return fs;
     }
     finalized = true;

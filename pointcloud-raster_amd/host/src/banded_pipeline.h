@@ -56,6 +56,8 @@ struct Pipeline::Banded {
     std::string spill_dir;
     std::unique_ptr<Grid> result;
     bool finalized = false;
+    std::vector<TreeTable> tree_tables;      // PipelineConfig::trees, entry by entry, as the last finalize left them
+    std::vector<Status> tree_status;
     size_t collections = 0, points = 0, tiles_active = 0;
     ProgressCallback callback;
     ScatterInfo last{};

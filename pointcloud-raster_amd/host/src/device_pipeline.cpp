@@ -30,6 +30,7 @@ Pipeline::Impl::~Impl() {
     bands.clear();
     band_buffers.clear();
     d_ground_work.release();
+    d_tree_work.clear();
     staging.clear();
     result.reset();
     if (own_stream && stream) pcr_hip_stream_destroy(stream);
@@ -126,6 +127,7 @@ Status Pipeline::Impl::init() {
     cstats = detail::plan_cell_stats(cfg, filters);
     if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
     if (!(s = detail::plan_terrain(cfg, ground, &terrain)).ok()) return s;
+    if (!(s = detail::plan_trees(cfg, ground, terrain, &tree_plan)).ok()) return s;
     if (!(s = detail::plan_surfaces(cfg)).ok()) return s;
     surfaces.resize(cfg.surface_channels.size());
 
@@ -376,6 +378,40 @@ Status Pipeline::Impl::finalize_terrain(bool* enqueued) {
         if (!s.ok()) return s;
     }
     return Status::success();
+}
+// Behind the terrain bands, on the pipeline's stream: per entry everything pcr_hip_trees enqueues, reading the source band as it
+// leaves the pipeline (`out`: filled) and storing the two new bands, which then leave as they are.  No plane-state event.
+Status Pipeline::Impl::finalize_trees(bool* enqueued) {
+    const int rows = own_rows(), W = hg.width;
+    const size_t first = outputs.size() + (size_t)ground.extra_bands() + (size_t)terrain.extra_bands();
+    if (d_tree_work.size() < tree_plan.entries.size()) d_tree_work.resize(tree_plan.entries.size());
+    for (size_t i = 0; i < tree_plan.entries.size(); ++i) {
+        const auto& e = tree_plan.entries[i];
+        size_t bytes = 0;
+        Status s = detail::hip_status(pcr_hip_trees_work_bytes(W, rows, &bytes));
+        if (!s.ok()) return s;
+        if (d_tree_work[i].bytes() < bytes && !(s = d_tree_work[i].allocate(bytes, MemoryLocation::Device)).ok()) return s;
+        const pcr_hip_tree_params p = detail::tree_params(e.spec, tree_plan.cell_size_x, tree_plan.cell_size_y);
+        const size_t id = first + 2 * i, height = id + 1;
+        *enqueued = true;
+        s = detail::hip_status(pcr_hip_trees(bands[(size_t)e.source].out, W, rows, W, &p, bands[id].raw, W, bands[height].raw, W,
+                                             d_tree_work[i].data(), d_tree_work[i].bytes(), stream));
+        if (s.ok()) s = band_leaves(id, enqueued);
+        if (s.ok()) s = band_leaves(height, enqueued);
+        if (!s.ok()) return s;
+    }
+    return Status::success();
+}
+// The table of entry i as the last finalize left it in the entry's work area, behind everything on the pipeline's stream.
+Status Pipeline::Impl::trees(int i, TreeTable* out) {
+    if (!out || i < 0 || !finalized || !result || (size_t)i >= tree_plan.entries.size() || (size_t)i >= d_tree_work.size())
+        return Status::error(StatusCode::InvalidArgument, "pipeline: trees: no trees entry " + std::to_string(i) + " (of a finalize)");
+    DeviceScope dev(cfg.cuda_device_id);
+    const auto& e = tree_plan.entries[(size_t)i];
+    Status s = detail::tree_table_device(bands[(size_t)e.source].out, hg.width, own_rows(), hg.width, d_tree_work[(size_t)i].data(),
+                                         d_tree_work[(size_t)i].bytes(), stream, out);
+    if (s.ok()) detail::tree_centres(*out, result->geometry(), tree_plan.cell_size_x, tree_plan.cell_size_y);
+    return s;
 }
 Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
     return detail::hip_status(pcr_hip_engine_tile_touched(engine, d, tx, ty));
@@ -1028,6 +1064,7 @@ Status Pipeline::Impl::allocate_result() {
     if (descs.empty()) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
     detail::append_ground_bands(ground, descs);
     detail::append_terrain_bands(terrain, descs);
+    detail::append_tree_bands(tree_plan, descs);
     if (rows <= 0) { result.reset(); return Status::success(); }
     const bool on_device = cfg.result_location == MemoryLocation::Device;
     result = on_device ? Grid::create(W, rows, descs, MemoryLocation::Device)
@@ -1036,7 +1073,7 @@ Status Pipeline::Impl::allocate_result() {
     if (rows == cfg.grid.height) (void)result->set_geometry(detail::result_geometry(cfg));     // (a shard's block is no grid of its own)
     // the table of leaving bands and the buffers behind it: the rule (device_pipeline.h, LeavingBand) applied once
     const size_t n_out = outputs.size();
-    bands.assign(n_out + (size_t)ground.extra_bands() + (size_t)terrain.extra_bands(), LeavingBand{});
+    bands.assign(n_out + (size_t)ground.extra_bands() + (size_t)terrain.extra_bands() + (size_t)tree_plan.extra_bands(), LeavingBand{});
     band_buffers.clear();
     Status s = Status::success();
     auto owned = [&]() -> float* {
@@ -1131,6 +1168,7 @@ Status Pipeline::Impl::finalize(bool wait) {
     if (!(s = finalize_cell_stats(&enqueued)).ok()) return s;
     if (!(s = finalize_ground(&enqueued)).ok()) return s;
     if (!(s = finalize_terrain(&enqueued)).ok()) return s;
+    if (!(s = finalize_trees(&enqueued)).ok()) return s;
     // write_cog: the overview levels are one more pass over the bands where they are, in HBM, behind the finalize
     // kernels on the same stream; only the levels (a third of the data) cross the bus, the host never halves the grid.
     std::vector<std::unique_ptr<Grid>> levels;

@@ -13,6 +13,7 @@
 #include "pipeline_common.h"
 #include "sample_grid.h"
 #include "terrain.h"
+#include "trees.h"
 
 #include <chrono>
 #include <map>
@@ -80,9 +81,9 @@ struct Pipeline::Impl {
     std::vector<Group> groups;
     std::vector<Output> outputs;
     // Which memory a band is.  One row per band of the result grid -- the outputs, then the DTM, then the hag band, then the
-    // terrain bands -- built once by allocate_result(); everything else only reads it.  A band is FILLED iff
-    // fill_nodata_radius > 0 and it is an output with fills_nodata(type), or it is the DTM; the hag band and the terrain bands
-    // never are.  Device result: `out` is the result grid's
+    // terrain bands, then the tree bands -- built once by allocate_result(); everything else only reads it.  A band is FILLED iff
+    // fill_nodata_radius > 0 and it is an output with fills_nodata(type), or it is the DTM; the hag band, the terrain bands and the tree
+    // bands never are.  Device result: `out` is the result grid's
     // band, `raw` is `out` unless the band is filled, then an owned buffer.  Host result: `raw` is an owned buffer, `out` is
     // `raw` unless the band is filled, then a second owned buffer.  The fill and the ground filter read a raw band and write
     // another buffer, so the raw bands stay what the plane-state rules take them for: the table is no plane-state event.
@@ -97,6 +98,10 @@ struct Pipeline::Impl {
     detail::GroundPlan ground;               // PipelineConfig::ground, planned at init
     detail::Buffer d_ground_work;            // its workspace, allocated by the first finalize, grow-only
     detail::TerrainPlan terrain;             // PipelineConfig::terrain, planned at init
+    detail::TreesPlan tree_plan;             // PipelineConfig::trees, planned at init
+    std::vector<detail::Buffer> d_tree_work; // entry by entry: the work area of pcr_hip_trees, allocated by the first finalize,
+                                             // grow-only; between a finalize and the next it holds the entry's tree count, ids
+                                             // and crown counts, which trees() reads
     detail::FilterPlan filters;              // PipelineConfig::filter (class 0) and every ReductionSpec::filter, planned at init
     detail::HistogramPlan hist;              // PipelineConfig::histograms, planned at init
     std::vector<detail::Buffer> cubes;       // entry by entry: count[bins][state_rows * width] in HBM, zeroed at create and only
@@ -179,6 +184,8 @@ struct Pipeline::Impl {
     Status cell_stats_state(int i, std::vector<uint32_t>* n, std::vector<int64_t>* s1, std::vector<uint64_t>* s2);
     Status finalize_ground(bool* enqueued);
     Status finalize_terrain(bool* enqueued);
+    Status finalize_trees(bool* enqueued);
+    Status trees(int i, TreeTable* out);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
     bool offer_bands(size_t gi);
     Status unpack_select(Group& gr);

@@ -4,6 +4,7 @@
 #include "fill_nodata.h"
 #include "ground_filter.h"
 #include "terrain.h"
+#include "trees.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -237,6 +238,8 @@ Status Pipeline::Host::finalize() {
     if (!gs.ok()) return gs;
     detail::TerrainPlan terrain;
     if (!(gs = detail::plan_terrain(cfg, ground, &terrain)).ok()) return gs;
+    detail::TreesPlan trees;
+    if (!(gs = detail::plan_trees(cfg, ground, terrain, &trees)).ok()) return gs;
     if (!result) {
         std::vector<BandDesc> bands;
         for (const auto& o : outputs) {                              // band naming: pipeline.cpp:1175-1186
@@ -248,6 +251,7 @@ Status Pipeline::Host::finalize() {
         }
         detail::append_ground_bands(ground, bands);
         detail::append_terrain_bands(terrain, bands);
+        detail::append_tree_bands(trees, bands);
         result = Grid::create(g.width, g.height, bands, MemoryLocation::Host);
         if (!result) return Status::error(StatusCode::OutOfMemory, "pipeline: failed to allocate result grid");
         (void)result->set_geometry(detail::result_geometry(cfg));
@@ -278,7 +282,7 @@ Status Pipeline::Host::finalize() {
     {                                                                // (the planes are the state: the bands are made anew by every finalize)
         std::vector<ReductionType> types;
         for (const auto& o : outputs) types.push_back(o.type);
-        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground, terrain);
+        Status fs = detail::finish_result_host(*result, types, cfg.fill_nodata_radius, ground, terrain, trees, &tree_tables, &tree_status);
         if (!fs.ok()) return fs;
     }
     finalized = true;

@@ -44,6 +44,8 @@ struct Pipeline::Host {
     std::vector<StatPlanes> stat_planes;
     std::unique_ptr<Grid> result;
     bool finalized = false;
+    std::vector<TreeTable> tree_tables;      // PipelineConfig::trees, entry by entry, as the last finalize left them
+    std::vector<Status> tree_status;
     ProgressCallback callback;
     size_t collections = 0, points = 0;
     ScatterInfo last{};

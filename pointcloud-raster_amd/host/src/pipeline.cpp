@@ -19,6 +19,7 @@
 #include "extremes.h"
 #include "histogram.h"
 #include "terrain.h"
+#include "trees.h"
 #include "host_pipeline.h"
 #include "las_io.h"
 #include "pcr/core/point_cloud.h"
@@ -115,6 +116,9 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         detail::TerrainPlan terrain;
         const Status ts = detail::plan_terrain(config, plan, &terrain);
         if (!ts.ok()) return fail_with(ts);
+        detail::TreesPlan trees;
+        const Status rs = detail::plan_trees(config, plan, terrain, &trees);
+        if (!rs.ok()) return fail_with(rs);
     }
     {
         const Status ss = detail::plan_surfaces(config);
@@ -336,6 +340,17 @@ Status Pipeline::cell_stats_shape(int i, int* rows, int* width) const {
         return Status::error(StatusCode::InvalidArgument, "pipeline: cell_stats_state: no cell_stats entry " + std::to_string(i));
     *rows = c->grid.height;                                  // (a row-block shard is refused: the window is the grid)
     *width = c->grid.width;
+    return Status::success();
+}
+Status Pipeline::trees(int i, TreeTable* out) const {
+    if (impl_) return impl_->trees(i, out);
+    const std::vector<TreeTable>& tables = host_ ? host_->tree_tables : banded_->tree_tables;
+    const std::vector<Status>& status = host_ ? host_->tree_status : banded_->tree_status;
+    const bool finalized = host_ ? host_->finalized : banded_->finalized;
+    if (!out || i < 0 || !finalized || (size_t)i >= tables.size())
+        return Status::error(StatusCode::InvalidArgument, "pipeline: trees: no trees entry " + std::to_string(i) + " (of a finalize)");
+    if (!status[(size_t)i].ok()) return status[(size_t)i];
+    *out = tables[(size_t)i];
     return Status::success();
 }
 Status Pipeline::finalize() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(); }

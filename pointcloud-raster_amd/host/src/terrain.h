@@ -155,10 +155,11 @@ inline void append_terrain_bands(const TerrainPlan& plan, std::vector<BandDesc>&
 
 /// The terrain bands of a host-resident result whose last plan.extra_bands() bands they are, from the source bands as they
 /// leave the pipeline: after finish_result_host.
-inline Status terrain_result_host(Grid& grid, const TerrainPlan& plan) {
+/// more_bands: bands that follow the terrain bands and are none of this function's business (trees.h).
+inline Status terrain_result_host(Grid& grid, const TerrainPlan& plan, int more_bands = 0) {
     if (!plan.on()) return Status::success();
     const int w = grid.cols(), h = grid.rows();
-    const int first = grid.num_bands() - plan.extra_bands();
+    const int first = grid.num_bands() - plan.extra_bands() - more_bands;
     if (first < 0) return Status::error(StatusCode::InvalidArgument, "pipeline: the result grid lacks the terrain bands");
     for (const auto& l : plan.launches) {
         const auto& f = plan.bands[(size_t)l.front()];
@@ -180,15 +181,15 @@ inline Status terrain_result_host(Grid& grid, const TerrainPlan& plan) {
 
 /// Everything behind the finalized bands of a host-resident result: finish_result_host, then the terrain bands.
 inline Status finish_result_host(Grid& grid, std::vector<ReductionType> types, int fill_radius, const GroundPlan& ground,
-                                 const TerrainPlan& terrain) {
+                                 const TerrainPlan& terrain, int more_bands = 0) {
     if (terrain.on()) {
         // (finish_result_host counts the bands it was promised: it sees the grid without the terrain bands' share)
-        const int first = grid.num_bands() - terrain.extra_bands();
+        const int first = grid.num_bands() - terrain.extra_bands() - more_bands;
         if (first != (int)types.size() + ground.extra_bands())
             return Status::error(StatusCode::InvalidArgument, "pipeline: the result grid lacks the terrain bands");
     }
-    Status s = finish_result_host(grid, std::move(types), fill_radius, ground, terrain.extra_bands());
-    return s.ok() ? terrain_result_host(grid, terrain) : s;
+    Status s = finish_result_host(grid, std::move(types), fill_radius, ground, terrain.extra_bands() + more_bands);
+    return s.ok() ? terrain_result_host(grid, terrain, more_bands) : s;
 }
 
 /// The gathered grid of a sharded run on rank 0 (the reductions' bands, on the host) as the unsharded pipeline `whole_cfg`

@@ -8,10 +8,12 @@
 #include "pcr/core/reproject.h"
 #include "pcr/core/sample_grid.h"
 #include "pcr/core/terrain.h"
+#include "pcr/core/trees.h"
 #include "pcr/engine/pipeline.h"
 #include "pcr_hip.h"
 #include "../../host/src/pipeline_common.h"
 #include "../../host/src/terrain.h"
+#include "../../host/src/trees.h"
 
 #include <cstring>
 
@@ -68,7 +70,7 @@ void bind_core(py::module_& m) {
         .value("Ok", StatusCode::Ok).value("InvalidArgument", StatusCode::InvalidArgument)
         .value("OutOfMemory", StatusCode::OutOfMemory).value("CudaError", StatusCode::CudaError)
         .value("IoError", StatusCode::IoError).value("CrsError", StatusCode::CrsError)
-        .value("NotImplemented", StatusCode::NotImplemented).export_values();
+        .value("NotImplemented", StatusCode::NotImplemented).value("OutOfRange", StatusCode::OutOfRange).export_values();
 
     py::class_<BBox>(m, "BBox")
         .def(py::init<>())
@@ -152,6 +154,17 @@ void bind_core(py::module_& m) {
         .def_readwrite("compute_edges", &TerrainSpec::compute_edges)
         .def_readwrite("azimuth", &TerrainSpec::azimuth)
         .def_readwrite("altitude", &TerrainSpec::altitude);
+    // extension: individual trees (pcr.segment_trees, PipelineConfig.trees)
+    py::class_<TreeSpec>(m, "TreeSpec", "Tree tops by a variable-window local-maximum filter and crown labels by seeded descent")
+        .def(py::init<>())
+        .def(py::init<const TreeSpec&>())
+        .def_readwrite("min_height", &TreeSpec::min_height)
+        .def_readwrite("window_base", &TreeSpec::window_base)
+        .def_readwrite("window_slope", &TreeSpec::window_slope)
+        .def_readwrite("max_radius_cells", &TreeSpec::max_radius_cells)
+        .def_readwrite("min_crown_height", &TreeSpec::min_crown_height)
+        .def_readwrite("crown_ratio", &TreeSpec::crown_ratio)
+        .def_readwrite("max_crown_radius", &TreeSpec::max_crown_radius);
     m.def("terrain_light", [](double azimuth, double altitude) {
         const TerrainLight l = terrain_light(azimuth, altitude);
         return py::make_tuple(l.sin_alt, l.ls, l.lc);
@@ -413,6 +426,33 @@ void bind_core(py::module_& m) {
         return out;
     }, py::arg("grid"), py::arg("band"), py::arg("products"), py::arg("spec") = py::none(), py::arg("cell_size_x") = 1.0,
        py::arg("cell_size_y") = -1.0);
+    // extension: tree tops and crown labels of a grid's band, where the grid lives (a Device grid: in HBM)
+    m.def("segment_trees", [](const Grid& grid, int band, py::object spec, double cell_size_x, double cell_size_y) {
+        Status s;
+        TreeTable t;
+        auto out = segment_trees(grid, band, spec.is_none() ? TreeSpec() : spec.cast<TreeSpec>(), cell_size_x, cell_size_y, &t, &s, nullptr);
+        raise_if_error(s);
+        return py::make_tuple(std::move(out), tree_table_dict(t));
+    }, py::arg("grid"), py::arg("band") = 0, py::arg("spec") = py::none(), py::arg("cell_size_x") = 1.0, py::arg("cell_size_y") = -1.0,
+       "(grid with the bands tree_id and tree_height, table): the table a dict of numpy arrays row, col, x, y, height, crown_cells");
+    // (tests) what the id band holds for an id: the clamp at 2^24 on its own
+    m.def("_tree_id_value", [](int64_t id) { return pcrhip::trees::id_value(id); }, py::arg("id"));
+    // (tests, tools) the host twin on an array, which the kernels are compared with; -> (id [h, w], height [h, w], table)
+    m.def("_trees_host", [](py::array_t<float, py::array::c_style | py::array::forcecast> src, py::object spec_in, double cell_size_x,
+                            double cell_size_y) {
+        if (src.ndim() != 2 || src.shape(0) < 1 || src.shape(1) < 1) throw std::invalid_argument("segment_trees: a 2-D array is needed");
+        const TreeSpec spec = spec_in.is_none() ? TreeSpec() : spec_in.cast<TreeSpec>();
+        const std::string bad = detail::tree_spec_error(spec);
+        if (!bad.empty()) throw std::invalid_argument("segment_trees: " + bad);
+        if (!detail::tree_cell_sizes_ok(cell_size_x, cell_size_y)) throw std::invalid_argument("segment_trees: cell sizes must be finite and not zero");
+        const int h = (int)src.shape(0), w = (int)src.shape(1);
+        py::array_t<float> id({(py::ssize_t)h, (py::ssize_t)w}), height({(py::ssize_t)h, (py::ssize_t)w});
+        TreeTable t;
+        raise_if_error(detail::trees_host(src.data(), w, h, w, detail::tree_consts(spec, cell_size_x, cell_size_y), id.mutable_data(), w,
+                                          height.mutable_data(), w, &t));
+        detail::tree_centres(t, nullptr, cell_size_x, cell_size_y);
+        return py::make_tuple(id, height, tree_table_dict(t));
+    }, py::arg("src"), py::arg("spec") = py::none(), py::arg("cell_size_x") = 1.0, py::arg("cell_size_y") = -1.0);
     // (tests, tools) the host loop on an array, which the kernel is compared with; -> [len(products), h, w]
     m.def("_terrain_host", [](py::array_t<float, py::array::c_style | py::array::forcecast> src, const std::vector<TerrainProduct>& products,
                               py::object spec_in, double cell_size_x, double cell_size_y, int threads) {

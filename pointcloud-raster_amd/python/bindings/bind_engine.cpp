@@ -95,6 +95,21 @@ void bind_engine(py::module_& m) {
         .def_readwrite("product", &TerrainBandConfig::product)
         .def_readwrite("band_name", &TerrainBandConfig::band_name);
 
+    py::class_<TreeBandConfig, TreeSpec>(m, "TreeBandConfig",
+                                         "The tree_id and tree_height bands of one band of the result, appended at finalize()")
+        .def(py::init<>())
+        .def(py::init<const TreeBandConfig&>())
+        .def(py::init([](const std::string& source_band, const std::string& id_band_name, const std::string& height_band_name) {
+            TreeBandConfig c;
+            c.source_band = source_band;
+            c.id_band_name = id_band_name;
+            c.height_band_name = height_band_name;
+            return c;
+        }), py::arg("source_band"), py::arg("id_band_name") = "", py::arg("height_band_name") = "")
+        .def_readwrite("source_band", &TreeBandConfig::source_band)
+        .def_readwrite("id_band_name", &TreeBandConfig::id_band_name)
+        .def_readwrite("height_band_name", &TreeBandConfig::height_band_name);
+
     py::class_<SurfaceChannelConfig>(m, "SurfaceChannelConfig")
         .def(py::init<>())
         .def(py::init<const SurfaceChannelConfig&>())
@@ -220,6 +235,9 @@ void bind_engine(py::module_& m) {
         .def_readwrite("fill_nodata_radius", &PipelineConfig::fill_nodata_radius)
         .def_readwrite("ground", &PipelineConfig::ground)
         .def_readwrite("terrain", &PipelineConfig::terrain)
+        .def_readwrite("trees", &PipelineConfig::trees,
+                       "Individual trees: two bands per entry, tree_id and tree_height of the named band, appended behind the terrain "
+                       "bands at finalize() (assign a list of TreeBandConfig); Pipeline.trees(i) reads an entry's table")
         .def_readwrite("las_gps_time_origin", &PipelineConfig::las_gps_time_origin)
         .def_readwrite("surface_channels", &PipelineConfig::surface_channels,
                        "Per-point Float32 channels derived at every ingest from a band given with Pipeline.set_surface (assign a "
@@ -307,6 +325,13 @@ void bind_engine(py::module_& m) {
         }, py::arg("i") = 0,
              "The state of cell_stats entry i as (N, S1, S2): numpy uint32, int64 and uint64 arrays (height, width) -- the count, "
              "the sum of the steps and the sum of their squares: host copies, valid after any ingest")
+        .def("trees", [](const Pipeline& p, int i) {
+            TreeTable t;
+            raise_if_error(p.trees(i, &t));
+            return tree_table_dict(t);
+        }, py::arg("i") = 0,
+             "The table of trees entry i of the last finalize as a dict of numpy arrays row, col, x, y, height, crown_cells; row k "
+             "is the tree with id k + 1")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },
              "Device-resident result: the finalize kernels are only enqueued on the pipeline's stream (complete after synchronize()); "

@@ -76,6 +76,7 @@ from ._pcr import (  # noqa: E402,F401
     read_las,
     GroundFilterSpec, GroundFilterConfig, ground_filter, ground_filter_levels,
     TerrainProduct, TerrainSpec, TerrainBandConfig, terrain, terrain_light,
+    TreeSpec, TreeBandConfig, segment_trees,
     SampleMode, SurfaceChannelConfig, sample_grid,
     HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig,
 )
@@ -179,6 +180,7 @@ __all__ = [
     "read_las",
     "GroundFilterSpec", "GroundFilterConfig", "ground_filter", "ground_filter_levels",
     "TerrainProduct", "TerrainSpec", "TerrainBandConfig", "terrain", "terrain_light",
+    "TreeSpec", "TreeBandConfig", "segment_trees",
     "SampleMode", "SurfaceChannelConfig", "sample_grid",
     "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig",
 ]

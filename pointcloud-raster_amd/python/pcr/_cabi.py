@@ -83,6 +83,20 @@ class LasLayout(C.Structure):
                 ("offset", C.c_double * 3), ("gps_time_origin", C.c_double)]
 
 
+class TreeParams(C.Structure):
+    """pcr_hip_tree_params with the defaults of pcr.TreeSpec."""
+    _fields_ = [("min_height", C.c_float), ("window_base", C.c_float), ("window_slope", C.c_float),
+                ("max_radius_cells", C.c_int32), ("min_crown_height", C.c_float), ("crown_ratio", C.c_float),
+                ("max_crown_radius", C.c_float), ("stop_after", C.c_int32), ("cell_size_x", C.c_double),
+                ("cell_size_y", C.c_double)]
+
+    def __init__(self, **kw):
+        d = dict(min_height=2.0, window_base=3.0, window_slope=0.07, max_radius_cells=16, min_crown_height=2.0,
+                 crown_ratio=0.45, max_crown_radius=10.0, stop_after=0, cell_size_x=1.0, cell_size_y=-1.0)
+        d.update(kw)
+        super().__init__(**d)
+
+
 # PCR_HIP_LAS_CH_* in order, under the names the clouds carry; a workgroup of the decode kernel owns 256 * this many records
 LAS_CHANNELS = ("z", "intensity", "return_number", "number_of_returns", "classification", "withheld", "overlap",
                 "scan_angle", "user_data", "point_source_id", "gps_time", "red", "green", "blue", "nir")
@@ -190,6 +204,12 @@ SYMBOLS = {
     "pcr_hip_band_difference": [_VP, _VP, _VP, C.c_int, C.c_int, _I64, _I64, _I64, _VP],
     "pcr_hip_terrain": [_VP, C.c_int, C.c_int, _I64, C.c_int, C.POINTER(C.c_int), C.POINTER(_VP), C.POINTER(_I64),
                         C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, _VP],
+    "pcr_hip_trees_work_bytes": [C.c_int, C.c_int, C.POINTER(_SZ)],
+    "pcr_hip_trees": [_VP, C.c_int, C.c_int, _I64, C.POINTER(TreeParams), _VP, _I64, _VP, _I64, _VP, _SZ, _VP],
+    "pcr_hip_trees_count": [_VP, _SZ, C.POINTER(_I64), C.POINTER(C.c_int), _VP],
+    "pcr_hip_trees_table": [_VP, C.c_int, C.c_int, _I64, _VP, _SZ, _I64, _VP, _VP, _VP, _VP, _VP],
+    "pcr_hip_trees_host": [_VP, C.c_int, C.c_int, _I64, C.POINTER(TreeParams), _VP, _I64, _VP, _I64, C.POINTER(_I64), _I64,
+                           _VP, _VP, _VP, _VP],
     "pcr_hip_las_decode": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), _VP],
     "pcr_hip_las_decode_host": [C.POINTER(LasLayout), _VP, _U64, _VP, _VP, C.POINTER(_VP), C.c_int],
     "pcr_hip_sample_grid": [C.POINTER(Grid), _VP, _I64, _VP, _VP, _VP, _U64, C.c_int, _VP, _VP],
