@@ -864,6 +864,72 @@ int pcr_hip_cell_stats_bands_host(const pcr_hip_grid* g, const uint32_t* h_n, co
                                   double origin, double resolution, int ddof, int n_products, const int* products,
                                   float* const* h_outs);
 
+/* ---- zonal tables: the per-cell stats planes and histogram cubes above folded by a LABEL BAND into one row per zone
+ *      (PipelineConfig::zonal, Pipeline::zonal): per tree with a tree_id band, per plot or stand with a rasterized label grid
+ *      -- lidR's crown_metrics and plot_metrics.  No reference counterpart.  The per-cell state is integers, so a zone's state
+ *      is the integer sum of its cells': the same bits on both engines for any order or grouping, with no tolerance anywhere.
+ *      The arithmetic is written once, in csrc/zonal.hpp, which the kernels, the host twins and the host engine compile with
+ *      contraction off.
+ *        zone       zone_of(v) = (uint32)v when v is finite, 1 <= v <= 2^24 and v == floorf(v); else 0: no zone (NaN, +-Inf,
+ *                   0, -0.0, negatives, 2.5).  Z is the greatest zone of the band (zone_max); a table has rows 0 .. Z - 1, row
+ *                   k is zone k + 1; a zone no cell carries has cells = 0.  A zone above the Z passed to a fold is skipped: it is
+ *                   never an index.
+ *        fold       all counters are 64-bit and wrap modulo 2^64; the caller zeroes the tables.  Per zone:
+ *                     cells   uint64, += 1 per cell of the zone
+ *                     n, s1, s2   uint64, int64, uint64: += the cell's N (uint32), S1 (int64), S2 (uint64)
+ *                     counts[zone][bin]   uint64, += the cell's count[bin][cell] (uint32)
+ *        rows, stats   mean, var, std: the per-cell bands' arithmetic ("per-cell stats" above) with a 64-bit n: NaN where
+ *                   n == 0, var and std NaN where n <= ddof; D = n * S2 - S1^2 modulo 2^128, one 64 x 64 -> 128 multiply per
+ *                   term; dd = (double)hi * 0x1p64 + (double)lo; den = (double)n * (double)(n - ddof); vq = dd / den;
+ *                   mean = (float)(origin + resolution * ((double)s1 / (double)n)); var = (float)((resolution * resolution) * vq);
+ *                   std = (float)(resolution * sqrt(vq)).
+ *        rows, histogram   hist_n = the sum of the zone's bins; per q: NaN where hist_n == 0, else k = min(max((int64)ceil(
+ *                   (double)q * (double)hist_n), 1), hist_n), b the smallest bin whose cumulative count C_b >= k, and
+ *                   (float)(lo + w * ((double)b + ((double)(k - C_{b-1}) - 0.5) / (double)counts[b])) -- "per-cell histograms"
+ *                   above with 64-bit counts (hist_n < 2^63).
+ *      Bands and planes are `height` rows of `width` elements, rows `*_stride` ELEMENTS apart (one plane_stride for N, S1 and S2);
+ *      the cube's planes are bin_stride elements apart.  Everything is enqueued on s; nothing is allocated.
+ *      zone_max: *d_max (one device word, zeroed on s by the call) = Z, or 0 for a band with no zone; a wave reduction, then one
+ *      atomic max per wave.  zone_fold_stats: one lane per cell; neighbouring lanes with one zone form a run, a segmented wave
+ *      scan sums along it and the run's last lane issues the 64-bit atomic adds (runs go on across a row end of a contiguous
+ *      band); a wave with no zone loads nothing further.  d_n, d_s1, d_s2, d_zn, d_zs1, d_zs2 may ALL be null (only cells), or
+ *      d_cells may be.  combine = 0 switches the run-combining off -- one set of atomics per cell, for A/B timing and for a test
+ *      that both forms give the same bits.  zone_fold_hist: the same lanes, plane after plane; only nonzero counts are added.
+ *      zone_rows_stats / zone_rows_percentiles: one lane per zone; a null column is not written; q and d_outs are HOST arrays;
+ *      n_q may be 0 (hist_n alone).  _host: the same lines on host arrays, one thread, one add per cell.
+ *      Argument errors -- a null pointer, a non-positive size, a stride below the width, bins outside 1..256, Z outside 1..2^24,
+ *      more than 2^31 - 1 cells, combine other than 0 or 1, n_q outside 0..16, q outside [0, 1], a table that overlaps an input
+ *      or another table -- are reported before any HIP call. */
+#define PCR_HIP_ZONE_MAX (1u << 24)
+typedef struct pcr_hip_zone_fold_params {
+    int32_t combine;                 /* 1: sum along runs of equal zones first; 0: one set of atomics per cell */
+    int32_t reserved_;
+} pcr_hip_zone_fold_params;
+int pcr_hip_zone_max(const float* d_zones, int width, int height, int64_t zone_stride, uint32_t* d_max, pcr_hip_stream s);
+int pcr_hip_zone_max_host(const float* h_zones, int width, int height, int64_t zone_stride, uint32_t* max);
+int pcr_hip_zone_fold_stats(const float* d_zones, int width, int height, int64_t zone_stride, const uint32_t* d_n, const long long* d_s1,
+                            const unsigned long long* d_s2, int64_t plane_stride, uint32_t Z, const pcr_hip_zone_fold_params* params,
+                            unsigned long long* d_cells, unsigned long long* d_zn, long long* d_zs1, unsigned long long* d_zs2,
+                            pcr_hip_stream s);
+int pcr_hip_zone_fold_stats_host(const float* h_zones, int width, int height, int64_t zone_stride, const uint32_t* h_n,
+                                 const long long* h_s1, const unsigned long long* h_s2, int64_t plane_stride, uint32_t Z,
+                                 const pcr_hip_zone_fold_params* params, unsigned long long* h_cells, unsigned long long* h_zn,
+                                 long long* h_zs1, unsigned long long* h_zs2);
+int pcr_hip_zone_fold_hist(const float* d_zones, int width, int height, int64_t zone_stride, const uint32_t* d_counts, int bins,
+                           int64_t count_stride, int64_t bin_stride, uint32_t Z, const pcr_hip_zone_fold_params* params,
+                           unsigned long long* d_zcounts, pcr_hip_stream s);
+int pcr_hip_zone_fold_hist_host(const float* h_zones, int width, int height, int64_t zone_stride, const uint32_t* h_counts, int bins,
+                                int64_t count_stride, int64_t bin_stride, uint32_t Z, const pcr_hip_zone_fold_params* params,
+                                unsigned long long* h_zcounts);
+int pcr_hip_zone_rows_stats(const unsigned long long* d_zn, const long long* d_zs1, const unsigned long long* d_zs2, uint32_t Z,
+                            double origin, double resolution, int ddof, float* d_mean, float* d_var, float* d_std, pcr_hip_stream s);
+int pcr_hip_zone_rows_stats_host(const unsigned long long* h_zn, const long long* h_zs1, const unsigned long long* h_zs2, uint32_t Z,
+                                 double origin, double resolution, int ddof, float* h_mean, float* h_var, float* h_std);
+int pcr_hip_zone_rows_percentiles(const unsigned long long* d_zcounts, int bins, uint32_t Z, double lo, double w, int n_q, const float* q,
+                                  unsigned long long* d_hist_n, float* const* d_outs, pcr_hip_stream s);
+int pcr_hip_zone_rows_percentiles_host(const unsigned long long* h_zcounts, int bins, uint32_t Z, double lo, double w, int n_q,
+                                       const float* q, unsigned long long* h_hist_n, float* const* h_outs);
+
 #ifdef __cplusplus
 }
 #endif

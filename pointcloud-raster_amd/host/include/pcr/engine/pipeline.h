@@ -166,6 +166,48 @@ struct CellStatsConfig {
     std::vector<std::string> band_names; // default "{value_channel}_mean" / "_var" / "_std"
 };
 
+/// One entry of PipelineConfig::zonal: a table with one row per zone -- per tree with a tree_id band, per plot or stand with a
+/// rasterized label grid -- of the chosen cell-stats entries and histograms, folded where their state lives (lidR's
+/// crown_metrics and plot_metrics).  The contract (include/pcr_hip.h, "zonal tables"; csrc/zonal.hpp):
+///   zone       of a cell: the label when it is a whole number in [1, 2^24], else none (NaN, +-Inf, 0, negatives, 2.5).  Z is the
+///              greatest zone present; row k of the table is zone k + 1; a zone no cell carries has cells = 0.
+///   fold       64-bit integer sums of the cells' N, S1, S2 and of their histogram counts, modulo 2^64.
+///   rows       mean, var, std: the cell-stats bands' arithmetic on the zone's sums, with the entry's origin, resolution and
+///              ddof; percentiles: the percentile bands' walk over the zone's counts.  NaN where the zone has no point.
+/// Both engines give the same bits.
+struct ZonalConfig {
+    std::string zones;                   // a band of the result by name (normally "{source}_tree_id"), or, with `external`, the
+                                         // name of a label grid given by Pipeline::set_zones
+    bool external = false;
+    std::vector<int> cell_stats;         // indices into PipelineConfig::cell_stats
+    std::vector<int> histograms;         // indices into PipelineConfig::histograms
+    bool own_percentiles = true;         // every chosen histogram with its entry's own percentile list; false: `percentiles`
+    std::vector<float> percentiles;      // each in [0, 1], at most 16
+    int max_zones = 1 << 22;             // 1..2^24: Pipeline::zonal answers OutOfRange for a band with a greater zone
+};
+
+/// Pipeline::zonal's table: rows 0 .. size() - 1 are zones 1 .. size().
+struct ZonalTable {
+    struct StatColumns {                 // one per chosen cell-stats entry: "{channel}_n", "_mean", "_var", "_std"
+        std::string channel;
+        std::vector<uint64_t> n;
+        std::vector<float> mean, var, stddev;
+    };
+    struct HistColumns {                 // one per chosen histogram: "{channel}_hist_n", "{channel}_p{round(q * 100)}"
+        std::string channel;
+        int bins = 0;
+        std::vector<uint64_t> hist_n;
+        std::vector<float> q;
+        std::vector<std::vector<float>> p;       // p[j]: the column of q[j]
+        std::vector<uint64_t> counts;            // [zone][bin]; filled only when asked for (Pipeline::zonal, with_counts)
+    };
+    std::vector<int32_t> zone;
+    std::vector<int64_t> cells;
+    std::vector<StatColumns> stats;
+    std::vector<HistColumns> hists;
+    size_t size() const { return zone.size(); }
+};
+
 struct PipelineConfig {
     GridConfig grid;
     std::vector<ReductionSpec> reductions;
@@ -299,6 +341,13 @@ struct PipelineConfig {
     // band, a row-block shard and a pipeline that has to run out of core; save_state, load_state and resume answer
     // NotImplemented while the list is non-empty.  Empty: nothing is allocated, launched or validated differently.
     std::vector<CellStatsConfig> cell_stats;
+    // Zonal tables (ZonalConfig): Pipeline::zonal(i) folds the chosen cell-stats planes and histogram cubes by entry i's label band
+    // into one row per zone -- on the HIP engine in HBM, only the table crosses PCIe.  Nothing happens at ingest or in finalize()
+    // and no band is added.  create() refuses more than 4 entries, an empty `zones`, a `zones` that names no band of the result
+    // unless `external` is set, an index outside cell_stats or histograms, more than 16 percentiles or one outside [0, 1], a
+    // column name that appears twice, max_zones outside 1..2^24, a row-block shard and a pipeline that has to run out of core.
+    // Empty: nothing is allocated, launched or validated differently.
+    std::vector<ZonalConfig> zonal;
 };
 
 struct ProgressInfo {
@@ -359,6 +408,18 @@ public:
     /// the pipeline's stream and fetches the table then); a later finalize replaces it.  InvalidArgument for an index outside
     /// the list or before the first finalize; OutOfRange for more than 2^24 trees.
     Status trees(int i, TreeTable* out) const;
+    /// Extension: gives the external label grid `name` (a PipelineConfig::zonal entry with `external`) its labels -- band `band`
+    /// of `grid`, which must have the pipeline's width and height.  The band is copied into memory the pipeline owns (HBM on
+    /// the HIP engine: a Host grid is uploaded, a Device grid copied in place on the device), so the caller's grid may die or
+    /// change afterwards.  InvalidArgument for an unknown name, another shape, a band outside the grid or not Float32.
+    Status set_zones(const std::string& name, const Grid& grid, int band = 0);
+    /// Extension: the table of PipelineConfig::zonal[i] -- the zone band as the last finalize() left it (or the external grid),
+    /// the cell-stats planes and cubes as they are.  Valid after a finalize with no ingest since (also finalize_async: on the HIP
+    /// engine the call is enqueued behind it on the pipeline's stream, which is waited for once for the number of zones and once
+    /// for the table).  InvalidArgument for an index outside the list, before the first finalize, after a further ingest or for
+    /// an external grid that was not set; OutOfRange for a zone above the entry's max_zones.  with_counts: also copy out every
+    /// histogram's [zone][bin] counts (HistColumns::counts; zones x bins x 8 bytes each), which are left empty otherwise.
+    Status zonal(int i, ZonalTable* out, bool with_counts = false) const;
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
     /// the finalize kernels are only ENQUEUED on the pipeline's stream -- result() is valid at once, its bands are complete

@@ -31,6 +31,7 @@ Pipeline::Impl::~Impl() {
     band_buffers.clear();
     d_ground_work.release();
     d_tree_work.clear();
+    zone_grids.clear();
     staging.clear();
     result.reset();
     if (own_stream && stream) pcr_hip_stream_destroy(stream);
@@ -128,6 +129,7 @@ Status Pipeline::Impl::init() {
     if (!(s = detail::plan_ground(cfg, &ground)).ok()) return s;
     if (!(s = detail::plan_terrain(cfg, ground, &terrain)).ok()) return s;
     if (!(s = detail::plan_trees(cfg, ground, terrain, &tree_plan)).ok()) return s;
+    if (!(s = detail::plan_zonal(cfg, ground, terrain, tree_plan, &zonal_plan)).ok()) return s;
     if (!(s = detail::plan_surfaces(cfg)).ok()) return s;
     surfaces.resize(cfg.surface_channels.size());
 
@@ -412,6 +414,39 @@ Status Pipeline::Impl::trees(int i, TreeTable* out) {
                                          d_tree_work[(size_t)i].bytes(), stream, out);
     if (s.ok()) detail::tree_centres(*out, result->geometry(), tree_plan.cell_size_x, tree_plan.cell_size_y);
     return s;
+}
+// PipelineConfig::zonal: the label band of an external entry into HBM the pipeline owns, behind everything on the stream.
+Status Pipeline::Impl::set_zones(const std::string& name, const Grid& grid, int band) {
+    DeviceScope dev(cfg.cuda_device_id);
+    Status s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+    return s.ok() ? detail::store_zones(cfg, name, grid, band, MemoryLocation::Device, stream, &zone_grids) : s;
+}
+// The table of entry i, behind the last finalize on the pipeline's stream: the label band as it left the pipeline (`out`), the
+// cell-stats planes and the cubes where they are.  Nothing of it runs in finalize: no plane-state event.
+Status Pipeline::Impl::zonal(int i, ZonalTable* out, bool with_counts) {
+    if (!out || i < 0 || !finalized || !zonal_fresh || !result || (size_t)i >= zonal_plan.entries.size())
+        return Status::error(StatusCode::InvalidArgument,
+                             "pipeline: zonal: no zonal entry " + std::to_string(i) + " (of a finalize with no ingest since)");
+    const auto& e = zonal_plan.entries[(size_t)i];
+    detail::ZonalInputs in;
+    in.device = true;
+    in.stream = stream;
+    in.width = hg.width;
+    in.rows = own_rows();
+    if (e.band >= 0) {
+        in.zones = bands[(size_t)e.band].out;
+    } else {
+        const auto it = zone_grids.find(e.zones);
+        if (it == zone_grids.end())
+            return Status::error(StatusCode::InvalidArgument, "pipeline: zonal: the label grid '" + e.zones + "' was not set (set_zones)");
+        in.zones = static_cast<const float*>(it->second.band.data());
+    }
+    for (const auto& p : stat_planes)
+        in.stats.push_back({static_cast<const uint32_t*>(p.n.data()), static_cast<const long long*>(p.s1.data()),
+                            static_cast<const unsigned long long*>(p.s2.data())});
+    for (const auto& c : cubes) in.cubes.push_back(static_cast<const uint32_t*>(c.data()));
+    DeviceScope dev(cfg.cuda_device_id);
+    return detail::zonal_table(e, cstats, hist, in, with_counts, out);
 }
 Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
     return detail::hip_status(pcr_hip_engine_tile_touched(engine, d, tx, ty));
@@ -1017,6 +1052,7 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     if (!(s = check_line_reach(in)).ok()) return s;
 
     // (this cloud's points change the planes and the touched flags)
+    zonal_fresh = false;
     if (!(s = bands_stale()).ok()) return s;
     // The touched flags are PipelineConfig::filter's survivors', whatever the groups' own filters keep.  An unfiltered group's
     // scatter sets exactly those; when every group is filtered a pass of its own does, ahead of the first scatter.
@@ -1206,6 +1242,7 @@ Status Pipeline::Impl::finalize(bool wait) {
         if (!s.ok()) return s;
     }
     finalized = true;
+    zonal_fresh = true;
     if (!cfg.output_path.empty()) {
         // pipeline.cpp:1351-1361 of the reference: the finalized grid goes to output_path as GeoTIFF.
         // A shard writes its own row block (georeferenced as such); a device-resident result is copied out first.

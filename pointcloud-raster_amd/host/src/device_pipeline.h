@@ -14,6 +14,7 @@
 #include "sample_grid.h"
 #include "terrain.h"
 #include "trees.h"
+#include "zonal.h"
 
 #include <chrono>
 #include <map>
@@ -102,6 +103,9 @@ struct Pipeline::Impl {
     std::vector<detail::Buffer> d_tree_work; // entry by entry: the work area of pcr_hip_trees, allocated by the first finalize,
                                              // grow-only; between a finalize and the next it holds the entry's tree count, ids
                                              // and crown counts, which trees() reads
+    detail::ZonalPlan zonal_plan;            // PipelineConfig::zonal, planned at init
+    std::map<std::string, detail::ZoneGrid> zone_grids;   // the label grids of set_zones, by name, in HBM
+    bool zonal_fresh = false;                // the last finalize's bands and the planes belong together: no ingest since
     detail::FilterPlan filters;              // PipelineConfig::filter (class 0) and every ReductionSpec::filter, planned at init
     detail::HistogramPlan hist;              // PipelineConfig::histograms, planned at init
     std::vector<detail::Buffer> cubes;       // entry by entry: count[bins][state_rows * width] in HBM, zeroed at create and only
@@ -186,6 +190,8 @@ struct Pipeline::Impl {
     Status finalize_terrain(bool* enqueued);
     Status finalize_trees(bool* enqueued);
     Status trees(int i, TreeTable* out);
+    Status set_zones(const std::string& name, const Grid& grid, int band);
+    Status zonal(int i, ZonalTable* out, bool with_counts);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
     bool offer_bands(size_t gi);
     Status unpack_select(Group& gr);

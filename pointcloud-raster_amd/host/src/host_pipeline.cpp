@@ -59,7 +59,44 @@ Status Pipeline::Host::init() {
     }
     // Tile state is identity-initialised (src/engine/tile_manager.cpp:183-260); here for the whole grid at once.
     for (auto& gr : groups) engine->init_planes(gr.planes, gr.mask, gr.select);
+    if (!cfg.zonal.empty()) {                                        // PipelineConfig::zonal: only the plan
+        detail::GroundPlan ground;
+        detail::TerrainPlan terrain;
+        detail::TreesPlan trees;
+        Status ok = detail::plan_ground(cfg, &ground);
+        if (ok.ok()) ok = detail::plan_terrain(cfg, ground, &terrain);
+        if (ok.ok()) ok = detail::plan_trees(cfg, ground, terrain, &trees);
+        if (ok.ok()) ok = detail::plan_zonal(cfg, ground, terrain, trees, &zonal_plan);
+        if (!ok.ok()) return ok;
+    }
     return Status::success();
+}
+
+// PipelineConfig::zonal: the label band of an external entry into host memory the pipeline owns.
+Status Pipeline::Host::set_zones(const std::string& name, const Grid& grid, int band) {
+    return detail::store_zones(cfg, name, grid, band, MemoryLocation::Host, nullptr, &zone_grids);
+}
+// The table of entry i through the C-ABI's host twins: the label band of the result, the planes and the cubes where they are.
+Status Pipeline::Host::zonal(int i, ZonalTable* out, bool with_counts) const {
+    if (!out || i < 0 || !finalized || !zonal_fresh || !result || (size_t)i >= zonal_plan.entries.size())
+        return Status::error(StatusCode::InvalidArgument,
+                             "pipeline: zonal: no zonal entry " + std::to_string(i) + " (of a finalize with no ingest since)");
+    const auto& e = zonal_plan.entries[(size_t)i];
+    detail::ZonalInputs in;
+    in.width = cfg.grid.width;
+    in.rows = cfg.grid.height;
+    if (e.band >= 0) {
+        in.zones = result->band_f32(e.band);
+    } else {
+        const auto it = zone_grids.find(e.zones);
+        if (it == zone_grids.end())
+            return Status::error(StatusCode::InvalidArgument, "pipeline: zonal: the label grid '" + e.zones + "' was not set (set_zones)");
+        in.zones = static_cast<const float*>(it->second.band.data());
+    }
+    for (const auto& p : stat_planes)
+        in.stats.push_back({p.n.data(), reinterpret_cast<const long long*>(p.s1.data()), reinterpret_cast<const unsigned long long*>(p.s2.data())});
+    for (const auto& c : cubes) in.cubes.push_back(c.data());
+    return detail::zonal_table(e, cstats, hist, in, with_counts, out);
 }
 
 // PipelineConfig::surface_channels: the band and its geometry into host memory the pipeline owns.
@@ -73,6 +110,7 @@ Status Pipeline::Host::set_surface(const std::string& name, const Grid& grid, in
 Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     const size_t n = cloud_in.count();
     if (n == 0) return Status::success();                            // pipeline.cpp:284-287
+    zonal_fresh = false;
     std::unique_ptr<PointCloud> copy;
     const PointCloud* cloud = &cloud_in;
     if (cloud->location() == MemoryLocation::Device) {
@@ -286,6 +324,7 @@ Status Pipeline::Host::finalize() {
         if (!fs.ok()) return fs;
     }
     finalized = true;
+    zonal_fresh = true;
     if (!cfg.output_path.empty()) return write_geotiff(cfg.output_path, *result, g, pipeline_output_options(cfg.write_cog));    // pipeline.cpp:1351-1361
     return Status::success();
 }

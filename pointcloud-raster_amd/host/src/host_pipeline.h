@@ -11,8 +11,10 @@
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
 #include "sample_grid.h"
+#include "zonal.h"
 
 #include <chrono>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -46,6 +48,9 @@ struct Pipeline::Host {
     bool finalized = false;
     std::vector<TreeTable> tree_tables;      // PipelineConfig::trees, entry by entry, as the last finalize left them
     std::vector<Status> tree_status;
+    detail::ZonalPlan zonal_plan;            // PipelineConfig::zonal, planned at init
+    std::map<std::string, detail::ZoneGrid> zone_grids;   // the label grids of set_zones, by name, in host memory
+    bool zonal_fresh = false;                // the last finalize's bands and the planes belong together: no ingest since
     ProgressCallback callback;
     size_t collections = 0, points = 0;
     ScatterInfo last{};
@@ -55,6 +60,8 @@ struct Pipeline::Host {
     Status ingest(const PointCloud& cloud);
     Status finalize();
     Status set_surface(const std::string& name, const Grid& grid, int band);
+    Status set_zones(const std::string& name, const Grid& grid, int band);
+    Status zonal(int i, ZonalTable* out, bool with_counts) const;
     Status save_state(const std::string& dir);
     Status load_state(const std::string& dir);
     ProgressInfo stats() const;

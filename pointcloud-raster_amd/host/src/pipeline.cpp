@@ -20,6 +20,7 @@
 #include "histogram.h"
 #include "terrain.h"
 #include "trees.h"
+#include "zonal.h"
 #include "host_pipeline.h"
 #include "las_io.h"
 #include "pcr/core/point_cloud.h"
@@ -119,6 +120,9 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         detail::TreesPlan trees;
         const Status rs = detail::plan_trees(config, plan, terrain, &trees);
         if (!rs.ok()) return fail_with(rs);
+        detail::ZonalPlan zonal;
+        const Status zs = detail::plan_zonal(config, plan, terrain, trees, &zonal);
+        if (!zs.ok()) return fail_with(zs);
     }
     {
         const Status ss = detail::plan_surfaces(config);
@@ -130,6 +134,7 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         if (!config.histograms.empty()) return fail_with(detail::histograms_out_of_core_error());
         if (!config.extremes.empty()) return fail_with(detail::extremes_out_of_core_error());
         if (!config.cell_stats.empty()) return fail_with(detail::cell_stats_out_of_core_error());
+        if (!config.zonal.empty()) return fail_with(detail::zonal_out_of_core_error());
         Status bs = Status::success();
         p->banded_ = Banded::create(config, p.get(), budget, &bs);
         if (!p->banded_) return fail_with(bs);
@@ -352,6 +357,16 @@ Status Pipeline::trees(int i, TreeTable* out) const {
     if (!status[(size_t)i].ok()) return status[(size_t)i];
     *out = tables[(size_t)i];
     return Status::success();
+}
+Status Pipeline::set_zones(const std::string& name, const Grid& grid, int band) {
+    if (host_) return host_->set_zones(name, grid, band);
+    if (banded_) return Status::error(StatusCode::InvalidArgument, "pipeline: set_zones: '" + name + "' names no external label grid of this pipeline");
+    return impl_->set_zones(name, grid, band);
+}
+Status Pipeline::zonal(int i, ZonalTable* out, bool with_counts) const {
+    if (impl_) return impl_->zonal(i, out, with_counts);
+    if (host_) return host_->zonal(i, out, with_counts);
+    return Status::error(StatusCode::InvalidArgument, "pipeline: zonal: no zonal entry " + std::to_string(i) + " (of a finalize with no ingest since)");
 }
 Status Pipeline::finalize() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(); }
 Status Pipeline::finalize_async() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(false); }

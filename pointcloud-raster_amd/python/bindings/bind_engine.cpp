@@ -203,6 +203,37 @@ void bind_engine(py::module_& m) {
         .def_readwrite("filter", &CellStatsConfig::filter)
         .def_readwrite("band_names", &CellStatsConfig::band_names);
 
+    py::class_<ZonalConfig>(m, "ZonalConfig",
+                            "One table with a row per zone -- per tree with a tree_id band, per plot with a label grid of "
+                            "Pipeline.set_zones -- of the chosen cell_stats entries and histograms (Pipeline.zonal)")
+        .def(py::init<>())
+        .def(py::init<const ZonalConfig&>())
+        .def(py::init([](const std::string& zones, bool external, const std::vector<int>& cell_stats, const std::vector<int>& histograms,
+                         const py::object& percentiles, int max_zones) {
+            ZonalConfig c;
+            c.zones = zones;
+            c.external = external;
+            c.cell_stats = cell_stats;
+            c.histograms = histograms;
+            c.own_percentiles = percentiles.is_none();
+            if (!c.own_percentiles) c.percentiles = percentiles.cast<std::vector<float>>();
+            c.max_zones = max_zones;
+            return c;
+        }), py::arg("zones"), py::arg("external") = false, py::arg("cell_stats") = std::vector<int>{},
+            py::arg("histograms") = std::vector<int>{}, py::arg("percentiles") = py::none(), py::arg("max_zones") = 1 << 22)
+        .def_readwrite("zones", &ZonalConfig::zones)
+        .def_readwrite("external", &ZonalConfig::external)
+        .def_readwrite("cell_stats", &ZonalConfig::cell_stats)
+        .def_readwrite("histograms", &ZonalConfig::histograms)
+        .def_property("percentiles", [](const ZonalConfig& c) -> py::object {
+            if (c.own_percentiles) return py::none();
+            return py::cast(c.percentiles);
+        }, [](ZonalConfig& c, const py::object& v) {
+            c.own_percentiles = v.is_none();
+            c.percentiles = c.own_percentiles ? std::vector<float>() : v.cast<std::vector<float>>();
+        }, "None: every chosen histogram with its entry's own percentile list")
+        .def_readwrite("max_zones", &ZonalConfig::max_zones);
+
     py::class_<PipelineConfig>(m, "PipelineConfig")
         .def(py::init<>())
         .def_readwrite("grid", &PipelineConfig::grid)
@@ -250,7 +281,10 @@ void bind_engine(py::module_& m) {
                        "finalize() appends behind the percentile bands (assign a list of ExtremesConfig)")
         .def_readwrite("cell_stats", &PipelineConfig::cell_stats,
                        "Per-cell integer sums kept at every ingest and the exact Mean / Variance / StdDev bands finalize() appends "
-                       "behind the extremes' bands (assign a list of CellStatsConfig)");
+                       "behind the extremes' bands (assign a list of CellStatsConfig)")
+        .def_readwrite("zonal", &PipelineConfig::zonal,
+                       "Zonal tables: Pipeline.zonal(i) folds the chosen cell_stats planes and histogram cubes by a label band into "
+                       "one row per zone (assign a list of ZonalConfig); nothing happens at ingest or in finalize()");
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
         .def(py::init<>())
@@ -332,6 +366,49 @@ void bind_engine(py::module_& m) {
         }, py::arg("i") = 0,
              "The table of trees entry i of the last finalize as a dict of numpy arrays row, col, x, y, height, crown_cells; row k "
              "is the tree with id k + 1")
+        .def("set_zones", [](Pipeline& p, const std::string& name, const Grid& grid, int band) {
+            raise_if_error(p.set_zones(name, grid, band));
+        }, py::arg("name"), py::arg("grid"), py::arg("band") = 0,
+             "Gives the external label grid `name` of a ZonalConfig its labels: band `band` of a grid with the pipeline's width and "
+             "height, copied into the pipeline")
+        .def("zonal", [](const Pipeline& p, int i) {
+            ZonalTable t;
+            raise_if_error(p.zonal(i, &t));
+            auto column = [](const auto& v) {
+                using T = typename std::decay_t<decltype(v)>::value_type;
+                py::array_t<T> a((py::ssize_t)v.size());
+                if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
+                return a;
+            };
+            py::dict d;
+            d["zone"] = column(t.zone);
+            d["cells"] = column(t.cells);
+            for (const auto& c : t.stats) {
+                d[py::str(c.channel + "_n")] = column(c.n);
+                d[py::str(c.channel + "_mean")] = column(c.mean);
+                d[py::str(c.channel + "_var")] = column(c.var);
+                d[py::str(c.channel + "_std")] = column(c.stddev);
+            }
+            for (const auto& c : t.hists) {
+                d[py::str(c.channel + "_hist_n")] = column(c.hist_n);
+                for (size_t j = 0; j < c.q.size(); ++j)
+                    d[py::str(c.channel + "_p" + std::to_string(std::lround((double)c.q[j] * 100.0)))] = column(c.p[j]);
+            }
+            return d;
+        }, py::arg("i") = 0,
+             "The table of zonal entry i as a dict of numpy arrays: zone (int32), cells (int64), per cell_stats entry "
+             "{channel}_n (uint64), _mean, _var, _std (float32), per histogram {channel}_hist_n (uint64) and {channel}_p{round(q*100)} "
+             "(float32); row k is zone k + 1.  Valid after a finalize with no ingest since")
+        .def("zonal_histogram", [](const Pipeline& p, int i, int h) {
+            ZonalTable t;
+            raise_if_error(p.zonal(i, &t, true));
+            if (h < 0 || (size_t)h >= t.hists.size()) throw std::runtime_error("pipeline: zonal_histogram: no histogram " + std::to_string(h) + " in the entry");
+            const auto& c = t.hists[(size_t)h];
+            py::array_t<uint64_t> a({(py::ssize_t)t.size(), (py::ssize_t)c.bins});
+            if (!c.counts.empty()) std::memcpy(a.mutable_data(), c.counts.data(), c.counts.size() * sizeof(uint64_t));
+            return a;
+        }, py::arg("i") = 0, py::arg("h") = 0,
+             "The (zones, bins) uint64 counts of the h-th histogram chosen by zonal entry i")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },
              "Device-resident result: the finalize kernels are only enqueued on the pipeline's stream (complete after synchronize()); "

@@ -78,7 +78,7 @@ from ._pcr import (  # noqa: E402,F401
     TerrainProduct, TerrainSpec, TerrainBandConfig, terrain, terrain_light,
     TreeSpec, TreeBandConfig, segment_trees,
     SampleMode, SurfaceChannelConfig, sample_grid,
-    HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig,
+    HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig, ZonalConfig,
 )
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
@@ -182,5 +182,5 @@ __all__ = [
     "TerrainProduct", "TerrainSpec", "TerrainBandConfig", "terrain", "terrain_light",
     "TreeSpec", "TreeBandConfig", "segment_trees",
     "SampleMode", "SurfaceChannelConfig", "sample_grid",
-    "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig",
+    "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig", "ZonalConfig",
 ]

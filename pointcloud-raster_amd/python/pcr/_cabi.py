@@ -83,6 +83,14 @@ class LasLayout(C.Structure):
                 ("offset", C.c_double * 3), ("gps_time_origin", C.c_double)]
 
 
+class ZoneFoldParams(C.Structure):
+    """pcr_hip_zone_fold_params: combine = 1 sums along runs of equal zones first, 0 issues one set of atomics per cell."""
+    _fields_ = [("combine", C.c_int32), ("reserved_", C.c_int32)]
+
+    def __init__(self, combine=1):
+        super().__init__(combine=combine, reserved_=0)
+
+
 class TreeParams(C.Structure):
     """pcr_hip_tree_params with the defaults of pcr.TreeSpec."""
     _fields_ = [("min_height", C.c_float), ("window_base", C.c_float), ("window_slope", C.c_float),
@@ -225,6 +233,18 @@ SYMBOLS = {
                                  C.POINTER(_VP), _VP],
     "pcr_hip_cell_stats_bands_host": [C.POINTER(Grid), _VP, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int),
                                       C.POINTER(_VP)],
+    "pcr_hip_zone_max": [_VP, C.c_int, C.c_int, _I64, _VP, _VP],
+    "pcr_hip_zone_max_host": [_VP, C.c_int, C.c_int, _I64, C.POINTER(_U32)],
+    "pcr_hip_zone_fold_stats": [_VP, C.c_int, C.c_int, _I64, _VP, _VP, _VP, _I64, _U32, C.POINTER(ZoneFoldParams), _VP, _VP, _VP, _VP,
+                                _VP],
+    "pcr_hip_zone_fold_stats_host": [_VP, C.c_int, C.c_int, _I64, _VP, _VP, _VP, _I64, _U32, C.POINTER(ZoneFoldParams), _VP, _VP, _VP,
+                                     _VP],
+    "pcr_hip_zone_fold_hist": [_VP, C.c_int, C.c_int, _I64, _VP, C.c_int, _I64, _I64, _U32, C.POINTER(ZoneFoldParams), _VP, _VP],
+    "pcr_hip_zone_fold_hist_host": [_VP, C.c_int, C.c_int, _I64, _VP, C.c_int, _I64, _I64, _U32, C.POINTER(ZoneFoldParams), _VP],
+    "pcr_hip_zone_rows_stats": [_VP, _VP, _VP, _U32, C.c_double, C.c_double, C.c_int, _VP, _VP, _VP, _VP],
+    "pcr_hip_zone_rows_stats_host": [_VP, _VP, _VP, _U32, C.c_double, C.c_double, C.c_int, _VP, _VP, _VP],
+    "pcr_hip_zone_rows_percentiles": [_VP, C.c_int, _U32, C.c_double, C.c_double, C.c_int, _VP, _VP, C.POINTER(_VP), _VP],
+    "pcr_hip_zone_rows_percentiles_host": [_VP, C.c_int, _U32, C.c_double, C.c_double, C.c_int, _VP, _VP, C.POINTER(_VP)],
 }
 
 _lib = None
