@@ -296,7 +296,7 @@ struct PipelineConfig {
     // which may test them.  A name works wherever the configuration names a Float32 channel: a reduction's value_channel or
     // timestamp_channel, a glyph's per-point channels, a predicate of `filter` or of a ReductionSpec::filter ("hag > 2").  A
     // NaN sample (a point outside the surface, over a NaN cell, with a NaN value) is a NaN channel value like one a cloud
-    // brings: reductions treat it as they do, every predicate on it is false.  On the HIP engine the channel is gathered in
+    // brings: reductions treat it as they do, every predicate on it but NotEqual and NotInSet is false.  On the HIP engine the channel is gathered in
     // HBM on the pipeline's stream -- ingest_file of a LAS tile still ships raw records -- and a configuration gives the same
     // channel bits on both engines.  Each name needs its surface before the first ingest (Pipeline::set_surface); checkpoints
     // record no surface.  create() refuses an empty or duplicate name, a value_channel that is itself a surface channel, more
@@ -405,7 +405,8 @@ public:
     Status cell_stats_shape(int i, int* rows, int* width) const;
     /// Extension: the table of PipelineConfig::trees[i] as the last finalize() left it -- one row per tree, ids 1..size(), the
     /// cell centres by the grid's geometry.  Valid after a finalize (also finalize_async: on the HIP engine the call waits for
-    /// the pipeline's stream and fetches the table then); a later finalize replaces it.  InvalidArgument for an index outside
+    /// the pipeline's stream and fetches the table then); a later finalize replaces it, and nothing else does: after further
+    /// ingests the table is still the last finalize's, like result().  InvalidArgument for an index outside
     /// the list or before the first finalize; OutOfRange for more than 2^24 trees.
     Status trees(int i, TreeTable* out) const;
     /// Extension: gives the external label grid `name` (a PipelineConfig::zonal entry with `external`) its labels -- band `band`
@@ -414,7 +415,10 @@ public:
     /// change afterwards.  InvalidArgument for an unknown name, another shape, a band outside the grid or not Float32.
     Status set_zones(const std::string& name, const Grid& grid, int band = 0);
     /// Extension: the table of PipelineConfig::zonal[i] -- the zone band as the last finalize() left it (or the external grid),
-    /// the cell-stats planes and cubes as they are.  Valid after a finalize with no ingest since (also finalize_async: on the HIP
+    /// the cell-stats planes and cubes as they are.  Valid after a finalize with no ingest since -- an ingest of an empty cloud, or
+    /// of one that PipelineConfig::filter keeps no point of, changes no state and does not count, on either engine; handing out or
+    /// writing through state_planes() and the touched flags, merge_touched and a refused save_state / load_state leave the table
+    /// as it is, as they leave Pipeline::trees' (also finalize_async: on the HIP
     /// engine the call is enqueued behind it on the pipeline's stream, which is waited for once for the number of zones and once
     /// for the table).  InvalidArgument for an index outside the list, before the first finalize, after a further ingest or for
     /// an external grid that was not set; OutOfRange for a zone above the entry's max_zones.  with_counts: also copy out every

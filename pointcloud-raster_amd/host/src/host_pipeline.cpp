@@ -110,7 +110,6 @@ Status Pipeline::Host::set_surface(const std::string& name, const Grid& grid, in
 Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     const size_t n = cloud_in.count();
     if (n == 0) return Status::success();                            // pipeline.cpp:284-287
-    zonal_fresh = false;
     std::unique_ptr<PointCloud> copy;
     const PointCloud* cloud = &cloud_in;
     if (cloud->location() == MemoryLocation::Device) {
@@ -207,6 +206,9 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         for (uint8_t k : keep) kept += k;
         if (kept == 0) return Status::success();                     // pipeline.cpp:349-353
     }
+    // (this cloud's points change the state: a cloud that is empty or that PipelineConfig::filter empties changes nothing, and the
+    // tables of the last finalize stay valid -- as on the HIP engine)
+    zonal_fresh = false;
     std::vector<std::vector<uint8_t>> class_keep(filters.classes.size());
     for (size_t k = 1; k < filters.classes.size(); ++k) apply(filters.classes[k], class_keep[k]);
     auto keep_of = [&](const Group& gr, size_t i0) -> const uint8_t* { return gr.cls ? class_keep[(size_t)gr.cls].data() + i0 : nullptr; };

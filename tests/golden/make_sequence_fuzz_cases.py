@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Writes tests/golden/sequence_fuzz_cases.json: one SHA-256 per seed (sequence_fuzz_common.case_digest) of the 40 cases that
 were the operation-sequence fuzz's suite before it drew terrain bands, recorded with the generator of that commit, and under
-the key `sha256_line` one per seed of LINE_SEEDS (the line cases: the digest covers the glyphs and the `dir` / `hl` arrays).
+the key `sha256_line` one per seed of LINE_SEEDS (the line cases: the digest covers the glyphs and the `dir` / `hl` arrays), and
+under `sha256_acc` one per seed of ACC_SEEDS (the accumulator cases: the digest of the case as it is, its filters, `acc` lists,
+trees, zonal and terrain lists and `z` arrays included).
 
     python tests/golden/make_sequence_fuzz_cases.py
 
@@ -31,11 +33,12 @@ def main():
 
     rec = {str(seed): digest(seed) for seed in SEEDS}
     line = {str(seed): digest(seed) for seed in S.LINE_SEEDS}
+    acc = {str(seed): S.case_digest(S.build(seed)) for seed in S.ACC_SEEDS}
     with open(OUT, "w") as f:
         json.dump(dict(what="sequence_fuzz_common.case_digest(build(seed)) per seed, before terrain was drawn", sha256=rec,
-                       sha256_line=line), f, indent=1)
+                       sha256_line=line, sha256_acc=acc), f, indent=1)
         f.write("\n")
-    print(f"{OUT}: {len(rec)} + {len(line)} seeds")
+    print(f"{OUT}: {len(rec)} + {len(line)} + {len(acc)} seeds")
 
 
 if __name__ == "__main__":

@@ -27,7 +27,15 @@ cloud a `dir` and an `hl` channel, and may replace clouds by a hot Line tile or 
 footprint (oracle/pcr_oracle.c through pcr_oracle_py, the one thing here that is not NumPy) in binary64 and needs no
 tolerance.  _line_pass checks the exactness condition for the Line sums with the oracle's binary64 mode on |v| and thins a
 cloud that would break it.  Gaussian groups are not drawn: their weights are expf values and their sums depend on the order
-of addition."""
+of addition.
+
+Accumulator cases: a seed from ACC_SEED_BASE on is what the Point-only generator draws for it, in core, plus (_acc_pass and
+_acc_tables, last and from generators of their own) a float32 channel `z` of arbitrary values on every cloud, surface channels,
+a filter of its own on reductions and accumulator entries, histograms, extremes and cell-stats entries, tree bands, zonal
+tables, and the ops read_acc, tables and set_zones.  `z` and the surface channels feed selections (Max, Min, MostRecent) and
+accumulators only, whose states are integers and whose bands are defined bit by bit: the model is the *_common model of each
+feature on the same routing, the host twin for the tree bands, zonal_common's Python ints for the tables -- no tolerance.
+save_state and load_state are refused while an accumulator list is non-empty: the ops stay, must raise, and move nothing."""
 import filecmp
 import os
 
@@ -88,7 +96,7 @@ def seeds_from_env(name="PCR_SEQ_FUZZ_SEEDS"):
         return list(range(int(a), int(b)))
     if env:
         return [int(v) for v in env.split(",")]
-    return list(DEFAULT_SEEDS) + list(LINE_SEEDS)
+    return list(DEFAULT_SEEDS) + list(LINE_SEEDS) + list(ACC_SEEDS)
 
 
 # ---- the generator (NumPy only; a line case: and the oracle) ------------------------------------------------------------------------------------------------
@@ -105,16 +113,17 @@ def cells_of(g, x, y):
 
 def groups_of(specs):
     """Accumulation groups as every engine forms them (pipeline_common.h: same_group): same value channel through the same
-    glyph -- every parameter of it, same_glyph -- (MostRecent: and timestamp channel, a group of its own)."""
+    glyph -- every parameter of it, same_glyph -- (MostRecent: and timestamp channel, a group of its own) under the same
+    ReductionSpec::filter (an accumulator case: the same predicates in the same order)."""
     groups = []
     for i, s in enumerate(specs):
         gl = s.get("glyph")
-        key = (s["ch"], s["type"] == "MostRecent", None if gl is None else tuple(sorted(gl.items())))
+        key = (s["ch"], s["type"] == "MostRecent", None if gl is None else tuple(sorted(gl.items())), filter_key(s.get("filt")))
         for gr in groups:
             if gr["key"] == key:
                 break
         else:
-            gr = dict(key=key, ch=s["ch"], select=key[1], glyph=gl, slots=set(), outs=[])
+            gr = dict(key=key, ch=s["ch"], select=key[1], glyph=gl, slots=set(), outs=[], filt=s.get("filt"))
             groups.append(gr)
         gr["slots"].update(PLANES_OF[s["type"]])
         gr["outs"].append(i)
@@ -140,14 +149,15 @@ def terrain_band_name(t):
     return t["name"] or f"{t['source']}_{t['product']}"
 
 
-def _draw_terrain(rng, specs, plan):
+def _draw_terrain(rng, specs, plan, more=()):
     """PipelineConfig::terrain of a plan: 0 to 6 entries (none in four plans of ten), each a product of any band that leaves
     under the plan.  Half of the entries copy source, z_factor and compute_edges from the entry before, so that launches of
     several products form -- also ones whose Hillshade entry is not the first and has a light of its own.  Every entry draws
-    all its numbers, used or not: what one entry draws does not move the next."""
-    sources = [band_name(i, s) for i, s in enumerate(specs)]
+    all its numbers, used or not: what one entry draws does not move the next.  `more`: an accumulator case's percentile,
+    extremes and Mean bands."""
+    sources = [band_name(i, s) for i, s in enumerate(specs)] + list(more)
     if plan["ground"]:
-        sources += ["dtm"] + (["hag"] if plan["ground"]["top"] is not None else [])
+        sources += ["dtm"] + (["hag"] if ground_names(specs, plan)[1] is not None else [])
     n = 0 if rng.uniform() < 0.4 else int(rng.integers(1, 7))
     out, taken = [], set(sources)
     for k in range(n):
@@ -235,8 +245,11 @@ CLOUD_KEYS = ("x", "y", "a", "b", "t", "cls")
 LINE_CLOUD_KEYS = ("dir", "hl")            # only the clouds of a line case have them
 
 
+ACC_CLOUD_KEYS = ("z",)                    # ... and only the clouds of an accumulator case this one
+
+
 def cloud_keys(c):
-    return CLOUD_KEYS + (LINE_CLOUD_KEYS if "dir" in c else ())
+    return CLOUD_KEYS + (LINE_CLOUD_KEYS if "dir" in c else ()) + (ACC_CLOUD_KEYS if "z" in c else ())
 
 
 def _thin(c, keep):
@@ -471,6 +484,341 @@ def _line_pass(seed, g, specs, ops, clouds, filt):
     return groups
 
 
+# ---- accumulator cases ---------------------------------------------------------------------------------------------------------
+# A seed from ACC_SEED_BASE on is an accumulator case (never a line case): what the Point-only generator draws for the seed, in
+# core, plus -- last and from generators of their own, (95000, seed, k) -- a float32 channel `z` on every cloud, surface channels,
+# per-reduction filters, histograms, extremes and cell-stats entries, tree bands and zonal tables, and the ops that read them.
+ACC_SEED_BASE = 10000
+ACC_ITEM_RECORDS = 1 << 16                 # kHistItemRecords, kExtItemRecords, kStatItemRecords: the scan splits a bin that holds more
+ACC_HOT_W, ACC_HOT_H = 128, 8              # every accumulator LDS tile is 128 columns wide and at least 8 rows tall, from cell (0, 0)
+HIST_BINS = (1, 8, 37, 256)
+ACC_MAX_COUNTERS = 6_000_000               # bins x cells of one cube: 256 bins up to ~150 x 150 cells, 37 up to ~400 x 400
+HIST_RANGES = ((-4.0, 28.0), (5.0, 12.0), (-1000.0, 1000.0), (40.0, 50.0))     # inside, narrower than, around and beyond the canopy's values
+HIST_QS = (0.0, 0.05, 0.25, 0.5, 0.75, 0.95, 1.0)
+EXT_K = (2, 4, 8)
+EXT_GAPS = (0.0, 0.5, 1.0, float("inf"))
+STAT_STEPS = ((0.0, 0.01), (-2.0, 2.0 ** -6), (1500.0, 0.001))
+STAT_SUFFIX = ("mean", "var", "std")       # CellStat's order
+ZONAL_MAX_BINS = 37                        # the Python-int fold walks every bin of every labelled cell
+# TreeSpec parameters tests/test_trees.py holds the host twin to the brute-force model with
+TREE_KW = (dict(), dict(max_radius_cells=1), dict(max_radius_cells=32, window_base=20.0, window_slope=1.5),
+           dict(window_base=0.0, window_slope=0.0), dict(min_height=5.0, min_crown_height=1.0, crown_ratio=0.8, max_crown_radius=3.0),
+           dict(crown_ratio=0.0, max_crown_radius=float("inf"), min_crown_height=-5.0),
+           dict(min_height=0.5, min_crown_height=0.25, window_base=5.0), dict(min_height=-100.0))
+SURFACE_THRESHOLDS = (-120.0, -95.0, 0.0, 2.5, 100.0)
+
+
+def filter_key(f):
+    """What makes two filters equal to same_predicate: the fields a predicate's op uses (the set of InSet / NotInSet, else the value)."""
+    return None if not f else tuple((p["ch"], p["op"], tuple(p["set"]) if p["op"] in ("InSet", "NotInSet") else p["value"]) for p in f)
+
+
+def pred_mask(ch, p):
+    """One predicate on float32 values, as NumPy compares them: a NaN fails all but NotEqual and NotInSet."""
+    v = np.asarray(ch, np.float32)
+    with np.errstate(all="ignore"):
+        if p["op"] in ("InSet", "NotInSet"):
+            inside = np.isin(v, np.array(p["set"], np.float32))
+            return inside if p["op"] == "InSet" else ~inside
+        t = np.float32(p["value"])
+        return {"Equal": v == t, "NotEqual": v != t, "Less": v < t, "LessEqual": v <= t, "Greater": v > t, "GreaterEqual": v >= t}[p["op"]]
+
+
+def conj_mask(chans, f, n):
+    """AND of a filter's predicates over the channels of a cloud (its surface channels included)."""
+    keep = np.ones(n, bool)
+    for p in f or ():
+        keep &= pred_mask(chans[p["ch"]], p)
+    return keep
+
+
+def surface_of(sc):
+    import sample_grid_common as SG
+    return SG.make_surface(sc["w"], sc["h"], sc["seed"], csx=sc["csx"], csy=sc["csy"], min_x=sc["min_x"], max_y=sc["max_y"])
+
+
+def surface_channels(acc, c):
+    """The cloud's channels and the surface channels of the case, by sample_grid_common.model."""
+    import sample_grid_common as SG
+    out = dict(c)
+    for sc in acc["surfaces"]:
+        out[sc["name"]] = SG.model(surface_of(sc), c["x"], c["y"], c["z"] if sc["value"] else None, sc["mode"]) if len(c["x"]) else np.zeros(0, np.float32)
+    return out
+
+
+def ground_names(specs, plan):
+    """(source band, top band or None) of a plan's ground filter: by index into the reductions, or -- an accumulator case --
+    by name."""
+    gr = plan["ground"]
+    if "source_name" in gr:
+        return gr["source_name"], gr["top_name"]
+    return band_name(gr["source"], specs[gr["source"]]), None if gr["top"] is None else band_name(gr["top"], specs[gr["top"]])
+
+
+def acc_bands(acc):
+    """The accumulator bands in the order they leave, behind the reductions': [(name, kind, entry, index within it)]."""
+    out = []
+    for i, h in enumerate(acc["hist"]):
+        out += [(f"h{i}_p{j}", "percentile", i, j) for j in range(len(h["qs"]))]
+    out += [(f"x{i}_{'high' if e['side'] else 'low'}", "extremes", i, 0) for i, e in enumerate(acc["ext"])]
+    for i, s in enumerate(acc["stats"]):
+        out += [(f"c{i}_{STAT_SUFFIX[p]}", STAT_SUFFIX[p], i, j) for j, p in enumerate(s["products"])]
+    return out
+
+
+def acc_filled(kind):
+    """fill_nodata_radius: percentile bands fill like Max, extremes like Min or Max, Mean like Average; Variance and StdDev never."""
+    return kind in ("percentile", "extremes", "mean")
+
+
+def acc_terrain_sources(acc):
+    return [name for name, kind, _, _ in acc_bands(acc) if acc_filled(kind)]
+
+
+def z_field(g, seed):
+    """The canopy of a case: Gaussian bumps of height 3..30 and sigma 1.5..5 cells (trees_common.canopy's kind), in cell units."""
+    r = np.random.default_rng((95000, seed, 999))
+    n = int(min(120, max(3, g["W"] * g["H"] // 400)))
+    return r.uniform(0, g["H"], n), r.uniform(0, g["W"], n), r.uniform(3.0, 30.0, n), r.uniform(1.5, 5.0, n)
+
+
+def _draw_z(rc, g, c, field, shift, specials=1.0):
+    """Channel `z` of a cloud: the canopy at the point plus noise (+ shift), float32; then a share of NaN, +-Inf, -0.0,
+    denormals, and values far beyond every histogram's [lo, hi) and every cell-stats entry's +-2^21 steps.  No +0.0: the
+    engines' Max and Min of -0.0 and +0.0 need not agree on the sign, and with one zero there is nothing to agree on."""
+    n = len(c["x"])
+    r0, c0, amp, sig = field
+    u, v = (c["x"] - g["min_x"]) / g["cs"], (g["max_y"] - c["y"]) / g["cs"]
+    z = np.zeros(n)
+    for k in range(len(r0)):
+        near = (np.abs(v - r0[k]) < 4 * sig[k]) & (np.abs(u - c0[k]) < 4 * sig[k])
+        z[near] = np.maximum(z[near], amp[k] * np.exp(-((v[near] - r0[k]) ** 2 + (u[near] - c0[k]) ** 2) / (2.0 * sig[k] ** 2)))
+    z = (z + rc.normal(0.0, 0.3, n) + shift).astype(np.float32)
+    kind = rc.uniform(size=n) * specials
+    z[kind < 0.03] = np.nan
+    z[(kind >= 0.03) & (kind < 0.035)] = np.inf
+    z[(kind >= 0.035) & (kind < 0.04)] = -np.inf
+    z[(kind >= 0.04) & (kind < 0.06)] = np.float32(-0.0)
+    den = (kind >= 0.06) & (kind < 0.07)
+    z[den] = rc.integers(1, 1 << 23, int(den.sum())).astype(np.uint32).view(np.float32) * rc.choice([-1.0, 1.0], int(den.sum())).astype(np.float32)
+    far = (kind >= 0.07) & (kind < 0.08)
+    z[far] = (rc.choice([-1.0, 1.0], int(far.sum())) * 10.0 ** rc.uniform(5, 9, int(far.sum()))).astype(np.float32)
+    z[z == 0] = np.float32(-0.0)
+    c["z"] = z
+
+
+def kept_classes(filt, *filters):
+    """The classes 0..3 that the pipeline filter and the `cls` predicates of every given filter keep."""
+    cls = np.arange(4, dtype=np.float32)
+    keep = keep_mask(filt, cls)
+    for f in filters:
+        for p in f or ():
+            if p["ch"] == "cls":
+                keep &= pred_mask(cls, p)
+    return cls[keep]
+
+
+def acc_entries(acc):
+    return [e for kind in ("hist", "ext", "stats") for e in acc[kind]]
+
+
+def _acc_pass(seed, g, specs, ops, clouds, filt, plan):
+    """What makes a seed >= ACC_SEED_BASE an accumulator case, from generators of its own (95000, seed, k): k = 0 the lists
+    and the plan, k = 1 + i channel `z` (and maybe the replacement) of cloud i.  -> (groups, acc)"""
+    ra = np.random.default_rng((95000, seed, 0))
+    W, H, cs = g["W"], g["H"], g["cs"]
+    # plane writes name a group: they follow their reduction when the filters regroup the specs
+    for o in ops:
+        if o["op"] == "planes_write":
+            o["spec"] = next(i for i, s in enumerate(specs) if s["group"] == o["group"] and o["slot"] in PLANES_OF[s["type"]]
+                             and s["type"] in ("Sum", "Count", "Average"))
+        elif o["op"] == "checkpoint":                            # refused: no new pipeline, plan or flavour
+            o["plan"] = o["flavour"] = None
+    surfaces = []
+    if ra.uniform() < 0.4:
+        kinds = [("hag", "z"), ("smp", "")]
+        two = bool(ra.uniform() < 0.4)
+        first = int(ra.uniform() < 0.3)
+        for name, value in ([kinds[first], kinds[1 - first]] if two else [kinds[first]]):
+            sw, sh = int(ra.integers(8, 41)), int(ra.integers(8, 41))
+            surfaces.append(dict(name=name, value=value, mode=int(ra.integers(0, 2)), w=sw, h=sh, seed=int(ra.integers(0, 1 << 30)),
+                                 csx=float(W * cs * ra.uniform(0.6, 1.1) / sw), csy=float(-H * cs * ra.uniform(0.6, 1.1) / sh),
+                                 min_x=float(g["min_x"] + W * cs * ra.uniform(-0.1, 0.2)), max_y=float(g["max_y"] - H * cs * ra.uniform(-0.1, 0.2))))
+    snames = [sc["name"] for sc in surfaces]
+    # the filters of the case: a pool of up to 5 conjunctions of 1 to 3 predicates (create's limits: 8 distinct filters, 16
+    # predicates per conjunction with the pipeline filter's, 32 in all), so that equal filters -- one class -- occur
+    pool = []
+    for _ in range(int(ra.integers(1, 6))):
+        f = []
+        for _ in range(int(ra.integers(1, 4))):
+            if snames and ra.uniform() < 0.25:
+                f.append(dict(ch=str(ra.choice(snames)), op=str(ra.choice(OPS8)), value=float(ra.choice(SURFACE_THRESHOLDS)),
+                              set=[float(v) for v in ra.choice(SURFACE_THRESHOLDS, 2, replace=False)]))
+            else:
+                f.append(dict(ch="cls", op=str(ra.choice(OPS8)), value=float(ra.integers(0, 4)),
+                              set=[float(v) for v in ra.choice(4, int(ra.integers(1, 4)), replace=False)]))
+        if filter_key(f) not in [filter_key(q) for q in pool]:
+            pool.append(f)
+    pick = lambda p: pool[int(ra.integers(0, len(pool)))] if ra.uniform() < p else []
+    chan = lambda: str(ra.choice(snames)) if snames and ra.uniform() < 0.35 else "z"
+    hist, ext, stats = [], [], []
+    counts = [int(ra.integers(0, 4)) for _ in range(3)]
+    if sum(counts) == 0:
+        counts[int(ra.integers(0, 3))] = 1
+    for _ in range(counts[0]):
+        lo, hi = HIST_RANGES[int(ra.integers(0, len(HIST_RANGES)))]
+        qs = [HIST_QS[i] for i in ra.permutation(len(HIST_QS))[:int(ra.integers(0, 5))]]
+        bins = int(ra.choice(HIST_BINS))
+        while bins * W * H > ACC_MAX_COUNTERS:                   # (the cube and the model's walk of it stay small: fewer bins on a large grid)
+            bins = HIST_BINS[HIST_BINS.index(bins) - 1]
+        hist.append(dict(ch=chan(), lo=lo, hi=hi, bins=bins, qs=qs, filt=pick(0.6)))
+    for _ in range(counts[1]):
+        ext.append(dict(ch=chan(), side=int(ra.integers(0, 2)), k=int(ra.choice(EXT_K)), gap=float(ra.choice(EXT_GAPS)), filt=pick(0.6)))
+    for _ in range(counts[2]):
+        origin, res = STAT_STEPS[int(ra.integers(0, 3))]
+        products = [int(p) for p in ra.permutation(3)[:int(ra.integers(1, 4))]]
+        stats.append(dict(ch=chan(), origin=origin, res=res, products=products, ddof=int(ra.integers(0, 2)), filt=pick(0.6)))
+    shift = 1500.0 if any(s["origin"] == 1500.0 for s in stats) else 0.0
+    for h in hist:
+        if h["ch"] == "z":
+            h["lo"], h["hi"] = h["lo"] + shift, h["hi"] + shift
+    # reductions on `z` and on surface channels: selections only (Max, Min, MostRecent); then every reduction's filter
+    for _ in range(int(ra.integers(0, 4))):
+        ch = chan()
+        specs.append(dict(type=str(ra.choice(["Max", "Min"] if ch != "z" else ["Max", "Min", "MostRecent"])), ch=ch))
+    if snames and "hag" in snames and ra.uniform() < 0.5:
+        specs.append(dict(type="Max", ch="hag"))                # the canopy height model trees are made for
+    for s in specs:
+        s["filt"] = pick(0.5)
+    groups = groups_of(specs)
+    for o in ops:
+        if o["op"] == "planes_write":
+            o["group"] = specs[o.pop("spec")]["group"]
+    acc = dict(surfaces=surfaces, hist=hist, ext=ext, stats=stats, shift=shift)
+    distinct = {filter_key(e["filt"]) for e in acc_entries(acc) + specs if e["filt"]}
+    assert len(distinct) <= 8 and sum(len(k) for k in distinct) + (1 if filt else 0) <= 32
+
+    # the plan: ground and top may name accumulator bands too
+    bands = acc_bands(acc)
+    low = [band_name(i, s) for i, s in enumerate(specs) if s["type"] == "Min"] + \
+          [n for n, kind, i, _ in bands if kind == "mean" or kind == "percentile" or (kind == "extremes" and not ext[i]["side"])]
+    high = [band_name(i, s) for i, s in enumerate(specs) if s["type"] == "Max"] + \
+           [n for n, kind, i, _ in bands if kind == "mean" or kind == "percentile" or (kind == "extremes" and ext[i]["side"])]
+    if low and ra.uniform() < 0.6:
+        hag = bool(high) and bool(ra.uniform() < 0.5)
+        plan["ground"] = dict(source_name=str(ra.choice(low)), top_name=str(ra.choice(high)) if hag else None, maxr=int(ra.choice([4, 8])))
+
+    # clouds: maybe a hot accumulator tile, a cloud an entry's filter empties, one the pipeline filter empties; `z` on all
+    field = z_field(g, seed)
+    filtered = [e for e in acc_entries(acc) if e["filt"]]
+    swap = {}
+    free = [i for i, c in enumerate(clouds) if c["shape"] != "hot"]
+    for kind, p in (("hot_acc", 0.35), ("entry_filtered", 0.35), ("pipeline_filtered", 0.2)):
+        if free and ra.uniform() < p:
+            swap[free.pop(int(ra.integers(0, len(free))))] = kind
+    total = 0
+    units = np.zeros((2, W * H))
+    for i, c in enumerate(clouds):
+        rc = np.random.default_rng((95000, seed, 1 + i))
+        kind = swap.get(i)
+        target = filtered[int(rc.integers(0, len(filtered)))]["filt"] if filtered else []
+        if kind == "hot_acc":                                   # more accepted records in the first 128 x 8 cells than one work item takes
+            every = acc_entries(acc)
+            keep = kept_classes(filt, every[int(rc.integers(0, len(every)))]["filt"])
+            keep = keep if len(keep) else kept_classes(filt)
+            n = ACC_ITEM_RECORDS + int(rc.integers(2000, 9000))
+            c = clouds[i] = dict(shape=kind, x=rc.uniform(g["min_x"], g["min_x"] + min(W, ACC_HOT_W) * cs, n),
+                                 y=rc.uniform(g["max_y"] - min(H, ACC_HOT_H) * cs, g["max_y"], n), cls=keep[rc.integers(0, len(keep), n)])
+        elif kind in ("entry_filtered", "pipeline_filtered"):
+            cls4 = np.arange(4, dtype=np.float32)
+            if kind == "entry_filtered":                        # classes the pipeline filter keeps and the entry's filter drops
+                keep = np.setdiff1d(kept_classes(filt), kept_classes(filt, target))
+            else:
+                keep = cls4[~keep_mask(filt, cls4)]
+            if len(keep):
+                n = int(np.exp(rc.uniform(0.0, np.log(20000.0))))    # (many small ones: the direct path of an Auto pipeline)
+                c = clouds[i] = dict(shape=kind, x=rc.uniform(g["min_x"], g["max_x"], n), y=rc.uniform(g["min_y"], g["max_y"], n),
+                                     cls=keep[rc.integers(0, len(keep), n)])
+        if "a" not in c:
+            n = len(c["x"])
+            c.update(a=(rc.integers(-64, 65, n) / 8.0).astype(np.float32), b=rc.integers(0, 64, n).astype(np.float32),
+                     t=rc.integers(0, 6, n).astype(np.float32))
+        _draw_z(rc, g, c, field, shift, specials=4.0 if c["shape"] == "hot_acc" else 1.0)
+        while (units + point_units(g, [c])).max() >= EXACT_UNITS:
+            _thin(c, np.arange(len(c["x"])) % 2 == 0)
+        units += point_units(g, [c])
+        total += len(c["x"])
+    # every counter stays below its wrap point (2^32) and S2 exact (below 2^22 accepted points a cell): the whole case is smaller
+    assert total < 1 << 22
+    return groups, acc
+
+
+def external_labels(g, lab):
+    """An external label grid: zonal_common.plot_labels (plots numbered row-major, a NaN column, the invalid labels in row 0)
+    with everything outside a window made no zone -- NaN, 0, a negative, 2.5 in turn."""
+    import zonal_common as Z
+    out = Z.plot_labels(g["W"], g["H"], lab["plot"])
+    r0, c0, h, w = lab["window"]
+    inside = np.zeros(out.shape, bool)
+    inside[r0:r0 + h, c0:c0 + w] = True
+    none = np.array([np.nan, 0.0, -3.0, 2.5], np.float32)[(np.arange(out.size) % 4).reshape(out.shape)]
+    return np.where(inside, out, none).astype(np.float32)
+
+
+def _acc_tables(seed, case):
+    """Tree bands and zonal tables of the plan, and the ops that read the accumulators and the tables, from a generator of
+    their own (95000, seed, 500): read_acc, tables and set_zones are INSERTED into the sequence ahead of its last finalize."""
+    rt = np.random.default_rng((95000, seed, 500))
+    g, specs, acc, plan, ops = case["grid"], case["specs"], case["acc"], case["plan"], case["ops"]
+    W, H = g["W"], g["H"]
+    bands = acc_bands(acc)
+    sources = [band_name(i, s) for i, s in enumerate(specs)] + [n for n, _, _, _ in bands]
+    if plan["ground"]:
+        sources += ["dtm"] + (["hag"] if ground_names(specs, plan)[1] is not None else [])
+    canopy = [band_name(i, s) for i, s in enumerate(specs) if s["type"] == "Max" and s["ch"] in ("z", "hag")]
+    trees = []
+    for k in range(int(rt.choice([0, 1, 2], p=[0.3, 0.45, 0.25]))):
+        src = str(rt.choice(canopy)) if canopy and rt.uniform() < 0.5 else sources[int(rt.integers(0, len(sources)))]
+        trees.append(dict(source=src, kw=int(rt.integers(0, len(TREE_KW)))))
+    plan["trees"] = trees
+    zonal, labels = [], []
+    folds = [i for i, h in enumerate(acc["hist"]) if h["bins"] <= ZONAL_MAX_BINS]
+    if acc["stats"] or folds:
+        for k in range(int(rt.choice([0, 1, 2], p=[0.3, 0.4, 0.3]))):
+            by_tree = bool(trees) and W * H <= 40000 and bool(rt.uniform() < 0.6)
+            if by_tree:
+                zones, external = f"t{int(rt.integers(0, len(trees)))}_id", False
+            else:
+                zones, external = f"plots{len(labels)}", True
+                h, w = int(rt.integers(8, min(H, 96) + 1)), int(rt.integers(8, min(W, 96) + 1))
+                sets = [dict(plot=int(rt.choice([8, 16, 32])), window=(int(rt.integers(0, H - h + 1)), int(rt.integers(0, W - w + 1)), h, w))
+                        for _ in range(1 + int(rt.uniform() < 0.4))]          # (a second set replaces the first)
+                labels.append(sets)
+            st = [int(rt.integers(0, len(acc["stats"])))] if acc["stats"] and rt.uniform() < 0.8 else []
+            hs = [int(rt.choice(folds))] if folds and (rt.uniform() < 0.7 or not st) else []
+            own = bool(rt.uniform() < 0.5)
+            qs = [] if own else [HIST_QS[i] for i in rt.permutation(len(HIST_QS))[:int(rt.integers(0, 4))]]
+            zonal.append(dict(zones=zones, external=external, stats=st, hists=hs, own=own, qs=qs,
+                              max_zones=int(rt.choice([1 << 22, 1 << 22, 1 << 22, 3, 40]))))
+    plan["zonal"] = zonal
+    acc["labels"] = labels
+    new = [dict(op="read_acc") for _ in range(int(rt.integers(1, 3)))]
+    if trees or zonal:
+        new += [dict(op="tables") for _ in range(int(rt.integers(1, 4)))]
+    for e, sets in enumerate(labels):
+        new += [dict(op="set_zones", entry=e, labels=k) for k in range(len(sets))]
+    new = [new[i] for i in rt.permutation(len(new))]
+    for e, sets in enumerate(labels):                            # (the set_zones of one grid keep their order)
+        for k, o in enumerate(o for o in new if o["op"] == "set_zones" and o["entry"] == e):
+            o["labels"] = k
+    at = sorted(int(rt.integers(0, len(ops))) for _ in new)
+    for k, (i, o) in enumerate(zip(at, new)):
+        ops.insert(i + k, o)
+    for i in range(1, len(ops)):                                 # a tables right behind an async ingest waits for nothing itself
+        if ops[i]["op"] in ("read_acc", "tables") and ops[i - 1]["op"] == "ingest" and ops[i - 1]["how"].startswith("async"):
+            ops[i - 1]["sync"] = ops[i - 1]["sync"] and bool(rt.uniform() < 0.5)
+
+
 def build(seed):
     rng = np.random.default_rng(91000 + seed)
     # How the sequence opens.  "union": what a row-block shard does -- one sparse cloud, the other ranks' flags merged in, finalize.
@@ -626,7 +974,13 @@ def build(seed):
     # (units of 1/8 on an `a` plane, of 1 on a `b` plane, like the clouds'; a Count never exceeds the points of a cell)
     patched = PATCH_UNITS * sum(o["op"] == "planes_write" for o in ops)
     assert units_a.max() + patched < 1 << 24 and units_b.max() + patched < 1 << 24
-    line = seed >= LINE_SEED_BASE
+    line = LINE_SEED_BASE <= seed < ACC_SEED_BASE
+    acc = None
+    if seed >= ACC_SEED_BASE:
+        # an accumulator case: in core, no line pass; everything else of it drawn last and from generators of its own
+        flavour = dict(flavour, ooc=False)
+        groups, acc = _acc_pass(seed, g, specs, ops, clouds, filt, plan)
+        assert point_units(g, clouds).max() + PATCH_UNITS * sum(o["op"] == "planes_write" for o in ops) < 1 << 24
     if line:
         # (it replaces clouds, thins others and adds plane writes: the Point condition again, on the clouds as they are now --
         # _line_pass holds the replaced clouds to it as it holds them to the Line condition)
@@ -641,15 +995,19 @@ def build(seed):
             k += 1
 
     case = dict(seed=seed, grid=g, specs=specs, groups=groups, filt=filt, plan=plan, flavour=flavour, fwfi=fwfi, path=path,
-                ops=ops, clouds=clouds, big=big, wide=wide, line=line)
+                ops=ops, clouds=clouds, big=big, wide=wide, line=line, acc=acc)
     first = clouds[next(o for o in ops if o["op"] == "ingest")["cloud"]]
     offered = _first_ingest_is_offered(case)
     case["marked"] = offered and first["shape"] != "hot"
     # ... or is offered them and splits a bin, so that the device's done word says no: the blocking finalize behind it reads 0
     case["split_first"] = offered and opening == "hot" and hot_records(case, first) > SPLIT_RECORDS
+    if acc is not None:                                          # (the marks are about the Point groups' stored bands: the last scatter of an
+        case["marked"] = case["split_first"] = False             # accumulator case's ingest is an accumulator's, and a filtered group is not offered)
     # the terrain bands of every plan, last and from generators of their own: no draw above moves, a seed stays the case it was
     # (tests/golden/sequence_fuzz_cases.json).  k = 0: the opening plan; k = index + 1: the plan of the checkpoint at ops[index]
-    plan["terrain"] = _draw_terrain(np.random.default_rng((93000, seed, 0)), specs, plan)
+    plan["terrain"] = _draw_terrain(np.random.default_rng((93000, seed, 0)), specs, plan, acc_terrain_sources(acc) if acc else ())
+    if acc is not None:
+        _acc_tables(seed, case)
     for i, o in enumerate(ops):
         if o["op"] == "checkpoint" and o["plan"] is not None:
             o["plan"]["terrain"] = _draw_terrain(np.random.default_rng((93000, seed, i + 1)), specs, o["plan"])
@@ -667,6 +1025,8 @@ def case_digest(case):
     def plain(v):
         if isinstance(v, dict):
             return {k: plain(w) for k, w in v.items() if k != "terrain"}
+        if type(v) is float and not np.isfinite(v):              # (an accumulator case: max_gap = +Inf)
+            return repr(v)
         if isinstance(v, (list, tuple)):
             return [plain(w) for w in v]
         assert v is None or type(v) in (bool, int, float, str), type(v)
@@ -674,6 +1034,9 @@ def case_digest(case):
 
     h = hashlib.sha256()
     head = {k: plain(case[k]) for k in ("grid", "specs", "filt", "flavour", "fwfi", "path", "plan", "ops", "marked", "split_first")}
+    if case.get("acc") is not None:                              # an accumulator case: the lists, and the plan's terrain after all
+        head["acc"] = plain(case["acc"])                          # (its sources are part of what the case is for)
+        head["terrain"] = plain(case["plan"]["terrain"])
     h.update(json.dumps(head, sort_keys=True, allow_nan=False).encode())
     for c in case["clouds"]:
         h.update(c["shape"].encode())
@@ -746,6 +1109,8 @@ def segments(case):
 def situations(case):
     """Which of the situations the fuzz is for occur in a case (tests/test_sequence_fuzz_host.py counts them over the seeds).
     Only what runs on the HIP engine counts: pointer ops in in-core segments, a hot spot that is binned."""
+    if case.get("acc") is not None:                              # (an accumulator case has situations of its own)
+        return acc_situations(case)
     found = set()
     types = [s["type"] for s in case["specs"]]
     real = lambda o: o["op"] == "ingest" and len(case["clouds"][o["cloud"]]["x"]) > 0
@@ -947,6 +1312,145 @@ LINE_SEEDS = [
     2385,   # masks 2 and 3: a hot Line tile, the list used, a write into a weight plane
 ]
 
+ACC_SITUATIONS = ("two entries sharing a class", "an entry whose filter empties a cloud that the pipeline filter keeps",
+                  "direct and binned scatters of one accumulator in one sequence", "a split bin in an accumulator tile",
+                  "ingest_file in chunks with a surface channel", "an async ingest followed by read_acc without a synchronize in between",
+                  "a DTM from an extremes band with fill > 0", "terrain of a Mean band", "trees of a Max-of-hag band",
+                  "trees of a filled band", "zonal by tree_id with a Device result", "zonal by tree_id with a Host result",
+                  "zonal by an external grid set after the finalize", "tables after an ingest (refused)",
+                  "tables after a plane read or write", "tables after merge_touched",
+                  "a second finalize with nothing new followed by tables", "a refused save_state between two ingests",
+                  "max_zones exceeded", "no accumulator band sourced anywhere, trees and zonal present",
+                  "a cloud that the pipeline filter empties", "tables after a cloud that the pipeline filter empties (still valid)")
+
+
+def acc_situations(case):
+    """The ACC_SITUATIONS that occur in an accumulator case, from the case alone.  "Binned" is the engine's own rule for a
+    cloud of n points (forced, or cells <= 16 n); a split bin is counted only where more than ACC_ITEM_RECORDS accepted records
+    lie in the first 128 x 8 cells, which every accumulator's first tile contains."""
+    found = set()
+    g, acc, plan, ops, specs = case["grid"], case["acc"], case["plan"], case["ops"], case["specs"]
+    cells = g["W"] * g["H"]
+    entries = acc_entries(acc)
+    keys = [filter_key(e["filt"]) for e in entries if e["filt"]]
+    if len(set(keys)) < len(keys) or set(keys) & {filter_key(s["filt"]) for s in specs if s["filt"]}:
+        found.add("two entries sharing a class")
+    kinds = {n: kind for n, kind, _, _ in acc_bands(acc)}
+    by_name = {band_name(i, s): s for i, s in enumerate(specs)}
+    filled = lambda n: n in ("dtm", "hag") or (n in kinds and acc_filled(kinds[n])) or (n in by_name and by_name[n]["type"] in FILL_TYPES)
+    trees, zonal = plan["trees"], plan["zonal"]
+    sourced = [t["source"] for t in plan["terrain"]] + [t["source"] for t in trees] + (list(ground_names(specs, plan)) if plan["ground"] else [])
+    if plan["ground"] and plan["fill"] > 0 and kinds.get(ground_names(specs, plan)[0]) == "extremes":
+        found.add("a DTM from an extremes band with fill > 0")
+    if any(kinds.get(t["source"]) == "mean" for t in plan["terrain"]):
+        found.add("terrain of a Mean band")
+    if any(t["source"] in by_name and by_name[t["source"]]["type"] == "Max" and by_name[t["source"]]["ch"] == "hag" for t in trees):
+        found.add("trees of a Max-of-hag band")
+    if plan["fill"] > 0 and any(filled(t["source"]) for t in trees):
+        found.add("trees of a filled band")
+    if any(not z["external"] for z in zonal):
+        found.add(f"zonal by tree_id with a {plan['loc']} result")
+    if trees and zonal and not any(n in kinds for n in sourced):
+        found.add("no accumulator band sourced anywhere, trees and zonal present")
+    externals = [z for z in zonal if z["external"]]
+    for z, sets in zip(externals, acc["labels"]):
+        lab = external_labels(g, sets[0])
+        with np.errstate(all="ignore"):
+            valid = np.isfinite(lab) & (lab >= 1) & (lab == np.floor(lab))
+        if valid.any() and lab[valid].max() > z["max_zones"]:
+            found.add("max_zones exceeded")
+    finalized = fresh = False
+    since = set()                                                # what happened since the last finalize
+    paths = set()
+    n_ingest = sum(o["op"] == "ingest" for o in ops)
+    seen_ingests = 0
+    for i, o in enumerate(ops):
+        nxt = ops[i + 1] if i + 1 < len(ops) else None
+        if o["op"] == "ingest":
+            seen_ingests += 1
+            c = case["clouds"][o["cloud"]]
+            n = len(c["x"])
+            keep = keep_mask(case["filt"], c["cls"])
+            if not keep.any():                                   # (in.kept == 0: the ingest returns before any accumulator runs)
+                if n:
+                    found.add("a cloud that the pipeline filter empties")
+                    since.add("filtered cloud")
+                continue
+            fresh = False
+            since = set()
+            chunk = max(1, int(n * o["chunk_frac"])) if o["how"] == "file" else n
+            if o["how"] == "file" and chunk < n and acc["surfaces"]:
+                found.add("ingest_file in chunks with a surface channel")
+            if o["how"].startswith("async") and not o["sync"] and nxt is not None and nxt["op"] == "read_acc":
+                found.add("an async ingest followed by read_acc without a synchronize in between")
+            binned = case["path"] == 2 or (case["path"] == 0 and chunk * 16 >= cells)
+            paths.add("binned" if binned else "direct")
+            ch = surface_channels(acc, c)
+            cell = cells_of(g, c["x"], c["y"])
+            first = (cell >= 0) & (cell // g["W"] < ACC_HOT_H) & (cell % g["W"] < ACC_HOT_W)
+            for e in entries:
+                mine = keep & conj_mask(ch, e["filt"], n)
+                if e["filt"] and not mine.any():
+                    found.add("an entry whose filter empties a cloud that the pipeline filter keeps")
+                if binned and o["how"] != "file" and (mine & first & ~np.isnan(ch[e["ch"]])).sum() > ACC_ITEM_RECORDS:
+                    found.add("a split bin in an accumulator tile")
+        elif o["op"] == "finalize":
+            if fresh and (trees or zonal):                       # (the runner reads every table behind every finalize)
+                found.add("a second finalize with nothing new followed by tables")
+            finalized = fresh = True
+            since = set()
+        elif o["op"] in ("planes_read", "planes_write", "merge"):
+            since.add(o["op"])
+        elif o["op"] == "set_zones" and finalized and fresh:
+            since.add("set_zones")
+        elif o["op"] == "tables":
+            if zonal and finalized and not fresh:
+                found.add("tables after an ingest (refused)")
+            if finalized and fresh and since & {"planes_read", "planes_write"}:
+                found.add("tables after a plane read or write")
+            if finalized and fresh and "merge" in since:
+                found.add("tables after merge_touched")
+            if zonal and finalized and fresh and "filtered cloud" in since:
+                found.add("tables after a cloud that the pipeline filter empties (still valid)")
+            if finalized and fresh and "set_zones" in since:
+                found.add("zonal by an external grid set after the finalize")
+        elif o["op"] == "checkpoint" and 0 < seen_ingests < n_ingest:
+            found.add("a refused save_state between two ingests")
+    if paths == {"direct", "binned"}:
+        found.add("direct and binned scatters of one accumulator in one sequence")
+    return found
+
+
+# The accumulator cases of the suite: a greedy cover of 10000..10399 in which every entry above occurs four times, cheaper cases
+# first (tests/test_sequence_fuzz_host.py asks for three).  A failing seed of a soak joins it.
+ACC_SEEDS = [
+    10003,  # Auto: direct and binned; trees of a Max-of-hag band; read_acc behind an async ingest that nobody waited for
+    10054,  # tables after a plane write and after merge_touched; a second finalize with nothing new
+    10055,  # a split accumulator bin; zonal by tree_id, Host result; no accumulator band sourced anywhere
+    10059,  # an external grid set after the finalize, max_zones exceeded; tables after a plane write and a merge
+    10067,  # ingest_file in chunks with a surface channel; trees of Max-of-hag; zonal by tree_id, Device result
+    10078,  # chunks with a surface channel; terrain of a Mean band
+    10111,  # chunks with a surface channel; zonal by tree_id, Device result; tables after a plane read
+    10113,  # Auto: direct and binned; zonal by tree_id, Device result
+    10133,  # an external grid set after the finalize; trees of Max-of-hag; tables after a plane write and a merge
+    10190,  # a split bin, direct and binned, read_acc behind an unwaited async ingest, max_zones exceeded
+    10204,  # a split bin; tables refused after an ingest; terrain of a Mean band; zones by tree_id and external
+    10207,  # a DTM from an extremes band, filled
+    10208,  # terrain of a Mean band; trees of Max-of-hag; zonal by tree_id, Host result
+    10216,  # a DTM from an extremes band, filled
+    10259,  # a DTM from an extremes band, filled
+    10264,  # a DTM from an extremes band, filled; zonal by tree_id, Device result, refused after an ingest
+    10288,  # Auto: direct and binned; chunks with a surface channel; max_zones exceeded
+    10312,  # a split bin; zonal by tree_id, Host result
+    10339,  # an external grid set after the finalize; tables after merge_touched; terrain of a Mean band
+    10431,  # a cloud that the pipeline filter empties (in.kept == 0: no accumulator runs)
+    11192,  # tables right behind such a cloud: still valid (the host engine used to refuse them); a split bin
+    11258,  # a cloud that the pipeline filter empties; terrain of a Mean band; max_zones exceeded
+    11790,  # tables behind a cloud that the pipeline filter empties, and refused behind one that it keeps
+    11833,  # tables behind a cloud that the pipeline filter empties and after merge_touched; zonal by tree_id, Host result
+    11581,  # soak: two filters that differ only in a field their op does not use are ONE class (the model's filter_key kept them apart)
+]
+
 SITUATIONS = ("finalize right after the only ingest, finalize_with_first_ingest on", "ingest after a finalize",
               "state_planes() between an ingest and its finalize", "plane write", "writable flag pointer before the first ingest",
               "merge_touched after a finalize", "checkpoint after a single ingest", "resume under a different finalize plan",
@@ -975,6 +1479,19 @@ class Model:
         self.touched = np.zeros((self.ty, self.tx), bool)
         self.survivors = 0
         self.og = oracle_grid(g) if case["line"] else None
+        self.acc = case.get("acc")
+        if self.acc:                                             # the accumulator states, integer arrays as the accessors hand them out
+            import extremes_common as E
+            a = self.acc
+            self.cubes = [np.zeros((h["bins"], self.H, self.W), np.uint32) for h in a["hist"]]
+            self.keys = [np.full((e["k"], self.H, self.W), E.EMPTY, np.uint32) for e in a["ext"]]
+            self.stats = [(np.zeros((self.H, self.W), np.uint32), np.zeros((self.H, self.W), np.int64), np.zeros((self.H, self.W), np.uint64))
+                          for _ in a["stats"]]
+            self.version = 0                                     # counts the ingests that changed an accumulator's input
+            self.fresh = False                                   # zonal tables: a finalize with no ingest since
+            self.finalized = None                                # (names, bands, tree tables) of the last finalize
+            self.zones = {}                                      # external label grids that were set
+            self._cache = {}
         self.planes = []
         for gr in case["groups"]:
             if gr["select"]:
@@ -995,7 +1512,12 @@ class Model:
         ok = keep & (cell >= 0)
         cell_ok = cell[ok]
         rows, cols = cell_ok // self.W, cell_ok % self.W
+        # (section 18's flag rule: the pipeline filter's survivors alone set the touched flags)
         self.touched[rows // self.g["th"], cols // self.g["tw"]] = True
+        if self.acc:
+            if keep.any():                                       # (a cloud the pipeline filter empties changes nothing: pipeline.h, Pipeline::zonal)
+                self._ingest_acc(c, keep)
+            return
         for gr, pl in zip(self.case["groups"], self.planes):
             v = c[gr["ch"]]
             if gr["select"]:
@@ -1015,6 +1537,58 @@ class Model:
             pl[1][:] = (pl[1].astype(np.float64) + np.bincount(cell_ok, minlength=self.W * self.H)).astype(np.float32)
             np.maximum.at(pl[2], cell_ok, v[ok])
             np.minimum.at(pl[3], cell_ok, v[ok])
+
+    def _ingest_acc(self, c, keep):
+        """An accumulator case's ingest: the surface channels first, then every group under its own filter AND the pipeline's
+        (Max and Min skip a NaN value: fmaxf / fminf), then the accumulators by their *_common models from the same routing."""
+        import cell_stats_common as CS
+        import extremes_common as E
+        import histogram_common as HC
+        import most_recent_common as MR
+        a, g, n = self.acc, self.g, len(c["x"])
+        self.version += 1
+        self.fresh = False
+        ch = surface_channels(a, c)
+        cell = cells_of(g, c["x"], c["y"])
+        for gr, pl in zip(self.case["groups"], self.planes):
+            mine = keep & conj_mask(ch, gr["filt"], n)
+            v = ch[gr["ch"]]
+            if gr["select"]:
+                MR.fold_words(cell, v, c["t"], self.W * self.H, keep=mine, words=pl)
+                continue
+            ok = mine & (cell >= 0)
+            pl[0][:] = (pl[0].astype(np.float64) + np.bincount(cell[ok], v[ok].astype(np.float64), self.W * self.H)).astype(np.float32) \
+                if gr["ch"] in ("a", "b") else pl[0]
+            pl[1][:] = (pl[1].astype(np.float64) + np.bincount(cell[ok], minlength=self.W * self.H)).astype(np.float32)
+            np.fmax.at(pl[2], cell[ok], v[ok])
+            np.fmin.at(pl[3], cell[ok], v[ok])
+        for i, h in enumerate(a["hist"]):
+            with np.errstate(over="ignore"):
+                self.cubes[i] += HC.cube(g, c["x"], c["y"], ch[h["ch"]], h["lo"], h["hi"], h["bins"], keep & conj_mask(ch, h["filt"], n))
+        for i, e in enumerate(a["ext"]):
+            new = E.planes(g, c["x"], c["y"], ch[e["ch"]], e["k"], e["side"], keep & conj_mask(ch, e["filt"], n))
+            both = np.sort(np.concatenate([self.keys[i], new]), axis=0)       # the k smallest DISTINCT keys of the union
+            both[1:][both[1:] == both[:-1]] = E.EMPTY
+            self.keys[i] = np.sort(both, axis=0)[:e["k"]]
+        for i, s in enumerate(a["stats"]):
+            self.stats[i] = CS.planes(g, c["x"], c["y"], ch[s["ch"]], s["origin"], s["res"], keep & conj_mask(ch, s["filt"], n), into=self.stats[i])
+
+    def acc_raw_bands(self):
+        """The accumulator bands as finalize makes them, in acc_bands' order (cached per state: the cell-stats model walks every
+        non-empty cell with Python ints)."""
+        import cell_stats_common as CS
+        import extremes_common as E
+        import histogram_common as HC
+        if self._cache.get("bands_version") != self.version:
+            a, out = self.acc, []
+            for h, cube in zip(a["hist"], self.cubes):
+                out += HC.percentiles(cube, h["lo"], h["hi"], h["bins"], h["qs"])
+            out += [E.band(keys, e["side"], e["gap"]) for e, keys in zip(a["ext"], self.keys)]
+            for s, st in zip(a["stats"], self.stats):
+                made = CS.bands(*st, s["origin"], s["res"], s["ddof"])
+                out += [made[p] for p in s["products"]]
+            self._cache["bands_version"], self._cache["bands"] = self.version, out
+        return [b.copy() for b in self._cache["bands"]]
 
     def patch(self, o):
         r0, c0, h, w = o["rect"]
@@ -1094,21 +1668,29 @@ class Model:
         import pcr
         raw = self.raw_bands()
         names = [band_name(i, s) for i, s in enumerate(self.case["specs"])]
-        out = list(raw)
         fills = [i for i, s in enumerate(self.case["specs"]) if s["type"] in FILL_TYPES]
+        if self.acc:
+            # the documented order: reductions, percentiles, extremes, cell stats -- then dtm, hag, terrain, tree bands; percentile,
+            # extremes and Mean bands are filled, Variance and StdDev bands never
+            for k, (name, kind, _, _) in enumerate(acc_bands(self.acc)):
+                fills += [len(names)] if acc_filled(kind) else []
+                names.append(name)
+            raw = raw + self.acc_raw_bands()
+        out = list(raw)
         if plan["fill"] > 0 and fills:
             filled = G.grid_bands(pcr.fill_nodata(G.make_grid(raw), plan["fill"], fills))
             out = [filled[i] if i in fills else raw[i] for i in range(len(raw))]
         if plan["ground"]:
             spec = pcr.GroundFilterSpec()
             spec.max_radius_cells = plan["ground"]["maxr"]
-            dtm = G.grid_bands(pcr.ground_filter(G.make_grid([raw[plan["ground"]["source"]]]), 0, spec, self.g["cs"]))[0]
+            source, top = ground_names(self.case["specs"], plan)
+            dtm = G.grid_bands(pcr.ground_filter(G.make_grid([raw[names.index(source)]]), 0, spec, self.g["cs"]))[0]
             if plan["fill"] > 0:
                 dtm = G.grid_bands(pcr.fill_nodata(G.make_grid([dtm]), plan["fill"]))[0]
             out.append(dtm)
             names.append("dtm")
-            if plan["ground"]["top"] is not None:
-                out.append(G.difference(out[plan["ground"]["top"]], dtm))
+            if top is not None:
+                out.append(G.difference(out[names.index(top)], dtm))
                 names.append("hag")
         # the terrain bands, in list order behind dtm / hag: each from its source band as it leaves (filled), by the NumPy
         # restatement of the contract (no engine code but the light constants, which are the contract), never filled themselves
@@ -1120,7 +1702,65 @@ class Model:
                                      edges=t["edges"], azimuth=t["azimuth"], altitude=t["altitude"], cell_size_x=self.g["cs"],
                                      cell_size_y=-self.g["cs"])[0])
                 names.append(terrain_band_name(t))
+        # the tree bands, two per entry behind the terrain bands: from the source as it leaves, by the host twin (which
+        # tests/test_trees.py holds to the brute-force model); the table's centres by the grid's geometry
+        tables = []
+        for i, t in enumerate(plan.get("trees") or []):
+            import trees_common as TR
+            got = TR.host(out[names.index(t["source"])], TR.spec(**TREE_KW[t["kw"]]), self.g["cs"], -self.g["cs"])
+            tab = got["table"]
+            tab["x"] = self.g["min_x"] + (tab["col"].astype(np.float64) + 0.5) * self.g["cs"]
+            tab["y"] = self.g["max_y"] + (tab["row"].astype(np.float64) + 0.5) * -self.g["cs"]
+            out += [got["id"], got["height"]]
+            names += [f"t{i}_id", f"t{i}_h"]
+            tables.append(tab)
+        if self.acc:
+            self.fresh, self.finalized = True, (names, out, tables)
         return names, out
+
+    def acc_states(self):
+        """What histogram(i), extremes(i) and cell_stats(i) answer: the cubes, the decoded key planes, (N, S1, S2)."""
+        import extremes_common as E
+        return (self.cubes, [E.value_of(k, e["side"]) for k, e in zip(self.keys, self.acc["ext"])], self.stats)
+
+    def trees_table(self, i):
+        """Pipeline::trees: the table of the last finalize, whatever came since; before the first: the refusal."""
+        return "no trees entry" if self.finalized is None else self.finalized[2][i]
+
+    def zonal_table(self, plan, i):
+        """Pipeline::zonal of entry i: (table, [counts per chosen histogram]) by zonal_common's Python-int model on the labelled
+        cells' bounding box (a cell without a zone adds nothing to any row), or the message of the documented refusal."""
+        import zonal_common as Z
+        z, a = plan["zonal"][i], self.acc
+        if self.finalized is None or not self.fresh:
+            return f"no zonal entry {i} \\(of a finalize with no ingest since\\)"
+        if z["external"]:
+            if z["zones"] not in self.zones:
+                return f"the label grid '{z['zones']}' was not set"
+            labels = self.zones[z["zones"]]
+        else:
+            labels = self.finalized[1][self.finalized[0].index(z["zones"])]
+        key = (self.version, bits_key(labels))                   # (the states and the labels: all the table is made of)
+        if self._cache.get("zonal_key", {}).get(i) != key:
+            with np.errstate(all="ignore"):
+                valid = np.isfinite(labels) & (labels >= 1) & (labels <= Z.MAX_ZONE) & (labels == np.floor(labels))
+            if valid.any():
+                rr, cc = np.nonzero(valid)
+                box = (slice(rr.min(), rr.max() + 1), slice(cc.min(), cc.max() + 1))
+            else:
+                box = (slice(0, 1), slice(0, 1))
+            zmax = Z.zone_max(labels[box])
+            if zmax > z["max_zones"]:
+                ans = f"is above max_zones = {z['max_zones']}"
+            else:
+                stats = [(a["stats"][k]["ch"], tuple(p[box] for p in self.stats[k]), a["stats"][k]["origin"], a["stats"][k]["res"], a["stats"][k]["ddof"])
+                         for k in z["stats"]]
+                hists = [(a["hist"][k]["ch"], self.cubes[k][(slice(None),) + box], *Z.hist_consts(a["hist"][k]["lo"], a["hist"][k]["hi"], a["hist"][k]["bins"]),
+                          a["hist"][k]["qs"] if z["own"] else z["qs"]) for k in z["hists"]]
+                ans = Z.table(labels[box], stats=stats, hists=hists)
+            self._cache.setdefault("zonal_key", {})[i] = key
+            self._cache.setdefault("zonal", {})[i] = ans
+        return self._cache["zonal"][i]
 
     def write_checkpoint(self, dirname):
         """The model's state as `.pcrt` files in the pipelines' layout: one file per touched tile and reduction."""
@@ -1139,6 +1779,11 @@ class Model:
 
 def band_name(i, s):
     return f"r{i}_{s['type']}_{s['ch']}"
+
+
+def bits_key(a):
+    import hashlib
+    return hashlib.sha1(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def overview_level_count(W, H):
@@ -1175,6 +1820,8 @@ def make_config(case, plan, flavour, exec_mode, engine, tmp_path, state_dir=None
             gl.type, gl.direction_channel, gl.half_length_channel = pcr.GlyphType.Line, "dir", s["glyph"]["hl_ch"]
             gl.default_half_length, gl.max_radius_cells = s["glyph"]["hl"], s["glyph"]["maxr"]
             r.glyph = gl
+        if s.get("filt"):
+            r.filter = filter_spec(s["filt"])
         reds.append(r)
     cfg.reductions = reds
     if case["filt"]:
@@ -1188,10 +1835,12 @@ def make_config(case, plan, flavour, exec_mode, engine, tmp_path, state_dir=None
         cfg.filter = f
     cfg.fill_nodata_radius = plan["fill"]
     if plan["ground"]:
-        cfg.ground.source_band = band_name(plan["ground"]["source"], case["specs"][plan["ground"]["source"]])
-        if plan["ground"]["top"] is not None:
-            cfg.ground.top_band = band_name(plan["ground"]["top"], case["specs"][plan["ground"]["top"]])
+        cfg.ground.source_band, top = ground_names(case["specs"], plan)
+        if top is not None:
+            cfg.ground.top_band = top
         cfg.ground.max_radius_cells = plan["ground"]["maxr"]
+    if case.get("acc"):
+        acc_config(pcr, cfg, case["acc"], plan)
     if plan.get("terrain"):
         import terrain_common as T
         cfg.terrain = [T.band_cfg(t["source"], T.PRODUCTS[TERRAIN_PRODUCTS.index(t["product"])], t["name"], z_factor=t["z_factor"],
@@ -1211,6 +1860,57 @@ def make_config(case, plan, flavour, exec_mode, engine, tmp_path, state_dir=None
     if state_dir is not None:
         cfg.state_dir, cfg.resume = state_dir, True
     return cfg
+
+
+def filter_spec(f):
+    import pcr
+    out = pcr.FilterSpec()
+    preds = []
+    for q in f:
+        pr = pcr.FilterPredicate()
+        pr.channel_name, pr.op = q["ch"], getattr(pcr.CompareOp, q["op"])
+        if q["op"] in ("InSet", "NotInSet"):
+            pr.value_set = q["set"]
+        else:
+            pr.value = q["value"]
+        preds.append(pr)
+    out.predicates = preds
+    return out
+
+
+def acc_config(pcr, cfg, acc, plan):
+    """The lists of an accumulator case, every band named as acc_bands names it."""
+    import trees_common as TR
+    cfg.surface_channels = [pcr.SurfaceChannelConfig(sc["name"], sc["value"], pcr.SampleMode.Bilinear if sc["mode"] else pcr.SampleMode.Nearest)
+                            for sc in acc["surfaces"]]
+    names = [n for n, _, _, _ in acc_bands(acc)]
+    at, hs, xs, cs = 0, [], [], []
+    for h in acc["hist"]:
+        e = pcr.HistogramConfig(h["ch"], h["lo"], h["hi"], h["bins"], [float(q) for q in h["qs"]])
+        e.band_names = names[at:at + len(h["qs"])]
+        at += len(h["qs"])
+        if h["filt"]:
+            e.filter = filter_spec(h["filt"])
+        hs.append(e)
+    for x in acc["ext"]:
+        e = pcr.ExtremesConfig(x["ch"], pcr.ExtremeSide.Highest if x["side"] else pcr.ExtremeSide.Lowest, x["k"], x["gap"])
+        e.band_name = names[at]
+        at += 1
+        if x["filt"]:
+            e.filter = filter_spec(x["filt"])
+        xs.append(e)
+    kinds = (pcr.CellStat.Mean, pcr.CellStat.Variance, pcr.CellStat.StdDev)
+    for c in acc["stats"]:
+        e = pcr.CellStatsConfig(c["ch"], origin=c["origin"], resolution=c["res"], products=[kinds[k] for k in c["products"]], ddof=c["ddof"])
+        e.band_names = names[at:at + len(c["products"])]
+        at += len(c["products"])
+        if c["filt"]:
+            e.filter = filter_spec(c["filt"])
+        cs.append(e)
+    cfg.histograms, cfg.extremes, cfg.cell_stats = hs, xs, cs
+    cfg.trees = [TR.band_cfg(t["source"], f"t{i}_id", f"t{i}_h", **TREE_KW[t["kw"]]) for i, t in enumerate(plan["trees"])]
+    cfg.zonal = [pcr.ZonalConfig(z["zones"], external=z["external"], cell_stats=z["stats"], histograms=z["hists"],
+                                 percentiles=None if z["own"] else [float(q) for q in z["qs"]], max_zones=z["max_zones"]) for z in plan["zonal"]]
 
 
 def _cloud(c, where):
@@ -1259,7 +1959,56 @@ def check_sequence(seed, exec_mode, engine, tmp_path):
         assert p is not None, f"seed {seed}: create: {pcr.pipeline_create_error()}"
         assert p.engine() == engine, f"seed {seed}: engine {p.engine()}"
         assert p.out_of_core() == (hip and flavour["ooc"]), f"seed {seed}: out_of_core() is {p.out_of_core()}"
+        for sc in (case["acc"] or {}).get("surfaces", ()):       # every surface before the first ingest
+            import sample_grid_common as SG
+            p.set_surface(sc["name"], SG.pcr_grid(pcr, surface_of(sc)))
         return p
+
+    def refusal(call, message, what):
+        try:
+            call()
+        except RuntimeError as e:
+            import re
+            assert re.search(message, str(e)), f"{what}: refused with '{e}', not with '{message}'"
+            return
+        raise AssertionError(f"{what}: answered, the model expects the refusal '{message}'")
+
+    def check_acc(at):
+        """histogram(i), extremes(i), cell_stats(i) against the model's states, bit for bit."""
+        import cell_stats_common as CS
+        import extremes_common as E
+        import histogram_common as HC
+        cubes, values, stats = model.acc_states()
+        for i, want in enumerate(cubes):
+            HC.cubes_equal(p.histogram(i), want, f"{at}: histogram({i})")
+        for i, want in enumerate(values):
+            HC.bits_equal(p.extremes(i), want, f"{at}: extremes({i})")
+        for i, want in enumerate(stats):
+            CS.planes_equal(p.cell_stats(i), want, f"{at}: cell_stats({i})")
+
+    def check_tables(at):
+        """trees(i), zonal(i) and zonal_histogram(i, h) against the model: a table, or the documented refusal."""
+        import trees_common as TR
+        import zonal_common as Z
+        for i in range(len(plan["trees"])):
+            want = model.trees_table(i)
+            if isinstance(want, str):
+                refusal(lambda: p.trees(i), want, f"{at}: trees({i})")
+                continue
+            got = {k: np.asarray(v) for k, v in p.trees(i).items()}
+            for k in TR.COLUMNS:
+                a, b = got[k], np.asarray(want[k])
+                assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{at}: trees({i}).{k} differs"
+        for i, z in enumerate(plan["zonal"]):
+            want = model.zonal_table(plan, i)
+            if isinstance(want, str):
+                refusal(lambda: p.zonal(i), want, f"{at}: zonal({i})")
+                refusal(lambda: p.zonal_histogram(i, 0), want, f"{at}: zonal_histogram({i}, 0)")
+                continue
+            Z.same_table(p.zonal(i), want[0], f"{at}: zonal({i})")
+            for h, counts in enumerate(want[1]):
+                Z.bits_equal(p.zonal_histogram(i, h), counts, f"{at}: zonal_histogram({i}, {h})")
+            refusal(lambda: p.zonal_histogram(i, len(want[1])), f"no histogram {len(want[1])} in the entry", f"{at}: zonal_histogram({i}, {len(want[1])})")
 
     def d2h(ptr, shape, dtype=np.float32):
         out = np.empty(shape, dtype)
@@ -1349,6 +2098,27 @@ def check_sequence(seed, exec_mode, engine, tmp_path):
                         M.bits_equal(pcr.read_geotiff_band(tif, b, lv + 1), lw, f"{at}, band {b} ({name}), level {lv + 1} of the GeoTIFF")
             assert p.stats().points_processed == model.survivors, \
                 f"{at}: points_processed {p.stats().points_processed} != {model.survivors} survivors of the filter"
+            if case["acc"]:
+                check_acc(at)
+                check_tables(at)
+        elif o["op"] == "read_acc":
+            check_acc(at)
+        elif o["op"] == "tables":
+            check_tables(at)
+        elif o["op"] == "set_zones":                             # an external label grid; a second set replaces the copy
+            import overviews_common as OV
+            z = [q for q in plan["zonal"] if q["external"]][o["entry"]]
+            labels = external_labels(case["grid"], case["acc"]["labels"][o["entry"]][o["labels"]])
+            p.set_zones(z["zones"], OV.make_grid([np.zeros_like(labels), labels]), 1)
+            model.zones[z["zones"]] = labels
+        elif case["acc"] and o["op"] in ("reload", "checkpoint"):
+            # checkpoints do not carry the accumulators: both calls are refused with the message of the first non-empty list,
+            # and neither the state nor the next finalize knows of the call (the model does not move)
+            a = case["acc"]
+            what = "histograms' cubes" if a["hist"] else "extremes' key planes" if a["ext"] else "cell stats' planes"
+            refusal(lambda: (p.load_state if o["op"] == "reload" else p.save_state)(str(tmp_path / f"ck{k}")),
+                    f"checkpoints do not carry the {what} yet", at)
+            assert not os.path.exists(str(tmp_path / f"ck{k}")), f"{at}: the refused call left files"
         elif o["op"] in ("planes_read", "planes_write"):
             if not in_core_hip:
                 continue                                         # (no plane pointers out of core or on the host engine)

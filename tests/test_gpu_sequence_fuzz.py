@@ -13,7 +13,13 @@ a Point WeightedAverage: exact sums again (a visit has weight 1), so the Line ti
 the listed and the direct path and the plane-state rules for glyph groups are held to the oracle's footprint bit for bit.
 Gaussian groups are not drawn (expf weights: no exact model).  The generator's _line_pass keeps every Line sum exact.
 last_scatter() reports the last scatter of an ingest, which in a line case is the last Line group's: where the binned path is
-forced, and on the hot and late-large clouds, check_sequence asserts that it went through the tile kernels."""
+forced, and on the hot and late-large clouds, check_sequence asserts that it went through the tile kernels.
+
+The accumulator cases (ACC_SEEDS; any seed from ACC_SEED_BASE on, so PCR_SEQ_FUZZ_SEEDS=10400:12400 soaks them) run one in-core
+pipeline with per-reduction filters, surface channels, histograms, extremes, cell stats, tree bands and zonal tables at once:
+the point mask across the scatters of one ingest, the scatter path per cloud, the band order and fill rules over every band
+kind, and what trees(i) / zonal(i) answer after pointers were handed out, planes written, flags merged, a checkpoint call refused
+or nothing happened -- every state, band and table bit for bit against the features' own integer models."""
 import pytest
 
 import pcr

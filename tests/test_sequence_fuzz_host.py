@@ -9,7 +9,11 @@ Line cases (seeds from LINE_SEED_BASE on; LINE_SEEDS in the suite) append Line-g
 what a seed draws: their sums are exact too (a visit has weight 1), so the model -- the oracle's footprint, added in binary64 --
 needs no tolerance.  Gaussian groups are not drawn: their weights are expf values and their sums depend on the order of
 addition.  _line_pass checks the exactness condition for the Line sums with the oracle's binary64 mode; the test of the
-generator below checks it again."""
+generator below checks it again.
+
+Accumulator cases (seeds from ACC_SEED_BASE on; ACC_SEEDS in the suite) add a float32 channel `z`, surface channels, per-reduction
+filters, histograms, extremes, cell stats, tree bands and zonal tables to what a seed draws, in core: integer states and
+bit-defined bands, so the model -- the *_common models of each feature, from the same routing -- needs no tolerance either."""
 import json
 import os
 
@@ -23,7 +27,7 @@ import terrain_common as T
 from conftest import GOLDEN
 
 
-@pytest.mark.parametrize("seed", S.DEFAULT_SEEDS + S.LINE_SEEDS)
+@pytest.mark.parametrize("seed", S.DEFAULT_SEEDS + S.LINE_SEEDS + S.ACC_SEEDS)
 def test_sequence_on_the_host_engine_equals_the_model(seed, tmp_path):
     S.check_sequence(seed, pcr.ExecutionMode.CPU, "host", tmp_path)
 
@@ -56,7 +60,7 @@ def test_the_line_seeds_cover_the_line_situations():
     """Every situation the line cases are for occurs in at least three of LINE_SEEDS, recognised from the case alone; no seed
     of the list is idle, and what a line case is holds for each."""
     assert all(seed >= S.LINE_SEED_BASE for seed in S.LINE_SEEDS) and max(S.DEFAULT_SEEDS) < S.LINE_SEED_BASE
-    assert S.seeds_from_env("PCR_SEQ_FUZZ_NO_SUCH_VARIABLE") == S.DEFAULT_SEEDS + S.LINE_SEEDS
+    assert S.seeds_from_env("PCR_SEQ_FUZZ_NO_SUCH_VARIABLE") == S.DEFAULT_SEEDS + S.LINE_SEEDS + S.ACC_SEEDS
     seen = {name: [] for name in S.LINE_SITUATIONS}
     for seed in S.LINE_SEEDS:
         case = S.build(seed)
@@ -102,6 +106,63 @@ def test_the_line_seeds_are_the_cases_they_were():
         for plan in [case["plan"]] + [o["plan"] for o in case["ops"] if o["op"] == "checkpoint" and o["plan"] is not None]:
             del plan["terrain"]
         assert S.case_digest(case) == want[str(seed)], f"line seed {seed} is another case than it was"
+
+
+def test_the_accumulator_seeds_cover_the_accumulator_situations():
+    """Every situation the accumulator cases are for occurs in at least three of ACC_SEEDS, recognised from the case alone; and
+    what an accumulator case is holds for each: in core, never a line case, at least one accumulator entry, filters within
+    create's limits, `z` on every cloud without a +0.0, every cell far below the counters' wrap points."""
+    assert all(seed >= S.ACC_SEED_BASE for seed in S.ACC_SEEDS) and max(S.LINE_SEEDS) < S.ACC_SEED_BASE
+    assert 15 <= len(S.ACC_SEEDS) <= 30 and len(set(S.ACC_SEEDS)) == len(S.ACC_SEEDS)
+    assert not S.build(S.LINE_SEEDS[0])["acc"] and not S.build(0)["acc"]
+    seen = {name: [] for name in S.ACC_SITUATIONS}
+    kinds = set()
+    for seed in S.ACC_SEEDS:
+        case = S.build(seed)
+        acc, plan = case["acc"], case["plan"]
+        assert acc is not None and not case["line"] and not case["flavour"]["ooc"] and case["ops"][-1]["op"] == "finalize", seed
+        assert not case["marked"] and not case["split_first"], seed
+        entries = S.acc_entries(acc)
+        assert 1 <= len(entries) <= 9 and max(len(acc[k]) for k in ("hist", "ext", "stats")) <= 3, seed
+        assert len(acc["surfaces"]) <= 2 and len(plan["trees"]) <= 2 and len(plan["zonal"]) <= 2, seed
+        filters = {S.filter_key(e["filt"]) for e in entries + case["specs"] if e["filt"]}
+        assert len(filters) <= 8 and all(len(f) <= 3 for f in filters), seed
+        assert all(s["ch"] in ("a", "b") for s in case["specs"] if s["type"] in ("Sum", "Count", "Average", "WeightedAverage")), seed
+        assert all(h["bins"] in S.HIST_BINS and h["bins"] * case["grid"]["W"] * case["grid"]["H"] <= S.ACC_MAX_COUNTERS for h in acc["hist"]), seed
+        assert all(e["k"] in S.EXT_K and e["gap"] in S.EXT_GAPS for e in acc["ext"]), seed
+        assert all((s["origin"], s["res"]) in S.STAT_STEPS and 1 <= len(set(s["products"])) == len(s["products"]) <= 3 for s in acc["stats"]), seed
+        names = [S.band_name(i, s) for i, s in enumerate(case["specs"])] + [n for n, _, _, _ in S.acc_bands(acc)]
+        assert len(set(names)) == len(names), seed
+        assert all(t["source"] in names + ["dtm", "hag"] for t in plan["trees"] + plan["terrain"]), seed
+        assert sum(len(c["x"]) for c in case["clouds"]) < 1 << 22, seed           # N below 2^32, S2 exact below 2^22 points a cell
+        for c in case["clouds"]:
+            assert c["z"].dtype == np.float32 and len(c["z"]) == len(c["x"]) and not (c["z"].view(np.uint32) == 0).any(), seed
+            kinds.add(c["shape"])
+        assert all(o["plan"] is None and o["flavour"] is None for o in case["ops"] if o["op"] == "checkpoint"), seed
+        found = S.situations(case)
+        assert found <= set(S.ACC_SITUATIONS)
+        for name in found:
+            seen[name].append(seed)
+    for name in S.ACC_SITUATIONS:
+        assert len(seen[name]) >= 3, f"'{name}' occurs in seeds {seen[name]} only"
+    assert {"hot_acc", "entry_filtered", "pipeline_filtered", "empty"} <= kinds, kinds
+
+
+def test_the_accumulator_seeds_are_the_cases_they_are():
+    """ACC_SEEDS are pinned under a key of their own: the digest of an accumulator case covers the filters of its specs, the
+    `acc` lists, the plan's trees, zonal and terrain lists, the inserted ops and the `z` arrays of its clouds."""
+    with open(os.path.join(GOLDEN, "sequence_fuzz_cases.json")) as f:
+        want = json.load(f)["sha256_acc"]
+    assert sorted(int(s) for s in want) == sorted(S.ACC_SEEDS)
+    for seed in S.ACC_SEEDS:
+        a, b = S.build(seed), S.build(seed)
+        assert S.case_digest(a) == S.case_digest(b) == want[str(seed)], f"accumulator seed {seed} is another case than it was"
+        z = np.concatenate([c["z"] for c in a["clouds"]])
+        if len(z) < 5000:                                         # (a case of a few points need not hold every kind)
+            continue
+        assert np.isnan(z).any() and np.isposinf(z).any() and np.isneginf(z).any() and (z.view(np.uint32) == 0x80000000).any(), seed
+        assert ((z.view(np.uint32) & 0x7F800000) == 0).sum() > (z.view(np.uint32) == 0x80000000).sum(), seed      # denormals
+        assert (np.abs(z[np.isfinite(z)]) > 1e5).any(), seed                       # beyond every [lo, hi) and +-2^21 steps
 
 
 def test_the_terrain_draw():

@@ -243,6 +243,24 @@ def test_pipeline_equals_the_model():
         pipe.zonal_histogram(0, 1)
 
 
+def test_a_cloud_the_pipeline_filter_empties_leaves_the_table_valid():
+    """An ingest that PipelineConfig::filter keeps no point of changes no state: zonal(i) answers as before, as on the HIP
+    engine (pipeline.h, Pipeline::zonal).  The host engine used to refuse it; the operation-sequence fuzz's model found the two
+    engines apart."""
+    cfg = Z.pipeline_cfg(pcr, WP, HP, CPU)
+    cfg.filter.add("value", pcr.CompareOp.GreaterEqual, -1.0e30)
+    pipe = Z.create(pcr, cfg, "host")
+    pipe.ingest(Z.canopy_points(pcr, WP, HP, 1))
+    pipe.finalize()
+    before = pipe.zonal(0)
+    pipe.ingest(Z._cloud(pcr, np.array([3.5, 20.5]), np.array([4.5, 30.5]), np.array([-1.0e31, -2.0e31], F32)))     # all filtered out
+    Z.same_table(pipe.zonal(0), before, "after a cloud the filter empties")
+    assert pipe.stats().points_processed == len(Z.CLOUDS[(WP, HP, 1)][0])
+    pipe.ingest(Z._cloud(pcr, np.array([3.5]), np.array([4.5]), np.array([1.0], F32)))                             # one point that counts
+    with pytest.raises(RuntimeError, match="no zonal entry 0"):
+        pipe.zonal(0)
+
+
 def test_two_cones_known_answer():
     z = Z.cones()
     pipe = Z.create(pcr, Z.pipeline_cfg(pcr, 40, 32, CPU), "host")
