@@ -1,6 +1,8 @@
 """Randomised differential test: HIP path (C-ABI) vs the CPU oracle over random grids (origins, cell sizes,
 reference tile sizes), glyphs (Point / Line / Gaussian with default or per-point channels, rotation), reductions,
 scatter paths and row-block windows.  Every case is derived from its seed alone, so a failure names the seed.
+Gaussian radii here stop at 20 cells; radii above 20 on the splat kernels (the wide, generic and apron-spill forms) belong
+to test_gpu_gauss_large_radius.py, which has a generator of its own and applies this file's comparison to it.
 Bars as everywhere: Count/Min/Max bit-exact; sums 1e-5 (glyphs 1e-4) against the oracle accumulated in double,
 relative to the same reduction over |v| because these values are signed and cancel; NaN masks exact (Gaussian: a
 cell whose only weight sits on the 1e-6 cut-off may flip)."""
@@ -100,7 +102,12 @@ def run_gpu(A, og, rt, c, own_rows=None, halo=0):
 
 @pytest.mark.parametrize("seed", range(240))
 def test_random_case_matches_oracle(A, seed):
-    c = build_case(seed)
+    check_case_matches_oracle(A, build_case(seed), seed)
+
+
+def check_case_matches_oracle(A, c, seed):
+    """The comparison of one case with the oracle, and its allowances (also applied by test_gpu_gauss_large_radius.py to
+    the cases of its own generator)."""
     og, rt = c["og"], RT[c["rname"]]
     what = f'seed {seed}: {c["kind"]}/{c["rname"]} path={c["path"]} {og.width}x{og.height} tile {og.tile_width}x{og.tile_height}'
     got, st = run_gpu(A, og, rt, c)
