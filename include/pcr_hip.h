@@ -930,6 +930,59 @@ int pcr_hip_zone_rows_percentiles(const unsigned long long* d_zcounts, int bins,
 int pcr_hip_zone_rows_percentiles_host(const unsigned long long* h_zcounts, int bins, uint32_t Z, double lo, double w, int n_q,
                                        const float* q, unsigned long long* h_hist_n, float* const* h_outs);
 
+/* ---- polygons: a polygon set burnt into a Float32 label band (pcr/core/polygons.h: rasterize_polygons; Pipeline::set_zones
+ *      with a PolygonSet) -- gdal_rasterize's cell-centre rule, for the plot and stand maps of the zonal tables above and for
+ *      clipping a cloud to an area (the band as a NEAREST surface channel with a filter on it).  No reference counterpart.  The
+ *      arithmetic is written once, in csrc/rasterize.hpp, which the kernels and the host twin compile with contraction off: they
+ *      agree bit for bit, and both are the per-cell rule below, bit for bit.
+ *        input    coords: n_vertices pairs (x, y) of binary64 in the grid's CRS; ring_offsets: n_rings + 1 int64 into the
+ *                 vertices; polygon_offsets: n_polygons + 1 int64 into the rings; each starts at 0, does not decrease and ends
+ *                 at the count it indexes.  A ring is closed implicitly (a repeated last vertex is a degenerate edge: harmless).
+ *                 A polygon is ALL of its rings under the even-odd rule: holes and the parts of a multipolygon are further
+ *                 rings, orientation plays no part.  values: n_polygons floats, or NULL for (float)(p + 1).  All HOST arrays.
+ *        centre   cx(c) = min_x + (c + 0.5) * cell_size_x, cy(r) = max_y + (r + 0.5) * cell_size_y -- GridConfig::cell_to_world's
+ *                 expression: c + 0.5 exact, one rounded product, one rounded sum.  Of the grid only min_x, max_y, the cell
+ *                 sizes (either sign), width and height are read.
+ *        edge     the endpoints of an edge are ordered so that a.y <= b.y: two polygons that share an edge compute the same bits
+ *                 whichever way each walks it.  The edge crosses row r when a.y <= cy(r) < b.y -- half-open: a horizontal edge
+ *                 crosses nothing.  Then t = (cy - a.y) / (b.y - a.y) (true division), xc = a.x + t * (b.x - a.x), every
+ *                 operation rounded once, never an fma.
+ *        inside   cell (r, c) is inside polygon p when the number of p's crossing edges of row r with xc > cx(c) is odd.  So a
+ *                 polygon is closed on its low-x and low-y sides and open on the high ones, in world coordinates, and polygons
+ *                 that share edges (the same vertex bits) and partition a region label each of its cell centres exactly once.
+ *        overlap  the greatest polygon index wins (GDAL's burn order), whatever the order of execution
+ *        out      `height` rows of `width` floats, out_stride floats apart: the winning polygon's value, or `background`
+ *                 (bit for bit; the project's NaN 0x7FC00000 by default) where no polygon covers the centre
+ *      Refused, before any HIP call and with the same message on both paths: a null argument; null or inconsistent offsets; a
+ *      ring of fewer than 3 vertices; a coordinate that is not finite or beyond 1e100 in magnitude (so that no intermediate
+ *      overflows); more than 2^31 - 2 polygons, or 2^30 edges in one; a grid of more than 2^31 - 1 cells, or whose origin or cell sizes are not finite
+ *      or zero; out_stride < width; an output that overlaps an input or the work area; work_bytes below
+ *      pcr_hip_rasterize_work_bytes(n_vertices, n_polygons, width, height) (4 bytes per cell + 32 per vertex + 44 per polygon;
+ *      answered without a device).  A polygon wholly outside the grid, or of zero area, labels nothing and is no error.
+ *      pcr_hip_rasterize_polygons: the host reads every vertex once (the checks, the ordered edges, each polygon's rows and
+ *      columns), the tables go to d_work on s and s is waited for ONCE, before the kernels -- the tables leave host memory that
+ *      ends with the call.  Then, enqueued on s with nothing allocated: k_poly_fill, one wave per (polygon, row) -- lanes stride
+ *      over the polygon's edges, a crossing toggles bit k (the first column the crossing does not count for, found from an
+ *      estimate corrected by comparing real cx values) of a per-wave LDS bitmap, PCR_HIP_RASTERIZE_BLOCK_COLS columns of the
+ *      polygon's box per pass, then a lane per cell and one global atomic max of p + 1 into a uint32 plane per inside cell;
+ *      and k_poly_values, the plane into the band.  params->events: when not NULL, events (pcr_hip_event_create) recorded on s
+ *      before k_poly_fill, between the kernels and behind k_poly_values, for timing them (tools/rasterize_time.py).
+ *      _host: the same on a host band, one thread, polygons in index order. */
+#define PCR_HIP_RASTERIZE_BLOCK_COLS 4096
+typedef struct pcr_hip_rasterize_params {
+    float background;                /* the bits cells outside every polygon get */
+    int32_t reserved_;
+    void* events[3];                 /* NULL, or events to record: before k_poly_fill, between the kernels, at the end */
+} pcr_hip_rasterize_params;
+int pcr_hip_rasterize_work_bytes(int64_t n_vertices, int64_t n_polygons, int width, int height, size_t* bytes);
+int pcr_hip_rasterize_polygons(const pcr_hip_grid* grid, const double* h_coords, int64_t n_vertices, const int64_t* h_ring_offsets,
+                               int64_t n_rings, const int64_t* h_polygon_offsets, int64_t n_polygons, const float* h_values,
+                               const pcr_hip_rasterize_params* params, float* d_out, int64_t out_stride, void* d_work, size_t work_bytes,
+                               pcr_hip_stream s);
+int pcr_hip_rasterize_polygons_host(const pcr_hip_grid* grid, const double* h_coords, int64_t n_vertices, const int64_t* h_ring_offsets,
+                                    int64_t n_rings, const int64_t* h_polygon_offsets, int64_t n_polygons, const float* h_values,
+                                    const pcr_hip_rasterize_params* params, float* h_out, int64_t out_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,54 @@
+// pcr/core/polygons.h -- polygons burnt into a label grid, done where the grid is to live: gdal_rasterize's cell-centre rule,
+// for the plot and stand maps of the zonal tables (Pipeline::set_zones) and for clipping a cloud to an area (the grid as a
+// Nearest surface channel with a filter on it).  Not in the reference.
+//
+// The contract, one definition for host and device (csrc/rasterize.hpp, include/pcr_hip.h: "polygons").
+//   centre   cx(c), cy(r): what GridConfig::cell_to_world returns, bit for bit
+//   edge     endpoints ordered so that a.y <= b.y; crosses row r when a.y <= cy(r) < b.y (horizontal edges never do);
+//            t = (cy - a.y) / (b.y - a.y), xc = a.x + t * (b.x - a.x), each operation rounded once
+//   inside   cell (r, c) is inside a polygon when its crossing edges of row r with xc > cx(c) are odd in number -- all rings of
+//            the polygon together (even-odd): holes and multipolygon parts are further rings, orientation plays no part.  A
+//            polygon is closed on its low-x and low-y sides and open on the high ones; polygons that share edges (the same
+//            vertex bits) and partition a region label each cell centre of it exactly once
+//   overlap  the greatest polygon index wins (GDAL's burn order)
+//   band     Float32: the winning polygon's value (`values`, or index + 1), `background` elsewhere
+// Not done: all_touched, lines and points, exact per-point tests (the clip is at cell resolution), reprojection (run
+// pcr::transform / pcr.transform_xy on the coordinates first), shapefile and GeoPackage readers.
+#pragma once
+
+#include "pcr/core/grid.h"
+#include "pcr/core/grid_config.h"
+#include "pcr/core/types.h"
+
+#include <cstdint>
+#include <limits>
+#include <memory>
+#include <vector>
+
+namespace pcr {
+
+/// P polygons of R rings of V vertices, in the CRS of the grid they are burnt into.
+struct PolygonSet {
+    std::vector<double> coords;              // x0, y0, x1, y1, ...: 2 * V; rings are closed implicitly
+    std::vector<int64_t> ring_offsets;       // R + 1, into the vertices: 0 first, V last, never decreasing
+    std::vector<int64_t> polygon_offsets;    // P + 1, into the rings: 0 first, R last, never decreasing
+    std::vector<float> values;               // empty: polygon p burns p + 1; else P burn values
+    int64_t num_vertices() const { return (int64_t)(coords.size() / 2); }
+    int64_t num_rings() const { return ring_offsets.empty() ? 0 : (int64_t)ring_offsets.size() - 1; }
+    int64_t num_polygons() const { return polygon_offsets.empty() ? 0 : (int64_t)polygon_offsets.size() - 1; }
+};
+
+struct RasterizeOptions {
+    float background = std::numeric_limits<float>::quiet_NaN();      // cells outside every polygon
+};
+
+/// A one-band Float32 grid "label" of grid_config's width and height at `location`, tagged with the geometry.  Host: the host
+/// twin.  Device: the kernels on `stream`, synchronised before the call returns.  nullptr and `status` on failure:
+/// InvalidArgument for inconsistent offsets, a ring of fewer than 3 vertices, a coordinate that is not finite or beyond 1e100,
+/// values of another length than the polygons, more than 2^31 - 2 polygons or 2^31 - 1 cells, a geometry that is not finite.
+std::unique_ptr<Grid> rasterize_polygons(const PolygonSet& polygons, const GridConfig& grid_config,
+                                         MemoryLocation location = MemoryLocation::Host,
+                                         const RasterizeOptions& options = RasterizeOptions(), Status* status = nullptr,
+                                         void* stream = nullptr);
+
+}  // namespace pcr

@@ -10,6 +10,7 @@
 
 #include "pcr/core/grid_config.h"
 #include "pcr/core/ground_filter.h"
+#include "pcr/core/polygons.h"
 #include "pcr/core/sample_grid.h"
 #include "pcr/core/terrain.h"
 #include "pcr/core/trees.h"
@@ -414,6 +415,12 @@ public:
     /// the HIP engine: a Host grid is uploaded, a Device grid copied in place on the device), so the caller's grid may die or
     /// change afterwards.  InvalidArgument for an unknown name, another shape, a band outside the grid or not Float32.
     Status set_zones(const std::string& name, const Grid& grid, int band = 0);
+    /// Extension: the same with the labels burnt from polygons on PipelineConfig::grid (pcr/core/polygons.h: the cell-centre
+    /// rule, the greatest index wins, p + 1 or `values`): a plot or stand map straight from its outlines.  On the HIP engine the
+    /// polygons are scan-converted in HBM on the pipeline's stream, into memory the pipeline owns; on the host engine by the host
+    /// twin, bit for bit the same band.  InvalidArgument for an unknown name (which a sharded or out-of-core pipeline has
+    /// none of) and for what rasterize_polygons refuses.
+    Status set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options = RasterizeOptions());
     /// Extension: the table of PipelineConfig::zonal[i] -- the zone band as the last finalize() left it (or the external grid),
     /// the cell-stats planes and cubes as they are.  Valid after a finalize with no ingest since -- an ingest of an empty cloud, or
     /// of one that PipelineConfig::filter keeps no point of, changes no state and does not count, on either engine; handing out or

@@ -421,6 +421,11 @@ Status Pipeline::Impl::set_zones(const std::string& name, const Grid& grid, int 
     Status s = detail::hip_status(pcr_hip_stream_synchronize(stream));
     return s.ok() ? detail::store_zones(cfg, name, grid, band, MemoryLocation::Device, stream, &zone_grids) : s;
 }
+// ... or burnt there from polygons, on the pipeline's stream.
+Status Pipeline::Impl::set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options) {
+    DeviceScope dev(cfg.cuda_device_id);
+    return detail::store_zones(cfg, name, polygons, options, MemoryLocation::Device, stream, &zone_grids);
+}
 // The table of entry i, behind the last finalize on the pipeline's stream: the label band as it left the pipeline (`out`), the
 // cell-stats planes and the cubes where they are.  Nothing of it runs in finalize: no plane-state event.
 Status Pipeline::Impl::zonal(int i, ZonalTable* out, bool with_counts) {

@@ -76,6 +76,9 @@ Status Pipeline::Host::init() {
 Status Pipeline::Host::set_zones(const std::string& name, const Grid& grid, int band) {
     return detail::store_zones(cfg, name, grid, band, MemoryLocation::Host, nullptr, &zone_grids);
 }
+Status Pipeline::Host::set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options) {
+    return detail::store_zones(cfg, name, polygons, options, MemoryLocation::Host, nullptr, &zone_grids);
+}
 // The table of entry i through the C-ABI's host twins: the label band of the result, the planes and the cubes where they are.
 Status Pipeline::Host::zonal(int i, ZonalTable* out, bool with_counts) const {
     if (!out || i < 0 || !finalized || !zonal_fresh || !result || (size_t)i >= zonal_plan.entries.size())

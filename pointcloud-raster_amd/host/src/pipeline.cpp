@@ -363,6 +363,11 @@ Status Pipeline::set_zones(const std::string& name, const Grid& grid, int band) 
     if (banded_) return Status::error(StatusCode::InvalidArgument, "pipeline: set_zones: '" + name + "' names no external label grid of this pipeline");
     return impl_->set_zones(name, grid, band);
 }
+Status Pipeline::set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options) {
+    if (host_) return host_->set_zones(name, polygons, options);
+    if (banded_) return Status::error(StatusCode::InvalidArgument, "pipeline: set_zones: '" + name + "' names no external label grid of this pipeline");
+    return impl_->set_zones(name, polygons, options);
+}
 Status Pipeline::zonal(int i, ZonalTable* out, bool with_counts) const {
     if (impl_) return impl_->zonal(i, out, with_counts);
     if (host_) return host_->zonal(i, out, with_counts);

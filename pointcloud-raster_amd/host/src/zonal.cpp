@@ -2,6 +2,7 @@
 #include "zonal.h"
 
 #include "pipeline_common.h"
+#include "polygons.h"
 
 #include <algorithm>
 #include <cmath>
@@ -92,12 +93,30 @@ Status plan_zonal(const PipelineConfig& cfg, const GroundPlan& ground, const Ter
     return Status::success();
 }
 
+namespace {
+Status unknown_zones(const PipelineConfig& cfg, const std::string& name) {
+    bool known = false;
+    for (const auto& z : cfg.zonal) known = known || (z.external && z.zones == name);
+    if (known) return Status::success();
+    return Status::error(StatusCode::InvalidArgument, "pipeline: set_zones: '" + name + "' names no external label grid of this pipeline");
+}
+}  // namespace
+
+Status store_zones(const PipelineConfig& cfg, const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options,
+                   MemoryLocation loc, void* stream, std::map<std::string, ZoneGrid>* grids) {
+    Status s = unknown_zones(cfg, name);
+    if (!s.ok()) return s;
+    ZoneGrid g;
+    s = g.band.allocate((size_t)cfg.grid.width * (size_t)cfg.grid.height * sizeof(float), loc);
+    if (s.ok()) s = rasterize_into(polygons, cfg.grid, options, static_cast<float*>(g.band.data()), loc, stream);
+    if (s.ok()) (*grids)[name] = std::move(g);
+    return s;
+}
+
 Status store_zones(const PipelineConfig& cfg, const std::string& name, const Grid& grid, int band, MemoryLocation loc, void* stream,
                    std::map<std::string, ZoneGrid>* grids) {
     auto bad = [](const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: set_zones: " + msg); };
-    bool known = false;
-    for (const auto& z : cfg.zonal) known = known || (z.external && z.zones == name);
-    if (!known) return bad("'" + name + "' names no external label grid of this pipeline");
+    if (Status known = unknown_zones(cfg, name); !known.ok()) return known;
     if (band < 0 || band >= grid.num_bands()) return bad("band index outside the grid");
     if (grid.band_desc(band).dtype != DataType::Float32 || !grid.band_f32(band)) return bad("the label band must be Float32");
     if (grid.cols() != cfg.grid.width || grid.rows() != cfg.grid.height)

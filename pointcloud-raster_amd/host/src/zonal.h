@@ -10,6 +10,7 @@
 #include "ground_filter.h"
 #include "histogram.h"
 #include "pcr/core/grid.h"
+#include "pcr/core/polygons.h"
 #include "pcr/engine/pipeline.h"
 #include "pcr_hip.h"
 #include "terrain.h"
@@ -52,6 +53,10 @@ struct ZoneGrid {
 /// set_zones' refusals and, when it passes, the copy into `loc` memory (on `stream`, which is then waited for).
 Status store_zones(const PipelineConfig& cfg, const std::string& name, const Grid& grid, int band, MemoryLocation loc, void* stream,
                    std::map<std::string, ZoneGrid>* grids);
+/// The same with the labels burnt from polygons on cfg.grid, in `loc` memory (polygons.h: rasterize_into): the name's refusal
+/// first, then rasterize_polygons' own.
+Status store_zones(const PipelineConfig& cfg, const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options,
+                   MemoryLocation loc, void* stream, std::map<std::string, ZoneGrid>* grids);
 
 /// What a table is made from: pointers into `device` or host memory, every band and plane rows x width, contiguous.
 struct ZonalInputs {

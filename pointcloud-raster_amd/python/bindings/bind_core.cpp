@@ -5,6 +5,7 @@
 #include "pcr/core/grid_config.h"
 #include "pcr/core/ground_filter.h"
 #include "pcr/core/point_cloud.h"
+#include "pcr/core/polygons.h"
 #include "pcr/core/reproject.h"
 #include "pcr/core/sample_grid.h"
 #include "pcr/core/terrain.h"
@@ -435,6 +436,57 @@ void bind_core(py::module_& m) {
         return py::make_tuple(std::move(out), tree_table_dict(t));
     }, py::arg("grid"), py::arg("band") = 0, py::arg("spec") = py::none(), py::arg("cell_size_x") = 1.0, py::arg("cell_size_y") = -1.0,
        "(grid with the bands tree_id and tree_height, table): the table a dict of numpy arrays row, col, x, y, height, crown_cells");
+    // extension: polygons burnt into a label grid (pcr.rasterize_polygons, Pipeline.set_zones)
+    using F64Array = py::array_t<double, py::array::c_style | py::array::forcecast>;
+    using I64Array = py::array_t<int64_t, py::array::c_style | py::array::forcecast>;
+    py::class_<PolygonSet>(m, "PolygonSet",
+                           "P polygons of R rings of V vertices: coords (V, 2) float64, ring_offsets (R + 1) and polygon_offsets (P + 1) "
+                           "int64, values (P) float32 or None for p + 1.  Rings close implicitly; a polygon is all of its rings under the "
+                           "even-odd rule")
+        .def(py::init([](F64Array coords, I64Array ring_offsets, I64Array polygon_offsets, py::object values) {
+            if (!((coords.ndim() == 2 && coords.shape(1) == 2) || coords.size() == 0))
+                throw std::invalid_argument("PolygonSet: coords must have the shape (V, 2)");
+            if (ring_offsets.ndim() != 1 || polygon_offsets.ndim() != 1) throw std::invalid_argument("PolygonSet: offsets must be 1-D");
+            PolygonSet s;
+            s.coords.assign(coords.data(), coords.data() + coords.size());
+            s.ring_offsets.assign(ring_offsets.data(), ring_offsets.data() + ring_offsets.size());
+            s.polygon_offsets.assign(polygon_offsets.data(), polygon_offsets.data() + polygon_offsets.size());
+            if (!values.is_none()) {
+                auto v = values.cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+                if (v.ndim() != 1 || v.size() + 1 != polygon_offsets.size()) throw std::invalid_argument("PolygonSet: values must be one per polygon");
+                s.values.assign(v.data(), v.data() + v.size());
+            }
+            return s;
+        }), py::arg("coords"), py::arg("ring_offsets"), py::arg("polygon_offsets"), py::arg("values") = py::none())
+        .def_property_readonly("coords", [](const PolygonSet& s) {
+            py::array_t<double> a({(py::ssize_t)s.num_vertices(), (py::ssize_t)2});
+            if (!s.coords.empty()) std::memcpy(a.mutable_data(), s.coords.data(), s.coords.size() * sizeof(double));
+            return a;
+        })
+        .def_property_readonly("ring_offsets", [](const PolygonSet& s) {
+            return py::array_t<int64_t>((py::ssize_t)s.ring_offsets.size(), s.ring_offsets.data());
+        })
+        .def_property_readonly("polygon_offsets", [](const PolygonSet& s) {
+            return py::array_t<int64_t>((py::ssize_t)s.polygon_offsets.size(), s.polygon_offsets.data());
+        })
+        .def_property_readonly("values", [](const PolygonSet& s) -> py::object {
+            if (s.values.empty()) return py::none();
+            return py::array_t<float>((py::ssize_t)s.values.size(), s.values.data());
+        })
+        .def_property_readonly("num_vertices", &PolygonSet::num_vertices)
+        .def_property_readonly("num_rings", &PolygonSet::num_rings)
+        .def_property_readonly("num_polygons", &PolygonSet::num_polygons);
+    m.def("rasterize_polygons", [](const PolygonSet& polygons, const GridConfig& grid_config, float background, MemoryLocation location) {
+        Status s;
+        RasterizeOptions o;
+        o.background = background;
+        auto out = rasterize_polygons(polygons, grid_config, location, o, &s, nullptr);
+        raise_if_error(s);
+        return out;
+    }, py::arg("polygons"), py::arg("grid_config"), py::arg("background") = std::numeric_limits<float>::quiet_NaN(),
+       py::arg("location") = MemoryLocation::Host,
+       "A one-band Float32 grid 'label' on grid_config at `location`: per cell the value of the greatest-index polygon that holds the "
+       "cell's centre (p + 1, or the set's values), `background` elsewhere");
     // (tests) what the id band holds for an id: the clamp at 2^24 on its own
     m.def("_tree_id_value", [](int64_t id) { return pcrhip::trees::id_value(id); }, py::arg("id"));
     // (tests, tools) the host twin on an array, which the kernels are compared with; -> (id [h, w], height [h, w], table)

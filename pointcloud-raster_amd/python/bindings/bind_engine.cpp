@@ -371,6 +371,12 @@ void bind_engine(py::module_& m) {
         }, py::arg("name"), py::arg("grid"), py::arg("band") = 0,
              "Gives the external label grid `name` of a ZonalConfig its labels: band `band` of a grid with the pipeline's width and "
              "height, copied into the pipeline")
+        .def("set_zones", [](Pipeline& p, const std::string& name, const PolygonSet& polygons, float background) {
+            RasterizeOptions o;
+            o.background = background;
+            raise_if_error(p.set_zones(name, polygons, o));
+        }, py::arg("name"), py::arg("polygons"), py::arg("background") = std::numeric_limits<float>::quiet_NaN(),
+             "... or burns them from a PolygonSet on the pipeline's grid (pcr.rasterize_polygons' rule): in HBM on the HIP engine")
         .def("zonal", [](const Pipeline& p, int i) {
             ZonalTable t;
             raise_if_error(p.zonal(i, &t));

@@ -79,7 +79,9 @@ from ._pcr import (  # noqa: E402,F401
     TreeSpec, TreeBandConfig, segment_trees,
     SampleMode, SurfaceChannelConfig, sample_grid,
     HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig, ZonalConfig,
+    PolygonSet, rasterize_polygons,
 )
+from .polygons import read_geojson_polygons  # noqa: E402,F401  (also gives PolygonSet its from_wkt)
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
 
@@ -183,4 +185,5 @@ __all__ = [
     "TreeSpec", "TreeBandConfig", "segment_trees",
     "SampleMode", "SurfaceChannelConfig", "sample_grid",
     "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig", "ZonalConfig",
+    "PolygonSet", "rasterize_polygons", "read_geojson_polygons",
 ]

@@ -91,6 +91,14 @@ class ZoneFoldParams(C.Structure):
         super().__init__(combine=combine, reserved_=0)
 
 
+class RasterizeParams(C.Structure):
+    """pcr_hip_rasterize_params: the background's bits default to the project's NaN; events: see include/pcr_hip.h."""
+    _fields_ = [("background", C.c_float), ("reserved_", C.c_int32), ("events", C.c_void_p * 3)]
+
+    def __init__(self, background=float("nan"), events=(None, None, None)):
+        super().__init__(background=background, reserved_=0, events=(C.c_void_p * 3)(*events))
+
+
 class TreeParams(C.Structure):
     """pcr_hip_tree_params with the defaults of pcr.TreeSpec."""
     _fields_ = [("min_height", C.c_float), ("window_base", C.c_float), ("window_slope", C.c_float),
@@ -245,6 +253,10 @@ SYMBOLS = {
     "pcr_hip_zone_rows_stats_host": [_VP, _VP, _VP, _U32, C.c_double, C.c_double, C.c_int, _VP, _VP, _VP],
     "pcr_hip_zone_rows_percentiles": [_VP, C.c_int, _U32, C.c_double, C.c_double, C.c_int, _VP, _VP, C.POINTER(_VP), _VP],
     "pcr_hip_zone_rows_percentiles_host": [_VP, C.c_int, _U32, C.c_double, C.c_double, C.c_int, _VP, _VP, C.POINTER(_VP)],
+    "pcr_hip_rasterize_work_bytes": [_I64, _I64, C.c_int, C.c_int, C.POINTER(_SZ)],
+    "pcr_hip_rasterize_polygons": [C.POINTER(Grid), _VP, _I64, _VP, _I64, _VP, _I64, _VP, C.POINTER(RasterizeParams), _VP, _I64, _VP,
+                                   _SZ, _VP],
+    "pcr_hip_rasterize_polygons_host": [C.POINTER(Grid), _VP, _I64, _VP, _I64, _VP, _I64, _VP, C.POINTER(RasterizeParams), _VP, _I64],
 }
 
 _lib = None
