@@ -983,6 +983,58 @@ int pcr_hip_rasterize_polygons_host(const pcr_hip_grid* grid, const double* h_co
                                     int64_t n_rings, const int64_t* h_polygon_offsets, int64_t n_polygons, const float* h_values,
                                     const pcr_hip_rasterize_params* params, float* h_out, int64_t out_stride);
 
+/* ---- polygon index: which polygon holds each POINT of a cloud, exactly (pcr/core/polygons.h: points_in_polygons) -- the clip
+ *      and the tagging that the label band above gives only at cell resolution (PDAL filters.crop / filters.overlay).  No
+ *      reference counterpart.  The rule is written once, in csrc/point_in_polygon.hpp, on rasterize.hpp's own edge arithmetic,
+ *      and compiled by the kernel, the host twin and the index builder with contraction off: they agree bit for bit.
+ *        input    the polygon arrays of pcr_hip_rasterize_polygons, with its refusals; a point is (x, y) in binary64 in the
+ *                 polygons' CRS
+ *        edge     endpoints ordered so that a.y <= b.y; the edge crosses the point's level when a.y <= y < b.y (a horizontal
+ *                 edge never does); then xc = a.x + ((y - a.y) / (b.y - a.y)) * (b.x - a.x), every operation rounded once
+ *        inside   the point is inside polygon p when the number of p's crossing edges with xc > x is odd, all rings together: a
+ *                 polygon is closed on its low-x and low-y sides and open on the high ones, and polygons that share edges (the
+ *                 same vertex bits) and partition a region hold every point of it exactly once
+ *        overlap  the greatest polygon index wins
+ *        out      Float32: values[p] or (float)(p + 1) of the winner; `background` (any bits, kept; default the project's NaN
+ *                 0x7FC00000) where no polygon holds the point.  A NaN coordinate is in no polygon; x = -Inf counts every
+ *                 crossing, an even number; x = +Inf and y = +-Inf count none.
+ *        grid     at a cell centre (cx(c), cy(r)) the answer is the band of pcr_hip_rasterize_polygons on that grid, bit for bit
+ *      The index is an accelerator and no part of the contract: a uniform grid of cols x rows cells over the vertices' bounding
+ *      box, built on the host (csrc/point_in_polygon_index.hpp, the one builder).  A cell lists, by polygon index descending,
+ *      the polygons that hold all of it (no edges) and those with an edge near it (a run of edges to count crossings over); a
+ *      walk stops at the first polygon that holds the point.  index_cols / index_rows: 0 automatic (2 * sqrt(vertices) a side,
+ *      1 .. 2048), or 1 .. 2048; an automatic side is halved until the tables fit max_index_bytes (0: 256 MiB), an explicit
+ *      size that does not fit is refused; either is halved where a cell is narrower than binary64's spacing (info tells).
+ *      _create: a host object, no HIP call.  _upload: the tables to d_tables (`bytes` >= _info's bytes) on s, which is waited for
+ *      ONCE.  pcr_hip_points_in_polygons: k_points_in_polygons on s, nothing allocated, no host wait: one pass, x and y read and
+ *      out stored non-temporally, 16 bytes wide where all three start on 16 bytes; a point whose cell lists more than 16 edges
+ *      for a polygon hands that walk to a whole wave through a queue in LDS; events: NULL, or two events (either may be
+ *      NULL) recorded before and behind the kernel.  _host: the same walk on host arrays over `threads` threads; every point is
+ *      independent, so the bits do not depend on the count.
+ *      Refused, before any HIP call and with the same message on both paths: what pcr_hip_rasterize_polygons refuses about the
+ *      polygon arrays; a null argument; index_cols or index_rows outside 0 .. 2048; tables over the cap; bytes too small; more
+ *      than 2^40 points; an output that overlaps x, y or the tables.  n == 0 is no error.  Polygons with no ring, no area or no
+ *      edge hold nothing.  Not done: all_touched, lines and points as geometries, reprojection of the polygons. */
+#define PCR_HIP_POLYGON_POINTS_PER_LANE 4
+typedef struct pcr_hip_polygon_index pcr_hip_polygon_index;
+typedef struct pcr_hip_polygon_index_params {
+    float background;                /* the bits points outside every polygon get */
+    int32_t index_cols, index_rows;  /* 0: automatic; 1 .. 2048 */
+    int32_t reserved_;
+    size_t max_index_bytes;          /* 0: 256 MiB */
+} pcr_hip_polygon_index_params;
+int pcr_hip_polygon_index_create(const double* h_coords, int64_t n_vertices, const int64_t* h_ring_offsets, int64_t n_rings,
+                                 const int64_t* h_polygon_offsets, int64_t n_polygons, const float* h_values,
+                                 const pcr_hip_polygon_index_params* params, pcr_hip_polygon_index** index);
+int pcr_hip_polygon_index_destroy(pcr_hip_polygon_index* index);
+int pcr_hip_polygon_index_info(const pcr_hip_polygon_index* index, int* cols, int* rows, int64_t* items, int64_t* listed_edges,
+                               size_t* bytes);
+int pcr_hip_polygon_index_upload(const pcr_hip_polygon_index* index, void* d_tables, size_t bytes, pcr_hip_stream s);
+int pcr_hip_points_in_polygons(const pcr_hip_polygon_index* index, const void* d_tables, const double* d_x, const double* d_y, uint64_t n,
+                               float* d_out, pcr_hip_stream s, void* const* events);
+int pcr_hip_points_in_polygons_host(const pcr_hip_polygon_index* index, const double* h_x, const double* h_y, uint64_t n, float* h_out,
+                                    int threads);
+
 #ifdef __cplusplus
 }
 #endif

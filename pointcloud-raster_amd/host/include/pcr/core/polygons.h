@@ -12,17 +12,23 @@
 //            vertex bits) and partition a region label each cell centre of it exactly once
 //   overlap  the greatest polygon index wins (GDAL's burn order)
 //   band     Float32: the winning polygon's value (`values`, or index + 1), `background` elsewhere
-// Not done: all_touched, lines and points, exact per-point tests (the clip is at cell resolution), reprojection (run
-// pcr::transform / pcr.transform_xy on the coordinates first), shapefile and GeoPackage readers.
+//
+// points_in_polygons is the same rule with the cell centre replaced by the POINT (csrc/point_in_polygon.hpp, include/pcr_hip.h:
+// "polygon index"): the exact clip and the exact tag, where the label grid gives the cell's.  At a cell centre the two agree
+// bit for bit.  A NaN coordinate is in no polygon.
+// Not done: all_touched, lines and points as geometries, reprojection (run pcr::transform / pcr.transform_xy on the coordinates
+// first), shapefile and GeoPackage readers.  (A pipeline derives such a channel at ingest: PipelineConfig::polygon_channels.)
 #pragma once
 
 #include "pcr/core/grid.h"
 #include "pcr/core/grid_config.h"
+#include "pcr/core/point_cloud.h"
 #include "pcr/core/types.h"
 
 #include <cstdint>
 #include <limits>
 #include <memory>
+#include <string>
 #include <vector>
 
 namespace pcr {
@@ -50,5 +56,19 @@ std::unique_ptr<Grid> rasterize_polygons(const PolygonSet& polygons, const GridC
                                          MemoryLocation location = MemoryLocation::Host,
                                          const RasterizeOptions& options = RasterizeOptions(), Status* status = nullptr,
                                          void* stream = nullptr);
+
+struct PointInPolygonOptions {
+    float background = std::numeric_limits<float>::quiet_NaN();      // points outside every polygon (any bits are kept)
+    int index_cols = 0, index_rows = 0;                              // the index: 0 automatic, or 1 .. 2048 (tests, tuning)
+    size_t max_index_bytes = 0;                                      // the cap on the index tables; 0: 256 MiB
+};
+
+/// Adds (or overwrites) the Float32 channel `channel` of `cloud`, where the cloud lives: per point the value of the
+/// greatest-index polygon that holds it (p + 1, or the set's values), `background` elsewhere.  The polygons are taken to be in
+/// the cloud's CRS.  Host: the host twin over the OpenMP thread count.  Device: the index is built on the host, uploaded, and
+/// the kernel runs on the default stream, which is waited for.  InvalidArgument for what rasterize_polygons refuses about the
+/// set, an empty channel name, an existing channel of another type, an index size outside 0 .. 2048 or over the cap.
+Status points_in_polygons(PointCloud& cloud, const PolygonSet& polygons, const std::string& channel = "polygon",
+                          const PointInPolygonOptions& options = PointInPolygonOptions());
 
 }  // namespace pcr

@@ -78,6 +78,13 @@ struct TreeBandConfig : TreeSpec {
     std::string height_band_name;        // default "{source_band}_tree_height"
 };
 
+/// One entry of PipelineConfig::polygon_channels: a per-point Float32 channel the pipeline derives at ingest from the polygons
+/// given with Pipeline::set_polygons -- the value of the greatest-index polygon that holds the point, exactly
+/// (pcr/core/polygons.h: points_in_polygons).
+struct PolygonChannelConfig {
+    std::string name;                    // the channel: usable wherever a Float32 channel is named
+};
+
 /// One entry of PipelineConfig::surface_channels: a per-point Float32 channel the pipeline derives at ingest from a finished
 /// band (Pipeline::set_surface) -- the band's sample at the point, or, with a value_channel, that channel minus the sample
 /// (z and a DTM: the height above ground).  The contract is pcr/core/sample_grid.h's.
@@ -304,6 +311,16 @@ struct PipelineConfig {
     // than 8 entries, a row-block shard and a pipeline that has to run out of core.  Empty: nothing is allocated, launched or
     // validated differently.
     std::vector<SurfaceChannelConfig> surface_channels;
+    // Per-point Float32 channels derived at ingest from polygons (PolygonChannelConfig, pcr/core/polygons.h: the exact per-point
+    // test): at every ingest and every chunk of ingest_file, after reprojection and beside the surface channels, before the
+    // filters, each point gets the value of the greatest-index polygon that holds it -- the exact clip (a filter on the name)
+    // and the exact tag ("which plot").  The name works wherever a Float32 channel is named.  On the HIP engine the index
+    // tables live in HBM the pipeline owns and the kernel runs on the pipeline's stream with no host wait; the host engine runs
+    // the twin and gives the same channel bits.  Each name needs its polygons before the first ingest
+    // (Pipeline::set_polygons); checkpoints record no polygons.  create() refuses an empty or duplicate name, a name that is
+    // also a surface channel, more than 8 entries, a row-block shard and a pipeline that has to run out of core.  Empty: nothing
+    // is allocated, launched or validated differently.
+    std::vector<PolygonChannelConfig> polygon_channels;
     // Per-cell histograms (HistogramConfig): every ingest also counts each entry's channel into its cube -- on the HIP engine
     // in HBM, bins * cells * 4 bytes that count towards gpu_memory_budget -- and finalize() appends its percentile bands BEHIND
     // the reductions' bands and AHEAD of the DTM, hag and terrain bands: with fill_nodata_radius they are filled like a Max
@@ -386,6 +403,13 @@ public:
     /// stream first.  InvalidArgument for an unknown name, a grid without geometry, a band outside the grid or not Float32;
     /// CrsError when the surface's CRS and the grid's are both identified and differ.
     Status set_surface(const std::string& name, const Grid& grid, int band = 0);
+    /// Extension: gives the polygon channel `name` (PipelineConfig::polygon_channels) its polygons, in the CRS of the pipeline's
+    /// grid.  The index is built on the host and kept (on the HIP engine its tables are uploaded once, into HBM the pipeline
+    /// owns, after waiting for the pipeline's stream), so the caller's set may die or change afterwards; it may be called again
+    /// between ingests.  InvalidArgument for an unknown name (which a sharded or out-of-core pipeline has none of) and for what
+    /// points_in_polygons refuses about the set and the options.
+    Status set_polygons(const std::string& name, const PolygonSet& polygons,
+                        const PointInPolygonOptions& options = PointInPolygonOptions());
     /// Extension: the cube of PipelineConfig::histograms[i] as a host copy, [bins][rows][width] counters, after synchronising
     /// with the pipeline's stream.  Valid after any ingest (all zero before the first); finalize() is not needed.  Height strata
     /// and canopy cover above any threshold are sums of its bin planes.  InvalidArgument for an index outside the list.

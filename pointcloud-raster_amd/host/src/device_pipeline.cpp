@@ -23,6 +23,7 @@ using detail::kPlaneBits;
 Pipeline::Impl::~Impl() {
     if (engine) pcr_hip_engine_destroy(engine);
     surfaces.clear();
+    polygon_sets.clear();
     cubes.clear();
     ext_keys.clear();
     stat_planes.clear();
@@ -132,6 +133,8 @@ Status Pipeline::Impl::init() {
     if (!(s = detail::plan_zonal(cfg, ground, terrain, tree_plan, &zonal_plan)).ok()) return s;
     if (!(s = detail::plan_surfaces(cfg)).ok()) return s;
     surfaces.resize(cfg.surface_channels.size());
+    if (!(s = detail::plan_polygon_channels(cfg)).ok()) return s;
+    polygon_sets.resize(cfg.polygon_channels.size());
 
     // row window of this device
     int r0 = 0, r1 = g.height;
@@ -872,6 +875,17 @@ Status Pipeline::Impl::set_surface(const std::string& name, const Grid& grid, in
     return detail::store_surface(grid, band, geom, MemoryLocation::Device, stream, &surfaces[(size_t)index]);
 }
 
+// PipelineConfig::polygon_channels: the index built on the host, its tables into HBM the pipeline owns.  Chunks in flight may
+// still read the old tables: the stream is waited for first (the upload waits for its copies, so the caller's set is free on
+// return).
+Status Pipeline::Impl::set_polygons(const std::string& name, const PolygonSet& polygons, const PointInPolygonOptions& options) {
+    if (detail::polygon_channel_index(cfg, name) < 0)
+        return detail::store_polygons(cfg, name, polygons, options, true, stream, &polygon_sets);        // (the refusal)
+    DeviceScope dev(cfg.cuda_device_id);
+    Status s = detail::hip_status(pcr_hip_stream_synchronize(stream));
+    return s.ok() ? detail::store_polygons(cfg, name, polygons, options, true, stream, &polygon_sets) : s;
+}
+
 // ---- ingest: the steps, in the order ingest() takes them ---------------------------------------------------------------------
 // Device pointer of a named Float32 channel (Ingest::channel): a surface channel as sample_surfaces left it, a channel of the
 // cloud staged once; null for no name or no such channel (-> the GlyphSpec's default).
@@ -923,6 +937,22 @@ Status Pipeline::Impl::sample_surfaces(Ingest& in) {
                                                    (int)sc.mode, static_cast<float*>(sb->data()), stream));
         if (!s.ok()) return s;
         in.staged[sc.name] = static_cast<const float*>(sb->data());
+    }
+    return Status::success();
+}
+
+// Polygon channels: each derived once, for all n points, from its index tables in HBM at the (reprojected) coordinates, into a
+// staging buffer of its own that the lookup then answers with, like a surface channel.  On the pipeline's stream, no host wait.
+Status Pipeline::Impl::locate_polygons(Ingest& in) {
+    for (size_t k = 0; k < polygon_sets.size(); ++k) {
+        const std::string& name = cfg.polygon_channels[k].name;
+        detail::Buffer* pb = nullptr;
+        Status s = staging_at_least("polygon:" + name, in.n * sizeof(float), &pb);
+        if (s.ok())
+            s = polygon_sets[k]->locate(static_cast<const double*>(in.dx), static_cast<const double*>(in.dy), in.n,
+                                        static_cast<float*>(pb->data()), true, stream, 1);
+        if (!s.ok()) return s;
+        in.staged[name] = static_cast<const float*>(pb->data());
     }
     return Status::success();
 }
@@ -1039,6 +1069,7 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     DeviceScope dev(cfg.cuda_device_id);
     // validate every predicate and reduction before touching state (pipeline_common.cpp: the reference's checks and messages)
     Status s = surfaces.empty() ? Status::success() : detail::validate_surfaces(cfg, cloud, surfaces);
+    if (s.ok() && !polygon_sets.empty()) s = detail::validate_polygon_channels(cfg, cloud, polygon_sets);
     if (s.ok()) s = detail::validate_cloud(cfg, cloud, PCR_HIP_MAX_FILTER_SET, PCR_HIP_MAX_FILTER_PREDICATES);
     detail::Reprojection rp;
     if (s.ok()) s = detail::plan_reprojection(cfg, cloud, &rp);
@@ -1047,6 +1078,7 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
 
     if (!(s = stage_xy(in, rp)).ok()) return s;
     if (!(s = sample_surfaces(in)).ok()) return s;
+    if (!(s = locate_polygons(in)).ok()) return s;
     if (!(s = filter_stage(in)).ok()) return s;
     if (in.kept == 0) return Status::success();                  // pipeline.cpp:349-353: PipelineConfig::filter keeps nothing
     pcr_hip_engine_set_point_mask(engine, in.class_mask[0]);

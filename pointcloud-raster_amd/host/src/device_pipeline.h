@@ -11,6 +11,7 @@
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
+#include "polygons.h"
 #include "sample_grid.h"
 #include "terrain.h"
 #include "trees.h"
@@ -118,6 +119,7 @@ struct Pipeline::Impl {
     std::vector<StatPlanes> stat_planes;     // entry by entry: N (uint32), S1 (int64), S2 (uint64) over state_rows * width in HBM,
                                              // zeroed at create and only ever added to: no part in the plane-state rules
     std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in HBM (set_surface)
+    detail::PolygonChannels polygon_sets;    // PipelineConfig::polygon_channels, entry by entry: the index, its tables in HBM (set_polygons)
     detail::Buffer d_bands_done;             // one word per group, set by a scatter that stored the group's bands.  Page-locked
                                              // host memory the device writes through its mapping (the pointer is the same on
                                              // both sides): the blocking finalize reads it after its synchronise and launches
@@ -141,6 +143,7 @@ struct Pipeline::Impl {
     Status ingest(const PointCloud& cloud, bool wait = true);
     Status finalize(bool wait = true);
     Status set_surface(const std::string& name, const Grid& grid, int band);
+    Status set_polygons(const std::string& name, const PolygonSet& polygons, const PointInPolygonOptions& options);
     Status save_state(const std::string& dir);
     Status load_state(const std::string& dir);
     ProgressInfo stats() const;
@@ -209,6 +212,7 @@ struct Pipeline::Impl {
     Status channel_of(Ingest& in, const std::string& name, const float** out);
     Status stage_xy(Ingest& in, const detail::Reprojection& rp);
     Status sample_surfaces(Ingest& in);
+    Status locate_polygons(Ingest& in);
     Status filter_stage(Ingest& in);
     Status check_line_reach(Ingest& in);
     Status scatter_groups(Ingest& in);

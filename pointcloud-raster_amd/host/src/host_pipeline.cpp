@@ -35,6 +35,8 @@ Status Pipeline::Host::init() {
         Status ok = detail::plan_surfaces(cfg);
         if (!ok.ok()) return ok;
         surfaces.resize(cfg.surface_channels.size());
+        if (!(ok = detail::plan_polygon_channels(cfg)).ok()) return ok;
+        polygon_sets.resize(cfg.polygon_channels.size());
     }
     engine = std::make_unique<detail::HostEngine>(g, (int)cfg.cpu_threads);        // cpu_threads = 0: every core (pipeline.h:78)
     {
@@ -110,6 +112,11 @@ Status Pipeline::Host::set_surface(const std::string& name, const Grid& grid, in
     return s.ok() ? detail::store_surface(grid, band, geom, MemoryLocation::Host, nullptr, &surfaces[(size_t)index]) : s;
 }
 
+// PipelineConfig::polygon_channels: the index, built and kept on the host.
+Status Pipeline::Host::set_polygons(const std::string& name, const PolygonSet& polygons, const PointInPolygonOptions& options) {
+    return detail::store_polygons(cfg, name, polygons, options, false, nullptr, &polygon_sets);
+}
+
 Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     const size_t n = cloud_in.count();
     if (n == 0) return Status::success();                            // pipeline.cpp:284-287
@@ -123,6 +130,10 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     // the reference's checks and messages (pipeline_common.cpp; no device limits on the host)
     if (!surfaces.empty()) {
         Status ok = detail::validate_surfaces(cfg, *cloud, surfaces);
+        if (!ok.ok()) return ok;
+    }
+    if (!polygon_sets.empty()) {
+        Status ok = detail::validate_polygon_channels(cfg, *cloud, polygon_sets);
         if (!ok.ok()) return ok;
     }
     {
@@ -157,6 +168,13 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
         Status ok = detail::sample_host(sf.geom, static_cast<const float*>(sf.band.data()), sf.geom.width, px, py,
                                         sc.value_channel.empty() ? nullptr : cloud->channel_f32(sc.value_channel), n, sc.mode,
                                         out.data(), engine->threads());
+        if (!ok.ok()) return ok;
+    }
+    // Polygon channels, beside them: the host twin of the C-ABI at the same coordinates, so the bits are the HIP engine's.
+    for (size_t k = 0; k < polygon_sets.size(); ++k) {
+        std::vector<float>& out = derived[cfg.polygon_channels[k].name];
+        out.resize(n);
+        Status ok = polygon_sets[k]->locate(px, py, n, out.data(), false, nullptr, engine->threads());
         if (!ok.ok()) return ok;
     }
     auto f32 = [&](const std::string& name) -> const float* {

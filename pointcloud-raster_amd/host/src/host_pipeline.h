@@ -10,6 +10,7 @@
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
+#include "polygons.h"
 #include "sample_grid.h"
 #include "zonal.h"
 
@@ -33,6 +34,7 @@ struct Pipeline::Host {
     std::vector<Output> outputs;
     detail::FilterPlan filters;          // ReductionSpec::filter of every spec, planned at init
     std::vector<detail::Surface> surfaces;   // PipelineConfig::surface_channels, entry by entry: the band in host memory
+    detail::PolygonChannels polygon_sets;    // PipelineConfig::polygon_channels, entry by entry: the index (set_polygons)
     detail::HistogramPlan hist;          // PipelineConfig::histograms, planned at init
     std::vector<std::vector<uint32_t>> cubes;    // entry by entry: count[bins][height * width], zero at create
     detail::ExtremesPlan ext;            // PipelineConfig::extremes, planned at init
@@ -60,6 +62,7 @@ struct Pipeline::Host {
     Status ingest(const PointCloud& cloud);
     Status finalize();
     Status set_surface(const std::string& name, const Grid& grid, int band);
+    Status set_polygons(const std::string& name, const PolygonSet& polygons, const PointInPolygonOptions& options);
     Status set_zones(const std::string& name, const Grid& grid, int band);
     Status set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options);
     Status zonal(int i, ZonalTable* out, bool with_counts) const;

@@ -25,6 +25,7 @@
 #include "las_io.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/point_cloud_io.h"
+#include "polygons.h"
 #include "sample_grid.h"
 
 #include <algorithm>
@@ -43,7 +44,7 @@ thread_local std::string g_create_error;
 std::vector<std::string> named_channels(const PipelineConfig& c) {
     std::vector<std::string> out;
     auto add = [&out, &c](const std::string& name) {
-        if (name.empty() || detail::surface_index(c, name) >= 0) return;
+        if (name.empty() || detail::derived_channel(c, name)) return;
         if (std::find(out.begin(), out.end(), name) == out.end()) out.push_back(name);
     };
     for (const auto& r : c.reductions) {
@@ -127,10 +128,13 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
     {
         const Status ss = detail::plan_surfaces(config);
         if (!ss.ok()) return fail_with(ss);
+        const Status ps = detail::plan_polygon_channels(config);
+        if (!ps.ok()) return fail_with(ps);
     }
     size_t budget = 0;
     if (Banded::needed(config, &budget)) {
         if (!config.surface_channels.empty()) return fail_with(detail::surfaces_out_of_core_error());
+        if (!config.polygon_channels.empty()) return fail_with(detail::polygon_channels_out_of_core_error());
         if (!config.histograms.empty()) return fail_with(detail::histograms_out_of_core_error());
         if (!config.extremes.empty()) return fail_with(detail::extremes_out_of_core_error());
         if (!config.cell_stats.empty()) return fail_with(detail::cell_stats_out_of_core_error());
@@ -289,6 +293,12 @@ Status Pipeline::ingest_las_records(const std::string& path, const LasOptions& o
     if (points_read) *points_read = total;
     return s;
 }
+Status Pipeline::set_polygons(const std::string& name, const PolygonSet& polygons, const PointInPolygonOptions& options) {
+    if (host_) return host_->set_polygons(name, polygons, options);
+    if (banded_) return Status::error(StatusCode::InvalidArgument, "pipeline: set_polygons: '" + name + "' names no polygon channel of this pipeline");
+    return impl_->set_polygons(name, polygons, options);
+}
+
 Status Pipeline::set_surface(const std::string& name, const Grid& grid, int band) {
     if (host_) return host_->set_surface(name, grid, band);
     if (banded_) return Status::error(StatusCode::InvalidArgument, "pipeline: set_surface: '" + name + "' names no surface channel of this pipeline");

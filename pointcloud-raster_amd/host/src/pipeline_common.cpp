@@ -3,6 +3,7 @@
 #include "pipeline_common.h"
 
 #include "buffer.h"
+#include "polygons.h"
 #include "sample_grid.h"
 
 #include "pcr/core/point_cloud.h"
@@ -16,8 +17,9 @@ namespace pcr {
 namespace detail {
 
 Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t max_set, size_t max_predicates) {
-    // (a surface channel is a Float32 channel the pipeline derives itself: validate_surfaces has checked it)
-    auto derived = [&cfg](const std::string& name) { return surface_index(cfg, name) >= 0; };
+    // (a surface or polygon channel is a Float32 channel the pipeline derives itself: validate_surfaces and
+    // validate_polygon_channels have checked it)
+    auto derived = [&cfg](const std::string& name) { return derived_channel(cfg, name); };
     auto check_filter = [&](const FilterSpec& filter) -> Status {
         for (const auto& pr : filter.predicates) {
             if (derived(pr.channel_name)) continue;

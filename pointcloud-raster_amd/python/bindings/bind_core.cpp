@@ -487,6 +487,23 @@ void bind_core(py::module_& m) {
        py::arg("location") = MemoryLocation::Host,
        "A one-band Float32 grid 'label' on grid_config at `location`: per cell the value of the greatest-index polygon that holds the "
        "cell's centre (p + 1, or the set's values), `background` elsewhere");
+    // extension: the exact per-point test (pcr.points_in_polygons)
+    m.def("points_in_polygons", [](PointCloud& cloud, const PolygonSet& polygons, const std::string& channel, float background,
+                                   int index_cols, int index_rows) {
+        PointInPolygonOptions o;
+        o.background = background;
+        o.index_cols = index_cols;
+        o.index_rows = index_rows;
+        Status s;
+        {
+            py::gil_scoped_release nogil;
+            s = points_in_polygons(cloud, polygons, channel, o);
+        }
+        raise_if_error(s);
+    }, py::arg("cloud"), py::arg("polygons"), py::arg("channel") = "polygon",
+       py::arg("background") = std::numeric_limits<float>::quiet_NaN(), py::arg("index_cols") = 0, py::arg("index_rows") = 0,
+       "Adds (or overwrites) the Float32 channel `channel`: per point the value of the greatest-index polygon that holds the point "
+       "(p + 1, or the set's values), `background` elsewhere -- exact, where a label grid sampled Nearest gives the cell's");
     // (tests) what the id band holds for an id: the clamp at 2^24 on its own
     m.def("_tree_id_value", [](int64_t id) { return pcrhip::trees::id_value(id); }, py::arg("id"));
     // (tests, tools) the host twin on an array, which the kernels are compared with; -> (id [h, w], height [h, w], table)

@@ -124,6 +124,18 @@ void bind_engine(py::module_& m) {
         .def_readwrite("value_channel", &SurfaceChannelConfig::value_channel)
         .def_readwrite("mode", &SurfaceChannelConfig::mode);
 
+    py::class_<PolygonChannelConfig>(m, "PolygonChannelConfig",
+                                     "One entry of PipelineConfig.polygon_channels: the Float32 channel `name`, derived at every ingest from "
+                                     "the polygons given with Pipeline.set_polygons -- the value of the polygon that holds the point, exactly")
+        .def(py::init<>())
+        .def(py::init<const PolygonChannelConfig&>())
+        .def(py::init([](const std::string& name) {
+            PolygonChannelConfig c;
+            c.name = name;
+            return c;
+        }), py::arg("name"))
+        .def_readwrite("name", &PolygonChannelConfig::name);
+
     py::class_<HistogramConfig>(m, "HistogramConfig",
                                 "One per-cell histogram of a Float32 channel (a surface channel included) and its percentile bands")
         .def(py::init<>())
@@ -273,6 +285,9 @@ void bind_engine(py::module_& m) {
         .def_readwrite("surface_channels", &PipelineConfig::surface_channels,
                        "Per-point Float32 channels derived at every ingest from a band given with Pipeline.set_surface (assign a "
                        "list of SurfaceChannelConfig): usable wherever a channel is named")
+        .def_readwrite("polygon_channels", &PipelineConfig::polygon_channels,
+                       "Per-point Float32 channels derived at every ingest from polygons given with Pipeline.set_polygons (assign a "
+                       "list of PolygonChannelConfig): the exact per-point test, usable wherever a channel is named")
         .def_readwrite("histograms", &PipelineConfig::histograms,
                        "Per-cell histograms counted at every ingest and the percentile bands finalize() appends behind the "
                        "reductions' bands (assign a list of HistogramConfig)")
@@ -317,6 +332,16 @@ void bind_engine(py::module_& m) {
             raise_if_error(p.set_surface(name, grid, band));
         }, py::arg("name"), py::arg("grid"), py::arg("band") = 0,
              "Gives the surface channel `name` its surface: band `band` of a grid that carries its geometry, copied into the pipeline")
+        .def("set_polygons", [](Pipeline& p, const std::string& name, const PolygonSet& polygons, float background, int index_cols,
+                                int index_rows) {
+            PointInPolygonOptions o;
+            o.background = background;
+            o.index_cols = index_cols;
+            o.index_rows = index_rows;
+            raise_if_error(p.set_polygons(name, polygons, o));
+        }, py::arg("name"), py::arg("polygons"), py::arg("background") = std::numeric_limits<float>::quiet_NaN(),
+             py::arg("index_cols") = 0, py::arg("index_rows") = 0,
+             "Gives the polygon channel `name` its polygons (in the grid's CRS): the index is built and kept by the pipeline")
         .def("histogram", [](const Pipeline& p, int i) {
             std::vector<uint32_t> counts;
             raise_if_error(p.histogram_counts(i, &counts));

@@ -77,9 +77,9 @@ from ._pcr import (  # noqa: E402,F401
     GroundFilterSpec, GroundFilterConfig, ground_filter, ground_filter_levels,
     TerrainProduct, TerrainSpec, TerrainBandConfig, terrain, terrain_light,
     TreeSpec, TreeBandConfig, segment_trees,
-    SampleMode, SurfaceChannelConfig, sample_grid,
+    SampleMode, SurfaceChannelConfig, sample_grid, PolygonChannelConfig,
     HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig, ZonalConfig,
-    PolygonSet, rasterize_polygons,
+    PolygonSet, rasterize_polygons, points_in_polygons,
 )
 from .polygons import read_geojson_polygons  # noqa: E402,F401  (also gives PolygonSet its from_wkt)
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
@@ -183,7 +183,7 @@ __all__ = [
     "GroundFilterSpec", "GroundFilterConfig", "ground_filter", "ground_filter_levels",
     "TerrainProduct", "TerrainSpec", "TerrainBandConfig", "terrain", "terrain_light",
     "TreeSpec", "TreeBandConfig", "segment_trees",
-    "SampleMode", "SurfaceChannelConfig", "sample_grid",
+    "SampleMode", "SurfaceChannelConfig", "sample_grid", "PolygonChannelConfig",
     "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig", "ZonalConfig",
-    "PolygonSet", "rasterize_polygons", "read_geojson_polygons",
+    "PolygonSet", "rasterize_polygons", "points_in_polygons", "read_geojson_polygons",
 ]

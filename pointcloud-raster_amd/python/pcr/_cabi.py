@@ -99,6 +99,16 @@ class RasterizeParams(C.Structure):
         super().__init__(background=background, reserved_=0, events=(C.c_void_p * 3)(*events))
 
 
+class PolygonIndexParams(C.Structure):
+    """pcr_hip_polygon_index_params: NaN background, an automatic index, the default cap."""
+    _fields_ = [("background", C.c_float), ("index_cols", C.c_int32), ("index_rows", C.c_int32), ("reserved_", C.c_int32),
+                ("max_index_bytes", C.c_size_t)]
+
+    def __init__(self, background=float("nan"), index_cols=0, index_rows=0, max_index_bytes=0):
+        super().__init__(background=background, index_cols=index_cols, index_rows=index_rows, reserved_=0,
+                         max_index_bytes=max_index_bytes)
+
+
 class TreeParams(C.Structure):
     """pcr_hip_tree_params with the defaults of pcr.TreeSpec."""
     _fields_ = [("min_height", C.c_float), ("window_base", C.c_float), ("window_slope", C.c_float),
@@ -257,6 +267,12 @@ SYMBOLS = {
     "pcr_hip_rasterize_polygons": [C.POINTER(Grid), _VP, _I64, _VP, _I64, _VP, _I64, _VP, C.POINTER(RasterizeParams), _VP, _I64, _VP,
                                    _SZ, _VP],
     "pcr_hip_rasterize_polygons_host": [C.POINTER(Grid), _VP, _I64, _VP, _I64, _VP, _I64, _VP, C.POINTER(RasterizeParams), _VP, _I64],
+    "pcr_hip_polygon_index_create": [_VP, _I64, _VP, _I64, _VP, _I64, _VP, C.POINTER(PolygonIndexParams), C.POINTER(_VP)],
+    "pcr_hip_polygon_index_destroy": [_VP],
+    "pcr_hip_polygon_index_info": [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_SZ)],
+    "pcr_hip_polygon_index_upload": [_VP, _VP, _SZ, _VP],
+    "pcr_hip_points_in_polygons": [_VP, _VP, _VP, _VP, _U64, _VP, _VP, C.POINTER(_VP)],
+    "pcr_hip_points_in_polygons_host": [_VP, _VP, _VP, _U64, _VP, C.c_int],
 }
 
 _lib = None
