@@ -1035,6 +1035,71 @@ int pcr_hip_points_in_polygons(const pcr_hip_polygon_index* index, const void* d
 int pcr_hip_points_in_polygons_host(const pcr_hip_polygon_index* index, const double* h_x, const double* h_y, uint64_t n, float* h_out,
                                     int threads);
 
+/* ---- point zonal tables: a value channel folded by a per-point LABEL CHANNEL into one row per zone (PipelineConfig::
+ *      point_zonal, Pipeline::point_zonal, pcr.point_zonal) -- lidR's plot_metrics and crown_metrics as what they are, a group-by
+ *      over POINTS: the zonal tables above give a return the zone of its cell, these give it the zone of its own label (a
+ *      polygon channel: exactly the plot that holds it; a Nearest surface channel over a tree_id band; point_source_id: one row
+ *      per flight line).  No reference counterpart.  The arithmetic is written once, in csrc/point_zonal.hpp, which the kernels,
+ *      the host twins and the host engine compile with contraction off.
+ *        zone       of a point: zone_of(label) of the zonal tables above, a whole number in [1, 2^24]; NaN, +-Inf, 0, -0.0,
+ *                   negatives and fractions are no zone.  A table has capacity Z: rows 0 .. Z - 1, row k is zone k + 1.  A zone
+ *                   above Z is never an index; each point with such a zone that its mask keeps adds 1 to info[1].
+ *        accepted   a point whose mask byte is nonzero (or d_mask is NULL), whose zone is in 1..Z and whose value is not NaN
+ *                   (cs::kNoStep, hist::kNoBin).  THE GRID PLAYS NO PART: neither x nor y is read, a point outside any grid
+ *                   but inside a plot counts.
+ *        fold       every counter is 64-bit and wraps modulo 2^64; the caller owns the tables and they ACCUMULATE across calls.
+ *                     points[zone]   uint64, += 1 per point with a nonzero mask byte and a zone in 1..Z, whatever its value
+ *                     n, s1, s2      per accepted point, q = step_of(v, origin, inv_res) of "per-cell stats": n += 1,
+ *                                    s1 += q (int64), s2 += q * q (uint64)
+ *                     counts[zone][bin_of(v, lo, inv_w, bins)] += 1 per accepted point ("per-cell histograms")
+ *                   Integer addition: any order, chunking, path or engine gives the same bits.
+ *        info       two uint64 words the caller owns, accumulated like the tables: info[0] = max(info[0], the greatest zone <= Z
+ *                   that a mask-kept point carried), info[1] += the overflow count.  NULL: not kept.
+ *        rows       pcr_hip_zone_rows_stats and pcr_hip_zone_rows_percentiles as they are; row k is zone k + 1, up to info[0].
+ *      Kernels (csrc/point_zonal.hip), on s, nothing allocated: persistent workgroups of PCR_HIP_POINT_FOLD_BLOCK lanes stride
+ *      over tiles of BLOCK * POINTS_PER_LANE points, TILES_IN_FLIGHT tiles loaded before the first is used; label (4 B), mask
+ *      (1 B) and value (4 B) are each read once, non-temporally, 16 / 4 / 16 bytes wide per lane where label and value start on
+ *      16 bytes and the mask on 4, else element by element.  In a wave neighbouring lanes with one zone (one zone and bin)
+ *      form a run; a segmented scan sums along it and its last lane adds the sums to the row:
+ *        path 1   with 64-bit global atomic adds, nothing returned -- any Z;
+ *        path 2   with LDS atomics into a workgroup-private table (zeroed at the start; a stats row is n << 43 | sum of (q + 2^21),
+ *                 S2, and a 32-bit point count -- PCR_HIP_POINT_FOLD_STATS_ROW_BYTES; a histogram row is bins 32-bit counters),
+ *                 whose nonzero entries are added to HBM at the end of the workgroup's sweep and after every 2^20 points it has
+ *                 read, which bounds the packed and 32-bit fields.  An argument error when Z rows exceed
+ *                 PCR_HIP_POINT_FOLD_LDS_BYTES;
+ *        path 0   path 2 where it fits, else path 1.
+ *      blocks: 0, or the number of workgroups (for timing); never more than there are trips.  info costs one wave reduction and
+ *      at most one atomic max and one atomic add per workgroup.  d_value, d_zn, d_zs1 and d_zs2 may ALL be null: `points` only.
+ *      pcr_hip_point_fold_plan answers what a call would launch: the path taken, the workgroups, the LDS bytes per workgroup.
+ *      _host: one thread, one add per point.  Argument errors -- a null pointer, bins outside 1..256, Z outside 1..2^24, a
+ *      non-finite or non-positive constant, a path outside 0..2 or one that does not fit, blocks outside 0..65536, more than 2^40
+ *      points, tables that overlap each other or an input -- are reported before any HIP call.  n == 0 changes nothing. */
+#define PCR_HIP_POINT_FOLD_BLOCK 256
+#define PCR_HIP_POINT_FOLD_POINTS_PER_LANE 4
+#define PCR_HIP_POINT_FOLD_TILES_IN_FLIGHT 4
+#define PCR_HIP_POINT_FOLD_LDS_BYTES 61440
+#define PCR_HIP_POINT_FOLD_STATS_ROW_BYTES 20
+#define PCR_HIP_POINT_FOLD_BLOCKS_PER_CU_GLOBAL 8
+#define PCR_HIP_POINT_FOLD_BLOCKS_PER_CU_LDS 4
+typedef struct pcr_hip_point_fold_params {
+    int32_t path;                    /* 0 auto, 1 global atomics, 2 a workgroup-private table in LDS */
+    int32_t blocks;                  /* 0: by path and CU count; else the persistent workgroups to launch */
+} pcr_hip_point_fold_params;
+int pcr_hip_point_fold_plan(uint32_t Z, int bins, uint64_t n, const pcr_hip_point_fold_params* params, int* path, int* blocks,
+                            size_t* lds_bytes);
+int pcr_hip_point_fold_stats(const float* d_label, const uint8_t* d_mask, const float* d_value, uint64_t n, double origin, double inv_res,
+                             uint32_t Z, const pcr_hip_point_fold_params* params, unsigned long long* d_points, unsigned long long* d_zn,
+                             long long* d_zs1, unsigned long long* d_zs2, unsigned long long* d_info, pcr_hip_stream s);
+int pcr_hip_point_fold_stats_host(const float* h_label, const uint8_t* h_mask, const float* h_value, uint64_t n, double origin,
+                                  double inv_res, uint32_t Z, const pcr_hip_point_fold_params* params, unsigned long long* h_points,
+                                  unsigned long long* h_zn, long long* h_zs1, unsigned long long* h_zs2, unsigned long long* h_info);
+int pcr_hip_point_fold_hist(const float* d_label, const uint8_t* d_mask, const float* d_value, uint64_t n, int bins, double lo, double inv_w,
+                            uint32_t Z, const pcr_hip_point_fold_params* params, unsigned long long* d_zcounts, unsigned long long* d_info,
+                            pcr_hip_stream s);
+int pcr_hip_point_fold_hist_host(const float* h_label, const uint8_t* h_mask, const float* h_value, uint64_t n, int bins, double lo,
+                                 double inv_w, uint32_t Z, const pcr_hip_point_fold_params* params, unsigned long long* h_zcounts,
+                                 unsigned long long* h_info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,7 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "csrc", "extremes.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "cell_stats.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "zonal.hpp"))
+    hdrs.append(os.path.join(HERE, "csrc", "point_zonal.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "rasterize.hpp"))
     for d in src_dirs:                                   # the internal headers next to the sources
         hdrs += [os.path.join(d, f) for f in os.listdir(d) if f.endswith(".h")]

@@ -216,6 +216,39 @@ struct ZonalTable {
     size_t size() const { return zone.size(); }
 };
 
+/// One entry of PipelineConfig::point_zonal: a table with one row per zone of a per-point LABEL CHANNEL -- the returns of each plot
+/// (a polygon channel: exactly those inside it), of each tree (a Nearest surface channel over a tree_id band), of each flight line
+/// (`point_source_id`) or class (`classification`) -- folded at every ingest: lidR's plot_metrics and crown_metrics as a group-by
+/// over POINTS, where PipelineConfig::zonal gives a return the zone of its cell.  The contract (include/pcr_hip.h, "point zonal
+/// tables"; csrc/point_zonal.hpp):
+///   zone       of a point: the label when it is a whole number in [1, 2^24], else none (NaN, +-Inf, 0, negatives, 2.5).  The
+///              table has max_zones rows of state; a kept point with a greater zone is counted as overflow and makes
+///              Pipeline::point_zonal answer OutOfRange.
+///   accepted   a point that PipelineConfig::filter AND the spec's filter keep, whose zone is in 1..max_zones and whose value is
+///              not NaN.  THE GRID PLAYS NO PART: x and y are not read, a point outside the grid but inside a plot counts.
+///   fold       64-bit integers modulo 2^64, accumulated over every ingest: points per zone (PipelineConfig::filter's survivors,
+///              whatever their value), per stats spec n, the sum of the steps and of their squares (CellStatsConfig's step), per
+///              histogram the counts of HistogramConfig's bins.
+///   rows       ZonalConfig's: the same columns from the same arithmetic, up to the greatest zone a point carried.
+/// The specs are OWNED: their value_channel, origin, resolution and ddof, or lo, hi, bins and percentiles, and their filter mean
+/// what they mean per cell, but no per-cell plane is allocated for them and products and band_names are not read.  Both engines
+/// give the same bits for any order, chunking or number of ingests.
+struct PointZonalConfig {
+    std::string label_channel;           // any Float32 channel: a polygon channel, a surface channel, or the cloud's own
+    std::vector<CellStatsConfig> cell_stats;     // at most 4
+    std::vector<HistogramConfig> histograms;     // at most 4
+    int max_zones = 1 << 16;             // 1..2^24: the rows of state kept
+};
+
+/// Pipeline::point_zonal's table: rows 0 .. size() - 1 are zones 1 .. size(), the columns ZonalTable's with `points` for `cells`.
+struct PointZonalTable {
+    std::vector<int32_t> zone;
+    std::vector<int64_t> points;
+    std::vector<ZonalTable::StatColumns> stats;
+    std::vector<ZonalTable::HistColumns> hists;
+    size_t size() const { return zone.size(); }
+};
+
 struct PipelineConfig {
     GridConfig grid;
     std::vector<ReductionSpec> reductions;
@@ -366,6 +399,17 @@ struct PipelineConfig {
     // column name that appears twice, max_zones outside 1..2^24, a row-block shard and a pipeline that has to run out of core.
     // Empty: nothing is allocated, launched or validated differently.
     std::vector<ZonalConfig> zonal;
+    // Point zonal tables (PointZonalConfig): at every ingest, and every chunk of ingest_file, each entry's specs are folded by its
+    // label channel into one row per zone, after the derived channels and the filter classes -- on the HIP engine in HBM on the
+    // pipeline's stream, max_zones * (8 + 24 * stats + 8 * sum of bins) bytes per entry that are allocated at create and count
+    // towards gpu_memory_budget; only the table crosses PCIe.  The grid plays no part: a point outside it counts.
+    // Pipeline::point_zonal(i) reads the table at any time; finalize() neither needs nor changes it.  Each spec's filter joins the
+    // plan of the ReductionSpec filters and counts against its limits.  ingest_file decodes a LAS channel that only an entry here
+    // names.  create() refuses more than 4 entries, more than 4 stats specs or 4 histograms in one, an empty label_channel, a
+    // column name that appears twice, max_zones outside 1..2^24, what PipelineConfig::cell_stats and ::histograms refuse about a
+    // spec's own fields, a row-block shard and a pipeline that has to run out of core; save_state, load_state and resume answer
+    // NotImplemented while the list is non-empty.  Empty: nothing is allocated, launched or validated differently.
+    std::vector<PointZonalConfig> point_zonal;
 };
 
 struct ProgressInfo {
@@ -455,6 +499,12 @@ public:
     /// an external grid that was not set; OutOfRange for a zone above the entry's max_zones.  with_counts: also copy out every
     /// histogram's [zone][bin] counts (HistColumns::counts; zones x bins x 8 bytes each), which are left empty otherwise.
     Status zonal(int i, ZonalTable* out, bool with_counts = false) const;
+    /// Extension: the table of PipelineConfig::point_zonal[i] as the ingests so far left it -- valid after any ingest (no row before
+    /// the first), finalize() is not needed and does not change it.  On the HIP engine the rows are made in HBM behind everything
+    /// on the pipeline's stream, which is waited for once for the info words and once for the table.  InvalidArgument for an
+    /// index outside the list; OutOfRange while the overflow counter is nonzero (a kept point carried a zone above max_zones).
+    /// with_counts: also copy out every histogram's [zone][bin] counts.
+    Status point_zonal(int i, PointZonalTable* out, bool with_counts = false) const;
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
     /// the finalize kernels are only ENQUEUED on the pipeline's stream -- result() is valid at once, its bands are complete
@@ -538,6 +588,12 @@ private:
     std::unique_ptr<Banded> banded_;
     std::unique_ptr<Host> host_;
 };
+
+/// Extension: PointZonalConfig for any cloud, where it lives: a Device cloud is folded in HBM by the kernels (on the default stream,
+/// which is waited for), a Host or HostPinned cloud by the host twins; the same bits either way.  No filter is applied: a spec
+/// with a non-empty filter is InvalidArgument (filters are a pipeline's).  What Pipeline::create refuses about an entry is
+/// InvalidArgument here, a missing or non-Float32 channel too; OutOfRange for a zone above max_zones.
+Status point_zonal(const PointCloud& cloud, const PointZonalConfig& config, PointZonalTable* out, bool with_counts = false);
 
 // Why the last Pipeline::create() on this thread returned nullptr.
 const std::string& pipeline_create_error();

@@ -33,7 +33,8 @@ bool Pipeline::Banded::needed(const PipelineConfig& config, size_t* budget) {
         size_t free_mem = 0, total_mem = 0;
         if (cuda_get_memory_info(&free_mem, &total_mem, config.cuda_device_id)) *budget = (size_t)(free_mem * 0.8);
     }
-    return *budget > 0 && bytes_per_row(config) * (size_t)g.height > *budget;
+    // (PipelineConfig::point_zonal: its tables are state in HBM too, whatever the grid's size)
+    return *budget > 0 && bytes_per_row(config) * (size_t)g.height + detail::point_zonal_state_bytes(config) > *budget;
 }
 
 std::unique_ptr<Pipeline::Banded> Pipeline::Banded::create(const PipelineConfig& config, const Pipeline* owner, size_t budget, Status* st) {

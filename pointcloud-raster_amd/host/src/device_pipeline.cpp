@@ -33,6 +33,7 @@ Pipeline::Impl::~Impl() {
     d_ground_work.release();
     d_tree_work.clear();
     zone_grids.clear();
+    pz_state.tables.clear();
     staging.clear();
     result.reset();
     if (own_stream && stream) pcr_hip_stream_destroy(stream);
@@ -50,6 +51,7 @@ Status Pipeline::Impl::init() {
         if (ok.ok()) ok = detail::check_extremes(cfg);
         if (ok.ok()) ok = detail::check_cell_stats(cfg);
         if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
+        if (ok.ok()) ok = detail::plan_point_zonal(cfg, filters, &pz_plan);
         if (!ok.ok()) return ok;
     }
 
@@ -210,6 +212,7 @@ Status Pipeline::Impl::init() {
             if (!(s = detail::hip_status(pcr_hip_memset(bufs[k]->data(), 0, bytes[k], stream))).ok()) return s;
         }
     }
+    if (!(s = pz_state.allocate(pz_plan, MemoryLocation::Device, stream)).ok()) return s;     // PipelineConfig::point_zonal: all zero
     if (!outputs.empty() && !(s = allocate_result()).ok()) return s;
     if (!(s = d_bands_done.allocate(std::max<size_t>(groups.size(), 1) * sizeof(uint32_t), MemoryLocation::HostPinned)).ok()) return s;
     std::memset(d_bands_done.data(), 0, d_bands_done.bytes());
@@ -1063,6 +1066,27 @@ Status Pipeline::Impl::scatter_cell_stats(Ingest& in) {
     return Status::success();
 }
 
+// PipelineConfig::point_zonal: every entry's specs folded by its label channel, on the pipeline's stream under the class masks of
+// the filter stage.  No coordinate is read, no plane, flag or band touched: no part in the plane-state rules.
+Status Pipeline::Impl::fold_point_zonal(Ingest& in) {
+    if (!pz_plan.on()) return Status::success();
+    detail::PointZonalInputs pin;
+    pin.device = true;
+    pin.stream = stream;
+    pin.n = in.n;
+    pin.channel = in.channel;
+    pin.mask = [&in](int cls) { return in.class_mask[(size_t)cls]; };
+    return detail::point_zonal_fold(pz_plan, pz_state, pin);
+}
+
+// Entry i's rows, made in HBM behind everything on the pipeline's stream.
+Status Pipeline::Impl::point_zonal(int i, PointZonalTable* out, bool with_counts) {
+    if (!out || i < 0 || (size_t)i >= pz_plan.entries.size())
+        return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal: no point_zonal entry " + std::to_string(i));
+    DeviceScope dev(cfg.cuda_device_id);
+    return detail::point_zonal_table(pz_plan.entries[(size_t)i], pz_state.tables[(size_t)i], stream, with_counts, out);
+}
+
 Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     Ingest in{cloud, cloud.count()};
     if (in.n == 0) return Status::success();
@@ -1071,6 +1095,7 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     Status s = surfaces.empty() ? Status::success() : detail::validate_surfaces(cfg, cloud, surfaces);
     if (s.ok() && !polygon_sets.empty()) s = detail::validate_polygon_channels(cfg, cloud, polygon_sets);
     if (s.ok()) s = detail::validate_cloud(cfg, cloud, PCR_HIP_MAX_FILTER_SET, PCR_HIP_MAX_FILTER_PREDICATES);
+    if (s.ok() && pz_plan.on()) s = detail::validate_point_zonal(cfg, cloud);
     detail::Reprojection rp;
     if (s.ok()) s = detail::plan_reprojection(cfg, cloud, &rp);
     if (!s.ok()) return s;
@@ -1103,6 +1128,7 @@ Status Pipeline::Impl::ingest(const PointCloud& cloud, bool wait) {
     if (!(s = scatter_histograms(in)).ok()) return s;
     if (!(s = scatter_extremes(in)).ok()) return s;
     if (!(s = scatter_cell_stats(in)).ok()) return s;
+    if (!(s = fold_point_zonal(in)).ok()) return s;
     // host arrays may be reused by the caller as soon as we return (ingest_async: page-locked arrays are
     // read by the DMA engine later, the caller keeps them alive until synchronize())
     const MemoryLocation loc = cloud.location();
@@ -1381,6 +1407,7 @@ Status Pipeline::Impl::save_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
     if (!cfg.cell_stats.empty()) return detail::cell_stats_checkpoint_error();
+    if (!cfg.point_zonal.empty()) return detail::point_zonal_checkpoint_error();
     std::string dir;
     Status s = checkpoint_dir(dir_in, &dir, true);
     if (!s.ok()) return s;
@@ -1394,6 +1421,7 @@ Status Pipeline::Impl::load_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
     if (!cfg.cell_stats.empty()) return detail::cell_stats_checkpoint_error();
+    if (!cfg.point_zonal.empty()) return detail::point_zonal_checkpoint_error();
     std::string dir;
     Status s = checkpoint_dir(dir_in, &dir, false);
     if (!s.ok()) return s;

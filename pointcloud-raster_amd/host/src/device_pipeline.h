@@ -11,6 +11,7 @@
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
+#include "point_zonal.h"
 #include "polygons.h"
 #include "sample_grid.h"
 #include "terrain.h"
@@ -107,6 +108,9 @@ struct Pipeline::Impl {
     detail::ZonalPlan zonal_plan;            // PipelineConfig::zonal, planned at init
     std::map<std::string, detail::ZoneGrid> zone_grids;   // the label grids of set_zones, by name, in HBM
     bool zonal_fresh = false;                // the last finalize's bands and the planes belong together: no ingest since
+    detail::PointZonalPlan pz_plan;          // PipelineConfig::point_zonal, planned at init
+    detail::PointZonalState pz_state;        // its tables in HBM, zeroed at create and only ever added to, at every ingest: no part
+                                             // in the plane-state rules
     detail::FilterPlan filters;              // PipelineConfig::filter (class 0) and every ReductionSpec::filter, planned at init
     detail::HistogramPlan hist;              // PipelineConfig::histograms, planned at init
     std::vector<detail::Buffer> cubes;       // entry by entry: count[bins][state_rows * width] in HBM, zeroed at create and only
@@ -196,6 +200,7 @@ struct Pipeline::Impl {
     Status set_zones(const std::string& name, const Grid& grid, int band);
     Status set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options);
     Status zonal(int i, ZonalTable* out, bool with_counts);
+    Status point_zonal(int i, PointZonalTable* out, bool with_counts);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
     bool offer_bands(size_t gi);
     Status unpack_select(Group& gr);
@@ -219,6 +224,7 @@ struct Pipeline::Impl {
     Status scatter_histograms(Ingest& in);
     Status scatter_extremes(Ingest& in);
     Status scatter_cell_stats(Ingest& in);
+    Status fold_point_zonal(Ingest& in);
     Status marshal_glyph(const GlyphSpec& gl, const detail::ChannelLookup& channel, pcr_hip_glyph* out) const;
     Status allocate_result();
     Status checkpoint_dir(const std::string& dir_in, std::string* dir, bool writing) const;

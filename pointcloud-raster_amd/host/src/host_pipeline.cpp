@@ -25,6 +25,8 @@ Status Pipeline::Host::init() {
         if (ok.ok()) ok = detail::check_extremes(cfg);
         if (ok.ok()) ok = detail::check_cell_stats(cfg);
         if (ok.ok()) ok = detail::plan_filters(cfg, &filters);
+        if (ok.ok()) ok = detail::plan_point_zonal(cfg, filters, &pz_plan);
+        if (ok.ok()) ok = pz_state.allocate(pz_plan, MemoryLocation::Host, nullptr);
         if (!ok.ok()) return ok;
     }
     if (cfg.shard_row_begin >= 0 || cfg.shard_row_end >= 0)
@@ -104,6 +106,13 @@ Status Pipeline::Host::zonal(int i, ZonalTable* out, bool with_counts) const {
     return detail::zonal_table(e, cstats, hist, in, with_counts, out);
 }
 
+// PipelineConfig::point_zonal: entry i's rows through the C-ABI's host twins, from the tables as the ingests left them.
+Status Pipeline::Host::point_zonal(int i, PointZonalTable* out, bool with_counts) const {
+    if (!out || i < 0 || (size_t)i >= pz_plan.entries.size())
+        return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal: no point_zonal entry " + std::to_string(i));
+    return detail::point_zonal_table(pz_plan.entries[(size_t)i], pz_state.tables[(size_t)i], nullptr, with_counts, out);
+}
+
 // PipelineConfig::surface_channels: the band and its geometry into host memory the pipeline owns.
 Status Pipeline::Host::set_surface(const std::string& name, const Grid& grid, int band) {
     int index = -1;
@@ -138,6 +147,7 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
     }
     {
         Status ok = detail::validate_cloud(cfg, *cloud, 0, 0);
+        if (ok.ok() && pz_plan.on()) ok = detail::validate_point_zonal(cfg, *cloud);
         if (!ok.ok()) return ok;
     }
     // a cloud in another CRS than the grid's: its coordinates transformed into host vectors (the cloud stays as it is)
@@ -278,6 +288,26 @@ Status Pipeline::Host::ingest(const PointCloud& cloud_in) {
             engine->scatter_cell_stats(p.n.data(), p.s1.data(), p.s2.data(), e.origin, e.inv_res, f32(e.value_channel) + i0, stat_keep(e, i0));
         }
     }
+    if (pz_plan.on()) {
+        // PipelineConfig::point_zonal: the twins on the same masks as the device's classes -- PipelineConfig::filter AND the class's
+        // own, made once per class that an entry uses.  The grid plays no part: all n points, routed or not.
+        std::vector<std::vector<uint8_t>> both(filters.classes.size());
+        detail::PointZonalInputs in;
+        in.n = n;
+        in.channel = [&](const std::string& name, const float** p) { *p = f32(name); return Status::success(); };
+        in.mask = [&](int cls) -> const uint8_t* {
+            if (cls == 0) return keep.empty() ? nullptr : keep.data();
+            if (keep.empty()) return class_keep[(size_t)cls].data();
+            std::vector<uint8_t>& m = both[(size_t)cls];
+            if (m.empty()) {
+                m.resize(n);
+                for (size_t i = 0; i < n; ++i) m[i] = keep[i] & class_keep[(size_t)cls][i];
+            }
+            return m.data();
+        };
+        Status ok = detail::point_zonal_fold(pz_plan, pz_state, in);
+        if (!ok.ok()) return ok;
+    }
     last = ScatterInfo{};
     last.path = -1;                                                  // neither of the device's scatter paths
     last.points_in = n;
@@ -356,6 +386,7 @@ Status Pipeline::Host::save_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
     if (!cfg.cell_stats.empty()) return detail::cell_stats_checkpoint_error();
+    if (!cfg.point_zonal.empty()) return detail::point_zonal_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     detail::StateWindow w;
@@ -369,6 +400,7 @@ Status Pipeline::Host::load_state(const std::string& dir_in) {
     if (!cfg.histograms.empty()) return detail::histograms_checkpoint_error();
     if (!cfg.extremes.empty()) return detail::extremes_checkpoint_error();
     if (!cfg.cell_stats.empty()) return detail::cell_stats_checkpoint_error();
+    if (!cfg.point_zonal.empty()) return detail::point_zonal_checkpoint_error();
     const std::string dir = dir_in.empty() ? cfg.state_dir : dir_in;
     if (dir.empty()) return Status::error(StatusCode::InvalidArgument, "pipeline: no state directory given");
     detail::StateWindow w;

@@ -10,6 +10,7 @@
 #include "pcr/core/grid.h"
 #include "pcr/engine/pipeline.h"
 #include "pipeline_common.h"
+#include "point_zonal.h"
 #include "polygons.h"
 #include "sample_grid.h"
 #include "zonal.h"
@@ -53,6 +54,8 @@ struct Pipeline::Host {
     detail::ZonalPlan zonal_plan;            // PipelineConfig::zonal, planned at init
     std::map<std::string, detail::ZoneGrid> zone_grids;   // the label grids of set_zones, by name, in host memory
     bool zonal_fresh = false;                // the last finalize's bands and the planes belong together: no ingest since
+    detail::PointZonalPlan pz_plan;          // PipelineConfig::point_zonal, planned at init
+    detail::PointZonalState pz_state;        // its tables in host memory, zero at create, added to by every ingest
     ProgressCallback callback;
     size_t collections = 0, points = 0;
     ScatterInfo last{};
@@ -66,6 +69,7 @@ struct Pipeline::Host {
     Status set_zones(const std::string& name, const Grid& grid, int band);
     Status set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options);
     Status zonal(int i, ZonalTable* out, bool with_counts) const;
+    Status point_zonal(int i, PointZonalTable* out, bool with_counts) const;
     Status save_state(const std::string& dir);
     Status load_state(const std::string& dir);
     ProgressInfo stats() const;

@@ -25,6 +25,7 @@
 #include "las_io.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/point_cloud_io.h"
+#include "point_zonal.h"
 #include "polygons.h"
 #include "sample_grid.h"
 
@@ -70,6 +71,17 @@ std::vector<std::string> named_channels(const PipelineConfig& c) {
     for (const auto& s : c.cell_stats) {
         add(s.value_channel);
         for (const auto& p : s.filter.predicates) add(p.channel_name);
+    }
+    for (const auto& z : c.point_zonal) {                    // (a LAS channel that only a point-zonal entry names is decoded too)
+        add(z.label_channel);
+        for (const auto& s : z.cell_stats) {
+            add(s.value_channel);
+            for (const auto& p : s.filter.predicates) add(p.channel_name);
+        }
+        for (const auto& h : z.histograms) {
+            add(h.value_channel);
+            for (const auto& p : h.filter.predicates) add(p.channel_name);
+        }
     }
     for (const auto& sc : c.surface_channels) add(sc.value_channel);
     return out;
@@ -126,6 +138,13 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
         if (!zs.ok()) return fail_with(zs);
     }
     {
+        detail::FilterPlan filters;                   // (every engine plans again for itself: here only the refusals)
+        detail::PointZonalPlan pz;
+        Status zs = detail::plan_filters(config, &filters);
+        if (zs.ok()) zs = detail::plan_point_zonal(config, filters, &pz);
+        if (!zs.ok()) return fail_with(zs);
+    }
+    {
         const Status ss = detail::plan_surfaces(config);
         if (!ss.ok()) return fail_with(ss);
         const Status ps = detail::plan_polygon_channels(config);
@@ -133,6 +152,7 @@ std::unique_ptr<Pipeline> Pipeline::create(const PipelineConfig& config) {
     }
     size_t budget = 0;
     if (Banded::needed(config, &budget)) {
+        if (!config.point_zonal.empty()) return fail_with(detail::point_zonal_out_of_core_error());     // (its tables count: first)
         if (!config.surface_channels.empty()) return fail_with(detail::surfaces_out_of_core_error());
         if (!config.polygon_channels.empty()) return fail_with(detail::polygon_channels_out_of_core_error());
         if (!config.histograms.empty()) return fail_with(detail::histograms_out_of_core_error());
@@ -382,6 +402,11 @@ Status Pipeline::zonal(int i, ZonalTable* out, bool with_counts) const {
     if (impl_) return impl_->zonal(i, out, with_counts);
     if (host_) return host_->zonal(i, out, with_counts);
     return Status::error(StatusCode::InvalidArgument, "pipeline: zonal: no zonal entry " + std::to_string(i) + " (of a finalize with no ingest since)");
+}
+Status Pipeline::point_zonal(int i, PointZonalTable* out, bool with_counts) const {
+    if (impl_) return impl_->point_zonal(i, out, with_counts);
+    if (host_) return host_->point_zonal(i, out, with_counts);
+    return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal: no point_zonal entry " + std::to_string(i));
 }
 Status Pipeline::finalize() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(); }
 Status Pipeline::finalize_async() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(false); }

@@ -67,6 +67,12 @@ Status validate_cloud(const PipelineConfig& cfg, const PointCloud& cloud, size_t
         if (!d || d->dtype != DataType::Float32)
             return Status::error(StatusCode::InvalidArgument, "pipeline: cell_stats value channel must be Float32");
     }
+    for (const auto& z : cfg.point_zonal) {                    // PipelineConfig::point_zonal: its specs' filters likewise (the channels:
+        for (const auto& c : z.cell_stats)                     // validate_point_zonal)
+            if (!(fs = check_filter(c.filter)).ok()) return fs;
+        for (const auto& h : z.histograms)
+            if (!(fs = check_filter(h.filter)).ok()) return fs;
+    }
     for (const auto& r : cfg.reductions) {
         if (!derived(r.value_channel)) {
             if (!cloud.channel_data(r.value_channel))
@@ -108,6 +114,12 @@ Status plan_filters(const PipelineConfig& cfg, FilterPlan* out) {
     for (const auto& h : cfg.histograms) out->hist_class_of.push_back(class_for(h.filter));   // (a histogram's filter is one more class)
     for (const auto& e : cfg.extremes) out->ext_class_of.push_back(class_for(e.filter));      // (and so is an extremes entry's)
     for (const auto& c : cfg.cell_stats) out->stat_class_of.push_back(class_for(c.filter));   // (and a cell-stats entry's)
+    for (const auto& z : cfg.point_zonal) {                                                   // (and every spec's of a point-zonal entry)
+        out->pz_stat_class_of.emplace_back();
+        out->pz_hist_class_of.emplace_back();
+        for (const auto& c : z.cell_stats) out->pz_stat_class_of.back().push_back(class_for(c.filter));
+        for (const auto& h : z.histograms) out->pz_hist_class_of.back().push_back(class_for(h.filter));
+    }
     if (out->classes.size() - 1 > kMaxSpecFilters)
         return Status::error(StatusCode::InvalidArgument, "pipeline: more than " + std::to_string(kMaxSpecFilters) +
                                                           " distinct reduction filters in one pipeline");

@@ -249,6 +249,7 @@ struct FilterPlan {
     std::vector<int> hist_class_of;          // per entry of PipelineConfig::histograms: its filter joins the same plan
     std::vector<int> ext_class_of;           // per entry of PipelineConfig::extremes: likewise
     std::vector<int> stat_class_of;          // per entry of PipelineConfig::cell_stats: likewise
+    std::vector<std::vector<int>> pz_stat_class_of, pz_hist_class_of;   // per entry of PipelineConfig::point_zonal, per spec: likewise
     std::vector<FilterPredicate> table;      // PipelineConfig::filter's predicates first
     std::vector<uint32_t> words;             // per class; words[0] == 0: no PipelineConfig::filter
     bool any() const { return classes.size() > 1; }

@@ -12,6 +12,35 @@
 
 using namespace pcr;
 
+namespace {
+
+// Pipeline.point_zonal's and pcr.point_zonal's dict: Pipeline.zonal's columns with `points` for `cells`.
+py::dict point_zonal_dict(const PointZonalTable& t) {
+    auto column = [](const auto& v) {
+        using T = typename std::decay_t<decltype(v)>::value_type;
+        py::array_t<T> a((py::ssize_t)v.size());
+        if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
+        return a;
+    };
+    py::dict d;
+    d["zone"] = column(t.zone);
+    d["points"] = column(t.points);
+    for (const auto& c : t.stats) {
+        d[py::str(c.channel + "_n")] = column(c.n);
+        d[py::str(c.channel + "_mean")] = column(c.mean);
+        d[py::str(c.channel + "_var")] = column(c.var);
+        d[py::str(c.channel + "_std")] = column(c.stddev);
+    }
+    for (const auto& c : t.hists) {
+        d[py::str(c.channel + "_hist_n")] = column(c.hist_n);
+        for (size_t j = 0; j < c.q.size(); ++j)
+            d[py::str(c.channel + "_p" + std::to_string(std::lround((double)c.q[j] * 100.0)))] = column(c.p[j]);
+    }
+    return d;
+}
+
+}  // namespace
+
 void bind_engine(py::module_& m) {
     py::enum_<ExecutionMode>(m, "ExecutionMode")
         .value("CPU", ExecutionMode::CPU).value("GPU", ExecutionMode::GPU)
@@ -246,6 +275,47 @@ void bind_engine(py::module_& m) {
         }, "None: every chosen histogram with its entry's own percentile list")
         .def_readwrite("max_zones", &ZonalConfig::max_zones);
 
+    py::class_<PointZonalConfig>(m, "PointZonalConfig",
+                                 "One table with a row per zone of a per-point label channel -- a polygon channel, a surface channel "
+                                 "or the cloud's own -- of its own CellStatsConfig and HistogramConfig specs, folded at every ingest "
+                                 "(Pipeline.point_zonal, pcr.point_zonal); the grid plays no part")
+        .def(py::init<>())
+        .def(py::init<const PointZonalConfig&>())
+        .def(py::init([](const std::string& label_channel, const std::vector<CellStatsConfig>& cell_stats,
+                         const std::vector<HistogramConfig>& histograms, int max_zones) {
+            PointZonalConfig c;
+            c.label_channel = label_channel;
+            c.cell_stats = cell_stats;
+            c.histograms = histograms;
+            c.max_zones = max_zones;
+            return c;
+        }), py::arg("label_channel"), py::arg("cell_stats") = std::vector<CellStatsConfig>{},
+            py::arg("histograms") = std::vector<HistogramConfig>{}, py::arg("max_zones") = 1 << 16)
+        .def_readwrite("label_channel", &PointZonalConfig::label_channel)
+        .def_readwrite("cell_stats", &PointZonalConfig::cell_stats)
+        .def_readwrite("histograms", &PointZonalConfig::histograms)
+        .def_readwrite("max_zones", &PointZonalConfig::max_zones);
+
+    m.def("point_zonal", [](const PointCloud& cloud, const std::string& label_channel, const std::vector<CellStatsConfig>& cell_stats,
+                            const std::vector<HistogramConfig>& histograms, int max_zones) {
+        PointZonalConfig c;
+        c.label_channel = label_channel;
+        c.cell_stats = cell_stats;
+        c.histograms = histograms;
+        c.max_zones = max_zones;
+        PointZonalTable t;
+        Status s;
+        {
+            py::gil_scoped_release release;
+            s = point_zonal(cloud, c, &t);
+        }
+        raise_if_error(s);
+        return point_zonal_dict(t);
+    }, py::arg("cloud"), py::arg("label_channel"), py::arg("cell_stats") = std::vector<CellStatsConfig>{},
+       py::arg("histograms") = std::vector<HistogramConfig>{}, py::arg("max_zones") = 1 << 16,
+          "PointZonalConfig's table for any cloud, where it lives: a Device cloud is folded in HBM, a Host cloud by the host twins; "
+          "the same bits either way.  Spec filters are a pipeline's and are refused here");
+
     py::class_<PipelineConfig>(m, "PipelineConfig")
         .def(py::init<>())
         .def_readwrite("grid", &PipelineConfig::grid)
@@ -299,7 +369,10 @@ void bind_engine(py::module_& m) {
                        "behind the extremes' bands (assign a list of CellStatsConfig)")
         .def_readwrite("zonal", &PipelineConfig::zonal,
                        "Zonal tables: Pipeline.zonal(i) folds the chosen cell_stats planes and histogram cubes by a label band into "
-                       "one row per zone (assign a list of ZonalConfig); nothing happens at ingest or in finalize()");
+                       "one row per zone (assign a list of ZonalConfig); nothing happens at ingest or in finalize()")
+        .def_readwrite("point_zonal", &PipelineConfig::point_zonal,
+                       "Point zonal tables: every ingest folds each entry's specs by its per-point label channel into one row per zone "
+                       "(assign a list of PointZonalConfig); Pipeline.point_zonal(i) reads the table at any time");
 
     py::class_<ProgressInfo>(m, "ProgressInfo")
         .def(py::init<>())
@@ -440,6 +513,24 @@ void bind_engine(py::module_& m) {
             return a;
         }, py::arg("i") = 0, py::arg("h") = 0,
              "The (zones, bins) uint64 counts of the h-th histogram chosen by zonal entry i")
+        .def("point_zonal", [](const Pipeline& p, int i) {
+            PointZonalTable t;
+            raise_if_error(p.point_zonal(i, &t));
+            return point_zonal_dict(t);
+        }, py::arg("i") = 0,
+             "The table of point_zonal entry i as a dict of numpy arrays: zone (int32), points (int64), per stats spec {channel}_n "
+             "(uint64), _mean, _var, _std (float32), per histogram {channel}_hist_n (uint64) and {channel}_p{round(q*100)} (float32); "
+             "row k is zone k + 1.  Valid after any ingest; finalize() is not needed and does not change it")
+        .def("point_zonal_histogram", [](const Pipeline& p, int i, int h) {
+            PointZonalTable t;
+            raise_if_error(p.point_zonal(i, &t, true));
+            if (h < 0 || (size_t)h >= t.hists.size())
+                throw std::runtime_error("pipeline: point_zonal_histogram: no histogram " + std::to_string(h) + " in the entry");
+            const auto& c = t.hists[(size_t)h];
+            py::array_t<uint64_t> a({(py::ssize_t)t.size(), (py::ssize_t)c.bins});
+            if (!c.counts.empty()) std::memcpy(a.mutable_data(), c.counts.data(), c.counts.size() * sizeof(uint64_t));
+            return a;
+        }, py::arg("i") = 0, py::arg("h") = 0, "The (zones, bins) uint64 counts of the h-th histogram of point_zonal entry i")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },
              "Device-resident result: the finalize kernels are only enqueued on the pipeline's stream (complete after synchronize()); "

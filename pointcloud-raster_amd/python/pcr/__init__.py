@@ -78,7 +78,7 @@ from ._pcr import (  # noqa: E402,F401
     TerrainProduct, TerrainSpec, TerrainBandConfig, terrain, terrain_light,
     TreeSpec, TreeBandConfig, segment_trees,
     SampleMode, SurfaceChannelConfig, sample_grid, PolygonChannelConfig,
-    HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig, ZonalConfig,
+    HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig, ZonalConfig, PointZonalConfig, point_zonal,
     PolygonSet, rasterize_polygons, points_in_polygons,
 )
 from .polygons import read_geojson_polygons  # noqa: E402,F401  (also gives PolygonSet its from_wkt)
@@ -184,6 +184,6 @@ __all__ = [
     "TerrainProduct", "TerrainSpec", "TerrainBandConfig", "terrain", "terrain_light",
     "TreeSpec", "TreeBandConfig", "segment_trees",
     "SampleMode", "SurfaceChannelConfig", "sample_grid", "PolygonChannelConfig",
-    "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig", "ZonalConfig",
+    "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig", "ZonalConfig", "PointZonalConfig", "point_zonal",
     "PolygonSet", "rasterize_polygons", "points_in_polygons", "read_geojson_polygons",
 ]

@@ -91,6 +91,19 @@ class ZoneFoldParams(C.Structure):
         super().__init__(combine=combine, reserved_=0)
 
 
+# PCR_HIP_POINT_FOLD_* of include/pcr_hip.h
+POINT_FOLD_BLOCK, POINT_FOLD_POINTS_PER_LANE, POINT_FOLD_TILES_IN_FLIGHT = 256, 4, 4
+POINT_FOLD_LDS_BYTES, POINT_FOLD_STATS_ROW_BYTES = 61440, 20
+
+
+class PointFoldParams(C.Structure):
+    """pcr_hip_point_fold_params: path 0 auto, 1 global atomics, 2 an LDS table; blocks 0 = by path and CU count."""
+    _fields_ = [("path", C.c_int32), ("blocks", C.c_int32)]
+
+    def __init__(self, path=0, blocks=0):
+        super().__init__(path=path, blocks=blocks)
+
+
 class RasterizeParams(C.Structure):
     """pcr_hip_rasterize_params: the background's bits default to the project's NaN; events: see include/pcr_hip.h."""
     _fields_ = [("background", C.c_float), ("reserved_", C.c_int32), ("events", C.c_void_p * 3)]
@@ -273,6 +286,13 @@ SYMBOLS = {
     "pcr_hip_polygon_index_upload": [_VP, _VP, _SZ, _VP],
     "pcr_hip_points_in_polygons": [_VP, _VP, _VP, _VP, _U64, _VP, _VP, C.POINTER(_VP)],
     "pcr_hip_points_in_polygons_host": [_VP, _VP, _VP, _U64, _VP, C.c_int],
+    "pcr_hip_point_fold_plan": [_U32, C.c_int, _U64, C.POINTER(PointFoldParams), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_SZ)],
+    "pcr_hip_point_fold_stats": [_VP, _VP, _VP, _U64, C.c_double, C.c_double, _U32, C.POINTER(PointFoldParams), _VP, _VP, _VP, _VP, _VP,
+                                 _VP],
+    "pcr_hip_point_fold_stats_host": [_VP, _VP, _VP, _U64, C.c_double, C.c_double, _U32, C.POINTER(PointFoldParams), _VP, _VP, _VP, _VP,
+                                      _VP],
+    "pcr_hip_point_fold_hist": [_VP, _VP, _VP, _U64, C.c_int, C.c_double, C.c_double, _U32, C.POINTER(PointFoldParams), _VP, _VP, _VP],
+    "pcr_hip_point_fold_hist_host": [_VP, _VP, _VP, _U64, C.c_int, C.c_double, C.c_double, _U32, C.POINTER(PointFoldParams), _VP, _VP],
 }
 
 _lib = None
