@@ -1,5 +1,6 @@
 // band_pass.hpp -- what the kernels over one strided band share (fill_nodata.hip, ground_filter.hip, overview.hip): the checks
-// their entry points start with, the bytes a band spans, the alignment that picks a VEC variant, and the quad load.
+// their entry points start with, the bytes a band spans (the zonal folds' too: zone_fold.hpp), the alignment that picks a VEC
+// variant, and the quad load.
 #pragma once
 
 #include "common.hpp"
@@ -12,14 +13,18 @@ namespace band {
 // The rows of a band start on 16 bytes: what a kernel's VEC variant (16-byte accesses) asks of every band it is used on.
 inline bool aligned16(const void* p, int64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && stride % 4 == 0; }
 
-// [b, e): the bytes a band of `height` rows of `width` floats `stride` apart spans, first cell to last; or `bytes` at p.
+// [b, e): the bytes a band of `height` rows of `width` elements (floats, unless `elem` says otherwise) `stride` apart spans, first
+// cell to last; or `bytes` at p.
 struct Span { uintptr_t b, e; };
-inline Span span_of(const void* p, int width, int height, int64_t stride) {
+inline Span span_of(const void* p, int width, int height, int64_t stride, size_t elem = 4) {
     const uintptr_t b = reinterpret_cast<uintptr_t>(p);
-    return {b, b + ((uintptr_t)(height - 1) * (uintptr_t)stride + (uintptr_t)width) * 4};
+    return {b, b + ((uintptr_t)(height - 1) * (uintptr_t)stride + (uintptr_t)width) * elem};
 }
 inline Span span_of(const void* p, size_t bytes) { return {reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes}; }
-inline bool overlap(Span x, Span y) { return !(x.e <= y.b || y.e <= x.b); }
+// An empty span overlaps nothing (the point folds' inputs when there is no point).  The band kernels never pass one: width, height
+// and Z are at least 1 and a work area is refused unless it has its bytes -- rasterize_polygons alone compares first, so a work
+// area of no bytes inside its output is refused as too small, not as overlapping.
+inline bool overlap(Span x, Span y) { return x.b != x.e && y.b != y.e && !(x.e <= y.b || y.e <= x.b); }
 
 // The checks of entry point `fn`, each PCR_HIP_OK or the failure with fn's message.  check_bands is the usual opening: no null
 // pointer (`pointers`: the ones that are no band), a positive extent, then every band's rows at least `width` floats apart.

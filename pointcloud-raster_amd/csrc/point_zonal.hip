@@ -8,8 +8,8 @@
 // bytes per lane where all three start on such a boundary (VEC: a lane owns four consecutive points), else element by element
 // (a lane owns points t, t + 256, t + 512, t + 768 of the tile).  Per slot k of the four, the 64 lanes of a wave hold 64 points:
 // neighbouring lanes with one zone (one zone and bin, for a histogram) form a run, a segmented wave scan sums along it, and the
-// run's last lane adds the run's sums to the zone's row -- k_zone_fold_stats' run-combining (csrc/zonal.hip).  The sums are
-// integers, so any grouping of equal labels gives the same bits, whether the lanes' points are neighbours in memory or not.
+// run's last lane adds the run's sums to the zone's row -- the run-combining of csrc/zone_fold.hpp, k_zone_fold_stats' too.  The
+// sums are integers, so any grouping of equal labels gives the same bits, whether the lanes' points are neighbours in memory or not.
 //   path 1  the row is in HBM: one set of 64-bit global atomic adds per run, no value returned.
 //   path 2  the row is in a workgroup-private table in LDS, zeroed at the start: one set of LDS atomics per run; the workgroup
 //           adds the table's NONZERO entries to HBM with global atomics at the end of its sweep.  An LDS row packs the count
@@ -18,7 +18,7 @@
 //           n <= 2^20 < 2^21 and sum of (q + 2^21) <= 2^20 * 2^22 < 2^43.
 // info: a lane keeps the greatest zone and the overflow count of its points; one wave reduction at the end of the sweep, the
 // waves' results through LDS, and at most one agent-scope atomic max and one atomic add per workgroup.
-#include "common.hpp"
+#include "zone_fold.hpp"
 #include "point_zonal.hpp"
 
 #include <algorithm>
@@ -29,7 +29,7 @@ namespace pcrhip {
 namespace {
 
 namespace pz = pzonal;
-using u64 = unsigned long long;
+using namespace zfold;
 
 constexpr int kBlock = PCR_HIP_POINT_FOLD_BLOCK;
 constexpr int kPer = PCR_HIP_POINT_FOLD_POINTS_PER_LANE;
@@ -47,7 +47,6 @@ constexpr int kBlocksPerCuLds = PCR_HIP_POINT_FOLD_BLOCKS_PER_CU_LDS;
 static_assert(kPer == 4, "the 16-byte accesses of the VEC variant cover four points");
 static_assert(kInFlight % 2 == 0 && kEpochPoints % (kTile * kInFlight) == 0, "an epoch is whole trips");
 
-__device__ __forceinline__ void add_u64(u64* p, u64 v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void lds_add_u64(u64* p, u64 v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_add_u32(uint32_t* p, uint32_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
@@ -89,35 +88,6 @@ __device__ __forceinline__ void load_tile(const float* __restrict__ label, const
         const bool kept = live && (!mask || __builtin_nontemporal_load(mask + i) != 0);
         s.keep |= kept ? (1u << k) : 0u;
     }
-}
-
-// ---- the runs of a wave (csrc/zonal.hip): lane L heads a run when L == 0 or its key differs from lane L - 1's
-struct Run {
-    int lane, start;
-    bool tail;
-};
-__device__ __forceinline__ Run run_from(bool head) {
-    Run r;
-    r.lane = threadIdx.x & 63;
-    const u64 heads = __ballot(r.lane == 0 || head);
-    r.start = 63 - __clzll((long long)(heads & (~0ull >> (63 - r.lane))));
-    r.tail = r.lane == 63 || ((heads >> (r.lane + 1)) & 1ull);
-    return r;
-}
-__device__ __forceinline__ Run run_of(uint32_t z) { return run_from((uint32_t)__shfl_up((int)z, 1) != z); }
-__device__ __forceinline__ Run run_of(uint32_t z, uint32_t b) {
-    const uint32_t pz_ = (uint32_t)__shfl_up((int)z, 1), pb = (uint32_t)__shfl_up((int)b, 1);
-    return run_from(pz_ != z || pb != b);
-}
-// The inclusive sum of v along the run: a lane takes lane - d's partial sum while that lane is inside its run.
-template <class T>
-__device__ __forceinline__ T run_sum(const Run& r, T v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T up = (T)__shfl_up(v, d);
-        if (r.lane - d >= r.start) v += up;
-    }
-    return v;
 }
 
 // ---- info: the lanes' greatest zone and overflow count, once per workgroup
@@ -341,10 +311,7 @@ __global__ __launch_bounds__(kBlock) void k_point_fold_hist(const FoldHist a) {
     info_leaves(zmax, over, a.info);
 }
 
-// ---- the argument checks the entry points share
-struct Span { uintptr_t b, e; };
-Span span_of(const void* p, size_t bytes) { return {reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes}; }
-bool overlap(Span x, Span y) { return x.b != x.e && y.b != y.e && !(x.e <= y.b || y.e <= x.b); }
+// ---- the argument checks the entry points share (the spans, Z, bins and the tables: csrc/zone_fold.hpp)
 
 // The greatest capacity path 2 takes: rows of kStatsRowBytes, or of 4 * bins bytes, in the LDS budget.
 uint32_t lds_capacity(int bins) { return kLdsBudget / (bins > 0 ? 4u * (uint32_t)bins : kStatsRowBytes); }
@@ -353,19 +320,11 @@ uint32_t lds_capacity(int bins) { return kLdsBudget / (bins > 0 ? 4u * (uint32_t
 int resolve_path(int path, uint32_t Z, int bins) { return path != 0 ? path : (Z <= lds_capacity(bins) ? 2 : 1); }
 
 int check_common(const std::string& fn, uint32_t Z, int bins, const pcr_hip_point_fold_params* params) {
-    PCR_REQUIRE(Z >= 1u && Z <= pz::kMaxZone, fn + ": Z must be between 1 and 2^24");
+    if (int rc = check_Z(fn, Z)) return rc;
     PCR_REQUIRE(params->path >= 0 && params->path <= 2, fn + ": path must be 0 (auto), 1 (global atomics) or 2 (LDS table)");
     PCR_REQUIRE(params->path != 2 || Z <= lds_capacity(bins),
                 fn + ": path 2 holds at most " + std::to_string(lds_capacity(bins)) + " zones of this row size in LDS");
     PCR_REQUIRE(params->blocks >= 0 && params->blocks <= 65536, fn + ": blocks must be between 0 (auto) and 65536");
-    return PCR_HIP_OK;
-}
-
-int check_tables(const std::string& fn, const std::vector<Span>& in, const std::vector<Span>& tables) {
-    for (size_t t = 0; t < tables.size(); ++t) {
-        for (const Span& s : in) PCR_REQUIRE(!overlap(tables[t], s), fn + ": a table overlaps an input");
-        for (size_t u = 0; u < t; ++u) PCR_REQUIRE(!overlap(tables[t], tables[u]), fn + ": two tables overlap");
-    }
     return PCR_HIP_OK;
 }
 
@@ -394,7 +353,7 @@ int check_fold_stats(const std::string& fn, const float* label, const uint8_t* m
 int check_fold_hist(const std::string& fn, const float* label, const uint8_t* mask, const float* value, uint64_t n, int bins, double lo,
                     double inv_w, uint32_t Z, const pcr_hip_point_fold_params* params, const u64* zcounts, const u64* info) {
     PCR_REQUIRE(label && value && params && zcounts, fn + ": null argument");
-    PCR_REQUIRE(bins >= 1 && bins <= pz::kMaxBins, fn + ": bins must be between 1 and 256");
+    if (int rc = check_bins(fn, bins)) return rc;
     if (int rc = check_common(fn, Z, bins, params)) return rc;
     PCR_REQUIRE(std::isfinite(lo) && std::isfinite(inv_w) && inv_w > 0.0, fn + ": lo and inv_w must be finite, inv_w positive");
     PCR_REQUIRE(n <= ((uint64_t)1 << 40), fn + ": more than 2^40 points in one call");

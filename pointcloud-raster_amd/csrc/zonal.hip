@@ -5,9 +5,9 @@
 // The folds are grouped reductions by atomics: one lane per cell, 64 consecutive cells per wave.  Neighbouring lanes with one
 // label form a run; a segmented wave scan sums along each run and only the run's last lane adds to the zone's row, with 64-bit
 // global atomic adds that return nothing.  The sums are integers, so any grouping of equal labels gives the same bits: runs may
-// go on across a row end of a contiguous band, and combine = 0 (one set of atomics per cell) gives the same table.
-#include "band_pass.hpp"
-#include "zonal.hpp"
+// go on across a row end of a contiguous band, and combine = 0 (one set of atomics per cell) gives the same table.  The runs, the
+// scan and the checks of Z, bins and the tables' spans are csrc/zone_fold.hpp, which the point folds (point_zonal.hip) share.
+#include "zone_fold.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -16,7 +16,7 @@ namespace pcrhip {
 namespace {
 
 namespace zn = zonal;
-using u64 = unsigned long long;
+using namespace zfold;
 
 constexpr int kBlock = 256;
 
@@ -29,8 +29,6 @@ struct Cells {                       // a band or plane of h rows of w elements,
         return r * stride + (i - r * w);
     }
 };
-
-__device__ __forceinline__ void add_u64(u64* p, u64 v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- 1: the greatest zone of a band
 __global__ __launch_bounds__(kBlock) void k_zone_max(const float* __restrict__ zones, Cells g, int64_t stride, uint32_t* out) {
@@ -51,31 +49,6 @@ __global__ __launch_bounds__(kBlock) void k_zone_max(const float* __restrict__ z
     // find their maximum there already (65536 atomics on the one word took fifty times a copy of the band).
     if ((threadIdx.x & 63) == 0 && m > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
         (void)__hip_atomic_fetch_max(out, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The runs of a wave: lane L heads a run when L == 0 or its zone differs from lane L - 1's.  `start` is the head of L's run,
-// `tail` says L is its last lane.  (Lanes past the band's end carry zone 0, like every cell with no zone.)
-struct Run {
-    int lane, start;
-    bool tail;
-};
-__device__ __forceinline__ Run run_of(uint32_t z) {
-    Run r;
-    r.lane = threadIdx.x & 63;
-    const uint32_t prev = (uint32_t)__shfl_up((int)z, 1);
-    const u64 heads = __ballot(r.lane == 0 || prev != z);
-    r.start = 63 - __clzll((long long)(heads & (~0ull >> (63 - r.lane))));
-    r.tail = r.lane == 63 || ((heads >> (r.lane + 1)) & 1ull);
-    return r;
-}
-// The inclusive sum of v along the run: six steps; a lane takes lane - d's partial sum while that lane is inside its run.
-__device__ __forceinline__ u64 run_sum(const Run& r, u64 v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 up = (u64)__shfl_up((long long)v, d);
-        if (r.lane - d >= r.start) v += up;
-    }
-    return v;
 }
 
 // ---- 2: cells, N, S1, S2 by zone
@@ -247,24 +220,8 @@ __global__ __launch_bounds__(kBlock) void k_zone_rows_pct(const RowsPct a) {
 }
 
 // ---- the argument checks the entry points share
-struct Span { uintptr_t b, e; };
-Span span_of(const void* p, int width, int height, int64_t stride, size_t elem) {
-    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
-    return {b, b + ((uintptr_t)(height - 1) * (uintptr_t)stride + (uintptr_t)width) * elem};
-}
-Span span_of(const void* p, size_t bytes) { return {reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes}; }
-bool overlap(Span x, Span y) { return !(x.e <= y.b || y.e <= x.b); }
-
 int check_cells(const std::string& fn, int width, int height) {
     PCR_REQUIRE((int64_t)width * height <= 2147483647LL, fn + ": more than 2^31 - 1 cells");
-    return PCR_HIP_OK;
-}
-int check_Z(const std::string& fn, uint32_t Z) {
-    PCR_REQUIRE(Z >= 1u && Z <= zn::kMaxZone, fn + ": Z must be between 1 and 2^24");
-    return PCR_HIP_OK;
-}
-int check_bins(const std::string& fn, int bins) {
-    PCR_REQUIRE(bins >= 1 && bins <= zn::kMaxBins, fn + ": bins must be between 1 and 256");
     return PCR_HIP_OK;
 }
 
@@ -272,7 +229,7 @@ int check_max(const std::string& fn, const float* zones, int width, int height, 
     if (int rc = band::check_extent(fn, zones && out, width, height)) return rc;
     if (int rc = band::check_stride(fn, "zone", stride, width)) return rc;
     if (int rc = check_cells(fn, width, height)) return rc;
-    PCR_REQUIRE(!overlap(span_of(zones, width, height, stride, 4), span_of(out, 4)), fn + ": the result overlaps the zone band");
+    PCR_REQUIRE(!overlap(span_of(zones, width, height, stride), span_of(out, 4)), fn + ": the result overlaps the zone band");
     return PCR_HIP_OK;
 }
 
@@ -288,9 +245,9 @@ int check_fold_stats(const std::string& fn, const float* zones, int width, int h
     if (int rc = check_Z(fn, Z)) return rc;
     if (int rc = check_cells(fn, width, height)) return rc;
     PCR_REQUIRE(params->combine == 0 || params->combine == 1, fn + ": combine must be 0 or 1");
-    std::vector<Span> in{span_of(zones, width, height, zone_stride, 4)}, tables;
+    std::vector<Span> in{span_of(zones, width, height, zone_stride)}, tables;
     if (planes) {
-        in.push_back(span_of(pn, width, height, plane_stride, 4));
+        in.push_back(span_of(pn, width, height, plane_stride));
         in.push_back(span_of(ps1, width, height, plane_stride, 8));
         in.push_back(span_of(ps2, width, height, plane_stride, 8));
         tables.push_back(span_of(tn, (size_t)Z * 8));
@@ -298,11 +255,7 @@ int check_fold_stats(const std::string& fn, const float* zones, int width, int h
         tables.push_back(span_of(ts2, (size_t)Z * 8));
     }
     if (cells) tables.push_back(span_of(cells, (size_t)Z * 8));
-    for (size_t t = 0; t < tables.size(); ++t) {
-        for (const Span& s : in) PCR_REQUIRE(!overlap(tables[t], s), fn + ": a table overlaps an input");
-        for (size_t u = 0; u < t; ++u) PCR_REQUIRE(!overlap(tables[t], tables[u]), fn + ": two tables overlap");
-    }
-    return PCR_HIP_OK;
+    return check_tables(fn, in, tables);
 }
 
 int check_fold_hist(const std::string& fn, const float* zones, int width, int height, int64_t zone_stride, const uint32_t* counts,
@@ -320,7 +273,7 @@ int check_fold_hist(const std::string& fn, const float* zones, int width, int he
     PCR_REQUIRE(params->combine == 0 || params->combine == 1, fn + ": combine must be 0 or 1");
     const Span table = span_of(zcounts, (size_t)Z * (size_t)bins * 8);
     const Span cube = span_of(counts, ((size_t)(bins - 1) * (size_t)bin_stride + (size_t)plane) * 4);
-    PCR_REQUIRE(!overlap(table, span_of(zones, width, height, zone_stride, 4)) && !overlap(table, cube), fn + ": the table overlaps an input");
+    PCR_REQUIRE(!overlap(table, span_of(zones, width, height, zone_stride)) && !overlap(table, cube), fn + ": the table overlaps an input");
     return PCR_HIP_OK;
 }
 

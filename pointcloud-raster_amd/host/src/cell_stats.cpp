@@ -10,9 +10,21 @@ namespace pcr {
 namespace detail {
 
 namespace {
-Status refuse(const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: " + msg); }
 bool known(CellStat p) { return p == CellStat::Mean || p == CellStat::Variance || p == CellStat::StdDev; }
 }  // namespace
+
+Status check_cell_stats_value(const CellStatsConfig& c, const std::string& where) {
+    if (c.value_channel.empty()) return refuse(where + ".value_channel is empty");
+    if (!std::isfinite(c.resolution) || !(c.resolution > 0.0) || !std::isfinite(1.0 / c.resolution))
+        return refuse(where + ".resolution must be finite and positive");
+    if (!std::isfinite(c.origin)) return refuse(where + ".origin must be finite");
+    return Status::success();
+}
+
+Status check_cell_stats_ddof(const CellStatsConfig& c, const std::string& where) {
+    if (c.ddof != 0 && c.ddof != 1) return refuse(where + ".ddof must be 0 or 1");
+    return Status::success();
+}
 
 Status check_cell_stats(const PipelineConfig& cfg) {
     const auto& list = cfg.cell_stats;
@@ -22,17 +34,14 @@ Status check_cell_stats(const PipelineConfig& cfg) {
     for (size_t i = 0; i < list.size(); ++i) {
         const CellStatsConfig& c = list[i];
         const std::string where = "cell_stats[" + std::to_string(i) + "]";
-        if (c.value_channel.empty()) return refuse(where + ".value_channel is empty");
-        if (!std::isfinite(c.resolution) || !(c.resolution > 0.0) || !std::isfinite(1.0 / c.resolution))
-            return refuse(where + ".resolution must be finite and positive");
-        if (!std::isfinite(c.origin)) return refuse(where + ".origin must be finite");
+        if (Status s = check_cell_stats_value(c, where); !s.ok()) return s;
         if (c.products.empty() || c.products.size() > PCR_HIP_CELL_STATS_MAX_PRODUCTS)
             return refuse(where + ".products must name between 1 and 3 bands");
         for (size_t j = 0; j < c.products.size(); ++j) {
             if (!known(c.products[j])) return refuse(where + ".products names an unknown band");
             if (std::count(c.products.begin(), c.products.end(), c.products[j]) != 1) return refuse(where + ".products names a band twice");
         }
-        if (c.ddof != 0 && c.ddof != 1) return refuse(where + ".ddof must be 0 or 1");
+        if (Status s = check_cell_stats_ddof(c, where); !s.ok()) return s;
         if (c.band_names.size() > c.products.size()) return refuse(where + ".band_names is longer than products");
     }
     // every band that leaves the pipeline, by name: the outputs (the cell-stats bands among them), the DTM and hag bands, the
@@ -62,20 +71,22 @@ Status cell_stats_checkpoint_error() {
                          "refused while PipelineConfig::cell_stats is not empty");
 }
 
+CellStatsEntry cell_stats_entry(const CellStatsConfig& c, int cls) {
+    CellStatsEntry e;
+    e.value_channel = c.value_channel;
+    e.origin = c.origin;
+    e.resolution = c.resolution;
+    e.inv_res = 1.0 / c.resolution;
+    e.ddof = c.ddof;
+    e.cls = cls;
+    for (CellStat p : c.products) e.products.push_back(static_cast<int>(p));
+    return e;
+}
+
 CellStatsPlan plan_cell_stats(const PipelineConfig& cfg, const FilterPlan& filters) {
     CellStatsPlan plan;
-    for (size_t i = 0; i < cfg.cell_stats.size(); ++i) {
-        const CellStatsConfig& c = cfg.cell_stats[i];
-        CellStatsEntry e;
-        e.value_channel = c.value_channel;
-        e.origin = c.origin;
-        e.resolution = c.resolution;
-        e.inv_res = 1.0 / c.resolution;
-        e.ddof = c.ddof;
-        e.cls = i < filters.stat_class_of.size() ? filters.stat_class_of[i] : 0;
-        for (CellStat p : c.products) e.products.push_back(static_cast<int>(p));
-        plan.entries.push_back(e);
-    }
+    for (size_t i = 0; i < cfg.cell_stats.size(); ++i)
+        plan.entries.push_back(cell_stats_entry(cfg.cell_stats[i], i < filters.stat_class_of.size() ? filters.stat_class_of[i] : 0));
     return plan;
 }
 

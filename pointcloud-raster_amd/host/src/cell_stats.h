@@ -37,12 +37,18 @@ struct CellStatsPlan {
 /// empty, longer than 3 or with a duplicate, ddof other than 0 or 1, band_names longer than products, a band name that collides
 /// with any other band that leaves the pipeline, a row-block shard.  An empty list refuses nothing.
 Status check_cell_stats(const PipelineConfig& cfg);
+/// The refusals of ONE spec that PointZonalConfig::cell_stats shares, `where` naming the spec: value_channel, resolution and origin
+/// -- and ddof, which check_cell_stats asks after the products.
+Status check_cell_stats_value(const CellStatsConfig& c, const std::string& where);
+Status check_cell_stats_ddof(const CellStatsConfig& c, const std::string& where);
 /// ... and the one of a pipeline that has to run out of core.
 Status cell_stats_out_of_core_error();
 /// ... and of the calls that would lose the planes (save_state, load_state, resume): NotImplemented.
 Status cell_stats_checkpoint_error();
 /// The plan of a configuration that passed check_cell_stats; `filters` is the configuration's plan_filters.
 CellStatsPlan plan_cell_stats(const PipelineConfig& cfg, const FilterPlan& filters);
+/// One spec that passed its checks as an entry of filter class `cls`: the one place that computes inv_res.
+CellStatsEntry cell_stats_entry(const CellStatsConfig& c, int cls);
 
 /// pcr_hip_cell_stats_bands_host over `threads` OpenMP threads, the rows shared out (every cell is independent).
 /// n, s1, s2: rows * width each; outs: one band of rows * width floats per product of the entry.

@@ -9,10 +9,6 @@
 namespace pcr {
 namespace detail {
 
-namespace {
-Status refuse(const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: " + msg); }
-}  // namespace
-
 Status check_extremes(const PipelineConfig& cfg) {
     const auto& list = cfg.extremes;
     if (list.empty()) return Status::success();

@@ -9,9 +9,15 @@
 namespace pcr {
 namespace detail {
 
-namespace {
-Status refuse(const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: " + msg); }
-}  // namespace
+Status check_histogram_spec(const HistogramConfig& h, const std::string& where) {
+    if (h.value_channel.empty()) return refuse(where + ".value_channel is empty");
+    if (h.bins < 1 || h.bins > PCR_HIP_HISTOGRAM_MAX_BINS) return refuse(where + ".bins must be between 1 and 256");
+    if (!std::isfinite(h.lo) || !std::isfinite(h.hi) || !(h.lo < h.hi)) return refuse(where + " needs finite bounds with lo < hi");
+    if (h.percentiles.size() > PCR_HIP_HISTOGRAM_MAX_PERCENTILES) return refuse(where + " has more than 16 percentiles");
+    for (float q : h.percentiles)
+        if (!(q >= 0.0f && q <= 1.0f)) return refuse(where + ".percentiles must lie in [0, 1]");
+    return Status::success();
+}
 
 Status check_histograms(const PipelineConfig& cfg) {
     const auto& list = cfg.histograms;
@@ -21,12 +27,7 @@ Status check_histograms(const PipelineConfig& cfg) {
     for (size_t i = 0; i < list.size(); ++i) {
         const HistogramConfig& h = list[i];
         const std::string where = "histograms[" + std::to_string(i) + "]";
-        if (h.value_channel.empty()) return refuse(where + ".value_channel is empty");
-        if (h.bins < 1 || h.bins > PCR_HIP_HISTOGRAM_MAX_BINS) return refuse(where + ".bins must be between 1 and 256");
-        if (!std::isfinite(h.lo) || !std::isfinite(h.hi) || !(h.lo < h.hi)) return refuse(where + " needs finite bounds with lo < hi");
-        if (h.percentiles.size() > PCR_HIP_HISTOGRAM_MAX_PERCENTILES) return refuse(where + " has more than 16 percentiles");
-        for (float q : h.percentiles)
-            if (!(q >= 0.0f && q <= 1.0f)) return refuse(where + ".percentiles must lie in [0, 1]");
+        if (Status s = check_histogram_spec(h, where); !s.ok()) return s;
         if (h.band_names.size() > h.percentiles.size()) return refuse(where + ".band_names is longer than percentiles");
     }
     // every band that leaves the pipeline, by name: the outputs (the percentile bands among them), the DTM and hag bands, the
@@ -56,20 +57,22 @@ Status histograms_checkpoint_error() {
                          "refused while PipelineConfig::histograms is not empty");
 }
 
+HistogramEntry histogram_entry(const HistogramConfig& h, int cls) {
+    HistogramEntry e;
+    e.value_channel = h.value_channel;
+    e.bins = h.bins;
+    e.lo = (double)h.lo;
+    e.inv_w = (double)h.bins / ((double)h.hi - (double)h.lo);
+    e.w = ((double)h.hi - (double)h.lo) / h.bins;
+    e.cls = cls;
+    e.q = h.percentiles;
+    return e;
+}
+
 HistogramPlan plan_histograms(const PipelineConfig& cfg, const FilterPlan& filters) {
     HistogramPlan plan;
-    for (size_t i = 0; i < cfg.histograms.size(); ++i) {
-        const HistogramConfig& h = cfg.histograms[i];
-        HistogramEntry e;
-        e.value_channel = h.value_channel;
-        e.bins = h.bins;
-        e.lo = (double)h.lo;
-        e.inv_w = (double)h.bins / ((double)h.hi - (double)h.lo);
-        e.w = ((double)h.hi - (double)h.lo) / h.bins;
-        e.cls = i < filters.hist_class_of.size() ? filters.hist_class_of[i] : 0;
-        e.q = h.percentiles;
-        plan.entries.push_back(e);
-    }
+    for (size_t i = 0; i < cfg.histograms.size(); ++i)
+        plan.entries.push_back(histogram_entry(cfg.histograms[i], i < filters.hist_class_of.size() ? filters.hist_class_of[i] : 0));
     return plan;
 }
 

@@ -38,12 +38,17 @@ struct HistogramPlan {
 /// value_channel, band_names longer than percentiles, a band name that collides with any other band that leaves the
 /// pipeline, a row-block shard.  An empty list refuses nothing.
 Status check_histograms(const PipelineConfig& cfg);
+/// The refusals of ONE spec that PointZonalConfig::histograms shares, `where` naming the spec, in this order: value_channel, bins,
+/// the bounds, more than 16 percentiles, a percentile outside [0, 1].
+Status check_histogram_spec(const HistogramConfig& h, const std::string& where);
 /// ... and the one of a pipeline that has to run out of core.
 Status histograms_out_of_core_error();
 /// ... and of the calls that would lose the cube (save_state, load_state, resume): NotImplemented.
 Status histograms_checkpoint_error();
 /// The plan of a configuration that passed check_histograms; `filters` is the configuration's plan_filters.
 HistogramPlan plan_histograms(const PipelineConfig& cfg, const FilterPlan& filters);
+/// One spec that passed its checks as an entry of filter class `cls`: the one place that computes lo, inv_w and w.
+HistogramEntry histogram_entry(const HistogramConfig& h, int cls);
 /// Bytes of every cube of the configuration over a window of `rows` rows: what counts towards gpu_memory_budget.
 size_t histogram_cube_bytes(const PipelineConfig& cfg, size_t rows);
 

@@ -17,6 +17,9 @@
 namespace pcr {
 namespace detail {
 
+// A refusal at create (InvalidArgument), as every plan routine words it.
+inline Status refuse(const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: " + msg); }
+
 // plane bits = PCR_HIP_PLANE_* of include/pcr_hip.h (sum, weight, max, min)
 constexpr uint32_t kPlaneBits[4] = {1u, 2u, 4u, 8u};
 
@@ -126,10 +129,14 @@ inline std::string default_band_name(const ReductionSpec& r) {
     return r.output_band_name.empty() ? r.value_channel + "_" + std::to_string(static_cast<int>(r.type)) : r.output_band_name;
 }
 
-// PipelineConfig::histograms: the name of entry h's j-th percentile band, "{value_channel}_p{round(q * 100)}" unless given.
+// "{channel}_p{round(q * 100)}": a percentile band of a histogram and a percentile column of a zonal table.
+inline std::string percentile_name(const std::string& channel, float q) {
+    return channel + "_p" + std::to_string(std::lround((double)q * 100.0));
+}
+// PipelineConfig::histograms: the name of entry h's j-th percentile band, percentile_name unless given.
 inline std::string histogram_band_name(const HistogramConfig& h, size_t j) {
     if (j < h.band_names.size() && !h.band_names[j].empty()) return h.band_names[j];
-    return h.value_channel + "_p" + std::to_string(std::lround((double)h.percentiles[j] * 100.0));
+    return percentile_name(h.value_channel, h.percentiles[j]);
 }
 // PipelineConfig::extremes: the name of an entry's band, "{value_channel}_low" / "{value_channel}_high" unless given.
 inline std::string extremes_band_name(const ExtremesConfig& e) {

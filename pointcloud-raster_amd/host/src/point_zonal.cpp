@@ -4,9 +4,9 @@
 #include "pcr/core/point_cloud.h"
 #include "polygons.h"
 #include "sample_grid.h"
+#include "zone_rows.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 namespace pcr {
@@ -14,17 +14,22 @@ namespace detail {
 
 namespace {
 
-Status refuse(const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: " + msg); }
-
-std::vector<std::string> column_names(const PointZonalConfig& z) {
-    std::vector<std::string> names{"zone", "points"};
-    for (const auto& c : z.cell_stats)
-        for (const char* suffix : {"_n", "_mean", "_var", "_std"}) names.push_back(c.value_channel + suffix);
-    for (const auto& h : z.histograms) {
-        names.push_back(h.value_channel + "_hist_n");
-        for (float q : h.percentiles) names.push_back(h.value_channel + "_p" + std::to_string(std::lround((double)q * 100.0)));
+// What zone_rows makes entry e's columns from: its specs, and with `t` (the entry's state) the integer tables.  t null: the
+// columns' names alone.
+ZoneRowsInputs rows_of(const PointZonalPlan::Entry& e, const unsigned long long* t) {
+    ZoneRowsInputs r;
+    if (t) r.count = t + e.points_at();
+    for (size_t k = 0; k < e.stats.size(); ++k) {
+        const CellStatsEntry& c = e.stats[k];
+        const unsigned long long* n = t ? t + e.stat_at(k) : nullptr;
+        r.stats.push_back({c.value_channel, n, t ? reinterpret_cast<const long long*>(n + e.Z) : nullptr, t ? n + 2 * (size_t)e.Z : nullptr,
+                           c.origin, c.resolution, c.ddof});
     }
-    return names;
+    for (size_t k = 0; k < e.hists.size(); ++k) {
+        const HistogramEntry& h = e.hists[k];
+        r.hists.push_back({h.value_channel, t ? t + e.hist_at(k) : nullptr, h.bins, h.lo, h.w, h.q});
+    }
+    return r;
 }
 
 // One entry's refusals and its plan; `stat_cls` / `hist_cls`: the specs' filter classes (empty: class 0).
@@ -40,43 +45,17 @@ Status plan_entry(const PointZonalConfig& z, const std::string& where, const std
     for (size_t k = 0; k < z.cell_stats.size(); ++k) {               // the per-spec refusals of PipelineConfig::cell_stats
         const CellStatsConfig& c = z.cell_stats[k];
         const std::string at = where + ".cell_stats[" + std::to_string(k) + "]";
-        if (c.value_channel.empty()) return refuse(at + ".value_channel is empty");
-        if (!std::isfinite(c.resolution) || !(c.resolution > 0.0) || !std::isfinite(1.0 / c.resolution))
-            return refuse(at + ".resolution must be finite and positive");
-        if (!std::isfinite(c.origin)) return refuse(at + ".origin must be finite");
-        if (c.ddof != 0 && c.ddof != 1) return refuse(at + ".ddof must be 0 or 1");
-        PointZonalPlan::Stat s;
-        s.channel = c.value_channel;
-        s.origin = c.origin;
-        s.resolution = c.resolution;
-        s.inv_res = 1.0 / c.resolution;
-        s.ddof = c.ddof;
-        s.cls = k < stat_cls.size() ? stat_cls[k] : 0;
-        e.stats.push_back(s);
+        Status s = check_cell_stats_value(c, at);
+        if (s.ok()) s = check_cell_stats_ddof(c, at);
+        if (!s.ok()) return s;
+        e.stats.push_back(cell_stats_entry(c, k < stat_cls.size() ? stat_cls[k] : 0));
     }
     for (size_t k = 0; k < z.histograms.size(); ++k) {               // ... and of PipelineConfig::histograms
         const HistogramConfig& h = z.histograms[k];
-        const std::string at = where + ".histograms[" + std::to_string(k) + "]";
-        if (h.value_channel.empty()) return refuse(at + ".value_channel is empty");
-        if (h.bins < 1 || h.bins > PCR_HIP_HISTOGRAM_MAX_BINS) return refuse(at + ".bins must be between 1 and 256");
-        if (!std::isfinite(h.lo) || !std::isfinite(h.hi) || !(h.lo < h.hi)) return refuse(at + " needs finite bounds with lo < hi");
-        if (h.percentiles.size() > PCR_HIP_HISTOGRAM_MAX_PERCENTILES) return refuse(at + " has more than 16 percentiles");
-        for (float q : h.percentiles)
-            if (!(q >= 0.0f && q <= 1.0f)) return refuse(at + ".percentiles must lie in [0, 1]");
-        PointZonalPlan::Hist p;
-        p.channel = h.value_channel;
-        p.bins = h.bins;
-        p.lo = (double)h.lo;
-        p.inv_w = (double)h.bins / ((double)h.hi - (double)h.lo);
-        p.w = ((double)h.hi - (double)h.lo) / h.bins;
-        p.q = h.percentiles;
-        p.cls = k < hist_cls.size() ? hist_cls[k] : 0;
-        e.hists.push_back(p);
+        if (Status s = check_histogram_spec(h, where + ".histograms[" + std::to_string(k) + "]"); !s.ok()) return s;
+        e.hists.push_back(histogram_entry(h, k < hist_cls.size() ? hist_cls[k] : 0));
     }
-    std::vector<std::string> cols = column_names(z);
-    std::sort(cols.begin(), cols.end());
-    const auto dup = std::adjacent_find(cols.begin(), cols.end());
-    if (dup != cols.end()) return refuse(where + ": column '" + *dup + "' appears twice");
+    if (Status s = check_zone_column_names(where, "points", rows_of(e, nullptr)); !s.ok()) return s;
     *out = std::move(e);
     return Status::success();
 }
@@ -180,7 +159,7 @@ Status point_zonal_fold(const PointZonalPlan& plan, PointZonalState& state, cons
         Status s = in.channel(e.label, &label);
         if (!s.ok()) return s;
         if (!label) return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal label channel not found: " + e.label);
-        auto stats = [&](const uint8_t* mask, const float* v, const PointZonalPlan::Stat* sp, size_t k, bool with_points) {
+        auto stats = [&](const uint8_t* mask, const float* v, const CellStatsEntry* sp, size_t k, bool with_points) {
             u64* pts = with_points ? t + e.points_at() : nullptr;
             u64* inf = with_points ? t : nullptr;
             u64* zn = sp ? t + e.stat_at(k) : nullptr;
@@ -200,15 +179,15 @@ Status point_zonal_fold(const PointZonalPlan& plan, PointZonalState& state, cons
         if (rider == e.stats.size() && !(s = stats(in.mask(0), nullptr, nullptr, 0, true)).ok()) return s;
         for (size_t k = 0; k < e.stats.size(); ++k) {
             const float* v = nullptr;
-            if (!(s = in.channel(e.stats[k].channel, &v)).ok()) return s;
-            if (!v) return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal value channel not found: " + e.stats[k].channel);
+            if (!(s = in.channel(e.stats[k].value_channel, &v)).ok()) return s;
+            if (!v) return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal value channel not found: " + e.stats[k].value_channel);
             if (!(s = stats(in.mask(e.stats[k].cls), v, &e.stats[k], k, k == rider)).ok()) return s;
         }
         for (size_t k = 0; k < e.hists.size(); ++k) {
-            const PointZonalPlan::Hist& h = e.hists[k];
+            const HistogramEntry& h = e.hists[k];
             const float* v = nullptr;
-            if (!(s = in.channel(h.channel, &v)).ok()) return s;
-            if (!v) return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal value channel not found: " + h.channel);
+            if (!(s = in.channel(h.value_channel, &v)).ok()) return s;
+            if (!v) return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal value channel not found: " + h.value_channel);
             u64* counts = t + e.hist_at(k);
             s = hip_status(in.device ? pcr_hip_point_fold_hist(label, in.mask(h.cls), v, in.n, h.bins, h.lo, h.inv_w, e.Z, &auto_path, counts,
                                                                nullptr, in.stream)
@@ -220,35 +199,16 @@ Status point_zonal_fold(const PointZonalPlan& plan, PointZonalState& state, cons
     return Status::success();
 }
 
-namespace {
-
-// The columns of one call in one allocation of `loc` memory: pieces are handed out on 256 bytes.
-struct Arena {
-    Buffer buf;
-    size_t used = 0;
-    static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(static_cast<char*>(buf.data()) + used);
-        used += padded(count * sizeof(T));
-        return p;
-    }
-};
-
-}  // namespace
-
 Status point_zonal_table(const PointZonalPlan::Entry& e, const Buffer& table, void* st, bool with_counts, PointZonalTable* out) {
     *out = PointZonalTable();
     using u64 = unsigned long long;
     const MemoryLocation loc = table.location();
-    const bool device = loc == MemoryLocation::Device;
     const u64* t = static_cast<const u64*>(table.data());
-    auto fetch = [&](void* dst, const void* src, size_t bytes) { return copy_bytes(dst, MemoryLocation::Host, src, loc, bytes, st); };
 
     // the info words: what the host has to see before it can size anything
     u64 info[2] = {0, 0};
-    Status s = fetch(info, t, sizeof info);
-    if (device) {
+    Status s = copy_bytes(info, MemoryLocation::Host, t, loc, sizeof info, st);
+    if (loc == MemoryLocation::Device) {
         const Status ws = hip_status(pcr_hip_stream_synchronize(st));
         if (s.ok()) s = ws;
     }
@@ -256,84 +216,7 @@ Status point_zonal_table(const PointZonalPlan::Entry& e, const Buffer& table, vo
     if (info[1] != 0)
         return Status::error(StatusCode::OutOfRange, "pipeline: point_zonal: " + std::to_string(info[1]) + " points of '" + e.label +
                                                      "' carry a zone above max_zones = " + std::to_string(e.Z));
-    const size_t Z = (size_t)info[0];
-    out->stats.resize(e.stats.size());
-    out->hists.resize(e.hists.size());
-    for (size_t k = 0; k < e.stats.size(); ++k) out->stats[k].channel = e.stats[k].channel;
-    for (size_t k = 0; k < e.hists.size(); ++k) {
-        out->hists[k].channel = e.hists[k].channel;
-        out->hists[k].bins = e.hists[k].bins;
-        out->hists[k].q = e.hists[k].q;
-        out->hists[k].p.resize(e.hists[k].q.size());
-    }
-    if (Z == 0) return Status::success();
-
-    // the float columns and hist_n, made where the tables live by the zonal tables' row routines
-    size_t bytes = 0;
-    for (size_t k = 0; k < e.stats.size(); ++k) bytes += 3 * Arena::padded(Z * 4);
-    for (size_t k = 0; k < e.hists.size(); ++k) bytes += Arena::padded(Z * 8) + e.hists[k].q.size() * Arena::padded(Z * 4);
-    Arena a;
-    if (!(s = a.buf.allocate(bytes, loc)).ok()) return s;
-    struct StatCols { float *mean, *var, *sd; };
-    struct HistCols { u64* n; std::vector<float*> p; };
-    std::vector<StatCols> sc(e.stats.size());
-    std::vector<HistCols> hc(e.hists.size());
-    const uint32_t rows = (uint32_t)Z;
-    for (size_t k = 0; k < e.stats.size() && s.ok(); ++k) {
-        const PointZonalPlan::Stat& sp = e.stats[k];
-        const u64* zn = t + e.stat_at(k);
-        const long long* zs1 = reinterpret_cast<const long long*>(zn + e.Z);
-        const u64* zs2 = zn + 2 * (size_t)e.Z;
-        sc[k] = {a.take<float>(Z), a.take<float>(Z), a.take<float>(Z)};
-        s = hip_status(device ? pcr_hip_zone_rows_stats(zn, zs1, zs2, rows, sp.origin, sp.resolution, sp.ddof, sc[k].mean, sc[k].var, sc[k].sd, st)
-                              : pcr_hip_zone_rows_stats_host(zn, zs1, zs2, rows, sp.origin, sp.resolution, sp.ddof, sc[k].mean, sc[k].var,
-                                                             sc[k].sd));
-    }
-    for (size_t k = 0; k < e.hists.size() && s.ok(); ++k) {
-        const PointZonalPlan::Hist& h = e.hists[k];
-        const u64* counts = t + e.hist_at(k);
-        hc[k].n = a.take<u64>(Z);
-        for (size_t j = 0; j < h.q.size(); ++j) hc[k].p.push_back(a.take<float>(Z));
-        const int nq = (int)h.q.size();
-        s = hip_status(device ? pcr_hip_zone_rows_percentiles(counts, h.bins, rows, h.lo, h.w, nq, h.q.data(), hc[k].n, hc[k].p.data(), st)
-                              : pcr_hip_zone_rows_percentiles_host(counts, h.bins, rows, h.lo, h.w, nq, h.q.data(), hc[k].n, hc[k].p.data()));
-    }
-
-    // the table leaves
-    out->zone.resize(Z);
-    for (size_t k = 0; k < Z; ++k) out->zone[k] = (int32_t)(k + 1);
-    out->points.resize(Z);
-    if (s.ok()) s = fetch(out->points.data(), t + e.points_at(), Z * 8);
-    for (size_t k = 0; k < e.stats.size() && s.ok(); ++k) {
-        ZonalTable::StatColumns& c = out->stats[k];
-        c.n.resize(Z);
-        c.mean.resize(Z);
-        c.var.resize(Z);
-        c.stddev.resize(Z);
-        s = fetch(c.n.data(), t + e.stat_at(k), Z * 8);
-        if (s.ok()) s = fetch(c.mean.data(), sc[k].mean, Z * 4);
-        if (s.ok()) s = fetch(c.var.data(), sc[k].var, Z * 4);
-        if (s.ok()) s = fetch(c.stddev.data(), sc[k].sd, Z * 4);
-    }
-    for (size_t k = 0; k < e.hists.size() && s.ok(); ++k) {
-        ZonalTable::HistColumns& c = out->hists[k];
-        c.hist_n.resize(Z);
-        s = fetch(c.hist_n.data(), hc[k].n, Z * 8);
-        if (with_counts) {
-            c.counts.resize(Z * (size_t)c.bins);
-            if (s.ok()) s = fetch(c.counts.data(), t + e.hist_at(k), c.counts.size() * 8);
-        }
-        for (size_t j = 0; j < c.p.size() && s.ok(); ++j) {
-            c.p[j].resize(Z);
-            s = fetch(c.p[j].data(), hc[k].p[j], Z * 4);
-        }
-    }
-    if (device) {
-        const Status ws = hip_status(pcr_hip_stream_synchronize(st));         // (the arena is released behind the copies)
-        if (s.ok()) s = ws;
-    }
-    if (!s.ok()) *out = PointZonalTable();
-    return s;
+    return zone_rows(loc, st, (size_t)info[0], rows_of(e, t), with_counts, out->zone, out->points, out->stats, out->hists);
 }
 
 }  // namespace detail

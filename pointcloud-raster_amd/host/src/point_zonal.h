@@ -1,11 +1,14 @@
 // point_zonal.h -- (internal) what the pipelines and pcr::point_zonal share of PipelineConfig::point_zonal: the ONE plan routine with
 // every refusal (one message each on every engine), the tables' memory, the fold of one ingest -- through the C-ABI's kernels on
-// device memory, through its host twins on host memory -- and the one routine that makes a table.  The arithmetic is
-// csrc/point_zonal.hpp; the contract is in include/pcr_hip.h ("point zonal tables").
+// device memory, through its host twins on host memory -- and the one routine that makes a table.  A spec's refusals and its
+// entry are cell_stats.h's and histogram.h's, the columns of a table zone_rows.h's: what the per-cell zonal tables (zonal.h) use
+// too.  The arithmetic is csrc/point_zonal.hpp; the contract is in include/pcr_hip.h ("point zonal tables").
 #pragma once
 
 #include "../../csrc/point_zonal.hpp"
 #include "buffer.h"
+#include "cell_stats.h"
+#include "histogram.h"
 #include "pcr/engine/pipeline.h"
 #include "pcr_hip.h"
 #include "pipeline_common.h"
@@ -22,24 +25,11 @@ constexpr size_t kMaxPointZonalSpecs = 4;    // stats specs, and histograms, per
 
 /// PipelineConfig::point_zonal as the engines use it.
 struct PointZonalPlan {
-    struct Stat {
-        std::string channel;
-        double origin = 0.0, resolution = 0.0, inv_res = 0.0;
-        int ddof = 0;
-        int cls = 0;                             // its filter class (FilterPlan::pz_stat_class_of)
-    };
-    struct Hist {
-        std::string channel;
-        int bins = 0;
-        double lo = 0.0, inv_w = 0.0, w = 0.0;   // HistogramEntry's constants
-        std::vector<float> q;
-        int cls = 0;
-    };
     struct Entry {
         std::string label;
         uint32_t Z = 0;                          // max_zones
-        std::vector<Stat> stats;
-        std::vector<Hist> hists;
+        std::vector<CellStatsEntry> stats;       // cell_stats.h's and histogram.h's entries, from the same routines: `products`
+        std::vector<HistogramEntry> hists;       // is not read, `cls` is FilterPlan::pz_stat_class_of / pz_hist_class_of
         // The entry's state, 64-bit words: [info 0, info 1][points Z][per stats spec: n Z, s1 Z, s2 Z][per histogram: counts Z * bins]
         size_t words() const;
         size_t points_at() const { return 2; }

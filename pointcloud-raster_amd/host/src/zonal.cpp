@@ -3,9 +3,9 @@
 
 #include "pipeline_common.h"
 #include "polygons.h"
+#include "zone_rows.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 namespace pcr {
@@ -15,26 +15,27 @@ namespace zn = pcrhip::zonal;
 
 namespace {
 
-Status refuse(const std::string& msg) { return Status::error(StatusCode::InvalidArgument, "pipeline: " + msg); }
-
 const std::vector<float>& percentiles_of(const PipelineConfig& cfg, const ZonalConfig& z, int h) {
     return z.own_percentiles ? cfg.histograms[(size_t)h].percentiles : z.percentiles;
+}
+
+// The entry's columns as zone_rows.h names them: channels and percentiles, no table yet.
+ZoneRowsInputs columns_of(const PipelineConfig& cfg, const ZonalConfig& z) {
+    ZoneRowsInputs r;
+    r.stats.resize(z.cell_stats.size());
+    r.hists.resize(z.histograms.size());
+    for (size_t k = 0; k < r.stats.size(); ++k) r.stats[k].channel = cfg.cell_stats[(size_t)z.cell_stats[k]].value_channel;
+    for (size_t k = 0; k < r.hists.size(); ++k) {
+        r.hists[k].channel = cfg.histograms[(size_t)z.histograms[k]].value_channel;
+        r.hists[k].q = percentiles_of(cfg, z, z.histograms[k]);
+    }
+    return r;
 }
 
 }  // namespace
 
 std::vector<std::string> zonal_column_names(const PipelineConfig& cfg, const ZonalConfig& z) {
-    std::vector<std::string> names{"zone", "cells"};
-    for (int x : z.cell_stats) {
-        const std::string& ch = cfg.cell_stats[(size_t)x].value_channel;
-        for (const char* suffix : {"_n", "_mean", "_var", "_std"}) names.push_back(ch + suffix);
-    }
-    for (int h : z.histograms) {
-        const std::string& ch = cfg.histograms[(size_t)h].value_channel;
-        names.push_back(ch + "_hist_n");
-        for (float q : percentiles_of(cfg, z, h)) names.push_back(ch + "_p" + std::to_string(std::lround((double)q * 100.0)));
-    }
-    return names;
+    return zone_column_names("cells", columns_of(cfg, z));
 }
 
 Status zonal_out_of_core_error() {
@@ -84,10 +85,7 @@ Status plan_zonal(const PipelineConfig& cfg, const GroundPlan& ground, const Ter
         for (int h : z.histograms) e.q.push_back(percentiles_of(cfg, z, h));
         if (z.max_zones < 1 || z.max_zones > (int)zn::kMaxZone) return refuse(where + ".max_zones must be between 1 and 2^24");
         e.max_zones = z.max_zones;
-        std::vector<std::string> cols = zonal_column_names(cfg, z);
-        std::sort(cols.begin(), cols.end());
-        const auto dup = std::adjacent_find(cols.begin(), cols.end());
-        if (dup != cols.end()) return refuse(where + ": column '" + *dup + "' appears twice");
+        if (Status s = check_zone_column_names(where, "cells", columns_of(cfg, z)); !s.ok()) return s;
         plan->entries.push_back(std::move(e));
     }
     return Status::success();
@@ -132,30 +130,12 @@ Status store_zones(const PipelineConfig& cfg, const std::string& name, const Gri
     return s;
 }
 
-namespace {
-
-// The tables of one call in one allocation of `loc` memory, zeroed: pieces are handed out on 256 bytes.
-struct Arena {
-    Buffer buf;
-    size_t used = 0;
-    static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    template <class T>
-    T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(static_cast<char*>(buf.data()) + used);
-        used += padded(count * sizeof(T));
-        return p;
-    }
-};
-
-}  // namespace
-
 Status zonal_table(const ZonalPlan::Entry& e, const CellStatsPlan& cstats, const HistogramPlan& hist, const ZonalInputs& in,
                    bool with_counts, ZonalTable* out) {
     *out = ZonalTable();
     const MemoryLocation loc = in.device ? MemoryLocation::Device : MemoryLocation::Host;
     const int W = in.width, H = in.rows;
     pcr_hip_stream st = in.stream;
-    auto fetch = [&](void* dst, const void* src, size_t bytes) { return copy_bytes(dst, MemoryLocation::Host, src, loc, bytes, st); };
 
     // Z: the one value the host has to see before it can size anything
     uint32_t Zmax = 0;
@@ -164,7 +144,7 @@ Status zonal_table(const ZonalPlan::Entry& e, const CellStatsPlan& cstats, const
         Buffer d_max;
         if (!(s = d_max.allocate(sizeof(uint32_t), MemoryLocation::Device)).ok()) return s;
         s = hip_status(pcr_hip_zone_max(in.zones, W, H, W, static_cast<uint32_t*>(d_max.data()), st));
-        if (s.ok()) s = fetch(&Zmax, d_max.data(), sizeof(uint32_t));
+        if (s.ok()) s = copy_bytes(&Zmax, MemoryLocation::Host, d_max.data(), loc, sizeof(uint32_t), st);
         const Status ws = hip_status(pcr_hip_stream_synchronize(st));
         if (s.ok()) s = ws;
     } else {
@@ -175,112 +155,59 @@ Status zonal_table(const ZonalPlan::Entry& e, const CellStatsPlan& cstats, const
         return Status::error(StatusCode::OutOfRange, "pipeline: zonal: zone " + std::to_string(Zmax) + " of '" + e.zones +
                                                      "' is above max_zones = " + std::to_string(e.max_zones));
     const size_t Z = Zmax;
-    out->stats.resize(e.stats.size());
-    out->hists.resize(e.hists.size());
-    for (size_t k = 0; k < e.stats.size(); ++k) out->stats[k].channel = cstats.entries[(size_t)e.stats[k]].value_channel;
+    ZoneRowsInputs rows;
+    for (size_t k = 0; k < e.stats.size(); ++k) {
+        const CellStatsEntry& ce = cstats.entries[(size_t)e.stats[k]];
+        rows.stats.push_back({ce.value_channel, nullptr, nullptr, nullptr, ce.origin, ce.resolution, ce.ddof});
+    }
     for (size_t k = 0; k < e.hists.size(); ++k) {
         const HistogramEntry& he = hist.entries[(size_t)e.hists[k]];
-        out->hists[k].channel = he.value_channel;
-        out->hists[k].bins = he.bins;
-        out->hists[k].q = e.q[k];
-        out->hists[k].p.resize(e.q[k].size());
+        rows.hists.push_back({he.value_channel, nullptr, he.bins, he.lo, he.w, e.q[k]});
     }
-    if (Z == 0) return Status::success();
 
-    size_t bytes = Arena::padded(Z * 8);
-    for (size_t k = 0; k < e.stats.size(); ++k) bytes += 3 * Arena::padded(Z * 8) + 3 * Arena::padded(Z * 4);
-    for (size_t k = 0; k < e.hists.size(); ++k)
-        bytes += Arena::padded(Z * (size_t)out->hists[k].bins * 8) + Arena::padded(Z * 8) + e.q[k].size() * Arena::padded(Z * 4);
+    // the integer tables, zeroed, in one allocation of `loc` memory; the first stats fold counts the cells
     Arena a;
-    if (!(s = a.buf.allocate(bytes, loc)).ok()) return s;
-    if (in.device) s = hip_status(pcr_hip_memset(a.buf.data(), 0, bytes, st));
-    else std::memset(a.buf.data(), 0, bytes);
-    if (!s.ok()) return s;
+    if (Z != 0) {
+        size_t bytes = Arena::padded(Z * 8);
+        for (size_t k = 0; k < e.stats.size(); ++k) bytes += 3 * Arena::padded(Z * 8);
+        for (size_t k = 0; k < e.hists.size(); ++k) bytes += Arena::padded(Z * (size_t)rows.hists[k].bins * 8);
+        if (!(s = a.buf.allocate(bytes, loc)).ok()) return s;
+        if (in.device) s = hip_status(pcr_hip_memset(a.buf.data(), 0, bytes, st));
+        else std::memset(a.buf.data(), 0, bytes);
+        if (!s.ok()) return s;
 
-    const pcr_hip_zone_fold_params fold{1, 0};
-    unsigned long long* cells = a.take<unsigned long long>(Z);
-    struct StatTables { unsigned long long* n; long long* s1; unsigned long long* s2; float *mean, *var, *sd; };
-    struct HistTables { unsigned long long* counts; unsigned long long* n; std::vector<float*> p; };
-    std::vector<StatTables> st_tab(e.stats.size());
-    std::vector<HistTables> hi_tab(e.hists.size());
-    if (e.stats.empty()) {                               // (cells alone)
-        s = in.device ? hip_status(pcr_hip_zone_fold_stats(in.zones, W, H, W, nullptr, nullptr, nullptr, W, Zmax, &fold, cells, nullptr,
-                                                           nullptr, nullptr, st))
-                      : hip_status(pcr_hip_zone_fold_stats_host(in.zones, W, H, W, nullptr, nullptr, nullptr, W, Zmax, &fold, cells, nullptr,
-                                                                nullptr, nullptr));
-    }
-    for (size_t k = 0; k < e.stats.size() && s.ok(); ++k) {
-        const CellStatsEntry& ce = cstats.entries[(size_t)e.stats[k]];
-        const ZonalInputs::Stat& p = in.stats[(size_t)e.stats[k]];
-        StatTables& t = st_tab[k];
-        t.n = a.take<unsigned long long>(Z);
-        t.s1 = a.take<long long>(Z);
-        t.s2 = a.take<unsigned long long>(Z);
-        t.mean = a.take<float>(Z);
-        t.var = a.take<float>(Z);
-        t.sd = a.take<float>(Z);
-        unsigned long long* c = k == 0 ? cells : nullptr;        // the first entry's fold counts the cells
-        if (in.device) {
-            s = hip_status(pcr_hip_zone_fold_stats(in.zones, W, H, W, p.n, p.s1, p.s2, W, Zmax, &fold, c, t.n, t.s1, t.s2, st));
-            if (s.ok()) s = hip_status(pcr_hip_zone_rows_stats(t.n, t.s1, t.s2, Zmax, ce.origin, ce.resolution, ce.ddof, t.mean, t.var, t.sd, st));
-        } else {
-            s = hip_status(pcr_hip_zone_fold_stats_host(in.zones, W, H, W, p.n, p.s1, p.s2, W, Zmax, &fold, c, t.n, t.s1, t.s2));
-            if (s.ok()) s = hip_status(pcr_hip_zone_rows_stats_host(t.n, t.s1, t.s2, Zmax, ce.origin, ce.resolution, ce.ddof, t.mean, t.var, t.sd));
+        const pcr_hip_zone_fold_params fold{1, 0};
+        auto fold_stats = [&](const ZonalInputs::Stat& p, unsigned long long* cells, unsigned long long* n, long long* s1, unsigned long long* s2) {
+            return hip_status(in.device ? pcr_hip_zone_fold_stats(in.zones, W, H, W, p.n, p.s1, p.s2, W, Zmax, &fold, cells, n, s1, s2, st)
+                                        : pcr_hip_zone_fold_stats_host(in.zones, W, H, W, p.n, p.s1, p.s2, W, Zmax, &fold, cells, n, s1, s2));
+        };
+        unsigned long long* cells = a.take<unsigned long long>(Z);
+        rows.count = cells;
+        if (e.stats.empty()) s = fold_stats({nullptr, nullptr, nullptr}, cells, nullptr, nullptr, nullptr);       // (cells alone)
+        for (size_t k = 0; k < e.stats.size() && s.ok(); ++k) {
+            unsigned long long* n = a.take<unsigned long long>(Z);
+            long long* s1 = a.take<long long>(Z);
+            unsigned long long* s2 = a.take<unsigned long long>(Z);
+            s = fold_stats(in.stats[(size_t)e.stats[k]], k == 0 ? cells : nullptr, n, s1, s2);
+            rows.stats[k].n = n;
+            rows.stats[k].s1 = s1;
+            rows.stats[k].s2 = s2;
+        }
+        for (size_t k = 0; k < e.hists.size() && s.ok(); ++k) {
+            const int bins = rows.hists[k].bins;
+            const uint32_t* cube = in.cubes[(size_t)e.hists[k]];
+            unsigned long long* counts = a.take<unsigned long long>(Z * (size_t)bins);
+            const int64_t plane = (int64_t)W * H;
+            s = hip_status(in.device ? pcr_hip_zone_fold_hist(in.zones, W, H, W, cube, bins, W, plane, Zmax, &fold, counts, st)
+                                     : pcr_hip_zone_fold_hist_host(in.zones, W, H, W, cube, bins, W, plane, Zmax, &fold, counts));
+            rows.hists[k].counts = counts;
+        }
+        if (!s.ok()) {
+            if (in.device) (void)pcr_hip_stream_synchronize(st);     // (the arena is released behind what was enqueued)
+            return s;
         }
     }
-    for (size_t k = 0; k < e.hists.size() && s.ok(); ++k) {
-        const HistogramEntry& he = hist.entries[(size_t)e.hists[k]];
-        const uint32_t* cube = in.cubes[(size_t)e.hists[k]];
-        HistTables& t = hi_tab[k];
-        t.counts = a.take<unsigned long long>(Z * (size_t)he.bins);
-        t.n = a.take<unsigned long long>(Z);
-        for (size_t j = 0; j < e.q[k].size(); ++j) t.p.push_back(a.take<float>(Z));
-        const int64_t plane = (int64_t)W * H;
-        const int nq = (int)e.q[k].size();
-        if (in.device) {
-            s = hip_status(pcr_hip_zone_fold_hist(in.zones, W, H, W, cube, he.bins, W, plane, Zmax, &fold, t.counts, st));
-            if (s.ok()) s = hip_status(pcr_hip_zone_rows_percentiles(t.counts, he.bins, Zmax, he.lo, he.w, nq, e.q[k].data(), t.n, t.p.data(), st));
-        } else {
-            s = hip_status(pcr_hip_zone_fold_hist_host(in.zones, W, H, W, cube, he.bins, W, plane, Zmax, &fold, t.counts));
-            if (s.ok()) s = hip_status(pcr_hip_zone_rows_percentiles_host(t.counts, he.bins, Zmax, he.lo, he.w, nq, e.q[k].data(), t.n, t.p.data()));
-        }
-    }
-
-    // the table leaves
-    out->zone.resize(Z);
-    for (size_t k = 0; k < Z; ++k) out->zone[k] = (int32_t)(k + 1);
-    out->cells.resize(Z);
-    if (s.ok()) s = fetch(out->cells.data(), cells, Z * 8);
-    for (size_t k = 0; k < e.stats.size() && s.ok(); ++k) {
-        ZonalTable::StatColumns& c = out->stats[k];
-        c.n.resize(Z);
-        c.mean.resize(Z);
-        c.var.resize(Z);
-        c.stddev.resize(Z);
-        s = fetch(c.n.data(), st_tab[k].n, Z * 8);
-        if (s.ok()) s = fetch(c.mean.data(), st_tab[k].mean, Z * 4);
-        if (s.ok()) s = fetch(c.var.data(), st_tab[k].var, Z * 4);
-        if (s.ok()) s = fetch(c.stddev.data(), st_tab[k].sd, Z * 4);
-    }
-    for (size_t k = 0; k < e.hists.size() && s.ok(); ++k) {
-        ZonalTable::HistColumns& c = out->hists[k];
-        c.hist_n.resize(Z);
-        s = fetch(c.hist_n.data(), hi_tab[k].n, Z * 8);
-        if (with_counts) {
-            c.counts.resize(Z * (size_t)c.bins);
-            if (s.ok()) s = fetch(c.counts.data(), hi_tab[k].counts, c.counts.size() * 8);
-        }
-        for (size_t j = 0; j < c.p.size() && s.ok(); ++j) {
-            c.p[j].resize(Z);
-            s = fetch(c.p[j].data(), hi_tab[k].p[j], Z * 4);
-        }
-    }
-    if (in.device) {
-        const Status ws = hip_status(pcr_hip_stream_synchronize(st));     // (the arena is released behind the copies)
-        if (s.ok()) s = ws;
-    }
-    if (!s.ok()) *out = ZonalTable();
-    return s;
+    return zone_rows(loc, st, Z, rows, with_counts, out->zone, out->cells, out->stats, out->hists);
 }
 
 }  // namespace detail

@@ -1,7 +1,8 @@
 // zonal.h -- (internal) what the pipelines share of PipelineConfig::zonal: the checks at create with one message each on every
 // engine, the plan (the label band's index, the chosen entries, the column names), the label grids of set_zones, and the one
-// routine that makes a table -- through the C-ABI's kernels on device memory, through its host twins on host memory.  The
-// arithmetic is csrc/zonal.hpp; the contract is in include/pcr_hip.h ("zonal tables").
+// routine that makes a table -- through the C-ABI's kernels on device memory, through its host twins on host memory: the folds
+// here, the columns from the folded tables in zone_rows.h, which the point zonal tables (point_zonal.h) share.  The arithmetic
+// is csrc/zonal.hpp; the contract is in include/pcr_hip.h ("zonal tables").
 #pragma once
 
 #include "../../csrc/zonal.hpp"

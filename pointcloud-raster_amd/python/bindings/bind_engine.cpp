@@ -9,34 +9,34 @@
 #include "pcr/engine/sharded_pipeline.h"
 #include "../../host/src/ground_filter.h"
 #include "../../host/src/terrain.h"
+#include "../../host/src/zone_rows.h"
 
 using namespace pcr;
 
 namespace {
 
-// Pipeline.point_zonal's and pcr.point_zonal's dict: Pipeline.zonal's columns with `points` for `cells`.
-py::dict point_zonal_dict(const PointZonalTable& t) {
-    auto column = [](const auto& v) {
+// Pipeline.zonal's, Pipeline.point_zonal's and pcr.point_zonal's dict: the columns of zone_rows.h, `count` as "cells" or "points".
+py::dict zone_dict(const std::vector<int32_t>& zone, const char* count_name, const std::vector<int64_t>& count,
+                   const std::vector<ZonalTable::StatColumns>& stats, const std::vector<ZonalTable::HistColumns>& hists) {
+    py::dict d;
+    detail::for_each_zone_column(zone, count_name, count, stats, hists, [&d](const std::string& name, const auto& v) {
         using T = typename std::decay_t<decltype(v)>::value_type;
         py::array_t<T> a((py::ssize_t)v.size());
         if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
-        return a;
-    };
-    py::dict d;
-    d["zone"] = column(t.zone);
-    d["points"] = column(t.points);
-    for (const auto& c : t.stats) {
-        d[py::str(c.channel + "_n")] = column(c.n);
-        d[py::str(c.channel + "_mean")] = column(c.mean);
-        d[py::str(c.channel + "_var")] = column(c.var);
-        d[py::str(c.channel + "_std")] = column(c.stddev);
-    }
-    for (const auto& c : t.hists) {
-        d[py::str(c.channel + "_hist_n")] = column(c.hist_n);
-        for (size_t j = 0; j < c.q.size(); ++j)
-            d[py::str(c.channel + "_p" + std::to_string(std::lround((double)c.q[j] * 100.0)))] = column(c.p[j]);
-    }
+        d[py::str(name)] = a;
+    });
     return d;
+}
+py::dict point_zonal_dict(const PointZonalTable& t) { return zone_dict(t.zone, "points", t.points, t.stats, t.hists); }
+
+// Pipeline.zonal_histogram's and Pipeline.point_zonal_histogram's array: the (zones, bins) counts of the h-th histogram.
+py::array_t<uint64_t> zone_histogram(const char* fn, size_t zones, const std::vector<ZonalTable::HistColumns>& hists, int h) {
+    if (h < 0 || (size_t)h >= hists.size())
+        throw std::runtime_error(std::string("pipeline: ") + fn + ": no histogram " + std::to_string(h) + " in the entry");
+    const auto& c = hists[(size_t)h];
+    py::array_t<uint64_t> a({(py::ssize_t)zones, (py::ssize_t)c.bins});
+    if (!c.counts.empty()) std::memcpy(a.mutable_data(), c.counts.data(), c.counts.size() * sizeof(uint64_t));
+    return a;
 }
 
 }  // namespace
@@ -478,27 +478,7 @@ void bind_engine(py::module_& m) {
         .def("zonal", [](const Pipeline& p, int i) {
             ZonalTable t;
             raise_if_error(p.zonal(i, &t));
-            auto column = [](const auto& v) {
-                using T = typename std::decay_t<decltype(v)>::value_type;
-                py::array_t<T> a((py::ssize_t)v.size());
-                if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(T));
-                return a;
-            };
-            py::dict d;
-            d["zone"] = column(t.zone);
-            d["cells"] = column(t.cells);
-            for (const auto& c : t.stats) {
-                d[py::str(c.channel + "_n")] = column(c.n);
-                d[py::str(c.channel + "_mean")] = column(c.mean);
-                d[py::str(c.channel + "_var")] = column(c.var);
-                d[py::str(c.channel + "_std")] = column(c.stddev);
-            }
-            for (const auto& c : t.hists) {
-                d[py::str(c.channel + "_hist_n")] = column(c.hist_n);
-                for (size_t j = 0; j < c.q.size(); ++j)
-                    d[py::str(c.channel + "_p" + std::to_string(std::lround((double)c.q[j] * 100.0)))] = column(c.p[j]);
-            }
-            return d;
+            return zone_dict(t.zone, "cells", t.cells, t.stats, t.hists);
         }, py::arg("i") = 0,
              "The table of zonal entry i as a dict of numpy arrays: zone (int32), cells (int64), per cell_stats entry "
              "{channel}_n (uint64), _mean, _var, _std (float32), per histogram {channel}_hist_n (uint64) and {channel}_p{round(q*100)} "
@@ -506,11 +486,7 @@ void bind_engine(py::module_& m) {
         .def("zonal_histogram", [](const Pipeline& p, int i, int h) {
             ZonalTable t;
             raise_if_error(p.zonal(i, &t, true));
-            if (h < 0 || (size_t)h >= t.hists.size()) throw std::runtime_error("pipeline: zonal_histogram: no histogram " + std::to_string(h) + " in the entry");
-            const auto& c = t.hists[(size_t)h];
-            py::array_t<uint64_t> a({(py::ssize_t)t.size(), (py::ssize_t)c.bins});
-            if (!c.counts.empty()) std::memcpy(a.mutable_data(), c.counts.data(), c.counts.size() * sizeof(uint64_t));
-            return a;
+            return zone_histogram("zonal_histogram", t.size(), t.hists, h);
         }, py::arg("i") = 0, py::arg("h") = 0,
              "The (zones, bins) uint64 counts of the h-th histogram chosen by zonal entry i")
         .def("point_zonal", [](const Pipeline& p, int i) {
@@ -524,12 +500,7 @@ void bind_engine(py::module_& m) {
         .def("point_zonal_histogram", [](const Pipeline& p, int i, int h) {
             PointZonalTable t;
             raise_if_error(p.point_zonal(i, &t, true));
-            if (h < 0 || (size_t)h >= t.hists.size())
-                throw std::runtime_error("pipeline: point_zonal_histogram: no histogram " + std::to_string(h) + " in the entry");
-            const auto& c = t.hists[(size_t)h];
-            py::array_t<uint64_t> a({(py::ssize_t)t.size(), (py::ssize_t)c.bins});
-            if (!c.counts.empty()) std::memcpy(a.mutable_data(), c.counts.data(), c.counts.size() * sizeof(uint64_t));
-            return a;
+            return zone_histogram("point_zonal_histogram", t.size(), t.hists, h);
         }, py::arg("i") = 0, py::arg("h") = 0, "The (zones, bins) uint64 counts of the h-th histogram of point_zonal entry i")
         .def("finalize", [](Pipeline& p) { raise_if_error(p.finalize()); })
         .def("finalize_async", [](Pipeline& p) { raise_if_error(p.finalize_async()); },

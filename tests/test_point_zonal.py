@@ -347,6 +347,38 @@ def test_equals_the_per_cell_table_when_every_point_has_its_cells_zone():
     P.bits_equal(p.point_zonal_histogram(0, 0), p.zonal_histogram(0, 0), "the counts")
 
 
+def test_specs_whose_constants_round_give_both_tables_the_same_bits():
+    """lo = 0.1, hi = 37.3, bins = 7 and resolution = 0.03: 1 / resolution, bins / (hi - lo) and (hi - lo) / bins all round, so
+    the two tables agree only while one routine makes a spec's constants for both.  A few hundred points on a 16 x 16 grid, each
+    labelled with its cell's zone."""
+    import overviews_common as OC
+    import reduction_filters_common as RF
+    import sample_grid_common as SG
+    g = dict(min_x=0.0, min_y=0.0, max_x=16.0, max_y=16.0, cs=1.0, W=16, H=16, tw=16, th=16)
+    labels = ZC.plot_labels(16, 16, plot=4)
+    rng = np.random.default_rng(9)
+    n = 300
+    c = dict(x=rng.uniform(0.01, 15.99, n), y=rng.uniform(0.01, 15.99, n), z=rng.uniform(-3.0, 41.0, n).astype(F32))
+    c["z"][::29] = np.nan
+    c["plot"] = labels[np.floor(16.0 - c["y"]).astype(int), np.floor(c["x"]).astype(int)]
+    cs = pcr.CellStatsConfig("z", 0.7, 0.03, [pcr.CellStat.Mean], 1)
+    h = pcr.HistogramConfig("z", 0.1, 37.3, 7, [0.1, 0.5, 0.9])
+    cfg = RF.make_config("cpu", [RF.S("Count", ch="z")], (), g, cell_stats=[cs], histograms=[h],
+                         zonal=[pcr.ZonalConfig("plots", external=True, cell_stats=[0], histograms=[0])],
+                         point_zonal=[pcr.PointZonalConfig("plot", [cs], [h], 64)])
+    p = pcr.Pipeline.create(cfg)
+    assert p is not None, pcr.pipeline_create_error()
+    p.ingest(SG.dict_cloud(pcr, c))
+    p.finalize()
+    p.set_zones("plots", OC.make_grid([labels]))
+    per_cell, per_point = p.zonal(0), p.point_zonal(0)
+    assert list(per_cell)[2:] == list(per_point)[2:] == ["z_n", "z_mean", "z_var", "z_std", "z_hist_n", "z_p10", "z_p50", "z_p90"]
+    assert len(per_point["zone"]) == len(per_cell["zone"]) == ZC.zone_max(labels) and int(per_point["z_n"].sum()) > 200
+    for k in list(per_cell)[2:]:
+        P.bits_equal(per_point[k], per_cell[k], f"column {k}")
+    P.bits_equal(p.point_zonal_histogram(0, 0), p.zonal_histogram(0, 0), "the counts")
+
+
 # ---- 5: why the feature exists ---------------------------------------------------------------------------------------------------
 def test_a_plots_count_is_exact_where_the_cell_route_is_not():
     """One triangular plot on a 10 m grid, points on a 1 m lattice off every cell centre and edge: the `points` column is NumPy's
