@@ -1100,6 +1100,72 @@ int pcr_hip_point_fold_hist_host(const float* h_label, const uint8_t* h_mask, co
                                  double inv_w, uint32_t Z, const pcr_hip_point_fold_params* params, unsigned long long* h_zcounts,
                                  unsigned long long* h_info);
 
+/* ---- polygonize: the zones of a Float32 label band as outlines (pcr/core/polygons.h: polygonize; Pipeline::polygonize) -- the
+ *      inverse of "polygons" above, gdal_polygonize's 4-connected rule: crowns from a tree-id band, a zone map as polygons.  No
+ *      reference counterpart.  The rule is written once, in csrc/polygonize.hpp, which the kernels and the host twin compile:
+ *      they agree bit for bit, and burning the result back with pcr_hip_rasterize_polygons on the same geometry gives the band's
+ *      zones cell for cell.
+ *        zone     "zonal tables"' rule: the band's value when it is a whole number in [1, 2^24]; NaN of any payload, +-Inf, 0,
+ *                 negatives, fractions, values above 2^24 and cells outside the band are no zone
+ *        lattice  corner (i, j), i in 0..height, j in 0..width; cell (r, c) has the corners (r, c), (r, c+1), (r+1, c+1), (r+1, c)
+ *        edge     side s of a zone cell -- 0 top, 1 right, 2 bottom, 3 left -- is a boundary edge when the cell across it has
+ *                 another zone or none.  It is directed with the cell on its right hand in (row-down, column-right) index space:
+ *                 top towards +column, right towards +row, bottom towards -column, left towards -row.  Its slot is
+ *                 4 * (r * width + c) + s, a uint32.
+ *        next     F = the unit step of direction s, O = that of direction (s + 3) % 4, the outward normal; ahead = the zone of
+ *                 cell + F, diag = that of cell + F + O.  ahead != z: (r, c, (s + 1) % 4), a right turn, also at a saddle
+ *                 (diag == z): regions are 4-connected.  Else diag == z: (cell + F + O, (s + 3) % 4), a left turn.  Else
+ *                 (cell + F, s), straight on.  A permutation of each zone's boundary edges whose cycles are the rings: simple
+ *                 lattice polygons; rings of one zone may touch at corners and never share an edge.
+ *        corner   an edge whose predecessor has another side number.  A ring's vertices are the start corners of its corner
+ *                 edges in cycle order, starting at the corner edge of smallest slot, the ring's key: at least 4, no three
+ *                 consecutive ones collinear.
+ *        table    R rings by ascending key: ring_zone[R] uint32, ring_offset[R + 1] int64 into the V vertices,
+ *                 vertex_row[V] and vertex_col[V] int32 lattice corners.  No geometry crosses this interface: the caller groups
+ *                 the rings by zone (stable, so a polygon's rings stay in key order; a polygon is all rings of its zone under
+ *                 the even-odd rule, holes and parts unmarked) and places corner (i, j) at x = min_x + (double)j * cell_size_x,
+ *                 y = max_y + (double)i * cell_size_y, one rounded product and one rounded sum each.
+ *      Refused, before any HIP call and with the same message by the host twin: a null argument; a non-positive width or height;
+ *      a stride below the width; more than 2^30 - 1 cells (slots fit 32 bits with a sentinel to spare); a work area below its
+ *      _work_bytes, or one that overlaps the band or the other; outputs that overlap an input, a work area or each other.  A band
+ *      without any zone has E = 0 and is no error: the caller stops there.
+ *      Everything is enqueued on s; nothing is allocated; only _count waits.  In order:
+ *      pcr_hip_polygonize_edges: d_cells_work, the caller's, of pcr_hip_polygonize_cells_work_bytes(width, height) bytes (2 per
+ *      cell; answered without a device): per cell its boundary sides and its edges' place in the compact edge list, which is in
+ *      slot order; E.
+ *      pcr_hip_polygonize_count: after synchronising with s, E, and once _rings ran R, V and the number of rounds of each
+ *      doubling phase that changed something (at most ceil(log2 E) + 1 each).  Any but n_edges may be NULL.
+ *      pcr_hip_polygonize_rings: n_edges = E >= 1; d_rings_work of pcr_hip_polygonize_rings_work_bytes(E) bytes (29 per edge).
+ *      Per edge its successor and corner flag; the ring keys by minimum-doubling over the cycles (m = min(m, m[j]), j = j[j] from
+ *      one buffer into another, ceil(log2 E) + 1 rounds, a round returning at once when the one before lowered no m); the
+ *      vertex ranks by a second doubling over the cycles cut at their key edges; R and V by a scan over the key edges.  No
+ *      result depends on the order of execution; the only atomic is the relaxed store of 1 into a round's "changed" word.
+ *      params: NULL, or events (pcr_hip_event_create) recorded on s behind the edge list, the key rounds, the rank rounds and
+ *      the scan (tools/polygonize_time.py).
+ *      pcr_hip_polygonize_fetch: n_rings = R and n_vertices = V as _count gave them; the table into the caller's DEVICE arrays.
+ *      pcr_hip_polygonize_host: the twin on host arrays, one thread: slots in ascending order, every unvisited corner edge's
+ *      cycle walked with the successor rule -- another algorithm than the kernels'.  The counts always; the table when R <=
+ *      ring_capacity and V <= vertex_capacity (the arrays may be NULL). */
+typedef struct pcr_hip_polygonize_params {
+    void* events[4];                 /* NULL, or events to record: behind the edge list, the key rounds, the rank rounds, the scan */
+} pcr_hip_polygonize_params;
+int pcr_hip_polygonize_cells_work_bytes(int width, int height, size_t* bytes);
+int pcr_hip_polygonize_rings_work_bytes(int64_t n_edges, size_t* bytes);
+int pcr_hip_polygonize_edges(const float* d_band, int width, int height, int64_t stride, void* d_cells_work, size_t cells_work_bytes,
+                             pcr_hip_stream s);
+int pcr_hip_polygonize_count(const void* d_cells_work, size_t cells_work_bytes, int64_t* n_edges, int64_t* n_rings, int64_t* n_vertices,
+                             int* key_rounds_worked, int* rank_rounds_worked, pcr_hip_stream s);
+int pcr_hip_polygonize_rings(const float* d_band, int width, int height, int64_t stride, const void* d_cells_work, size_t cells_work_bytes,
+                             int64_t n_edges, void* d_rings_work, size_t rings_work_bytes, const pcr_hip_polygonize_params* params,
+                             pcr_hip_stream s);
+int pcr_hip_polygonize_fetch(const float* d_band, int width, int height, int64_t stride, const void* d_cells_work, size_t cells_work_bytes,
+                             int64_t n_edges, void* d_rings_work, size_t rings_work_bytes, int64_t n_rings, int64_t n_vertices,
+                             uint32_t* d_ring_zone, int64_t* d_ring_offset, int32_t* d_vertex_row, int32_t* d_vertex_col,
+                             pcr_hip_stream s);
+int pcr_hip_polygonize_host(const float* h_band, int width, int height, int64_t stride, int64_t* n_edges, int64_t* n_rings,
+                            int64_t* n_vertices, int64_t ring_capacity, int64_t vertex_capacity, uint32_t* h_ring_zone,
+                            int64_t* h_ring_offset, int32_t* h_vertex_row, int32_t* h_vertex_col);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,7 @@ def build_host(force=False):
     hdrs.append(os.path.join(HERE, "csrc", "zonal.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "point_zonal.hpp"))
     hdrs.append(os.path.join(HERE, "csrc", "rasterize.hpp"))
+    hdrs.append(os.path.join(HERE, "csrc", "polygonize.hpp"))
     for d in src_dirs:                                   # the internal headers next to the sources
         hdrs += [os.path.join(d, f) for f in os.listdir(d) if f.endswith(".h")]
     hdr_t = newest(hdrs)

@@ -57,6 +57,28 @@ std::unique_ptr<Grid> rasterize_polygons(const PolygonSet& polygons, const GridC
                                          const RasterizeOptions& options = RasterizeOptions(), Status* status = nullptr,
                                          void* stream = nullptr);
 
+/// The other way round: the zones of band `band` of `grid` as polygons, where the grid lives -- gdal_polygonize's 4-connected
+/// outlines: crowns from a tree-id band, a zone map for a GIS.  The contract, one definition for host and device
+/// (csrc/polygonize.hpp, include/pcr_hip.h: "polygonize"):
+///   zone     the zonal tables' rule: a whole number in [1, 2^24]; NaN, +-Inf, 0, negatives, fractions and greater values are none
+///   edge     a side of a zone cell whose neighbour has another zone or none, directed with the cell on its right hand
+///   ring     a cycle of the successor rule (right turn first, so a saddle separates: regions are 4-connected), reduced to its
+///            corners, from the corner edge of smallest slot 4 * (r * width + c) + side, the ring's key: a simple lattice polygon
+///            of at least 4 vertices, no three in a row collinear
+///   set      one polygon per zone present, by ascending zone, its rings by ascending key, its value the zone; a polygon is all of
+///            its rings under the even-odd rule -- PolygonSet's own meaning: holes and parts are not marked
+///   world    corner (i, j) lies at x = min_x + (double)j * cell_size_x, y = max_y + (double)i * cell_size_y of `geometry`
+/// so that rasterize_polygons of the result on the same geometry gives the band's zones back cell for cell (where every cell
+/// centre rounds strictly between its corners).  Host: the host twin, a sequential trace.  Device: the kernels on `stream`
+/// (pointer doubling), which is waited for; only the ring table crosses PCIe.  Both give the same set bit for bit.  A band
+/// without a zone gives an empty set.  `geometry` null: the grid's own (Grid::geometry).  An empty set and `status` on failure:
+/// InvalidArgument for a band outside the grid or not Float32, no geometry, one whose width and height are not the grid's, more
+/// than 2^30 - 1 cells.
+/// Not done: 8-connectivity, simplified or smoothed outlines, bands of arbitrary values, shards, out-of-core and sharded
+/// pipelines, shapefile or GeoPackage output.
+PolygonSet polygonize(const Grid& grid, int band = 0, const GridConfig* geometry = nullptr, Status* status = nullptr,
+                      void* stream = nullptr);
+
 struct PointInPolygonOptions {
     float background = std::numeric_limits<float>::quiet_NaN();      // points outside every polygon (any bits are kept)
     int index_cols = 0, index_rows = 0;                              // the index: 0 automatic, or 1 .. 2048 (tests, tuning)

@@ -505,6 +505,14 @@ public:
     /// index outside the list; OutOfRange while the overflow counter is nonzero (a kept point carried a zone above max_zones).
     /// with_counts: also copy out every histogram's [zone][bin] counts.
     Status point_zonal(int i, PointZonalTable* out, bool with_counts = false) const;
+    /// Extension: the zones of the result's band `band_name` as polygons on PipelineConfig::grid (pcr/core/polygons.h: polygonize)
+    /// -- the crowns of a "..._tree_id" band, whose polygon of value z belongs to row z - 1 of zonal(i) and trees(i).  The set
+    /// comes from the band as the last finalize() left it and is valid under zonal(i)'s condition: after a finalize with no ingest
+    /// since.  On the HIP engine it is made in HBM behind everything on the pipeline's stream, in work areas of the call's own, and
+    /// only the ring table crosses PCIe; the host engine runs the host twin: the same set bit for bit.  InvalidArgument for a name
+    /// that is no Float32 band of the result, before the first finalize, after a further ingest, for a row-block shard and for an
+    /// out-of-core pipeline.
+    Status polygonize(const std::string& band_name, PolygonSet* out) const;
     Status finalize();
     /// Extension, the counterpart of ingest_async: with a device-resident result (result_location = Device, no output_path)
     /// the finalize kernels are only ENQUEUED on the pipeline's stream -- result() is valid at once, its bands are complete

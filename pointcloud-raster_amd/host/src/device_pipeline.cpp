@@ -7,6 +7,7 @@
 #include "fill_nodata.h"
 #include "ground_filter.h"
 #include "overviews.h"
+#include "polygonize.h"
 #include "pcr/core/point_cloud.h"
 #include "pcr/io/grid_io.h"
 
@@ -458,6 +459,14 @@ Status Pipeline::Impl::zonal(int i, ZonalTable* out, bool with_counts) {
     for (const auto& c : cubes) in.cubes.push_back(static_cast<const uint32_t*>(c.data()));
     DeviceScope dev(cfg.cuda_device_id);
     return detail::zonal_table(e, cstats, hist, in, with_counts, out);
+}
+// The zones of a band of the result as polygons, behind the last finalize on the pipeline's stream: the band as it left the
+// pipeline (`out`), in HBM.  Nothing of it runs in finalize: no plane-state event.
+Status Pipeline::Impl::polygonize(const std::string& band_name, PolygonSet* out) {
+    int b = -1;
+    if (Status s = detail::polygonize_check(cfg, out, finalized && zonal_fresh, result.get(), band_name, &b); !s.ok()) return s;
+    DeviceScope dev(cfg.cuda_device_id);
+    return detail::polygonize_band(bands[(size_t)b].out, cfg.grid, MemoryLocation::Device, stream, out);
 }
 Status Pipeline::Impl::touched_flags(uint32_t** d, int* tx, int* ty) const {
     return detail::hip_status(pcr_hip_engine_tile_touched(engine, d, tx, ty));

@@ -200,6 +200,7 @@ struct Pipeline::Impl {
     Status set_zones(const std::string& name, const Grid& grid, int band);
     Status set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options);
     Status zonal(int i, ZonalTable* out, bool with_counts);
+    Status polygonize(const std::string& band_name, PolygonSet* out);
     Status point_zonal(int i, PointZonalTable* out, bool with_counts);
     Status touched_flags(uint32_t** d, int* tx = nullptr, int* ty = nullptr) const;
     bool offer_bands(size_t gi);

@@ -3,6 +3,7 @@
 
 #include "fill_nodata.h"
 #include "ground_filter.h"
+#include "polygonize.h"
 #include "terrain.h"
 #include "trees.h"
 #include "pcr/core/point_cloud.h"
@@ -104,6 +105,13 @@ Status Pipeline::Host::zonal(int i, ZonalTable* out, bool with_counts) const {
         in.stats.push_back({p.n.data(), reinterpret_cast<const long long*>(p.s1.data()), reinterpret_cast<const unsigned long long*>(p.s2.data())});
     for (const auto& c : cubes) in.cubes.push_back(c.data());
     return detail::zonal_table(e, cstats, hist, in, with_counts, out);
+}
+
+// The zones of a band of the result as polygons, by the host twin.
+Status Pipeline::Host::polygonize(const std::string& band_name, PolygonSet* out) const {
+    int b = -1;
+    if (Status s = detail::polygonize_check(cfg, out, finalized && zonal_fresh, result.get(), band_name, &b); !s.ok()) return s;
+    return detail::polygonize_band(result->band_f32(b), cfg.grid, MemoryLocation::Host, nullptr, out);
 }
 
 // PipelineConfig::point_zonal: entry i's rows through the C-ABI's host twins, from the tables as the ingests left them.

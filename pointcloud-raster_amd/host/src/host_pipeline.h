@@ -69,6 +69,7 @@ struct Pipeline::Host {
     Status set_zones(const std::string& name, const Grid& grid, int band);
     Status set_zones(const std::string& name, const PolygonSet& polygons, const RasterizeOptions& options);
     Status zonal(int i, ZonalTable* out, bool with_counts) const;
+    Status polygonize(const std::string& band_name, PolygonSet* out) const;
     Status point_zonal(int i, PointZonalTable* out, bool with_counts) const;
     Status save_state(const std::string& dir);
     Status load_state(const std::string& dir);

@@ -408,6 +408,11 @@ Status Pipeline::point_zonal(int i, PointZonalTable* out, bool with_counts) cons
     if (host_) return host_->point_zonal(i, out, with_counts);
     return Status::error(StatusCode::InvalidArgument, "pipeline: point_zonal: no point_zonal entry " + std::to_string(i));
 }
+Status Pipeline::polygonize(const std::string& band_name, PolygonSet* out) const {
+    if (impl_) return impl_->polygonize(band_name, out);
+    if (host_) return host_->polygonize(band_name, out);
+    return Status::error(StatusCode::InvalidArgument, "pipeline: polygonize: not on an out-of-core pipeline");
+}
 Status Pipeline::finalize() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(); }
 Status Pipeline::finalize_async() { return host_ ? host_->finalize() : banded_ ? banded_->finalize() : impl_->finalize(false); }
 

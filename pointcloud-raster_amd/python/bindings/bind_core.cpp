@@ -504,6 +504,18 @@ void bind_core(py::module_& m) {
        py::arg("background") = std::numeric_limits<float>::quiet_NaN(), py::arg("index_cols") = 0, py::arg("index_rows") = 0,
        "Adds (or overwrites) the Float32 channel `channel`: per point the value of the greatest-index polygon that holds the point "
        "(p + 1, or the set's values), `background` elsewhere -- exact, where a label grid sampled Nearest gives the cell's");
+    // extension: the other way round, the zones of a band as polygons (pcr.polygonize, Pipeline.polygonize)
+    m.def("polygonize", [](const Grid& grid, int band, py::object grid_config) {
+        Status s;
+        GridConfig g;
+        if (!grid_config.is_none()) g = grid_config.cast<GridConfig>();
+        PolygonSet out = polygonize(grid, band, grid_config.is_none() ? nullptr : &g, &s, nullptr);
+        raise_if_error(s);
+        return out;
+    }, py::arg("grid"), py::arg("band") = 0, py::arg("grid_config") = py::none(),
+       "The zones of a band (whole numbers in [1, 2^24]) as a PolygonSet, made where the grid lives: one polygon per zone by "
+       "ascending zone, its value the zone, its rings the 4-connected outlines under the even-odd rule, on grid_config or the "
+       "grid's own geometry");
     // (tests) what the id band holds for an id: the clamp at 2^24 on its own
     m.def("_tree_id_value", [](int64_t id) { return pcrhip::trees::id_value(id); }, py::arg("id"));
     // (tests, tools) the host twin on an array, which the kernels are compared with; -> (id [h, w], height [h, w], table)

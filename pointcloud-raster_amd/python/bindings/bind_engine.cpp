@@ -475,6 +475,13 @@ void bind_engine(py::module_& m) {
             raise_if_error(p.set_zones(name, polygons, o));
         }, py::arg("name"), py::arg("polygons"), py::arg("background") = std::numeric_limits<float>::quiet_NaN(),
              "... or burns them from a PolygonSet on the pipeline's grid (pcr.rasterize_polygons' rule): in HBM on the HIP engine")
+        .def("polygonize", [](const Pipeline& p, const std::string& band_name) {
+            PolygonSet out;
+            raise_if_error(p.polygonize(band_name, &out));
+            return out;
+        }, py::arg("band_name"),
+             "The zones of the result's band `band_name` as a PolygonSet on the pipeline's grid (pcr.polygonize's rule), from the "
+             "band as the last finalize left it: in HBM on the HIP engine")
         .def("zonal", [](const Pipeline& p, int i) {
             ZonalTable t;
             raise_if_error(p.zonal(i, &t));

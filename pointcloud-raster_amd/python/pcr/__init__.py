@@ -79,9 +79,9 @@ from ._pcr import (  # noqa: E402,F401
     TreeSpec, TreeBandConfig, segment_trees,
     SampleMode, SurfaceChannelConfig, sample_grid, PolygonChannelConfig,
     HistogramConfig, ExtremeSide, ExtremesConfig, CellStat, CellStatsConfig, ZonalConfig, PointZonalConfig, point_zonal,
-    PolygonSet, rasterize_polygons, points_in_polygons,
+    PolygonSet, rasterize_polygons, points_in_polygons, polygonize,
 )
-from .polygons import read_geojson_polygons  # noqa: E402,F401  (also gives PolygonSet its from_wkt)
+from .polygons import read_geojson_polygons, write_geojson_polygons  # noqa: E402,F401  (also gives PolygonSet its from_wkt, to_wkt)
 from ._pcr import _transform_xy_device, _transform_xy_host  # noqa: E402
 
 
@@ -185,5 +185,5 @@ __all__ = [
     "TreeSpec", "TreeBandConfig", "segment_trees",
     "SampleMode", "SurfaceChannelConfig", "sample_grid", "PolygonChannelConfig",
     "HistogramConfig", "ExtremeSide", "ExtremesConfig", "CellStat", "CellStatsConfig", "ZonalConfig", "PointZonalConfig", "point_zonal",
-    "PolygonSet", "rasterize_polygons", "points_in_polygons", "read_geojson_polygons",
+    "PolygonSet", "rasterize_polygons", "points_in_polygons", "read_geojson_polygons", "polygonize", "write_geojson_polygons",
 ]

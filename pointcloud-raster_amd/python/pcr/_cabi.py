@@ -122,6 +122,14 @@ class PolygonIndexParams(C.Structure):
                          max_index_bytes=max_index_bytes)
 
 
+class PolygonizeParams(C.Structure):
+    """pcr_hip_polygonize_params: events recorded behind the phases of pcr_hip_polygonize_rings (include/pcr_hip.h)."""
+    _fields_ = [("events", C.c_void_p * 4)]
+
+    def __init__(self, events=(None, None, None, None)):
+        super().__init__(events=(C.c_void_p * 4)(*events))
+
+
 class TreeParams(C.Structure):
     """pcr_hip_tree_params with the defaults of pcr.TreeSpec."""
     _fields_ = [("min_height", C.c_float), ("window_base", C.c_float), ("window_slope", C.c_float),
@@ -293,6 +301,14 @@ SYMBOLS = {
                                       _VP],
     "pcr_hip_point_fold_hist": [_VP, _VP, _VP, _U64, C.c_int, C.c_double, C.c_double, _U32, C.POINTER(PointFoldParams), _VP, _VP, _VP],
     "pcr_hip_point_fold_hist_host": [_VP, _VP, _VP, _U64, C.c_int, C.c_double, C.c_double, _U32, C.POINTER(PointFoldParams), _VP, _VP],
+    "pcr_hip_polygonize_cells_work_bytes": [C.c_int, C.c_int, C.POINTER(_SZ)],
+    "pcr_hip_polygonize_rings_work_bytes": [_I64, C.POINTER(_SZ)],
+    "pcr_hip_polygonize_edges": [_VP, C.c_int, C.c_int, _I64, _VP, _SZ, _VP],
+    "pcr_hip_polygonize_count": [_VP, _SZ, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), C.POINTER(C.c_int), C.POINTER(C.c_int), _VP],
+    "pcr_hip_polygonize_rings": [_VP, C.c_int, C.c_int, _I64, _VP, _SZ, _I64, _VP, _SZ, C.POINTER(PolygonizeParams), _VP],
+    "pcr_hip_polygonize_fetch": [_VP, C.c_int, C.c_int, _I64, _VP, _SZ, _I64, _VP, _SZ, _I64, _I64, _VP, _VP, _VP, _VP, _VP],
+    "pcr_hip_polygonize_host": [_VP, C.c_int, C.c_int, _I64, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64), _I64, _I64, _VP, _VP,
+                                _VP, _VP],
 }
 
 _lib = None

@@ -1,9 +1,17 @@
-"""Polygon sets from text: WKT strings and GeoJSON files, for pcr.rasterize_polygons and Pipeline.set_zones.
+"""Polygon sets from and to text: WKT strings and GeoJSON files, for pcr.rasterize_polygons and Pipeline.set_zones, and for
+what pcr.polygonize and Pipeline.polygonize give.
 
 Standard library and numpy only.  One input geometry becomes ONE polygon of the set: the rings of a POLYGON (the shell and its
 holes) and, for a MULTIPOLYGON, the rings of all its parts -- a polygon of the set is all of its rings under the even-odd rule,
 so holes and parts need no marking and ring orientation plays no part.  The closing vertex that WKT and GeoJSON repeat is
-dropped (rings close implicitly).  Z and M ordinates are read and ignored."""
+dropped (rings close implicitly).  Z and M ordinates are read and ignored.
+
+The writers go the other way and have to MARK what the set leaves unmarked, since WKT and GeoJSON want shells and holes.  Per
+polygon, a ring's depth is the number of the polygon's other rings that hold the midpoint of its first edge (even-odd ray rule):
+even depth is a shell, odd depth a hole of the ring of depth - 1 that holds it.  Shells are written counter-clockwise and holes
+clockwise in world coordinates (RFC 7946), the closing vertex repeated, coordinates with repr() -- they read back to the same
+bits.  That is well defined when the rings of a polygon neither cross nor share an edge, as polygonize's never do (they may touch
+at corners); for other sets it is undefined.  A polygon of one ring skips all of it."""
 import json
 import re
 
@@ -101,4 +109,110 @@ def read_geojson_polygons(path, value_property=None):
     return _build(polygons, values if value_property is not None else None)
 
 
+def _holders(rings):
+    """Per ring, which of the others hold the midpoint of its first edge: a ray towards +x, an edge counted when it passes the
+    point's y.  One sweep over all edges of the polygon per ring."""
+    a = np.concatenate(rings)
+    b = np.concatenate([np.roll(r, -1, axis=0) for r in rings])
+    owner = np.repeat(np.arange(len(rings)), [len(r) for r in rings])
+    out = []
+    for i, r in enumerate(rings):
+        nxt = r[1 % len(r)]
+        px, py = 0.5 * (r[0, 0] + nxt[0]), 0.5 * (r[0, 1] + nxt[1])
+        at = np.nonzero(((a[:, 1] > py) != (b[:, 1] > py)) & (owner != i))[0]
+        xc = a[at, 0] + (py - a[at, 1]) / (b[at, 1] - a[at, 1]) * (b[at, 0] - a[at, 0])
+        odd = np.bincount(owner[at][xc > px], minlength=len(rings)) % 2
+        out.append(np.nonzero(odd)[0].tolist())
+    return out
+
+
+def _turned(ring, ccw):
+    """The ring counter-clockwise (or clockwise) in world coordinates: reversed when its shoelace sum says otherwise."""
+    d = ring - ring[0]                                   # (about its first vertex: no cancellation at UTM magnitudes)
+    n = np.roll(d, -1, axis=0)
+    area2 = float(np.sum(d[:, 0] * n[:, 1] - n[:, 0] * d[:, 1]))
+    return ring if (area2 > 0) == ccw else ring[::-1]
+
+
+def _parts(rings):
+    """[(shell, [holes])] of one polygon's rings, wound as RFC 7946 asks."""
+    if len(rings) == 1:
+        return [(_turned(rings[0], True), [])]
+    holders = _holders(rings)
+    depth = [len(h) for h in holders]
+    parts, place = [], {}
+    for i, r in enumerate(rings):
+        if depth[i] % 2 == 0:
+            place[i] = len(parts)
+            parts.append((_turned(r, True), []))
+    for i, r in enumerate(rings):
+        if depth[i] % 2 == 1:
+            shell = [j for j in holders[i] if depth[j] == depth[i] - 1]
+            if len(shell) != 1:
+                raise ValueError("a hole without a shell: the rings of a polygon cross or share an edge")
+            parts[place[shell[0]]][1].append(_turned(r, False))
+    return parts
+
+
+def _rings_of(polygons, p):
+    xy, ro, po = polygons.coords, polygons.ring_offsets, polygons.polygon_offsets
+    return [xy[ro[j]:ro[j + 1]] for j in range(po[p], po[p + 1])]
+
+
+def _closed(ring):
+    return [[float(x), float(y)] for x, y in ring] + [[float(ring[0, 0]), float(ring[0, 1])]]
+
+
+def to_wkt(polygons):
+    """One WKT string per polygon of the set: POLYGON when it has one shell, MULTIPOLYGON when several, POLYGON EMPTY when no
+    ring.  PolygonSet.from_wkt of the list gives a set that rasterizes to the same grid."""
+    def ring(r):
+        return "(" + ", ".join(f"{x!r} {y!r}" for x, y in _closed(r)) + ")"
+
+    def part(shell, holes):
+        return "(" + ", ".join(ring(r) for r in [shell] + holes) + ")"
+
+    out = []
+    for p in range(polygons.num_polygons):
+        parts = _parts(_rings_of(polygons, p)) if polygons.polygon_offsets[p + 1] > polygons.polygon_offsets[p] else []
+        if not parts:
+            out.append("POLYGON EMPTY")
+        elif len(parts) == 1:
+            out.append("POLYGON " + part(*parts[0]))
+        else:
+            out.append("MULTIPOLYGON (" + ", ".join(part(*q) for q in parts) + ")")
+    return out
+
+
+def _json_value(v):
+    v = v.item() if hasattr(v, "item") else v
+    return None if isinstance(v, float) and v != v else v
+
+
+def write_geojson_polygons(path, polygons, properties=None):
+    """Writes the set as a GeoJSON FeatureCollection, one Feature per polygon: a Polygon when it has one shell, else a
+    MultiPolygon.  properties: a dict of per-polygon columns (sequences of num_polygons entries), for example the arrays of
+    Pipeline.zonal(i) selected by `values - 1` for the crowns of a tree-id band; "value" is the set's own values (p + 1 when it has
+    none) unless the dict brings its own.  NaN is written as null.  read_geojson_polygons(path, "value") gives back a set that
+    rasterizes to the same grid."""
+    P = polygons.num_polygons
+    columns = {"value": polygons.values if polygons.values is not None else np.arange(1, P + 1, dtype=np.float32)}
+    for name, column in (properties or {}).items():
+        if len(column) != P:
+            raise ValueError(f"write_geojson_polygons: property {name!r} has {len(column)} entries for {P} polygons")
+        columns[name] = column
+    features = []
+    for p in range(P):
+        parts = [[_closed(shell)] + [_closed(h) for h in holes] for shell, holes in _parts(_rings_of(polygons, p))] \
+            if polygons.polygon_offsets[p + 1] > polygons.polygon_offsets[p] else []
+        if len(parts) == 1:
+            geometry = {"type": "Polygon", "coordinates": parts[0]}
+        else:
+            geometry = {"type": "MultiPolygon", "coordinates": parts}
+        features.append({"type": "Feature", "properties": {k: _json_value(c[p]) for k, c in columns.items()}, "geometry": geometry})
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump({"type": "FeatureCollection", "features": features}, f)
+
+
 PolygonSet.from_wkt = staticmethod(from_wkt)
+PolygonSet.to_wkt = to_wkt
