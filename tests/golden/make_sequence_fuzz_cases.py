@@ -3,7 +3,8 @@
 were the operation-sequence fuzz's suite before it drew terrain bands, recorded with the generator of that commit, and under
 the key `sha256_line` one per seed of LINE_SEEDS (the line cases: the digest covers the glyphs and the `dir` / `hl` arrays), and
 under `sha256_acc` one per seed of ACC_SEEDS (the accumulator cases: the digest of the case as it is, its filters, `acc` lists,
-trees, zonal and terrain lists and `z` arrays included).
+trees, zonal and terrain lists and `z` arrays included), and under `sha256_poly` one per seed of POLY_SEEDS (the polygon cases:
+the polygon sets' vertex bits and options, the uses, the point zonal entries, the new ops and the `lab` arrays too).
 
     python tests/golden/make_sequence_fuzz_cases.py
 
@@ -34,11 +35,12 @@ def main():
     rec = {str(seed): digest(seed) for seed in SEEDS}
     line = {str(seed): digest(seed) for seed in S.LINE_SEEDS}
     acc = {str(seed): S.case_digest(S.build(seed)) for seed in S.ACC_SEEDS}
+    poly = {str(seed): S.case_digest(S.build(seed)) for seed in S.POLY_SEEDS}
     with open(OUT, "w") as f:
         json.dump(dict(what="sequence_fuzz_common.case_digest(build(seed)) per seed, before terrain was drawn", sha256=rec,
-                       sha256_line=line, sha256_acc=acc), f, indent=1)
+                       sha256_line=line, sha256_acc=acc, sha256_poly=poly), f, indent=1)
         f.write("\n")
-    print(f"{OUT}: {len(rec)} + {len(line)} + {len(acc)} seeds")
+    print(f"{OUT}: {len(rec)} + {len(line)} + {len(acc)} + {len(poly)} seeds")
 
 
 if __name__ == "__main__":

@@ -35,7 +35,17 @@ a filter of its own on reductions and accumulator entries, histograms, extremes 
 tables, and the ops read_acc, tables and set_zones.  `z` and the surface channels feed selections (Max, Min, MostRecent) and
 accumulators only, whose states are integers and whose bands are defined bit by bit: the model is the *_common model of each
 feature on the same routing, the host twin for the tree bands, zonal_common's Python ints for the tables -- no tolerance.
-save_state and load_state are refused while an accumulator list is non-empty: the ops stay, must raise, and move nothing."""
+save_state and load_state are refused while an accumulator list is non-empty: the ops stay, must raise, and move nothing.
+
+Polygon cases: a seed from POLY_SEED_BASE on is what the accumulator generator draws for seed - POLY_SEED_BASE + ACC_SEED_BASE
+plus (_poly_pass, last and from generators of its own) 1 to 3 polygon channels with one or two polygon sets each, a use of
+every channel -- in PipelineConfig::filter, in the filters of reductions and accumulator entries, as the value of a Max, Min or
+filtered Count, as a histogram's channel, as a label -- 1 to 3 point zonal entries, a `lab` channel, points outside the grid and
+inside a polygon in every cloud, and the ops set_polygons, point_tables, set_zones_poly, polygonize and reburn.  The model of a
+polygon channel is points_in_polygons_common.model with the set that is current at the ingest; of a point zonal table
+point_zonal_common.table_masked on the concatenated points of every ingest that counted (the contract: the bits depend on the
+multiset of points only); of a burnt label grid rasterize_common.model; of an outline polygonize_common.model.  The reburn chain
+needs no model: a zonal entry whose zones were burnt from polygonize(tree_id) answers the by-band entry's table, bit for bit."""
 import filecmp
 import os
 
@@ -96,7 +106,7 @@ def seeds_from_env(name="PCR_SEQ_FUZZ_SEEDS"):
         return list(range(int(a), int(b)))
     if env:
         return [int(v) for v in env.split(",")]
-    return list(DEFAULT_SEEDS) + list(LINE_SEEDS) + list(ACC_SEEDS)
+    return list(DEFAULT_SEEDS) + list(LINE_SEEDS) + list(ACC_SEEDS) + list(POLY_SEEDS)
 
 
 # ---- the generator (NumPy only; a line case: and the oracle) ------------------------------------------------------------------------------------------------
@@ -248,8 +258,11 @@ LINE_CLOUD_KEYS = ("dir", "hl")            # only the clouds of a line case have
 ACC_CLOUD_KEYS = ("z",)                    # ... and only the clouds of an accumulator case this one
 
 
+POLY_CLOUD_KEYS = ("lab",)                 # ... and the clouds of a polygon case with a point zonal entry by `lab` this one
+
+
 def cloud_keys(c):
-    return CLOUD_KEYS + (LINE_CLOUD_KEYS if "dir" in c else ()) + (ACC_CLOUD_KEYS if "z" in c else ())
+    return CLOUD_KEYS + (LINE_CLOUD_KEYS if "dir" in c else ()) + (ACC_CLOUD_KEYS if "z" in c else ()) + (POLY_CLOUD_KEYS if "lab" in c else ())
 
 
 def _thin(c, keep):
@@ -820,6 +833,9 @@ def _acc_tables(seed, case):
 
 
 def build(seed):
+    poly_seed = seed if seed >= POLY_SEED_BASE else None
+    if poly_seed is not None:                                    # a polygon case: the accumulator case of this seed, then _poly_pass
+        seed = seed - POLY_SEED_BASE + ACC_SEED_BASE
     rng = np.random.default_rng(91000 + seed)
     # How the sequence opens.  "union": what a row-block shard does -- one sparse cloud, the other ranks' flags merged in, finalize.
     # "overlay": a checkpoint of an earlier pipeline loaded over the first ingest of a new one.  "hot": the hot spot as the first
@@ -1011,6 +1027,10 @@ def build(seed):
     for i, o in enumerate(ops):
         if o["op"] == "checkpoint" and o["plan"] is not None:
             o["plan"]["terrain"] = _draw_terrain(np.random.default_rng((93000, seed, i + 1)), specs, o["plan"])
+    case["poly"] = None
+    if poly_seed is not None:
+        case["seed"] = poly_seed
+        _poly_pass(poly_seed, case)
     return case
 
 
@@ -1037,7 +1057,17 @@ def case_digest(case):
     if case.get("acc") is not None:                              # an accumulator case: the lists, and the plan's terrain after all
         head["acc"] = plain(case["acc"])                          # (its sources are part of what the case is for)
         head["terrain"] = plain(case["plan"]["terrain"])
+    if case.get("poly") is not None:                             # a polygon case: the sets' options, the uses, the entries (the new ops
+        po = case["poly"]                                        # are in `ops`, `lab` is a cloud key); the vertex bits below
+        head["poly"] = plain({k: v for k, v in po.items() if k not in ("sets", "zone_sets")})
+        head["poly_sets"] = plain([[st["opts"] for st in sets] for sets in po["sets"]] + [st["opts"] for st in po["zone_sets"]])
     h.update(json.dumps(head, sort_keys=True, allow_nan=False).encode())
+    if case.get("poly") is not None:
+        for st in [st for sets in case["poly"]["sets"] for st in sets] + case["poly"]["zone_sets"]:
+            pl = st["polys"]
+            for a in (pl.coords, pl.ring_offsets, pl.polygon_offsets) + (() if pl.values is None else (pl.values,)):
+                h.update(f"{a.dtype.str}:{a.shape}".encode())
+                h.update(np.ascontiguousarray(a).tobytes())
     for c in case["clouds"]:
         h.update(c["shape"].encode())
         for k in cloud_keys(c):
@@ -1109,6 +1139,8 @@ def segments(case):
 def situations(case):
     """Which of the situations the fuzz is for occur in a case (tests/test_sequence_fuzz_host.py counts them over the seeds).
     Only what runs on the HIP engine counts: pointer ops in in-core segments, a hot spot that is binned."""
+    if case.get("poly") is not None:                             # (a polygon case has situations of its own)
+        return poly_situations(case)
     if case.get("acc") is not None:                              # (an accumulator case has situations of its own)
         return acc_situations(case)
     found = set()
@@ -1466,6 +1498,515 @@ TERRAIN_SITUATIONS = ("terrain of a band that the first ingest stored, finalize 
 SITUATIONS += TERRAIN_SITUATIONS
 
 
+# ---- polygon cases ---------------------------------------------------------------------------------------------------------------
+# A seed from POLY_SEED_BASE on is a polygon case: the accumulator case of seed - POLY_SEED_BASE + ACC_SEED_BASE, then -- last and
+# from generators of their own, (97000, seed, k) -- polygon channels and their sets, their uses, point zonal entries, the ops
+# that set and read them, and what the clouds need for them (k = 0 the lists, 1 the ops, 10 + i cloud i).
+POLY_SEED_BASE = 20000
+POLY_NAMES = ("plot", "stand", "clip")
+POLY_BACKGROUNDS = (float("nan"), -1.0, 0.0)
+POLY_MAX_EDGES = 400                       # of one set: the models walk every edge for every point and every row
+PZ_MAX_ZONES = (3, 40, 4096)
+PZ_ITEM = 1 << 16                          # the fold's item: a cloud with more kept points in one zone meets one long run
+PZ_CHANNELS = ("z", "a", "b")
+
+
+def grid_geom(g):
+    import rasterize_common as RC
+    return RC.Geom(g["W"], g["H"], min_x=g["min_x"], max_y=g["max_y"], csx=g["cs"], csy=-g["cs"])
+
+
+def _draw_polys(rp, g, outside):
+    """One polygon set in the grid's world coordinates, from rasterize_common's makers: a jittered partition over part of the
+    grid, a donut over it, a rectangle half outside the grid (`outside`: for sure), a handful of overlapping n-gons, one of
+    points_in_polygons_common.degenerate()'s area-less polygons; then values (or none), a background and an index size.
+    -> dict(polys, opts)"""
+    import points_in_polygons_common as PIP
+    import rasterize_common as RC
+    w, h = g["W"] * g["cs"], g["H"] * g["cs"]
+    x0, y0 = g["min_x"], g["min_y"]
+    polygons, kinds, rect = [], [], None
+    if rp.uniform() < 0.7:
+        ax, ay = x0 + w * rp.uniform(0.0, 0.3), y0 + h * rp.uniform(0.0, 0.3)
+        polygons += RC.partition(ax, ay, ax + w * rp.uniform(0.3, 0.65), ay + h * rp.uniform(0.3, 0.65), int(rp.integers(1, 4)),
+                                 int(rp.integers(1, 4)), seed=int(rp.integers(0, 1 << 30)), wiggle=2)
+        kinds.append("partition")
+    if rp.uniform() < 0.4:
+        r = min(w, h) * rp.uniform(0.1, 0.3)
+        polygons.append(RC.donut(x0 + w * rp.uniform(0.2, 0.8), y0 + h * rp.uniform(0.2, 0.8), r, r * rp.uniform(0.2, 0.7), n=12))
+        kinds.append("donut")
+    if rp.uniform() < 0.5:
+        cx, cy = x0 + w * rp.uniform(0.2, 0.8), y0 + h * rp.uniform(0.2, 0.8)
+        for _ in range(int(rp.integers(2, 6))):
+            polygons.append([RC.ngon(cx + w * rp.uniform(-0.1, 0.1), cy + h * rp.uniform(-0.1, 0.1), min(w, h) * rp.uniform(0.05, 0.2),
+                                     int(rp.integers(3, 10)), rp.uniform(0, 1))])
+        kinds.append("ngons")
+    if rp.uniform() < 0.4:
+        d = PIP.degenerate()
+        k = int(rp.integers(1, 5))                               # no ring; three collinear points; a sliver of no height; forth and back
+        ox, oy, s = x0 + w * rp.uniform(0.1, 0.8), y0 + h * rp.uniform(0.1, 0.8), 3.0 * g["cs"]
+        polygons.append([np.array([ox, oy]) + s * ring for ring in d.polygon(k)])
+        kinds.append(f"degenerate{k}")
+    if outside or not polygons or rp.uniform() < 0.5:            # half outside the grid, to the right of it or above it
+        if rp.uniform() < 0.5:
+            rect = (g["max_x"] - w * rp.uniform(0.05, 0.2), y0 + h * rp.uniform(0.1, 0.4), g["max_x"] + w * rp.uniform(0.05, 0.2), y0 + h * rp.uniform(0.5, 0.9))
+        else:
+            rect = (x0 + w * rp.uniform(0.1, 0.4), g["max_y"] - h * rp.uniform(0.05, 0.2), x0 + w * rp.uniform(0.5, 0.9), g["max_y"] + h * rp.uniform(0.05, 0.2))
+        rect = tuple(float(v) for v in rect)
+        polygons.append([RC.rect(*rect)])
+        kinds.append("rect")
+    order = rp.permutation(len(polygons))
+    polygons = [polygons[i] for i in order]
+    P = len(polygons)
+    values = None
+    if rp.uniform() < 0.6:                                       # whole numbers a little beyond P, maybe one that is no zone
+        values = rp.integers(1, P + 4, P).astype(np.float32)
+        if rp.uniform() < 0.3:
+            values[int(rp.integers(0, P))] = np.float32(rp.choice([2.5, 0.0, -3.0]))
+    polys = RC.Polys(polygons, values)
+    assert len(polys.coords) <= POLY_MAX_EDGES, len(polys.coords)
+    cols, rows = PIP.INDEX_SIZES[int(rp.integers(0, len(PIP.INDEX_SIZES)))]
+    opts = dict(background=float(POLY_BACKGROUNDS[int(rp.integers(0, 3))]), index_cols=cols, index_rows=rows, kinds=kinds,
+                rect=None if rect is None else list(rect))
+    return dict(polys=polys, opts=opts)
+
+
+def set_values(st):
+    """The values a set's polygons carry."""
+    pl = st["polys"]
+    return [float(v) for v in (np.arange(1, pl.P + 1, dtype=np.float32) if pl.values is None else pl.values)]
+
+
+def _poly_pred(rp, name, sets):
+    """A predicate on a polygon channel that keeps some points and drops others under most sets."""
+    vals = sorted({v for st in sets for v in set_values(st)})
+    kind = int(rp.integers(0, 5))
+    some = [float(v) for v in rp.choice(vals, min(len(vals), int(rp.integers(1, 4))), replace=False)]
+    op, value = (("GreaterEqual", 1.0), ("Greater", 0.0), ("InSet", 0.0), ("NotInSet", 0.0), ("LessEqual", vals[len(vals) // 2]))[kind]
+    return dict(ch=name, op=op, value=float(value), set=some)
+
+
+def poly_channels(case, k, current):
+    """The polygon channels of cloud k under the sets `current` (an index per channel): points_in_polygons_common.model at the
+    cloud's x and y, with the set's background as float32 bits.  Kept with the case: the model and poly_situations share them."""
+    import points_in_polygons_common as PIP
+    po, c = case["poly"], case["clouds"][k]
+    memo = case.setdefault("_poly_memo", {})
+    out = {}
+    for name, sets, j in zip(po["names"], po["sets"], current):
+        if (k, name, j) not in memo:
+            st = sets[j]
+            memo[(k, name, j)] = PIP.model(st["polys"], c["x"], c["y"], np.float32(st["opts"]["background"])) if len(c["x"]) else np.zeros(0, np.float32)
+        out[name] = memo[(k, name, j)]
+    return out
+
+
+def pipeline_keep(case, ch):
+    """PipelineConfig::filter of a case over the channels of a cloud: the `cls` predicate AND a polygon case's clip predicates."""
+    keep = keep_mask(case["filt"], ch["cls"])
+    return keep & conj_mask(ch, (case.get("poly") or {}).get("clip"), len(keep))
+
+
+def zones_of(labels):
+    """The zone of every label by zonal's rule (polygonize_common.zones_of: a whole number in [1, 2^24], else 0), as int64."""
+    import polygonize_common as PG
+    return PG.zones_of(labels).astype(np.int64)
+
+
+def _poly_pass(seed, case):
+    """What makes a seed >= POLY_SEED_BASE a polygon case, on top of the accumulator case `case`: the channels, their sets and
+    their uses and the point zonal entries here (k = 0), then _poly_ops (k = 1) and _poly_clouds (k = 2 and 10 + i).  It only
+    appends: reductions behind the reductions, a histogram behind the histograms, zonal entries behind the zonal entries, so
+    every band and entry the accumulator case names keeps its index; a filter it replaces regroups the specs as in _acc_pass,
+    and a plane write follows its reduction."""
+    rp = np.random.default_rng((97000, seed, 0))
+    g, specs, acc, ops, clouds = case["grid"], case["specs"], case["acc"], case["ops"], case["clouds"]
+    names = list(POLY_NAMES[:int(rp.integers(1, 4))])
+    sets = [[_draw_polys(rp, g, k == 0) for _ in range(int(rp.integers(1, 3)))] for k in range(len(names))]
+    snames = [sc["name"] for sc in acc["surfaces"]]
+    # the uses of every channel, each drawn on its own
+    clip, ppool = [], []
+    for name, ss in zip(names, sets):
+        pred = _poly_pred(rp, name, ss)
+        if rp.uniform() < 0.3:
+            clip.append(pred)
+        pred = _poly_pred(rp, name, ss)
+        if rp.uniform() < 0.6:                                   # into the pool: alone, or behind a predicate on `cls`
+            f = [pred]
+            if rp.uniform() < 0.4:
+                f.insert(0, dict(ch="cls", op=str(rp.choice(OPS8)), value=float(rp.integers(0, 4)),
+                                 set=[float(v) for v in rp.choice(4, int(rp.integers(1, 4)), replace=False)]))
+            ppool.append(f)
+    old_pool = []
+    for e in acc_entries(acc) + specs:
+        if e["filt"] and filter_key(e["filt"]) not in [filter_key(q) for q in old_pool]:
+            old_pool.append(e["filt"])
+    pool = old_pool + ppool
+    pick = lambda p: pool[int(rp.integers(0, len(pool)))] if pool and rp.uniform() < p else []
+    for o in ops:                                                # (plane writes follow their reduction when the filters regroup the specs)
+        if o["op"] == "planes_write":
+            o["spec"] = next(i for i, s in enumerate(specs) if s["group"] == o["group"] and o["slot"] in PLANES_OF[s["type"]]
+                             and s["type"] in ("Sum", "Count", "Average"))
+    for e in acc_entries(acc) + specs:                           # a polygon predicate in the filters of what the case had
+        if ppool and rp.uniform() < 0.25:
+            e["filt"] = ppool[int(rp.integers(0, len(ppool)))]
+    max_bands = []
+    for name, ss in zip(names, sets):
+        if rp.uniform() < 0.6:                                   # the channel as a value: selections and counts only, like `z`
+            t = str(rp.choice(["Max", "Max", "Min", "Count"]))
+            filt = pick(1.0 if t == "Count" else 0.5)
+            if t == "Count" and not filt:                        # (a Count only under a filter; a case without one takes a Max)
+                t = "Max"
+            specs.append(dict(type=t, ch=name, filt=filt))
+            if t == "Max":
+                max_bands.append(band_name(len(specs) - 1, specs[-1]))
+        if rp.uniform() < 0.4 and len(acc["hist"]) < 4:          # ... and as a histogram's channel, over the plot numbers (create takes 4)
+            top = max([1.0] + [max(set_values(st)) for st in ss])     # (a set of one polygon of value -3 spans nothing)
+            bins = int(rp.choice([8, 37]))
+            qs = [HIST_QS[i] for i in rp.permutation(len(HIST_QS))[:int(rp.integers(0, 3))]]
+            acc["hist"].append(dict(ch=name, lo=-1.5, hi=float(top) + 0.5, bins=bins, qs=qs, filt=pick(0.4)))
+    groups = groups_of(specs)
+    case["groups"] = groups
+    for o in ops:
+        if o["op"] == "planes_write":
+            o["group"] = specs[o.pop("spec")]["group"]
+    # point zonal entries
+    pz = []
+    labels = list(names) + [sc["name"] for sc in acc["surfaces"] if sc["mode"] == 0] + ["cls", "lab"]
+    for i in range(int(rp.integers(1, 4))):
+        label = names[int(rp.integers(0, len(names)))] if rp.uniform() < 0.5 else labels[int(rp.integers(0, len(labels)))]
+        max_zones = int(rp.choice(PZ_MAX_ZONES))
+        chans = list(PZ_CHANNELS) + snames + [n for n in names if n != label]
+        n_stats, n_hists = int(rp.integers(0, 3)), int(rp.integers(0, 3))
+        if n_stats + n_hists == 0:
+            n_stats, n_hists = (1, 0) if rp.uniform() < 0.5 else (0, 1)
+        st, hs = [], []
+        for ch in rp.choice(chans, n_stats, replace=False):      # (two specs of one channel would name a column twice)
+            origin, res = STAT_STEPS[int(rp.integers(0, 3))]
+            st.append(dict(ch=str(ch), origin=origin, res=res, ddof=int(rp.integers(0, 2)), filt=pick(0.5)))
+        for ch in rp.choice(chans, n_hists, replace=False):
+            lo, hi = HIST_RANGES[int(rp.integers(0, len(HIST_RANGES)))]
+            bins = int(rp.choice(HIST_BINS))
+            if max_zones > 40:                                   # (the Python-int rows walk every bin of every zone)
+                bins = min(bins, ZONAL_MAX_BINS)
+            qs = [HIST_QS[j] for j in rp.permutation(len(HIST_QS))[:int(rp.integers(0, 4))]]
+            hs.append(dict(ch=str(ch), lo=lo, hi=hi, bins=bins, qs=qs, filt=pick(0.5)))
+        pz.append(dict(label=label, max_zones=max_zones, stats=st, hists=hs))
+    distinct = {filter_key(e["filt"]) for e in acc_entries(acc) + specs + [s for e in pz for s in e["stats"] + e["hists"]] if e["filt"]}
+    assert len(distinct) <= 8 and sum(len(k) for k in distinct) + (1 if case["filt"] else 0) + len(clip) <= 32, (seed, len(distinct))
+    case["poly"] = dict(names=names, sets=sets, clip=clip, pz=pz, zone_sets=[], max_bands=max_bands)
+    _poly_ops(seed, case)
+    _poly_clouds(seed, case)
+    assert point_units(g, clouds).max() + PATCH_UNITS * sum(o["op"] == "planes_write" for o in ops) < 1 << 24
+    assert sum(len(c["x"]) for c in clouds) < 1 << 22
+
+
+def _poly_ops(seed, case):
+    """The ops of a polygon case, INSERTED into the sequence ahead of its last finalize as _acc_tables inserts its own, and the
+    zonal entries they need: a twin of a by-tree entry for the reburn chain, an external entry for polygon-burnt zones."""
+    ro = np.random.default_rng((97000, seed, 1))
+    po, plan, acc, ops, specs = case["poly"], case["plan"], case["acc"], case["ops"], case["specs"]
+    g = case["grid"]
+    zonal, trees = plan["zonal"], plan["trees"]
+    new = [dict(op="set_polygons", channel=k, sync=bool(ro.uniform() < 0.5)) for k, ss in enumerate(po["sets"]) if len(ss) == 2]
+    new += [dict(op="point_tables", counts=bool(ro.uniform() < 0.5), sync=bool(ro.uniform() < 0.5)) for _ in range(int(ro.integers(1, 5)))]
+    # the reburn chain: a by-tree entry and an external twin with the same lists, burnt from polygonize(tree_id)
+    for i, z in enumerate(list(zonal)):
+        if not z["external"] and len(zonal) < 4 and ro.uniform() < 0.5:
+            zonal.append(dict(z, zones=f"burn{i}", external=True, twin_of=i))
+            new += [dict(op="reburn", zonal=len(zonal) - 1, band=z["zones"]) for _ in range(int(ro.integers(1, 3)))]
+    # zones burnt from a polygon set: on an external entry the case has, or on one of its own
+    externals = [i for i, z in enumerate(zonal) if z["external"] and "twin_of" not in z]
+    folds = [i for i, h in enumerate(acc["hist"]) if h["bins"] <= ZONAL_MAX_BINS]
+    if not externals and len(zonal) < 4 and (acc["stats"] or folds) and ro.uniform() < 0.6:
+        st = [int(ro.integers(0, len(acc["stats"])))] if acc["stats"] else []
+        hs = [int(ro.choice(folds))] if folds and (ro.uniform() < 0.5 or not st) else []
+        zonal.append(dict(zones="zp", external=True, stats=st, hists=hs, own=True, qs=[], max_zones=int(ro.choice([1 << 22, 3, 40]))))
+        externals = [len(zonal) - 1]
+    for i in externals:
+        if ro.uniform() < 0.7:
+            po["zone_sets"].append(_draw_polys(ro, g, False))
+            new.append(dict(op="set_zones_poly", zonal=i, poly=len(po["zone_sets"]) - 1))
+    # outlines: of a tree-id band, of a Max band of a polygon channel, of a Max band of `z`, of no band at all
+    cands = [f"t{i}_id" for i in range(len(trees))] + po["max_bands"] + \
+            [band_name(i, s) for i, s in enumerate(specs) if s["type"] == "Max" and s["ch"] == "z"][:1] + ["nope"]
+    new += [dict(op="polygonize", band=cands[int(ro.integers(0, len(cands)))]) for _ in range(int(ro.integers(1, 4)))]
+    po["outlines"] = sorted({o["band"] for o in new if o["op"] in ("polygonize", "reburn")})
+    new = [new[i] for i in ro.permutation(len(new))]
+    first = next(i for i, o in enumerate(ops) if o["op"] == "ingest")
+    at = []
+    for o in new:                                                # a second set comes between ingests; everything else anywhere
+        lo = first + 1 if o["op"] == "set_polygons" else 0
+        asyncs = [i + 1 for i in range(lo, len(ops)) if ops[i]["op"] == "ingest" and ops[i]["how"].startswith("async") and i + 1 < len(ops)]
+        if o["op"] == "set_polygons" and asyncs and ro.uniform() < 0.5:
+            at.append(int(ro.choice(asyncs)))                    # right behind an async ingest
+        else:
+            at.append(int(ro.integers(min(lo, len(ops) - 1), len(ops))))
+    order = np.argsort(at, kind="stable")
+    for k, j in enumerate(order):
+        ops.insert(at[j] + k, new[j])
+    for i in range(1, len(ops)):                                 # right behind an async ingest they wait for nothing themselves
+        if ops[i]["op"] in ("set_polygons", "point_tables") and ops[i - 1]["op"] == "ingest" and ops[i - 1]["how"].startswith("async"):
+            ops[i - 1]["sync"] = ops[i - 1]["sync"] and ops[i]["sync"]
+
+
+def poly_walk(case):
+    """The ingests of a polygon case in order: [(op index, cloud index, the sets current then (an index per channel))]."""
+    cur, out = [0] * len(case["poly"]["names"]), []
+    for i, o in enumerate(case["ops"]):
+        if o["op"] == "set_polygons":
+            cur[o["channel"]] = 1
+        elif o["op"] == "ingest":
+            out.append((i, o["cloud"], tuple(cur)))
+    return out
+
+
+def cloud_channels(case, k, current):
+    """Every channel of cloud k of a polygon case: its own, the surface channels, the polygon channels under `current`."""
+    memo = case.setdefault("_surface_memo", {})
+    if k not in memo:
+        ch = surface_channels(case["acc"], case["clouds"][k])
+        memo[k] = {n: ch[n] for n in (sc["name"] for sc in case["acc"]["surfaces"])}
+    return dict(case["clouds"][k], **memo[k], **poly_channels(case, k, current))
+
+
+def _poly_clouds(seed, case):
+    """What the clouds of a polygon case need: maybe one with more than 2^16 kept points in one zone of entry 0, maybe one that
+    the pipeline filter empties, `lab` on all where an entry folds by it, and in every cloud a share of points moved (x and y
+    only) outside the grid and inside a polygon."""
+    po, g, clouds, filt = case["poly"], case["grid"], case["clouds"], case["filt"]
+    r0 = np.random.default_rng((97000, seed, 2))
+    W, H, cs = g["W"], g["H"], g["cs"]
+    walk = poly_walk(case)
+    cur_of = {k: cur for _, k, cur in walk}
+    free = [k for k, c in enumerate(clouds) if c["shape"] not in ("hot", "hot_acc") and k in cur_of]
+    swap = {}
+    for kind in ("hot_zone", "pipeline_emptied"):
+        if free and r0.uniform() < 1 / 3:
+            swap[free.pop(int(r0.integers(0, len(free))))] = kind
+    e0 = po["pz"][0]
+    lab_entries = [e for e in po["pz"] if e["label"] == "lab"]
+    field = z_field(g, seed - POLY_SEED_BASE + ACC_SEED_BASE)
+    cls4 = np.arange(4, dtype=np.float32)
+    kept_cls = cls4[keep_mask(filt, cls4)]
+    for k, c in enumerate(clouds):
+        rc = np.random.default_rng((97000, seed, 10 + k))
+        kind = swap.get(k)
+        if kind == "hot_zone" and e0["label"] not in [sc["name"] for sc in case["acc"]["surfaces"]] and len(kept_cls):
+            # one point more than the fold's item in ONE zone, where a sample of the grid finds the zone most often; 2000 others
+            n = PZ_ITEM + 1 + 2000
+            x, y = rc.uniform(g["min_x"], g["max_x"], n), rc.uniform(g["min_y"], g["max_y"], n)
+            cls = kept_cls[rc.integers(0, len(kept_cls), n)]
+            if e0["label"] in po["names"]:
+                import points_in_polygons_common as PIP
+                j = po["names"].index(e0["label"])
+                st = po["sets"][j][cur_of[k][j]]
+                zs = zones_of(PIP.model(st["polys"], x[:4000], y[:4000], np.float32(st["opts"]["background"])))
+                zs[zs > e0["max_zones"]] = 0
+                if zs.any():
+                    at = np.flatnonzero(zs == np.bincount(zs[zs > 0]).argmax())
+                    pick = at[rc.integers(0, len(at), PZ_ITEM + 1)]
+                    x[2000:], y[2000:] = x[pick], y[pick]
+            elif e0["label"] == "cls":
+                zone = kept_cls[kept_cls >= 1]
+                cls[2000:] = zone[0] if len(zone) else cls[2000:]
+            c = clouds[k] = dict(shape=kind, x=x, y=y, cls=cls, a=(rc.integers(-16, 17, n) / 8.0).astype(np.float32),
+                                 b=rc.integers(0, 16, n).astype(np.float32), t=rc.integers(0, 6, n).astype(np.float32))
+            _draw_z(rc, g, c, field, case["acc"]["shift"])
+        elif kind == "pipeline_emptied":
+            n = len(c["x"])
+            dropped = cls4[~keep_mask(filt, cls4)]
+            c["shape"] = kind
+            if len(dropped):
+                c["cls"] = dropped[rc.integers(0, len(dropped), n)]
+            elif po["clip"]:                                     # far from every polygon: the background, which most clips drop
+                c["x"] = rc.uniform(g["max_x"] + 1000 * cs, g["max_x"] + 2000 * cs, n)
+        n = len(c["x"])
+        if lab_entries:                                          # whole numbers up to max_zones, every invalid label; in one cloud of three a few above
+            import point_zonal_common as PZC
+            Z = lab_entries[0]["max_zones"]
+            lab = rc.integers(1, min(Z, 64) + 1, n).astype(np.float32)
+            wide = rc.uniform(size=n) < 0.2
+            lab[wide] = rc.integers(1, Z + 1, int(wide.sum()))
+            bad = rc.uniform(size=n) < 0.1
+            lab[bad] = np.array(PZC.INVALID, np.float32)[rc.integers(0, len(PZC.INVALID), int(bad.sum()))]
+            if n and rc.uniform() < 1 / 3:
+                lab[rc.integers(0, n, 1 + n // 500)] = Z + rc.integers(1, 4)
+            if kind == "hot_zone" and e0["label"] == "lab":
+                lab[2000:] = min(Z, 2)
+            c["lab"] = lab
+        # a share outside the grid and inside a polygon: into the outer part of a half-outside rectangle of channel 0
+        rects = [st["opts"]["rect"] for st in po["sets"][0]]
+        rect = rects[cur_of[k][0]] if k in cur_of else rects[0]
+        share = 0.005 if c["shape"] in ("hot", "hot_acc", "hot_zone") else 0.04
+        move = np.flatnonzero(rc.uniform(size=n) < share)
+        if len(move) and kind != "pipeline_emptied":
+            rx0, ry0, rx1, ry1 = rect
+            if rx1 > g["max_x"]:
+                c["x"][move], c["y"][move] = rc.uniform(g["max_x"] + 0.01 * cs, rx1, len(move)), rc.uniform(ry0, ry1, len(move))
+            else:
+                c["x"][move], c["y"][move] = rc.uniform(rx0, rx1, len(move)), rc.uniform(g["max_y"] + 0.01 * cs, ry1, len(move))
+    # the exactness condition again, on the clouds as they are now (a replaced cloud is new to the sums)
+    units = np.zeros((2, W * H))
+    for c in clouds:
+        while (units + point_units(g, [c])).max() >= EXACT_UNITS:
+            _thin(c, np.arange(len(c["x"])) % 2 == 0)
+        units += point_units(g, [c])
+
+
+POLY_SITUATIONS = ("a polygon channel as a point zonal label, with counted points outside the grid",
+                   "set_polygons behind an unsynchronised async ingest", "set_polygons before a larger cloud than any so far",
+                   "a polygon channel in the pipeline filter", "a polygon channel in a reduction's filter",
+                   "a polygon channel in a point zonal spec's filter", "a polygon channel as a histogram's value channel",
+                   "ingest_file in more than one chunk with a polygon-labelled entry",
+                   "a cloud the pipeline filter empties between two point_tables",
+                   "a spec filter that empties a cloud the pipeline filter keeps", "a point zonal overflow and a read after it",
+                   "point_tables before the first ingest", "a surface channel as the label", "more than 2^16 kept points in one zone",
+                   "set_zones_poly replacing a grid", "a grid replacing set_zones_poly", "polygonize with a Device result",
+                   "polygonize refused after an ingest, and valid again after the next finalize",
+                   "polygonize valid behind an emptied cloud", "the reburn chain with at least 20 crowns")
+
+
+def poly_situations(case):
+    """The POLY_SITUATIONS that occur in a polygon case, from the case alone: the channels by the models, the crowns of the
+    reburn chain by the model of the sequence (only where a reburn is valid at all)."""
+    found = set()
+    po, ops, plan, acc, specs, g = case["poly"], case["ops"], case["plan"], case["acc"], case["specs"], case["grid"]
+    names, pz = po["names"], po["pz"]
+    uses = lambda f: any(p["ch"] in names for p in f or ())
+    if any(uses(s["filt"]) for s in specs):
+        found.add("a polygon channel in a reduction's filter")
+    if any(uses(s["filt"]) for e in pz for s in e["stats"] + e["hists"]):
+        found.add("a polygon channel in a point zonal spec's filter")
+    if any(h["ch"] in names for h in acc["hist"] + [h for e in pz for h in e["hists"]]):
+        found.add("a polygon channel as a histogram's value channel")
+    if any(e["label"] in [sc["name"] for sc in acc["surfaces"]] for e in pz):
+        found.add("a surface channel as the label")
+    cur_at = {i: (k, cur) for i, k, cur in poly_walk(case)}
+    finalized = fresh = False
+    counted = biggest = 0
+    since, pending, zone_kind = set(), False, {}
+    over = [False] * len(pz)
+    tables_seen = emptied_since_tables = False
+    refused_after_ingest = False
+    valid_reburn = False
+    for i, o in enumerate(ops):
+        prev = ops[i - 1] if i else None
+        if o["op"] == "ingest":
+            k, cur = cur_at[i]
+            c = case["clouds"][k]
+            n = len(c["x"])
+            if n == 0:
+                continue
+            if pending and biggest and n > biggest:
+                found.add("set_polygons before a larger cloud than any so far")
+            pending, biggest = False, max(biggest, n)
+            ch = cloud_channels(case, k, cur)
+            keep = pipeline_keep(case, ch)
+            if not keep.any():
+                since.add("emptied")
+                emptied_since_tables = emptied_since_tables or (tables_seen and counted > 0)
+                continue
+            if po["clip"] and keep.sum() < keep_mask(case["filt"], c["cls"]).sum():
+                found.add("a polygon channel in the pipeline filter")
+            counted, fresh, since = counted + 1, False, set()
+            tables_seen = emptied_since_tables = False
+            outside = cells_of(g, c["x"], c["y"]) < 0
+            chunk = max(1, int(n * o["chunk_frac"])) if o["how"] == "file" else n
+            for j, e in enumerate(pz):
+                zs = zones_of(ch[e["label"]])
+                if e["label"] in names and (keep & outside & (zs > 0)).any():
+                    found.add("a polygon channel as a point zonal label, with counted points outside the grid")
+                if e["label"] in names and chunk < n:
+                    found.add("ingest_file in more than one chunk with a polygon-labelled entry")
+                if any(s["filt"] and not (keep & conj_mask(ch, s["filt"], n)).any() for s in e["stats"] + e["hists"]):
+                    found.add("a spec filter that empties a cloud the pipeline filter keeps")
+                if (keep & (zs > e["max_zones"])).any():
+                    over[j] = True
+                inz = zs[keep & (zs > 0) & (zs <= e["max_zones"])]
+                if len(inz) and np.bincount(inz).max() > PZ_ITEM:
+                    found.add("more than 2^16 kept points in one zone")
+        elif o["op"] == "finalize":
+            finalized = fresh = True
+            since = set()
+            if refused_after_ingest:
+                found.add("polygonize refused after an ingest, and valid again after the next finalize")
+        elif o["op"] == "set_polygons":
+            pending = True
+            if prev is not None and prev["op"] == "ingest" and prev["how"].startswith("async") and not prev["sync"] and len(case["clouds"][prev["cloud"]]["x"]):
+                found.add("set_polygons behind an unsynchronised async ingest")
+        elif o["op"] == "point_tables":
+            if not any(q["op"] == "ingest" for q in ops[:i]):
+                found.add("point_tables before the first ingest")
+            if emptied_since_tables:
+                found.add("a cloud the pipeline filter empties between two point_tables")
+            tables_seen, emptied_since_tables = True, False
+        elif o["op"] == "set_zones":
+            zname = [q for q in plan["zonal"] if q["external"]][o["entry"]]["zones"]
+            if zone_kind.get(zname) == "poly":
+                found.add("a grid replacing set_zones_poly")
+            zone_kind[zname] = "grid"
+        elif o["op"] == "set_zones_poly":
+            zname = plan["zonal"][o["zonal"]]["zones"]
+            if zone_kind.get(zname) == "grid":
+                found.add("set_zones_poly replacing a grid")
+            zone_kind[zname] = "poly"
+        elif o["op"] in ("polygonize", "reburn"):
+            real = o["band"] != "nope"
+            if real and finalized and fresh:
+                if plan["loc"] == "Device":
+                    found.add("polygonize with a Device result")
+                if "emptied" in since:
+                    found.add("polygonize valid behind an emptied cloud")
+                valid_reburn = valid_reburn or o["op"] == "reburn"
+            elif real and finalized:
+                refused_after_ingest = True
+    if any(over):                                                # (the runner reads every table behind every finalize: the last op is one)
+        found.add("a point zonal overflow and a read after it")
+    if valid_reburn and reburn_crowns(case) >= 20:
+        found.add("the reburn chain with at least 20 crowns")
+    return found
+
+
+def reburn_crowns(case):
+    """The most crowns a valid reburn of the case burns: the rows of the tree table of the model's last finalize then."""
+    model, most = Model(case), 0
+    for o in case["ops"]:
+        if o["op"] == "ingest":
+            model.ingest(case["clouds"][o["cloud"]])
+        elif o["op"] == "set_polygons":
+            model.current[o["channel"]] = 1
+        elif o["op"] == "planes_write":
+            model.patch(o)
+        elif o["op"] == "finalize":
+            model.leaving_bands(case["plan"])
+        elif o["op"] == "reburn" and model.finalized is not None and model.fresh:
+            most = max(most, len(model.finalized[2][int(o["band"][1:].split("_")[0])]["row"]))
+    return most
+
+
+# The polygon cases of the suite: a greedy cover of 20000..20999 in which every entry above occurs three times, cheaper cases first
+# (tests/test_sequence_fuzz_host.py counts).  A failing seed of a soak joins it.
+POLY_SEEDS = [
+    20026,  # 2^16 + 1 kept points in one zone; the reburn chain with 20 crowns and more; polygonize with a Device result
+    20264,  # ingest_file in chunks with a polygon-labelled entry; a polygon channel in the pipeline filter; a Device result
+    20359,  # chunks with a polygon-labelled entry; polygonize refused after an ingest; a grid and a polygon set replacing each other
+    20428,  # chunks with a polygon-labelled entry; set_polygons before the largest cloud so far; a polygon predicate in a spec's filter
+    20459,  # the reburn chain; a point zonal overflow and reads after it; a spec filter that empties a cloud
+    20578,  # 2^16 + 1 kept points in one zone; point_tables before the first ingest; a polygon channel in the pipeline filter
+    20671,  # polygonize refused after an ingest and valid after the next finalize; a grid and a polygon set replacing each other
+    20690,  # a surface channel as the label; set_polygons before the largest cloud so far; polygonize with a Device result
+    20730,  # 2^16 + 1 kept points in one zone; polygonize refused after an ingest; set_zones_poly replacing a grid
+    20773,  # a grid replacing set_zones_poly; set_polygons before the largest cloud so far; polygonize with a Device result
+    20794,  # polygonize valid behind an emptied cloud; an emptied cloud between two point_tables; set_polygons behind an unwaited ingest_async
+    20820,  # an emptied cloud between two point_tables; set_polygons behind an unwaited ingest_async; an overflow
+    20876,  # the reburn chain; point_tables before the first ingest; a polygon predicate in a spec's filter
+    20890,  # set_polygons behind an unwaited ingest_async; a polygon channel in the pipeline filter and in a reduction's
+    20908,  # an emptied cloud between two point_tables; a surface channel as the label; polygonize valid behind an emptied cloud
+    20925,  # a surface channel as the label; polygonize valid behind an emptied cloud; set_zones_poly replacing a grid
+]
+
+
 # ---- the model -------------------------------------------------------------------------------------------------------------------
 class Model:
     """Per group four float32 planes (sum, count, max, min) or the MostRecent word plane of most_recent_common; one touched-tile
@@ -1492,6 +2033,13 @@ class Model:
             self.finalized = None                                # (names, bands, tree tables) of the last finalize
             self.zones = {}                                      # external label grids that were set
             self._cache = {}
+        self.poly = case.get("poly")
+        if self.poly:                                            # the current set per channel; per point zonal entry the points of every
+            self.current = [0] * len(self.poly["names"])         # ingest that counted: (label, kept, [(mask, value) per spec])
+            self.pz = [[] for _ in self.poly["pz"]]
+            self.cloud_index = {id(c): k for k, c in enumerate(case["clouds"])}
+            self.finalizes = 0
+            self.burnt = {}                                      # twin entry -> the finalize its zones were burnt from
         self.planes = []
         for gr in case["groups"]:
             if gr["select"]:
@@ -1507,6 +2055,10 @@ class Model:
         import most_recent_common as MR
         import pcr_oracle_py as O
         keep = keep_mask(self.case["filt"], c["cls"])
+        ch = None
+        if self.poly:                                            # the derived channels first: PipelineConfig::filter may name one
+            ch = cloud_channels(self.case, self.cloud_index[id(c)], tuple(self.current))
+            keep = pipeline_keep(self.case, ch)
         self.survivors += int(keep.sum())
         cell = cells_of(self.g, c["x"], c["y"])
         ok = keep & (cell >= 0)
@@ -1516,7 +2068,7 @@ class Model:
         self.touched[rows // self.g["th"], cols // self.g["tw"]] = True
         if self.acc:
             if keep.any():                                       # (a cloud the pipeline filter empties changes nothing: pipeline.h, Pipeline::zonal)
-                self._ingest_acc(c, keep)
+                self._ingest_acc(c, keep, ch)
             return
         for gr, pl in zip(self.case["groups"], self.planes):
             v = c[gr["ch"]]
@@ -1538,7 +2090,7 @@ class Model:
             np.maximum.at(pl[2], cell_ok, v[ok])
             np.minimum.at(pl[3], cell_ok, v[ok])
 
-    def _ingest_acc(self, c, keep):
+    def _ingest_acc(self, c, keep, ch=None):
         """An accumulator case's ingest: the surface channels first, then every group under its own filter AND the pipeline's
         (Max and Min skip a NaN value: fmaxf / fminf), then the accumulators by their *_common models from the same routing."""
         import cell_stats_common as CS
@@ -1548,8 +2100,12 @@ class Model:
         a, g, n = self.acc, self.g, len(c["x"])
         self.version += 1
         self.fresh = False
-        ch = surface_channels(a, c)
+        ch = surface_channels(a, c) if ch is None else ch
         cell = cells_of(g, c["x"], c["y"])
+        # a polygon case's point zonal entries: label, PipelineConfig::filter's mask and per spec its mask and value, of ALL n
+        # points -- the grid plays no part
+        for e, chunks in zip(self.poly["pz"] if self.poly else (), self.pz if self.poly else ()):
+            chunks.append((ch[e["label"]], keep, [(keep & conj_mask(ch, sp["filt"], n), ch[sp["ch"]]) for sp in e["stats"] + e["hists"]]))
         for gr, pl in zip(self.case["groups"], self.planes):
             mine = keep & conj_mask(ch, gr["filt"], n)
             v = ch[gr["ch"]]
@@ -1716,7 +2272,52 @@ class Model:
             tables.append(tab)
         if self.acc:
             self.fresh, self.finalized = True, (names, out, tables)
+        if self.poly:
+            self.finalizes += 1
         return names, out
+
+    def point_zonal_table(self, i):
+        """Pipeline::point_zonal of entry i: (table, [counts per histogram]) by point_zonal_common.table_masked on the points of
+        every ingest that counted, concatenated (the bits depend on the multiset of points only) -- or the OutOfRange message
+        once a kept point carried a zone above max_zones, whatever its value.  Points that PipelineConfig::filter drops or
+        that carry no zone add nothing to any word: they are left out of the Python-int walk."""
+        import point_zonal_common as PZC
+        e, chunks = self.poly["pz"][i], self.pz[i]
+        if self._cache.get(("pz", i), (None,))[0] != len(chunks):
+            specs = e["stats"] + e["hists"]
+            cat = lambda parts, dtype: np.concatenate(parts).astype(dtype) if parts else np.zeros(0, dtype)
+            labels, base = cat([c[0] for c in chunks], np.float32), cat([c[1] for c in chunks], bool)
+            zs = zones_of(labels)
+            over = int((base & (zs > e["max_zones"])).sum())
+            if over:
+                ans = f"{over} points of '{e['label']}' carry a zone above max_zones = {e['max_zones']}"
+            else:
+                sel = base & (zs > 0)
+                cols = [(cat([c[2][k][0] for c in chunks], bool)[sel], cat([c[2][k][1] for c in chunks], np.float32)[sel]) for k in range(len(specs))]
+                stats = [(sp["ch"], v, m, sp["origin"], sp["res"], sp["ddof"]) for sp, (m, v) in zip(e["stats"], cols)]
+                hists = [(sp["ch"], v, m, sp["lo"], sp["hi"], sp["bins"], sp["qs"]) for sp, (m, v) in zip(e["hists"], cols[len(e["stats"]):])]
+                ans = PZC.table_masked(labels[sel], e["max_zones"], None, stats=stats, hists=hists)
+            self._cache[("pz", i)] = (len(chunks), ans)
+        return self._cache[("pz", i)][1]
+
+    def outline(self, name):
+        """Pipeline::polygonize: the polygon set of polygonize_common.model on the band as the last finalize left it, under
+        zonal's condition (a finalize with no ingest since) -- or the message of the documented refusal."""
+        import polygonize_common as PG
+        if self.finalized is None or not self.fresh:
+            return f"no band '{name}' \\(of a finalize with no ingest since\\)"
+        if name not in self.finalized[0]:
+            return f"'{name}' names no Float32 band of the result"
+        band = self.finalized[1][self.finalized[0].index(name)]
+        key = ("outline", bits_key(band))
+        if key not in self._cache:
+            self._cache[key] = PG.set_of(PG.model(band), grid_geom(self.g))
+        return self._cache[key]
+
+    def burn(self, polys, background):
+        """set_zones(name, polygons): rasterize_common.model on the pipeline's grid."""
+        import rasterize_common as RC
+        return RC.model(polys, grid_geom(self.g), background)
 
     def acc_states(self):
         """What histogram(i), extremes(i) and cell_stats(i) answer: the cubes, the decoded key planes, (N, S1, S2)."""
@@ -1824,7 +2425,12 @@ def make_config(case, plan, flavour, exec_mode, engine, tmp_path, state_dir=None
             r.filter = filter_spec(s["filt"])
         reds.append(r)
     cfg.reductions = reds
-    if case["filt"]:
+    if case.get("poly"):                                         # PipelineConfig::filter: the `cls` predicate, then the clip
+        first = [dict(case["filt"], ch="cls")] if case["filt"] else []
+        if first or case["poly"]["clip"]:
+            cfg.filter = filter_spec(first + case["poly"]["clip"])
+        poly_config(pcr, cfg, case["poly"])
+    elif case["filt"]:
         f = pcr.FilterSpec()
         if case["filt"]["op"] in ("InSet", "NotInSet"):
             pr = pcr.FilterPredicate()
@@ -1913,6 +2519,32 @@ def acc_config(pcr, cfg, acc, plan):
                                  percentiles=None if z["own"] else [float(q) for q in z["qs"]], max_zones=z["max_zones"]) for z in plan["zonal"]]
 
 
+def poly_config(pcr, cfg, po):
+    """The polygon channels and the point zonal entries of a polygon case."""
+    cfg.polygon_channels = [pcr.PolygonChannelConfig(n) for n in po["names"]]
+    kinds = (pcr.CellStat.Mean, pcr.CellStat.Variance, pcr.CellStat.StdDev)
+    entries = []
+    for e in po["pz"]:
+        st, hs = [], []
+        for sp in e["stats"]:
+            c = pcr.CellStatsConfig(sp["ch"], origin=sp["origin"], resolution=sp["res"], products=[kinds[2]], ddof=sp["ddof"])
+            if sp["filt"]:
+                c.filter = filter_spec(sp["filt"])
+            st.append(c)
+        for sp in e["hists"]:
+            h = pcr.HistogramConfig(sp["ch"], sp["lo"], sp["hi"], sp["bins"], [float(q) for q in sp["qs"]])
+            if sp["filt"]:
+                h.filter = filter_spec(sp["filt"])
+            hs.append(h)
+        entries.append(pcr.PointZonalConfig(e["label"], st, hs, e["max_zones"]))
+    cfg.point_zonal = entries
+
+
+def set_polygons(p, name, st):
+    p.set_polygons(name, st["polys"].to_pcr(), background=st["opts"]["background"], index_cols=st["opts"]["index_cols"],
+                   index_rows=st["opts"]["index_rows"])
+
+
 def _cloud(c, where):
     import pcr
     n = len(c["x"])
@@ -1962,6 +2594,8 @@ def check_sequence(seed, exec_mode, engine, tmp_path):
         for sc in (case["acc"] or {}).get("surfaces", ()):       # every surface before the first ingest
             import sample_grid_common as SG
             p.set_surface(sc["name"], SG.pcr_grid(pcr, surface_of(sc)))
+        for name, sets in zip(*((case["poly"]["names"], case["poly"]["sets"]) if case["poly"] else ((), ()))):
+            set_polygons(p, name, sets[0])                       # every channel's first set before the first ingest, as create requires
         return p
 
     def refusal(call, message, what):
@@ -2009,6 +2643,45 @@ def check_sequence(seed, exec_mode, engine, tmp_path):
             for h, counts in enumerate(want[1]):
                 Z.bits_equal(p.zonal_histogram(i, h), counts, f"{at}: zonal_histogram({i}, {h})")
             refusal(lambda: p.zonal_histogram(i, len(want[1])), f"no histogram {len(want[1])} in the entry", f"{at}: zonal_histogram({i}, {len(want[1])})")
+
+    def check_point_tables(at, counts=True):
+        """point_zonal(i) and point_zonal_histogram(i, h) of every entry against the model: a table, or the OutOfRange message."""
+        import point_zonal_common as PZC
+        import zonal_common as Z
+        for i, e in enumerate(case["poly"]["pz"]):
+            want = model.point_zonal_table(i)
+            if isinstance(want, str):
+                refusal(lambda: p.point_zonal(i), want, f"{at}: point_zonal({i})")
+                if counts and e["hists"]:
+                    refusal(lambda: p.point_zonal_histogram(i, 0), want, f"{at}: point_zonal_histogram({i}, 0)")
+                continue
+            Z.same_table(p.point_zonal(i), want[0], f"{at}: point_zonal({i})")
+            for h, cnt in enumerate(want[1] if counts else []):
+                PZC.bits_equal(p.point_zonal_histogram(i, h), cnt, f"{at}: point_zonal_histogram({i}, {h})")
+
+    def check_outline(at, name):
+        import polygonize_common as PG
+        want = model.outline(name)
+        if isinstance(want, str):
+            refusal(lambda: p.polygonize(name), want, f"{at}: polygonize('{name}')")
+            return None
+        got = p.polygonize(name)
+        if want.P == 0:                                          # (no zone in the band: the empty set carries no values)
+            assert (got.num_polygons, got.num_rings, got.num_vertices) == (0, 0, 0), f"{at}: polygonize('{name}') of a band without a zone"
+            return got
+        PG.bits_equal(got, want, f"{at}: polygonize('{name}')")
+        return got
+
+    def check_twins(at):
+        """The reburn chain: where a twin's zones were burnt from the tree-id band of THIS finalize and both tables answer, the
+        twin's table is the by-band entry's, bit for bit -- engine against engine, no model between them."""
+        import zonal_common as Z
+        for i, z in enumerate(plan["zonal"]):
+            if "twin_of" in z and model.burnt.get(i) == model.finalizes and model.fresh and not isinstance(model.zonal_table(plan, i), str):
+                got, want = p.zonal(i), p.zonal(z["twin_of"])
+                Z.same_table(got, want, f"{at}: zonal({i}), burnt from polygonize('{plan['zonal'][z['twin_of']]['zones']}'), against zonal({z['twin_of']})")
+                for h in range(len(z["hists"])):
+                    Z.bits_equal(p.zonal_histogram(i, h), p.zonal_histogram(z["twin_of"], h), f"{at}: zonal_histogram({i}, {h}) against the by-band entry's")
 
     def d2h(ptr, shape, dtype=np.float32):
         out = np.empty(shape, dtype)
@@ -2101,6 +2774,32 @@ def check_sequence(seed, exec_mode, engine, tmp_path):
             if case["acc"]:
                 check_acc(at)
                 check_tables(at)
+            if case["poly"]:
+                check_point_tables(at)
+                check_twins(at)
+                for name in case["poly"]["outlines"]:
+                    check_outline(at, name)
+        elif o["op"] == "set_polygons":                          # a channel's second set, between ingests: maybe right behind an
+            set_polygons(p, case["poly"]["names"][o["channel"]], case["poly"]["sets"][o["channel"]][1])     # ingest nobody waited for
+            model.current[o["channel"]] = 1
+        elif o["op"] == "point_tables":
+            check_point_tables(at, o["counts"])
+        elif o["op"] == "set_zones_poly":                        # an external entry's labels burnt from a polygon set
+            st = case["poly"]["zone_sets"][o["poly"]]
+            zname = plan["zonal"][o["zonal"]]["zones"]
+            p.set_zones(zname, st["polys"].to_pcr(), background=st["opts"]["background"])
+            model.zones[zname] = model.burn(st["polys"], np.float32(st["opts"]["background"]))
+        elif o["op"] == "polygonize":
+            check_outline(at, o["band"])
+        elif o["op"] == "reburn":                                # the twin's zones from the crowns' outlines; refused: nothing is set
+            import polygonize_common as PG
+            got = check_outline(at, o["band"])
+            if got is not None:
+                zname = plan["zonal"][o["zonal"]]["zones"]
+                p.set_zones(zname, got)
+                model.zones[zname] = PG.burn_target(model.finalized[1][model.finalized[0].index(o["band"])])
+                model.burnt[o["zonal"]] = model.finalizes
+                check_twins(at)
         elif o["op"] == "read_acc":
             check_acc(at)
         elif o["op"] == "tables":
@@ -2113,7 +2812,9 @@ def check_sequence(seed, exec_mode, engine, tmp_path):
             model.zones[z["zones"]] = labels
         elif case["acc"] and o["op"] in ("reload", "checkpoint"):
             # checkpoints do not carry the accumulators: both calls are refused with the message of the first non-empty list,
-            # and neither the state nor the next finalize knows of the call (the model does not move)
+            # and neither the state nor the next finalize knows of the call (the model does not move).  A polygon case has
+            # point_zonal entries too: save_state and load_state of both engines ask histograms, extremes, cell_stats and only
+            # then point_zonal, and an accumulator case has one of the first three -- the pinned message stays theirs
             a = case["acc"]
             what = "histograms' cubes" if a["hist"] else "extremes' key planes" if a["ext"] else "cell stats' planes"
             refusal(lambda: (p.load_state if o["op"] == "reload" else p.save_state)(str(tmp_path / f"ck{k}")),

@@ -19,7 +19,16 @@ The accumulator cases (ACC_SEEDS; any seed from ACC_SEED_BASE on, so PCR_SEQ_FUZ
 pipeline with per-reduction filters, surface channels, histograms, extremes, cell stats, tree bands and zonal tables at once:
 the point mask across the scatters of one ingest, the scatter path per cloud, the band order and fill rules over every band
 kind, and what trees(i) / zonal(i) answer after pointers were handed out, planes written, flags merged, a checkpoint call refused
-or nothing happened -- every state, band and table bit for bit against the features' own integer models."""
+or nothing happened -- every state, band and table bit for bit against the features' own integer models.
+
+The polygon cases (POLY_SEEDS; any seed from POLY_SEED_BASE on, so PCR_SEQ_FUZZ_SEEDS=20000:20400 soaks them) put polygon
+channels, point zonal tables, polygon-burnt zone grids and polygonize on top of an accumulator case: the per-ingest staging
+buffer of a polygon channel read by the filter classes, every scatter, every accumulator and the point zonal fold on one
+stream; set_polygons between ingests, also right behind an ingest_async nobody waited for and before a larger cloud that grows
+the staging buffer; the early return for an emptied cloud, which must leave the tables as they were; points outside the grid
+that count in the tables and in no scatter; chunked ingest_file; outlines under zonal's freshness rule, with Host and Device
+results; and the round trip polygonize -> set_zones -> zonal against the by-band table.  The clouds come from host, page-locked and device
+memory and from files, as the seed draws it for every family."""
 import pytest
 
 import pcr

@@ -13,7 +13,13 @@ generator below checks it again.
 
 Accumulator cases (seeds from ACC_SEED_BASE on; ACC_SEEDS in the suite) add a float32 channel `z`, surface channels, per-reduction
 filters, histograms, extremes, cell stats, tree bands and zonal tables to what a seed draws, in core: integer states and
-bit-defined bands, so the model -- the *_common models of each feature, from the same routing -- needs no tolerance either."""
+bit-defined bands, so the model -- the *_common models of each feature, from the same routing -- needs no tolerance either.
+
+Polygon cases (seeds from POLY_SEED_BASE on; POLY_SEEDS in the suite) are the accumulator case of seed - POLY_SEED_BASE +
+ACC_SEED_BASE with polygon channels, point zonal entries, polygon-burnt zones and outlines on top: set_polygons between ingests
+(also right behind an ingest_async nobody waited for), point_zonal read anywhere, set_zones from a polygon set, polygonize under
+zonal's freshness rule, and zones burnt back from the crowns' outlines.  The models are the features' own brute-force ones
+(points_in_polygons_common, point_zonal_common, rasterize_common, polygonize_common): everything bit for bit again."""
 import json
 import os
 
@@ -27,7 +33,7 @@ import terrain_common as T
 from conftest import GOLDEN
 
 
-@pytest.mark.parametrize("seed", S.DEFAULT_SEEDS + S.LINE_SEEDS + S.ACC_SEEDS)
+@pytest.mark.parametrize("seed", S.DEFAULT_SEEDS + S.LINE_SEEDS + S.ACC_SEEDS + S.POLY_SEEDS)
 def test_sequence_on_the_host_engine_equals_the_model(seed, tmp_path):
     S.check_sequence(seed, pcr.ExecutionMode.CPU, "host", tmp_path)
 
@@ -60,7 +66,7 @@ def test_the_line_seeds_cover_the_line_situations():
     """Every situation the line cases are for occurs in at least three of LINE_SEEDS, recognised from the case alone; no seed
     of the list is idle, and what a line case is holds for each."""
     assert all(seed >= S.LINE_SEED_BASE for seed in S.LINE_SEEDS) and max(S.DEFAULT_SEEDS) < S.LINE_SEED_BASE
-    assert S.seeds_from_env("PCR_SEQ_FUZZ_NO_SUCH_VARIABLE") == S.DEFAULT_SEEDS + S.LINE_SEEDS + S.ACC_SEEDS
+    assert S.seeds_from_env("PCR_SEQ_FUZZ_NO_SUCH_VARIABLE") == S.DEFAULT_SEEDS + S.LINE_SEEDS + S.ACC_SEEDS + S.POLY_SEEDS
     seen = {name: [] for name in S.LINE_SITUATIONS}
     for seed in S.LINE_SEEDS:
         case = S.build(seed)
@@ -163,6 +169,94 @@ def test_the_accumulator_seeds_are_the_cases_they_are():
         assert np.isnan(z).any() and np.isposinf(z).any() and np.isneginf(z).any() and (z.view(np.uint32) == 0x80000000).any(), seed
         assert ((z.view(np.uint32) & 0x7F800000) == 0).sum() > (z.view(np.uint32) == 0x80000000).sum(), seed      # denormals
         assert (np.abs(z[np.isfinite(z)]) > 1e5).any(), seed                       # beyond every [lo, hi) and +-2^21 steps
+
+
+def test_the_polygon_seeds_cover_the_polygon_situations():
+    """Every situation the polygon cases are for occurs in at least three of POLY_SEEDS, recognised from the case alone; no seed
+    of the list is idle; and what a polygon case is holds for each: the accumulator case of its seed underneath, 1 to 3 polygon
+    channels of 1 or 2 sets below POLY_MAX_EDGES edges, 1 to 3 point zonal entries within create's limits, points outside the
+    grid and inside a polygon in every cloud that has points to spare, checkpoints refused."""
+    import points_in_polygons_common as PIP
+    assert all(seed >= S.POLY_SEED_BASE for seed in S.POLY_SEEDS) and max(S.ACC_SEEDS) < S.POLY_SEED_BASE
+    assert 12 <= len(S.POLY_SEEDS) <= 24 and len(set(S.POLY_SEEDS)) == len(S.POLY_SEEDS)
+    seen = {name: [] for name in S.POLY_SITUATIONS}
+    op_kinds, label_kinds, set_kinds = set(), set(), set()
+    for seed in S.POLY_SEEDS:
+        case = S.build(seed)
+        base = S.build(seed - S.POLY_SEED_BASE + S.ACC_SEED_BASE)
+        po, acc, plan, g = case["poly"], case["acc"], case["plan"], case["grid"]
+        assert po is not None and acc is not None and not case["line"] and not case["flavour"]["ooc"] and case["ops"][-1]["op"] == "finalize", seed
+        # the accumulator case underneath: the grid, the plan's drawn parts, the ops it had in their order, the specs it had
+        assert case["grid"] == base["grid"] and case["fwfi"] == base["fwfi"] and case["path"] == base["path"] and case["filt"] == base["filt"], seed
+        new_ops = ("set_polygons", "point_tables", "set_zones_poly", "polygonize", "reburn")
+        strip = lambda o: {k: v for k, v in o.items() if k not in ("group", "sync")}
+        assert [strip(o) for o in case["ops"] if o["op"] not in new_ops] == [strip(o) for o in base["ops"]], seed
+        assert [(s["type"], s["ch"]) for s in case["specs"][:len(base["specs"])]] == [(s["type"], s["ch"]) for s in base["specs"]], seed
+        assert plan["terrain"] == base["plan"]["terrain"] and plan["trees"] == base["plan"]["trees"], seed
+        assert 1 <= len(po["names"]) <= 3 and po["names"] == list(S.POLY_NAMES[:len(po["names"])]), seed
+        for sets in po["sets"]:
+            assert 1 <= len(sets) <= 2, seed
+            for st in sets + po["zone_sets"]:
+                assert len(st["polys"].coords) <= S.POLY_MAX_EDGES and st["polys"].P >= 1, seed
+                assert (st["opts"]["index_cols"], st["opts"]["index_rows"]) in PIP.INDEX_SIZES, seed
+                set_kinds.update(st["opts"]["kinds"])
+        assert all(st["opts"]["rect"] is not None for st in po["sets"][0]), seed
+        assert 1 <= len(po["pz"]) <= 3 and len(acc["hist"]) <= 4 and len(plan["zonal"]) <= 4, seed
+        for e in po["pz"]:
+            assert e["max_zones"] in S.PZ_MAX_ZONES and 1 <= len(e["stats"]) + len(e["hists"]) <= 4, seed
+            assert len({s["ch"] for s in e["stats"]}) == len(e["stats"]) and len({h["ch"] for h in e["hists"]}) == len(e["hists"]), seed
+            assert all((s["origin"], s["res"]) in S.STAT_STEPS for s in e["stats"]), seed
+            assert all((h["lo"], h["hi"]) in S.HIST_RANGES and h["bins"] in S.HIST_BINS for h in e["hists"]), seed
+            label_kinds.add("polygon" if e["label"] in po["names"] else "surface" if e["label"] in [sc["name"] for sc in acc["surfaces"]] else e["label"])
+        filters = {S.filter_key(e["filt"]) for e in S.acc_entries(acc) + case["specs"] + [s for e in po["pz"] for s in e["stats"] + e["hists"]]
+                   if e["filt"]}
+        assert len(filters) <= 8 and sum(len(f) for f in filters) + (1 if case["filt"] else 0) + len(po["clip"]) <= 32, seed
+        assert all(s["ch"] in ("a", "b") for s in case["specs"] if s["type"] in ("Sum", "Average", "WeightedAverage")), seed
+        assert sum(len(c["x"]) for c in case["clouds"]) < 1 << 22, seed
+        assert S.point_units(g, case["clouds"]).max() + S.PATCH_UNITS * sum(o["op"] == "planes_write" for o in case["ops"]) < 1 << 24, seed
+        for i, k, cur in S.poly_walk(case):
+            c = case["clouds"][k]
+            assert ("lab" in c) == any(e["label"] == "lab" for e in po["pz"]) and S.cloud_keys(c)[:7] == S.CLOUD_KEYS + S.ACC_CLOUD_KEYS, seed
+            if len(c["x"]) >= 2000 and c["shape"] != "pipeline_emptied":     # a share outside the grid and inside a polygon
+                ch = S.poly_channels(case, k, cur)
+                out = S.cells_of(g, c["x"], c["y"]) < 0
+                assert any((out & (S.zones_of(v) > 0)).any() or (out & (v != np.float32(st[j]["opts"]["background"])) & ~np.isnan(v)).any()
+                           for (name, v), st, j in zip(ch.items(), po["sets"], cur)), (seed, k)
+        assert all(o["plan"] is None and o["flavour"] is None for o in case["ops"] if o["op"] == "checkpoint"), seed
+        op_kinds.update(o["op"] for o in case["ops"])
+        found = S.situations(case)
+        assert found <= set(S.POLY_SITUATIONS)
+        for name in found:
+            seen[name].append(seed)
+    for name in S.POLY_SITUATIONS:
+        assert len(seen[name]) >= 3, f"'{name}' occurs in seeds {seen[name]} only"
+    for seed in S.POLY_SEEDS:                                     # no seed of the list is idle
+        rest = [s for s in S.POLY_SEEDS if s != seed]
+        assert any(sum(s in seen[name] for s in rest) < 3 for name in S.POLY_SITUATIONS), f"seed {seed} adds nothing"
+    assert {"set_polygons", "point_tables", "set_zones_poly", "polygonize", "reburn", "checkpoint"} <= op_kinds, op_kinds
+    assert {"polygon", "surface", "cls", "lab"} <= label_kinds, label_kinds
+    assert {"partition", "donut", "ngons", "rect"} <= set_kinds and any(k.startswith("degenerate") for k in set_kinds), set_kinds
+
+
+def test_the_polygon_seeds_are_the_cases_they_are():
+    """POLY_SEEDS are pinned under a key of their own: the digest of a polygon case covers the polygon sets (vertex bits) and
+    their options, the uses, the point zonal entries, the inserted ops and the `lab` arrays.  Two builds are one case."""
+    with open(os.path.join(GOLDEN, "sequence_fuzz_cases.json")) as f:
+        want = json.load(f)["sha256_poly"]
+    assert sorted(int(s) for s in want) == sorted(S.POLY_SEEDS)
+    for seed in S.POLY_SEEDS:
+        a, b = S.build(seed), S.build(seed)
+        assert S.case_digest(a) == S.case_digest(b) == want[str(seed)], f"polygon seed {seed} is another case than it was"
+    # the digest sees a vertex, an option, an entry and a label
+    a = S.build(S.POLY_SEEDS[0])
+    d0 = S.case_digest(a)
+    a["poly"]["sets"][0][0]["polys"].coords[0, 0] = np.nextafter(a["poly"]["sets"][0][0]["polys"].coords[0, 0], np.inf)
+    d1 = S.case_digest(a)
+    a["poly"]["sets"][0][0]["opts"]["index_cols"] += 1
+    d2 = S.case_digest(a)
+    a["poly"]["pz"][0]["max_zones"] += 1
+    d3 = S.case_digest(a)
+    assert len({d0, d1, d2, d3}) == 4
 
 
 def test_the_terrain_draw():
